@@ -45,6 +45,8 @@ FLOP_PER_SIGNAL = 2 * sum(a * b for a, b in zip(DIMS[:-1], DIMS[1:]))  # 860,288
 BYTES_PER_SIGNAL = 4 * (DIMS[0] + DIMS[-1])                            # 1,832
 PEAK_TFLOPS = {"f16": 2500.0, "bf16": 2500.0, "f32": 157.3}            # dense MFMA, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
+# --dump-outputs: rows of the timed step's output written out, at most (32,768 x 451 float32 = 59 MB)
+DUMP_ROWS = 32768
 
 
 def glorot(dims, seed):
@@ -722,6 +724,19 @@ def _reduce_clock_stamps(st, ms_per_launch_events):
     }
 
 
+def dump_outputs(directory, y):
+    """The emulated signals of the timed path's last step (B x 451 float32, as predict returns them) as
+    DIR/signals.npy: every row if they fit in DUMP_ROWS, else the same seeded sample of DUMP_ROWS rows every run, in
+    row order (DIR/signal_rows.npy: their row numbers, float64)."""
+    os.makedirs(directory, exist_ok=True)
+    rows = np.arange(len(y))
+    if len(y) > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(len(y), DUMP_ROWS, replace=False))
+    np.save(os.path.join(directory, "signals.npy"), np.ascontiguousarray(y[rows], np.float32))
+    np.save(os.path.join(directory, "signal_rows.npy"), rows.astype(np.float64))
+    return {"dir": directory, "signals": [len(rows), y.shape[1]], "rows_of": len(y)}
+
+
 def _claim_stdout():
     """Point file descriptor 1 at stderr (whatever C++ libraries print -- `[Gloo] Rank ...`, c10d warnings -- goes
     there) and return a text stream on a duplicate of the ORIGINAL stdout for the one JSON line."""
@@ -749,7 +764,11 @@ def main():
     ap.add_argument("--train-batch", type=int, default=4096)
     ap.add_argument("--train-steps", type=int, default=200,
                     help="timed optimizer steps of the training legs (40 until r3: the one host sync at the end was ~1 us per step of a 45-us step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (rank 0; a seeded sample of %d rows)" % DUMP_ROWS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -828,6 +847,11 @@ def main():
         sync_all(); barrier(); sync_all()
         wall = time.perf_counter() - t0
         ev_ms = ctx.elapsed_ms(e0, e1)
+        # what the last timed step left in d_y, copied after the timed region (--dump-outputs)
+        timed.output = None
+        if args.dump_outputs and rank == 0:
+            timed.output = np.empty((B, DIMS[-1]), np.float32)
+            ctx.d2h(timed.output, d_y)
         # per-launch durations of a second, untimed run of the same K launches (an event pair around every launch
         # costs a few us of host time per step, so it stays out of the timed region): min / median beside the mean
         evs = [ctx.event() for _ in range(steps + 1)]
@@ -877,6 +901,10 @@ def main():
         return wall, ev_ms
 
     wall, ev_ms = timed(args.precision, args.steps, args.warmup)
+    dumped = None
+    if timed.output is not None:
+        dumped = dump_outputs(args.dump_outputs, timed.output)
+        timed.output = None
     value = world * B * args.steps / wall
     kern_s = ev_ms * 1e-3 / args.steps  # average launch duration on the launch stream (HIP events)
     achieved_tf = FLOP_PER_SIGNAL * B / kern_s / 1e12
@@ -895,6 +923,7 @@ def main():
         "vs_baseline": None,
         "dtype": {"f16": "f16 (f32 accumulate)", "bf16": "bf16 (f32 accumulate)", "f32": "f32"}[args.precision],
         "data": "synthetic",
+        "outputs_dumped": dumped,
         "config": {"workload": "configs[1]: direct emulator 7->[352,352,352,224]->451 batched predict, "
                                "batch=%d per GPU, device-resident in/out, fused par_transform+unpreproc" % B,
                    "batch_per_gpu": B, "weights": "Glorot-uniform seed 3", "parallelism": "rows sharded, no collective"},

@@ -41,6 +41,18 @@ def tag_of(k):
         "" if k["kind"] == "direct" else "latent %d enc %s dec %s" % (k["lat"], k["enc"], k["dec"]))
 
 
+def settle_jit(em, kind, prec):
+    """Wait for the run-time instantiated kernel of the stack `em.predict` runs on (a stack outside csrc/archs.h): it is
+    compiled in the background from the first call on, and predict takes it once it is ready -- a bitwise comparison of two
+    predictions must not straddle that switch of route (the f16 kernels round differently from the fallback's)."""
+    nat = importlib.import_module("21cmvae_amd._native")
+    model = em.emulator if kind == "direct" else em._predict_chain()
+    try:
+        model._ensure_stack().jit(prec)
+    except nat.EngineError:
+        pass  # no run-time kernel for this stack: its route does not change
+
+
 def run_case(k):
     """-> ("OK" | "BAD" | "refused", message)"""
     emu = importlib.import_module("21cmvae_amd.emulator")
@@ -76,6 +88,7 @@ def run_case(k):
         if not (np.isfinite(loss).all() and np.isfinite(val).all()):
             why.append("loss not finite")
         # predictions against the float64 oracle on the weights the object reports
+        settle_jit(em, kind, prec)
         p32 = np.atleast_2d(em.predict(q32)); p64 = np.atleast_2d(em.predict(q32.astype(np.float64)))
         if kind == "direct":
             chain = [(em.emulator.get_weights(), [1] * len(hid) + [0])]
@@ -105,6 +118,7 @@ def run_case(k):
                 em.emulator.save(os.path.join(d, "e.h5")); em.autoencoder.encoder.save(os.path.join(d, "enc.h5")); em.autoencoder.decoder.save(os.path.join(d, "dec.h5"))
                 em2 = emu.AutoEncoderEmulator(par[0], par[1], par[2], sig[0], sig[1], sig[2], precision=prec)
                 em2.load_model(os.path.join(d, "e.h5"), os.path.join(d, "enc.h5"), os.path.join(d, "dec.h5"))
+            settle_jit(em2, kind, prec)
             again = np.atleast_2d(em2.predict(q32))
             if not np.array_equal(again, p32):
                 why.append("predictions after save -> load differ by %.3g" % float(np.abs(again - p32).max()))

@@ -8,6 +8,7 @@ import subprocess
 import sys
 import types
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -66,3 +67,35 @@ def test_main_self_launches_when_no_launcher_is_in_the_environment(monkeypatch):
     with pytest.raises(SystemExit):
         bench.main()
     assert called == {"n": 4, "argv": ["--gpus", "4", "--steps", "3"]}
+
+
+def test_dump_outputs_writes_the_same_bounded_sample_every_run(tmp_path):
+    """--dump-outputs: the timed step's output as float32 .npy (a seeded row sample when it is larger than DUMP_ROWS, with the
+    row numbers beside it), the same rows on every run, at most 64 MB in all."""
+    bench = _bench()
+    y = np.random.default_rng(5).normal(size=(bench.BATCH, bench.DIMS[-1])).astype(np.float32)
+    a, b = tmp_path / "a", tmp_path / "b"
+    info = bench.dump_outputs(str(a), y)
+    bench.dump_outputs(str(b), y)
+    files = sorted(os.listdir(a))
+    assert files == ["signal_rows.npy", "signals.npy"] and info["signals"] == [bench.DUMP_ROWS, bench.DIMS[-1]]
+    assert sum(os.path.getsize(a / f) for f in files) <= 64 << 20
+    s, rows = np.load(a / "signals.npy"), np.load(a / "signal_rows.npy")
+    assert s.dtype == np.float32 and rows.dtype == np.float64 and s.shape == (bench.DUMP_ROWS, bench.DIMS[-1])
+    assert np.all(np.diff(rows) > 0) and rows[-1] < len(y)
+    np.testing.assert_array_equal(s, y[rows.astype(np.int64)])
+    for f in files:
+        np.testing.assert_array_equal(np.load(a / f), np.load(b / f))
+    # an output that fits is written whole
+    small = y[:100]
+    bench.dump_outputs(str(tmp_path / "c"), small)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "signals.npy"), small)
+
+
+def test_steps_must_be_positive(monkeypatch):
+    bench = _bench()
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
