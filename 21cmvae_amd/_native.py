@@ -106,6 +106,13 @@ SIGNATURES = {
                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "v21_trainer_jit": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "v21_mlp_last_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "v21_mlp_jacobian": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, _F, C.c_int, C.c_int]),
+    "v21_mlp_jacobian_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_int]),
+    "v21_mlp_set_likelihood": (C.c_int, [_P, _F, _F, C.c_int32]),
+    "v21_mlp_loglike": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, _F, C.c_int, C.c_int]),
+    "v21_mlp_loglike_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int]),
+    "v21_route_jacobian": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
+    "v21_mlp_last_jac_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "v21_trainer_last_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "v21_route_name": (C.c_char_p, [C.c_int, C.c_int]),
     "v21_trainer_get_data_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
@@ -152,6 +159,18 @@ def route_forward(dims, act, precision, n, flags=0, rt_ready=False):
     check(load_library().v21_route_forward(L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act]),
                                            precision_id(precision), int(n), int(flags), 1 if rt_ready else 0, C.byref(r)))
     return FWD_ROUTES[r.value]
+
+
+JAC_ROUTES = {1: "fused", 2: "generic"}
+
+
+def route_jacobian(dims, act, precision, n, flags=0):
+    """The route v21_mlp_jacobian / v21_mlp_loglike take for this stack (pure host logic: no GPU).  -> name of JAC_ROUTES."""
+    L = len(act)
+    r = C.c_int(0)
+    check(load_library().v21_route_jacobian(L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act]),
+                                            precision_id(precision), int(n), int(flags), C.byref(r)))
+    return JAC_ROUTES[r.value]
 
 
 def route_train(dims, act, precision, max_batch, rows, nranks=1, rt_ready=False):
@@ -541,6 +560,64 @@ class Stack(_Owned):
             check(self.lib.v21_mlp_forward(self.h, x.ctypes.data_as(_P), dt, x.shape[0], _fptr(y),
                                            precision_id(precision), flags))
         return y
+
+    def _rows(self, x):
+        x = np.asarray(x)
+        if x.dtype != np.float64:
+            x = x.astype(np.float32, copy=False)
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2 or x.shape[1] != self.dims[0]:
+            raise ValueError("expected input of shape (n, %d), got %r" % (self.dims[0], x.shape))
+        return x, (1 if x.dtype == np.float64 else 0)
+
+    def jacobian(self, x, precision="f32", flags=0, return_outputs=False):
+        """host (n, in) float32/float64 -> jac (n, in, out) float32: jac[n, j, k] = d out[n, k] / d x[n, j] (include/v21.h:
+        v21_mlp_jacobian; flags as for forward).  return_outputs: (y, jac) with y the forward's (n, out)."""
+        x, dt = self._rows(x)
+        n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
+        jac = np.empty((n, din, dout), np.float32)
+        y = np.empty((n, dout), np.float32) if return_outputs else None
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_jacobian(self.h, x.ctypes.data_as(_P), dt, n, _fptr(y) if y is not None else None, _fptr(jac),
+                                            precision_id(precision), flags))
+        return (y, jac) if return_outputs else jac
+
+    def set_likelihood(self, data, inv_var):
+        """Gaussian likelihood record: data d and inverse variances 1 / sigma^2 per output bin (copied; None clears)."""
+        if data is None:
+            check(self.lib.v21_mlp_set_likelihood(self.h, None, None, 0))
+            return
+        d = np.ascontiguousarray(data, dtype=np.float32).ravel()
+        w = np.ascontiguousarray(inv_var, dtype=np.float32).ravel()
+        if d.size != self.dims[-1] or w.size != self.dims[-1]:
+            raise ValueError("likelihood: expected %d bins, got %d / %d" % (self.dims[-1], d.size, w.size))
+        check(self.lib.v21_mlp_set_likelihood(self.h, _fptr(d), _fptr(w), d.size))
+
+    def loglike(self, x, precision="f32", flags=0, grad=True):
+        """host (n, in) -> lnl (n,) [, grad (n, in)]: ln L = -1/2 sum w (d - out)^2 of the record set_likelihood left."""
+        x, dt = self._rows(x)
+        n = x.shape[0]
+        lnl = np.empty(n, np.float32)
+        g = np.empty((n, self.dims[0]), np.float32) if grad else None
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_loglike(self.h, x.ctypes.data_as(_P), dt, n, _fptr(lnl), _fptr(g) if g is not None else None,
+                                           precision_id(precision), flags))
+        return (lnl, g) if grad else lnl
+
+    def jacobian_dev(self, d_x, ldx, n, d_y, ldy, d_jac, precision="f32", flags=0):
+        check(self.lib.v21_mlp_jacobian_dev(self.h, _P(d_x), ldx, n, _P(d_y) if d_y else None, ldy, _P(d_jac),
+                                            precision_id(precision), flags))
+
+    def loglike_dev(self, d_x, ldx, n, d_lnl, d_grad, precision="f32", flags=0):
+        check(self.lib.v21_mlp_loglike_dev(self.h, _P(d_x), ldx, n, _P(d_lnl), _P(d_grad) if d_grad else None,
+                                           precision_id(precision), flags))
+
+    def last_jac_route(self):
+        """(route name of the last Jacobian / log-likelihood call, {route name: calls since creation})."""
+        r = C.c_int(0)
+        cnt = (C.c_longlong * 4)()
+        check(self.lib.v21_mlp_last_jac_route(self.h, C.byref(r), cnt))
+        return JAC_ROUTES.get(r.value, "none"), {JAC_ROUTES[i]: int(cnt[i]) for i in JAC_ROUTES if cnt[i]}
 
     def forward_clocked(self, d_x, ldx, n, d_y, ldy, d_stamps, precision="f16", flags=0):
         """forward_dev through the clock-stamped instantiation of the headline stack's kernel (include/v21.h:

@@ -146,6 +146,8 @@ extern "C" int v21_mlp_destroy(v21_mlp* m) {
   if (m->d_xs) hipFree(m->d_xs);
   if (m->d_xs64) hipFree(m->d_xs64);
   if (m->d_ys) hipFree(m->d_ys);
+  for (float* p : {m->d_lk_data, m->d_lk_w, m->d_lk_ws, m->d_jxt, m->d_jfac, m->d_jy, m->d_jout}) if (p) hipFree(p);
+  if (m->d_jx64) hipFree(m->d_jx64);
   delete m;
   return V21_OK;
 }
@@ -242,6 +244,12 @@ static int ensure_stream(v21_mlp* m, int prec) {
   hipLaunchKernelGGL(pack_stream_kernel, dim3((padded + 3) / 4), dim3(256), 0, m->ctx->stream, pa);
   HIPCHK(hipGetLastError());
   m->stream_ok[prec] = true;
+  return V21_OK;
+}
+
+int mlp_fused_stream(v21_mlp* m, int prec, const unsigned char** stream) {
+  CHK(ensure_stream(m, prec));
+  *stream = m->d_stream[prec];
   return V21_OK;
 }
 

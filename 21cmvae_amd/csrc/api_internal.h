@@ -145,7 +145,20 @@ struct v21_mlp {
   unsigned long long* clk_stamps = nullptr;  // set for the duration of v21_debug_forward_clocked
   // width of layer l's Dense output: dims[l+1], or 2*dims[l+1] = [z_mean | z_log_var] for V21_ACT_GAUSS
   int nw(int l) const { return act[l] == V21_ACT_GAUSS ? 2 * dims[l + 1] : dims[l + 1]; }
+  // parameter Jacobian / log-likelihood (api_jacobian.hip): the likelihood record (d, 1 / sigma^2; out_dim floats
+  // each), staging, and the route of the last call (routes.h: JacRoute)
+  float *d_lk_data = nullptr, *d_lk_w = nullptr;
+  float* d_lk_ws = nullptr;  // the fused route's likelihood: y and jac of one slice before they are reduced
+  long long lk_ws_rows = 0;
+  bool has_lk = false;
+  float *d_jxt = nullptr, *d_jfac = nullptr, *d_jy = nullptr, *d_jout = nullptr;
+  double* d_jx64 = nullptr;
+  long long jstage_rows = 0, jhost_rows = 0;  // rows of d_jxt / d_jfac; of d_jx64 / d_jy / d_jout (host API chunks)
+  int last_jac_route = 0;
+  long long jac_route_count[4] = {0, 0, 0, 0};
 };
+// api_forward.hip: fused_fwd's packed weight stream of this stack (built on first use)
+int mlp_fused_stream(v21_mlp* m, int prec, const unsigned char** stream);
 
 // ---- trainer (api_trainer.hip)
 struct v21_trainer {

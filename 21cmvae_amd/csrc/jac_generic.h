@@ -1,0 +1,190 @@
+// jac_generic.h -- the parameter Jacobian's kernels outside the fused route (api_jacobian.hip):
+//   jac_prep_kernel     the input transform of every route (par_transform.h, the forward's own functions: the primal
+//                       sees the bits the forward's prologue computes) and its chain-rule factor per (row, column);
+//   jac_loglike_kernel  ln L and its gradient from y and the Jacobian on the device (the fused route's likelihood mode:
+//                       8 floats per row leave the device instead of 1 + in_dim rows of out_dim);
+//   jac_generic_kernel  primal + tangents of ANY stack (any hidden_dims and in_dim, > 512 wide, V21_ACT_GAUSS heads
+//                       evaluated as z = z_mean like the deterministic forward) in f32 arithmetic.  One workgroup per
+//                       (row, group of up to 7 tangents); the G columns of a layer's activation live in LDS, every
+//                       output unit is one thread's k-ordered fmaf chain per column.  Correct, not fast: every
+//                       workgroup streams the whole weight set through L2.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "par_transform.h"
+
+namespace v21 {
+
+// d par_transform / dx at the floored value t: 2 / span, times 1 / (t ln 10) for a log column (float64, rounded once)
+__device__ __forceinline__ float par_transform_grad(double t, int lm, double span) {
+  double d = 2.0 / span;
+  if (lm) d /= t * 2.302585092994045684;
+  return (float)d;
+}
+
+// one thread per (row, column): xt = the transformed f32 parameter (or the plain value), fac = its derivative (1)
+template <class SRC>
+__global__ void jac_prep_kernel(float* __restrict__ xt, float* __restrict__ fac, const SRC* __restrict__ src, long long lds_,
+                                long long n, int din, int tin_on, const v21_affine_in t) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * din) return;
+  const long long row = i / din;
+  const int j = (int)(i % din);
+  const SRC x = src[row * lds_ + j];
+  if (!tin_on) {
+    xt[i] = (float)x;
+    fac[i] = 1.f;
+    return;
+  }
+  if constexpr (sizeof(SRC) == 8) {
+    xt[i] = par_transform_f64(x, t.log_mask[j], t.zero_floor[j], t.lo[j], t.span[j]);
+    const double tf = (t.zero_floor[j] > 0.0 && x == 0.0) ? t.zero_floor[j] : (double)x;
+    fac[i] = par_transform_grad(tf, t.log_mask[j], t.span[j]);
+  } else {
+    xt[i] = par_transform_f32(x, t.log_mask[j], t.zero_floor[j], t.lo[j], t.span[j]);
+    const float tf = (t.zero_floor[j] > 0.0 && x == 0.f) ? (float)t.zero_floor[j] : x;
+    fac[i] = par_transform_grad((double)tf, t.log_mask[j], t.span[j]);
+  }
+}
+
+// one wave per row (block 256 = 4 rows, grid ceil(n_rows / 4)): lnl[n] = -1/2 sum_k w_k (d_k - y_k)^2,
+// grad[n, j] = sum_k w_k (d_k - y_k) jac[n, j, k]; bins with w == 0 are skipped (whatever d holds there).  Lanes walk the
+// bins (coalesced rows of jac), the sums are reduced across the wave by shuffles: no LDS, no barrier.
+constexpr int kJacMaxIn = 15;
+__global__ void __launch_bounds__(256) jac_loglike_kernel(const float* __restrict__ y, const float* __restrict__ jac,
+                                                          const float* __restrict__ data, const float* __restrict__ wv,
+                                                          float* __restrict__ lnl, float* __restrict__ grad, long long n_rows,
+                                                          int din, int dout) {
+  const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (n >= n_rows) return;  // (whole waves: the shuffles below run with every lane of a live wave)
+  float lp = 0.f, gp[kJacMaxIn] = {};
+  for (int k = lane; k < dout; k += 64) {
+    const float w = wv[k];
+    if (w == 0.f) continue;
+    const float r = data[k] - y[n * dout + k], wr = w * r;
+    lp += wr * r;
+#pragma unroll
+    for (int j = 0; j < kJacMaxIn; ++j)
+      if (j < din) gp[j] += wr * jac[(n * din + j) * dout + k];
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    lp += __shfl_xor(lp, o);
+#pragma unroll
+    for (int j = 0; j < kJacMaxIn; ++j)
+      if (j < din) gp[j] += __shfl_xor(gp[j], o);
+  }
+  if (lane == 0) {
+    lnl[n] = -0.5f * lp;
+    if (grad)
+#pragma unroll
+      for (int j = 0; j < kJacMaxIn; ++j)
+        if (j < din) grad[n * din + j] = gp[j];
+  }
+}
+
+constexpr int kJacGenCols = 8;  // primal + up to 7 tangents per workgroup
+struct JacGenArgs {
+  int L, in_dim, tc, maxw;      // tc: tangents per workgroup (<= kJacGenCols - 1); maxw: LDS row pitch
+  int dims[17], act[16], nw[16];
+  long long w_off[16], b_off[16];
+  const float* w;               // the stack's parameter arena
+  const float* xt;              // (n, in_dim) transformed rows
+  const float* fac;             // (n, in_dim)
+  long long n_rows;
+  float* y; long long ldy;      // nullable
+  float* jac;                   // (n, in_dim, out) -- Jacobian mode
+  float* lnl; float* grad;      // likelihood mode (grad nullable)
+  const float* data; const float* wv;
+  int like;
+  float out_std;
+  const float* mean;            // nullable: no output transform
+};
+
+// grid (n_rows, ceil(in_dim / tc)); block 256; dynamic LDS 2 * (tc + 1) * maxw floats
+__global__ void __launch_bounds__(256) jac_generic_kernel(const JacGenArgs a) {
+  extern __shared__ float jsh[];
+  const long long n = blockIdx.x;
+  const int t0 = blockIdx.y * a.tc;
+  const int C = 1 + min(a.tc, a.in_dim - t0);  // columns: primal + tangents t0 .. t0 + C - 2
+  float* buf[2] = {jsh, jsh + (size_t)(a.tc + 1) * a.maxw};
+  for (int i = threadIdx.x; i < C * a.in_dim; i += blockDim.x) {
+    const int c = i / a.in_dim, k = i % a.in_dim;
+    buf[0][c * a.maxw + k] = c == 0 ? a.xt[n * a.in_dim + k] : (k == t0 + c - 1 ? 1.f : 0.f);
+  }
+  __syncthreads();
+  float lp = 0.f, gp[kJacGenCols] = {};
+  int cur = 0;
+  for (int l = 0; l < a.L; ++l) {
+    const int K = a.dims[l], N = a.dims[l + 1], nw = a.nw[l];
+    const float* W = a.w + a.w_off[l];  // V21_ACT_GAUSS: the z_mean columns only (z = z_mean)
+    const float* b = a.w + a.b_off[l];
+    const float* in = buf[cur];
+    float* out = buf[cur ^ 1];
+    const bool last = l == a.L - 1;
+    for (int o = threadIdx.x; o < N; o += blockDim.x) {
+      float s[kJacGenCols];
+      s[0] = b[o];
+#pragma unroll
+      for (int c = 1; c < kJacGenCols; ++c) s[c] = 0.f;
+      for (int k = 0; k < K; ++k) {
+        const float wk = W[(long long)k * nw + o];
+#pragma unroll
+        for (int c = 0; c < kJacGenCols; ++c)
+          if (c < C) s[c] = __builtin_fmaf(in[c * a.maxw + k], wk, s[c]);
+      }
+      // ReLU on every layer that has it, the output layer included (a stack may end in one: the engine's Dense and
+      // the forward routes accept it); the primal's z > 0 masks primal and tangents together
+      if (a.act[l] == V21_ACT_RELU && !(s[0] > 0.f)) {
+#pragma unroll
+        for (int c = 0; c < kJacGenCols; ++c) s[c] = 0.f;
+      }
+      if (!last) {
+#pragma unroll
+        for (int c = 0; c < kJacGenCols; ++c)
+          if (c < C) out[c * a.maxw + o] = s[c];
+        continue;
+      }
+      const float yv = a.mean ? s[0] * a.out_std + a.mean[o] : s[0];
+      if (!a.like) {
+        if (a.y && blockIdx.y == 0) a.y[n * a.ldy + o] = yv;
+#pragma unroll
+        for (int c = 1; c < kJacGenCols; ++c)
+          if (c < C) {
+            const int j = t0 + c - 1;
+            a.jac[(n * a.in_dim + j) * N + o] = s[c] * a.out_std * a.fac[n * a.in_dim + j];
+          }
+      } else if (a.wv[o] != 0.f) {
+        const float r = a.data[o] - yv, wr = a.wv[o] * r;
+        lp += wr * r;
+#pragma unroll
+        for (int c = 1; c < kJacGenCols; ++c)
+          if (c < C) gp[c] += wr * (s[c] * a.out_std);
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (!a.like) return;
+  // block sums of lp and gp[1 ..] (the activation buffers are free now)
+  float* red = jsh;
+  for (int c = 0; c < C; ++c) {
+    red[threadIdx.x] = c == 0 ? lp : gp[c];
+    __syncthreads();
+    for (int st = blockDim.x / 2; st > 0; st >>= 1) {
+      if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      if (c == 0) { if (blockIdx.y == 0) a.lnl[n] = -0.5f * red[0]; }
+      else if (a.grad) {
+        const int j = t0 + c - 1;
+        a.grad[n * a.in_dim + j] = red[0] * a.fac[n * a.in_dim + j];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace v21

@@ -210,4 +210,17 @@ inline int decide_forward(const FwdQuery& q) {
   return FWD_GENERIC;
 }
 
+// ---- parameter Jacobian and Gaussian log-likelihood (v21_mlp_jacobian[_dev], v21_mlp_loglike[_dev]).  Its own enum:
+// the forward's routes and their table are untouched.  ldy: the row pitch of y (fused_jac
+// addresses a workgroup's rows with 32-bit offsets, as fused_fwd does).
+enum JacRoute {
+  JAC_NONE = 0,
+  JAC_FUSED = 1,    // fused_jac<Arch, Prec> compiled into the library (archs.h S1-S4; fused_jac.h)
+  JAC_GENERIC = 2,  // any other stack, any in_dim, variational stacks: jac_generic_kernel (jac_generic.h), f32 arithmetic
+};
+inline int decide_jacobian(bool fused_compiled, int in_dim, int flags, long long ldy) {
+  const bool fused = fused_compiled && in_dim <= 15 && !(flags & V21_FWD_FORCE_GENERIC) && ldy < (1ll << 21);
+  return fused ? JAC_FUSED : JAC_GENERIC;
+}
+
 }  // namespace v21

@@ -207,6 +207,72 @@ class _EmulatorBase:
         pred = model.predict(x, devices=devices, flags=flags)
         return pred[0, :] if pred.shape[0] == 1 else pred
 
+    def _diff_stack(self, params):
+        """(stack, flags, rows) of the model ``predict`` evaluates, with both transforms set, for the derivatives below:
+        float32 / float64 rows are handed over raw (the library differentiates par_transform for their dtype), any
+        other dtype is cast to float64 first."""
+        from . import _native as nat
+        model = self._predict_chain() if hasattr(self, "_predict_chain") else self.emulator
+        x = np.asarray(params)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)
+        st = model._ensure_stack()
+        ss = pp.SignalStats.of(self.signal_train)
+        if getattr(st, "_out_stats", None) is not ss:
+            st.set_output_transform(ss.std, ss.mean)
+            st._out_stats = ss
+        ps = pp.ParamStats.of(self.par_train)
+        if getattr(st, "_in_stats", None) is not ps:
+            st.set_input_transform(ps.log_mask, ps.zero_floor, ps.lo, ps.hi)
+            st._in_stats = ps
+        return model, st, nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM, x
+
+    def jacobian(self, params, return_signal=False):
+        """d signal / d params in mK per raw parameter unit (not in the reference: there, tf.GradientTape around
+        ``emulator.emulator``): (451, 7) for one parameter vector, (N, 451, 7) for an (N, 7) array; the log10 columns
+        are differentiated at the value after the fx zero floor.  return_signal: (signal, jacobian), the signal being
+        what ``predict`` returns (bit for bit where ``predict`` takes the fused kernel: 16-bit precisions, or more than
+        4,096 rows)."""
+        model, st, flags, x = self._diff_stack(params)
+        y, jac = st.jacobian(x, model.precision, flags, return_outputs=True)
+        J = jac.transpose(0, 2, 1)
+        if x.shape[0] == 1:
+            y, J = y[0], J[0]
+        return (y, J) if return_signal else J
+
+    def log_likelihood(self, params, data, sigma, flow=None, fhigh=None, grad=False):
+        """Gaussian ln L = -1/2 sum_k (data_k - signal_k)^2 / sigma_k^2 over the bins of the band [flow, fhigh] of
+        ``self.frequencies`` (as ``error`` selects them; bins outside get weight 0), and with grad=True its gradient
+        with respect to the raw parameters -- both reduced on the device (not in the reference).  ``sigma``: a scalar or
+        one value per bin, mK.  One value (and a (7,) gradient) for a parameter vector, (N,) (and (N, 7)) for N.  The
+        data / sigma record is kept on the device per stack: a sampler's repeated call uploads only its parameters."""
+        model, st, flags, x = self._diff_stack(params)
+        nb = st.dims[-1]
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
+        s = np.broadcast_to(np.asarray(sigma, np.float64), (nb,))
+        w = (1.0 / s ** 2).astype(np.float32)
+        if flow or fhigh:
+            if self.frequencies is None:
+                raise ValueError("No frequency array is given, cannot select a frequency band.")
+            nu = np.asarray(self.frequencies)
+            sel = np.ones(nb, bool)
+            if flow:
+                sel &= nu >= flow
+            if fhigh:
+                sel &= nu <= fhigh
+            w = np.where(sel, w, np.float32(0))
+        rec = getattr(st, "_lk_record", None)
+        if rec is None or not (np.array_equal(rec[0], d) and np.array_equal(rec[1], w)):
+            st.set_likelihood(d, w)
+            st._lk_record = (d.copy(), w.copy())
+        out = st.loglike(x, model.precision, flags, grad=grad)
+        if grad:
+            lnl, g = out
+            return (lnl[0], g[0]) if x.shape[0] == 1 else (lnl, g)
+        return out[0] if x.shape[0] == 1 else out
+
     def save(self):
         raise NotImplementedError("Not implemented yet.")
 

@@ -284,6 +284,19 @@ class Model:
     def __call__(self, x, training=False):
         return self.predict(np.asarray(x))
 
+    def jacobian(self, x, precision=None):
+        """numpy (n, in) -> numpy float32 (n, out, in): J[n, k, j] = d out_k / d in_j of the plain network (not in the
+        reference, whose Keras model is differentiated with tf.GradientTape).  The result is a transposed VIEW of the
+        library's (n, in, out) buffer (include/v21.h: v21_mlp_jacobian); ``np.ascontiguousarray`` it where the layout
+        matters.  A ReLU at exactly zero has derivative 0, as the forward's mask (z > 0) implies."""
+        x = np.asarray(x)
+        if x.ndim == 1:
+            x = x[None, :]
+        if not self.built:
+            self.build((None, x.shape[-1]))
+        st = self._ensure_stack()
+        return st.jacobian(x, precision or self.precision).transpose(0, 2, 1)
+
     # -- training ------------------------------------------------------------------
     def compile(self, optimizer="adam", loss=None, **_):
         prev = self.optimizer

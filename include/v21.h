@@ -172,6 +172,32 @@ int v21_jit_prebuild(int n_layers, const int* dims, const int* act, int precisio
 #define V21_FWD_FORCE_JIT 32
 #define V21_SMALL_BATCH_ROWS 4096
 
+/* ---- parameter Jacobian and Gaussian log-likelihood (forward mode: the primal and its in_dim tangents pushed through
+ * the stack in one launch; the reference differentiates its Keras model with tf.GradientTape).
+ *   v21_mlp_jacobian[_dev]  y[n, :] = the forward's output (nullable) and jac[n, j, :] = d y[n, :] / d x[n, j], layout
+ *     (n, in_dim, out_dim), float32.  flags: V21_FWD_IN_TRANSFORM / V21_FWD_OUT_TRANSFORM as for the forward; with the
+ *     input transform the derivative is with respect to the RAW parameter, taken at the value after the zero floor
+ *     (the two input branches of v21_affine_in: float32 and float64 rows); the output transform contributes std.
+ *   v21_mlp_set_likelihood  the data vector d and the inverse variances w = 1 / sigma^2 (out_dim floats each, copied;
+ *     NULL clears).  Bins with w == 0 do not influence any result.
+ *   v21_mlp_loglike[_dev]   lnl[n] = -1/2 sum_k w_k (d_k - y_k)^2 and grad[n, j] = d lnl / d x[n, j] (nullable), reduced
+ *     on the device (4 (1 + in_dim) bytes per row leave it instead of the whole Jacobian).
+ * Routes (v21_route_jacobian; csrc/routes.h: 1 = fused, 2 = generic): the stacks of archs.h (S1-S4, up to 15 inputs)
+ * take fused_jac<Arch, Prec>, whose primal is bit-identical to the forward's fused route in the same precision; every
+ * other stack (any hidden_dims, any in_dim, wider than 512, V21_ACT_GAUSS evaluated as z = z_mean) takes a generic
+ * kernel in f32 arithmetic whatever the precision.  n = 0 is a no-op.  The _dev forms are asynchronous on the
+ * context's stream; the host forms return when the results are in place.  v21_mlp_last_jac_route: the route of the
+ * last call and the calls per route (counts[4], indexed by route). */
+int v21_mlp_jacobian(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, float* y, float* jac, int precision, int flags);
+int v21_mlp_jacobian_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, float* d_y, int64_t ldy, float* d_jac,
+                         int precision, int flags);
+int v21_mlp_set_likelihood(v21_mlp* mlp, const float* data, const float* inv_var, int32_t n);
+int v21_mlp_loglike(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, float* lnl, float* grad, int precision, int flags);
+int v21_mlp_loglike_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, float* d_lnl, float* d_grad, int precision,
+                        int flags);
+int v21_route_jacobian(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int* route);
+int v21_mlp_last_jac_route(v21_mlp* mlp, int* route, long long counts[4]);
+
 /* ---- trainer: replaces Model.compile + Model.fit (emulator.py:369-378, :739-747,
  * :756-764; optimizer/loss from notebooks/Training.ipynb cells 4 and 10). ------- */
 typedef struct {
