@@ -6,6 +6,7 @@ preprocess.par_transform (taken at the value after the fx zero floor, floored in
 output transform."""
 import numpy as np
 
+import half_ref
 from oracle import ref_numpy as ora
 
 RELU, GAUSS = 1, 2
@@ -32,27 +33,15 @@ def forward(Ws, bs, act, xt):
 
 
 def round16(a, prec):
-    """float64 -> the nearest f16 / bf16 value (round to nearest even), as float64"""
-    a = np.asarray(a, np.float64)
-    if prec == "f16":
-        return a.astype(np.float16).astype(np.float64)
-    u = a.astype(np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(np.float32).astype(np.float64)
+    """float64 -> the nearest f16 / bf16 value (round to nearest even), as float64 (half_ref.round16)"""
+    return half_ref.round16(a, prec)
 
 
 def masks16(Ws, bs, act, xt, prec, with_z=False):
     """the ReLU decisions of a 16-bit primal as the fused kernels form it: operands (input, weights, activations) rounded
     to f16 / bf16, products summed wide, the f32 bias added, z > 0 -- per layer a bool (n, units) array or None (and the
-    pre-activations with with_z)"""
-    h = round16(xt, prec)
-    out, zs = [], []
-    for (W, b), a in zip(layer_params(Ws, bs, act), act):
-        z = h @ round16(W, prec) + b
-        out.append(z > 0 if a == RELU else None)
-        zs.append(z)
-        h = round16(np.maximum(z, 0) if a == RELU else z, prec)
-    return (out, zs) if with_z else out
+    pre-activations with with_z).  One definition: half_ref.masks16."""
+    return half_ref.masks16(Ws, bs, act, xt, prec, with_z=with_z)
 
 
 def jvp(Ws, bs, act, xt, flips=None, masks=None):

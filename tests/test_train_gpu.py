@@ -156,7 +156,11 @@ def test_reference_architecture_step_all_precisions(ctx):
         assert cos > cos_min
         assert abs(loss - ref[0]) / ref[0] < (1e-5 if prec == "f32" else 2e-2)
         from helpers import per_layer_gradient_check   # (r5: layer by layer -- the cosine of the whole arena cannot see a small layer)
-        ok, note = per_layer_gradient_check(dims, [1, 1, 1, 1, 0], Ws, bs, x, g, ref[1], prec)
+        model = None
+        if prec != "f32":   # the 16-bit branch: the rounding reference of the route's model (tests/half_ref.py)
+            import half_ref as hr
+            model = hr.route_model(tr.last_route()[0][0])
+        ok, note = per_layer_gradient_check(dims, [1, 1, 1, 1, 0], Ws, bs, x, g, ref[1], prec, tgt=y, w=w, loss=loss, model=model)
         assert ok, (prec, note)
 
 
@@ -352,8 +356,10 @@ def test_fused_training_kernel_matches_chain_route_and_oracle(ctx, case, prec, r
         tr.set_data(0, x, y, w)
         l1 = tr.run_epoch(None, n)
         g1 = tr.get_grad()
+        kind = tr.last_route()[0][0]
+        w_mid = st.get_weights()                                 # the arena Adam moved: what the second step's stream is packed from
         l2 = tr.run_epoch(ora.epoch_permutation(n, 3, 0), n)     # gathered through an index table, weights moved by Adam
-        res[route] = (l1, g1, l2, st.get_weights())
+        res[route] = (l1, g1, l2, st.get_weights(), kind, w_mid)
         rc = tr.route_counters()   # "the routes agree" must not pass with both taking the same kernel
         assert (rc["chain"], rc["fused"]) == ((2, 0) if route == "chain" else (0, 2)), (route, rc)
         if route == "fused":       # the first step packs the stream, the second finds it written by the first's Adam pass
@@ -374,15 +380,26 @@ def test_fused_training_kernel_matches_chain_route_and_oracle(ctx, case, prec, r
         dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
     go = ora.flatten_params(dWs, dbs)
     tol_l, tol_c = (3e-3, 0.9995) if prec == "f16" else (3e-2, 0.995)
+    import half_ref as hr
+    from helpers import HALF_STEP_TOL, per_layer_gradient_check
+    perm2 = ora.epoch_permutation(n, 3, 0)
     for route in ("chain", "fused"):
-        l1, g1, l2, _ = res[route]
+        l1, g1, l2, _, kind, w_mid = res[route]
+        assert kind == ("chain16" if route == "chain" else ("fused64" if rows_per_wave == 16 else "fused128")), (route, kind)
         assert abs(l1 - lo) / lo < tol_l, (name, route, l1, lo)
         cos = float(g1 @ go / (np.linalg.norm(g1) * np.linalg.norm(go)))
         assert cos > tol_c and abs(np.linalg.norm(g1) / np.linalg.norm(go) - 1) < 10 * tol_l, (name, route, cos)
-        from helpers import per_layer_gradient_check
-        ok, note = per_layer_gradient_check(dims, act, Ws, bs, x, g1, go, prec)
+        # ... and against the rounding reference of the route's model (tests/half_ref.py), every mutation refused
+        ok, note = per_layer_gradient_check(dims, act, Ws, bs, x, g1, go, prec, tgt=tgt, w=w, loss=l1, model=hr.route_model(kind))
         assert ok, (name, route, note)
-    (lc, gc, lc2, wc), (lf, gf, lf2, wf) = res["chain"], res["fused"]
+        # the second step runs on weights Adam repacked: its loss against the rounding reference of the device's OWN arena
+        # weights before it (a stale or misplaced packed fragment shows at ~1e-6 here, not at the float64 bound of 3e-3)
+        Wm, bm = ora.unflatten_params(np.asarray(w_mid, np.float32), dims)
+        l2r, _ = hr.step(Wm, bm, act, x[perm2], tgt[perm2], w[perm2], prec, mask=hr.route_model(kind))
+        e2 = abs(l2 - l2r) / l2r
+        print("HALFREF second step %s %s %s loss %.1e" % (name, prec, kind, e2))
+        assert e2 <= HALF_STEP_TOL[prec]["loss"], (name, route, "second step loss vs rounding reference", e2)
+    (lc, gc, lc2, wc, _, _), (lf, gf, lf2, wf, _, _) = res["chain"], res["fused"]
     # the two routes round the same operands to 16 bits and sum in fp32: they agree far better than either meets float64
     assert abs(lf - lc) / lc < 1e-5 and abs(lf2 - lc2) / lc2 < 1e-3, (name, lf, lc, lf2, lc2)
     cos = float(gc @ gf / (np.linalg.norm(gc) * np.linalg.norm(gf)))
@@ -574,7 +591,18 @@ def test_vae_trainer_argument_errors(ctx):
 
 
 # ---- one-kernel forward + activation-gradient chain (csrc/train_chain.h) --------------------
-def _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain):
+def _half_ref_check(tag, dims, act, Ws, bs, x, tgt, w, loss, g, prec, route, brows=None):
+    """the 16-bit branch of the step checks (helpers.half_step_check): loss and FULL gradient against the float64 reference
+    that rounds where the kernels round, in the ReLU model of the route taken (tests/half_ref.py); every mutation of the
+    catalogue applied to the device's own result refused"""
+    import half_ref as hr
+    from helpers import half_step_check
+    dims = [np.shape(Ws[0])[0]] + [np.shape(W)[1] for W in Ws]
+    ok, note, _ = half_step_check(dims, act, Ws, bs, x, tgt, w, loss, g, prec, hr.route_model(route), brows=brows)
+    assert ok, (tag, route, note)
+
+
+def _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain, route=None):
     import os
     native = pkg("_native")
     Ws, bs = ora.init_mlp(dims, seed=31)
@@ -592,6 +620,8 @@ def _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain):
     tr.set_adam(lr=1e-3)
     tr.set_data(0, x, y, w)
     loss = tr.run_epoch(perm, batch)
+    if route is not None:   # (a list: the forward route the step took is appended)
+        route.append(tr.last_route()[0][0])
     return loss, tr.get_grad().astype(np.float64), st.get_weights(), (Ws, bs)
 
 
@@ -622,8 +652,12 @@ def test_chain_kernel_matches_per_layer_path_and_oracle(ctx, prec, case):
         batch = n
     w = ora.relative_mse_row_weight(x if y is None else y, sig).astype(np.float32)
     perm = np.random.default_rng(2).permutation(n).astype(np.int32)
-    lc, gc, wc, (Ws, bs) = _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain=True)
-    ln, gn, wn, _ = _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain=False)
+    routes = []
+    lc, gc, wc, (Ws, bs) = _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain=True, route=routes)
+    ln, gn, wn, _ = _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain=False, route=routes)
+    assert routes == ["chain16", "per_layer"], routes
+    for (l_, g_), r_ in zip(((lc, gc), (ln, gn)), routes):   # both routes against the rounding reference
+        _half_ref_check(case, dims, act, Ws, bs, x[perm], (x if y is None else y)[perm], w[perm], l_, g_, prec, r_)
     # float64 oracle of the same step
     W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
     xs = x[perm].astype(np.float64); ys = xs if y is None else y[perm].astype(np.float64)
@@ -720,7 +754,10 @@ def test_chain_kernel_odd_shapes(ctx, dims, act, n):
     y = None if dims[0] == dims[-1] and len(dims) > 2 else rng.normal(size=(n, dims[-1])).astype(np.float32)
     w = rng.uniform(0.5, 1.5, size=n).astype(np.float32) / dims[-1]
     perm = rng.permutation(n).astype(np.int32)
-    lc, gc, _, (Ws, bs) = _one_step(ctx, dims, act, "f16", x, y, w, perm, max(n, 2), chain=True)
+    routes = []
+    lc, gc, _, (Ws, bs) = _one_step(ctx, dims, act, "f16", x, y, w, perm, max(n, 2), chain=True, route=routes)
+    assert routes == ["chain16"], routes
+    _half_ref_check(dims, dims, act, Ws, bs, x[perm], (x if y is None else y)[perm], w[perm], lc, gc, "f16", routes[0])
     W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
     xs = x[perm].astype(np.float64); ys = xs if y is None else y[perm].astype(np.float64)
     acts = [xs]
@@ -773,11 +810,17 @@ def test_one_launch_gradient_adam_kernel_state_and_packed_copies(ctx, prec, dims
         t = x.astype(np.float64) if y is None else y.astype(np.float64)
         return float(np.mean(ora.per_sample_loss(h, t, w.astype(np.float64))))
 
+    import half_ref as hr
     for step in range(3):
-        expect = oracle_loss(st.get_weights().astype(np.float64))
+        before = st.get_weights()
+        expect = oracle_loss(before.astype(np.float64))
         loss = tr.run_epoch(None, n)
         assert abs(loss - expect) / expect < tol, (step, loss, expect)
         g = tr.get_grad().astype(np.float64)
+        # ... and against the rounding reference of the arena weights before the step: steps 2 and 3 run on the packed
+        # copies this kernel rebuilt, where a stale or misplaced fragment shows at ~1e-6 instead of the float64 bound
+        Wb, bb = ora.unflatten_params(before, dims)
+        _half_ref_check((dims, step), dims, act, Wb, bb, x, x if y is None else y, w, loss, g, prec, tr.last_route()[0][0])
         flat = ora.adam_step(flat, g, ostate)
         it, m, v = tr.get_state()
         assert it == step + 1
@@ -939,6 +982,10 @@ def test_data_parallel_arithmetic_without_a_communicator(ctx, prec):
         ctx.h2d(d_x, np.ascontiguousarray(y[rows])); ctx.h2d(d_w, np.ascontiguousarray(w[rows]))
         tr.step_dev(d_x, None, d_w, len(y[rows]), global_rows)
         g, l = tr.get_grad().astype(np.float64), tr.last_step_loss()
+        if prec != "f32":   # each slice against the rounding reference with the GLOBAL row count (loss scale and gs); the
+            # loss slot holds sum_i w_i sum_j (p - y)^2 of the slice, not yet divided by the global rows (api_trainer.hip:1653)
+            _half_ref_check((rows, global_rows), dims, act, Ws, bs, y[rows], y[rows], w[rows], l / global_rows, g, prec,
+                            tr.last_route()[0][0], brows=global_rows)
         ctx.free(d_x); ctx.free(d_w)
         return g, l
     g_all, l_all = grad_of(slice(0, n), n)
