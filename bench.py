@@ -9,7 +9,11 @@ inputs resident in HBM, full DirectEmulator.predict arithmetic on the device
 float32 written to HBM.  One "step" = one such pass.  Weak scaling: every rank runs its
 own batch (rows are independent; no data-path collective).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+  A plain run sets up, settles the clock, runs the W warm-up and K timed steps, writes --dump-outputs and prints the line.
+  --full adds everything else: the per-launch and clock-stamped repeats of the K launches (roofline min / median / clock),
+  the other precisions and forward routes, the training / sweep / fit legs, accuracy, class surface, latency and the CPU
+  baseline (--no-extras, --no-train and --no-cpu-baseline then leave parts of that out).
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
           (or plain `python bench.py --gpus N`: without WORLD_SIZE in the environment the script starts that
           launcher itself as a CHILD process, before anything here touches the GPU, and relays rank 0's line)
@@ -758,6 +762,9 @@ def main():
     ap.add_argument("--settle", type=float, default=0.3, help="seconds of untimed launches before the warm-up steps")
     ap.add_argument("--precision", default="f16", choices=["f16", "bf16", "f32"])
     ap.add_argument("--batch", type=int, default=BATCH)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every auxiliary measurement (repeats of the timed launches, other precisions and routes, "
+                         "training legs, CPU baseline); a plain run does only the headline steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-train", action="store_true")
@@ -852,15 +859,18 @@ def main():
         if args.dump_outputs and rank == 0:
             timed.output = np.empty((B, DIMS[-1]), np.float32)
             ctx.d2h(timed.output, d_y)
+        # --full only from here on: the untimed repeats of the K launches
+        timed.per_launch_ms = None
         # per-launch durations of a second, untimed run of the same K launches (an event pair around every launch
         # costs a few us of host time per step, so it stays out of the timed region): min / median beside the mean
-        evs = [ctx.event() for _ in range(steps + 1)]
-        ctx.record(evs[0])
-        for i in range(steps):
-            stack.forward_dev(d_x, DIMS[0], B, d_y, DIMS[-1], prec, flags)
-            ctx.record(evs[i + 1])
-        ctx.sync()
-        timed.per_launch_ms = [ctx.elapsed_ms(evs[i], evs[i + 1]) for i in range(steps)]
+        if args.full:
+            evs = [ctx.event() for _ in range(steps + 1)]
+            ctx.record(evs[0])
+            for i in range(steps):
+                stack.forward_dev(d_x, DIMS[0], B, d_y, DIMS[-1], prec, flags)
+                ctx.record(evs[i + 1])
+            ctx.sync()
+            timed.per_launch_ms = [ctx.elapsed_ms(evs[i], evs[i + 1]) for i in range(steps)]
         # (r4 ran a THIRD repeat here with one sampling wave beside the launches -- v21_debug_clock_probe_*.  r5 dropped it: that wave
         #  sits on ONE CU and reads ITS clock between samples -- 2.44 GHz beside launches whose own workgroups measure 1.5-1.6 GHz
         #  (gpurun_out runs of r5; VERDICT r4 weak 2 had spotted that the same 52-54 us came with "clocks" of 1.78 and 2.40 GHz))
@@ -870,7 +880,7 @@ def main():
         # pairs of scalar counter reads and one 40-byte store per workgroup): wave 0 of EVERY workgroup of EVERY one of the K
         # launches reads s_memtime (shader-clock cycles) and s_memrealtime (100 MHz) at its start and end, and its XCD.
         timed.inkernel = None
-        if prec in ("f16", "bf16") and rank == 0:
+        if args.full and prec in ("f16", "bf16") and rank == 0:
             try:
                 nwg = (B + 127) // 128
                 d_st = ctx.malloc(steps * nwg * 40)
@@ -923,6 +933,7 @@ def main():
         "vs_baseline": None,
         "dtype": {"f16": "f16 (f32 accumulate)", "bf16": "bf16 (f32 accumulate)", "f32": "f32"}[args.precision],
         "data": "synthetic",
+        "full": args.full,
         "outputs_dumped": dumped,
         "config": {"workload": "configs[1]: direct emulator 7->[352,352,352,224]->451 batched predict, "
                                "batch=%d per GPU, device-resident in/out, fused par_transform+unpreproc" % B,
@@ -931,9 +942,10 @@ def main():
                      "unit": "TFLOP/s", "frac": achieved_tf / PEAK_TFLOPS[args.precision], "traffic": None,
                      "kernel": "fused_fwd<ArchS1, Prec%sx2sp>" % args.precision.upper() if args.precision != "f32" else "fused_fwd<ArchS1, PrecF32>",
                      "kernel_ms": kern_s * 1e3,
-                     "kernel_ms_min": float(min(timed.per_launch_ms)), "kernel_ms_median": float(np.median(timed.per_launch_ms)),
+                     "kernel_ms_min": float(min(timed.per_launch_ms)) if timed.per_launch_ms else None,
+                     "kernel_ms_median": float(np.median(timed.per_launch_ms)) if timed.per_launch_ms else None,
                      "time_base": "HIP events on the launch stream around the K timed launches (mean); min / median from "
-                                  "per-launch event pairs of a second run; profiles/%s/kernel_stats_bench_f16.csv " % PROFILE_TAG +
+                                  "per-launch event pairs of a second run (--full); profiles/%s/kernel_stats_bench_f16.csv " % PROFILE_TAG +
                                   "(rocprofv3 --kernel-trace --stats of this command) must agree with the mean",
                      # (the same fraction from the ONE number the driver times itself: ms_per_step, launch gaps included)
                      "frac_from_ms_per_step": FLOP_PER_SIGNAL * B / (wall / args.steps) / 1e12 / PEAK_TFLOPS[args.precision],
@@ -984,7 +996,7 @@ def main():
         except Exception:
             pass
 
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         modes = {}
         for prec in ("f32", "bf16", "f16"):
             if prec == args.precision:
@@ -1130,7 +1142,7 @@ def main():
         out["host_roundtrip_signals_per_s"] = B * reps / (time.perf_counter() - t0)
         del yk
 
-    if not args.no_train and not args.no_extras:
+    if args.full and not args.no_train and not args.no_extras:
         try:  # before the communicator exists: the models of a sweep are independent per rank
             out["sweep"] = sweep_leg(native, ctx, args.precision)
         except Exception as e:
@@ -1150,7 +1162,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             out["sweep"]["model_steps_per_s_grouped_all_ranks"] = float(t.item())
 
-    if not args.no_train:
+    if args.full and not args.no_train:
         def run_train():
             try:
                 if dist is not None and dist.get_backend() == "nccl":
@@ -1280,7 +1292,7 @@ def main():
         else:
             run_train()
 
-    if rank == 0 and world == 1 and not args.no_train and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_train and not args.no_extras:
         try:
             out["fit_reference_recipe"] = [fit_leg("f32"), fit_leg("f16")]
             out["fit_n30000"] = [fit_leg("f16", n_train=30000), fit_leg("f16", n_train=30000, joint=True),
@@ -1300,7 +1312,7 @@ def main():
         except Exception as e:
             out["single_call_latency"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # last: see _BLAS_LIMIT
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # last: see _BLAS_LIMIT
         xt = pp.par_transform(params.astype(np.float64), par_train).astype(np.float32)
         out["cpu_baseline"] = cpu_baseline(wflat, xt)
 

@@ -1,5 +1,5 @@
 """Duration statistics of a window of n dispatches of a kernel in a rocprofv3 kernel-trace CSV, `tail` dispatches
-before the end (bench.py launches W warm-up, K timed, then K more with an event pair each: the timed ones are
+before the end (bench.py --full launches W warm-up, K timed, then K more with an event pair each: the timed ones are
 n = K, tail = K):  python scripts/kstats_trace.py <kernel_trace.csv> <name substring> <n> [tail]"""
 import csv, json, sys
 import numpy as np

@@ -1,6 +1,6 @@
 """MFMA-pipe occupancy of a window of dispatches in a rocprofv3 --pmc counter CSV (the timed launches
 only).  python scripts/pmc_timed.py <kernel substring> <n> <tail> <counter_collection.csv>...
-bench.py --no-extras --no-train launches the headline kernel: settle, W warm-up, K timed, K with per-launch events, K with
+bench.py --full --no-extras --no-train launches the headline kernel: settle, W warm-up, K timed, K with per-launch events, K with
 the clock probe beside them -- the timed ones are n = K dispatches ending tail = 2 K before the last."""
 import csv, json, sys, collections
 pat, n, tail = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])

@@ -2,6 +2,7 @@
 script starts one rank per GPU as CHILD processes before anything touches the GPU, relays rank 0's JSON line -- and only
 that -- to stdout, and passes the children's failure on."""
 import importlib.util
+import io
 import json
 import os
 import subprocess
@@ -99,3 +100,94 @@ def test_steps_must_be_positive(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 2
+
+
+class _FakeNative:
+    """Stands in for 21cmvae_amd._native inside bench.main(): no GPU, every launch recorded in order."""
+    FWD_IN_TRANSFORM, FWD_OUT_TRANSFORM = 1, 2
+
+    def __init__(self):
+        self.launches = []
+        fake = self
+
+        class Context:
+            def __init__(self, device=0):
+                self.next = 1 << 20
+
+            def malloc(self, nbytes):
+                self.next += nbytes + 256
+                return self.next - nbytes - 256
+
+            def d2h(self, arr, dptr):
+                arr[...] = 0
+
+            def event(self):
+                return object()
+
+            def elapsed_ms(self, a, b):
+                return 0.05
+
+            h2d = memset = lambda self, *a: None
+            sync = free = record = lambda self, *a: None
+
+        class Stack:
+            def __init__(self, ctx, dims, act):
+                pass
+
+            set_weights = set_input_transform = set_output_transform = lambda self, *a: None
+
+            def forward_dev(self, d_x, ldx, n, d_y, ldy, prec, flags):
+                fake.launches.append(("forward", prec, n))
+
+            def forward_clocked(self, d_x, ldx, n, d_y, ldy, d_st, prec, flags):
+                fake.launches.append(("clocked", prec, n))
+
+        self.Context, self.Stack = Context, Stack
+
+
+def _run_main(monkeypatch, argv):
+    bench = _bench()
+    native = _FakeNative()
+    monkeypatch.setitem(sys.modules, "21cmvae_amd._native", native)
+    monkeypatch.setitem(sys.modules, "torch", None)          # single rank: no process group, no torch device sync
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    for k in ("RANK", "LOCAL_RANK", "V21_BENCH_REHEARSAL"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(bench, "_reduce_clock_stamps", lambda st, ms: {"stamped_launches": int(st.shape[0])})
+    line = io.StringIO()
+    monkeypatch.setattr(bench, "_claim_stdout", lambda: line)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    bench.main()
+    return json.loads(line.getvalue()), native.launches
+
+
+AUXILIARY_KEYS = ("other_precisions_1gpu", "predict_two_streams", "predict_generic_S1", "predict_table_driven_S1", "predict_jit_S1",
+                  "predict_custom", "predict_hidden_352", "host_roundtrip_signals_per_s", "sweep", "sweep_scaling", "sweep_f32",
+                  "train", "dp_compute_only", "train_custom_b16384", "train_ref_batch256_f32", "train_b16384", "train_b32768",
+                  "train_variational", "fit_reference_recipe", "fit_n30000", "accuracy_on_trained_stack",
+                  "class_surface_predict", "single_call_latency", "cpu_baseline")
+
+
+def test_plain_run_launches_only_the_warm_up_and_timed_steps(monkeypatch, tmp_path):
+    """Without --full the run is set-up, W warm-up and K timed launches of the headline kernel, the dump and the line: no
+    repeat of the K launches, no other precision, route or leg."""
+    out, launches = _run_main(monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "3", "--settle", "0", "--batch", "300",
+                                            "--dump-outputs", str(tmp_path / "d")])
+    assert launches == [("forward", "f16", 300)] * (3 + 7)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["metric"] == "emulated signals/sec (batched predict)" and out["unit"] == "signals/s" and out["higher_is_better"] is True
+    assert out["steps"] == 7 and out["warmup"] == 3 and out["full"] is False
+    assert not [k for k in AUXILIARY_KEYS if k in out]
+    assert out["roofline"]["kernel_ms_median"] is None and out["roofline"]["clock_in_kernel"] is None
+    assert np.load(tmp_path / "d" / "signals.npy").shape == (300, 451)
+
+
+def test_full_run_repeats_the_timed_launches(monkeypatch):
+    """--full (here without the legs) adds the per-launch-event repeat of the K launches and the clock-stamped one (settle,
+    W warm-up, K stamped) after the timed steps, which stay first and unchanged."""
+    out, launches = _run_main(monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "3", "--settle", "0", "--batch", "300",
+                                            "--full", "--no-extras", "--no-train", "--no-cpu-baseline"])
+    assert launches == [("forward", "f16", 300)] * (3 + 7 + 7) + [("clocked", "f16", 300)] * (3 + 7)
+    assert out["full"] is True and out["roofline"]["kernel_ms_median"] == 0.05
+    assert out["roofline"]["clock_in_kernel"] == {"stamped_launches": 7}
