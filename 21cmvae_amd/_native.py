@@ -51,6 +51,15 @@ class Adam(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
 
 
+class FitOpts(C.Structure):
+    """v21_fit_opts (include/v21_types.h)"""
+    _fields_ = [("max_iter", C.c_int), ("lambda0", C.c_double), ("xtol", C.c_double), ("check_every", C.c_int)]
+
+
+FIT_DEFAULTS = {"max_iter": 50, "lambda0": 1e-3, "xtol": 1e-7, "check_every": 8}
+FIT_STATUS = {0: "iteration limit", 1: "converged", 2: "no improving step", 3: "no information"}
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 # name -> (restype, argtypes); every symbol include/v21.h declares
@@ -113,6 +122,11 @@ SIGNATURES = {
     "v21_mlp_loglike_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int]),
     "v21_route_jacobian": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
     "v21_mlp_last_jac_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "v21_mlp_fisher": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, _F, _F, C.c_int, C.c_int]),
+    "v21_mlp_fisher_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int]),
+    "v21_mlp_fit": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(FitOpts), _P, _F, _F, _F, C.POINTER(C.c_int32),
+                              C.c_int, C.c_int]),
+    "v21_mlp_fit_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(FitOpts), _P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "v21_trainer_last_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "v21_route_name": (C.c_char_p, [C.c_int, C.c_int]),
     "v21_trainer_get_data_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
@@ -611,6 +625,71 @@ class Stack(_Owned):
     def loglike_dev(self, d_x, ldx, n, d_lnl, d_grad, precision="f32", flags=0):
         check(self.lib.v21_mlp_loglike_dev(self.h, _P(d_x), ldx, n, _P(d_lnl), _P(d_grad) if d_grad else None,
                                            precision_id(precision), flags))
+
+    def fisher(self, x, precision="f32", flags=0, lnl=False, grad=False):
+        """host (n, in) -> F (n, in, in) float32, F = J^T W J with W the inverse variances of the likelihood record
+        (include/v21.h: v21_mlp_fisher); with lnl / grad also ln L (n,) / its gradient (n, in): (F, lnl[, grad])."""
+        x, dt = self._rows(x)
+        n, din = x.shape[0], self.dims[0]
+        F = np.empty((n, din, din), np.float32)
+        lv = np.empty(n, np.float32) if lnl else None
+        g = np.empty((n, din), np.float32) if grad else None
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_fisher(self.h, x.ctypes.data_as(_P), dt, n, _fptr(F), _fptr(lv) if lv is not None else None,
+                                          _fptr(g) if g is not None else None, precision_id(precision), flags))
+        return (F,) + tuple(a for a in (lv, g) if a is not None) if (lnl or grad) else F
+
+    @staticmethod
+    def fit_opts(max_iter=None, lambda0=None, xtol=None, check_every=None):
+        o = dict(FIT_DEFAULTS)
+        for k, v in (("max_iter", max_iter), ("lambda0", lambda0), ("xtol", xtol), ("check_every", check_every)):
+            if v is not None:
+                o[k] = v
+        return FitOpts(int(o["max_iter"]), float(o["lambda0"]), float(o["xtol"]), int(o["check_every"]))
+
+    def fit(self, x0, precision="f32", flags=0, data=None, max_iter=None, lambda0=None, xtol=None, check_every=None,
+            fisher=False):
+        """Projected Levenberg-Marquardt maximum-likelihood fit of every start row (include/v21.h: v21_mlp_fit; needs the
+        input transform and a likelihood record).  x0: (n, in) raw starts, float32 or float64; data: None (the record's
+        data) or (n_data, out) with n % n_data == 0, row i fitting data row i // (n // n_data).
+        -> dict x_hat (n, in) in x0's dtype, lnl, lnl_start (n,) float32, status (n,) int32 [, fisher (n, in, in)]."""
+        x, dt = self._rows(x0)
+        n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
+        if din > 8:
+            raise ValueError("fit: %d parameters (at most 8)" % din)
+        nd, dp = 0, None
+        if data is not None:
+            dp = np.ascontiguousarray(data, dtype=np.float32)
+            if dp.ndim == 1:
+                dp = dp[None, :]
+            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
+                raise ValueError("fit: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
+            nd = dp.shape[0]
+            if n % nd:
+                raise ValueError("fit: %d rows are not a multiple of %d data rows" % (n, nd))
+        opts = self.fit_opts(max_iter, lambda0, xtol, check_every)
+        xh = np.empty_like(x)
+        lnl, l0, status = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32)
+        F = np.empty((n, din, din), np.float32) if fisher else None
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_fit(self.h, x.ctypes.data_as(_P), dt, n, _fptr(dp) if dp is not None else None, nd, C.byref(opts),
+                                       xh.ctypes.data_as(_P), _fptr(lnl), _fptr(l0), _fptr(F) if F is not None else None,
+                                       status.ctypes.data_as(C.POINTER(C.c_int32)), precision_id(precision), flags))
+        out = {"x_hat": xh, "lnl": lnl, "lnl_start": l0, "status": status}
+        if fisher:
+            out["fisher"] = F
+        return out
+
+    def fisher_dev(self, d_x, ldx, n, d_fisher, d_lnl=None, d_grad=None, precision="f32", flags=0):
+        check(self.lib.v21_mlp_fisher_dev(self.h, _P(d_x), ldx, n, _P(d_fisher), _P(d_lnl) if d_lnl else None,
+                                          _P(d_grad) if d_grad else None, precision_id(precision), flags))
+
+    def fit_dev(self, d_x0, ldx, n, d_data, n_data, d_x_hat, d_lnl, d_lnl_start=None, d_fisher=None, d_status=None,
+                precision="f32", flags=0, **opts):
+        o = self.fit_opts(**opts)
+        check(self.lib.v21_mlp_fit_dev(self.h, _P(d_x0), ldx, n, _P(d_data) if d_data else None, n_data, C.byref(o), _P(d_x_hat),
+                                       _P(d_lnl), _P(d_lnl_start) if d_lnl_start else None, _P(d_fisher) if d_fisher else None,
+                                       _P(d_status) if d_status else None, precision_id(precision), flags))
 
     def last_jac_route(self):
         """(route name of the last Jacobian / log-likelihood call, {route name: calls since creation})."""

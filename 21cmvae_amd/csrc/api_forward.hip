@@ -148,6 +148,9 @@ extern "C" int v21_mlp_destroy(v21_mlp* m) {
   if (m->d_ys) hipFree(m->d_ys);
   for (float* p : {m->d_lk_data, m->d_lk_w, m->d_lk_ws, m->d_jxt, m->d_jfac, m->d_jy, m->d_jout}) if (p) hipFree(p);
   if (m->d_jx64) hipFree(m->d_jx64);
+  for (float* p : {m->d_fF, m->d_fl, m->d_fg, m->d_fdata, m->d_fout}) if (p) hipFree(p);
+  if (m->d_fit) hipFree(m->d_fit);
+  if (m->d_fit_cnt) hipFree(m->d_fit_cnt);
   delete m;
   return V21_OK;
 }

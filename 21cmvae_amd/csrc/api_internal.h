@@ -156,9 +156,28 @@ struct v21_mlp {
   long long jstage_rows = 0, jhost_rows = 0;  // rows of d_jxt / d_jfac; of d_jx64 / d_jy / d_jout (host API chunks)
   int last_jac_route = 0;
   long long jac_route_count[4] = {0, 0, 0, 0};
+  // Fisher matrices and fits (api_fit.hip): per-row fit state, the evaluation's results (F, ln L, gradient), the
+  // active-row count per iteration, and the host API's staging of results (rows of each)
+  void* d_fit = nullptr;
+  float *d_fF = nullptr, *d_fl = nullptr, *d_fg = nullptr;
+  long long fit_rows = 0;
+  int* d_fit_cnt = nullptr;
+  int fit_cnt_cap = 0;
+  float *d_fdata = nullptr, *d_fout = nullptr;
+  long long fdata_rows = 0, fout_rows = 0;
 };
 // api_forward.hip: fused_fwd's packed weight stream of this stack (built on first use)
 int mlp_fused_stream(v21_mlp* m, int prec, const unsigned char** stream);
+// api_jacobian.hip, shared with api_fit.hip: staging of transformed rows and factors (d_jxt / d_jfac, pitch in_dim) and of
+// the host API's chunks (kJacHostChunk rows), argument checks, the likelihood workspace (kLkSlice rows per slice) and
+// the input transform of device rows and one Jacobian-mode evaluation on a given route
+constexpr long long kJacHostChunk = 8192, kLkSlice = 16384;
+int jac_stage(v21_mlp* m, long long rows);
+int jac_stage_host(v21_mlp* m, long long rows);
+int jac_check(v21_mlp* m, int precision, int flags, bool like);
+int lk_ws_reserve(v21_mlp* m, long long rows);
+int jac_prep_rows(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n, int tin);
+int jac_eval_rows(v21_mlp* m, int route, const float* xt, const float* fac, long long n, float* y, float* jac, int prec, int flags);
 
 // ---- trainer (api_trainer.hip)
 struct v21_trainer {

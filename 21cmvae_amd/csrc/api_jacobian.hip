@@ -67,7 +67,7 @@ extern "C" int v21_mlp_set_likelihood(v21_mlp* m, const float* data, const float
 }
 
 // (re)size the staging of transformed rows and factors for `rows` rows (every route: a _dev call grows it to its n)
-static int jac_stage(v21_mlp* m, long long rows) {
+int jac_stage(v21_mlp* m, long long rows) {
   const int din = m->dims[0];
   if (m->jstage_rows >= rows) return V21_OK;
   for (float** p : {&m->d_jxt, &m->d_jfac}) if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
@@ -78,8 +78,7 @@ static int jac_stage(v21_mlp* m, long long rows) {
   return V21_OK;
 }
 // ... and the host API's input and result staging, sized by its chunk (at most kJacHostChunk rows), apart from the above
-constexpr long long kJacHostChunk = 8192;
-static int jac_stage_host(v21_mlp* m, long long rows) {
+int jac_stage_host(v21_mlp* m, long long rows) {
   const int din = m->dims[0], dout = m->dims[m->L];
   if (m->jhost_rows >= rows) return V21_OK;
   for (float** p : {&m->d_jy, &m->d_jout}) if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
@@ -89,6 +88,87 @@ static int jac_stage_host(v21_mlp* m, long long rows) {
   HIPCHK(hipMalloc((void**)&m->d_jy, (size_t)rows * dout * sizeof(float)));
   HIPCHK(hipMalloc((void**)&m->d_jout, (size_t)rows * din * std::max(dout, 2) * sizeof(float)));
   m->jhost_rows = rows;
+  return V21_OK;
+}
+
+// the generic kernel's stack description, tangents per workgroup and LDS size (and its LDS attribute, once per device)
+static int jac_gen_setup(v21_mlp* m, JacGenArgs& g, size_t* lds_out) {
+  const int L = m->L, din = m->dims[0];
+  g.L = L; g.in_dim = din;
+  int maxw = 0;
+  for (int l = 0; l <= L; ++l) { g.dims[l] = m->dims[l]; maxw = std::max(maxw, m->dims[l]); }
+  for (int l = 0; l < L; ++l) { g.act[l] = m->act[l]; g.nw[l] = m->nw(l); g.w_off[l] = m->w_off[l]; g.b_off[l] = m->b_off[l]; }
+  constexpr size_t kLdsMax = 160 * 1024;  // gfx950: LDS per workgroup
+  int tc = std::min(din, kJacGenCols - 1);
+  while (tc > 1 && (size_t)2 * (tc + 1) * maxw * sizeof(float) > kLdsMax) --tc;
+  const size_t lds = std::max((size_t)2 * (tc + 1) * maxw, (size_t)256) * sizeof(float);
+  if (lds > kLdsMax) return fail(V21_ERR_UNSUPPORTED, "Jacobian: a %d-wide layer does not fit the generic kernel's LDS", maxw);
+  g.tc = tc; g.maxw = maxw;
+  static bool attr_done[64] = {};
+  if (!attr_done[m->ctx->device & 63]) {
+    HIPCHK(hipFuncSetAttribute((const void*)jac_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    attr_done[m->ctx->device & 63] = true;
+  }
+  *lds_out = lds;
+  return V21_OK;
+}
+
+// the likelihood workspace (m->d_lk_ws): y and jac of up to `rows` rows, (1 + in_dim) out_dim floats each
+int lk_ws_reserve(v21_mlp* m, long long rows) {
+  const int din = m->dims[0], dout = m->dims[m->L];
+  if (m->lk_ws_rows >= rows) return V21_OK;
+  if (m->d_lk_ws) { HIPCHK(hipFree(m->d_lk_ws)); m->d_lk_ws = nullptr; }
+  m->lk_ws_rows = 0;
+  HIPCHK(hipMalloc((void**)&m->d_lk_ws, (size_t)rows * (din + 1) * dout * sizeof(float)));
+  m->lk_ws_rows = rows;
+  return V21_OK;
+}
+
+// Jacobian mode of `route` on rows (xt, fac) of pitch in_dim: y (n, out_dim) and jac (n, in_dim, out_dim), on the
+// context's stream (api_fit.hip: one slice of the likelihood workspace; the caller counts the route)
+int jac_eval_rows(v21_mlp* m, int route, const float* xt, const float* fac, long long n, float* y, float* jac, int prec, int flags) {
+  hipStream_t st = m->ctx->stream;
+  const int din = m->dims[0], dout = m->dims[m->L];
+  const bool tout = (flags & V21_FWD_OUT_TRANSFORM) != 0;
+  if (route == JAC_FUSED) {
+    JacArgs a{};
+    a.x = xt; a.ldx = din; a.fac = fac;
+    a.y = y; a.ldy = dout; a.jac = jac; a.n_rows = n;
+    CHK(mlp_fused_stream(m, prec, &a.stream));
+    a.out_std = tout ? m->out_std : 1.0f;
+    a.out_mean_scale = tout ? 1.0f : 0.0f;
+    HIPCHK(g_jac[m->fused_id][prec](a, st));
+    return V21_OK;
+  }
+  JacGenArgs g{};
+  size_t lds = 0;
+  CHK(jac_gen_setup(m, g, &lds));
+  g.w = m->d_w; g.fac = fac; g.ldy = dout; g.like = 0;
+  g.data = m->d_lk_data; g.wv = m->d_lk_w;
+  g.out_std = tout ? m->out_std : 1.0f;
+  g.mean = tout ? m->d_mean : nullptr;
+  for (long long r0 = 0; r0 < n; r0 += 65535) {
+    const long long rows = std::min<long long>(65535, n - r0);
+    g.xt = xt + r0 * din; g.fac = fac + r0 * din; g.n_rows = rows;
+    g.y = y ? y + r0 * dout : nullptr; g.jac = jac + r0 * din * dout;
+    hipLaunchKernelGGL(jac_generic_kernel, dim3((unsigned)rows, (unsigned)((din + g.tc - 1) / g.tc)), dim3(256), lds, st, g);
+    HIPCHK(hipGetLastError());
+  }
+  return V21_OK;
+}
+
+// device rows (float32 / float64, pitch ld) -> m->d_jxt / d_jfac (the caller has staged n rows), on the context's stream
+int jac_prep_rows(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n, int tin) {
+  const int din = m->dims[0];
+  const long long tot = n * din;
+  const dim3 grid((unsigned)((tot + 255) / 256));
+  if (dtype == V21_DTYPE_F64)
+    hipLaunchKernelGGL(jac_prep_kernel<double>, grid, dim3(256), 0, m->ctx->stream, m->d_jxt, m->d_jfac, (const double*)d_src, ld, n, din,
+                       tin, m->tin);
+  else
+    hipLaunchKernelGGL(jac_prep_kernel<float>, grid, dim3(256), 0, m->ctx->stream, m->d_jxt, m->d_jfac, (const float*)d_src, ld, n, din,
+                       tin, m->tin);
+  HIPCHK(hipGetLastError());
   return V21_OK;
 }
 
@@ -102,7 +182,7 @@ static int jac_launch(v21_mlp* m, long long n, float* d_y, long long ldy, float*
   m->last_jac_route = route; m->jac_route_count[route] += 1;
   if (route == JAC_FUSED) {
     // likelihood: the Jacobian-mode kernel into a device workspace, reduced there (jac_loglike_kernel), in slices
-    constexpr long long kSlice = 16384;
+    constexpr long long kSlice = kLkSlice;
     JacArgs a{};
     a.x = m->d_jxt; a.ldx = din; a.fac = m->d_jfac;
     a.y = d_y; a.ldy = ldy; a.jac = d_jac;
@@ -115,11 +195,7 @@ static int jac_launch(v21_mlp* m, long long n, float* d_y, long long ldy, float*
       return V21_OK;
     }
     const long long rows_ws = std::min(n, kSlice);
-    if (m->lk_ws_rows < rows_ws) {
-      if (m->d_lk_ws) HIPCHK(hipFree(m->d_lk_ws));
-      HIPCHK(hipMalloc((void**)&m->d_lk_ws, (size_t)rows_ws * (din + 1) * dout * sizeof(float)));
-      m->lk_ws_rows = rows_ws;
-    }
+    CHK(lk_ws_reserve(m, rows_ws));
     for (long long r0 = 0; r0 < n; r0 += kSlice) {
       const long long rows = std::min(kSlice, n - r0);
       a.x = m->d_jxt + r0 * din; a.fac = m->d_jfac + r0 * din; a.n_rows = rows;
@@ -133,26 +209,14 @@ static int jac_launch(v21_mlp* m, long long n, float* d_y, long long ldy, float*
     return V21_OK;
   }
   JacGenArgs g{};
-  g.L = L; g.in_dim = din;
-  int maxw = 0;
-  for (int l = 0; l <= L; ++l) { g.dims[l] = m->dims[l]; maxw = std::max(maxw, m->dims[l]); }
-  for (int l = 0; l < L; ++l) { g.act[l] = m->act[l]; g.nw[l] = m->nw(l); g.w_off[l] = m->w_off[l]; g.b_off[l] = m->b_off[l]; }
-  constexpr size_t kLdsMax = 160 * 1024;  // gfx950: LDS per workgroup
-  int tc = std::min(din, kJacGenCols - 1);
-  while (tc > 1 && (size_t)2 * (tc + 1) * maxw * sizeof(float) > kLdsMax) --tc;
-  const size_t lds = std::max((size_t)2 * (tc + 1) * maxw, (size_t)256) * sizeof(float);
-  if (lds > kLdsMax) return fail(V21_ERR_UNSUPPORTED, "Jacobian: a %d-wide layer does not fit the generic kernel's LDS", maxw);
-  g.tc = tc; g.maxw = maxw;
+  size_t lds = 0;
+  CHK(jac_gen_setup(m, g, &lds));
   g.w = m->d_w; g.xt = m->d_jxt; g.fac = m->d_jfac; g.n_rows = n;
   g.y = d_y; g.ldy = ldy; g.jac = d_jac; g.lnl = d_lnl; g.grad = d_grad;
   g.data = m->d_lk_data; g.wv = m->d_lk_w; g.like = like ? 1 : 0;
   g.out_std = tout ? m->out_std : 1.0f;
   g.mean = tout ? m->d_mean : nullptr;
-  static bool attr_done[64] = {};
-  if (!attr_done[m->ctx->device & 63]) {
-    HIPCHK(hipFuncSetAttribute((const void*)jac_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-    attr_done[m->ctx->device & 63] = true;
-  }
+  const int tc = g.tc;
   for (long long r0 = 0; r0 < n; r0 += 65535) {  // (grid.x <= 65,535 rows per launch; the row offsets move the pointers)
     JacGenArgs gs = g;
     const long long rows = std::min<long long>(65535, n - r0);
@@ -166,7 +230,7 @@ static int jac_launch(v21_mlp* m, long long n, float* d_y, long long ldy, float*
   return V21_OK;
 }
 
-static int jac_check(v21_mlp* m, int precision, int flags, bool like) {
+int jac_check(v21_mlp* m, int precision, int flags, bool like) {
   if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
   if ((flags & V21_FWD_IN_TRANSFORM) && !m->has_tin) return fail(V21_ERR_STATE, "input transform requested but not set");
   if ((flags & V21_FWD_OUT_TRANSFORM) && !m->has_tout) return fail(V21_ERR_STATE, "output transform requested but not set");

@@ -8,6 +8,7 @@ observe are listed in INTEGRATION.md (no dataset download, ``precision=`` option
 training-set statistics cached, AE predict evaluated as one fused device stack).
 """
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -147,6 +148,10 @@ def _grid(redshifts_, frequencies):
     return redshifts_, frequencies
 
 
+# fit_parameters' result (fisher: None unless asked for)
+FitResult = namedtuple("FitResult", ["params", "lnl", "status", "fisher"])
+
+
 class _EmulatorBase:
     par_labels = ["fstar", "Vc", "fx", "tau", "alpha", "nu_min", "Rmfp"]
 
@@ -251,6 +256,16 @@ class _EmulatorBase:
         model, st, flags, x = self._diff_stack(params)
         nb = st.dims[-1]
         d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
+        w = self._band_weights(nb, sigma, flow, fhigh)
+        self._set_record(st, d, w)
+        out = st.loglike(x, model.precision, flags, grad=grad)
+        if grad:
+            lnl, g = out
+            return (lnl[0], g[0]) if x.shape[0] == 1 else (lnl, g)
+        return out[0] if x.shape[0] == 1 else out
+
+    def _band_weights(self, nb, sigma, flow, fhigh):
+        """float32 1 / sigma^2 per bin, 0 outside the band [flow, fhigh] of ``self.frequencies`` (as ``error`` selects it)"""
         s = np.broadcast_to(np.asarray(sigma, np.float64), (nb,))
         w = (1.0 / s ** 2).astype(np.float32)
         if flow or fhigh:
@@ -263,15 +278,76 @@ class _EmulatorBase:
             if fhigh:
                 sel &= nu <= fhigh
             w = np.where(sel, w, np.float32(0))
+        return w
+
+    @staticmethod
+    def _set_record(st, d, w):
+        """the stack's likelihood record (data d, weights w), uploaded only when it changed (``st._lk_record``)"""
         rec = getattr(st, "_lk_record", None)
         if rec is None or not (np.array_equal(rec[0], d) and np.array_equal(rec[1], w)):
             st.set_likelihood(d, w)
             st._lk_record = (d.copy(), w.copy())
-        out = st.loglike(x, model.precision, flags, grad=grad)
-        if grad:
-            lnl, g = out
-            return (lnl[0], g[0]) if x.shape[0] == 1 else (lnl, g)
-        return out[0] if x.shape[0] == 1 else out
+
+    def fisher(self, params, sigma, flow=None, fhigh=None):
+        """Fisher matrix F = J^T diag(1 / sigma^2) J of the signal at ``params`` in raw parameter units (not in the
+        reference), over the bins of the band [flow, fhigh] as ``log_likelihood`` selects them; computed and reduced on
+        the device.  (7, 7) for one parameter vector, (N, 7, 7) for N.  Its inverse is the Gaussian forecast covariance."""
+        model, st, flags, x = self._diff_stack(params)
+        nb = st.dims[-1]
+        w = self._band_weights(nb, sigma, flow, fhigh)
+        rec = getattr(st, "_lk_record", None)
+        d = rec[0] if rec is not None else np.zeros(nb, np.float32)  # (the data are not read: keep the record's)
+        self._set_record(st, d, w)
+        F = st.fisher(x, model.precision, flags)
+        return F[0] if x.shape[0] == 1 else F
+
+    def fit_parameters(self, data, sigma, p0=None, n_starts=8, max_iter=50, flow=None, fhigh=None, seed=0, return_all=False,
+                       return_fisher=False):
+        """Maximum-likelihood parameters of observed signal(s) (not in the reference): a projected Levenberg-Marquardt fit
+        per (spectrum, start) on the device, inside the training box, of the Gaussian ln L of ``log_likelihood``.
+        ``data``: (451,) or (M, 451) mK.  Starts: ``p0`` ((7,) or (S, 7) raw parameters, the same for every spectrum), or
+        the box centre and ``n_starts - 1`` uniform points of the box (seeded; uniform in par_transform's coordinates).
+        Returns a ``FitResult`` (params, lnl, status[, fisher]) of the best start per spectrum (the lowest start index
+        among equals), or of every start with ``return_all`` ((M, S, ...); the M axis dropped for one spectrum).  status:
+        1 converged, 2 no improving step, 3 no information (all weights zero), 0 ``max_iter`` reached.  ``fisher``: the
+        Fisher matrix at the result in raw units.  Bounds: a log column's lower bound comes back as 10^lo (the fx zero
+        floor 1e-6, not 0)."""
+        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
+        nb = st.dims[-1]
+        dat = np.asarray(data, np.float32)
+        one = dat.ndim == 1
+        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
+        if dat.ndim != 2 or dat.shape[1] != nb:
+            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        din = st.dims[0]
+        if p0 is None:
+            if int(n_starts) < 1:
+                raise ValueError("n_starts must be >= 1")
+            rng = np.random.default_rng(seed)
+            u = np.vstack([np.zeros((1, din)), rng.uniform(-1.0, 1.0, size=(int(n_starts) - 1, din))])
+            starts = pp.par_untransform(u, self.par_train)
+        else:
+            starts = np.array(p0, np.float64, ndmin=2)
+            if starts.ndim != 2 or starts.shape[1] != din:
+                raise ValueError("p0 must be (%d,) or (S, %d), got %r" % (din, din, np.shape(p0)))
+        M, S = dat.shape[0], starts.shape[0]
+        w = self._band_weights(nb, sigma, flow, fhigh)
+        self._set_record(st, dat[0], w)
+        x0 = np.ascontiguousarray(np.tile(starts, (M, 1)))
+        r = st.fit(x0, model.precision, flags, data=dat, max_iter=max_iter, fisher=return_fisher)
+        xh = r["x_hat"].reshape(M, S, din)
+        lnl = r["lnl"].reshape(M, S)
+        status = r["status"].reshape(M, S)
+        F = r["fisher"].reshape(M, S, din, din) if return_fisher else None
+        if not return_all:
+            best = np.argmax(np.where(np.isnan(lnl), -np.inf, lnl), axis=1)  # (first maximum: the lowest start index)
+            i = np.arange(M)
+            xh, lnl, status = xh[i, best], lnl[i, best], status[i, best]
+            F = F[i, best] if F is not None else None
+        if one:
+            xh, lnl, status = xh[0], lnl[0], status[0]
+            F = F[0] if F is not None else None
+        return FitResult(xh, lnl, status, F)
 
     def save(self):
         raise NotImplementedError("Not implemented yet.")

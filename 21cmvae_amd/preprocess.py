@@ -98,6 +98,20 @@ class ParamStats:
         return _cached("par", params_train, cls)
 
 
+def par_untransform(u, params_train):
+    """Inverse of :func:`par_transform` (not in the reference), float64: lo + (u + 1) span / 2, then 10^ for the
+    LOG_COLUMNS.  A log column's lower bound maps to 10^lo -- for fx the zero floor 1e-6 when the training set holds
+    fx = 0, never 0 itself.  1-D input becomes one row, as in par_transform."""
+    q = np.array(u, dtype=np.float64, ndmin=2)
+    st = ParamStats.of(params_train)
+    span = st.hi - st.lo
+    out = st.lo + (q + 1.0) * span / 2.0
+    for j in range(out.shape[1]):
+        if st.log_mask[j]:
+            out[:, j] = 10.0 ** out[:, j]
+    return out
+
+
 def _to_log_space(p):
     """log10 of the LOG_COLUMNS, taken IN THE DTYPE OF THE INPUT for floating arrays, as the reference
     does (preprocess.py:74-78 / 89-93: `.copy()` of the columns, the floor written into that copy,

@@ -198,6 +198,39 @@ int v21_mlp_loglike_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, 
 int v21_route_jacobian(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int* route);
 int v21_mlp_last_jac_route(v21_mlp* mlp, int* route, long long counts[4]);
 
+/* ---- Fisher matrices and batched maximum-likelihood fits, on the Jacobian of the block above.
+ *   v21_mlp_fisher[_dev]  fisher[n, i, j] = sum_k w_k jac[n, i, k] jac[n, j, k], (n, in_dim, in_dim) float32, exactly
+ *     symmetric, with w the inverse variances of the likelihood record (v21_mlp_set_likelihood, required) and jac as
+ *     v21_mlp_jacobian computes it for the same flags (raw units with V21_FWD_IN_TRANSFORM); lnl / grad (nullable) as
+ *     v21_mlp_loglike -- the record's data is read only for them.  in_dim <= 15 (V21_ERR_UNSUPPORTED otherwise).
+ *   v21_mlp_fit[_dev]     per row, a projected Levenberg-Marquardt maximisation of ln L in the transformed coordinates
+ *     u = par_transform(x) in [-1, 1]^in_dim, the training box of the input transform (required: V21_ERR_STATE
+ *     without it; in_dim <= 8).  x0: start rows in raw units, clamped into the box.  Iteration: evaluate ln L, its
+ *     gradient g and Fisher matrix F at the proposal; accept it if ln L rose (the start always), lambda /= 10 (>= 1e-12),
+ *     else lambda *= 10; solve (F + lambda diag(max(F_ii, tiny))) delta = g (float64 Cholesky); proposal =
+ *     clamp(u + delta, -1, 1).  status[n]: 1 the projected step is <= xtol, 2 lambda > 1e12 (no improving step),
+ *     3 no information (every F_ii == 0: the start is kept), 0 max_iter proposals evaluated.  lnl: ln L at x_hat, never
+ *     below lnl_start (ln L at the clamped start).  x_hat: the accepted point, mapped back in float64
+ *     (lo + (u + 1) span / 2, then 10^ for a log column: a log column's lower bound comes back as 10^lo, e.g. the fx
+ *     zero floor, not 0), in x0's dtype (_dev: float32, pitch in_dim).  fisher (nullable): v21_mlp_fisher at x_hat in raw
+ *     units.  data: NULL = the record's data for every row, else (n_data, out_dim) float32 with n % n_data == 0, row n
+ *     fitting data row n / (n / n_data); the record's inverse variances weigh every row.  opts: v21_types.h.
+ *     (data non-NULL with n_data < 1, or n % n_data != 0: V21_ERR_ARG.)  lnl_start, fisher and status are nullable.
+ *     The evaluations take the Jacobian's route for the flags given (V21_FWD_IN_TRANSFORM is implied); rows are
+ *     independent of each other and of how a call is chunked.  v21_mlp_last_jac_route counts each call of these entries
+ *     once per Fisher evaluation it asks for: a fisher call once, a fit once for its iterations and once more for the
+ *     Fisher matrix at x_hat when that is asked for (never per iteration or per chunk).
+ * The host forms work in chunks of 8,192 rows and return when the results are in place; the _dev forms are
+ * asynchronous on the context's stream except that a fit reads its running-row count every check_every iterations. */
+int v21_mlp_fisher(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, float* fisher, float* lnl, float* grad, int precision, int flags);
+int v21_mlp_fisher_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, float* d_fisher, float* d_lnl, float* d_grad,
+                       int precision, int flags);
+int v21_mlp_fit(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_fit_opts* opts,
+                void* x_hat, float* lnl, float* lnl_start, float* fisher, int32_t* status, int precision, int flags);
+int v21_mlp_fit_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                    const v21_fit_opts* opts, float* d_x_hat, float* d_lnl, float* d_lnl_start, float* d_fisher, int32_t* d_status,
+                    int precision, int flags);
+
 /* ---- trainer: replaces Model.compile + Model.fit (emulator.py:369-378, :739-747,
  * :756-764; optimizer/loss from notebooks/Training.ipynb cells 4 and 10). ------- */
 typedef struct {

@@ -10,4 +10,11 @@ typedef struct {
   double lo[8];     /* column minimum of the log-transformed TRAINING parameters (preprocess.py:100-101) */
   double span[8];   /* maximum - minimum (preprocess.py:106) */
 } v21_affine_in;
+/* options of v21_mlp_fit[_dev] (a NULL pointer: the defaults in brackets) */
+typedef struct {
+  int max_iter;     /* [50] LM proposals evaluated after the start; 0: the clamped start is the result */
+  double lambda0;   /* [1e-3] initial damping */
+  double xtol;      /* [1e-7] converged when the projected step's largest |component| (u units) is <= xtol */
+  int check_every;  /* [8] the host reads the count of running rows every check_every iterations */
+} v21_fit_opts;
 #endif /* V21_TYPES_H */
