@@ -146,12 +146,7 @@ extern "C" int v21_mlp_destroy(v21_mlp* m) {
   if (m->d_xs) hipFree(m->d_xs);
   if (m->d_xs64) hipFree(m->d_xs64);
   if (m->d_ys) hipFree(m->d_ys);
-  for (float* p : {m->d_lk_data, m->d_lk_w, m->d_lk_ws, m->d_jxt, m->d_jfac, m->d_jy, m->d_jout}) if (p) hipFree(p);
-  if (m->d_jx64) hipFree(m->d_jx64);
-  for (float* p : {m->d_fF, m->d_fl, m->d_fg, m->d_fdata, m->d_fout}) if (p) hipFree(p);
-  if (m->d_fit) hipFree(m->d_fit);
-  if (m->d_fit_cnt) hipFree(m->d_fit_cnt);
-  delete m;
+  delete m;  // (and with it the DevBuf members)
   return V21_OK;
 }
 extern "C" int v21_mlp_num_params(const v21_mlp* m, size_t* n) {

@@ -8,11 +8,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -96,6 +98,31 @@ struct v21_ctx {
 };
 int use(v21_ctx* c);
 
+// a grow-only device allocation: reserve(bytes) reallocates only to grow (freeing first; capacity 0 if the allocation
+// fails), release() frees, and so does the destructor (v21_mlp_destroy makes the device current before it deletes)
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  int reserve(size_t bytes) {
+    if (cap >= bytes) return V21_OK;
+    if (p) { HIPCHK(hipFree(p)); p = nullptr; }
+    cap = 0;
+    HIPCHK(hipMalloc(&p, bytes));
+    cap = bytes;
+    return V21_OK;
+  }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
 // ---- dense stack (api_forward.hip)
 struct v21_mlp {
   v21_ctx* ctx = nullptr;
@@ -145,39 +172,48 @@ struct v21_mlp {
   unsigned long long* clk_stamps = nullptr;  // set for the duration of v21_debug_forward_clocked
   // width of layer l's Dense output: dims[l+1], or 2*dims[l+1] = [z_mean | z_log_var] for V21_ACT_GAUSS
   int nw(int l) const { return act[l] == V21_ACT_GAUSS ? 2 * dims[l + 1] : dims[l + 1]; }
-  // parameter Jacobian / log-likelihood (api_jacobian.hip): the likelihood record (d, 1 / sigma^2; out_dim floats
-  // each), staging, and the route of the last call (routes.h: JacRoute)
-  float *d_lk_data = nullptr, *d_lk_w = nullptr;
-  float* d_lk_ws = nullptr;  // the fused route's likelihood: y and jac of one slice before they are reduced
-  long long lk_ws_rows = 0;
+  // parameter Jacobian, log-likelihood, Fisher matrices and fits (api_jacobian.hip, api_fit.hip): the likelihood record
+  // (d, 1 / sigma^2; out_dim floats each) and the route of the last call (routes.h: JacRoute).  Buffers, grown on demand:
+  DevBuf lk_data, lk_w;
+  DevBuf lk_ws;      // y and jac of one kLkSlice slice of rows before they are reduced
+  DevBuf jxt, jfac;  // transformed rows and their factors, pitch in_dim (jac_prep)
+  DevBuf hin, hout;  // the host forms' chunk: its raw rows (float32 / float64; a fit's x_hat) and its results
+  DevBuf fit, fF, fl, fg, fit_cnt, fdata;  // fit state, F / ln L / gradient of its rows, running rows per iteration, data
   bool has_lk = false;
-  float *d_jxt = nullptr, *d_jfac = nullptr, *d_jy = nullptr, *d_jout = nullptr;
-  double* d_jx64 = nullptr;
-  long long jstage_rows = 0, jhost_rows = 0;  // rows of d_jxt / d_jfac; of d_jx64 / d_jy / d_jout (host API chunks)
   int last_jac_route = 0;
   long long jac_route_count[4] = {0, 0, 0, 0};
-  // Fisher matrices and fits (api_fit.hip): per-row fit state, the evaluation's results (F, ln L, gradient), the
-  // active-row count per iteration, and the host API's staging of results (rows of each)
-  void* d_fit = nullptr;
-  float *d_fF = nullptr, *d_fl = nullptr, *d_fg = nullptr;
-  long long fit_rows = 0;
-  int* d_fit_cnt = nullptr;
-  int fit_cnt_cap = 0;
-  float *d_fdata = nullptr, *d_fout = nullptr;
-  long long fdata_rows = 0, fout_rows = 0;
 };
 // api_forward.hip: fused_fwd's packed weight stream of this stack (built on first use)
 int mlp_fused_stream(v21_mlp* m, int prec, const unsigned char** stream);
-// api_jacobian.hip, shared with api_fit.hip: staging of transformed rows and factors (d_jxt / d_jfac, pitch in_dim) and of
-// the host API's chunks (kJacHostChunk rows), argument checks, the likelihood workspace (kLkSlice rows per slice) and
-// the input transform of device rows and one Jacobian-mode evaluation on a given route
+// api_jacobian.hip, shared with api_fit.hip.  The host forms work in chunks of kJacHostChunk rows; the likelihood
+// workspace holds kLkSlice rows.
 constexpr long long kJacHostChunk = 8192, kLkSlice = 16384;
-int jac_stage(v21_mlp* m, long long rows);
-int jac_stage_host(v21_mlp* m, long long rows);
-int jac_check(v21_mlp* m, int precision, int flags, bool like);
-int lk_ws_reserve(v21_mlp* m, long long rows);
-int jac_prep_rows(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n, int tin);
-int jac_eval_rows(v21_mlp* m, int route, const float* xt, const float* fac, long long n, float* y, float* jac, int prec, int flags);
+constexpr long long kNoPitch = LLONG_MAX;  // jac_args: the pitch of rows a call does not have
+// what an entry point is checked for beyond its arguments: its in_dim limit, whether it reads the likelihood record,
+// and whether it is a fit (input transform required, state checked even for n == 0)
+struct JacEntry { const char* name; int max_in; bool like, fit; };
+// the checks of all eight entry points: the pointers they require (ptrs), n >= 0, pitches (ldx, ldy; host rows:
+// kNoPitch) and x_dtype, the entry's in_dim limit, then -- from here on only for n > 0, except for a fit -- precision and
+// the state the call needs.  Leaves flags with their defined bits only and, for n > 0, the context's device current.
+int jac_args(v21_mlp* m, bool ptrs, long long n, long long ldx, long long ldy, int x_dtype, int precision, int& flags, const JacEntry& e);
+// the route of one entry-point call (on ldy: a _dev Jacobian's y pitch, else out_dim), counted once
+int jac_route(v21_mlp* m, int flags, long long ldy);
+// device rows (float32 / float64, pitch ld) -> m->jxt / jfac, grown to n rows, on the context's stream
+int jac_prep(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n, int tin);
+// Jacobian mode of `route` on the prepped rows into the likelihood workspace, slice by slice, each slice then reduced
+// there by reduce(y, jac, r0, rows) (y: nullptr unless want_y; r0: the slice's first row)
+int jac_slices(v21_mlp* m, int route, long long n, bool want_y, int prec, int flags,
+               const std::function<int(const float*, const float*, long long, long long)>& reduce);
+// a host form's rows, chunk by chunk: upload (m->hin) and prep them, run(r0, rows, out) on the chunk (out: m->hout of
+// out_floats per row, and never fewer than a Jacobian row's y and jac, so that no host form regrows what another left),
+// then sync
+int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, long long out_floats,
+               const std::function<int(long long, long long, float*)>& run);
+// device -> host on the context's stream (the host forms' results; jac_chunks syncs)
+static inline int to_host(v21_mlp* m, void* dst, const void* src, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->ctx->stream));
+  return V21_OK;
+}
 
 // ---- trainer (api_trainer.hip)
 struct v21_trainer {

@@ -310,6 +310,11 @@ def test_fit_data_count_checked_and_routes_counted(ctx):
     assert counts() - c0 == 2 and st.last_jac_route()[0] == "fused"
     assert np.array_equal(r["fisher"], st.fisher(r["x_hat"], "f16", flags))
     assert counts() - c0 == 3
+    # so do the Jacobian and the log-likelihood: once per call, not once per host chunk
+    for call in (st.jacobian, st.loglike):
+        c0 = counts()
+        call(big, "f16", flags)
+        assert counts() - c0 == 1, call.__name__
     st.set_likelihood(None, None)
 
 

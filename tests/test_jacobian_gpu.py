@@ -148,6 +148,93 @@ def test_guard_region_and_device_entry_points(ctx):
         st.set_likelihood(None, None)
 
 
+@pytest.mark.parametrize("n", [8193, 16385])
+@pytest.mark.parametrize("name,prec", [("D1", "f16"), ("NB", "f32")])
+def test_host_and_device_entry_points_agree(ctx, name, prec, n):
+    """each host form (chunks of 8,192 rows) equals its _dev form (rows of pitch in_dim + 3, one call) bit for bit across
+    a host chunk and a 16,384-row workspace slice, on a fused and a generic stack; every call counts its route once and
+    the bytes past row n of the _dev outputs stay as they were"""
+    nat = pkg("_native")
+    st, dims, act, *_ = stack_of(ctx, name)
+    din, dout = dims[0], dims[-1]
+    flags = nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM
+    route = "fused" if name == "D1" else "generic"
+    rng = np.random.default_rng(7)
+    st.set_likelihood(rng.normal(size=dout).astype(np.float32), np.where(rng.uniform(size=dout) < 0.2, 0, 4.0).astype(np.float32))
+    x = rows_for(dims, n, 11, np.float32)
+    xp = np.zeros((n, din + 3), np.float32)
+    xp[:, :din] = x
+    g = 64
+    sizes = {"x": xp.nbytes, "y": (n + g) * dout, "jac": (n + g) * din * dout, "lnl": n + g, "grad": (n + g) * din,
+             "F": (n + g) * din * din, "xh": (n + g) * din, "lnl0": n + g, "status": n + g}
+    d = {}
+    counts = lambda: st.last_jac_route()[1].get(route, 0)
+
+    def out(key, shape, dtype=np.float32):
+        a = np.empty(shape, dtype)
+        ctx.d2h(a, d[key])
+        return a
+
+    def poisoned(a):
+        return np.all(a[n:].view(np.uint32) == np.frombuffer(b"\x7f\x7f\x7f\x7f", np.uint32)[0])
+
+    try:
+        for k, v in sizes.items():
+            d[k] = ctx.malloc(v if k == "x" else v * 4)
+            if k != "x":
+                ctx.memset(d[k], 0x7F, v * 4)
+        ctx.h2d(d["x"], xp)
+        c0 = counts()
+        st.jacobian_dev(d["x"], din + 3, n, d["y"], dout, d["jac"], prec, flags)
+        st.loglike_dev(d["x"], din + 3, n, d["lnl"], d["grad"], prec, flags)
+        ctx.sync()
+        assert counts() - c0 == 2
+        y, j = out("y", (n + g, dout)), out("jac", (n + g, din, dout))
+        lnl, gr = out("lnl", n + g), out("grad", (n + g, din))
+        for a in (y, j, lnl, gr):
+            assert poisoned(a)
+        c0 = counts()
+        yh, jh = st.jacobian(x, prec, flags, return_outputs=True)
+        assert np.array_equal(yh, y[:n]) and np.array_equal(jh, j[:n])
+        lh, gh = st.loglike(x, prec, flags)
+        assert np.array_equal(lh, lnl[:n]) and np.array_equal(gh, gr[:n])
+        assert counts() - c0 == 2
+        for k in ("lnl", "grad"):
+            ctx.memset(d[k], 0x7F, sizes[k] * 4)
+        c0 = counts()
+        st.fisher_dev(d["x"], din + 3, n, d["F"], d["lnl"], d["grad"], prec, flags)
+        ctx.sync()
+        assert counts() - c0 == 1
+        F, lnl, gr = out("F", (n + g, din, din)), out("lnl", n + g), out("grad", (n + g, din))
+        for a in (F, lnl, gr):
+            assert poisoned(a)
+        c0 = counts()
+        Fh, lh, gh = st.fisher(x, prec, flags, lnl=True, grad=True)
+        assert counts() - c0 == 1
+        assert np.array_equal(Fh, F[:n]) and np.array_equal(lh, lnl[:n]) and np.array_equal(gh, gr[:n])
+        for k in ("F", "lnl"):
+            ctx.memset(d[k], 0x7F, sizes[k] * 4)
+        c0 = counts()
+        st.fit_dev(d["x"], din + 3, n, None, 0, d["xh"], d["lnl"], d["lnl0"], d["F"], d["status"], prec, flags, max_iter=5,
+                   check_every=2)
+        ctx.sync()
+        assert counts() - c0 == 2
+        xh, lnl, l0 = out("xh", (n + g, din)), out("lnl", n + g), out("lnl0", n + g)
+        F, ss = out("F", (n + g, din, din)), out("status", n + g, np.int32)
+        for a in (xh, lnl, l0, F, ss):
+            assert poisoned(a)
+        c0 = counts()
+        r = st.fit(x, prec, flags, max_iter=5, check_every=2, fisher=True)
+        assert counts() - c0 == 2
+        for key, a in (("x_hat", xh), ("lnl", lnl), ("lnl_start", l0), ("fisher", F), ("status", ss)):
+            assert np.array_equal(r[key].view(np.uint8), a[:n].view(np.uint8)), key
+        assert np.all(np.isfinite(r["lnl"])) and np.all(r["lnl"] >= r["lnl_start"])
+    finally:
+        for p in d.values():
+            ctx.free(p)
+        st.set_likelihood(None, None)
+
+
 @pytest.mark.parametrize("prec", ["f32", "f16", "bf16"])
 @pytest.mark.parametrize("name", ["D1", "S3", "S4", "NB"])
 def test_loglike(ctx, name, prec):
