@@ -262,7 +262,6 @@ struct v21_trainer {
   int* d_jobs = nullptr;  // train_chain32s.h: C32sJob rows
   int c32_frags(int d) const { return chain32s ? chain32s_frags(d) : chain32_frags(d); }
   int c32_tiles(int d) const { return chain32s ? (d + 63) / 64 : (d + 31) / 32; }
-  int loss_slot_pending = -2;  // f32 chain step on one rank: the Adam launch publishes the loss (-2: nothing pending)
   void *d_fw = nullptr, *d_bw = nullptr;
   long long fw_bytes = 0, bw_bytes = 0;
   std::vector<long long> fw_off, bw_off;  // element offsets per layer
@@ -322,10 +321,9 @@ static inline int zalloc(float** p, size_t nfloat, hipStream_t st) {
 // one grouped launch of the latency-oriented NT GEMM (gemm_nt.h); instantiated per unit and group type
 template <class GROUP>
 static int launch_nt(int prec, GROUP& grp, hipStream_t st) {
-  // 64x64 workgroup tiles once the problems are large enough to fill the chip with them
-  long long work = 0;
+  long long work = 0;  // (routes.h: nt_tile)
   for (int i = 0; i < grp.count; ++i) work += (long long)((grp.p[i].M + 63) / 64) * ((grp.p[i].N + 63) / 64) * std::max(1, grp.p[i].nz);
-  const int T = work >= 192 ? 2 : 1;
+  const int T = nt_tile(work) / 32;
   int blocks = 0;
   for (int i = 0; i < grp.count; ++i) {
     NtArgs& g = grp.p[i];
@@ -335,9 +333,7 @@ static int launch_nt(int prec, GROUP& grp, hipStream_t st) {
     if (g.a_scale == 0.f) g.a_scale = 1.f;
     if (g.b_scale == 0.f) g.b_scale = 1.f;
     if (g.out_scale == 0.f) g.out_scale = 1.f;
-    if (g.nz == 1) { g.k_chunk = g.K > 0 ? g.K : 1; g.slab_stride = 0; }
-    // (kNtMaxKPerWg = 512 is the range a workgroup keeps in flight at once -- the split of the weight gradient's batch
-    //  contraction aims at it; a longer range, e.g. a layer fed by 600 features, is walked in rounds by the same loop)
+    if (g.nz == 1) { g.k_chunk = g.K > 0 ? g.K : 1; g.slab_stride = 0; }  // (routes.h: nt_slices)
     grp.first[i] = blocks;
     blocks += g.nx * g.ny * g.nz;
   }
@@ -356,17 +352,18 @@ static int launch_nt(int prec, GROUP& grp, hipStream_t st) {
   return V21_OK;
 }
 float adam_alpha(const v21_adam& a, long long t);  // api_trainer.hip
-AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt = false);  // api_trainer.hip
+// Where a step's batch loss goes.  `slot` >= 0: entry `slot` of the epoch's loss table (v21_trainer::d_steploss), written by
+// the kernel that publishes the loss -- a device-to-device copy per step would be a launch of its own.  Otherwise the step
+// ends by copying the arena's loss slot (d_g[P]) to `out`, if there is one.
+struct StepLoss { float* out; int slot; };
+AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt = false, const StepLoss* pub = nullptr);  // api_trainer.hip
 int chain_attr(int prec);  // api_trainer.hip
 ChainModel chain_model(v21_trainer* t);  // api_trainer.hip
 ChainModel chain_model32(v21_trainer* t);  // api_trainer.hip
 int chain_prefetchers(int ncons, int models);  // api_trainer.hip
 ChainStep chain_step(const float* x, long long ldx, const float* y, long long ldy, const float* rw, const int* d_idx, long long first, int rows, int brows, int dout, const v21_trainer* vae = nullptr, long long row0 = 0);  // api_trainer.hip
 void destroy_graphs(v21_trainer* t);  // api_trainer.hip
-void dw16_problems(v21_trainer* t, int rows, int brows, int* nslice_out, std::vector<Dw16Args>& probs, float* loss_out2 = nullptr);  // api_trainer.hip
-// every entry of an epoch's row table names a row of the training set (an entry outside it is a GPU memory fault in the
-// gather of whichever kernel takes the step: checked on the host, one pass over n ints per epoch)
-int check_row_table(const int32_t* perm, long long n);
+void dw16_problems(v21_trainer* t, int rows, int brows, int* nslice_out, std::vector<Dw16Args>& probs);  // api_trainer.hip
 int ensure_copies(v21_trainer* t, bool need_nt = true);  // api_trainer.hip
 int gather_batch(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy_src, const float* rw, const int* d_idx, long long first, int rows);  // api_trainer.hip
 float grad_opscale(int brows, int dout);  // api_trainer.hip
@@ -377,12 +374,53 @@ int launch_dw32_group(const std::vector<v21_trainer*>& trs, const Dw32Model* d_t
 int launch_dw_adam_group(const std::vector<v21_trainer*>& tr, const DwAdamModel* d_tab, const std::vector<DwAdamModel>& h_tab, int rows, int brows, long long slot, hipStream_t st);  // api_trainer.hip
 void launch_joint32_kernel(int rpw, bool gauss, dim3 grid, dim3 block, hipStream_t st, const ChainModel* tab, const ChainStep& sa, const ChainStep& sb);  // api_trainer.hip
 void launch_joint_kernel(int prec, bool gauss, dim3 grid, dim3 block, hipStream_t st, const ChainModel* tab, const ChainStep& sa, const ChainStep& sb);  // api_trainer.hip
-int reduce_and_update(v21_trainer* t, bool chain_copies, int fold, bool exchanged = false);  // api_trainer.hip
+// exchange (unless `exchanged`), Adam, packed copies; `pub`: this Adam pass publishes the loss (api_trainer.hip)
+int reduce_and_update(v21_trainer* t, int fold, bool exchanged = false, const StepLoss* pub = nullptr);
+void weights_updated(v21_trainer* t, bool nt_ok);  // api_trainer.hip: every copy but the updater's own is stale
+int step_tail(v21_trainer* t, const StepLoss& loss);  // api_trainer.hip: the loss copied out (slot < 0), weights_updated
+int chain32_update(v21_trainer* t, int rows, float* loss_out);  // api_trainer.hip: the update of an f32 step whose chain ran
 // api_base.hip: the all-reduce of d_buf[0, n) on a stream of the caller's choice (RCCL: enqueued there; host-staged
 // transport: blocking, staged through that stream; null transport / one rank: nothing)
 int comm_allreduce_on(v21_ctx* c, float* d_buf, size_t n, hipStream_t st);
 int refresh_dw32_table(const std::vector<v21_trainer*>& trs, Dw32Model* d_tab, std::vector<Dw32Model>& h_tab, int* max_blocks, bool* ok, hipStream_t st);  // api_sweep.hip
 int refresh_dw_adam_table(const std::vector<v21_trainer*>& tr, DwAdamModel** d_tab, std::vector<DwAdamModel>& h_tab, hipStream_t st);  // api_trainer.hip
-int train_on_rows_chain32(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy, const float* rw, const int* d_idx, long long first, int rows, int brows, float* loss_out, long long row0, bool chain_done = false /* the joint step: the chain of this model ran in the joint launch */);  // api_trainer.hip
 int launch_nt_many(int prec, std::vector<NtArgs>& probs, hipStream_t st);  // api_trainer.hip
 void launch_chain_forward_mode(int prec, dim3 grid, dim3 block, hipStream_t st, const ChainArgs& a);  // api_trainer.hip
+
+// ---- pieces of a step shared by the trainer, the sweep and the joint step (api_trainer.hip)
+int zero_grad(v21_trainer* t);                 // arena + loss slot = 0: a rank without rows in this step
+int reduce_slabs(v21_trainer* t, int nslice);  // the nslice split-K slabs summed into the arena
+// layer l's NT problems: forward (A: its input rows), [dW; db] = [H^T; 1^T] dZ over the slices `sl`, dH = dZ W^T masked
+NtArgs nt_forward(const v21_trainer* t, int l, const float* A, int rows, bool want_t);
+NtArgs nt_dw(const v21_trainer* t, int l, const float* A, const float* B, int rows, NtSlices sl, float gs);
+NtArgs nt_dx(const v21_trainer* t, int l, const float* A, int rows, float gs);
+// every layer's f32 gradient + Adam in one launch (dw_adam32.h), less what changes per step (K, alpha, replay, slot: -1);
+// returns the launch's workgroups
+int dw32_model(const v21_trainer* t, int tile, Dw32Model& md);
+
+// a device table built on the host, uploaded only when it changed (after the stream drained: a step in flight may read it)
+template <class T>
+static int upload_if_changed(const std::vector<T>& tab, std::vector<T>& host, T* dev, hipStream_t st) {
+  if (tab.size() == host.size() && memcmp(tab.data(), host.data(), tab.size() * sizeof(T)) == 0) return V21_OK;
+  HIPCHK(hipStreamSynchronize(st));
+  host = tab;
+  HIPCHK(hipMemcpyAsync(dev, host.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return V21_OK;
+}
+
+// ---- epochs (api_trainer.hip): the row table checked and uploaded (*d_idx: nullptr without one); the loss table grown
+int upload_rows(v21_trainer* t, const int32_t* perm, const int** d_idx);
+int ensure_steploss(v21_trainer* t, long long cap);
+struct EpochBatch { long long first, lo; int brows, rows; };  // global batch [first, first + brows), this rank's [lo, lo + rows)
+static inline EpochBatch epoch_batch(const v21_ctx* c, long long n, int batch, long long s) {
+  EpochBatch b;
+  b.first = s * batch;
+  b.brows = (int)std::min<long long>(batch, n - b.first);
+  b.lo = b.first + (long long)b.brows * c->rank / c->nranks;
+  b.rows = (int)(b.first + (long long)b.brows * (c->rank + 1) / c->nranks - b.lo);
+  return b;
+}
+// loss[k]: trainer k's per-step losses summed over n rows (Keras' epoch loss) / its fixed-point validation sum, cleared
+int epoch_losses(const std::vector<v21_trainer*>& trs, long long steps, long long n, double* loss);
+int read_tickets(const std::vector<v21_trainer*>& trs, long long n, double* loss);

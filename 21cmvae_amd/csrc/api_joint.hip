@@ -58,6 +58,15 @@ extern "C" int v21_joint_destroy(v21_joint* j) {
   delete j;
   return V21_OK;
 }
+// the chain table of the joint launches: both models, the autoencoder's latent captured; `sample` = 0: no noise drawn
+static std::vector<ChainModel> joint_table(const v21_joint* j, int sample) {
+  std::vector<ChainModel> tab = j->f32 ? std::vector<ChainModel>{chain_model32(j->ae), chain_model32(j->em)}
+                                       : std::vector<ChainModel>{chain_model(j->ae), chain_model(j->em)};
+  tab[0].zcap_layer = j->latent_layer;
+  if (j->f32) tab[0].stamps = tab[1].stamps = nullptr;
+  if (!sample) tab[0].sample = 0;
+  return tab;
+}
 // one epoch: the autoencoder trainer holds the signals (set_data(0, signals, NULL, w)), the emulator trainer the
 // parameters of the SAME rows (set_data(0, params, any (n, latent) array, w_mse)); losses[0] = autoencoder,
 // losses[1] = emulator (Keras epoch losses)
@@ -69,40 +78,13 @@ extern "C" int v21_joint_run_epoch(v21_joint* j, const int32_t* perm, int batch,
   CHK(use(ta->ctx));
   hipStream_t st = ta->ctx->stream;
   const long long n = ta->n[0];
-  const int R = ta->ctx->nranks, rk = ta->ctx->rank;
+  const int R = ta->ctx->nranks;
   if (batch < 1 || (batch + R - 1) / R > ta->max_batch) return fail(V21_ERR_ARG, "per-rank batch %d not in [1, max_batch %d]", (batch + R - 1) / R, ta->max_batch);
   const int* d_idx = nullptr;
-  if (perm) {
-    CHK(check_row_table(perm, n));
-    if (ta->perm_cap < n) {
-      if (ta->d_perm) HIPCHK(hipFree(ta->d_perm));
-      HIPCHK(hipMalloc((void**)&ta->d_perm, (size_t)n * sizeof(int)));
-      ta->perm_cap = n;
-    }
-    HIPCHK(hipMemcpyAsync(ta->d_perm, perm, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    d_idx = ta->d_perm;
-  }
+  CHK(upload_rows(ta, perm, &d_idx));
   const long long steps = (n + batch - 1) / batch;
-  for (v21_trainer* t : {ta, te})
-    if (t->steploss_cap < steps) {
-      HIPCHK(hipStreamSynchronize(st));
-      destroy_graphs(t);
-      if (t->d_steploss) HIPCHK(hipFree(t->d_steploss));
-      HIPCHK(hipMalloc((void**)&t->d_steploss, (size_t)steps * sizeof(float)));
-      t->steploss_cap = steps;
-    }
-  {
-    std::vector<ChainModel> tab = j->f32 ? std::vector<ChainModel>{chain_model32(ta), chain_model32(te)}
-                                         : std::vector<ChainModel>{chain_model(ta), chain_model(te)};
-    tab[0].zcap_layer = j->latent_layer;
-    if (j->f32) tab[0].stamps = tab[1].stamps = nullptr;
-    if (tab.size() != j->h_tab.size() || memcmp(tab.data(), j->h_tab.data(), 2 * sizeof(ChainModel)) != 0) {
-      HIPCHK(hipStreamSynchronize(st));
-      j->h_tab = tab;
-      HIPCHK(hipMemcpyAsync(j->d_tab, j->h_tab.data(), 2 * sizeof(ChainModel), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-  }
+  for (v21_trainer* t : {ta, te}) CHK(ensure_steploss(t, steps));
+  CHK(upload_if_changed(joint_table(j, 1), j->h_tab, j->d_tab, st));
   if (R == 1 && !j->f32) CHK(refresh_dw_adam_table({ta, te}, &j->d_dwadam, j->h_dwadam, st));
   bool group32 = j->f32 && R == 1 && batch <= kDw32MaxRows;
   int max_blocks32 = 0;
@@ -113,48 +95,39 @@ extern "C" int v21_joint_run_epoch(v21_joint* j, const int32_t* perm, int batch,
   CHK(chain_attr(ta->prec));
   const int dsig = ta->mlp->dims[0], dpar = te->mlp->dims[0], dlat = te->mlp->dims[te->mlp->L];
   for (long long s = 0; s < steps; ++s) {
-    const long long first = s * batch;
-    const int brows = (int)std::min<long long>(batch, n - first);  // rows of the global batch
-    const long long lo = first + (long long)brows * rk / R, hi = first + (long long)brows * (rk + 1) / R;
-    const int rows = (int)(hi - lo);                                // this rank's share (data parallel: SURVEY 8e)
+    const EpochBatch b = epoch_batch(ta->ctx, n, batch, s);  // this rank's share of the global batch (data parallel: SURVEY 8e)
+    const long long lo = b.lo, first = b.first;
+    const int rows = b.rows, brows = b.brows;
     for (v21_trainer* t : {ta, te}) CHK(ensure_copies(t, false));
-    if (j->f32) {
-      // the reference's arithmetic: one joint chain launch (train_chain32s_joint_kernel), then each model's gradients and
-      // Adam as after a chain step of its own (train_on_rows_chain32: one launch on a single rank; the exchange otherwise)
-      if (rows > 0) {
-        ChainStep sa = chain_step(ta->d_x[0], dsig, nullptr, dsig, ta->d_rw[0], d_idx, lo, rows, brows, dsig, nullptr, lo - first);
-        ChainStep sb = chain_step(te->d_x[0], dpar, nullptr, dlat, te->d_rw[0], d_idx, lo, rows, brows, dlat, nullptr, lo - first);
-        sa.gs = sb.gs = 1.0f;
-        sa.step_off = (unsigned long long)s;  // the table holds the autoencoder's step counter as of the epoch's start (noise key)
-        sb.y_from_lds = 1;
-        const char* er = getenv("V21_C32S_ROWS");
-        const int force_rows = er ? atoi(er) : 0;
-        const int rpw = force_rows == 4 || force_rows == 8 ? force_rows : (2 * ((rows + 3) / 4) <= 256 ? 4 : 8);
-        sa.ncons = sb.ncons = ((rows + rpw - 1) / rpw + 7) / 8 * 8;
-        const dim3 grid(2 * sa.ncons), block(64 * kC32sWaves);
-        launch_joint32_kernel(rpw, ta->gl >= 0, grid, block, st, (const ChainModel*)j->d_tab, sa, sb);
-        HIPCHK(hipGetLastError());
-      }
-      if (group32) {
-        CHK(launch_dw32_group({ta, te}, j->d_dw32, rows, s, max_blocks32, st));
-        continue;
-      }
-      for (v21_trainer* t : {ta, te}) {
-        CHK(train_on_rows_chain32(t, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, rows, brows, t->d_steploss + s, 0, true));
-      }
-      continue;
-    }
-    if (rows > 0) {
+    if (rows > 0) {  // the reference's arithmetic: one joint chain launch (train_chain_joint_kernel / train_chain32s_joint_kernel)
       ChainStep sa = chain_step(ta->d_x[0], dsig, nullptr, dsig, ta->d_rw[0], d_idx, lo, rows, brows, dsig, nullptr, lo - first);
       ChainStep sb = chain_step(te->d_x[0], dpar, nullptr, dlat, te->d_rw[0], d_idx, lo, rows, brows, dlat, nullptr, lo - first);
       sa.step_off = (unsigned long long)s;  // the table holds the autoencoder's step counter as of the epoch's start (noise key)
       sb.y_from_lds = 1;
-      sa.ncons = sb.ncons = ((rows + 31) / 32 + 7) / 8 * 8;
-      sb.blk0 = sa.ncons;                   // the emulator's row blocks follow the autoencoder's in the grid
-      sa.npref = sb.npref = chain_prefetchers(2 * sa.ncons, 1);
-      const dim3 grid(2 * sa.ncons + 8 * sa.npref), block(64 * kChainWaves);
-      launch_joint_kernel(ta->prec, ta->gl >= 0, grid, block, st, (const ChainModel*)j->d_tab, sa, sb);
+      if (j->f32) {
+        sa.gs = sb.gs = 1.0f;
+        const char* er = getenv("V21_C32S_ROWS");
+        const int force_rows = er ? atoi(er) : 0;
+        const int rpw = force_rows == 4 || force_rows == 8 ? force_rows : (2 * ((rows + 3) / 4) <= 256 ? 4 : 8);
+        sa.ncons = sb.ncons = ((rows + rpw - 1) / rpw + 7) / 8 * 8;
+        launch_joint32_kernel(rpw, ta->gl >= 0, dim3(2 * sa.ncons), dim3(64 * kC32sWaves), st, (const ChainModel*)j->d_tab, sa, sb);
+      } else {
+        sa.ncons = sb.ncons = ((rows + 31) / 32 + 7) / 8 * 8;
+        sb.blk0 = sa.ncons;  // the emulator's row blocks follow the autoencoder's in the grid
+        sa.npref = sb.npref = chain_prefetchers(2 * sa.ncons, 1);
+        launch_joint_kernel(ta->prec, ta->gl >= 0, dim3(2 * sa.ncons + 8 * sa.npref), dim3(64 * kChainWaves), st,
+                            (const ChainModel*)j->d_tab, sa, sb);
+      }
       HIPCHK(hipGetLastError());
+    }
+    // then each model's gradients and Adam as after a chain step of its own: both models in one launch on a single rank
+    if (group32) {
+      CHK(launch_dw32_group({ta, te}, j->d_dw32, rows, s, max_blocks32, st));
+      continue;
+    }
+    if (j->f32) {  // (chain32_update: one launch on a single rank, the exchange otherwise)
+      for (v21_trainer* t : {ta, te}) CHK(chain32_update(t, rows, t->d_steploss + s));
+      continue;
     }
     if (R == 1) {
       CHK(launch_dw_adam_group({ta, te}, j->d_dwadam, j->h_dwadam, rows, brows, s, st));
@@ -163,37 +136,20 @@ extern "C" int v21_joint_run_epoch(v21_joint* j, const int32_t* perm, int batch,
     // data parallel: each model's weight gradients (this rank's rows), summed over the ranks, then Adam -- the same
     // exchange as a plain step (reduce_and_update: all-reduce, or reduce-scatter + sharded Adam + all-gather)
     for (v21_trainer* t : {ta, te}) {
-      int fold = 1;
       if (rows > 0) {
         int nslice = 1;
         std::vector<Dw16Args> probs;
         dw16_problems(t, rows, brows, &nslice, probs);
         CHK(launch_dw16(t->prec, probs, st));
-        if (nslice > 1) {
-          const long long n4 = ((long long)t->P + 3) / 4;
-          hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, t->d_g,
-                             (const float*)t->d_slab, nslice, (long long)t->P + 4, (long long)t->P);
-          HIPCHK(hipGetLastError());
-        }
+        if (nslice > 1) CHK(reduce_slabs(t, nslice));
       } else {
-        HIPCHK(hipMemsetAsync(t->d_g, 0, (t->P + 1) * sizeof(float), st));
+        CHK(zero_grad(t));
       }
-      CHK(reduce_and_update(t, true, fold));
-      HIPCHK(hipMemcpyAsync(t->d_steploss + s, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-      invalidate_streams(t->mlp);
-      t->mlp->wpad_ok = true;
+      CHK(reduce_and_update(t, 1));
+      CHK(step_tail(t, StepLoss{t->d_steploss + s, -1}));
     }
   }
-  std::vector<float> h((size_t)steps * 2);
-  HIPCHK(hipMemcpyAsync(h.data(), ta->d_steploss, (size_t)steps * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h.data() + steps, te->d_steploss, (size_t)steps * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (int k = 0; k < 2; ++k) {
-    double tot = 0.0;
-    for (long long i = 0; i < steps; ++i) tot += (double)h[(size_t)k * steps + i];
-    losses[k] = tot / (double)n;
-  }
-  return V21_OK;
+  return epoch_losses({ta, te}, steps, n, losses);
 }
 
 // validation of both models in ONE launch: the autoencoder's loss on its validation signals, and the emulator's loss on
@@ -209,19 +165,7 @@ extern "C" int v21_joint_eval(v21_joint* j, double* losses) {
   const long long n = ta->n[1];
   if (n > (1ll << 30)) return fail(V21_ERR_ARG, "too many rows for one validation launch");
   for (v21_trainer* t : {ta, te}) CHK(ensure_copies(t, false));
-  {
-    std::vector<ChainModel> tab = j->f32 ? std::vector<ChainModel>{chain_model32(ta), chain_model32(te)}
-                                         : std::vector<ChainModel>{chain_model(ta), chain_model(te)};
-    tab[0].zcap_layer = j->latent_layer;
-    if (j->f32) tab[0].stamps = tab[1].stamps = nullptr;
-    tab[0].sample = 0;  // evaluation passes draw no noise
-    if (tab.size() != j->h_tab.size() || memcmp(tab.data(), j->h_tab.data(), 2 * sizeof(ChainModel)) != 0) {
-      HIPCHK(hipStreamSynchronize(st));
-      j->h_tab = tab;
-      HIPCHK(hipMemcpyAsync(j->d_tab, j->h_tab.data(), 2 * sizeof(ChainModel), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-  }
+  CHK(upload_if_changed(joint_table(j, 0), j->h_tab, j->d_tab, st));  // (evaluation passes draw no noise)
   CHK(chain_attr(ta->prec));
   const int dsig = ta->mlp->dims[0], dpar = te->mlp->dims[0], dlat = te->mlp->dims[te->mlp->L];
   ChainStep sa = chain_step(ta->d_x[1], dsig, nullptr, dsig, ta->d_rw[1], nullptr, 0, (int)n, (int)n, dsig);
@@ -246,15 +190,5 @@ extern "C" int v21_joint_eval(v21_joint* j, double* losses) {
     launch_joint_kernel(ta->prec, ta->gl >= 0, grid, block, st, (const ChainModel*)j->d_tab, sa, sb);
   }
   HIPCHK(hipGetLastError());
-  long long acc[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(&acc[0], ta->d_ticket, sizeof(long long), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&acc[1], te->d_ticket, sizeof(long long), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemsetAsync(ta->d_ticket, 0, sizeof(long long), st));
-  HIPCHK(hipMemsetAsync(te->d_ticket, 0, sizeof(long long), st));
-  HIPCHK(hipStreamSynchronize(st));
-  losses[0] = (double)acc[0] * (1.0 / 4294967296.0) / (double)n;
-  losses[1] = (double)acc[1] * (1.0 / 4294967296.0) / (double)n;
-  return V21_OK;
+  return read_tickets({ta, te}, n, losses);
 }
-
-

@@ -90,7 +90,29 @@ extern "C" int v21_sweep_destroy(v21_sweep* s) {
   return V21_OK;
 }
 
-
+// the end of a sweep step that did not take a one-launch update: every model's gradients summed over the ranks (its loss
+// then into the epoch's table: a rank without rows takes part, so this is the only writer), Adam of every model in one
+// launch, the packed copies (nt_ok: the fp32 NT copies too)
+static int sweep_adam(v21_sweep* s, long long step_index, bool nt_ok) {
+  hipStream_t st = s->ctx->stream;
+  const int G = (int)s->tr.size();
+  AlphaGroup al{};
+  size_t maxP = 0;
+  for (int k = 0; k < G; ++k) {
+    v21_trainer* t = s->tr[k];
+    CHK(v21_comm_allreduce_f32(t->ctx, t->d_g, t->P + 1));
+    if (s->ctx->nranks > 1 && step_index >= 0)
+      HIPCHK(hipMemcpyAsync(t->d_steploss + step_index, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
+    t->iter += 1;
+    al.a[k] = adam_alpha(t->adam, t->iter);
+    maxP = std::max(maxP, t->P);
+  }
+  hipLaunchKernelGGL(adam_repack_group_kernel, dim3((unsigned)((maxP + 255) / 256), G), dim3(256), 0, st,
+                     (const AdamArgs*)s->d_adam, al);
+  HIPCHK(hipGetLastError());
+  for (v21_trainer* t : s->tr) weights_updated(t, nt_ok);
+  return V21_OK;
+}
 // one optimizer step of every model on the batch gathered into model 0's h[0]/ht[0]/yb/wb
 static int sweep_step(v21_sweep* s, const float* yb, long long ldy, int rows, int brows, long long step_index) {
   v21_trainer* t0 = s->tr[0];
@@ -102,19 +124,7 @@ static int sweep_step(v21_sweep* s, const float* yb, long long ldy, int rows, in
     std::vector<NtArgs> probs;
     for (int l = 0; l < L; ++l) {  // forward, layer l of every model
       probs.clear();
-      for (v21_trainer* t : s->tr) {
-        v21_mlp* m = t->mlp;
-        NtArgs g{};
-        g.A = l == 0 ? t0->d_h[0] : t->d_h[l]; g.lda = p16(m->dims[l]);
-        g.B = t->d_wt + t->wt_off[l]; g.ldb = p16(m->dims[l]);
-        g.C = t->d_h[l + 1]; g.ldc = p16(m->dims[l + 1]);
-        g.CT = l + 1 < L ? t->d_ht[l + 1] : nullptr; g.ldct = t->Bp;
-        g.M = rows; g.N = m->dims[l + 1]; g.K = m->dims[l];
-        g.bias = m->d_w + m->b_off[l];
-        g.ep = m->act[l] == V21_ACT_RELU ? NT_FWD_RELU : NT_FWD;
-        g.nz = 1;
-        probs.push_back(g);
-      }
+      for (v21_trainer* t : s->tr) probs.push_back(nt_forward(t, l, l == 0 ? t0->d_h[0] : t->d_h[l], rows, true));
       CHK(launch_nt_many(t0->prec, probs, st));
     }
     LossGroup lg{};
@@ -134,69 +144,22 @@ static int sweep_step(v21_sweep* s, const float* yb, long long ldy, int rows, in
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(sum_group_kernel, dim3(G), dim3(256), 0, st, sg);
     HIPCHK(hipGetLastError());
-    int nslice = (rows + kNtMaxKPerWg - 1) / kNtMaxKPerWg;
-    const int k_chunk = ((rows + nslice - 1) / nslice + 15) / 16 * 16;
-    nslice = (rows + k_chunk - 1) / k_chunk;
+    const NtSlices sl = nt_slices(rows, false);
     const float gs = grad_opscale(brows, dout);
     for (int l = L - 1; l >= 0; --l) {  // backward, layer l of every model: dW (and dX below the top)
       probs.clear();
       for (v21_trainer* t : s->tr) {
-        v21_mlp* m = t->mlp;
-        const int K = m->dims[l], N = m->dims[l + 1];
-        NtArgs g{};
-        g.A = l == 0 ? t0->d_ht[0] : t->d_ht[l]; g.lda = t->Bp;
-        g.B = t->d_dzt[l + 1]; g.ldb = t->Bp;
-        g.C = (nslice > 1 ? t->d_slab : t->d_g) + m->w_off[l]; g.ldc = N;
-        g.M = K + 1; g.N = N; g.K = rows;
-        g.ep = NT_DW; g.nz = nslice; g.k_chunk = k_chunk; g.slab_stride = (long long)t->P + 4;
-        g.b_scale = gs; g.out_scale = 1.0f / gs;
-        probs.push_back(g);
-        if (l > 0) {
-          NtArgs d{};
-          d.A = t->d_dz[l + 1]; d.lda = p16(N);
-          d.B = t->d_wp + t->wp_off[l]; d.ldb = p16(N);
-          d.C = t->d_dz[l]; d.ldc = p16(K);
-          d.CT = t->d_dzt[l]; d.ldct = t->Bp;
-          d.M = rows; d.N = K; d.K = N;
-          d.mask = t->d_h[l]; d.ldmask = p16(K);
-          d.ep = m->act[l - 1] == V21_ACT_RELU ? NT_DX_MASK : NT_DX;
-          d.nz = 1;
-          d.a_scale = gs; d.out_scale = 1.0f / gs;
-          probs.push_back(d);
-        }
+        probs.push_back(nt_dw(t, l, l == 0 ? t0->d_ht[0] : t->d_ht[l], t->d_dzt[l + 1], rows, sl, gs));
+        if (l > 0) probs.push_back(nt_dx(t, l, t->d_dz[l + 1], rows, gs));
       }
       CHK(launch_nt_many(t0->prec, probs, st));
     }
-    if (nslice > 1)
-      for (v21_trainer* t : s->tr) {
-        const long long n4 = ((long long)t->P + 3) / 4;
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, t->d_g,
-                           (const float*)t->d_slab, nslice, (long long)t->P + 4, (long long)t->P);
-        HIPCHK(hipGetLastError());
-      }
+    if (sl.nslice > 1)
+      for (v21_trainer* t : s->tr) CHK(reduce_slabs(t, sl.nslice));
   } else {
-    for (v21_trainer* t : s->tr) HIPCHK(hipMemsetAsync(t->d_g, 0, (t->P + 1) * sizeof(float), st));
+    for (v21_trainer* t : s->tr) CHK(zero_grad(t));
   }
-  AlphaGroup al{};
-  size_t maxP = 0;
-  for (int k = 0; k < G; ++k) {
-    v21_trainer* t = s->tr[k];
-    CHK(v21_comm_allreduce_f32(t->ctx, t->d_g, t->P + 1));
-    if (s->ctx->nranks > 1 && step_index >= 0)
-      HIPCHK(hipMemcpyAsync(t->d_steploss + step_index, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-    t->iter += 1;
-    al.a[k] = adam_alpha(t->adam, t->iter);
-    maxP = std::max(maxP, t->P);
-  }
-  hipLaunchKernelGGL(adam_repack_group_kernel, dim3((unsigned)((maxP + 255) / 256), G), dim3(256), 0, st,
-                     (const AdamArgs*)s->d_adam, al);
-  HIPCHK(hipGetLastError());
-  for (v21_trainer* t : s->tr) {
-    t->copies_ok = true; t->nt_ok = true;
-    invalidate_streams(t->mlp);
-    t->mlp->wpad_ok = true;
-  }
-  return V21_OK;
+  return sweep_adam(s, step_index, true);
 }
 
 // chain form of a sweep step: ONE launch carries every model's rows through forward, loss and the
@@ -220,6 +183,13 @@ static int sweep_chain_launch(v21_sweep* s, const ChainStep& csp, int g0, int g1
   HIPCHK(hipGetLastError());
   return V21_OK;
 }
+// two streams, the epoch's first step: half B starts after half A's chain launch -- the offset that makes B's chain meet
+// A's Adam launch, not A's chain
+static int sweep_offset(v21_sweep* s) {
+  HIPCHK(hipEventRecord(s->ev_off, s->ctx->stream));
+  HIPCHK(hipStreamWaitEvent(s->s2, s->ev_off, 0));
+  return V21_OK;
+}
 static int sweep_dwadam_launch(v21_sweep* s, int g0, int g1, int rows, int brows, long long step_index, hipStream_t st) {
   const std::vector<v21_trainer*> part(s->tr.begin() + g0, s->tr.begin() + g1);
   const std::vector<DwAdamModel> hpart(s->h_dwadam.begin() + g0, s->h_dwadam.begin() + g1);
@@ -239,10 +209,7 @@ static int sweep_step_chain(v21_sweep* s, const ChainStep& cs, int brows, long l
     if (s->two_streams) {  // one rank: half A on the context's stream, half B on the second one, B one launch behind A
       const int GA = (G + 1) / 2;
       CHK(sweep_chain_launch(s, csp, 0, GA, st));
-      if (step_index == 0) {  // (the offset that makes B's chain meet A's Adam launch, not A's chain)
-        HIPCHK(hipEventRecord(s->ev_off, st));
-        HIPCHK(hipStreamWaitEvent(s->s2, s->ev_off, 0));
-      }
+      if (step_index == 0) CHK(sweep_offset(s));
       CHK(sweep_chain_launch(s, csp, GA, G, s->s2));
       CHK(sweep_dwadam_launch(s, 0, GA, rows, brows, step_index, st));
       return sweep_dwadam_launch(s, GA, G, rows, brows, step_index, s->s2);
@@ -250,78 +217,28 @@ static int sweep_step_chain(v21_sweep* s, const ChainStep& cs, int brows, long l
     CHK(sweep_chain_launch(s, csp, 0, G, st));
     if (s->ctx->nranks == 1)  // nothing to exchange: all gradients, all Adam updates, all packed copies in one launch
       return launch_dw_adam_group(s->tr, s->d_dwadam, s->h_dwadam, rows, brows, step_index, st);
-    int nslice = 1;
+    int nslice = 1;  // data-parallel ranks: every model's gradients in one launch, the exchange, Adam
     std::vector<Dw16Args> probs;
-    for (v21_trainer* t : s->tr)
-      dw16_problems(t, rows, brows, &nslice, probs,
-                    (s->ctx->nranks == 1 && step_index >= 0) ? t->d_steploss + step_index : nullptr);
+    for (v21_trainer* t : s->tr) dw16_problems(t, rows, brows, &nslice, probs);
     CHK(launch_dw16(t0->prec, probs, st));
     if (nslice > 1)
-      for (v21_trainer* t : s->tr) {
-        const long long n4 = ((long long)t->P + 3) / 4;
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, t->d_g,
-                           (const float*)t->d_slab, nslice, (long long)t->P + 4, (long long)t->P);
-        HIPCHK(hipGetLastError());
-      }
+      for (v21_trainer* t : s->tr) CHK(reduce_slabs(t, nslice));
   } else {
-    for (v21_trainer* t : s->tr) HIPCHK(hipMemsetAsync(t->d_g, 0, (t->P + 1) * sizeof(float), st));
+    for (v21_trainer* t : s->tr) CHK(zero_grad(t));
   }
-  AlphaGroup al{};
-  size_t maxP = 0;
-  for (int k = 0; k < G; ++k) {
-    v21_trainer* t = s->tr[k];
-    CHK(v21_comm_allreduce_f32(t->ctx, t->d_g, t->P + 1));
-    if ((s->ctx->nranks > 1 || rows == 0) && step_index >= 0)
-      HIPCHK(hipMemcpyAsync(t->d_steploss + step_index, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-    t->iter += 1;
-    al.a[k] = adam_alpha(t->adam, t->iter);
-    maxP = std::max(maxP, t->P);
-  }
-  hipLaunchKernelGGL(adam_repack_group_kernel, dim3((unsigned)((maxP + 255) / 256), G), dim3(256), 0, st,
-                     (const AdamArgs*)s->d_adam, al);
-  HIPCHK(hipGetLastError());
-  for (v21_trainer* t : s->tr) {
-    t->copies_ok = true; t->nt_ok = false;
-    invalidate_streams(t->mlp);
-    t->mlp->wpad_ok = true;
-  }
-  return V21_OK;
+  return sweep_adam(s, step_index, false);
 }
 
-// f32 members (train_chain32s.h): the problem and Adam blocks of one model's gradient launch, as train_on_rows_chain32
-// builds them per step -- without what changes from step to step (contraction length, step size, loss slot: Dw32Step).
-// false: this model's gradient launch would take 64 x 64 tiles (gemm_nt_dwadam_kernel<2>): the sweep then keeps the
-// per-layer path, so that a member trains bit for bit as it would on its own.
+// f32 members (train_chain32s.h): the problem and Adam blocks of one model's gradient launch, as a step of the trainer
+// builds them (dw32_model) -- without what changes from step to step (contraction length, step size, loss slot: Dw32Step).
+// false: this model's gradient launch would take 64 x 64 tiles (routes.h: dw32_tile; gemm_nt_dwadam_kernel<2>): the sweep
+// then keeps the per-layer path, so that a member trains bit for bit as it would on its own.
 static bool build_dw32_model(v21_trainer* t, Dw32Model& md, int& blocks) {
-  v21_mlp* m = t->mlp;
-  const int L = m->L;
+  const v21_mlp* m = t->mlp;
   md = Dw32Model{};
   blocks = 0;
-  if (L > kNtMaxGroup) return false;
-  long long work = 0;
-  md.grp.count = L;
-  for (int l = 0; l < L; ++l) {
-    NtArgs& g = md.grp.p[l];
-    g.A = t->d_ht[l]; g.lda = t->Bp;
-    g.B = t->d_dzt[l + 1]; g.ldb = t->Bp;
-    g.C = t->d_g + m->w_off[l]; g.ldc = m->nw(l);
-    g.M = m->dims[l] + 1; g.N = m->nw(l);
-    g.ep = NT_DW; g.nz = 1; g.tile = 32;
-    g.nx = (g.N + 31) / 32; g.ny = (g.M + 31) / 32;
-    g.a_scale = g.b_scale = g.out_scale = 1.f;
-    work += (long long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-    md.grp.first[l] = blocks;
-    blocks += g.nx * g.ny;
-    md.ad.lt[l] = NtAdamLayer{m->w_off[l], t->fw_off[l], t->bw_off[l], m->dims[l], t->c32_frags(m->dims[l]), t->c32_frags(m->nw(l))};
-  }
-  md.grp.first[L] = blocks;
-  if (work >= 192) return false;
-  NtAdamInfo& ad = md.ad;
-  ad.w = m->d_w; ad.m = t->d_m; ad.v = t->d_v; ad.fw = (float*)t->d_fw; ad.bw = (float*)t->d_bw;
-  ad.omb1 = 1.0f - t->adam.beta1; ad.omb2 = 1.0f - t->adam.beta2; ad.eps = t->adam.eps;
-  ad.loss_acc = (unsigned long long*)t->d_ticket; ad.loss_out = t->d_g + t->P; ad.loss_out2 = t->d_steploss;
-  ad.loss_slot = -1;
-  ad.fmt = 4;
+  if (m->L > kNtMaxGroup || dw32_tile(m->L, m->dims.data(), m->act.data()) != 32) return false;
+  blocks = dw32_model(t, 32, md);
   return true;
 }
 // every weight gradient + Adam + packed streams + batch loss of several f32 models in one launch (dw_adam32.h)
@@ -340,11 +257,7 @@ int launch_dw32_group(const std::vector<v21_trainer*>& trs, const Dw32Model* d_t
   if (small_slabs) hipLaunchKernelGGL(dwadam32_group_kernel<128>, dim3(max_blocks, G), dim3(256), 0, st, d_tab, ds);
   else hipLaunchKernelGGL(dwadam32_group_kernel<256>, dim3(max_blocks, G), dim3(256), 0, st, d_tab, ds);
   HIPCHK(hipGetLastError());
-  for (v21_trainer* t : trs) {
-    t->copies_ok = true; t->nt_ok = false;
-    invalidate_streams(t->mlp);
-    t->mlp->wpad_ok = true;
-  }
+  for (v21_trainer* t : trs) weights_updated(t, false);
   return V21_OK;
 }
 // builds / refreshes the device table of launch_dw32_group; *ok = false: a member's gradient launch takes 64 x 64 tiles
@@ -358,13 +271,7 @@ int refresh_dw32_table(const std::vector<v21_trainer*>& trs, Dw32Model* d_tab, s
     *max_blocks = std::max(*max_blocks, blocks);
   }
   if (!*ok) return V21_OK;
-  if (dtab.size() != h_tab.size() || memcmp(dtab.data(), h_tab.data(), dtab.size() * sizeof(Dw32Model)) != 0) {
-    HIPCHK(hipStreamSynchronize(st));  // (a step in flight may still read the old table)
-    h_tab = dtab;
-    HIPCHK(hipMemcpyAsync(d_tab, h_tab.data(), dtab.size() * sizeof(Dw32Model), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return V21_OK;
+  return upload_if_changed(dtab, h_tab, d_tab, st);
 }
 // one optimizer step of every f32 member in TWO launches: the chain of every model (blockIdx.y = model), then every
 // weight gradient + Adam + packed streams + batch loss
@@ -402,10 +309,7 @@ static int sweep_step_chain32(v21_sweep* s, const ChainStep& cs, long long step_
     const int GA = (G + 1) / 2;
     const std::vector<v21_trainer*> pa(s->tr.begin(), s->tr.begin() + GA), pb(s->tr.begin() + GA, s->tr.end());
     CHK(sweep_chain32_launch(s, csp, rpw, 0, GA, st));
-    if (step_index == 0) {
-      HIPCHK(hipEventRecord(s->ev_off, st));
-      HIPCHK(hipStreamWaitEvent(s->s2, s->ev_off, 0));
-    }
+    if (step_index == 0) CHK(sweep_offset(s));
     CHK(sweep_chain32_launch(s, csp, rpw, GA, G, s->s2));
     CHK(launch_dw32_group(pa, s->d_dw32, rows, step_index, max_blocks, st, small_slabs));
     return launch_dw32_group(pb, s->d_dw32 + GA, rows, step_index, max_blocks, s->s2, small_slabs);
@@ -422,46 +326,22 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
   hipStream_t st = s->ctx->stream;
   v21_mlp* m = t0->mlp;
   const long long n = t0->n[0];
-  const int R = s->ctx->nranks, rk = s->ctx->rank;
+  const int R = s->ctx->nranks;
   if (batch < 1) return fail(V21_ERR_ARG, "batch must be >= 1");
   if ((batch + R - 1) / R > t0->max_batch) return fail(V21_ERR_ARG, "per-rank batch %d exceeds max_batch %d", (batch + R - 1) / R, t0->max_batch);
   const int* d_idx = nullptr;
-  if (perm) {
-    CHK(check_row_table(perm, n));
-    if (t0->perm_cap < n) {
-      if (t0->d_perm) HIPCHK(hipFree(t0->d_perm));
-      HIPCHK(hipMalloc((void**)&t0->d_perm, (size_t)n * sizeof(int)));
-      t0->perm_cap = n;
-    }
-    HIPCHK(hipMemcpyAsync(t0->d_perm, perm, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    d_idx = t0->d_perm;
-  }
+  CHK(upload_rows(t0, perm, &d_idx));
   const long long steps = (n + batch - 1) / batch;
-  for (v21_trainer* t : s->tr)
-    if (t->steploss_cap < steps) {
-      HIPCHK(hipStreamSynchronize(st));
-      destroy_graphs(t);  // captured steps of this trainer hold the old pointer (as v21_trainer_run_epoch does)
-      if (t->d_steploss) HIPCHK(hipFree(t->d_steploss));
-      HIPCHK(hipMalloc((void**)&t->d_steploss, (size_t)steps * sizeof(float)));
-      t->steploss_cap = steps;
-    }
+  for (v21_trainer* t : s->tr) CHK(ensure_steploss(t, steps));
   // the Adam hyper-parameters may have changed since create (set_adam / set_lr): refresh the device table
   std::vector<AdamArgs> tab;
   for (v21_trainer* t : s->tr) tab.push_back(adam_args(t, true, 0.f, s->chain));
-  if (memcmp(tab.data(), s->h_adam.data(), tab.size() * sizeof(AdamArgs)) != 0) {
-    s->h_adam = tab;
-    HIPCHK(hipMemcpyAsync(s->d_adam, s->h_adam.data(), tab.size() * sizeof(AdamArgs), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
+  CHK(upload_if_changed(tab, s->h_adam, s->d_adam, st));
   const int din = m->dims[0], dout = m->dims[m->L];
   if (s->chain) {
     std::vector<ChainModel> tab;
     for (v21_trainer* t : s->tr) tab.push_back(chain_model(t));
-    if (tab.size() != s->h_chain.size() || memcmp(tab.data(), s->h_chain.data(), tab.size() * sizeof(ChainModel)) != 0) {
-      s->h_chain = tab;
-      HIPCHK(hipMemcpyAsync(s->d_chain, s->h_chain.data(), tab.size() * sizeof(ChainModel), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
+    CHK(upload_if_changed(tab, s->h_chain, s->d_chain, st));
     if (R == 1) CHK(refresh_dw_adam_table(s->tr, &s->d_dwadam, s->h_dwadam, st));
   }
   bool group32 = s->chain32s && R == 1 && batch <= kDw32MaxRows && !(getenv("V21_SWEEP32_GROUP") && getenv("V21_SWEEP32_GROUP")[0] == '0');
@@ -478,12 +358,7 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
       tab.push_back(chain_model32(t));
       tab.back().stamps = nullptr;
     }
-    if (tab.size() != s->h_chain.size() || memcmp(tab.data(), s->h_chain.data(), tab.size() * sizeof(ChainModel)) != 0) {
-      HIPCHK(hipStreamSynchronize(st));  // (a step in flight may still read the old table)
-      s->h_chain = tab;
-      HIPCHK(hipMemcpyAsync(s->d_chain, s->h_chain.data(), tab.size() * sizeof(ChainModel), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
+    CHK(upload_if_changed(tab, s->h_chain, s->d_chain, st));
   }
   // r5: two half-groups on two streams (v21_sweep: s2) for the grouped chain launches of one rank; V21_SWEEP_STREAMS=1: one stream
   s->two_streams = R == 1 && (s->chain || group32) && s->tr.size() >= 16 && RouteEnv::read().sweep_streams == 2;  // (below 16 members the second stream's hand-overs cost more than they hide: tiny members, 8 per group: 17.4 -> 23.6 us per step)
@@ -497,10 +372,9 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
     HIPCHK(hipStreamWaitEvent(s->s2, s->ev_fork, 0));
   }
   for (long long sidx = 0; sidx < steps; ++sidx) {
-    const long long first = sidx * batch;
-    const int brows = (int)std::min<long long>(batch, n - first);
-    const long long lo = first + (long long)brows * rk / R, hi = first + (long long)brows * (rk + 1) / R;
-    const int rows = (int)(hi - lo);
+    const EpochBatch b = epoch_batch(s->ctx, n, batch, sidx);
+    const long long lo = b.lo, first = b.first;
+    const int rows = b.rows, brows = b.brows;
     if (s->chain) {
       ChainStep cs = chain_step(t0->d_x[0], din, t0->y_is_x[0] ? nullptr : t0->d_y[0], dout, t0->d_rw[0], d_idx, lo, rows,
                                 brows, dout, nullptr, lo - first);
@@ -525,16 +399,5 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
     HIPCHK(hipEventRecord(s->ev_join, s->s2));
     HIPCHK(hipStreamWaitEvent(st, s->ev_join, 0));
   }
-  std::vector<float> h((size_t)steps * s->tr.size());
-  for (size_t k = 0; k < s->tr.size(); ++k)
-    HIPCHK(hipMemcpyAsync(h.data() + k * steps, s->tr[k]->d_steploss, (size_t)steps * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (size_t k = 0; k < s->tr.size(); ++k) {
-    double tot = 0.0;
-    for (long long i = 0; i < steps; ++i) tot += (double)h[k * steps + i];
-    losses[k] = tot / (double)n;
-  }
-  return V21_OK;
+  return epoch_losses(s->tr, steps, n, losses);
 }
-
-

@@ -400,12 +400,9 @@ float adam_alpha(const v21_adam& a, long long t) {
   return a.lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
 }
 
-
-
-
 // Adam (do_adam) and/or refresh of the W^T / padded-W copies from the arena
-static int adam_and_copies(v21_trainer* t, bool do_adam, float alpha, bool skip_nt = false, int nslab = 1) {
-  AdamArgs a = adam_args(t, do_adam, alpha, skip_nt);
+static int adam_and_copies(v21_trainer* t, bool do_adam, float alpha, bool skip_nt = false, int nslab = 1, const StepLoss* pub = nullptr) {
+  AdamArgs a = adam_args(t, do_adam, alpha, skip_nt, pub);
   if (nslab > 1) { a.gw = t->d_g; a.slab = t->d_slab; a.nslab = nslab; a.slab_stride = (long long)t->P + 4; }
   hipLaunchKernelGGL(adam_repack_kernel, dim3((unsigned)((t->P + 255) / 256)), dim3(256), 0, t->ctx->stream, a);
   HIPCHK(hipGetLastError());
@@ -415,7 +412,7 @@ static int adam_and_copies(v21_trainer* t, bool do_adam, float alpha, bool skip_
   if (a.ts) t->n_stream_adam += 1;
   return V21_OK;
 }
-AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt) {
+AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt, const StepLoss* pub) {
   v21_mlp* m = t->mlp;
   AdamArgs a{};
   a.w = m->d_w; a.m = t->d_m; a.v = t->d_v; a.g = t->d_g; a.wt = t->d_wt; a.wp = t->d_wp;
@@ -445,9 +442,9 @@ AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt) {
     }
   }
   a.skip_nt = (skip_nt && (t->chain || t->chain32)) ? 1 : 0;
-  if (do_adam && t->chain32 && t->loss_slot_pending > -2) {  // a single-rank f32 chain step: this launch publishes its loss
+  if (do_adam && pub) {  // a single-rank f32 chain step: this launch publishes its loss
     a.loss_acc = (unsigned long long*)t->d_ticket; a.loss_out = t->d_g + t->P; a.loss_out2 = t->d_steploss;
-    a.loss_slot = t->loss_slot_pending;
+    a.loss_slot = pub->slot;
   }
   a.sc = step_ctx(t);
   return a;
@@ -461,10 +458,13 @@ AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt) {
 //                rides in slot P: summed by the reduce-scatter, it is copied into the weight arena's first pad
 //                float by its owner, so that the all-gather hands it to everyone.
 // `fold` > 1 (single rank): Adam sums that many split-K slabs itself.
-int reduce_and_update(v21_trainer* t, bool chain_copies, int fold, bool exchanged) {
+int reduce_and_update(v21_trainer* t, int fold, bool exchanged, const StepLoss* pub) {
   v21_ctx* c = t->ctx;
   hipStream_t st = c->stream;
   const size_t P = t->P;
+  const bool chain_copies = t->chain || t->chain32;  // (the chain trainers never read the fp32 NT copies)
+  // recorded, not run: iteration count, step size and loss slot come from the descriptors
+  if (t->capturing) return adam_and_copies(t, true, 0.f, chain_copies, fold, pub);
   if (c->nranks > 1 && c->sharded) {
     const int R = c->nranks;
     const size_t S = (P + 1 + R - 1) / R;  // elements per rank (the last ranks' tails are padding)
@@ -491,8 +491,37 @@ int reduce_and_update(v21_trainer* t, bool chain_copies, int fold, bool exchange
   if (!exchanged) CHK(v21_comm_allreduce_f32(c, t->d_g, P + 1));  // (exchanged: the step reduced its two buckets itself)
   phase_mark(t, 3);
   t->iter += 1;
-  CHK(adam_and_copies(t, true, adam_alpha(t->adam, t->iter), chain_copies, fold));
+  CHK(adam_and_copies(t, true, adam_alpha(t->adam, t->iter), chain_copies, fold, pub));
   phase_mark(t, 4);
+  return V21_OK;
+}
+void weights_updated(v21_trainer* t, bool nt_ok) {
+  t->copies_ok = true;
+  t->nt_ok = nt_ok;
+  invalidate_streams(t->mlp);
+  t->mlp->wpad_ok = true;  // ... but the updater's own copies were just refreshed
+}
+int step_tail(v21_trainer* t, const StepLoss& loss) {
+  if (t->capturing) return V21_OK;  // (recorded, not run: after_replay does the bookkeeping of each replay)
+  if (loss.out && loss.slot < 0) HIPCHK(hipMemcpyAsync(loss.out, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, t->ctx->stream));
+  weights_updated(t, !t->chain && !t->chain32);
+  return V21_OK;
+}
+// the loss of a step of >= 1 row: one rank, an epoch's per-step slot -- the kernel that publishes the batch loss writes
+// the slot itself, on every route but the split-K one (its gradient launch publishes the loss before the exchange)
+static StepLoss step_loss(const v21_trainer* t, const StepRoute& r, float* out) {
+  const bool listed = out && t->d_steploss && out >= t->d_steploss && out < t->d_steploss + t->steploss_cap;
+  return StepLoss{out, listed && t->ctx->nranks == 1 && r.upd != UP_DW16_SPLITK ? (int)(out - t->d_steploss) : -1};
+}
+int zero_grad(v21_trainer* t) {
+  HIPCHK(hipMemsetAsync(t->d_g, 0, (t->P + 1) * sizeof(float), t->ctx->stream));
+  return V21_OK;
+}
+int reduce_slabs(v21_trainer* t, int nslice) {
+  const long long n4 = ((long long)t->P + 3) / 4;
+  hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, t->ctx->stream, t->d_g,
+                     (const float*)t->d_slab, nslice, (long long)t->P + 4, (long long)t->P);
+  HIPCHK(hipGetLastError());
   return V21_OK;
 }
 
@@ -521,25 +550,57 @@ static GaussArgs gauss_args(v21_trainer* t, int rows, bool sample, long long row
   return a;
 }
 
+NtArgs nt_forward(const v21_trainer* t, int l, const float* A, int rows, bool want_t) {
+  const v21_mlp* m = t->mlp;
+  const bool gauss = m->act[l] == V21_ACT_GAUSS;
+  NtArgs g{};
+  g.A = A; g.lda = p16(m->dims[l]);
+  g.B = t->d_wt + t->wt_off[l]; g.ldb = p16(m->dims[l]);
+  g.C = gauss ? t->d_zs : t->d_h[l + 1]; g.ldc = p16(m->nw(l));
+  g.CT = (want_t && l + 1 < m->L && !gauss) ? t->d_ht[l + 1] : nullptr; g.ldct = t->Bp;
+  g.M = rows; g.N = m->nw(l); g.K = m->dims[l];
+  g.bias = m->d_w + m->b_off[l];
+  g.ep = m->act[l] == V21_ACT_RELU ? NT_FWD_RELU : NT_FWD;
+  g.nz = 1;
+  return g;
+}
+NtArgs nt_dw(const v21_trainer* t, int l, const float* A, const float* B, int rows, NtSlices sl, float gs) {
+  const v21_mlp* m = t->mlp;
+  NtArgs g{};
+  g.A = A; g.lda = t->Bp;
+  g.B = B; g.ldb = t->Bp;
+  g.C = (sl.nslice > 1 ? t->d_slab : t->d_g) + m->w_off[l]; g.ldc = m->nw(l);
+  g.M = m->dims[l] + 1; g.N = m->nw(l); g.K = rows;
+  g.ep = NT_DW; g.nz = sl.nslice; g.k_chunk = sl.k_chunk; g.slab_stride = (long long)t->P + 4;
+  g.b_scale = gs; g.out_scale = 1.0f / gs;
+  return g;
+}
+NtArgs nt_dx(const v21_trainer* t, int l, const float* A, int rows, float gs) {
+  const v21_mlp* m = t->mlp;
+  const int K = m->dims[l], N = m->nw(l);
+  NtArgs d{};
+  d.A = A; d.lda = p16(N);
+  d.B = t->d_wp + t->wp_off[l]; d.ldb = p16(N);
+  d.C = t->d_dz[l]; d.ldc = p16(K);
+  d.CT = t->d_dzt[l]; d.ldct = t->Bp;
+  d.M = rows; d.N = K; d.K = N;
+  d.mask = t->d_h[l]; d.ldmask = p16(K);
+  d.ep = m->act[l - 1] == V21_ACT_RELU ? NT_DX_MASK : NT_DX;
+  d.nz = 1;
+  d.a_scale = gs; d.out_scale = 1.0f / gs;
+  return d;
+}
+
 // forward through the stack; h[0] / ht[0] hold the batch.  `sample`: draw eps at the
 // variational layer (training); row0 = position of this rank's first row in the global batch
 static int trainer_forward(v21_trainer* t, int rows, bool want_t, bool sample = false, long long row0 = 0) {
   v21_mlp* m = t->mlp;
   for (int l = 0; l < m->L; ++l) {
-    const bool gauss = m->act[l] == V21_ACT_GAUSS;
     NtGroup grp{};
     grp.count = 1;
-    NtArgs& g = grp.p[0];
-    g.A = t->d_h[l]; g.lda = p16(m->dims[l]);
-    g.B = t->d_wt + t->wt_off[l]; g.ldb = p16(m->dims[l]);
-    g.C = gauss ? t->d_zs : t->d_h[l + 1]; g.ldc = p16(m->nw(l));
-    g.CT = (want_t && l + 1 < m->L && !gauss) ? t->d_ht[l + 1] : nullptr; g.ldct = t->Bp;
-    g.M = rows; g.N = m->nw(l); g.K = m->dims[l];
-    g.bias = m->d_w + m->b_off[l];
-    g.ep = m->act[l] == V21_ACT_RELU ? NT_FWD_RELU : NT_FWD;
-    g.nz = 1;
+    grp.p[0] = nt_forward(t, l, t->d_h[l], rows, want_t);
     CHK(launch_nt(t->prec, grp, t->ctx->stream));
-    if (gauss) {  // z = z_mean + exp(z_log_var / 2) eps -> h[l+1] (and its transpose), kl_weight * KL_i -> klrow
+    if (m->act[l] == V21_ACT_GAUSS) {  // z = z_mean + exp(z_log_var / 2) eps -> h[l+1] (and its transpose), kl_weight * KL_i -> klrow
       GaussArgs a = gauss_args(t, rows, sample, row0);
       a.ht = want_t ? t->d_ht[l + 1] : nullptr;
       hipLaunchKernelGGL(gauss_sample_kernel, dim3((rows + 3) / 4), dim3(256), 0, t->ctx->stream, a);
@@ -549,89 +610,43 @@ static int trainer_forward(v21_trainer* t, int rows, bool want_t, bool sample = 
   return V21_OK;
 }
 
-// one optimizer step on the batch already gathered into h[0]/ht[0], yb, wb
-static int trainer_step(v21_trainer* t, const float* yb, long long ldy, int rows, int brows, float* loss_out,
-                        long long row0) {
+// The per-layer route (gemm_nt.h) on the batch gathered into h[0]/ht[0], yb, wb: forward, loss, then per layer from the
+// top its weight gradient and the activation gradient of the layer below in one grouped launch, the slabs summed, the update
+static int per_layer_step(v21_trainer* t, const float* yb, long long ldy, int rows, int brows, const StepRoute& r,
+                          const StepLoss& loss, long long row0) {
   v21_mlp* m = t->mlp;
   hipStream_t st = t->ctx->stream;
   const int L = m->L, dout = m->dims[L];
-  if (rows > t->max_batch) return fail(V21_ERR_ARG, "batch of %d rows exceeds max_batch %d", rows, t->max_batch);
-  // single rank, an epoch's per-step slot: the sum kernel writes it itself (a device-to-device copy per step is a launch)
-  const bool in_table = t->ctx->nranks == 1 && rows > 0 && loss_out && t->d_steploss && loss_out >= t->d_steploss &&
-                        loss_out < t->d_steploss + t->steploss_cap;
-  phase_mark(t, 0);
-  if (rows > 0) {
-    note_route(t, step_route(t, rows));
-    CHK(ensure_copies(t));
-    CHK(trainer_forward(t, rows, true, true, row0));
-    const int wpb = 4;  // waves (rows) per block
-    hipLaunchKernelGGL(loss_grad_t_kernel, dim3((rows + wpb - 1) / wpb), dim3(64 * wpb), 0, st, t->d_h[L], p16(dout), yb,
-                       ldy, t->d_wb, t->d_dz[L], p16(dout), t->d_dzt[L], t->Bp, t->d_rowloss, rows, dout,
-                       2.0f / (float)brows, (const float*)t->d_klrow);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, st, t->d_rowloss, rows, t->d_g + t->P, 0, t->d_steploss,
-                       step_ctx(t), in_table ? (int)(loss_out - t->d_steploss) : -1);
-    HIPCHK(hipGetLastError());
-    // weight gradients contract over the batch: slices of <= kNtMaxKPerWg rows -> slabs
-    int nslice = (rows + kNtMaxKPerWg - 1) / kNtMaxKPerWg;
-    const int k_chunk = ((rows + nslice - 1) / nslice + 15) / 16 * 16;
-    nslice = (rows + k_chunk - 1) / k_chunk;
-    const long long slab_stride = (long long)t->P + 4;
-    const float gs = grad_opscale(brows, dout);
-    for (int l = L - 1; l >= 0; --l) {
-      const int K = m->dims[l], N = m->nw(l);
-      const bool gauss = l == t->gl;  // gradient w.r.t. this layer's Dense output: dzs / dzst instead of dz[l+1]
-      if (gauss) {  // dz[l+1] = dL/dz  ->  dL/d[z_mean | z_log_var] (+ the KL term's own gradient)
-        GaussArgs a = gauss_args(t, rows, true, row0);
-        a.beta = t->kl_weight / (float)brows;
-        hipLaunchKernelGGL(gauss_sample_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a);
-        HIPCHK(hipGetLastError());
-      }
-      NtGroup grp{};
-      NtArgs& g = grp.p[0];  // [dW; db] = [H^T; 1^T] dZ
-      g.A = t->d_ht[l]; g.lda = t->Bp;
-      g.B = gauss ? t->d_dzst : t->d_dzt[l + 1]; g.ldb = t->Bp;
-      g.C = (nslice > 1 ? t->d_slab : t->d_g) + m->w_off[l]; g.ldc = N;
-      g.M = K + 1; g.N = N; g.K = rows;
-      g.ep = NT_DW; g.nz = nslice; g.k_chunk = k_chunk; g.slab_stride = slab_stride;
-      g.b_scale = gs; g.out_scale = 1.0f / gs;
-      grp.count = 1;
-      if (l > 0) {  // dH = dZ W^T, masked by the ReLU of the layer below -> dz[l], dzt[l]
-        NtArgs& d = grp.p[1];
-        d.A = gauss ? t->d_dzs : t->d_dz[l + 1]; d.lda = p16(N);
-        d.B = t->d_wp + t->wp_off[l]; d.ldb = p16(N);
-        d.C = t->d_dz[l]; d.ldc = p16(K);
-        d.CT = t->d_dzt[l]; d.ldct = t->Bp;
-        d.M = rows; d.N = K; d.K = N;
-        d.mask = t->d_h[l]; d.ldmask = p16(K);
-        d.ep = m->act[l - 1] == V21_ACT_RELU ? NT_DX_MASK : NT_DX;
-        d.nz = 1;
-        d.a_scale = gs; d.out_scale = 1.0f / gs;
-        grp.count = 2;
-      }
-      CHK(launch_nt(t->prec, grp, st));
-    }
-    if (nslice > 1) {
-      const long long n4 = ((long long)t->P + 3) / 4;
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, t->d_g,
-                         (const float*)t->d_slab, nslice, slab_stride, (long long)t->P);
+  CHK(ensure_copies(t));
+  CHK(trainer_forward(t, rows, true, true, row0));
+  const int wpb = 4;  // waves (rows) per block
+  hipLaunchKernelGGL(loss_grad_t_kernel, dim3((rows + wpb - 1) / wpb), dim3(64 * wpb), 0, st, t->d_h[L], p16(dout), yb,
+                     ldy, t->d_wb, t->d_dz[L], p16(dout), t->d_dzt[L], t->Bp, t->d_rowloss, rows, dout,
+                     2.0f / (float)brows, (const float*)t->d_klrow);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, st, t->d_rowloss, rows, t->d_g + t->P, 0, t->d_steploss,
+                     step_ctx(t), loss.slot);
+  HIPCHK(hipGetLastError());
+  const NtSlices sl{r.nslice, r.k_chunk};  // weight gradients contract over the batch: slices -> slabs (routes.h: nt_slices)
+  const float gs = grad_opscale(brows, dout);
+  for (int l = L - 1; l >= 0; --l) {
+    const bool gauss = l == t->gl;  // gradient w.r.t. this layer's Dense output: dzs / dzst instead of dz[l+1]
+    if (gauss) {  // dz[l+1] = dL/dz  ->  dL/d[z_mean | z_log_var] (+ the KL term's own gradient)
+      GaussArgs a = gauss_args(t, rows, true, row0);
+      a.beta = t->kl_weight / (float)brows;
+      hipLaunchKernelGGL(gauss_sample_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a);
       HIPCHK(hipGetLastError());
     }
-  } else {
-    HIPCHK(hipMemsetAsync(t->d_g, 0, (t->P + 1) * sizeof(float), st));
+    NtGroup grp{};
+    grp.p[0] = nt_dw(t, l, t->d_ht[l], gauss ? t->d_dzst : t->d_dzt[l + 1], rows, sl, gs);
+    grp.count = 1;
+    if (l > 0) { grp.p[1] = nt_dx(t, l, gauss ? t->d_dzs : t->d_dz[l + 1], rows, gs); grp.count = 2; }
+    CHK(launch_nt(t->prec, grp, st));
   }
-  if (t->capturing) {  // recorded, not run: iteration count, step size and loss slot come from the descriptors
-    CHK(adam_and_copies(t, true, 0.f));
-    return V21_OK;
-  }
+  if (sl.nslice > 1) CHK(reduce_slabs(t, sl.nslice));
   phase_mark(t, 1); phase_mark(t, 2);  // (per-layer path: forward, loss and every backward launch are reported as the first phase)
-  CHK(reduce_and_update(t, false, 1));
-  if (loss_out && !in_table) HIPCHK(hipMemcpyAsync(loss_out, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-  invalidate_streams(m);
-  m->wpad_ok = true;  // ... but our own copies were just refreshed
-  return V21_OK;
+  return reduce_and_update(t, 1);
 }
-
 
 // forward + loss + activation gradients of the chain path: ONE launch (train_chain.h)
 ChainModel chain_model(v21_trainer* t) {
@@ -817,19 +832,16 @@ static int launch_fused_train(v21_trainer* t, const float* x, long long ldx, con
   else HIPCHK(g_train[t->train_arch].fn[t->prec == V21_PREC_F16 ? 0 : 1](a, st));
   return V21_OK;
 }
-static int launch_chain(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy, const float* rw,
-                        const int* d_idx, long long first, int rows, int brows, long long row0) {
-  ChainArgs a{};
-  static_cast<ChainModel&>(a) = chain_model(t);
-  static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, t->mlp->dims[t->mlp->L], t, row0);
+// a 16-bit trainer's chain launch over a.rows rows: a training step, or (fwd = kChainFwd) a validation pass
+static int launch_chain(v21_trainer* t, ChainArgs& a, int fwd) {
   CHK(chain_attr(t->prec));
-  a.ncons = ((rows + 31) / 32 + 7) / 8 * 8;  // whole rounds of the 8 XCDs
+  a.ncons = ((a.rows + 31) / 32 + 7) / 8 * 8;  // whole rounds of the 8 XCDs
   a.npref = chain_prefetchers(a.ncons, 1);
   const dim3 grid(a.ncons + 8 * a.npref), block(64 * kChainWaves);
   // (train_chain.h: FEAT -- a trainer's launch never needs the joint step's or FORWARD mode's code, and the variational
   //  head's only when the stack has one; V21_CHAIN_PLAIN=0: everything through the variational instantiation)
   static const bool plain_ok = !(getenv("V21_CHAIN_PLAIN") && getenv("V21_CHAIN_PLAIN")[0] == '0');
-  const int feat = plain_ok && t->gl < 0 ? 0 : kChainGauss;
+  const int feat = fwd | (plain_ok && t->gl < 0 ? 0 : kChainGauss);
   if (t->prec == V21_PREC_F16) launch_chain_kernel<PrecF16>(feat, grid, block, t->ctx->stream, a);
   else launch_chain_kernel<PrecBF16>(feat, grid, block, t->ctx->stream, a);
   HIPCHK(hipGetLastError());
@@ -914,10 +926,8 @@ int launch_chain32_args(ChainArgs& a, hipStream_t st, bool small, int rows_per_w
   return V21_OK;
 }
 
-
 // weight gradients of chain-mode trainers: problems in groups of <= 16 per launch
-void dw16_problems(v21_trainer* t, int rows, int brows, int* nslice_out, std::vector<Dw16Args>& probs,
-                          float* loss_out2) {
+void dw16_problems(v21_trainer* t, int rows, int brows, int* nslice_out, std::vector<Dw16Args>& probs) {
   v21_mlp* m = t->mlp;
   const int L = m->L;
   const int steps = (rows + 15) / 16;
@@ -936,8 +946,8 @@ void dw16_problems(v21_trainer* t, int rows, int brows, int* nslice_out, std::ve
     g.slab_stride = (long long)t->P + 4;
     g.out_scale = 1.0f / gs;
     if (l == 0) {
-      g.loss_acc = (unsigned long long*)t->d_ticket; g.loss_out = t->d_g + t->P; g.loss_out2 = loss_out2;
-      if (t->capturing) { g.loss_out2 = t->d_steploss; g.sc = step_ctx(t); }
+      g.loss_acc = (unsigned long long*)t->d_ticket; g.loss_out = t->d_g + t->P;
+      if (t->capturing) { g.loss_out2 = t->d_steploss; g.sc = step_ctx(t); }  // (eager steps: the loss is copied after the exchange)
     }
     probs.push_back(g);
   }
@@ -1034,8 +1044,6 @@ static int launch_dw_adam(v21_trainer* t, int rows, int brows, float alpha, int 
   if (t->prec == V21_PREC_F16) hipLaunchKernelGGL(dw16_adam_kernel<PrecF16>, grid, dim3(64 * kDwAdamWaves), 0, t->ctx->stream, md, st);
   else hipLaunchKernelGGL(dw16_adam_kernel<PrecBF16>, grid, dim3(64 * kDwAdamWaves), 0, t->ctx->stream, md, st);
   HIPCHK(hipGetLastError());
-  t->copies_ok = true;
-  t->nt_ok = false;
   return V21_OK;
 }
 
@@ -1045,12 +1053,7 @@ int refresh_dw_adam_table(const std::vector<v21_trainer*>& tr, DwAdamModel** d_t
   std::vector<DwAdamModel> tab(tr.size());
   for (size_t k = 0; k < tr.size(); ++k) dw_adam_model(tr[k], tab[k]);
   if (!*d_tab) HIPCHK(hipMalloc((void**)d_tab, tab.size() * sizeof(DwAdamModel)));
-  if (tab.size() != h_tab.size() || memcmp(tab.data(), h_tab.data(), tab.size() * sizeof(DwAdamModel)) != 0) {
-    h_tab = tab;
-    HIPCHK(hipMemcpyAsync(*d_tab, h_tab.data(), tab.size() * sizeof(DwAdamModel), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return V21_OK;
+  return upload_if_changed(tab, h_tab, *d_tab, st);
 }
 // every model takes one Adam step (iter advanced here) on the operands its chain launch left; slot: see DwAdamStep
 int launch_dw_adam_group(const std::vector<v21_trainer*>& tr, const DwAdamModel* d_tab,
@@ -1077,17 +1080,10 @@ int launch_dw_adam_group(const std::vector<v21_trainer*>& tr, const DwAdamModel*
     else hipLaunchKernelGGL((dw16_adam_group_kernel<PrecBF16, kDwAdamInFlight>), grid, dim3(64 * kDwAdamWaves), 0, st, d_tab, stp);
   }
   HIPCHK(hipGetLastError());
-  for (v21_trainer* t : tr) {
-    t->copies_ok = true; t->nt_ok = false;
-    invalidate_streams(t->mlp);
-    t->mlp->wpad_ok = true;
-  }
+  for (v21_trainer* t : tr) weights_updated(t, false);
   return V21_OK;
 }
 
-static int trainer_step(v21_trainer* t, const float* yb, long long ldy, int rows, int brows, float* loss_out,
-                        long long row0);
-// one optimizer step on rows [first, first+rows) (through d_idx when given) of (x, y, rw)
 // launch `probs` in groups of <= kNtMaxGroup
 int launch_nt_many(int prec, std::vector<NtArgs>& probs, hipStream_t st) {
   for (size_t o = 0; o < probs.size(); o += kNtMaxGroup) {
@@ -1098,250 +1094,207 @@ int launch_nt_many(int prec, std::vector<NtArgs>& probs, hipStream_t st) {
   }
   return V21_OK;
 }
-// one f32 optimizer step in THREE launches (train_chain32.h): the chain over this rank's rows, every layer's weight
-// gradient in one grouped NT launch on the fp32 operands the chain left, Adam (which also rebuilds the packed fp32
-// streams and, on a single rank, publishes the batch loss)
-int train_on_rows_chain32(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy, const float* rw,
-                                 const int* d_idx, long long first, int rows, int brows, float* loss_out, long long row0,
-                                 bool chain_done) {
-  v21_mlp* m = t->mlp;
-  hipStream_t st = t->ctx->stream;
-  const int L = m->L, dout = m->dims[L];
-  if (rows > t->max_batch) return fail(V21_ERR_ARG, "batch of %d rows exceeds max_batch %d", rows, t->max_batch);
-  const bool single = t->ctx->nranks == 1;
-  const bool in_table = single && rows > 0 && loss_out && t->d_steploss && loss_out >= t->d_steploss &&
-                        loss_out < t->d_steploss + t->steploss_cap;
-  int fold = 1;
-  if (rows > 0) {
-    // which kernels: csrc/routes.h (decide_step).  One rank, a step of <= kDw32MaxRows rows, 32 x 32 tiles: gradients,
-    // Adam, packed streams and batch loss in ONE launch whose workgroups walk the whole batch in slabs of 256 rows
-    // (dw_adam32.h: UP_DWADAM32); one contraction slice with 64 x 64 tiles: gemm_nt_dwadam_kernel (UP_NT_DWADAM);
-    // larger steps and data-parallel ranks: sliced gradients, [slab sum, exchange], Adam (UP_NT_SLICED)
-    const StepRoute route = step_route(t, rows);
-    if (!chain_done) {
-      phase_mark(t, 0);
-      CHK(ensure_copies(t, false));
-      ChainArgs a{};
-      static_cast<ChainModel&>(a) = chain_model32(t);
-      static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, dout, t, row0);
-      a.gs = 1.0f;  // fp32 operands: no scaling of the gradients
-      CHK(launch_chain32_args(a, st, t->chain32s, route.fwd == TR_CHAIN32S_4 ? 4 : 8));
-      phase_mark(t, 1);
-    }
-    note_route(t, route);  // (the joint step ran this model's chain in its own launch: the update route is what is recorded)
-    long long work = 0;
-    for (int l = 0; l < L; ++l) work += (long long)((m->dims[l] + 1 + 63) / 64) * ((m->nw(l) + 63) / 64);
-    const bool dw32 = route.upd == UP_DWADAM32;
-    int nslice = dw32 ? 1 : (rows + kNtMaxKPerWg - 1) / kNtMaxKPerWg;
-    const int k_chunk = ((rows + nslice - 1) / nslice + 15) / 16 * 16;
-    nslice = (rows + k_chunk - 1) / k_chunk;
-    std::vector<NtArgs> probs;
-    for (int l = 0; l < L; ++l) {  // [dW; db] = [H^T; 1^T] dZ
-      NtArgs g{};
-      g.A = t->d_ht[l]; g.lda = t->Bp;
-      g.B = t->d_dzt[l + 1]; g.ldb = t->Bp;
-      g.C = (nslice > 1 ? t->d_slab : t->d_g) + m->w_off[l]; g.ldc = m->nw(l);
-      g.M = m->dims[l] + 1; g.N = m->nw(l); g.K = rows;
-      g.ep = NT_DW; g.nz = nslice; g.k_chunk = k_chunk; g.slab_stride = (long long)t->P + 4;
-      probs.push_back(g);
-    }
-    // (one contraction slice = up to kNtMaxKPerWg rows.  Letting one workgroup walk 1,024 or 2,048 rows instead of the
-    //  sliced three-launch path below: 71.3 against 70.6 us and 96.7 against 92.8 us per step -- no gain.)
-    if (route.upd == UP_DWADAM32 || route.upd == UP_NT_DWADAM) {
-      // one rank, the batch is one contraction slice: gradients, Adam, the packed fp32 streams and the batch loss in ONE
-      // launch (gemm_nt.h: NtAdamInfo) -- the step is 2 launches
-      NtGroupBig grp{};
-      grp.count = L;
-      const int T = work >= 192 ? 2 : 1;
-      int blocks = 0;
-      NtAdamInfo ad{};
-      for (int l = 0; l < L; ++l) {
-        NtArgs& g = grp.p[l];
-        g = probs[l];
-        g.tile = 32 * T;
-        g.nx = (g.N + g.tile - 1) / g.tile; g.ny = (g.M + g.tile - 1) / g.tile; g.nz = 1;
-        g.a_scale = g.b_scale = g.out_scale = 1.f;
-        g.k_chunk = g.K; g.slab_stride = 0;
-        grp.first[l] = blocks;
-        blocks += g.nx * g.ny;
-        ad.lt[l] = NtAdamLayer{m->w_off[l], t->fw_off[l], t->bw_off[l], m->dims[l], t->c32_frags(m->dims[l]), t->c32_frags(m->nw(l))};
-      }
-      grp.first[L] = blocks;
-      if (!t->capturing) t->iter += 1;
-      ad.w = m->d_w; ad.m = t->d_m; ad.v = t->d_v; ad.fw = (float*)t->d_fw; ad.bw = (float*)t->d_bw;
-      ad.alpha = t->capturing ? 0.f : adam_alpha(t->adam, t->iter);
-      ad.omb1 = 1.0f - t->adam.beta1; ad.omb2 = 1.0f - t->adam.beta2; ad.eps = t->adam.eps;
-      ad.sc = step_ctx(t);
-      ad.loss_acc = (unsigned long long*)t->d_ticket; ad.loss_out = t->d_g + t->P; ad.loss_out2 = t->d_steploss;
-      ad.loss_slot = in_table ? (int)(loss_out - t->d_steploss) : -1;
-      ad.fmt = t->chain32s ? 4 : 3;
-#ifdef V21_CHAIN_FINE
-      ad.dbg = t->stamps_on ? t->d_stamps + 1024 : nullptr;
-#endif
-      phase_mark(t, 2); phase_mark(t, 3);  // (gradients + Adam are ONE launch here: reported under the Adam phase)
-      if (T == 2) hipLaunchKernelGGL(gemm_nt_dwadam_kernel<2>, dim3(blocks), dim3(256), 0, st, grp, ad);
-      else if (route.upd == UP_DWADAM32) hipLaunchKernelGGL(dwadam32_kernel, dim3(blocks), dim3(256), 0, st, grp, ad);  // operands through LDS in whole rows (dw_adam32.h)
-      else hipLaunchKernelGGL(gemm_nt_dwadam_kernel<1>, dim3(blocks), dim3(256), 0, st, grp, ad);
-      HIPCHK(hipGetLastError());
-      phase_mark(t, 4);
-      t->copies_ok = true;
-      t->nt_ok = false;
-      if (t->capturing) return V21_OK;
-      if (loss_out && !in_table) HIPCHK(hipMemcpyAsync(loss_out, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-      invalidate_streams(m);
-      m->wpad_ok = true;
-      return V21_OK;
-    }
-    CHK(launch_nt_many(t->prec, probs, st));
-    fold = nslice > 1 && single ? nslice : 1;  // single rank: Adam sums the slabs itself
-    if (nslice > 1 && fold == 1) {
-      const long long n4 = ((long long)t->P + 3) / 4;
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, t->d_g,
-                         (const float*)t->d_slab, nslice, (long long)t->P + 4, (long long)t->P);
-      HIPCHK(hipGetLastError());
-    }
-    if (!single) {  // the loss numerator rides in slot P of the arena: it must be there before the exchange
-      hipLaunchKernelGGL(chain32_loss_kernel, dim3(1), dim3(1), 0, st, (unsigned long long*)t->d_ticket, t->d_g + t->P);
-      HIPCHK(hipGetLastError());
-    }
-    phase_mark(t, 2);
-  } else {
-    HIPCHK(hipMemsetAsync(t->d_g, 0, (t->P + 1) * sizeof(float), st));
-    phase_mark(t, 0); phase_mark(t, 1); phase_mark(t, 2);
+int dw32_model(const v21_trainer* t, int tile, Dw32Model& md) {
+  const v21_mlp* m = t->mlp;
+  const int L = m->L;
+  md = Dw32Model{};
+  int blocks = 0;
+  md.grp.count = L;
+  for (int l = 0; l < L; ++l) {
+    NtArgs& g = md.grp.p[l];  // [dW; db] = [H^T; 1^T] dZ on the fp32 operands the chain left
+    g.A = t->d_ht[l]; g.lda = t->Bp;
+    g.B = t->d_dzt[l + 1]; g.ldb = t->Bp;
+    g.C = t->d_g + m->w_off[l]; g.ldc = m->nw(l);
+    g.M = m->dims[l] + 1; g.N = m->nw(l);
+    g.ep = NT_DW; g.nz = 1; g.tile = tile;
+    g.nx = (g.N + tile - 1) / tile; g.ny = (g.M + tile - 1) / tile;
+    g.a_scale = g.b_scale = g.out_scale = 1.f;
+    md.grp.first[l] = blocks;
+    blocks += g.nx * g.ny;
+    md.ad.lt[l] = NtAdamLayer{m->w_off[l], t->fw_off[l], t->bw_off[l], m->dims[l], t->c32_frags(m->dims[l]), t->c32_frags(m->nw(l))};
   }
-  t->loss_slot_pending = (single && rows > 0) ? (in_table ? (int)(loss_out - t->d_steploss) : -1) : -2;
-  int r;
-  if (t->capturing) r = adam_and_copies(t, true, 0.f, true, fold);  // recorded, not run: step size and slot come from the descriptors
-  else r = reduce_and_update(t, true, fold);
-  t->loss_slot_pending = -2;
-  CHK(r);
-  if (t->capturing) return V21_OK;
-  if (loss_out && !in_table) HIPCHK(hipMemcpyAsync(loss_out, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-  invalidate_streams(m);
-  m->wpad_ok = true;
-  return V21_OK;
+  md.grp.first[L] = blocks;
+  NtAdamInfo& ad = md.ad;
+  ad.w = m->d_w; ad.m = t->d_m; ad.v = t->d_v; ad.fw = (float*)t->d_fw; ad.bw = (float*)t->d_bw;
+  ad.omb1 = 1.0f - t->adam.beta1; ad.omb2 = 1.0f - t->adam.beta2; ad.eps = t->adam.eps;
+  ad.loss_acc = (unsigned long long*)t->d_ticket; ad.loss_out = t->d_g + t->P; ad.loss_out2 = t->d_steploss;
+  ad.loss_slot = -1;
+  ad.fmt = t->chain32s ? 4 : 3;
+  return blocks;
 }
 
+// ---- the update stage of one step, by route (routes.h: TrainUpdRoute); the forward / activation-gradient launch ran
+// the f32 chain's (train_chain32.h): every layer's weight gradient from the fp32 operands the chain left, Adam (which also
+// rebuilds the packed fp32 streams and, on a single rank, publishes the batch loss)
+static int update32(v21_trainer* t, const StepRoute& r, int rows, const StepLoss& loss) {
+  v21_mlp* m = t->mlp;
+  hipStream_t st = t->ctx->stream;
+  const int L = m->L;
+  if (r.upd == UP_DWADAM32 || r.upd == UP_NT_DWADAM) {
+    // one rank, the batch is one contraction slice: gradients, Adam, the packed fp32 streams and the batch loss in ONE
+    // launch (gemm_nt.h: NtAdamInfo) -- the step is 2 launches
+    Dw32Model md;
+    const int blocks = dw32_model(t, r.tile, md);
+    for (int l = 0; l < L; ++l) md.grp.p[l].K = md.grp.p[l].k_chunk = rows;
+    NtAdamInfo& ad = md.ad;
+    if (!t->capturing) t->iter += 1;
+    ad.alpha = t->capturing ? 0.f : adam_alpha(t->adam, t->iter);
+    ad.sc = step_ctx(t);
+    ad.loss_slot = loss.slot;
+#ifdef V21_CHAIN_FINE
+    ad.dbg = t->stamps_on ? t->d_stamps + 1024 : nullptr;
+#endif
+    phase_mark(t, 2); phase_mark(t, 3);  // (gradients + Adam are ONE launch here: reported under the Adam phase)
+    if (r.tile == 64) hipLaunchKernelGGL(gemm_nt_dwadam_kernel<2>, dim3(blocks), dim3(256), 0, st, md.grp, ad);
+    else if (r.upd == UP_DWADAM32) hipLaunchKernelGGL(dwadam32_kernel, dim3(blocks), dim3(256), 0, st, md.grp, ad);  // operands through LDS in whole rows (dw_adam32.h)
+    else hipLaunchKernelGGL(gemm_nt_dwadam_kernel<1>, dim3(blocks), dim3(256), 0, st, md.grp, ad);
+    HIPCHK(hipGetLastError());
+    phase_mark(t, 4);
+    return V21_OK;
+  }
+  // UP_NT_SLICED: the gradients in one grouped launch over batch slices, [slab sum, exchange], Adam
+  const NtSlices sl{r.nslice, r.k_chunk};
+  std::vector<NtArgs> probs;
+  for (int l = 0; l < L; ++l) probs.push_back(nt_dw(t, l, t->d_ht[l], t->d_dzt[l + 1], rows, sl, 1.0f));  // (fp32 operands: no scaling)
+  CHK(launch_nt_many(t->prec, probs, st));
+  const bool single = t->ctx->nranks == 1;
+  const int fold = sl.nslice > 1 && single ? sl.nslice : 1;  // single rank: Adam sums the slabs itself
+  if (sl.nslice > 1 && fold == 1) CHK(reduce_slabs(t, sl.nslice));
+  if (!single) {  // the loss numerator rides in slot P of the arena: it must be there before the exchange
+    hipLaunchKernelGGL(chain32_loss_kernel, dim3(1), dim3(1), 0, st, (unsigned long long*)t->d_ticket, t->d_g + t->P);
+    HIPCHK(hipGetLastError());
+  }
+  phase_mark(t, 2);
+  return reduce_and_update(t, fold, false, single ? &loss : nullptr);
+}
+// the 16-bit chain's: gradients, Adam and the packed copies in one launch (UP_DW16_ADAM), or the LDS-staged split-K
+// gradients (in two bucket launches when the exchange is bucketed), the slab sum, the exchange, Adam (UP_DW16_SPLITK).
+// `fused`: the step took a fused training kernel (the next one probably will too: its stream comes out of this Adam pass);
+// `xr`: its layer-0 operand is gathered from the resident training rows.
+static int update16(v21_trainer* t, const StepRoute& r, int rows, int brows, const StepLoss& loss, bool fused, const DwXRows* xr) {
+  v21_mlp* m = t->mlp;
+  hipStream_t st = t->ctx->stream;
+  if (r.upd == UP_DW16_ADAM) {
+    if (!t->capturing) t->iter += 1;
+    phase_mark(t, 2); phase_mark(t, 3);  // (gradients + Adam are ONE launch here: reported under the Adam phase)
+    CHK(launch_dw_adam(t, rows, brows, t->capturing ? 0.f : adam_alpha(t->adam, t->iter), loss.slot));
+    phase_mark(t, 4);
+    return V21_OK;
+  }
+  int nslice = 1, fold = 1;
+  std::vector<Dw16Args> probs;
+  dw16_problems(t, rows, brows, &nslice, probs);  // every weight gradient in one launch: [dW; db] = [H^T; 1^T] dZ
+  if (xr) probs[0].A = nullptr;
+  const bool bucketed = dp_bucketed(t);
+  if (bucketed) {
+    // two launches, the upper layers first (their bucket also carries the loss slot: the batch loss is published by
+    // whichever problem holds loss_acc -- the first of THIS launch); each problem's tiles are the same workgroups doing
+    // the same sums as in the one-launch form: bit-identical gradients
+    const int ksplit = dp_split_layer(m);
+    const size_t lo1 = (size_t)m->w_off[ksplit];  // bucket 1 = arena [lo1, P + 1), bucket 2 = [0, lo1)
+    Dw16Args& p0 = probs[0]; Dw16Args& pk = probs[ksplit];
+    pk.loss_acc = p0.loss_acc; pk.loss_out = p0.loss_out; pk.loss_out2 = p0.loss_out2; pk.sc = p0.sc;
+    p0.loss_acc = nullptr; p0.loss_out = nullptr; p0.loss_out2 = nullptr;
+    const std::vector<Dw16Args> upper(probs.begin() + ksplit, probs.end()), lower(probs.begin(), probs.begin() + ksplit);
+    CHK(launch_dw16(t->prec, upper, st, xr));
+    if (nslice > 1) CHK(reduce_slabs_range(t, nslice, (long long)lo1, (long long)t->P));
+    CHK(dp_exchange_bucket(t, 0, lo1, t->P + 1));
+    CHK(launch_dw16(t->prec, lower, st, xr));
+    if (nslice > 1) CHK(reduce_slabs_range(t, nslice, 0, (long long)lo1));
+    phase_mark(t, 2);
+    CHK(dp_exchange_bucket(t, 1, 0, lo1));
+    CHK(dp_exchange_join(t));
+  } else {
+    CHK(launch_dw16(t->prec, probs, st, xr));
+    fold = nslice > 1 && t->ctx->nranks == 1 ? nslice : 1;  // single rank: Adam sums the slabs itself
+    if (nslice > 1 && fold == 1) CHK(reduce_slabs(t, nslice));
+    phase_mark(t, 2);
+  }
+  t->ts_write = fused;
+  const int ru = reduce_and_update(t, fold, bucketed);
+  t->ts_write = false;
+  return ru;
+}
+// a rank without rows in this step: no gradients of its own, the same exchange and update as the other ranks
+static int empty_step(v21_trainer* t, float* loss_out) {
+  CHK(zero_grad(t));
+  phase_mark(t, 1); phase_mark(t, 2);
+  const bool bucketed = t->chain && dp_bucketed(t);
+  if (bucketed) {  // (the same two messages as the ranks with rows)
+    const size_t lo1 = (size_t)t->mlp->w_off[dp_split_layer(t->mlp)];
+    CHK(dp_exchange_bucket(t, 0, lo1, t->P + 1));
+    CHK(dp_exchange_bucket(t, 1, 0, lo1));
+    CHK(dp_exchange_join(t));
+  }
+  CHK(reduce_and_update(t, 1, bucketed));
+  return step_tail(t, StepLoss{loss_out, -1});
+}
+
+// ONE optimizer step of this rank's `rows` rows [first, first + rows) (through d_idx when given) of (x, y, rw), of a
+// global batch of `brows` rows, on the route csrc/routes.h decides: the preamble, the forward / activation-gradient
+// stage (route.fwd), the update stage (route.upd), the tail
 static int train_on_rows(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy, const float* rw,
                          const int* d_idx, long long first, int rows, int brows, float* loss_out, long long row0) {
   v21_mlp* m = t->mlp;
   const int L = m->L, din = m->dims[0], dout = m->dims[L];
-  if (t->chain32) return train_on_rows_chain32(t, x, ldx, y, ldy, rw, d_idx, first, rows, brows, loss_out, row0);
-  if (!t->chain) {
-    if (rows > 0) CHK(gather_batch(t, x, ldx, y, ldy, rw, d_idx, first, rows));
-    const float* yb = y ? t->d_yb : t->d_h[0];
-    return trainer_step(t, yb, y ? p16(dout) : p16(din), rows, brows, loss_out, row0);
-  }
-  hipStream_t st = t->ctx->stream;
-  int fold = 1;
   if (rows > t->max_batch) return fail(V21_ERR_ARG, "batch of %d rows exceeds max_batch %d", rows, t->max_batch);
-  bool fused_step = false;
-  DwXRows xrows{};  // x16 != nullptr: this step's layer-0 gradient operand is gathered from the resident rows
-  const bool bucketed = dp_bucketed(t);
-  const int ksplit = bucketed ? dp_split_layer(m) : 0;
-  const size_t lo1 = bucketed ? (size_t)m->w_off[ksplit] : 0;  // bucket 1 = arena [lo1, P + 1), bucket 2 = [0, lo1)
+  const bool per_layer = !t->chain && !t->chain32;
+  if (per_layer && rows > 0) CHK(gather_batch(t, x, ldx, y, ldy, rw, d_idx, first, rows));  // (ahead of the step's first mark)
   phase_mark(t, 0);
-  if (rows > 0) {
-    const bool ts_fresh = t->tstream_fresh && t->copies_ok && t->mlp->wpad_ok;  // (read before ensure_copies clears it)
+  if (rows == 0) return empty_step(t, loss_out);
+  const StepRoute route = step_route(t, rows);
+  note_route(t, route);
+  const StepLoss loss = step_loss(t, route, loss_out);
+  if (per_layer) {
+    CHK(per_layer_step(t, y ? t->d_yb : t->d_h[0], y ? p16(dout) : p16(din), rows, brows, route, loss, row0));
+  } else if (t->chain32) {  // TR_CHAIN32, TR_CHAIN32S_8 / _4
     CHK(ensure_copies(t, false));
-    // steps of >= V21_FUSED_TRAIN_ROWS rows of a stack with a compiled fused training kernel take it; below, the 32-row chain.
-    // Default: 8,193 rows for a trainer on the 16-rows-per-wave kernel (fused_train16.h; max_batch < 24,576: the chain's
-    // second round of 256 workgroups starts there -- 9,216 rows 67 against 80 us, 10,240 rows 69 against 81, 12,288 rows 72
-    // against 83, 16,384 rows 78-82 against 90-92, 20,480 rows 94 against 119), 16,384 rows for one on the 128-row kernel
-    // (fused_train.h: 24,576 rows 101 against 127, 32,768 rows 123-130 against 152-160).  The kernel's weight stream is
-    // written by the previous step's Adam pass (AdamArgs::ts), so a step is 3 launches.  (Autoencoder stack, f16, whole
-    // steps, r4; read per step: the tests force it.)
-    const StepRoute route = step_route(t, rows);  // csrc/routes.h: decide_step
-    const bool fused = route.fwd == TR_FUSED64 || route.fwd == TR_FUSED128;
-    note_route(t, route);
-    fused_step = fused;
-    bool fused_done = false;
+    ChainArgs a{};
+    static_cast<ChainModel&>(a) = chain_model32(t);
+    static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, dout, t, row0);
+    a.gs = 1.0f;  // fp32 operands: no scaling of the gradients
+    CHK(launch_chain32_args(a, t->ctx->stream, t->chain32s, route.fwd == TR_CHAIN32S_4 ? 4 : 8));
+    phase_mark(t, 1);
+    CHK(update32(t, route, rows, loss));
+  } else {  // TR_CHAIN16, TR_FUSED64 / TR_FUSED128
+    const bool ts_fresh = t->tstream_fresh && t->copies_ok && m->wpad_ok;  // (read before ensure_copies clears it)
+    CHK(ensure_copies(t, false));
+    // A fused training kernel's weight stream is written by the previous step's Adam pass (AdamArgs::ts), so such a step
+    // is 3 launches.  (Thresholds: routes.h, decide_step.)
+    bool fused = route.fwd == TR_FUSED64 || route.fwd == TR_FUSED128;
+    DwXRows xrows{};  // x16 != nullptr: this step's layer-0 gradient operand is gathered from the resident rows
     if (fused) {
       // (the LDS-staged gradient kernel only: launch_dw16 takes it from 64 batch steps of 16 rows on)
       const bool want_xr = route.upd == UP_DW16_SPLITK && (rows + 15) / 16 >= 64 && RouteEnv::read().dw_xrows;
       const int fr = launch_fused_train(t, x, ldx, y, ldy, rw, d_idx, first, rows, brows, row0, ts_fresh, want_xr ? &xrows : nullptr);
-      if (fr != V21_OK) xrows = DwXRows{};
-      if (fr == V21_OK) fused_done = true;
-      else if (t->train_arch >= 0) return fr;
-      else {  // the run-time kernel could not be loaded (it spills: marked failed): this step and every later one take the chain
+      if (fr != V21_OK) {
+        if (t->train_arch >= 0) return fr;
+        // the run-time kernel could not be loaded (it spills: marked failed): this step and every later one take the chain
+        xrows = DwXRows{};
         t->kind.train_rt = false; t->train_jit = nullptr;
-        fused_step = false;
+        fused = false;
         t->last_route.fwd = TR_CHAIN16; t->fwd_count[TR_CHAIN16] += 1; t->fwd_count[route.fwd & 7] -= 1;
       }
     }
-    if (!fused_done) { CHK(launch_chain(t, x, ldx, y, ldy, rw, d_idx, first, rows, brows, row0)); if (!t->capturing) t->n_chain_steps += 1; }
+    if (!fused) {
+      ChainArgs a{};
+      static_cast<ChainModel&>(a) = chain_model(t);
+      static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, dout, t, row0);
+      CHK(launch_chain(t, a, 0));
+      if (!t->capturing) t->n_chain_steps += 1;
+    }
     phase_mark(t, 1);
-    // Single rank, nothing to exchange: gradients, Adam and the packed copies in one launch (dw_adam.h) -- up to the
-    // batch where its 32 x 32 tiles, each pulling its operands over the WHOLE batch through one CU, lose to the
-    // 128 x 128 LDS-staged split-K kernel + an Adam launch that sums the slabs (V21_DW_SPLIT_ROWS overrides the
-    // threshold; measured r3, autoencoder stack, f16: see DESIGN.md section 3)
-    if (route.upd == UP_DW16_ADAM) {
-      if (!t->capturing) t->iter += 1;
-      // an epoch's per-step loss slot is written by the kernel itself (a device-to-device copy per step is a launch)
-      const bool in_table = loss_out && t->d_steploss && loss_out >= t->d_steploss && loss_out < t->d_steploss + t->steploss_cap;
-      phase_mark(t, 2); phase_mark(t, 3);  // (gradients + Adam are ONE launch here: reported under the Adam phase)
-      CHK(launch_dw_adam(t, rows, brows, t->capturing ? 0.f : adam_alpha(t->adam, t->iter),
-                         in_table ? (int)(loss_out - t->d_steploss) : -1));
-      phase_mark(t, 4);
-      if (t->capturing) return V21_OK;
-      if (loss_out && !in_table) HIPCHK(hipMemcpyAsync(loss_out, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-      invalidate_streams(m);
-      m->wpad_ok = true;
-      return V21_OK;
-    }
-    int nslice = 1;
-    std::vector<Dw16Args> probs;
-    dw16_problems(t, rows, brows, &nslice, probs);  // every weight gradient in one launch: [dW; db] = [H^T; 1^T] dZ
-    const DwXRows* xr = xrows.x16 ? &xrows : nullptr;
-    if (xr) probs[0].A = nullptr;
-    if (bucketed) {
-      // two launches, the upper layers first (their bucket also carries the loss slot: the batch loss is published by
-      // whichever problem holds loss_acc -- the first of THIS launch); each problem's tiles are the same workgroups doing
-      // the same sums as in the one-launch form: bit-identical gradients
-      Dw16Args& p0 = probs[0]; Dw16Args& pk = probs[ksplit];
-      pk.loss_acc = p0.loss_acc; pk.loss_out = p0.loss_out; pk.loss_out2 = p0.loss_out2; pk.sc = p0.sc;
-      p0.loss_acc = nullptr; p0.loss_out = nullptr; p0.loss_out2 = nullptr;
-      const std::vector<Dw16Args> upper(probs.begin() + ksplit, probs.end()), lower(probs.begin(), probs.begin() + ksplit);
-      CHK(launch_dw16(t->prec, upper, st, xr));
-      if (nslice > 1) CHK(reduce_slabs_range(t, nslice, (long long)lo1, (long long)t->P));
-      CHK(dp_exchange_bucket(t, 0, lo1, t->P + 1));
-      CHK(launch_dw16(t->prec, lower, st, xr));
-      if (nslice > 1) CHK(reduce_slabs_range(t, nslice, 0, (long long)lo1));
-      phase_mark(t, 2);
-      CHK(dp_exchange_bucket(t, 1, 0, lo1));
-      CHK(dp_exchange_join(t));
-    } else {
-      CHK(launch_dw16(t->prec, probs, st, xr));
-      fold = nslice > 1 && t->ctx->nranks == 1 ? nslice : 1;  // single rank: Adam sums the slabs itself
-      if (nslice > 1 && fold == 1) {
-        const long long n4 = ((long long)t->P + 3) / 4;
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, t->d_g,
-                           (const float*)t->d_slab, nslice, (long long)t->P + 4, (long long)t->P);
-        HIPCHK(hipGetLastError());
-      }
-      phase_mark(t, 2);
-    }
-  } else {
-    HIPCHK(hipMemsetAsync(t->d_g, 0, (t->P + 1) * sizeof(float), st));
-    phase_mark(t, 1); phase_mark(t, 2);
-    if (bucketed) {  // a rank without rows takes part in the same two messages
-      CHK(dp_exchange_bucket(t, 0, lo1, t->P + 1));
-      CHK(dp_exchange_bucket(t, 1, 0, lo1));
-      CHK(dp_exchange_join(t));
-    }
+    CHK(update16(t, route, rows, brows, loss, fused, xrows.x16 ? &xrows : nullptr));
   }
-  if (t->capturing) {
-    CHK(adam_and_copies(t, true, 0.f, true, fold));
-    return V21_OK;
-  }
-  t->ts_write = fused_step;  // the next step probably takes the fused kernel too: its stream comes out of this Adam pass
-  const int ru = reduce_and_update(t, true, fold, bucketed);
-  t->ts_write = false;
-  CHK(ru);
-  if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, st));
-  invalidate_streams(m);
-  m->wpad_ok = true;
-  return V21_OK;
+  return step_tail(t, loss);
+}
+int chain32_update(v21_trainer* t, int rows, float* loss_out) {
+  if (rows == 0) { phase_mark(t, 0); return empty_step(t, loss_out); }
+  const StepRoute route = step_route(t, rows);
+  note_route(t, route);  // (the joint launch ran this model's chain: the update route is what is recorded)
+  const StepLoss loss = step_loss(t, route, loss_out);
+  CHK(update32(t, route, rows, loss));
+  return step_tail(t, loss);
 }
 
 int gather_batch(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy_src,
@@ -1381,15 +1334,16 @@ static int ensure_desc(v21_trainer* t, long long n) {
   return V21_OK;
 }
 // upload descriptors [0, count) from h_desc and point the device cursor at the first
-static int publish_desc(v21_trainer* t, long long count) {
+// descriptors of the next `count` steps (step s: first row s * stride), staged, uploaded; the device cursor at the first
+static int publish_desc(v21_trainer* t, long long count, long long stride) {
   hipStream_t st = t->ctx->stream;
+  HIPCHK(hipStreamSynchronize(st));  // (the staging copy of the previous table may still be in flight)
+  for (long long s = 0; s < count; ++s) t->h_desc[s] = StepDesc{s * stride, adam_alpha(t->adam, t->iter + s + 1), (int)s};
   HIPCHK(hipMemcpyAsync(t->d_desc, t->h_desc, (size_t)count * sizeof(StepDesc), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(t->d_cur, 0, 4, st));
   t->desc_count = count; t->desc_next = 0;
   return V21_OK;
 }
-static int train_on_rows(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy, const float* rw,
-                         const int* d_idx, long long first, int rows, int brows, float* loss_out, long long row0);
 // the captured step for this batch geometry and these pointers (captured on first use); nullptr if capture failed
 static int step_graph(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy, const float* rw,
                       const int* d_idx, int rows, int brows, long long row0, hipGraphExec_t* out) {
@@ -1441,17 +1395,61 @@ static int step_graph(v21_trainer* t, const float* x, long long ldx, const float
 static void after_replay(v21_trainer* t) {
   t->iter += 1;
   t->desc_next += 1;
-  t->copies_ok = true;
-  t->nt_ok = !t->chain && !t->chain32;
-  invalidate_streams(t->mlp);
-  t->mlp->wpad_ok = true;
+  weights_updated(t, !t->chain && !t->chain32);
 }
 
-int check_row_table(const int32_t* perm, long long n) {
+// every entry of an epoch's row table names a row of the training set (an entry outside it is a GPU memory fault in the
+// gather of whichever kernel takes the step: checked on the host, one pass over n ints per epoch)
+static int check_row_table(const int32_t* perm, long long n) {
   for (long long i = 0; i < n; ++i)
     if (perm[i] < 0 || perm[i] >= n)
       return fail(V21_ERR_ARG, "row table: entry %lld = %d is outside the training set's %lld rows (the table must hold one entry per row)",
                   i, (int)perm[i], n);
+  return V21_OK;
+}
+int upload_rows(v21_trainer* t, const int32_t* perm, const int** d_idx) {
+  *d_idx = nullptr;
+  if (!perm) return V21_OK;
+  const long long n = t->n[0];
+  CHK(check_row_table(perm, n));
+  if (t->perm_cap < n) {
+    if (t->d_perm) HIPCHK(hipFree(t->d_perm));
+    HIPCHK(hipMalloc((void**)&t->d_perm, (size_t)n * sizeof(int)));
+    t->perm_cap = n;
+  }
+  HIPCHK(hipMemcpyAsync(t->d_perm, perm, (size_t)n * sizeof(int), hipMemcpyHostToDevice, t->ctx->stream));
+  *d_idx = t->d_perm;
+  return V21_OK;
+}
+int ensure_steploss(v21_trainer* t, long long cap) {
+  if (t->steploss_cap >= cap) return V21_OK;
+  HIPCHK(hipStreamSynchronize(t->ctx->stream));
+  destroy_graphs(t);  // captured steps hold the old pointer
+  if (t->d_steploss) HIPCHK(hipFree(t->d_steploss));
+  HIPCHK(hipMalloc((void**)&t->d_steploss, (size_t)cap * sizeof(float)));
+  t->steploss_cap = cap;
+  return V21_OK;
+}
+int epoch_losses(const std::vector<v21_trainer*>& trs, long long steps, long long n, double* loss) {
+  hipStream_t st = trs[0]->ctx->stream;
+  std::vector<float> h((size_t)steps * trs.size());
+  for (size_t k = 0; k < trs.size(); ++k)
+    HIPCHK(hipMemcpyAsync(h.data() + k * steps, trs[k]->d_steploss, (size_t)steps * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t k = 0; k < trs.size(); ++k) {
+    double tot = 0.0;
+    for (long long i = 0; i < steps; ++i) tot += (double)h[k * steps + i];  // each entry = batch_loss * n_b  ([K] epoch loss)
+    loss[k] = tot / (double)n;
+  }
+  return V21_OK;
+}
+int read_tickets(const std::vector<v21_trainer*>& trs, long long n, double* loss) {
+  hipStream_t st = trs[0]->ctx->stream;
+  std::vector<long long> acc(trs.size(), 0);  // 2^-32 fixed point (order-independent sum over the workgroups)
+  for (size_t k = 0; k < trs.size(); ++k) HIPCHK(hipMemcpyAsync(&acc[k], trs[k]->d_ticket, sizeof(long long), hipMemcpyDeviceToHost, st));
+  for (v21_trainer* t : trs) HIPCHK(hipMemsetAsync(t->d_ticket, 0, sizeof(long long), st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t k = 0; k < trs.size(); ++k) loss[k] = (double)acc[k] * (1.0 / 4294967296.0) / (double)n;
   return V21_OK;
 }
 extern "C" int v21_trainer_run_epoch(v21_trainer* t, const int32_t* perm, int batch, double* loss) {
@@ -1461,46 +1459,26 @@ extern "C" int v21_trainer_run_epoch(v21_trainer* t, const int32_t* perm, int ba
   hipStream_t st = t->ctx->stream;
   v21_mlp* m = t->mlp;
   const long long n = t->n[0];
-  const int R = t->ctx->nranks, rk = t->ctx->rank;
+  const int R = t->ctx->nranks;
   if (batch < 1) return fail(V21_ERR_ARG, "batch must be >= 1");
   if ((batch + R - 1) / R > t->max_batch) return fail(V21_ERR_ARG, "per-rank batch %d exceeds max_batch %d", (batch + R - 1) / R, t->max_batch);
   const int* d_idx = nullptr;
-  if (perm) {
-    CHK(check_row_table(perm, n));
-    if (t->perm_cap < n) {
-      if (t->d_perm) HIPCHK(hipFree(t->d_perm));
-      HIPCHK(hipMalloc((void**)&t->d_perm, (size_t)n * sizeof(int)));
-      t->perm_cap = n;
-    }
-    HIPCHK(hipMemcpyAsync(t->d_perm, perm, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    d_idx = t->d_perm;
-  }
+  CHK(upload_rows(t, perm, &d_idx));
   const long long steps = (n + batch - 1) / batch;
-  if (t->steploss_cap < std::max<long long>(steps, kDescRing)) {
-    HIPCHK(hipStreamSynchronize(st));
-    destroy_graphs(t);  // captured steps hold the old pointer
-    if (t->d_steploss) HIPCHK(hipFree(t->d_steploss));
-    t->steploss_cap = std::max<long long>(steps, kDescRing);
-    HIPCHK(hipMalloc((void**)&t->d_steploss, (size_t)t->steploss_cap * sizeof(float)));
-  }
+  CHK(ensure_steploss(t, std::max<long long>(steps, kDescRing)));
   const int din = m->dims[0], dout = m->dims[m->L];
   bool replay = graph_eligible(t);
   if (replay) {  // one descriptor per step of this epoch
     CHK(ensure_desc(t, std::max<long long>(steps, kDescRing)));
-    HIPCHK(hipStreamSynchronize(st));  // a preceding step_dev's copy of the staging table may still be in flight
-    for (long long s = 0; s < steps; ++s) t->h_desc[s] = StepDesc{s * batch, adam_alpha(t->adam, t->iter + s + 1), (int)s};
-    CHK(publish_desc(t, steps));
+    CHK(publish_desc(t, steps, batch));
     t->desc_epoch = true;
   }
+  const float* yy = t->y_is_x[0] ? nullptr : t->d_y[0];
   for (long long s = 0; s < steps; ++s) {
-    const long long first = s * batch;
-    const int brows = (int)std::min<long long>(batch, n - first);  // rows of the global batch
-    const long long lo = first + (long long)brows * rk / R, hi = first + (long long)brows * (rk + 1) / R;
-    const int rows = (int)(hi - lo);
-    const float* yy = t->y_is_x[0] ? nullptr : t->d_y[0];
+    const EpochBatch b = epoch_batch(t->ctx, n, batch, s);
     if (replay) {
       hipGraphExec_t exec = nullptr;
-      CHK(step_graph(t, t->d_x[0], din, yy, dout, t->d_rw[0], d_idx, rows, brows, 0, &exec));
+      CHK(step_graph(t, t->d_x[0], din, yy, dout, t->d_rw[0], d_idx, b.rows, b.brows, 0, &exec));
       if (exec) {
         HIPCHK(hipGraphLaunch(exec, st));
         after_replay(t);
@@ -1509,15 +1487,9 @@ extern "C" int v21_trainer_run_epoch(v21_trainer* t, const int32_t* perm, int ba
       // capture is not possible here: the rest of the epoch runs eagerly; the steps replayed so far are unaffected
       replay = false;
     }
-    CHK(train_on_rows(t, t->d_x[0], din, yy, dout, t->d_rw[0], d_idx, lo, rows, brows, t->d_steploss + s, lo - first));
+    CHK(train_on_rows(t, t->d_x[0], din, yy, dout, t->d_rw[0], d_idx, b.lo, b.rows, b.brows, t->d_steploss + s, b.lo - b.first));
   }
-  std::vector<float> h(steps);
-  HIPCHK(hipMemcpyAsync(h.data(), t->d_steploss, (size_t)steps * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  double tot = 0.0;
-  for (float v : h) tot += (double)v;  // each entry = batch_loss * n_b  ([K] epoch loss)
-  *loss = tot / (double)n;
-  return V21_OK;
+  return epoch_losses({t}, steps, n, loss);
 }
 
 extern "C" int v21_trainer_eval(v21_trainer* t, int which, int batch, double* loss) {
@@ -1529,49 +1501,20 @@ extern "C" int v21_trainer_eval(v21_trainer* t, int which, int batch, double* lo
   const long long n = t->n[which];
   const int din = m->dims[0], dout = m->dims[m->L];
   if (batch < 1) return fail(V21_ERR_ARG, "batch must be >= 1");
-  if (t->chain32) {  // the same in fp32 (train_chain32.h)
+  if (t->chain || t->chain32) {
+    // ONE forward-only launch of the chain kernel over all n rows (csrc/train_chain.h, train_chain32.h: fwd_only) instead
+    // of 8 launches per batch of the per-layer path: the same arithmetic as the training loss of this precision, no noise
+    // drawn (a variational head evaluates z = z_mean: include/v21.h)
     if (n > (1ll << 30)) return fail(V21_ERR_ARG, "too many rows for one validation launch");
     CHK(ensure_copies(t, false));
     ChainArgs a{};
-    static_cast<ChainModel&>(a) = chain_model32(t);
-    a.sample = 0;  // a variational head evaluates z = z_mean (include/v21.h)
-    static_cast<ChainStep&>(a) = chain_step(t->d_x[which], din, t->y_is_x[which] ? nullptr : t->d_y[which], dout,
-                                            t->d_rw[which], nullptr, 0, (int)n, (int)n, dout);
-    a.fwd_only = 1;
-    CHK(launch_chain32_args(a, st, t->chain32s));
-    long long acc = 0;
-    HIPCHK(hipMemcpyAsync(&acc, t->d_ticket, sizeof acc, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemsetAsync(t->d_ticket, 0, sizeof acc, st));
-    HIPCHK(hipStreamSynchronize(st));
-    *loss = (double)acc * (1.0 / 4294967296.0) / (double)n;
-    return V21_OK;
-  }
-  if (t->chain) {
-    // ONE forward-only launch of the chain kernel over all n rows (csrc/train_chain.h: fwd_only) instead of 8 launches
-    // per batch of the per-layer path: the same arithmetic as the training loss of this precision, no noise drawn
-    if (n > (1ll << 30)) return fail(V21_ERR_ARG, "too many rows for one validation launch");
-    CHK(ensure_copies(t, false));
-    ChainArgs a{};
-    static_cast<ChainModel&>(a) = chain_model(t);
+    static_cast<ChainModel&>(a) = t->chain32 ? chain_model32(t) : chain_model(t);
     a.sample = 0;
     static_cast<ChainStep&>(a) = chain_step(t->d_x[which], din, t->y_is_x[which] ? nullptr : t->d_y[which], dout,
                                             t->d_rw[which], nullptr, 0, (int)n, (int)n, dout);
     a.fwd_only = 1;
-    a.ncons = (int)(((n + 31) / 32 + 7) / 8 * 8);
-    a.npref = chain_prefetchers(a.ncons, 1);
-    CHK(chain_attr(t->prec));
-    const dim3 grid(a.ncons + 8 * a.npref), block(64 * kChainWaves);
-    static const bool plain_ok = !(getenv("V21_CHAIN_PLAIN") && getenv("V21_CHAIN_PLAIN")[0] == '0');  // (see launch_chain)
-    const int feat = kChainFwd | (t->gl < 0 && plain_ok ? 0 : kChainGauss);
-    if (t->prec == V21_PREC_F16) launch_chain_kernel<PrecF16>(feat, grid, block, st, a);
-    else launch_chain_kernel<PrecBF16>(feat, grid, block, st, a);
-    HIPCHK(hipGetLastError());
-    long long acc = 0;  // 2^-32 fixed point (order-independent sum over the workgroups)
-    HIPCHK(hipMemcpyAsync(&acc, t->d_ticket, sizeof acc, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemsetAsync(t->d_ticket, 0, sizeof acc, st));
-    HIPCHK(hipStreamSynchronize(st));
-    *loss = (double)acc * (1.0 / 4294967296.0) / (double)n;
-    return V21_OK;
+    CHK(t->chain32 ? launch_chain32_args(a, st, t->chain32s) : launch_chain(t, a, kChainFwd));
+    return read_tickets({t}, n, loss);
   }
   const int b = std::min(batch, t->max_batch);
   CHK(ensure_copies(t));
@@ -1619,18 +1562,10 @@ extern "C" int v21_trainer_step_dev(v21_trainer* t, const float* d_x, const floa
     // descriptors for the next kDescRing steps (first = 0: the caller's pointers are the batch); rebuilt when
     // they run out, after an epoch used the table, or when lr / the iteration count changed behind them
     CHK(ensure_desc(t, kDescRing));
-    if (t->steploss_cap < kDescRing) {
-      HIPCHK(hipStreamSynchronize(t->ctx->stream));
-      destroy_graphs(t);
-      if (t->d_steploss) HIPCHK(hipFree(t->d_steploss));
-      HIPCHK(hipMalloc((void**)&t->d_steploss, (size_t)kDescRing * sizeof(float)));
-      t->steploss_cap = kDescRing;
-    }
+    CHK(ensure_steploss(t, kDescRing));
     if (t->desc_epoch || t->desc_next >= t->desc_count || t->desc_lr != t->adam.lr ||
         t->desc_iter0 + t->desc_next != t->iter) {
-      HIPCHK(hipStreamSynchronize(t->ctx->stream));  // the staging copy may still be in flight
-      for (long long i = 0; i < kDescRing; ++i) t->h_desc[i] = StepDesc{0, adam_alpha(t->adam, t->iter + i + 1), (int)i};
-      CHK(publish_desc(t, kDescRing));
+      CHK(publish_desc(t, kDescRing, 0));
       t->desc_epoch = false; t->desc_lr = t->adam.lr; t->desc_iter0 = t->iter;
     }
     hipGraphExec_t exec = nullptr;
@@ -1687,7 +1622,6 @@ extern "C" int v21_trainer_get_grad(v21_trainer* t, float* g, size_t n) {
   HIPCHK(hipStreamSynchronize(t->ctx->stream));
   return V21_OK;
 }
-
 
 extern "C" int v21_trainer_set_vae(v21_trainer* t, float kl_weight, int sample, uint64_t seed) {
   if (!t) return fail(V21_ERR_ARG, "null trainer");
@@ -1811,5 +1745,3 @@ extern "C" int v21_trainer_use_graph(v21_trainer* t, int enable) {
   t->graph_mode = enable ? 1 : 0;
   return V21_OK;
 }
-
-

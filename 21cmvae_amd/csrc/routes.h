@@ -48,7 +48,10 @@ enum TrainUpdRoute {
   UP_NT_DWADAM = 5,     // gemm_nt_dwadam_kernel: register operands, Adam in the epilogue (gemm_nt.h; one rank)
   UP_NT_SLICED = 6,     // grouped NT launch over batch slices (+ slab sum) + [exchange] + adam_repack_kernel (fp32 chain)
 };
-struct StepRoute { int fwd = TR_NONE, upd = UP_NONE; };
+// fwd / upd: the routes.  The rest is how the step's weight gradients are cut up, for the routes that take an NT launch:
+// the workgroup tile of the f32 one-launch update (32 or 64), and the batch slices of a sliced update (nslice slices of
+// k_chunk rows; one slice: no slab to sum)
+struct StepRoute { int fwd = TR_NONE, upd = UP_NONE; int tile = 32, nslice = 1, k_chunk = 0; };
 
 // Every environment switch that changes a route.  Read per decision (a getenv is ~0.1 us; the tests set them per case).
 struct RouteEnv {
@@ -84,6 +87,46 @@ struct RouteEnv {
   }
 };
 
+// ---- the NT GEMM's cuts (gemm_nt.h), shared by every launch of it.  64 x 64 workgroup tiles once a launch has enough of
+// them to fill the chip, 32 x 32 below.  `work`: the launch's 64 x 64 tiles, every batch slice counted.
+inline int nt_tile(long long work) { return work >= 192 ? 64 : 32; }
+// the weight gradient's contraction over `rows` batch rows in slices of at most kNtMaxKPerWg rows (whole 16-row steps;
+// `whole`: one slice whatever the length).  kNtMaxKPerWg = 512 is the range a workgroup keeps in flight at once; a
+// longer one (a layer fed by 600 features) is walked in rounds by the same loop.
+struct NtSlices { int nslice, k_chunk; };
+inline NtSlices nt_slices(int rows, bool whole) {
+  int nslice = whole ? 1 : (rows + kNtMaxKPerWg - 1) / kNtMaxKPerWg;
+  if (nslice < 1) nslice = 1;
+  const int k_chunk = ((rows + nslice - 1) / nslice + 15) / 16 * 16;
+  return NtSlices{(rows + k_chunk - 1) / k_chunk, k_chunk};
+}
+inline int route_nw(const int* dims, const int* act, int l) { return act[l] == V21_ACT_GAUSS ? 2 * dims[l + 1] : dims[l + 1]; }
+// the tile of a stack's f32 weight gradients in one launch: every layer's [dW; db] problem, one slice each
+inline int dw32_tile(int L, const int* dims, const int* act) {
+  long long work = 0;
+  for (int l = 0; l < L; ++l) work += (long long)((dims[l] + 1 + 63) / 64) * ((route_nw(dims, act, l) + 63) / 64);
+  return nt_tile(work);
+}
+// The update of an f32 chain step of `rows` rows.  One rank, a step of <= kDw32MaxRows rows, 32 x 32 tiles: gradients,
+// Adam, packed streams and batch loss in ONE launch whose workgroups walk the whole batch in slabs of 256 rows
+// (dw_adam32.h: UP_DWADAM32); one contraction slice with 64 x 64 tiles: gemm_nt_dwadam_kernel (UP_NT_DWADAM); larger
+// steps and data-parallel ranks: sliced gradients, [slab sum, exchange], Adam (UP_NT_SLICED).  (Letting one workgroup
+// walk 1,024 or 2,048 rows instead of the sliced three-launch form: 71.3 against 70.6 us and 96.7 against 92.8 us per
+// step -- no gain.)
+inline StepRoute plan_update32(int L, const int* dims, const int* act, int rows, int nranks, const RouteEnv& e) {
+  StepRoute r;
+  const bool single = nranks == 1;
+  r.tile = dw32_tile(L, dims, act);
+  const bool dw32 = single && e.dw32_adam && e.dw32_lds && L <= kNtMaxGroup && r.tile == 32 && rows <= kDw32MaxRows;
+  const NtSlices sl = nt_slices(rows, dw32);
+  if (single && sl.nslice <= 1 && L <= kNtMaxGroup && e.dw32_adam)
+    r.upd = r.tile == 64 ? UP_NT_DWADAM : (rows <= kDw32MaxRows && e.dw32_lds ? UP_DWADAM32 : UP_NT_DWADAM);
+  else
+    r.upd = UP_NT_SLICED;
+  if (r.upd == UP_NT_SLICED) { const NtSlices s = nt_slices(rows, false); r.nslice = s.nslice; r.k_chunk = s.k_chunk; }
+  return r;
+}
+
 // What a trainer commits to when it is created (buffers and packed stream formats depend on it).
 struct TrainerKind {
   bool chain = false;     // 16-bit chain path (train_chain.h) -- otherwise per-layer
@@ -98,7 +141,6 @@ struct TrainerKind {
 int fused_train_arch_of(int L, const int* dims, const int* act);
 bool fused_train_rt_eligible(int L, const int* dims, const int* act);
 
-inline int route_nw(const int* dims, const int* act, int l) { return act[l] == V21_ACT_GAUSS ? 2 * dims[l + 1] : dims[l + 1]; }
 
 inline TrainerKind decide_trainer_kind(int L, const int* dims, const int* act, int precision, int max_batch, const RouteEnv& e) {
   TrainerKind k;
@@ -141,27 +183,20 @@ inline StepRoute decide_step(const TrainerKind& k, int L, const int* dims, const
                              bool fused_ready, const RouteEnv& e) {
   StepRoute r;
   if (k.chain32) {
+    r = plan_update32(L, dims, act, rows, nranks, e);
     if (k.chain32s) {
       const int rpw = e.c32s_rows == 4 || e.c32s_rows == 8 ? e.c32s_rows : (rows <= kC32sRows4Max ? 4 : 8);
       r.fwd = rpw == 4 ? TR_CHAIN32S_4 : TR_CHAIN32S_8;
     } else {
       r.fwd = TR_CHAIN32;
     }
-    const bool single = nranks == 1;
-    long long work = 0;
-    for (int l = 0; l < L; ++l) work += (long long)((dims[l] + 1 + 63) / 64) * ((route_nw(dims, act, l) + 63) / 64);
-    const bool dw32 = single && e.dw32_adam && e.dw32_lds && L <= kNtMaxGroup && work < 192 && rows <= kDw32MaxRows;
-    int nslice = dw32 ? 1 : (rows + kNtMaxKPerWg - 1) / kNtMaxKPerWg;
-    if (nslice < 1) nslice = 1;
-    const int k_chunk = ((rows + nslice - 1) / nslice + 15) / 16 * 16;
-    nslice = (rows + k_chunk - 1) / k_chunk;
-    if (single && nslice <= 1 && L <= kNtMaxGroup && e.dw32_adam)
-      r.upd = work >= 192 ? UP_NT_DWADAM : (rows <= kDw32MaxRows && e.dw32_lds ? UP_DWADAM32 : UP_NT_DWADAM);
-    else
-      r.upd = UP_NT_SLICED;
     return r;
   }
-  if (!k.chain) { r.fwd = TR_PER_LAYER; r.upd = UP_PER_LAYER; return r; }
+  if (!k.chain) {
+    const NtSlices sl = nt_slices(rows, false);
+    r.fwd = TR_PER_LAYER; r.upd = UP_PER_LAYER; r.nslice = sl.nslice; r.k_chunk = sl.k_chunk;
+    return r;
+  }
   // 16-bit chain trainers.  Steps of >= fused_rows rows of a stack with a fused training kernel take it: 8,193 rows for a
   // trainer on the 16-rows-per-wave kernel (the chain's second round of 256 workgroups starts there: 9,216 rows 67 against
   // 80 us, 12,288 rows 72 against 83, 16,384 rows 78-82 against 90-92), 16,384 rows for one on the 128-row kernel
