@@ -92,12 +92,12 @@ extern "C" int v21_ctx_create(int device, v21_ctx** out) {
   HIPCHK(hipGetDeviceCount(&n));
   if (device < 0 || device >= n) return fail(V21_ERR_ARG, "device %d out of range (%d visible)", device, n);
   HIPCHK(hipSetDevice(device));
-  v21_ctx* c = new v21_ctx();
+  std::unique_ptr<v21_ctx> c(new v21_ctx());
   c->device = device;
   hipError_t e = hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking);
-  if (e != hipSuccess) { delete c; return fail(V21_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(V21_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
   c->stream = c->own;
-  *out = c;
+  *out = c.release();
   return V21_OK;
 }
 extern "C" int v21_ctx_destroy(v21_ctx* c) {
@@ -111,7 +111,6 @@ extern "C" int v21_ctx_destroy(v21_ctx* c) {
   if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
   for (hipEvent_t e : c->slice_done) if (e) hipEventDestroy(e);
   if (c->probe_stream) { hipStreamSynchronize(c->probe_stream); hipStreamDestroy(c->probe_stream); }
-  if (c->d_probe) hipFree(c->d_probe);
   delete c;
   return V21_OK;
 }
@@ -351,14 +350,10 @@ extern "C" int v21_debug_clock_probe_start(v21_ctx* c, double duration_ms, doubl
   if (!(duration_ms > 0.0) || duration_ms > 2000.0 || !(period_us >= 1.0)) return fail(V21_ERR_ARG, "clock probe: duration in (0, 2000] ms, period >= 1 us");
   if (!c->probe_stream) HIPCHK(hipStreamCreateWithFlags(&c->probe_stream, hipStreamNonBlocking));
   const int nmax = (int)std::min(65536.0, duration_ms * 1000.0 / period_us + 2.0);
-  if (c->probe_cap < nmax) {
-    if (c->d_probe) HIPCHK(hipFree(c->d_probe));
-    HIPCHK(hipMalloc((void**)&c->d_probe, ((size_t)2 * nmax + 1) * sizeof(unsigned long long)));
-    c->probe_cap = nmax;
-  }
-  HIPCHK(hipMemsetAsync(c->d_probe, 0, ((size_t)2 * c->probe_cap + 1) * sizeof(unsigned long long), c->probe_stream));
+  CHK(c->d_probe.reserve((size_t)2 * nmax + 1));
+  HIPCHK(hipMemsetAsync(c->d_probe, 0, c->d_probe.n * sizeof(unsigned long long), c->probe_stream));
   // (s_memrealtime: 100 MHz -> 100 ticks per microsecond)
-  hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, c->probe_stream, c->d_probe, c->probe_cap,
+  hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, c->probe_stream, c->d_probe.get(), c->probe_cap(),
                      (unsigned long long)(period_us * 100.0), (unsigned long long)(duration_ms * 100000.0));
   HIPCHK(hipGetLastError());
   return V21_OK;
@@ -367,10 +362,10 @@ extern "C" int v21_debug_clock_probe_read(v21_ctx* c, double* ghz_mean, double* 
   CHK(use(c));
   if (!ghz_mean || !ghz_min || !ghz_max || !samples) return fail(V21_ERR_ARG, "null argument");
   if (!c->probe_stream || !c->d_probe) return fail(V21_ERR_STATE, "no clock probe was started");
-  std::vector<unsigned long long> h((size_t)2 * c->probe_cap + 1);
+  std::vector<unsigned long long> h(c->d_probe.n);
   HIPCHK(hipMemcpyAsync(h.data(), c->d_probe, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->probe_stream));
   HIPCHK(hipStreamSynchronize(c->probe_stream));
-  const int n = (int)h[(size_t)2 * c->probe_cap];
+  const int n = (int)h[(size_t)2 * c->probe_cap()];
   *samples = n;
   *ghz_mean = *ghz_min = *ghz_max = 0.0;
   if (n < 2) return fail(V21_ERR_STATE, "the clock probe took %d samples", n);

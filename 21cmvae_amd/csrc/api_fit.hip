@@ -15,7 +15,7 @@ static int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_l
   auto kern = din <= kFitMaxIn ? jac_fisher_kernel<kFitMaxIn> : jac_fisher_kernel<kFisherMaxIn>;
   return jac_slices(m, route, n, d_lnl || d_grad, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {
     hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, m->ctx->stream, wy, wj, d_data, ld_data, rpd, row0 + r0,
-                       m->lk_w.as<const float>(), d_F + r0 * din * din, d_lnl ? d_lnl + r0 : nullptr, d_grad ? d_grad + r0 * din : nullptr,
+                       m->lk_w.get(), d_F + r0 * din * din, d_lnl ? d_lnl + r0 : nullptr, d_grad ? d_grad + r0 * din : nullptr,
                        rows, din, dout);
     return V21_OK;
   });
@@ -39,21 +39,21 @@ static int fit_run(v21_mlp* m, int route, long long n, const float* d_data, long
                    float* d_F) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0];
-  CHK(m->fit.reserve((size_t)n * sizeof(FitRow)));
-  CHK(m->fF.reserve((size_t)n * din * din * sizeof(float)));
-  CHK(m->fl.reserve((size_t)n * sizeof(float)));
-  CHK(m->fg.reserve((size_t)n * din * sizeof(float)));
-  CHK(m->fit_cnt.reserve((size_t)(o.max_iter + 1) * sizeof(int)));
-  FitRow* fs = m->fit.as<FitRow>();
-  int* cnt = m->fit_cnt.as<int>();
-  float *F = m->fF.as<float>(), *l = m->fl.as<float>(), *g = m->fg.as<float>();
+  CHK(m->fit.reserve((size_t)n));
+  CHK(m->fF.reserve((size_t)n * din * din));
+  CHK(m->fl.reserve((size_t)n));
+  CHK(m->fg.reserve((size_t)n * din));
+  CHK(m->fit_cnt.reserve((size_t)(o.max_iter + 1)));
+  FitRow* fs = m->fit.get();
+  int* cnt = m->fit_cnt.get();
+  float *F = m->fF.get(), *l = m->fl.get(), *g = m->fg.get();
   const dim3 grid((unsigned)((n + 255) / 256));
   HIPCHK(hipMemsetAsync(cnt, 0, (size_t)(o.max_iter + 1) * sizeof(int), st));
-  hipLaunchKernelGGL(fit_init_kernel, grid, dim3(256), 0, st, fs, m->jxt.as<float>(), m->jfac.as<float>(), n, din, o.lambda0);
+  hipLaunchKernelGGL(fit_init_kernel, grid, dim3(256), 0, st, fs, m->jxt.get(), m->jfac.get(), n, din, o.lambda0);
   HIPCHK(hipGetLastError());
   for (int it = 0; it <= o.max_iter; ++it) {
     CHK(fisher_run(m, route, n, F, l, g, d_data, ld_data, rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    hipLaunchKernelGGL(fit_lm_kernel, grid, dim3(256), 0, st, fs, m->jxt.as<float>(), (const float*)l, (const float*)g, (const float*)F, n,
+    hipLaunchKernelGGL(fit_lm_kernel, grid, dim3(256), 0, st, fs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, n,
                        din, it == 0 ? 1 : 0, o.xtol, cnt + it);
     HIPCHK(hipGetLastError());
     if (it < o.max_iter && (it + 1) % o.check_every == 0) {
@@ -72,7 +72,7 @@ static int fit_run(v21_mlp* m, int route, long long n, const float* d_data, long
   HIPCHK(hipGetLastError());
   if (!d_F) return V21_OK;
   CHK(jac_prep(m, x_hat, x_dtype, din, n, 1));
-  return fisher_run(m, route, n, d_F, nullptr, nullptr, m->lk_data.as<const float>(), 0, 1, 0, prec, flags | V21_FWD_IN_TRANSFORM);
+  return fisher_run(m, route, n, d_F, nullptr, nullptr, m->lk_data.get(), 0, 1, 0, prec, flags | V21_FWD_IN_TRANSFORM);
 }
 
 // has_data: a data matrix of n_data rows was handed in (at least one, dividing n); without one n_data is ignored
@@ -99,7 +99,7 @@ extern "C" int v21_mlp_fisher_dev(v21_mlp* m, const float* d_x, int64_t ldx, int
   CHK(jac_args(m, d_x && d_fisher, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFisher));
   if (n == 0) return V21_OK;
   CHK(jac_prep(m, d_x, V21_DTYPE_F32, ldx, n, flags & V21_FWD_IN_TRANSFORM));
-  return fisher_run(m, jac_route(m, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, m->lk_data.as<const float>(), 0, 1, 0, precision,
+  return fisher_run(m, jac_route(m, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, m->lk_data.get(), 0, 1, 0, precision,
                     flags);
 }
 
@@ -113,7 +113,7 @@ extern "C" int v21_mlp_fisher(v21_mlp* m, const void* x, int x_dtype, int64_t n,
   return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, din * din + din + 3, [&](long long r0, long long rows, float* dF) {
     float* dl = lnl ? dF + rows * din * din : nullptr;
     float* dg = grad ? dF + rows * (din * din + 1) : nullptr;
-    CHK(fisher_run(m, route, rows, dF, dl, dg, m->lk_data.as<const float>(), 0, 1, 0, precision, flags));
+    CHK(fisher_run(m, route, rows, dF, dl, dg, m->lk_data.get(), 0, 1, 0, precision, flags));
     CHK(to_host(m, fisher + r0 * din * din, dF, (size_t)rows * din * din * sizeof(float)));
     if (lnl) CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
     return grad ? to_host(m, grad + r0 * din, dg, (size_t)rows * din * sizeof(float)) : V21_OK;
@@ -128,7 +128,7 @@ extern "C" int v21_mlp_fit_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64
   CHK(jac_args(m, d_x0 && d_x_hat && d_lnl, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFit));
   CHK(fit_check(n, d_data != nullptr, n_data, o));
   if (n == 0) return V21_OK;
-  const float* data = d_data ? d_data : m->lk_data.as<const float>();
+  const float* data = d_data ? d_data : m->lk_data.get();
   const long long ld = d_data ? m->dims[m->L] : 0, rpd = d_data ? n / n_data : 1;
   const int route = fit_route(m, flags, d_fisher != nullptr);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
@@ -143,10 +143,10 @@ extern "C" int v21_mlp_fit(v21_mlp* m, const void* x0, int x_dtype, int64_t n, c
   if (n == 0) return V21_OK;
   const int din = m->dims[0], dout = m->dims[m->L];
   if (data) {
-    CHK(m->fdata.reserve((size_t)n_data * dout * sizeof(float)));
+    CHK(m->fdata.reserve((size_t)n_data * dout));
     HIPCHK(hipMemcpyAsync(m->fdata.p, data, (size_t)n_data * dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
   }
-  const float* d_data = data ? m->fdata.as<const float>() : m->lk_data.as<const float>();
+  const float* d_data = data ? m->fdata.get() : m->lk_data.get();
   const long long ld = data ? dout : 0, rpd = data ? n / n_data : 1;
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   const int route = fit_route(m, flags, fisher != nullptr);

@@ -111,7 +111,7 @@ extern "C" int v21_mlp_create(v21_ctx* ctx, int n_layers, const int* dims, const
   int n_gauss = 0;
   for (int i = 0; i < n_layers; ++i) n_gauss += act[i] == V21_ACT_GAUSS;
   if (n_gauss > 1) return fail(V21_ERR_UNSUPPORTED, "at most one V21_ACT_GAUSS layer per stack");
-  v21_mlp* m = new v21_mlp();
+  std::unique_ptr<v21_mlp> m(new v21_mlp());
   m->ctx = ctx;
   m->L = n_layers;
   m->dims.assign(dims, dims + n_layers + 1);
@@ -123,30 +123,16 @@ extern "C" int v21_mlp_create(v21_ctx* ctx, int n_layers, const int* dims, const
   }
   m->nparams = (size_t)o;
   m->maxdim = *std::max_element(m->dims.begin(), m->dims.end());
-  hipError_t e = hipMalloc((void**)&m->d_w, (m->nparams + kArenaPad) * sizeof(float));
-  if (e != hipSuccess) { delete m; return fail(V21_ERR_HIP, "hipMalloc weights: %s", hipGetErrorString(e)); }
-  hipMemsetAsync(m->d_w, 0, (m->nparams + kArenaPad) * sizeof(float), ctx->stream);
+  CHK(m->d_w.zeroed(m->nparams + kArenaPad, ctx->stream));
   m->fused_id = fused_id_of(n_layers, dims, act);
-  *out = m;
+  *out = m.release();
   return V21_OK;
 }
 extern "C" int v21_mlp_destroy(v21_mlp* m) {
   if (!m) return V21_OK;
   hipSetDevice(m->ctx->device);
   hipStreamSynchronize(m->ctx->stream);
-  hipFree(m->d_w);
-  for (int i = 0; i < 3; ++i) if (m->d_stream[i]) hipFree(m->d_stream[i]);
-  if (m->d_mean) hipFree(m->d_mean);
-  for (int i = 0; i < 2; ++i) if (m->d_act[i]) hipFree(m->d_act[i]);
-  for (int i = 0; i < 2; ++i) if (m->d_small[i]) hipFree(m->d_small[i]);
-  if (m->d_wt) hipFree(m->d_wt);
-  if (m->d_xpad) hipFree(m->d_xpad);
-  for (int i = 0; i < 3; ++i) { if (m->d_cfw[i]) hipFree(m->d_cfw[i]); if (m->d_cbw[i]) hipFree(m->d_cbw[i]); }
-  if (m->d_tin) hipFree(m->d_tin);
-  if (m->d_xs) hipFree(m->d_xs);
-  if (m->d_xs64) hipFree(m->d_xs64);
-  if (m->d_ys) hipFree(m->d_ys);
-  delete m;  // (and with it the DevBuf members)
+  delete m;
   return V21_OK;
 }
 extern "C" int v21_mlp_num_params(const v21_mlp* m, size_t* n) {
@@ -188,7 +174,7 @@ extern "C" int v21_mlp_set_input_transform(v21_mlp* m, const v21_affine_in* t) {
   m->tin = *t;
   m->has_tin = true;
   CHK(use(m->ctx));
-  if (!m->d_tin) HIPCHK(hipMalloc((void**)&m->d_tin, sizeof(v21_affine_in)));
+  CHK(m->d_tin.reserve(1));
   HIPCHK(hipMemcpyAsync(m->d_tin, &m->tin, sizeof(v21_affine_in), hipMemcpyHostToDevice, m->ctx->stream));
   HIPCHK(hipStreamSynchronize(m->ctx->stream));
   return V21_OK;
@@ -199,7 +185,7 @@ extern "C" int v21_mlp_set_output_transform(v21_mlp* m, const v21_affine_out* t)
   invalidate_streams(m);
   if (!t) { m->has_tout = false; return V21_OK; }
   if (t->n != m->dims[m->L] || !t->mean) return fail(V21_ERR_ARG, "output transform: n = %d, stack output = %d", t->n, m->dims[m->L]);
-  if (!m->d_mean) HIPCHK(hipMalloc((void**)&m->d_mean, (size_t)t->n * sizeof(float)));
+  CHK(m->d_mean.reserve((size_t)t->n));
   HIPCHK(hipMemcpyAsync(m->d_mean, t->mean, (size_t)t->n * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
   HIPCHK(hipStreamSynchronize(m->ctx->stream));
   m->out_std = t->std;
@@ -217,8 +203,8 @@ static int ensure_stream(v21_mlp* m, int prec) {
   if (m->stream_ok[prec]) return V21_OK;
   int total, padded;
   stream_geometry(m, prec, &total, &padded);
-  unsigned char*& dst = m->d_stream[prec];
-  if (!dst) HIPCHK(hipMalloc((void**)&dst, (size_t)padded * 1024));
+  Dev<unsigned char>& dst = m->d_stream[prec];
+  CHK(dst.reserve((size_t)padded * 1024));
   PackArgs pa{};
   pa.w = m->d_w;
   pa.mean = m->has_tout ? m->d_mean : nullptr;
@@ -275,6 +261,23 @@ static int launch_gemm_prec(int prec, const GemmArgs& g, hipStream_t st) {
   return fail(V21_ERR_ARG, "precision %d unknown", prec);
 }
 
+// rows of src (float32 / float64, pitch lds) through the input transform -> dst (pitch ldd)
+template <class T>
+static int launch_affine_in(v21_mlp* m, float* dst, long long ldd, const T* src, long long lds, long long rows) {
+  const long long tot = rows * m->dims[0];
+  hipLaunchKernelGGL(affine_in_kernel<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, m->ctx->stream, dst, ldd, src, lds, rows, m->tin);
+  HIPCHK(hipGetLastError());
+  return V21_OK;
+}
+// the output transform on rows of y, in place
+static int launch_affine_out(v21_mlp* m, float* y, long long ldy, long long rows) {
+  const long long tot = rows * m->dims[m->L];
+  hipLaunchKernelGGL(affine_out_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, m->ctx->stream, y, ldy, rows, m->dims[m->L],
+                     m->out_std, m->d_mean.get());
+  HIPCHK(hipGetLastError());
+  return V21_OK;
+}
+
 // one dense layer: out = act(in W + b)
 static int dense_forward(v21_mlp* m, int l, const float* in, long long ldin, float* out, long long ldout,
                          int rows, int prec, hipStream_t st) {
@@ -291,23 +294,14 @@ static int forward_generic(v21_mlp* m, const float* d_x, long long ldx, long lon
                            int prec, int flags) {
   hipStream_t st = m->ctx->stream;
   const long long chunk = 8192;
-  if (m->act_rows < chunk) {
-    for (int i = 0; i < 2; ++i) {
-      if (m->d_act[i]) HIPCHK(hipFree(m->d_act[i]));
-      HIPCHK(hipMalloc((void**)&m->d_act[i], (size_t)chunk * m->maxdim * sizeof(float)));
-    }
-    m->act_rows = chunk;
-  }
+  for (Dev<float>& a : m->d_act) CHK(a.reserve((size_t)chunk * m->maxdim));
   for (long long r0 = 0; r0 < n; r0 += chunk) {
     const int rows = (int)std::min(chunk, n - r0);
     const float* in = d_x + r0 * ldx;
     long long ldin = ldx;
     int cur = 0;
     if ((flags & V21_FWD_IN_TRANSFORM) && m->has_tin) {
-      const long long tot = (long long)rows * m->dims[0];
-      hipLaunchKernelGGL(affine_in_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m->d_act[0],
-                         (long long)m->dims[0], in, ldx, (long long)rows, m->tin);
-      HIPCHK(hipGetLastError());
+      CHK(launch_affine_in(m, m->d_act[0], m->dims[0], in, ldx, rows));
       in = m->d_act[0]; ldin = m->dims[0]; cur = 1;
     }
     for (int l = 0; l < m->L; ++l) {
@@ -317,12 +311,7 @@ static int forward_generic(v21_mlp* m, const float* d_x, long long ldx, long lon
       CHK(dense_forward(m, l, in, ldin, out, ldo, rows, prec, st));
       in = out; ldin = ldo; cur ^= 1;
     }
-    if ((flags & V21_FWD_OUT_TRANSFORM) && m->has_tout) {
-      const long long tot = (long long)rows * m->dims[m->L];
-      hipLaunchKernelGGL(affine_out_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_y + r0 * ldy,
-                         ldy, (long long)rows, m->dims[m->L], m->out_std, m->d_mean);
-      HIPCHK(hipGetLastError());
-    }
+    if ((flags & V21_FWD_OUT_TRANSFORM) && m->has_tout) CHK(launch_affine_out(m, d_y + r0 * ldy, ldy, rows));
   }
   return V21_OK;
 }
@@ -341,31 +330,44 @@ static int forward_chain(v21_mlp* m, const float* d_x, long long ldx, long long 
 // internal: this device call belongs to a host call that found no run-time kernel when it started -- do not pick one up
 // half way (one result array must not hold two roundings); decide_forward (routes.h) knows the flag
 static_assert(V21_FWD_RT_LATCH_OFF == 0x200, "routes.h and api_forward.hip agree on the internal flag");
-// the run-time kernel of this stack: asked for on first need; true when its code object can be launched now
-static bool jit_ready_now(v21_mlp* m, int precision) {
-  if (m->fused_id >= 0) return false;
+// the run-time kernel of (stack, precision), asked for at most once; nullptr: the stack cannot have one, or V21_JIT=0
+static v21::JitKernel* jit_kernel(v21_mlp* m, int precision) {
   if (!m->jit_asked[precision]) {
     m->jit[precision] = v21::jit_request(m->L, m->dims.data(), m->act.data(), precision);
     m->jit_asked[precision] = true;
   }
-  return m->jit[precision] && v21::jit_state(m->jit[precision]) == v21::JIT_READY;
+  return m->jit[precision];
 }
+static bool jit_ready(v21::JitKernel* k) { return k && v21::jit_state(k) == v21::JIT_READY; }
 
-extern "C" int v21_mlp_forward_dev(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_y, int64_t ldy,
-                                   int precision, int flags) {
-  if (!m || !d_x || !d_y) return fail(V21_ERR_ARG, "null argument");
+// The argument checks of the forward family, before anything is allocated or enqueued.  `dev`: device rows with pitches
+// (v21_mlp_forward_dev, v21_debug_forward_clocked); otherwise dense host rows of x_dtype (v21_mlp_forward), where a call
+// without rows is checked no further.  Leaves the context's device current for n > 0.
+static int fwd_args(v21_mlp* m, bool ptrs, bool dev, long long n, long long ldx, long long ldy, int x_dtype, int precision, int flags) {
+  if (!m || !ptrs) return fail(V21_ERR_ARG, "null argument");
+  if (!dev) {
+    if (n < 0) return fail(V21_ERR_ARG, "negative row count");
+    if (x_dtype != V21_DTYPE_F32 && x_dtype != V21_DTYPE_F64) return fail(V21_ERR_ARG, "x_dtype %d unknown", x_dtype);
+    if (n == 0) return V21_OK;
+  }
   if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
-  if (n < 0 || ldx < m->dims[0] || ldy < m->dims[m->L]) return fail(V21_ERR_ARG, "bad shape: n=%lld ldx=%lld ldy=%lld", (long long)n, (long long)ldx, (long long)ldy);
+  if (dev && (n < 0 || ldx < m->dims[0] || ldy < m->dims[m->L])) return fail(V21_ERR_ARG, "bad shape: n=%lld ldx=%lld ldy=%lld", n, ldx, ldy);
   if (n == 0) return V21_OK;
-  CHK(use(m->ctx));
   if ((flags & V21_FWD_IN_TRANSFORM) && !m->has_tin) return fail(V21_ERR_STATE, "input transform requested but not set");
   if ((flags & V21_FWD_OUT_TRANSFORM) && !m->has_tout) return fail(V21_ERR_STATE, "output transform requested but not set");
+  return use(m->ctx);
+}
+// the one place that records which route served a device call (v21_mlp_last_route)
+static void note_route(v21_mlp* m, int route) { m->last_route = route; m->route_count[route] += 1; }
+
+// n > 0 checked rows on the device -> the route csrc/routes.h decides (every forward entry point ends here)
+static int forward_rows(v21_mlp* m, const float* d_x, long long ldx, long long n, float* d_y, long long ldy, int precision, int flags) {
   // which route: csrc/routes.h (decide_forward) -- the same function answers v21_route_forward
-  FwdQuery q{m->L, m->dims.data(), m->act.data(), m->fused_id >= 0, 0, precision, (long long)n, flags, (long long)ldy};
+  FwdQuery q{m->L, m->dims.data(), m->act.data(), m->fused_id >= 0, 0, precision, n, flags, ldy};
   // few rows: one latency-oriented launch per layer beats one wave walking the whole stack in f32
   // (and the K-loop GEMM of the generic path in any precision)
   if (decide_forward(q) == FWD_SMALL) {
-    m->last_route = FWD_SMALL; m->route_count[FWD_SMALL] += 1;
+    note_route(m, FWD_SMALL);
     return forward_small(m, d_x, ldx, n, d_y, ldy, precision, flags);
   }
   // a stack outside archs.h: the same fused kernel, instantiated for it at run time (jit.h).  The first call asks for
@@ -375,52 +377,47 @@ extern "C" int v21_mlp_forward_dev(v21_mlp* m, const float* d_x, int64_t ldx, in
   const bool force_jit = (flags & V21_FWD_FORCE_JIT) != 0;
   if ((m->fused_id < 0 || force_jit) && !(flags & (V21_FWD_FORCE_GENERIC | V21_FWD_FORCE_CHAIN | V21_FWD_RT_LATCH_OFF)) && ldy < (1ll << 21) &&
       (!(flags & V21_FWD_IN_TRANSFORM) || m->dims[0] <= 8)) {
-    if (!m->jit_asked[precision]) {
-      m->jit[precision] = v21::jit_request(m->L, m->dims.data(), m->act.data(), precision);
-      m->jit_asked[precision] = true;
-    }
-    if (force_jit && m->jit[precision]) v21::jit_wait(m->jit[precision], -1);  // (diagnostics: this route or an error)
-    if (m->jit[precision] && v21::jit_state(m->jit[precision]) == v21::JIT_READY) jk = m->jit[precision];
+    v21::JitKernel* k = jit_kernel(m, precision);
+    if (force_jit && k) v21::jit_wait(k, -1);  // (diagnostics: this route or an error)
+    if (jit_ready(k)) jk = k;
     if (force_jit && !jk) {
       std::string why = "not eligible, or V21_JIT=0";
-      if (m->jit[precision]) v21::jit_state(m->jit[precision], &why);
+      if (k) v21::jit_state(k, &why);
       return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: no run-time kernel for this stack: %s", why.c_str());
     }
   }
   q.jit = jk ? 2 : 0;
-  const int route = decide_forward(q);
-  m->last_route = route; m->route_count[route] += 1;
+  int route = decide_forward(q);
+  FusedArgs a{};
+  hipError_t rt = hipSuccess;  // the run-time kernel's launch, should the route be that
+  if (route == FWD_FUSED || route == FWD_FUSED_RT) {  // the fused kernel's arguments, compiled or run-time
+    CHK(ensure_stream(m, precision));
+    a.x = d_x; a.ldx = ldx; a.y = d_y; a.ldy = ldy; a.n_rows = n;
+    a.stream = m->d_stream[precision];
+    const bool tout = (flags & V21_FWD_OUT_TRANSFORM) != 0;
+    a.out_std = tout ? m->out_std : 1.0f;
+    a.out_mean_scale = tout ? 1.0f : 0.0f;
+    a.in_transform = (flags & V21_FWD_IN_TRANSFORM) ? 1 : 0;
+    if (a.in_transform) a.tin = m->tin;
+#ifdef V21_FUSED_STAMP  // diagnostic build only: where the cycle stamps go
+    a.dbg = (unsigned long long*)(getenv("V21_FUSED_DBG_PTR") ? strtoull(getenv("V21_FUSED_DBG_PTR"), nullptr, 0) : 0ull);
+#endif
+  }
+  if (route == FWD_FUSED_RT) {
+    rt = v21::jit_launch(jk, m->ctx->device, a, m->ctx->stream);
+    if (rt != hipSuccess) (void)hipGetLastError();
+    // the code object could not be loaded or needs scratch memory (jit_launch marked it failed): this call and every
+    // later one take the table-driven route, and that is the route recorded
+    if (rt != hipSuccess && !force_jit) { q.jit = 0; route = decide_forward(q); }
+  }
+  note_route(m, route);
   if (route == FWD_TABLE) return forward_chain(m, d_x, ldx, n, d_y, ldy, precision, flags);
   if (route == FWD_GENERIC) return forward_generic(m, d_x, ldx, n, d_y, ldy, precision, flags);
-  CHK(ensure_stream(m, precision));
-  FusedArgs a{};
-  a.x = d_x; a.ldx = ldx; a.y = d_y; a.ldy = ldy; a.n_rows = n;
-  a.stream = m->d_stream[precision];
-  const bool tout = (flags & V21_FWD_OUT_TRANSFORM) != 0;
-  a.out_std = tout ? m->out_std : 1.0f;
-  a.out_mean_scale = tout ? 1.0f : 0.0f;
-  a.in_transform = (flags & V21_FWD_IN_TRANSFORM) ? 1 : 0;
-  if (a.in_transform) a.tin = m->tin;
-#ifdef V21_FUSED_STAMP  // diagnostic build only: where the cycle stamps go
-  a.dbg = (unsigned long long*)(getenv("V21_FUSED_DBG_PTR") ? strtoull(getenv("V21_FUSED_DBG_PTR"), nullptr, 0) : 0ull);
-#endif
-  if (jk) {
-    const hipError_t e = v21::jit_launch(jk, m->ctx->device, a, m->ctx->stream);
-    if (e == hipSuccess) return V21_OK;
-    (void)hipGetLastError();
-    if (force_jit) {
-      std::string why;
-      v21::jit_state(jk, &why);
-      return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: %s (%s)", why.c_str(), hipGetErrorString(e));
-    }
-    // the code object could not be loaded or needs scratch memory (jit_launch marked it failed): this call and every
-    // later one take the table-driven route
-    m->route_count[route] -= 1;
-    q.jit = 0;
-    const int r2 = decide_forward(q);
-    m->last_route = r2; m->route_count[r2] += 1;
-    if (r2 == FWD_TABLE) return forward_chain(m, d_x, ldx, n, d_y, ldy, precision, flags);
-    return forward_generic(m, d_x, ldx, n, d_y, ldy, precision, flags);
+  if (route == FWD_FUSED_RT) {
+    if (rt == hipSuccess) return V21_OK;
+    std::string why;
+    v21::jit_state(jk, &why);
+    return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: %s (%s)", why.c_str(), hipGetErrorString(rt));
   }
   if (m->clk_stamps) {  // v21_debug_forward_clocked: the clock-stamped instantiation of the same kernel
     a.dbg = m->clk_stamps;
@@ -429,6 +426,11 @@ extern "C" int v21_mlp_forward_dev(v21_mlp* m, const float* d_x, int64_t ldx, in
   }
   HIPCHK(g_fused[m->fused_id].fn[precision](a, m->ctx->stream));
   return V21_OK;
+}
+extern "C" int v21_mlp_forward_dev(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_y, int64_t ldy,
+                                   int precision, int flags) {
+  CHK(fwd_args(m, d_x && d_y, true, n, ldx, ldy, V21_DTYPE_F32, precision, flags));
+  return n == 0 ? V21_OK : forward_rows(m, d_x, ldx, n, d_y, ldy, precision, flags);
 }
 extern "C" int v21_debug_forward_clocked(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_y, int64_t ldy, int precision,
                                          int flags, unsigned long long* d_stamps) {
@@ -450,11 +452,7 @@ extern "C" int v21_mlp_jit(v21_mlp* m, int precision, int wait_ms, int* status) 
   if (m->fused_id >= 0) { *status = 1; return V21_OK; }  // compiled into the library (archs.h)
   std::string why;
   if (!v21::jit_eligible(m->L, m->dims.data(), m->act.data(), &why)) return fail(V21_ERR_UNSUPPORTED, "no fused kernel for this stack: %s", why.c_str());
-  if (!m->jit_asked[precision]) {
-    m->jit[precision] = v21::jit_request(m->L, m->dims.data(), m->act.data(), precision);
-    m->jit_asked[precision] = true;
-  }
-  v21::JitKernel* k = m->jit[precision];
+  v21::JitKernel* k = jit_kernel(m, precision);
   if (!k) return fail(V21_ERR_UNSUPPORTED, "run-time compilation is switched off (V21_JIT=0) and no cached kernel exists");
   int s = v21::jit_state(k);
   if (s == v21::JIT_COMPILING && wait_ms != 0) s = v21::jit_wait(k, wait_ms);
@@ -473,29 +471,17 @@ extern "C" int v21_jit_prebuild(int n_layers, const int* dims, const int* act, i
 }
 
 extern "C" int v21_mlp_forward(v21_mlp* m, const void* x, int x_dtype, int64_t n, float* y, int precision, int flags) {
-  if (!m || !x || !y) return fail(V21_ERR_ARG, "null argument");
-  if (n < 0) return fail(V21_ERR_ARG, "negative row count");
-  if (x_dtype != V21_DTYPE_F32 && x_dtype != V21_DTYPE_F64) return fail(V21_ERR_ARG, "x_dtype %d unknown", x_dtype);
+  flags &= 0xFF;
+  CHK(fwd_args(m, x && y, false, n, 0, 0, x_dtype, precision, flags));
   if (n == 0) return V21_OK;
-  CHK(use(m->ctx));
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0], dout = m->dims[m->L];
   const long long chunk = 1 << 18;  // rows per host round trip
-  const long long need = std::min<long long>(n, chunk);
-  if (m->stage_rows < need) {
-    if (m->d_xs) HIPCHK(hipFree(m->d_xs));
-    if (m->d_ys) HIPCHK(hipFree(m->d_ys));
-    if (m->d_xs64) HIPCHK(hipFree(m->d_xs64));
-    HIPCHK(hipMalloc((void**)&m->d_xs, (size_t)need * din * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&m->d_xs64, (size_t)need * din * sizeof(double)));
-    HIPCHK(hipMalloc((void**)&m->d_ys, (size_t)need * dout * sizeof(float)));
-    m->stage_rows = need;
-  }
+  const size_t need = (size_t)std::min<long long>(n, chunk);
+  CHK(m->d_xs.reserve(need * din));
+  CHK(m->d_xs64.reserve(need * din));
+  CHK(m->d_ys.reserve(need * dout));
   std::vector<float> tmp;
-  flags &= 0xFF;
-  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
-  if ((flags & V21_FWD_IN_TRANSFORM) && !m->has_tin) return fail(V21_ERR_STATE, "input transform requested but not set");
-  if ((flags & V21_FWD_OUT_TRANSFORM) && !m->has_tout) return fail(V21_ERR_STATE, "output transform requested but not set");
   const bool tin = (flags & V21_FWD_IN_TRANSFORM) != 0;
   // par_transform of one value ON THE HOST, for the few-row route below: par_transform.h's two functions themselves
   // (__host__ __device__; r5: until r4 the host used libm's log10f and the device the float64 log10 rounded to float32,
@@ -516,17 +502,12 @@ extern "C" int v21_mlp_forward(v21_mlp* m, const void* x, int x_dtype, int64_t n
     // few rows: transform (if asked) and pad the rows on the host, so the first layer reads the staging buffer in
     // place (two launches fewer than transforming on the device)
     const long long ldp = p16(din);
-    if (m->stage_pad_rows < n) {
-      if (m->d_xpad) HIPCHK(hipFree(m->d_xpad));
-      HIPCHK(hipMalloc((void**)&m->d_xpad, (size_t)(n + 2) * ldp * sizeof(float)));
-      m->stage_pad_rows = n;
-    }
+    CHK(m->d_xpad.reserve((size_t)(n + 2) * ldp));
     tmp.assign((size_t)n * ldp, 0.f);
     for (long long r = 0; r < n; ++r)
       for (int j = 0; j < din; ++j) tmp[(size_t)r * ldp + j] = host_value(r, j);
     HIPCHK(hipMemcpyAsync(m->d_xpad, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    m->last_route = FWD_SMALL; m->route_count[FWD_SMALL] += 1;
-    CHK(forward_small(m, m->d_xpad, ldp, n, m->d_ys, dout, precision, (flags & ~V21_FWD_IN_TRANSFORM) | V21_FWD_X_PADDED));
+    CHK(forward_rows(m, m->d_xpad, ldp, n, m->d_ys, dout, precision, (flags & ~V21_FWD_IN_TRANSFORM) | V21_FWD_X_PADDED));  // (FWD_SMALL, as decided)
     HIPCHK(hipMemcpyAsync(y, m->d_ys, (size_t)n * dout * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return V21_OK;
@@ -534,7 +515,7 @@ extern "C" int v21_mlp_forward(v21_mlp* m, const void* x, int x_dtype, int64_t n
   // The route is decided ONCE per host call: a call that starts before the run-time kernel of its stack has arrived
   // keeps the table-driven route for every chunk and slice (the two routes round differently: ADVICE r4), the next call
   // takes the kernel.  v21_mlp_jit(mlp, precision, -1) waits for it: bit-stable results from the first call on.
-  const bool rt_off = m->fused_id < 0 && !(flags & (V21_FWD_FORCE_JIT | V21_FWD_FORCE_GENERIC | V21_FWD_FORCE_CHAIN)) && !jit_ready_now(m, precision);
+  const bool rt_off = m->fused_id < 0 && !(flags & (V21_FWD_FORCE_JIT | V21_FWD_FORCE_GENERIC | V21_FWD_FORCE_CHAIN)) && !jit_ready(jit_kernel(m, precision));
   for (long long r0 = 0; r0 < n; r0 += chunk) {
     const long long rows = std::min(chunk, n - r0);
     int fl = flags | (rt_off ? V21_FWD_RT_LATCH_OFF : 0);
@@ -543,10 +524,7 @@ extern "C" int v21_mlp_forward(v21_mlp* m, const void* x, int x_dtype, int64_t n
       // branch, preprocess.py:74-108), the float32 cast after the map as Keras does it [K]
       const double* xd = (const double*)x + r0 * din;
       HIPCHK(hipMemcpyAsync(m->d_xs64, xd, (size_t)rows * din * sizeof(double), hipMemcpyHostToDevice, st));
-      const long long tot = rows * din;
-      hipLaunchKernelGGL(affine_in_kernel<double>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m->d_xs, (long long)din,
-                         (const double*)m->d_xs64, (long long)din, rows, m->tin);
-      HIPCHK(hipGetLastError());
+      CHK(launch_affine_in(m, m->d_xs, din, (const double*)m->d_xs64, din, rows));
       fl &= ~V21_FWD_IN_TRANSFORM;
     } else {
       const float* src;
@@ -566,7 +544,7 @@ extern "C" int v21_mlp_forward(v21_mlp* m, const void* x, int x_dtype, int64_t n
     // 0.46 ms of kernel + 2.2 ms of copy one after the other -> 0.12 + 2.2 ms).
     constexpr long long kSliceRows = 16384;
     if (rows <= kSliceRows) {
-      CHK(v21_mlp_forward_dev(m, m->d_xs, din, rows, m->d_ys, dout, precision, fl));
+      CHK(forward_rows(m, m->d_xs, din, rows, m->d_ys, dout, precision, fl));
       HIPCHK(hipMemcpyAsync(y + r0 * dout, m->d_ys, (size_t)rows * dout * sizeof(float), hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       continue;
@@ -583,7 +561,7 @@ extern "C" int v21_mlp_forward(v21_mlp* m, const void* x, int x_dtype, int64_t n
     int k = 0;
     for (long long s0 = 0; s0 < rows; s0 += per, ++k) {
       const long long srows = std::min(per, rows - s0);
-      CHK(v21_mlp_forward_dev(m, m->d_xs + s0 * din, din, srows, m->d_ys + s0 * dout, dout, precision, fl | V21_FWD_NO_SMALL));
+      CHK(forward_rows(m, m->d_xs + s0 * din, din, srows, m->d_ys + s0 * dout, dout, precision, fl | V21_FWD_NO_SMALL));
       // (an event is reused every other slice: the copy that waited on its previous record was enqueued before this one)
       HIPCHK(hipEventRecord(c->slice_done[k & 1], st));
       HIPCHK(hipStreamWaitEvent(c->copy_stream, c->slice_done[k & 1], 0));
@@ -605,13 +583,8 @@ static int forward_small(v21_mlp* m, const float* d_x, long long ldx, long long 
   if (!m->d_wt) {
     long long ot = 0;
     for (int l = 0; l < L; ++l) { m->wt_off.push_back(ot); ot += (long long)(m->nw(l) + 32) * p16(m->dims[l]); }
-    HIPCHK(hipMalloc((void**)&m->d_wt, (size_t)(ot + 64) * sizeof(float)));
-    HIPCHK(hipMemsetAsync(m->d_wt, 0, (size_t)(ot + 64) * sizeof(float), st));
-    for (int i = 0; i < 2; ++i) {
-      const size_t nb = (size_t)(V21_SMALL_BATCH_ROWS + 32) * p16(m->maxdim) * sizeof(float);
-      HIPCHK(hipMalloc((void**)&m->d_small[i], nb));
-      HIPCHK(hipMemsetAsync(m->d_small[i], 0, nb, st));
-    }
+    CHK(m->d_wt.zeroed((size_t)(ot + 64), st));
+    for (Dev<float>& s : m->d_small) CHK(s.zeroed((size_t)(V21_SMALL_BATCH_ROWS + 32) * p16(m->maxdim), st));
   }
   if (!m->wt_ok) {
     AdamArgs a{};
@@ -630,15 +603,13 @@ static int forward_small(v21_mlp* m, const float* d_x, long long ldx, long long 
   if (flags & V21_FWD_X_PADDED) {
     a0 = d_x; lda0 = ldx;
   } else if ((flags & V21_FWD_IN_TRANSFORM) && m->has_tin) {
-    const long long tot = (long long)rows * m->dims[0];
-    hipLaunchKernelGGL(affine_in_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m->d_small[0], ld0, d_x,
-                       ldx, (long long)rows, m->tin);
+    CHK(launch_affine_in(m, m->d_small[0], ld0, d_x, ldx, rows));
   } else {
     const long long tot = (long long)rows * ld0;
-    hipLaunchKernelGGL(copy_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m->d_small[0], ld0, d_x,
+    hipLaunchKernelGGL(copy_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m->d_small[0].get(), ld0, d_x,
                        ldx, (long long)rows, m->dims[0]);
+    HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipGetLastError());
   int cur = 0;
   bool unpre_done = false;
   for (int l = 0; l < L; ++l) {
@@ -661,12 +632,7 @@ static int forward_small(v21_mlp* m, const float* d_x, long long ldx, long long 
     CHK(launch_nt(prec, grp, st));
     cur ^= 1;
   }
-  if ((flags & V21_FWD_OUT_TRANSFORM) && m->has_tout && !unpre_done) {
-    const long long tot = (long long)rows * m->dims[L];
-    hipLaunchKernelGGL(affine_out_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_y, ldy, (long long)rows,
-                       m->dims[L], m->out_std, m->d_mean);
-    HIPCHK(hipGetLastError());
-  }
+  if ((flags & V21_FWD_OUT_TRANSFORM) && m->has_tout && !unpre_done) CHK(launch_affine_out(m, d_y, ldy, rows));
   return V21_OK;
 }
 
@@ -675,20 +641,11 @@ static int ensure_chain_stream(v21_mlp* m, int prec) {
   if (m->cfw_ok[prec]) return V21_OK;
   hipStream_t st = m->ctx->stream;
   const int L = m->L;
-  const int pc = prec == V21_PREC_F32 ? 1 : 0;
-  const int esz = pc ? 4 : 2;
-  if (m->cfw_off[pc].empty()) {
-    long long of = 0, ob = 0;  // elements
-    for (int l = 0; l < L; ++l) {
-      const int K = m->dims[l], N = m->nw(l);
-      m->cfw_off[pc].push_back(of); of += (long long)((N + 31) / 32) * (pc ? chain32_frags(K) * 256 : chain_steps(K) * 512);
-      m->cbw_off[pc].push_back(ob); ob += (long long)((K + 31) / 32) * (pc ? chain32_frags(N) * 256 : chain_steps(N) * 512);
-    }
-    m->cfw_bytes[pc] = of * esz; m->cbw_bytes[pc] = ob * esz;
-  }
+  ChainLayout& lay = m->clay[prec == V21_PREC_F32 ? 1 : 0];
+  if (lay.fw_off.empty()) lay = chain_layout(m, prec == V21_PREC_F32 ? CHAIN_FMT_32 : CHAIN_FMT_16);
   if (!m->d_cfw[prec]) {
-    HIPCHK(hipMalloc(&m->d_cfw[prec], (size_t)m->cfw_bytes[pc] + kChainStreamSlack)); HIPCHK(hipMemsetAsync(m->d_cfw[prec], 0, (size_t)m->cfw_bytes[pc] + kChainStreamSlack, st));
-    HIPCHK(hipMalloc(&m->d_cbw[prec], (size_t)m->cbw_bytes[pc] + kChainStreamSlack)); HIPCHK(hipMemsetAsync(m->d_cbw[prec], 0, (size_t)m->cbw_bytes[pc] + kChainStreamSlack, st));
+    CHK(m->d_cfw[prec].zeroed((size_t)lay.fw_bytes + kChainStreamSlack, st));
+    CHK(m->d_cbw[prec].zeroed((size_t)lay.bw_bytes + kChainStreamSlack, st));
   }
   AdamArgs a{};  // the arena -> the packed streams (the trainer's repacking kernel without the Adam update)
   a.w = m->d_w; a.n = (long long)m->nparams; a.L = L; a.do_adam = 0; a.skip_nt = 1;
@@ -696,8 +653,7 @@ static int ensure_chain_stream(v21_mlp* m, int prec) {
   for (int l = 0; l < L; ++l) {
     AdamLayer& al = a.lt[l];
     al.w_off = m->w_off[l]; al.K = m->dims[l]; al.N = m->nw(l);
-    al.fw_off = m->cfw_off[pc][l]; al.bw_off = m->cbw_off[pc][l];
-    al.KS = pc ? chain32_frags(al.K) : chain_steps(al.K); al.NS = pc ? chain32_frags(al.N) : chain_steps(al.N);
+    lay.layer(al, l);
   }
   hipLaunchKernelGGL(adam_repack_kernel, dim3((unsigned)((m->nparams + 255) / 256)), dim3(256), 0, st, a);
   HIPCHK(hipGetLastError());
@@ -710,6 +666,7 @@ static int forward_chain(v21_mlp* m, const float* d_x, long long ldx, long long 
   const int L = m->L;
   const int pc = prec == V21_PREC_F32 ? 1 : 0;
   CHK(ensure_chain_stream(m, prec));
+  const ChainLayout& lay = m->clay[pc];
   CHK(chain_attr(prec));
   ChainArgs a{};
   a.L = L;
@@ -717,15 +674,13 @@ static int forward_chain(v21_mlp* m, const float* d_x, long long ldx, long long 
     ChainLayer& c = a.lt[l];
     c.K = m->dims[l]; c.N = m->nw(l);
     c.gauss = m->act[l] == V21_ACT_GAUSS;
-    c.KS = pc ? chain32_frags(c.K) : chain_steps(c.K); c.NT = (c.N + 31) / 32;
-    c.NS = pc ? chain32_frags(c.N) : chain_steps(c.N); c.KT = (c.K + 31) / 32;
+    lay.layer(c, l);
     c.relu = m->act[l] == V21_ACT_RELU;
     c.mask_tile = -1;  // no backward pass: no ReLU masks kept
-    c.fw_off = m->cfw_off[pc][l] / (pc ? 4 : 8); c.bw_off = m->cbw_off[pc][l] / (pc ? 4 : 8);  // units of one lane's 16 bytes
     c.b_off = m->b_off[l];
   }
   a.fw = m->d_cfw[prec]; a.bw = m->d_cbw[prec]; a.w = m->d_w;
-  a.fw_bytes = m->cfw_bytes[pc]; a.bw_bytes = 0;  // (the prefetchers touch the forward stream only)
+  a.fw_bytes = lay.fw_bytes; a.bw_bytes = 0;  // (the prefetchers touch the forward stream only)
   a.zcap_layer = -1;
   a.sample = 0;  // a variational head evaluates z = z_mean (include/v21.h)
   a.x = d_x; a.ldx = ldx; a.rows = (int)n;

@@ -2,7 +2,8 @@
 // now api_base.hip (errors, contexts, memory, events, communicator, diagnostics), api_forward.hip (dense stacks and the
 // forward routes), api_trainer.hip (trainers, the step machinery, captured steps), api_sweep.hip and api_joint.hip --
 // all behind the unchanged include/v21.h).  Kernels live in the headers included below; a kernel template is
-// instantiated by the unit that launches it, non-template kernels have internal linkage.
+// instantiated by the unit that launches it, non-template kernels have internal linkage.  Device memory of a handle is
+// owned by its Dev members (below): nothing here or in the units frees a handle's buffer by hand.
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -40,6 +42,7 @@ constexpr int kStampSlots = 64;
 #include "dw_adam.h"
 #include "routes.h"
 
+namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip)
 using namespace v21;
 
 // ---- errors: v21_last_error() returns the calling thread's last message (api_base.hip)
@@ -64,6 +67,42 @@ constexpr size_t kChainStreamSlack = 8192;
 // floats behind the P parameters of an arena: the loss slot, then room to round P + 1 up to whole shards of up to
 // 64 ranks (sharded data-parallel Adam works on nranks * ceil((P + 1) / nranks) elements in place)
 constexpr size_t kArenaPad = 4 + 64;
+
+// ---- device memory: every device allocation of a handle (v21_ctx, v21_mlp, v21_trainer, v21_sweep, v21_joint) is a Dev
+// member of it.  A grow-only allocation of T elements: reserve(count) reallocates only to grow (the old block is freed
+// first, so two copies are never live; capacity 0 if the allocation fails), zeroed(count, st) also clears those elements
+// on st, release() frees, and so does the destructor -- which is why every v21_*_destroy makes the device current and
+// drains the handle's stream(s) BEFORE it deletes the handle, and why a create function that fails half way leaks nothing.
+// Converts to T*; get() spells the pointer out where a type is deduced from it (kernel-launch arguments).
+template <class T>
+struct Dev {
+  T* p = nullptr;
+  size_t n = 0;  // capacity, elements
+  Dev() = default;
+  Dev(const Dev&) = delete;
+  Dev& operator=(const Dev&) = delete;
+  ~Dev() { release(); }
+  int reserve(size_t count) {
+    if (n >= count) return V21_OK;
+    if (p) { HIPCHK(hipFree(p)); p = nullptr; }
+    n = 0;
+    HIPCHK(hipMalloc((void**)&p, count * sizeof(T)));
+    n = count;
+    return V21_OK;
+  }
+  int zeroed(size_t count, hipStream_t st) {
+    CHK(reserve(count));
+    HIPCHK(hipMemsetAsync(p, 0, count * sizeof(T), st));
+    return V21_OK;
+  }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+  T* get() const { return p; }
+  operator T*() const { return p; }
+};
 
 // ---- context (api_base.hip)
 typedef void* nccl_comm;  // (rccl.h is not included: librccl is dlopen'ed by api_base.hip)
@@ -93,34 +132,30 @@ struct v21_ctx {
   hipEvent_t slice_done[2] = {nullptr, nullptr};
   // v21_debug_clock_probe_*: the sampling wave runs on its own stream beside the kernels under test
   hipStream_t probe_stream = nullptr;
-  unsigned long long* d_probe = nullptr;
-  int probe_cap = 0;
+  Dev<unsigned long long> d_probe;  // 2 * probe_cap() stamps, then the sample count
+  int probe_cap() const { return d_probe.n ? (int)((d_probe.n - 1) / 2) : 0; }
 };
 int use(v21_ctx* c);
 
-// a grow-only device allocation: reserve(bytes) reallocates only to grow (freeing first; capacity 0 if the allocation
-// fails), release() frees, and so does the destructor (v21_mlp_destroy makes the device current before it deletes)
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  int reserve(size_t bytes) {
-    if (cap >= bytes) return V21_OK;
-    if (p) { HIPCHK(hipFree(p)); p = nullptr; }
-    cap = 0;
-    HIPCHK(hipMalloc(&p, bytes));
-    cap = bytes;
-    return V21_OK;
+// ---- the chain kernels' packed weight streams (train_chain.h, train_chain32.h, train_chain32s.h), by format: where layer
+// l's fragments start in the forward and the backward stream (elements), the fragment and tile counts of a width, the
+// streams' bytes (an allocation adds kChainStreamSlack).  A trainer's Adam pass writes the streams that the forward route
+// of its stack reads: both take the layout from here.
+enum ChainFmt { CHAIN_FMT_16, CHAIN_FMT_32, CHAIN_FMT_32S };  // 16-bit; fp32 in 32-feature tiles; fp32 in 64-feature tiles
+struct ChainLayout {
+  ChainFmt fmt = CHAIN_FMT_16;
+  std::vector<long long> fw_off, bw_off;
+  long long fw_bytes = 0, bw_bytes = 0;
+  int esize() const { return fmt == CHAIN_FMT_16 ? 2 : 4; }
+  int frags(int d) const { return fmt == CHAIN_FMT_16 ? chain_steps(d) : fmt == CHAIN_FMT_32S ? chain32s_frags(d) : chain32_frags(d); }
+  int tiles(int d) const { return fmt == CHAIN_FMT_32S ? (d + 63) / 64 : (d + 31) / 32; }
+  // layer l (c.K -> c.N) for a chain kernel: KS / NT / NS / KT, the offsets in units of one lane's 16 bytes
+  void layer(ChainLayer& c, int l) const {
+    c.KS = frags(c.K); c.NT = tiles(c.N); c.NS = frags(c.N); c.KT = tiles(c.K);
+    c.fw_off = fw_off[l] / (16 / esize()); c.bw_off = bw_off[l] / (16 / esize());
   }
-  void release() {
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T> T* as() const { return static_cast<T*>(p); }
+  // ... and for the Adam pass that packs the streams: KS / NS, the offsets in elements
+  void layer(AdamLayer& a, int l) const { a.fw_off = fw_off[l]; a.bw_off = bw_off[l]; a.KS = frags(a.K); a.NS = frags(a.N); }
 };
 
 // ---- dense stack (api_forward.hip)
@@ -130,38 +165,32 @@ struct v21_mlp {
   std::vector<int> dims, act;
   std::vector<long long> w_off, b_off;
   size_t nparams = 0;
-  float* d_w = nullptr;  // nparams (+4 pad) floats
+  Dev<float> d_w;  // nparams + kArenaPad floats
   int fused_id = -1;
-  unsigned char* d_stream[3] = {nullptr, nullptr, nullptr};
+  Dev<unsigned char> d_stream[3];
   bool stream_ok[3] = {false, false, false};
   bool has_tin = false, has_tout = false;
   v21_affine_in tin{};
   float out_std = 1.f;
-  float* d_mean = nullptr;
-  // generic path scratch
-  float* d_act[2] = {nullptr, nullptr};
-  long long act_rows = 0;
+  Dev<float> d_mean;
+  Dev<float> d_act[2];  // generic path scratch
   // host-API staging
-  float *d_xs = nullptr, *d_ys = nullptr;
-  double* d_xs64 = nullptr;  // float64 rows of v21_mlp_forward awaiting the float64 par_transform
-  long long stage_rows = 0;
+  Dev<float> d_xs, d_ys;
+  Dev<double> d_xs64;  // float64 rows of v21_mlp_forward awaiting the float64 par_transform
   int maxdim = 0;
   bool wpad_ok = false;  // false after the arena was rewritten from outside a trainer (set_weights)
   // small-batch latency path: fp32 W^T copies + two padded activation images
-  float* d_wt = nullptr;
+  Dev<float> d_wt;
   std::vector<long long> wt_off;
   bool wt_ok = false;
-  float* d_small[2] = {nullptr, nullptr};
-  float* d_xpad = nullptr;  // host-API staging of zero-padded input rows
-  long long stage_pad_rows = 0;
+  Dev<float> d_small[2];
+  Dev<float> d_xpad;  // host-API staging of zero-padded input rows
   // one-launch forward of ANY stack up to 512 wide in f16 / bf16 (train_chain.h, FORWARD mode): the packed forward
   // weight stream per precision (+ the backward stream the packing kernel writes beside it), rebuilt lazily
-  void* d_cfw[3] = {nullptr, nullptr, nullptr};
-  void* d_cbw[3] = {nullptr, nullptr, nullptr};
+  Dev<unsigned char> d_cfw[3], d_cbw[3];
   bool cfw_ok[3] = {false, false, false};
-  std::vector<long long> cfw_off[2], cbw_off[2];  // element offsets per layer; [0]: 16-bit streams, [1]: fp32 (train_chain32.h)
-  long long cfw_bytes[2] = {0, 0}, cbw_bytes[2] = {0, 0};
-  v21_affine_in* d_tin = nullptr;           // device copy of the input transform
+  ChainLayout clay[2];  // [0]: 16-bit streams, [1]: fp32 (train_chain32.h); filled on first use
+  Dev<v21_affine_in> d_tin;  // device copy of the input transform
   // fused_fwd<this stack, precision> instantiated at run time (jit.h) for stacks outside archs.h; requested on the
   // first large forward call, used once its code object is there
   v21::JitKernel* jit[3] = {nullptr, nullptr, nullptr};
@@ -174,15 +203,32 @@ struct v21_mlp {
   int nw(int l) const { return act[l] == V21_ACT_GAUSS ? 2 * dims[l + 1] : dims[l + 1]; }
   // parameter Jacobian, log-likelihood, Fisher matrices and fits (api_jacobian.hip, api_fit.hip): the likelihood record
   // (d, 1 / sigma^2; out_dim floats each) and the route of the last call (routes.h: JacRoute).  Buffers, grown on demand:
-  DevBuf lk_data, lk_w;
-  DevBuf lk_ws;      // y and jac of one kLkSlice slice of rows before they are reduced
-  DevBuf jxt, jfac;  // transformed rows and their factors, pitch in_dim (jac_prep)
-  DevBuf hin, hout;  // the host forms' chunk: its raw rows (float32 / float64; a fit's x_hat) and its results
-  DevBuf fit, fF, fl, fg, fit_cnt, fdata;  // fit state, F / ln L / gradient of its rows, running rows per iteration, data
+  Dev<float> lk_data, lk_w;
+  Dev<float> lk_ws;      // y and jac of one kLkSlice slice of rows before they are reduced
+  Dev<float> jxt, jfac;  // transformed rows and their factors, pitch in_dim (jac_prep)
+  Dev<double> hin;       // the host forms' chunk: its raw rows (float32 or float64; a fit's x_hat) ...
+  Dev<float> hout;       // ... and its results
+  Dev<FitRow> fit;       // fit state (fit_kernels.h), then F / ln L / gradient of its rows, running rows per iteration, data
+  Dev<float> fF, fl, fg, fdata;
+  Dev<int> fit_cnt;
   bool has_lk = false;
   int last_jac_route = 0;
   long long jac_route_count[4] = {0, 0, 0, 0};
 };
+// the layout of this stack's chain streams in `fmt`
+static inline ChainLayout chain_layout(const v21_mlp* m, ChainFmt fmt) {
+  ChainLayout y;
+  y.fmt = fmt;
+  const long long frag = fmt == CHAIN_FMT_16 ? 512 : 256;  // elements of one fragment
+  long long of = 0, ob = 0;
+  for (int l = 0; l < m->L; ++l) {
+    const int K = m->dims[l], N = m->nw(l);
+    y.fw_off.push_back(of); of += (long long)y.tiles(N) * y.frags(K) * frag;
+    y.bw_off.push_back(ob); ob += (long long)y.tiles(K) * y.frags(N) * frag;
+  }
+  y.fw_bytes = of * y.esize(); y.bw_bytes = ob * y.esize();
+  return y;
+}
 // api_forward.hip: fused_fwd's packed weight stream of this stack (built on first use)
 int mlp_fused_stream(v21_mlp* m, int prec, const unsigned char** stream);
 // api_jacobian.hip, shared with api_fit.hip.  The host forms work in chunks of kJacHostChunk rows; the likelihood
@@ -223,57 +269,51 @@ struct v21_trainer {
   v21_adam adam{1e-3f, 0.9f, 0.999f, 1e-7f};
   long long iter = 0;
   size_t P = 0;
-  float *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;  // P + 4 floats; d_g[P] = loss slot
-  float* d_x[2] = {nullptr, nullptr};
-  unsigned short* d_x16 = nullptr; long long ldx16 = 0;  // the training inputs as 16-bit operand elements (fused training kernels: ChainStep::x16)
+  Dev<float> d_g, d_m, d_v;  // P + kArenaPad floats; d_g[P] = loss slot
+  // the data sets (0: training, 1: validation), each replaced as a whole by v21_trainer_set_data; n[which] == 0: none.
+  // d_y is a view: of d_ybuf, or of d_x where the targets are the inputs (y_is_x)
+  Dev<float> d_x[2], d_ybuf[2], d_rw[2];
   float* d_y[2] = {nullptr, nullptr};
-  float* d_rw[2] = {nullptr, nullptr};
+  Dev<unsigned short> d_x16; long long ldx16 = 0;  // the training inputs as 16-bit operand elements (fused training kernels: ChainStep::x16)
   long long n[2] = {0, 0};
   bool y_is_x[2] = {false, false};
-  int* d_perm = nullptr;
-  long long perm_cap = 0;
+  Dev<int> d_perm;
   long long Bp = 0;  // row pitch of the transposed buffers (batch padded to 32, + slack)
-  std::vector<float*> d_h, d_ht, d_dz, d_dzt;
-  float *d_wt = nullptr, *d_wp = nullptr;
+  std::vector<Dev<float>> d_h, d_ht, d_dz, d_dzt;
+  Dev<float> d_wt, d_wp;
   std::vector<long long> wt_off, wp_off;
   bool copies_ok = false;
   bool nt_ok = false;  // the fp32 W^T / padded-W copies of the per-layer path are fresh (chain steps skip them)
-  float* d_yb = nullptr;
-  float* d_wb = nullptr;
-  float* d_rowloss = nullptr;
-  float* d_steploss = nullptr;
-  long long steploss_cap = 0;
-  float* d_evalsum = nullptr;
-  float* d_slab = nullptr;  // split-K partial gradients: max_slices x (P + 4)
+  Dev<float> d_yb, d_wb, d_rowloss;
+  Dev<float> d_steploss;  // an epoch's per-step losses (ensure_steploss)
+  Dev<float> d_evalsum;
+  Dev<float> d_slab;  // split-K partial gradients: max_slices x (P + 4)
   int max_slices = 1;
   // variational latent layer (V21_ACT_GAUSS, A13): gl = its index or -1
   int gl = -1;
-  float *d_zs = nullptr, *d_dzs = nullptr, *d_dzst = nullptr;  // [z_mean | z_log_var], its gradient, transposed
-  float* d_klrow = nullptr;
+  Dev<float> d_zs, d_dzs, d_dzst;  // [z_mean | z_log_var], its gradient, transposed
+  Dev<float> d_klrow;
   float kl_weight = 0.f;
   int sample = 1;
   unsigned long long seed = 0;
   // one-kernel forward + activation-gradient chain (train_chain.h; f16 / bf16 stacks up to 512 wide)
   bool chain = false;
   // the same chain in fp32 (train_chain32.h): f32 stacks up to 512 wide without a variational layer; d_fw / d_bw then
-  // hold fp32 fragments, fw_off / bw_off count floats, and the weight-gradient operands are d_ht / d_dzt
+  // hold fp32 fragments and the weight-gradient operands are d_ht / d_dzt
   bool chain32 = false;
   bool chain32s = false;  // ... with the 8-row kernel and its stream format (train_chain32s.h): trainers of small batches
-  int* d_jobs = nullptr;  // train_chain32s.h: C32sJob rows
-  int c32_frags(int d) const { return chain32s ? chain32s_frags(d) : chain32_frags(d); }
-  int c32_tiles(int d) const { return chain32s ? (d + 63) / 64 : (d + 31) / 32; }
-  void *d_fw = nullptr, *d_bw = nullptr;
-  long long fw_bytes = 0, bw_bytes = 0;
-  std::vector<long long> fw_off, bw_off;  // element offsets per layer
-  float* d_partial = nullptr;
-  unsigned* d_ticket = nullptr;
-  std::vector<void*> d_ht16, d_dzt16;  // fragment-ordered weight-gradient operands (train_chain.h)
+  Dev<int> d_jobs;  // train_chain32s.h: C32sJob rows
+  Dev<unsigned char> d_fw, d_bw;  // the packed streams (+ kChainStreamSlack), allocated once at creation
+  ChainLayout lay;                // ... and their layout in this trainer's format
+  Dev<float> d_partial;
+  Dev<unsigned long long> d_ticket;  // the batch loss as 2^-32 fixed point (16 bytes)
+  std::vector<Dev<unsigned short>> d_ht16, d_dzt16;  // fragment-ordered weight-gradient operands (train_chain.h)
   // large steps of f16 / bf16 trainers whose stack has a compiled fused training kernel (fused_train.h; archs.h: T1 ..):
   // index into the registry of api_trainer.hip or -1, and that kernel's packed stream (rebuilt before every launch)
   int train_arch = -1;
   v21::JitKernel* train_jit = nullptr;  // r5: ... or its run-time instantiation for a stack outside archs.h (jit.hip; asked for at creation)
   bool train16 = false;  // the fused training kernel on 16 rows per wave (fused_train16.h): the stream below is in ITS format
-  unsigned char* d_tstream = nullptr;
+  Dev<unsigned char> d_tstream;
   int tstream_total = 0, tstream_padded = 0;
   std::vector<int> ts_first;    // first fragment of every virtual layer (2 L - 1 of them)
   bool ts_write = false;        // the Adam pass that ends the current step also rewrites d_tstream (the step took the fused kernel)
@@ -284,19 +324,18 @@ struct v21_trainer {
   StepRoute last_route;
   long long fwd_count[8] = {0, 0, 0, 0, 0, 0, 0, 0}, upd_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool tstream_fresh = false;   // d_tstream holds the arena's current weights (cleared by every ensure_copies: any other step, eval, sweep, joint)
-  int* d_dworder = nullptr;            // dw_adam.h: tile order per XCD (two-dimensional blocks per layer)
+  Dev<int> d_dworder;                  // dw_adam.h: tile order per XCD (two-dimensional blocks per layer)
   int dw_xper = 0;
   long long BS = 0;                    // batch steps of 16 per feature tile
-  unsigned long long* d_stamps = nullptr;
+  Dev<unsigned long long> d_stamps;
   bool stamps_on = false;  // v21_trainer_enable_stamps: a stamp costs the stamping wave ~600 cycles (s_memtime + its wait), eleven per launch
   // ---- replayed steps (hipGraph).  One optimizer step is captured once per (rows, global rows, data pointers)
   // and replayed; what differs between steps comes from a device table of StepDesc (train_kernels.h) that the
   // host fills for the steps ahead: an epoch's steps in run_epoch, the next kDescRing steps in step_dev.
   int graph_mode = 0;         // 0: off (default, see graph_eligible), 1: asked for (v21_trainer_use_graph)
   bool capturing = false;     // train_on_rows is being recorded, not run
-  StepDesc* d_desc = nullptr; StepDesc* h_desc = nullptr;  // device table, page-locked staging copy
-  long long desc_cap = 0;
-  int* d_cur = nullptr;       // index of the next step's descriptor
+  Dev<StepDesc> d_desc; StepDesc* h_desc = nullptr;  // device table, page-locked staging copy of as many entries
+  Dev<int> d_cur;             // index of the next step's descriptor
   long long desc_next = 0, desc_count = 0;  // host mirror of *d_cur, entries valid in the table
   long long desc_iter0 = -1; float desc_lr = -1.f; bool desc_epoch = false;  // what the table was built for
   // r5: HIP-event stamps of an eager step (v21_trainer_phase_timing / v21_trainer_phase_times): two events per step -- its
@@ -311,11 +350,6 @@ struct v21_trainer {
 };
 constexpr long long kDescRing = 1024;
 static inline StepCtx step_ctx(const v21_trainer* t) { return t->capturing ? StepCtx{t->d_desc, t->d_cur} : StepCtx{nullptr, nullptr}; }
-static inline int zalloc(float** p, size_t nfloat, hipStream_t st) {
-  HIPCHK(hipMalloc((void**)p, nfloat * sizeof(float)));
-  HIPCHK(hipMemsetAsync(*p, 0, nfloat * sizeof(float), st));
-  return V21_OK;
-}
 
 // ---- shared between the units
 // one grouped launch of the latency-oriented NT GEMM (gemm_nt.h); instantiated per unit and group type
@@ -383,7 +417,7 @@ int chain32_update(v21_trainer* t, int rows, float* loss_out);  // api_trainer.h
 // transport: blocking, staged through that stream; null transport / one rank: nothing)
 int comm_allreduce_on(v21_ctx* c, float* d_buf, size_t n, hipStream_t st);
 int refresh_dw32_table(const std::vector<v21_trainer*>& trs, Dw32Model* d_tab, std::vector<Dw32Model>& h_tab, int* max_blocks, bool* ok, hipStream_t st);  // api_sweep.hip
-int refresh_dw_adam_table(const std::vector<v21_trainer*>& tr, DwAdamModel** d_tab, std::vector<DwAdamModel>& h_tab, hipStream_t st);  // api_trainer.hip
+int refresh_dw_adam_table(const std::vector<v21_trainer*>& tr, Dev<DwAdamModel>& d_tab, std::vector<DwAdamModel>& h_tab, hipStream_t st);  // api_trainer.hip
 int launch_nt_many(int prec, std::vector<NtArgs>& probs, hipStream_t st);  // api_trainer.hip
 void launch_chain_forward_mode(int prec, dim3 grid, dim3 block, hipStream_t st, const ChainArgs& a);  // api_trainer.hip
 

@@ -57,8 +57,8 @@ extern "C" int v21_mlp_set_likelihood(v21_mlp* m, const float* data, const float
   for (int k = 0; k < n; ++k)
     if (!(inv_var[k] >= 0.f) || !std::isfinite(inv_var[k])) return fail(V21_ERR_ARG, "likelihood: inv_var[%d] = %g", k, (double)inv_var[k]);
   CHK(use(m->ctx));
-  CHK(m->lk_data.reserve((size_t)dout * sizeof(float)));
-  CHK(m->lk_w.reserve((size_t)dout * sizeof(float)));
+  CHK(m->lk_data.reserve((size_t)dout));
+  CHK(m->lk_w.reserve((size_t)dout));
   HIPCHK(hipMemcpyAsync(m->lk_data.p, data, (size_t)dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
   HIPCHK(hipMemcpyAsync(m->lk_w.p, inv_var, (size_t)dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
   HIPCHK(hipStreamSynchronize(m->ctx->stream));
@@ -91,11 +91,11 @@ int jac_route(v21_mlp* m, int flags, long long ldy) {
 
 int jac_prep(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n, int tin) {
   const int din = m->dims[0];
-  CHK(m->jxt.reserve((size_t)n * din * sizeof(float)));
-  CHK(m->jfac.reserve((size_t)n * din * sizeof(float)));
+  CHK(m->jxt.reserve((size_t)n * din));
+  CHK(m->jfac.reserve((size_t)n * din));
   const long long tot = n * din;
   const dim3 grid((unsigned)((tot + 255) / 256));
-  float *xt = m->jxt.as<float>(), *fac = m->jfac.as<float>();
+  float *xt = m->jxt.get(), *fac = m->jfac.get();
   if (dtype == V21_DTYPE_F64)
     hipLaunchKernelGGL(jac_prep_kernel<double>, grid, dim3(256), 0, m->ctx->stream, xt, fac, (const double*)d_src, ld, n, din, tin, m->tin);
   else
@@ -112,8 +112,8 @@ static int jac_run(v21_mlp* m, int route, long long r0, long long n, float* y, l
   hipStream_t st = m->ctx->stream;
   const int L = m->L, din = m->dims[0], dout = m->dims[L];
   const bool tout = (flags & V21_FWD_OUT_TRANSFORM) != 0;
-  const float* xt = m->jxt.as<float>() + r0 * din;
-  const float* fac = m->jfac.as<float>() + r0 * din;
+  const float* xt = m->jxt.get() + r0 * din;
+  const float* fac = m->jfac.get() + r0 * din;
   if (route == JAC_FUSED) {
     JacArgs a{};
     a.x = xt; a.ldx = din; a.fac = fac;
@@ -142,7 +142,7 @@ static int jac_run(v21_mlp* m, int route, long long r0, long long n, float* y, l
     attr_done[m->ctx->device & 63] = true;
   }
   g.w = m->d_w; g.ldy = ldy;
-  g.data = m->lk_data.as<float>(); g.wv = m->lk_w.as<float>(); g.like = lnl ? 1 : 0;
+  g.data = m->lk_data.get(); g.wv = m->lk_w.get(); g.like = lnl ? 1 : 0;
   g.out_std = tout ? m->out_std : 1.0f;
   g.mean = tout ? m->d_mean : nullptr;
   for (long long q = 0; q < n; q += 65535) {  // (grid.x <= 65,535 rows per launch; the row offsets move the pointers)
@@ -162,9 +162,9 @@ int jac_slices(v21_mlp* m, int route, long long n, bool want_y, int prec, int fl
                const std::function<int(const float*, const float*, long long, long long)>& reduce) {
   const int din = m->dims[0], dout = m->dims[m->L];
   const long long rows_ws = std::min(n, kLkSlice);
-  CHK(m->lk_ws.reserve((size_t)rows_ws * (din + 1) * dout * sizeof(float)));
-  float* wy = want_y ? m->lk_ws.as<float>() : nullptr;
-  float* wj = m->lk_ws.as<float>() + rows_ws * dout;
+  CHK(m->lk_ws.reserve((size_t)rows_ws * (din + 1) * dout));
+  float* wy = want_y ? m->lk_ws.get() : nullptr;
+  float* wj = m->lk_ws.get() + rows_ws * dout;
   for (long long r0 = 0; r0 < n; r0 += kLkSlice) {
     const long long rows = std::min(kLkSlice, n - r0);
     CHK(jac_run(m, route, r0, rows, wy, dout, wj, nullptr, nullptr, prec, flags));
@@ -180,13 +180,13 @@ int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, lon
   const int din = m->dims[0], dout = m->dims[m->L];
   const long long chunk = std::min(n, kJacHostChunk);
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
-  CHK(m->hin.reserve((size_t)chunk * din * sizeof(double)));
-  CHK(m->hout.reserve((size_t)chunk * std::max(out_floats, (long long)dout * (1 + din)) * sizeof(float)));
+  CHK(m->hin.reserve((size_t)chunk * din));
+  CHK(m->hout.reserve((size_t)chunk * std::max(out_floats, (long long)dout * (1 + din))));
   for (long long r0 = 0; r0 < n; r0 += kJacHostChunk) {
     const long long rows = std::min(kJacHostChunk, n - r0);
     HIPCHK(hipMemcpyAsync(m->hin.p, (const char*)x + r0 * din * esz, (size_t)rows * din * esz, hipMemcpyHostToDevice, st));
     CHK(jac_prep(m, m->hin.p, x_dtype, din, rows, tin));
-    CHK(run(r0, rows, m->hout.as<float>()));
+    CHK(run(r0, rows, m->hout.get()));
     HIPCHK(hipStreamSynchronize(st));
   }
   return V21_OK;
@@ -199,7 +199,7 @@ static int loglike_run(v21_mlp* m, int route, long long n, float* d_lnl, float* 
   const int din = m->dims[0], dout = m->dims[m->L];
   return jac_slices(m, route, n, true, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {
     hipLaunchKernelGGL(jac_loglike_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, m->ctx->stream, wy, wj,
-                       m->lk_data.as<const float>(), m->lk_w.as<const float>(), d_lnl + r0, d_grad ? d_grad + r0 * din : nullptr,
+                       m->lk_data.get(), m->lk_w.get(), d_lnl + r0, d_grad ? d_grad + r0 * din : nullptr,
                        rows, din, dout);
     return V21_OK;
   });

@@ -14,12 +14,12 @@ struct v21_joint {
   v21_trainer *ae = nullptr, *em = nullptr;
   v21_ctx* ctx = nullptr;  // (kept: destroying the joint object must not look into trainers that may already be gone)
   int latent_layer = 0;
-  ChainModel* d_tab = nullptr;
+  Dev<ChainModel> d_tab;
   std::vector<ChainModel> h_tab;
-  DwAdamModel* d_dwadam = nullptr;  // gradients + Adam of both models in one grouped launch (dw_adam.h)
+  Dev<DwAdamModel> d_dwadam;  // gradients + Adam of both models in one grouped launch (dw_adam.h)
   std::vector<DwAdamModel> h_dwadam;
   bool f32 = false;  // both trainers on the small-batch f32 chain (train_chain32s.h: train_chain32s_joint_kernel)
-  Dw32Model* d_dw32 = nullptr;  // ... and, on a single rank with steps of <= kDw32MaxRows rows, both models' gradients + Adam in one launch
+  Dev<Dw32Model> d_dw32;  // ... and, on a single rank with steps of <= kDw32MaxRows rows, both models' gradients + Adam in one launch
   std::vector<Dw32Model> h_dw32;
 };
 extern "C" int v21_joint_create(v21_trainer* ae, v21_trainer* em, int latent_layer, v21_joint** out) {
@@ -41,20 +41,16 @@ extern "C" int v21_joint_create(v21_trainer* ae, v21_trainer* em, int latent_lay
                 me->dims[me->L], 2 * kChainMaxLatent);
   if (ma->dims[0] != ma->dims[ma->L]) return fail(V21_ERR_ARG, "the first trainer must be an autoencoder (in == out width)");
   CHK(use(ae->ctx));
-  v21_joint* j = new v21_joint();
+  std::unique_ptr<v21_joint> j(new v21_joint());
   j->ae = ae; j->em = em; j->ctx = ae->ctx; j->latent_layer = latent_layer; j->f32 = f32;
-  hipError_t e = hipMalloc((void**)&j->d_tab, 2 * sizeof(ChainModel));
-  if (e != hipSuccess) { delete j; return fail(V21_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
-  *out = j;
+  CHK(j->d_tab.reserve(2));
+  *out = j.release();
   return V21_OK;
 }
 extern "C" int v21_joint_destroy(v21_joint* j) {
   if (!j) return V21_OK;
   hipSetDevice(j->ctx->device);
   hipStreamSynchronize(j->ctx->stream);
-  hipFree(j->d_tab);
-  if (j->d_dwadam) hipFree(j->d_dwadam);
-  if (j->d_dw32) hipFree(j->d_dw32);
   delete j;
   return V21_OK;
 }
@@ -84,12 +80,12 @@ extern "C" int v21_joint_run_epoch(v21_joint* j, const int32_t* perm, int batch,
   CHK(upload_rows(ta, perm, &d_idx));
   const long long steps = (n + batch - 1) / batch;
   for (v21_trainer* t : {ta, te}) CHK(ensure_steploss(t, steps));
-  CHK(upload_if_changed(joint_table(j, 1), j->h_tab, j->d_tab, st));
-  if (R == 1 && !j->f32) CHK(refresh_dw_adam_table({ta, te}, &j->d_dwadam, j->h_dwadam, st));
+  CHK(upload_if_changed(joint_table(j, 1), j->h_tab, j->d_tab.get(), st));
+  if (R == 1 && !j->f32) CHK(refresh_dw_adam_table({ta, te}, j->d_dwadam, j->h_dwadam, st));
   bool group32 = j->f32 && R == 1 && batch <= kDw32MaxRows;
   int max_blocks32 = 0;
   if (group32) {
-    if (!j->d_dw32) HIPCHK(hipMalloc((void**)&j->d_dw32, 2 * sizeof(Dw32Model)));
+    CHK(j->d_dw32.reserve(2));
     CHK(refresh_dw32_table({ta, te}, j->d_dw32, j->h_dw32, &max_blocks32, &group32, st));
   }
   CHK(chain_attr(ta->prec));
@@ -165,7 +161,7 @@ extern "C" int v21_joint_eval(v21_joint* j, double* losses) {
   const long long n = ta->n[1];
   if (n > (1ll << 30)) return fail(V21_ERR_ARG, "too many rows for one validation launch");
   for (v21_trainer* t : {ta, te}) CHK(ensure_copies(t, false));
-  CHK(upload_if_changed(joint_table(j, 0), j->h_tab, j->d_tab, st));  // (evaluation passes draw no noise)
+  CHK(upload_if_changed(joint_table(j, 0), j->h_tab, j->d_tab.get(), st));  // (evaluation passes draw no noise)
   CHK(chain_attr(ta->prec));
   const int dsig = ta->mlp->dims[0], dpar = te->mlp->dims[0], dlat = te->mlp->dims[te->mlp->L];
   ChainStep sa = chain_step(ta->d_x[1], dsig, nullptr, dsig, ta->d_rw[1], nullptr, 0, (int)n, (int)n, dsig);

@@ -12,17 +12,17 @@
 struct v21_sweep {
   v21_ctx* ctx = nullptr;
   std::vector<v21_trainer*> tr;
-  AdamArgs* d_adam = nullptr;
+  Dev<AdamArgs> d_adam;
   std::vector<AdamArgs> h_adam;  // what d_adam holds
   bool chain = false;            // every member runs the chain kernel: one grouped launch of it per step
-  ChainModel* d_chain = nullptr;
+  Dev<ChainModel> d_chain;
   std::vector<ChainModel> h_chain;
-  DwAdamModel* d_dwadam = nullptr;  // single rank: gradients + Adam in one grouped launch (dw_adam.h)
+  Dev<DwAdamModel> d_dwadam;  // single rank: gradients + Adam in one grouped launch (dw_adam.h)
   std::vector<DwAdamModel> h_dwadam;
   // f32 members on the small-batch chain (train_chain32s.h): one grouped chain launch + one grouped gradient / Adam launch
   // (dw_adam32.h) per step on a single rank, steps of <= kDw32MaxRows rows
   bool chain32s = false;
-  Dw32Model* d_dw32 = nullptr;
+  Dev<Dw32Model> d_dw32;
   std::vector<Dw32Model> h_dw32;
   // r5: TWO half-groups on two streams (one rank, grouped chain launches).  A group step is two launches of complementary
   // character -- every member's chain (latency-bound per workgroup, little HBM traffic) and every member's gradients + Adam
@@ -60,30 +60,26 @@ extern "C" int v21_sweep_create(v21_trainer** trainers, int count, v21_sweep** o
       if (trainers[j] == t) return fail(V21_ERR_ARG, "trainer %d listed twice", k);
   }
   CHK(use(t0->ctx));
-  v21_sweep* s = new v21_sweep();
+  std::unique_ptr<v21_sweep> s(new v21_sweep());
   s->ctx = t0->ctx;
   s->tr.assign(trainers, trainers + count);
-  HIPCHK(hipMalloc((void**)&s->d_adam, (size_t)count * sizeof(AdamArgs)));
+  CHK(s->d_adam.reserve(count));
   s->chain = true;
   for (int k = 0; k < count; ++k) s->chain = s->chain && trainers[k]->chain;
   for (int k = 0; k < count; ++k) s->h_adam.push_back(adam_args(trainers[k], true, 0.f, s->chain));
   HIPCHK(hipMemcpyAsync(s->d_adam, s->h_adam.data(), s->h_adam.size() * sizeof(AdamArgs), hipMemcpyHostToDevice, s->ctx->stream));
   s->chain32s = !s->chain;
   for (int k = 0; k < count; ++k) s->chain32s = s->chain32s && trainers[k]->chain32s && trainers[k]->mlp->L <= kNtMaxGroup;
-  if (s->chain || s->chain32s) HIPCHK(hipMalloc((void**)&s->d_chain, (size_t)count * sizeof(ChainModel)));
-  if (s->chain32s) HIPCHK(hipMalloc((void**)&s->d_dw32, (size_t)count * sizeof(Dw32Model)));
+  if (s->chain || s->chain32s) CHK(s->d_chain.reserve(count));
+  if (s->chain32s) CHK(s->d_dw32.reserve(count));
   HIPCHK(hipStreamSynchronize(s->ctx->stream));
-  *out = s;
+  *out = s.release();
   return V21_OK;
 }
 extern "C" int v21_sweep_destroy(v21_sweep* s) {
   if (!s) return V21_OK;
   hipSetDevice(s->ctx->device);
   hipStreamSynchronize(s->ctx->stream);
-  hipFree(s->d_adam);
-  if (s->d_chain) hipFree(s->d_chain);
-  if (s->d_dwadam) hipFree(s->d_dwadam);
-  if (s->d_dw32) hipFree(s->d_dw32);
   if (s->s2) { hipStreamSynchronize(s->s2); hipStreamDestroy(s->s2); }
   for (hipEvent_t e : {s->ev_fork, s->ev_off, s->ev_join}) if (e) hipEventDestroy(e);
   delete s;
@@ -336,13 +332,13 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
   // the Adam hyper-parameters may have changed since create (set_adam / set_lr): refresh the device table
   std::vector<AdamArgs> tab;
   for (v21_trainer* t : s->tr) tab.push_back(adam_args(t, true, 0.f, s->chain));
-  CHK(upload_if_changed(tab, s->h_adam, s->d_adam, st));
+  CHK(upload_if_changed(tab, s->h_adam, s->d_adam.get(), st));
   const int din = m->dims[0], dout = m->dims[m->L];
   if (s->chain) {
     std::vector<ChainModel> tab;
     for (v21_trainer* t : s->tr) tab.push_back(chain_model(t));
-    CHK(upload_if_changed(tab, s->h_chain, s->d_chain, st));
-    if (R == 1) CHK(refresh_dw_adam_table(s->tr, &s->d_dwadam, s->h_dwadam, st));
+    CHK(upload_if_changed(tab, s->h_chain, s->d_chain.get(), st));
+    if (R == 1) CHK(refresh_dw_adam_table(s->tr, s->d_dwadam, s->h_dwadam, st));
   }
   bool group32 = s->chain32s && R == 1 && batch <= kDw32MaxRows && !(getenv("V21_SWEEP32_GROUP") && getenv("V21_SWEEP32_GROUP")[0] == '0');
   int max_blocks32 = 0;
@@ -358,7 +354,7 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
       tab.push_back(chain_model32(t));
       tab.back().stamps = nullptr;
     }
-    CHK(upload_if_changed(tab, s->h_chain, s->d_chain, st));
+    CHK(upload_if_changed(tab, s->h_chain, s->d_chain.get(), st));
   }
   // r5: two half-groups on two streams (v21_sweep: s2) for the grouped chain launches of one rank; V21_SWEEP_STREAMS=1: one stream
   s->two_streams = R == 1 && (s->chain || group32) && s->tr.size() >= 16 && RouteEnv::read().sweep_streams == 2;  // (below 16 members the second stream's hand-overs cost more than they hide: tiny members, 8 per group: 17.4 -> 23.6 us per step)

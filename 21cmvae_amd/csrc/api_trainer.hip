@@ -117,39 +117,48 @@ static int reduce_slabs_range(v21_trainer* t, int nslice, long long lo, long lon
 }
 
 static int build_chain32s_jobs(v21_trainer* t);
+// a chain trainer's packed streams in `fmt` (the slack behind them is read ahead: zeroed), loss accumulator and stamps
+static int alloc_chain_streams(v21_trainer* t, ChainFmt fmt) {
+  hipStream_t st = t->ctx->stream;
+  t->lay = chain_layout(t->mlp, fmt);
+  CHK(t->d_fw.zeroed((size_t)t->lay.fw_bytes + kChainStreamSlack, st));
+  CHK(t->d_bw.zeroed((size_t)t->lay.bw_bytes + kChainStreamSlack, st));
+  CHK(t->d_ticket.zeroed(2, st));
+  CHK(t->d_stamps.zeroed(kStampSlots, st));
+  return V21_OK;
+}
 extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_trainer** out) {
   if (!m || !out) return fail(V21_ERR_ARG, "null argument");
   if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
   if (max_batch < 1 || max_batch > (1 << 20)) return fail(V21_ERR_ARG, "max_batch %d out of range", max_batch);
   CHK(use(m->ctx));
   hipStream_t st = m->ctx->stream;
-  v21_trainer* t = new v21_trainer();
+  std::unique_ptr<v21_trainer> owner(new v21_trainer());  // (freed, with every buffer made so far, by any return before the last)
+  v21_trainer* t = owner.get();
   t->mlp = m; t->ctx = m->ctx; t->prec = precision; t->max_batch = max_batch; t->P = m->nparams;
   const int L = m->L;
   for (int l = 0; l < L; ++l)
     if (m->act[l] == V21_ACT_GAUSS) t->gl = l;
-  if (t->gl == L - 1) { delete t; return fail(V21_ERR_UNSUPPORTED, "a V21_ACT_GAUSS layer cannot be the last layer of a trained stack"); }
+  if (t->gl == L - 1) return fail(V21_ERR_UNSUPPORTED, "a V21_ACT_GAUSS layer cannot be the last layer of a trained stack");
   if (m->act[L - 1] != V21_ACT_LINEAR) {  // (the loss gradient is taken w.r.t. the Dense output: no output non-linearity is differentiated)
-    delete t;
     return fail(V21_ERR_UNSUPPORTED, "the output layer of a trained stack must be linear (the reference's output Dense has no activation, emulator.py:44)");
   }
-  CHK(zalloc(&t->d_g, t->P + kArenaPad, st));
-  CHK(zalloc(&t->d_m, t->P + kArenaPad, st));
-  CHK(zalloc(&t->d_v, t->P + kArenaPad, st));
+  CHK(t->d_g.zeroed(t->P + kArenaPad, st));
+  CHK(t->d_m.zeroed(t->P + kArenaPad, st));
+  CHK(t->d_v.zeroed(t->P + kArenaPad, st));
   t->Bp = ((long long)max_batch + 31) / 32 * 32 + 32;
-  t->d_h.assign(L + 1, nullptr); t->d_ht.assign(L + 1, nullptr);
-  t->d_dz.assign(L + 1, nullptr); t->d_dzt.assign(L + 1, nullptr);
+  for (auto* v : {&t->d_h, &t->d_ht, &t->d_dz, &t->d_dzt}) *v = std::vector<Dev<float>>(L + 1);
   std::vector<float> ones((size_t)t->Bp, 1.0f);
   for (int l = 0; l <= L; ++l) {
-    CHK(zalloc(&t->d_h[l], (size_t)(max_batch + 32) * p16(m->dims[l]), st));
+    CHK(t->d_h[l].zeroed((size_t)(max_batch + 32) * p16(m->dims[l]), st));
     if (l < L) {  // the output activation is never a weight-gradient operand
-      CHK(zalloc(&t->d_ht[l], (size_t)(m->dims[l] + 1 + 32) * t->Bp, st));
+      CHK(t->d_ht[l].zeroed((size_t)(m->dims[l] + 1 + 32) * t->Bp, st));
       HIPCHK(hipMemcpyAsync(t->d_ht[l] + (size_t)m->dims[l] * t->Bp, ones.data(), (size_t)t->Bp * sizeof(float),
                             hipMemcpyHostToDevice, st));  // the row of ones -> bias gradient
     }
     if (l >= 1) {
-      CHK(zalloc(&t->d_dz[l], (size_t)(max_batch + 32) * p16(m->dims[l]), st));
-      CHK(zalloc(&t->d_dzt[l], (size_t)(m->dims[l] + 32) * t->Bp, st));
+      CHK(t->d_dz[l].zeroed((size_t)(max_batch + 32) * p16(m->dims[l]), st));
+      CHK(t->d_dzt[l].zeroed((size_t)(m->dims[l] + 32) * t->Bp, st));
     }
   }
   HIPCHK(hipStreamSynchronize(st));  // `ones` is a host temporary
@@ -160,53 +169,43 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
   }
   if (t->gl >= 0) {
     const int W2 = m->nw(t->gl);
-    CHK(zalloc(&t->d_zs, (size_t)(max_batch + 32) * p16(W2), st));
-    CHK(zalloc(&t->d_dzs, (size_t)(max_batch + 32) * p16(W2), st));
-    CHK(zalloc(&t->d_dzst, (size_t)(W2 + 32) * t->Bp, st));
-    CHK(zalloc(&t->d_klrow, (size_t)max_batch + 32, st));
+    CHK(t->d_zs.zeroed((size_t)(max_batch + 32) * p16(W2), st));
+    CHK(t->d_dzs.zeroed((size_t)(max_batch + 32) * p16(W2), st));
+    CHK(t->d_dzst.zeroed((size_t)(W2 + 32) * t->Bp, st));
+    CHK(t->d_klrow.zeroed((size_t)max_batch + 32, st));
   }
-  CHK(zalloc(&t->d_wt, (size_t)ot + 64, st));
-  CHK(zalloc(&t->d_wp, (size_t)op + 64, st));
-  CHK(zalloc(&t->d_yb, (size_t)(max_batch + 32) * p16(m->dims[L]), st));
-  CHK(zalloc(&t->d_wb, (size_t)max_batch + 32, st));
-  CHK(zalloc(&t->d_rowloss, (size_t)max_batch + 32, st));
-  CHK(zalloc(&t->d_evalsum, 4, st));
+  CHK(t->d_wt.zeroed((size_t)ot + 64, st));
+  CHK(t->d_wp.zeroed((size_t)op + 64, st));
+  CHK(t->d_yb.zeroed((size_t)(max_batch + 32) * p16(m->dims[L]), st));
+  CHK(t->d_wb.zeroed((size_t)max_batch + 32, st));
+  CHK(t->d_rowloss.zeroed((size_t)max_batch + 32, st));
+  CHK(t->d_evalsum.zeroed(4, st));
   // what this trainer commits to: csrc/routes.h (the same function answers v21_route_train)
   t->kind = decide_trainer_kind(L, m->dims.data(), m->act.data(), precision, max_batch, RouteEnv::read());
   {  // the 16-bit chain kernel
     const bool ok = t->kind.chain;
     if (ok) {
-      long long of = 0, ob = 0;
-      for (int l = 0; l < L; ++l) {
-        const int K = m->dims[l], N = m->nw(l);
-        t->fw_off.push_back(of); of += (long long)((N + 31) / 32) * chain_steps(K) * 512;
-        t->bw_off.push_back(ob); ob += (long long)((K + 31) / 32) * chain_steps(N) * 512;
-      }
-      t->fw_bytes = of * 2; t->bw_bytes = ob * 2;
-      HIPCHK(hipMalloc(&t->d_fw, (size_t)of * 2 + kChainStreamSlack)); HIPCHK(hipMemsetAsync(t->d_fw, 0, (size_t)of * 2 + kChainStreamSlack, st));
-      HIPCHK(hipMalloc(&t->d_bw, (size_t)ob * 2 + kChainStreamSlack)); HIPCHK(hipMemsetAsync(t->d_bw, 0, (size_t)ob * 2 + kChainStreamSlack, st));
-      CHK(zalloc(&t->d_partial, (size_t)(max_batch + 31) / 32 + 4, st));
-      HIPCHK(hipMalloc((void**)&t->d_ticket, 16)); HIPCHK(hipMemsetAsync(t->d_ticket, 0, 16, st));
-      HIPCHK(hipMalloc((void**)&t->d_stamps, kStampSlots * 8)); HIPCHK(hipMemsetAsync(t->d_stamps, 0, kStampSlots * 8, st));
+      CHK(alloc_chain_streams(t, CHAIN_FMT_16));
+      CHK(t->d_partial.zeroed((size_t)(max_batch + 31) / 32 + 4, st));
       // 16-row groups per feature tile of the operand buffers, for whole 128-row blocks: the fused training kernel
       // (fused_train.h) stores every group of a workgroup's 128 rows, pad rows included, and a group past BS would land in
       // the NEXT feature tile's first rows (r4: with BS from 32-row blocks, a ragged step whose last 128-row block reached
       // past it -- 777 rows of max_batch 777 -- had rows 0-63 of the following tile overwritten by whichever workgroup
       // finished last; launch_fused_train checks the bound)
       t->BS = ((long long)max_batch + 127) / 128 * 8 + 2;
-      t->d_ht16.assign(L + 1, nullptr); t->d_dzt16.assign(L + 1, nullptr);
+      for (auto* v : {&t->d_ht16, &t->d_dzt16}) *v = std::vector<Dev<unsigned short>>(L + 1);
       const unsigned short one = precision == V21_PREC_F16 ? 0x3C00 : 0x3F80;
       for (int l = 0; l < L; ++l) {
         const int K = m->dims[l], N = m->nw(l);
         const size_t na = (size_t)((K + 1 + 31) / 32) * t->BS * 512, nb = (size_t)((N + 31) / 32) * t->BS * 512;
-        HIPCHK(hipMalloc(&t->d_ht16[l], na * 2)); HIPCHK(hipMemsetAsync(t->d_ht16[l], 0, na * 2, st));
-        HIPCHK(hipMalloc(&t->d_dzt16[l + 1], nb * 2)); HIPCHK(hipMemsetAsync(t->d_dzt16[l + 1], 0, nb * 2, st));
+        CHK(t->d_ht16[l].zeroed(na, st));
+        CHK(t->d_dzt16[l + 1].zeroed(nb, st));
         // feature K of the input operand: the constant row of ones that turns [dW; db] into one contraction
         std::vector<unsigned short> tile((size_t)t->BS * 512, 0);
         for (long long b = 0; b < t->BS * 16; ++b)
           tile[(size_t)((b >> 4) * 64 + ((b >> 3) & 1) * 32 + (K & 31)) * 8 + (b & 7)] = one;
         // (only element f%32 == K%32 of the last feature tile is set; the chain kernel writes features < K only)
-        HIPCHK(hipMemcpyAsync((char*)t->d_ht16[l] + (size_t)(K >> 5) * t->BS * 1024, tile.data(), tile.size() * 2, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t->d_ht16[l] + (size_t)(K >> 5) * t->BS * 512, tile.data(), tile.size() * 2, hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
       }
       t->chain = true;
@@ -233,8 +232,7 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
         }
         t->tstream_total = total;
         t->tstream_padded = (total + 7) / 8 * 8;
-        HIPCHK(hipMalloc((void**)&t->d_tstream, (size_t)t->tstream_padded * 1024 + kChainStreamSlack));
-        HIPCHK(hipMemsetAsync(t->d_tstream, 0, (size_t)t->tstream_padded * 1024 + kChainStreamSlack, st));
+        CHK(t->d_tstream.zeroed((size_t)t->tstream_padded * 1024 + kChainStreamSlack, st));
       }
       if (!(getenv("V21_DW_BLOCKS") && getenv("V21_DW_BLOCKS")[0] == '0')) {
         // tile order of dw16_adam_kernel: per layer the R x C tile grid in 8 blocks (rb x cb = 8, the shape with the least
@@ -270,7 +268,7 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
         for (auto& v : per) xper = std::max(xper, v.size());
         std::vector<int> order(8 * xper, -1);
         for (int x = 0; x < 8; ++x) std::copy(per[x].begin(), per[x].end(), order.begin() + x * xper);
-        HIPCHK(hipMalloc((void**)&t->d_dworder, order.size() * sizeof(int) + 16));
+        CHK(t->d_dworder.reserve(order.size() + 4));
         HIPCHK(hipMemcpyAsync(t->d_dworder, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
         t->dw_xper = (int)xper;
@@ -282,56 +280,23 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
     const bool ok = t->kind.chain32;
     t->chain32s = t->kind.chain32s;
     if (ok) {
-      long long of = 0, ob = 0;  // floats
-      for (int l = 0; l < L; ++l) {
-        const int K = m->dims[l], N = m->nw(l);
-        t->fw_off.push_back(of); of += (long long)t->c32_tiles(N) * t->c32_frags(K) * 256;
-        t->bw_off.push_back(ob); ob += (long long)t->c32_tiles(K) * t->c32_frags(N) * 256;
-      }
-      t->fw_bytes = of * 4; t->bw_bytes = ob * 4;
-      HIPCHK(hipMalloc(&t->d_fw, (size_t)of * 4 + kChainStreamSlack)); HIPCHK(hipMemsetAsync(t->d_fw, 0, (size_t)of * 4 + kChainStreamSlack, st));
-      HIPCHK(hipMalloc(&t->d_bw, (size_t)ob * 4 + kChainStreamSlack)); HIPCHK(hipMemsetAsync(t->d_bw, 0, (size_t)ob * 4 + kChainStreamSlack, st));
-      HIPCHK(hipMalloc((void**)&t->d_ticket, 16)); HIPCHK(hipMemsetAsync(t->d_ticket, 0, 16, st));
-      HIPCHK(hipMalloc((void**)&t->d_stamps, kStampSlots * 8)); HIPCHK(hipMemsetAsync(t->d_stamps, 0, kStampSlots * 8, st));
+      CHK(alloc_chain_streams(t, t->chain32s ? CHAIN_FMT_32S : CHAIN_FMT_32));
       t->chain32 = true;
     }
   }
   t->max_slices = std::max(1, (max_batch + 127) / 128);  // weight-gradient slices down to 8 batch steps
-  CHK(zalloc(&t->d_slab, (size_t)t->max_slices * (t->P + 4), st));
+  CHK(t->d_slab.zeroed((size_t)t->max_slices * (t->P + 4), st));
   if (t->chain32s) CHK(build_chain32s_jobs(t));
-  *out = t;
+  *out = owner.release();
   return V21_OK;
 }
 extern "C" int v21_trainer_destroy(v21_trainer* t) {
   if (!t) return V21_OK;
   hipSetDevice(t->ctx->device);
   hipStreamSynchronize(t->ctx->stream);
-  hipFree(t->d_g); hipFree(t->d_m); hipFree(t->d_v);
-  for (int i = 0; i < 2; ++i) {
-    if (t->d_x[i]) hipFree(t->d_x[i]);
-    if (t->d_y[i] && !t->y_is_x[i]) hipFree(t->d_y[i]);
-    if (t->d_rw[i]) hipFree(t->d_rw[i]);
-  }
-  if (t->d_perm) hipFree(t->d_perm);
-  for (auto* v : {&t->d_h, &t->d_ht, &t->d_dz, &t->d_dzt})
-    for (float* p : *v) if (p) hipFree(p);
-  hipFree(t->d_wt); hipFree(t->d_wp);
-  hipFree(t->d_yb); hipFree(t->d_wb); hipFree(t->d_rowloss); hipFree(t->d_evalsum);
   destroy_graphs(t);
   for (hipEvent_t e : t->phase_ev) hipEventDestroy(e);
-  if (t->d_desc) hipFree(t->d_desc);
   if (t->h_desc) hipHostFree(t->h_desc);
-  if (t->d_cur) hipFree(t->d_cur);
-  if (t->d_steploss) hipFree(t->d_steploss);
-  if (t->d_slab) hipFree(t->d_slab);
-  if (t->d_zs) { hipFree(t->d_zs); hipFree(t->d_dzs); hipFree(t->d_dzst); hipFree(t->d_klrow); }
-  if (t->d_dworder) hipFree(t->d_dworder);
-  if (t->d_tstream) hipFree(t->d_tstream);
-  if (t->d_x16) hipFree(t->d_x16);
-  if (t->chain32) { hipFree(t->d_fw); hipFree(t->d_bw); hipFree(t->d_ticket); hipFree(t->d_stamps); if (t->d_jobs) hipFree(t->d_jobs); }
-  if (t->chain) { hipFree(t->d_fw); hipFree(t->d_bw); hipFree(t->d_partial); hipFree(t->d_ticket); hipFree(t->d_stamps);
-    for (void* p : t->d_ht16) if (p) hipFree(p);
-    for (void* p : t->d_dzt16) if (p) hipFree(p); }
   delete t;
   return V21_OK;
 }
@@ -357,32 +322,31 @@ extern "C" int v21_trainer_set_data(v21_trainer* t, int which, const float* x, c
   if (!y && din != dout) return fail(V21_ERR_ARG, "y == NULL (y = x) needs in_dim == out_dim");
   hipStream_t st = t->ctx->stream;
   if (which == 0) { HIPCHK(hipStreamSynchronize(st)); destroy_graphs(t); }  // captured steps hold the old pointers
-  if (t->d_x[which]) { HIPCHK(hipFree(t->d_x[which])); t->d_x[which] = nullptr; }
-  if (t->d_y[which] && !t->y_is_x[which]) HIPCHK(hipFree(t->d_y[which]));
+  // the old set goes first (the training set is sized to fit: never two of them at once); from here until the last
+  // line the trainer has no set of this kind, which is also what a failure leaves behind
+  t->n[which] = 0;
   t->d_y[which] = nullptr;
-  if (t->d_rw[which]) { HIPCHK(hipFree(t->d_rw[which])); t->d_rw[which] = nullptr; }
-  HIPCHK(hipMalloc((void**)&t->d_x[which], (size_t)n * din * sizeof(float)));
+  for (Dev<float>* b : {&t->d_x[which], &t->d_ybuf[which], &t->d_rw[which]}) b->release();
+  CHK(t->d_x[which].reserve((size_t)n * din));
   HIPCHK(hipMemcpyAsync(t->d_x[which], x, (size_t)n * din * sizeof(float), hipMemcpyHostToDevice, st));
   if (which == 0) {  // the fused training kernels gather the training rows as 16-bit elements (ChainStep::x16)
-    if (t->d_x16) { HIPCHK(hipFree(t->d_x16)); t->d_x16 = nullptr; }
+    t->d_x16.release();
     if ((t->train_arch >= 0 || t->kind.train_rt) && !(getenv("V21_TRAIN_X16") && getenv("V21_TRAIN_X16")[0] == '0')) {
       t->ldx16 = (din + 31) / 32 * 32;
       const long long tot = (long long)n * t->ldx16;
-      HIPCHK(hipMalloc((void**)&t->d_x16, (size_t)tot * 2));
+      CHK(t->d_x16.reserve((size_t)tot));
       hipLaunchKernelGGL(rows_to_half_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)t->d_x[0], din, (long long)n,
-                         t->d_x16, t->ldx16, t->prec == V21_PREC_BF16 ? 1 : 0);
+                         t->d_x16.get(), t->ldx16, t->prec == V21_PREC_BF16 ? 1 : 0);
       HIPCHK(hipGetLastError());
     }
   }
   if (y) {
-    HIPCHK(hipMalloc((void**)&t->d_y[which], (size_t)n * dout * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(t->d_y[which], y, (size_t)n * dout * sizeof(float), hipMemcpyHostToDevice, st));
-    t->y_is_x[which] = false;
-  } else {
-    t->d_y[which] = t->d_x[which];
-    t->y_is_x[which] = true;
+    CHK(t->d_ybuf[which].reserve((size_t)n * dout));
+    HIPCHK(hipMemcpyAsync(t->d_ybuf[which], y, (size_t)n * dout * sizeof(float), hipMemcpyHostToDevice, st));
   }
-  HIPCHK(hipMalloc((void**)&t->d_rw[which], (size_t)n * sizeof(float)));
+  t->y_is_x[which] = !y;
+  t->d_y[which] = y ? t->d_ybuf[which] : t->d_x[which];
+  CHK(t->d_rw[which].reserve((size_t)n));
   HIPCHK(hipMemcpyAsync(t->d_rw[which], rw, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
   t->n[which] = n;
@@ -422,13 +386,7 @@ AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt, cons
     AdamLayer& al = a.lt[l];
     al.w_off = m->w_off[l]; al.wt_off = t->wt_off[l]; al.wp_off = t->wp_off[l];
     al.K = m->dims[l]; al.N = m->nw(l); al.ldwt = p16(al.K); al.ldwp = p16(al.N);
-    if (t->chain) {
-      al.fw_off = t->fw_off[l]; al.bw_off = t->bw_off[l];
-      al.KS = chain_steps(al.K); al.NS = chain_steps(al.N);
-    } else if (t->chain32) {
-      al.fw_off = t->fw_off[l]; al.bw_off = t->bw_off[l];
-      al.KS = t->c32_frags(al.K); al.NS = t->c32_frags(al.N);
-    }
+    if (t->chain || t->chain32) t->lay.layer(al, l);
   }
   if (t->chain) { a.fw = t->d_fw; a.bw = t->d_bw; a.cprec = t->prec == V21_PREC_F16 ? 1 : 2; }
   if (t->chain32) { a.fw = t->d_fw; a.bw = t->d_bw; a.cprec = t->chain32s ? 4 : 3; }
@@ -443,7 +401,7 @@ AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt, cons
   }
   a.skip_nt = (skip_nt && (t->chain || t->chain32)) ? 1 : 0;
   if (do_adam && pub) {  // a single-rank f32 chain step: this launch publishes its loss
-    a.loss_acc = (unsigned long long*)t->d_ticket; a.loss_out = t->d_g + t->P; a.loss_out2 = t->d_steploss;
+    a.loss_acc = t->d_ticket; a.loss_out = t->d_g + t->P; a.loss_out2 = t->d_steploss;
     a.loss_slot = pub->slot;
   }
   a.sc = step_ctx(t);
@@ -510,7 +468,7 @@ int step_tail(v21_trainer* t, const StepLoss& loss) {
 // the loss of a step of >= 1 row: one rank, an epoch's per-step slot -- the kernel that publishes the batch loss writes
 // the slot itself, on every route but the split-K one (its gradient launch publishes the loss before the exchange)
 static StepLoss step_loss(const v21_trainer* t, const StepRoute& r, float* out) {
-  const bool listed = out && t->d_steploss && out >= t->d_steploss && out < t->d_steploss + t->steploss_cap;
+  const bool listed = out && t->d_steploss && out >= t->d_steploss && out < t->d_steploss + t->d_steploss.n;
   return StepLoss{out, listed && t->ctx->nranks == 1 && r.upd != UP_DW16_SPLITK ? (int)(out - t->d_steploss) : -1};
 }
 int zero_grad(v21_trainer* t) {
@@ -659,20 +617,18 @@ ChainModel chain_model(v21_trainer* t) {
     ChainLayer& c = a.lt[l];
     c.K = m->dims[l]; c.N = m->nw(l);
     c.gauss = m->act[l] == V21_ACT_GAUSS;
-    c.KS = chain_steps(c.K); c.NT = (c.N + 31) / 32;
-    c.NS = chain_steps(c.N); c.KT = (c.K + 31) / 32;
+    t->lay.layer(c, l);
     c.relu = m->act[l] == V21_ACT_RELU;
     c.mask_tile = -1;
     if (c.relu && l + 1 < L) { c.mask_tile = mt; mt += c.NT; }
-    c.fw_off = t->fw_off[l] / 8; c.bw_off = t->bw_off[l] / 8;
     c.b_off = m->b_off[l];
     c.ht16 = t->d_ht16[l]; c.dzt16 = t->d_dzt16[l + 1];
   }
   a.fw = t->d_fw; a.bw = t->d_bw; a.w = m->d_w;
-  a.fw_bytes = t->fw_bytes; a.bw_bytes = t->bw_bytes;
+  a.fw_bytes = t->lay.fw_bytes; a.bw_bytes = t->lay.bw_bytes;
   a.BS = t->BS;
-  a.loss_acc = (unsigned long long*)t->d_ticket;
-  a.stamps = t->stamps_on ? t->d_stamps : nullptr;
+  a.loss_acc = t->d_ticket;
+  a.stamps = t->stamps_on ? t->d_stamps.get() : nullptr;
   a.zcap_layer = -1;
   if (t->gl >= 0) { a.kl_weight = t->kl_weight; a.sample = t->sample; a.seed = t->seed; a.step = (unsigned long long)t->iter; }
   return a;
@@ -807,7 +763,7 @@ static int launch_fused_train(v21_trainer* t, const float* x, long long ldx, con
   ChainArgs a{};
   static_cast<ChainModel&>(a) = chain_model(t);
   static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, m->dims[L], nullptr, row0);
-  a.stamps = t->stamps_on ? t->d_stamps : nullptr;  // (written by diagnostic builds only: -DV21_T_STAMPS)
+  a.stamps = t->stamps_on ? t->d_stamps.get() : nullptr;  // (written by diagnostic builds only: -DV21_T_STAMPS)
   a.fw = t->d_tstream; a.fw_bytes = (long long)t->tstream_padded * 1024;
   // rows of the resident training set: the kernels gather their 16-bit copy
   if (t->d_x16 && ldx == m->dims[0] && x >= t->d_x[0] && x < t->d_x[0] + (size_t)t->n[0] * ldx && (x - t->d_x[0]) % ldx == 0) {
@@ -858,20 +814,18 @@ ChainModel chain_model32(v21_trainer* t) {
   for (int l = 0; l < L; ++l) {
     ChainLayer& c = a.lt[l];
     c.K = m->dims[l]; c.N = m->nw(l);
-    c.KS = t->c32_frags(c.K); c.NT = t->c32_tiles(c.N);   // fragments per tile (32 wide; 64 in the 8-row kernel)
-    c.NS = t->c32_frags(c.N); c.KT = t->c32_tiles(c.K);
+    t->lay.layer(c, l);  // fragments per tile (32 wide; 64 in the 8-row kernel)
     c.relu = m->act[l] == V21_ACT_RELU;
     c.mask_tile = -1;
     if (c.relu && l + 1 < L) { c.mask_tile = mt; mt += c.NT; }
-    c.fw_off = t->fw_off[l] / 4; c.bw_off = t->bw_off[l] / 4;  // units of one lane's 16 bytes
     c.b_off = m->b_off[l];
     c.ht16 = t->d_ht[l]; c.dzt16 = t->d_dzt[l + 1];           // fp32, feature-major, batch contiguous (pitch Bp)
   }
   a.fw = t->d_fw; a.bw = t->d_bw; a.w = m->d_w;
-  a.fw_bytes = t->fw_bytes; a.bw_bytes = t->bw_bytes;
+  a.fw_bytes = t->lay.fw_bytes; a.bw_bytes = t->lay.bw_bytes;
   a.BS = t->Bp;
-  a.loss_acc = (unsigned long long*)t->d_ticket;
-  a.stamps = t->stamps_on ? t->d_stamps : nullptr;
+  a.loss_acc = t->d_ticket;
+  a.stamps = t->stamps_on ? t->d_stamps.get() : nullptr;
   a.zcap_layer = -1;
   a.jobs = t->d_jobs;
   if (t->gl >= 0) {
@@ -887,9 +841,9 @@ static int build_chain32s_jobs(v21_trainer* t) {
   c32s_build_jobs(a, tab.data());
   // the kernel follows these rows without range checks: every chunk and bias a row names must lie inside the buffers
   // allocated above, or the trainer is not created (the alternative is a GPU memory fault in the first step)
-  if (const char* why = c32s_validate_jobs(a, tab.data(), t->fw_bytes / 16, t->bw_bytes / 16, (long long)t->P))
+  if (const char* why = c32s_validate_jobs(a, tab.data(), t->lay.fw_bytes / 16, t->lay.bw_bytes / 16, (long long)t->P))
     return fail(V21_ERR_STATE, "%s", why);
-  HIPCHK(hipMalloc((void**)&t->d_jobs, tab.size() * sizeof(C32sJob)));
+  CHK(t->d_jobs.reserve(tab.size() * sizeof(C32sJob) / sizeof(int)));
   HIPCHK(hipMemcpyAsync(t->d_jobs, tab.data(), tab.size() * sizeof(C32sJob), hipMemcpyHostToDevice, t->ctx->stream));
   HIPCHK(hipStreamSynchronize(t->ctx->stream));
   return V21_OK;
@@ -946,7 +900,7 @@ void dw16_problems(v21_trainer* t, int rows, int brows, int* nslice_out, std::ve
     g.slab_stride = (long long)t->P + 4;
     g.out_scale = 1.0f / gs;
     if (l == 0) {
-      g.loss_acc = (unsigned long long*)t->d_ticket; g.loss_out = t->d_g + t->P;
+      g.loss_acc = t->d_ticket; g.loss_out = t->d_g + t->P;
       if (t->capturing) { g.loss_out2 = t->d_steploss; g.sc = step_ctx(t); }  // (eager steps: the loss is copied after the exchange)
     }
     probs.push_back(g);
@@ -1012,14 +966,14 @@ static void dw_adam_model(v21_trainer* t, DwAdamModel& md) {
     DwAdamLayer& d = md.lt[l];
     d.A = t->d_ht16[l]; d.B = t->d_dzt16[l + 1]; d.BS = t->BS;
     d.w = m->d_w + m->w_off[l]; d.m = t->d_m + m->w_off[l]; d.v = t->d_v + m->w_off[l]; d.g = t->d_g + m->w_off[l];
-    d.fw = t->d_fw; d.bw = t->d_bw; d.fw_off = t->fw_off[l]; d.bw_off = t->bw_off[l];
+    d.fw = t->d_fw; d.bw = t->d_bw; d.fw_off = t->lay.fw_off[l]; d.bw_off = t->lay.bw_off[l];
     d.K = m->dims[l]; d.N = m->nw(l);
-    d.KS = chain_steps(d.K); d.NS = chain_steps(d.N);
+    d.KS = t->lay.frags(d.K); d.NS = t->lay.frags(d.N);
     d.nt = (d.N + 31) / 32;
     d.first = nb;
     nb += ((d.K + 1 + 31) / 32) * d.nt;
     if (l == 0) {
-      d.loss_acc = (unsigned long long*)t->d_ticket; d.loss_out = t->d_g + t->P;
+      d.loss_acc = t->d_ticket; d.loss_out = t->d_g + t->P;
       d.loss_out2 = t->d_steploss;  // (may be null: then no step asks for a slot)
     }
   }
@@ -1048,12 +1002,12 @@ static int launch_dw_adam(v21_trainer* t, int rows, int brows, float alpha, int 
 }
 
 // group form (sweep, joint step): per-model blocks in a device table, refreshed when anything in them changed
-int refresh_dw_adam_table(const std::vector<v21_trainer*>& tr, DwAdamModel** d_tab, std::vector<DwAdamModel>& h_tab,
+int refresh_dw_adam_table(const std::vector<v21_trainer*>& tr, Dev<DwAdamModel>& d_tab, std::vector<DwAdamModel>& h_tab,
                                  hipStream_t st) {
   std::vector<DwAdamModel> tab(tr.size());
   for (size_t k = 0; k < tr.size(); ++k) dw_adam_model(tr[k], tab[k]);
-  if (!*d_tab) HIPCHK(hipMalloc((void**)d_tab, tab.size() * sizeof(DwAdamModel)));
-  return upload_if_changed(tab, h_tab, *d_tab, st);
+  CHK(d_tab.reserve(tab.size()));
+  return upload_if_changed(tab, h_tab, d_tab.get(), st);
 }
 // every model takes one Adam step (iter advanced here) on the operands its chain launch left; slot: see DwAdamStep
 int launch_dw_adam_group(const std::vector<v21_trainer*>& tr, const DwAdamModel* d_tab,
@@ -1111,13 +1065,13 @@ int dw32_model(const v21_trainer* t, int tile, Dw32Model& md) {
     g.a_scale = g.b_scale = g.out_scale = 1.f;
     md.grp.first[l] = blocks;
     blocks += g.nx * g.ny;
-    md.ad.lt[l] = NtAdamLayer{m->w_off[l], t->fw_off[l], t->bw_off[l], m->dims[l], t->c32_frags(m->dims[l]), t->c32_frags(m->nw(l))};
+    md.ad.lt[l] = NtAdamLayer{m->w_off[l], t->lay.fw_off[l], t->lay.bw_off[l], m->dims[l], t->lay.frags(m->dims[l]), t->lay.frags(m->nw(l))};
   }
   md.grp.first[L] = blocks;
   NtAdamInfo& ad = md.ad;
-  ad.w = m->d_w; ad.m = t->d_m; ad.v = t->d_v; ad.fw = (float*)t->d_fw; ad.bw = (float*)t->d_bw;
+  ad.w = m->d_w; ad.m = t->d_m; ad.v = t->d_v; ad.fw = (float*)t->d_fw.get(); ad.bw = (float*)t->d_bw.get();
   ad.omb1 = 1.0f - t->adam.beta1; ad.omb2 = 1.0f - t->adam.beta2; ad.eps = t->adam.eps;
-  ad.loss_acc = (unsigned long long*)t->d_ticket; ad.loss_out = t->d_g + t->P; ad.loss_out2 = t->d_steploss;
+  ad.loss_acc = t->d_ticket; ad.loss_out = t->d_g + t->P; ad.loss_out2 = t->d_steploss;
   ad.loss_slot = -1;
   ad.fmt = t->chain32s ? 4 : 3;
   return blocks;
@@ -1161,7 +1115,7 @@ static int update32(v21_trainer* t, const StepRoute& r, int rows, const StepLoss
   const int fold = sl.nslice > 1 && single ? sl.nslice : 1;  // single rank: Adam sums the slabs itself
   if (sl.nslice > 1 && fold == 1) CHK(reduce_slabs(t, sl.nslice));
   if (!single) {  // the loss numerator rides in slot P of the arena: it must be there before the exchange
-    hipLaunchKernelGGL(chain32_loss_kernel, dim3(1), dim3(1), 0, st, (unsigned long long*)t->d_ticket, t->d_g + t->P);
+    hipLaunchKernelGGL(chain32_loss_kernel, dim3(1), dim3(1), 0, st, t->d_ticket.get(), t->d_g + t->P);
     HIPCHK(hipGetLastError());
   }
   phase_mark(t, 2);
@@ -1322,16 +1276,14 @@ static bool graph_eligible(const v21_trainer* t) {
   return t->graph_mode == 1 && t->ctx->nranks == 1 && t->gl < 0;
 }
 static int ensure_desc(v21_trainer* t, long long n) {
-  if (t->desc_cap >= n) return V21_OK;
+  if (t->d_desc.n >= (size_t)n) return V21_OK;
   HIPCHK(hipStreamSynchronize(t->ctx->stream));
-  if (t->d_desc) HIPCHK(hipFree(t->d_desc));
-  if (t->h_desc) HIPCHK(hipHostFree(t->h_desc));
-  HIPCHK(hipMalloc((void**)&t->d_desc, (size_t)n * sizeof(StepDesc)));
-  HIPCHK(hipHostMalloc((void**)&t->h_desc, (size_t)n * sizeof(StepDesc), hipHostMallocDefault));
-  if (!t->d_cur) HIPCHK(hipMalloc((void**)&t->d_cur, 16));
-  t->desc_cap = n;
   destroy_graphs(t);  // captured steps hold the old table
-  return V21_OK;
+  t->d_desc.release();  // (its capacity says that table, staging copy and cursor are there: it is allocated last)
+  if (t->h_desc) { HIPCHK(hipHostFree(t->h_desc)); t->h_desc = nullptr; }
+  HIPCHK(hipHostMalloc((void**)&t->h_desc, (size_t)n * sizeof(StepDesc), hipHostMallocDefault));
+  CHK(t->d_cur.reserve(4));
+  return t->d_desc.reserve((size_t)n);
 }
 // upload descriptors [0, count) from h_desc and point the device cursor at the first
 // descriptors of the next `count` steps (step s: first row s * stride), staged, uploaded; the device cursor at the first
@@ -1412,23 +1364,16 @@ int upload_rows(v21_trainer* t, const int32_t* perm, const int** d_idx) {
   if (!perm) return V21_OK;
   const long long n = t->n[0];
   CHK(check_row_table(perm, n));
-  if (t->perm_cap < n) {
-    if (t->d_perm) HIPCHK(hipFree(t->d_perm));
-    HIPCHK(hipMalloc((void**)&t->d_perm, (size_t)n * sizeof(int)));
-    t->perm_cap = n;
-  }
+  CHK(t->d_perm.reserve((size_t)n));
   HIPCHK(hipMemcpyAsync(t->d_perm, perm, (size_t)n * sizeof(int), hipMemcpyHostToDevice, t->ctx->stream));
   *d_idx = t->d_perm;
   return V21_OK;
 }
 int ensure_steploss(v21_trainer* t, long long cap) {
-  if (t->steploss_cap >= cap) return V21_OK;
+  if (t->d_steploss.n >= (size_t)cap) return V21_OK;
   HIPCHK(hipStreamSynchronize(t->ctx->stream));
   destroy_graphs(t);  // captured steps hold the old pointer
-  if (t->d_steploss) HIPCHK(hipFree(t->d_steploss));
-  HIPCHK(hipMalloc((void**)&t->d_steploss, (size_t)cap * sizeof(float)));
-  t->steploss_cap = cap;
-  return V21_OK;
+  return t->d_steploss.reserve((size_t)cap);
 }
 int epoch_losses(const std::vector<v21_trainer*>& trs, long long steps, long long n, double* loss) {
   hipStream_t st = trs[0]->ctx->stream;
@@ -1656,8 +1601,8 @@ extern "C" int v21_debug_check_chain_jobs(v21_trainer* t, long long fw_bytes, lo
   const ChainModel a = chain_model32(t);
   std::vector<C32sJob> tab((size_t)2 * a.L * kC32sWaves);
   c32s_build_jobs(a, tab.data());
-  if (const char* why = c32s_validate_jobs(a, tab.data(), (fw_bytes < 0 ? t->fw_bytes : fw_bytes) / 16,
-                                           (bw_bytes < 0 ? t->bw_bytes : bw_bytes) / 16, (long long)t->P))
+  if (const char* why = c32s_validate_jobs(a, tab.data(), (fw_bytes < 0 ? t->lay.fw_bytes : fw_bytes) / 16,
+                                           (bw_bytes < 0 ? t->lay.bw_bytes : bw_bytes) / 16, (long long)t->P))
     return fail(V21_ERR_STATE, "%s", why);
   return V21_OK;
 }

@@ -1485,6 +1485,49 @@ def test_a_script_that_ends_with_live_joint_sweep_and_trainers_exits_cleanly(tmp
         assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
 
 
+def test_created_and_destroyed_handles_give_their_device_memory_back(ctx):
+    """Every device buffer of a stack and a trainer is owned by a member whose destructor frees it (csrc/api_internal.h:
+    Dev).  One warm-up round, then 200 rounds of stack + trainer (f16, and f32 with a variational head) + set_data + one
+    step + destroy: the device's free memory may fall by what the allocator keeps, but by less than ONE round holds while
+    alive -- a single trainer buffer forgotten per round would show as 200 of them."""
+    import gc
+    import torch
+    native = pkg("_native")
+    n = 256
+    x = np.random.default_rng(0).uniform(-1, 1, size=(n, 451)).astype(np.float32)
+    w = np.full(n, 1.0 / 451, np.float32)
+
+    def build():
+        objs = []
+        for act, prec in (([1, 0, 1, 1, 0], "f16"), ([1, 2, 1, 1, 0], "f32")):
+            st = native.Stack(ctx, [451, 352, 9, 32, 352, 451], act)
+            st.set_weights((np.random.default_rng(1).normal(size=st.num_params) * 0.03).astype(np.float32))
+            tr = native.Trainer(st, prec, n)
+            tr.set_adam(lr=1e-4)
+            tr.set_data(0, x, None, w)
+            tr.set_data(1, x[:100], None, w[:100])
+            assert np.isfinite(tr.run_epoch(None, n))
+            objs += [tr, st]
+        return objs
+
+    def free_bytes():
+        gc.collect()
+        ctx.sync()
+        return torch.cuda.mem_get_info()[0]
+
+    del build()[:]
+    before = free_bytes()
+    alive = build()
+    held = before - free_bytes()
+    del alive[:]
+    for _ in range(200):
+        del build()[:]
+    fall = before - free_bytes()
+    print("one round holds %d bytes while alive; free memory fell by %d bytes over 200 rounds" % (held, fall))
+    assert held > 0
+    assert fall < held, (fall, held)
+
+
 @pytest.mark.parametrize("rows_per_wave", [32, 16])
 def test_fused_training_gathers_the_resident_16_bit_copy_with_identical_results(ctx, rows_per_wave, monkeypatch):
     """v21_trainer_set_data keeps the training inputs of a trainer with a fused training kernel as 16-bit rows as well
