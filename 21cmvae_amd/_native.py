@@ -7,6 +7,7 @@ the library and listing its symbols works without a GPU (used by the CPU test su
 import ctypes as C
 import os
 import threading
+import weakref
 
 import numpy as np
 
@@ -168,10 +169,9 @@ TRAIN_UPD_ROUTES = {1: "per_layer", 2: "dw16_adam", 3: "dw16_splitk", 4: "dwadam
 
 def route_forward(dims, act, precision, n, flags=0, rt_ready=False):
     """The route v21_mlp_forward_dev takes for n rows of this stack (pure host logic: no GPU).  -> name of FWD_ROUTES."""
-    L = len(act)
     r = C.c_int(0)
-    check(load_library().v21_route_forward(L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act]),
-                                           precision_id(precision), int(n), int(flags), 1 if rt_ready else 0, C.byref(r)))
+    check(load_library().v21_route_forward(*_layers(dims, act), precision_id(precision), int(n), int(flags), 1 if rt_ready else 0,
+                                           C.byref(r)))
     return FWD_ROUTES[r.value]
 
 
@@ -180,10 +180,8 @@ JAC_ROUTES = {1: "fused", 2: "generic"}
 
 def route_jacobian(dims, act, precision, n, flags=0):
     """The route v21_mlp_jacobian / v21_mlp_loglike take for this stack (pure host logic: no GPU).  -> name of JAC_ROUTES."""
-    L = len(act)
     r = C.c_int(0)
-    check(load_library().v21_route_jacobian(L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act]),
-                                            precision_id(precision), int(n), int(flags), C.byref(r)))
+    check(load_library().v21_route_jacobian(*_layers(dims, act), precision_id(precision), int(n), int(flags), C.byref(r)))
     return JAC_ROUTES[r.value]
 
 
@@ -191,10 +189,9 @@ def route_train(dims, act, precision, max_batch, rows, nranks=1, rt_ready=False)
     """The kernels one optimizer step of `rows` rows takes for a trainer created with max_batch on nranks ranks (pure host
     logic: no GPU; rt_ready: the run-time instantiated fused training kernel of a stack outside archs.h has arrived).
     -> (name of TRAIN_FWD_ROUTES, name of TRAIN_UPD_ROUTES)."""
-    L = len(act)
     f, u = C.c_int(0), C.c_int(0)
-    check(load_library().v21_route_train(L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act]),
-                                         precision_id(precision), int(max_batch), int(rows), int(nranks), 1 if rt_ready else 0, C.byref(f), C.byref(u)))
+    check(load_library().v21_route_train(*_layers(dims, act), precision_id(precision), int(max_batch), int(rows), int(nranks),
+                                         1 if rt_ready else 0, C.byref(f), C.byref(u)))
     return TRAIN_FWD_ROUTES[f.value], TRAIN_UPD_ROUTES[u.value]
 
 
@@ -238,17 +235,43 @@ def precision_id(p):
         raise ValueError("unknown precision %r (use f32, f16 or bf16)" % (p,)) from None
 
 
+def _layers(dims, act):
+    """A stack's layout as the C ABI takes it: (L, int[L + 1] widths, int[L] activations)."""
+    L = len(act)
+    return L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act])
+
+
 def _row_table(perm, n_rows, who):
-    """An epoch's row table as the C ABI takes it: int32, contiguous, one entry per row of the training set (the library
-    reads exactly that many entries from the pointer: a shorter array would be read past its end)."""
+    """An epoch's row table as the C ABI takes it: a pointer to int32, contiguous, one entry per row of the training set (the
+    library reads exactly that many entries from the pointer: a shorter array would be read past its end); None (the rows
+    in order) stays None.  (The pointer keeps its array alive.)"""
+    if perm is None:
+        return None
     perm = np.ascontiguousarray(perm, dtype=np.int32)
     if n_rows is not None and perm.shape != (n_rows,):
         raise ValueError("%s: the row table has shape %s, the training set has %d rows" % (who, perm.shape, n_rows))
-    return perm
+    return perm.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def _fptr(a):
     return a.ctypes.data_as(_F)
+
+
+def _opt(a):
+    """An optional pointer argument: a float32 numpy array -> float*, a device address -> void*, None / 0 -> NULL."""
+    if isinstance(a, np.ndarray):
+        return _fptr(a)
+    return _P(a) if a else None
+
+
+def _last_route(fn, h, tables, slots=8):
+    """fn(h, int* route per table, long long counts[slots] per table) -> ([name of the last route per table],
+    [{route name: calls since creation, zero counts left out} per table])."""
+    routes = [C.c_int(0) for _ in tables]
+    counts = [(C.c_longlong * slots)() for _ in tables]
+    check(fn(h, *[C.byref(r) for r in routes], *counts))
+    return ([t.get(r.value, "none") for t, r in zip(tables, routes)],
+            [{t[i]: int(c[i]) for i in t if c[i]} for t, c in zip(tables, counts)])
 
 
 class _Owned:
@@ -304,6 +327,9 @@ class Context:
         check(self.lib.v21_ctx_create(device, C.byref(h)))
         self.h, self.device = h, device
         self.lock = threading.Lock()
+        self.nranks, self.rank = 1, 0  # the data-parallel communicator's (comm_init*)
+        self._host_ops = None          # comm_init_host: the callbacks the library holds pointers to
+        self._pin_pool = {"free": [], "live": 0, "lock": threading.Lock()}  # pinned_empty: (pointer, bytes) of idle buffers
 
     @classmethod
     def default(cls, device=None):
@@ -352,13 +378,10 @@ class Context:
 
     def pinned_empty(self, shape, dtype=np.float32):
         """A numpy array in page-locked memory, or None (pool exhausted / small / unavailable)."""
-        import weakref
         nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         if nbytes < self.PIN_MIN_BYTES:
             return None
-        import threading
-        pool = self.__dict__.setdefault("_pin_pool", {"free": [], "live": 0, "lock": threading.Lock()})
-        ptr = None
+        pool, ptr = self._pin_pool, None
         with pool["lock"]:  # finalizers of released arrays may run on any thread
             for i, (p, cap) in enumerate(pool["free"]):
                 if cap >= nbytes:
@@ -416,8 +439,6 @@ class Context:
         buf = (C.c_ubyte * COMM_ID_BYTES)()
         check(self.lib.v21_comm_get_unique_id(self.h, buf))
         return bytes(buf)
-
-    nranks, rank = 1, 0
 
     def comm_init(self, nranks, rank, uid):
         buf = (C.c_ubyte * COMM_ID_BYTES).from_buffer_copy(uid)
@@ -495,15 +516,15 @@ class Stack(_Owned):
         self.ctx, self.lib = ctx, ctx.lib
         self.dims, self.act = [int(d) for d in dims], [int(a) for a in act]
         assert len(self.act) == len(self.dims) - 1
-        L = len(self.act)
         h = _P()
-        check(self.lib.v21_mlp_create(ctx.h, L, (C.c_int * (L + 1))(*self.dims), (C.c_int * L)(*self.act), C.byref(h)))
+        check(self.lib.v21_mlp_create(ctx.h, *_layers(self.dims, self.act), C.byref(h)))
         self.h = h
         self._own(self.lib.v21_mlp_destroy)
         n = C.c_size_t(0)
         check(self.lib.v21_mlp_num_params(h, C.byref(n)))
         self.num_params = n.value
-        self._mean_keep = None
+        # what the device holds, as use_output_stats / use_input_stats / use_likelihood left it (None: nothing, or set directly)
+        self.out_stats = self.in_stats = self.lk_record = None
 
     def set_weights(self, flat):
         flat = np.ascontiguousarray(flat, dtype=np.float32).ravel()
@@ -515,6 +536,7 @@ class Stack(_Owned):
         return out
 
     def set_input_transform(self, log_mask, zero_floor, lo, hi):
+        self.in_stats = None
         if log_mask is None:
             check(self.lib.v21_mlp_set_input_transform(self.h, None))
             return
@@ -529,12 +551,34 @@ class Stack(_Owned):
         check(self.lib.v21_mlp_set_input_transform(self.h, C.byref(t)))
 
     def set_output_transform(self, std, mean):
+        self.out_stats = None
         if mean is None:
             check(self.lib.v21_mlp_set_output_transform(self.h, None))
             return
         mean = np.ascontiguousarray(mean, dtype=np.float32)
         t = AffineOut(float(std), _fptr(mean), mean.size)
         check(self.lib.v21_mlp_set_output_transform(self.h, C.byref(t)))
+
+    # The records the class surface evaluates with, uploaded only when they changed: the statistics records are compared
+    # by identity (preprocess hands out a new one whenever the training set changed), the likelihood record by value.
+    def use_output_stats(self, ss):
+        """set_output_transform from a preprocess.SignalStats record"""
+        if self.out_stats is not ss:
+            self.set_output_transform(ss.std, ss.mean)
+            self.out_stats = ss
+
+    def use_input_stats(self, ps):
+        """set_input_transform from a preprocess.ParamStats record"""
+        if self.in_stats is not ps:
+            self.set_input_transform(ps.log_mask, ps.zero_floor, ps.lo, ps.hi)
+            self.in_stats = ps
+
+    def use_likelihood(self, d, w):
+        """set_likelihood(d, w); the record is kept on the host as `lk_record` = (d, w)"""
+        rec = self.lk_record
+        if rec is None or not (np.array_equal(rec[0], d) and np.array_equal(rec[1], w)):
+            self.set_likelihood(d, w)
+            self.lk_record = (d.copy(), w.copy())
 
     def has_fused(self, precision="f32"):
         y = C.c_int(0)
@@ -544,10 +588,8 @@ class Stack(_Owned):
     def last_route(self):
         """(route name of the last device forward call, {route name: calls since creation}) -- written where the kernels
         are launched (include/v21.h: v21_mlp_last_route)."""
-        r = C.c_int(0)
-        cnt = (C.c_longlong * 8)()
-        check(self.lib.v21_mlp_last_route(self.h, C.byref(r), cnt))
-        return FWD_ROUTES.get(r.value, "none"), {FWD_ROUTES[i]: int(cnt[i]) for i in FWD_ROUTES if cnt[i]}
+        (last,), (counts,) = _last_route(self.lib.v21_mlp_last_route, self.h, [FWD_ROUTES])
+        return last, counts
 
     def jit(self, precision="f32", wait_ms=-1):
         """Ask for the fused kernel of THIS stack (run-time instantiation, include/v21.h: v21_mlp_jit) and wait up to
@@ -558,15 +600,7 @@ class Stack(_Owned):
 
     def forward(self, x, precision="f32", flags=0):
         """host (n, in) float32/float64 -> host (n, out) float32"""
-        x = np.asarray(x)
-        if x.dtype == np.float64:
-            dt = 1
-        else:
-            x = x.astype(np.float32, copy=False)
-            dt = 0
-        x = np.ascontiguousarray(x)
-        if x.ndim != 2 or x.shape[1] != self.dims[0]:
-            raise ValueError("expected input of shape (n, %d), got %r" % (self.dims[0], x.shape))
+        x, dt = self._rows(x)
         y = self.ctx.pinned_empty((x.shape[0], self.dims[-1]))
         if y is None:
             y = np.empty((x.shape[0], self.dims[-1]), np.float32)
@@ -576,6 +610,7 @@ class Stack(_Owned):
         return y
 
     def _rows(self, x):
+        """host rows as the library takes them: (contiguous (n, in) float32 or float64, 1 for float64 / 0)"""
         x = np.asarray(x)
         if x.dtype != np.float64:
             x = x.astype(np.float32, copy=False)
@@ -592,12 +627,13 @@ class Stack(_Owned):
         jac = np.empty((n, din, dout), np.float32)
         y = np.empty((n, dout), np.float32) if return_outputs else None
         with self.ctx.lock:
-            check(self.lib.v21_mlp_jacobian(self.h, x.ctypes.data_as(_P), dt, n, _fptr(y) if y is not None else None, _fptr(jac),
+            check(self.lib.v21_mlp_jacobian(self.h, x.ctypes.data_as(_P), dt, n, _opt(y), _fptr(jac),
                                             precision_id(precision), flags))
         return (y, jac) if return_outputs else jac
 
     def set_likelihood(self, data, inv_var):
         """Gaussian likelihood record: data d and inverse variances 1 / sigma^2 per output bin (copied; None clears)."""
+        self.lk_record = None
         if data is None:
             check(self.lib.v21_mlp_set_likelihood(self.h, None, None, 0))
             return
@@ -614,17 +650,14 @@ class Stack(_Owned):
         lnl = np.empty(n, np.float32)
         g = np.empty((n, self.dims[0]), np.float32) if grad else None
         with self.ctx.lock:
-            check(self.lib.v21_mlp_loglike(self.h, x.ctypes.data_as(_P), dt, n, _fptr(lnl), _fptr(g) if g is not None else None,
-                                           precision_id(precision), flags))
+            check(self.lib.v21_mlp_loglike(self.h, x.ctypes.data_as(_P), dt, n, _fptr(lnl), _opt(g), precision_id(precision), flags))
         return (lnl, g) if grad else lnl
 
     def jacobian_dev(self, d_x, ldx, n, d_y, ldy, d_jac, precision="f32", flags=0):
-        check(self.lib.v21_mlp_jacobian_dev(self.h, _P(d_x), ldx, n, _P(d_y) if d_y else None, ldy, _P(d_jac),
-                                            precision_id(precision), flags))
+        check(self.lib.v21_mlp_jacobian_dev(self.h, _P(d_x), ldx, n, _opt(d_y), ldy, _P(d_jac), precision_id(precision), flags))
 
     def loglike_dev(self, d_x, ldx, n, d_lnl, d_grad, precision="f32", flags=0):
-        check(self.lib.v21_mlp_loglike_dev(self.h, _P(d_x), ldx, n, _P(d_lnl), _P(d_grad) if d_grad else None,
-                                           precision_id(precision), flags))
+        check(self.lib.v21_mlp_loglike_dev(self.h, _P(d_x), ldx, n, _P(d_lnl), _opt(d_grad), precision_id(precision), flags))
 
     def fisher(self, x, precision="f32", flags=0, lnl=False, grad=False):
         """host (n, in) -> F (n, in, in) float32, F = J^T W J with W the inverse variances of the likelihood record
@@ -635,8 +668,7 @@ class Stack(_Owned):
         lv = np.empty(n, np.float32) if lnl else None
         g = np.empty((n, din), np.float32) if grad else None
         with self.ctx.lock:
-            check(self.lib.v21_mlp_fisher(self.h, x.ctypes.data_as(_P), dt, n, _fptr(F), _fptr(lv) if lv is not None else None,
-                                          _fptr(g) if g is not None else None, precision_id(precision), flags))
+            check(self.lib.v21_mlp_fisher(self.h, x.ctypes.data_as(_P), dt, n, _fptr(F), _opt(lv), _opt(g), precision_id(precision), flags))
         return (F,) + tuple(a for a in (lv, g) if a is not None) if (lnl or grad) else F
 
     @staticmethod
@@ -672,8 +704,8 @@ class Stack(_Owned):
         lnl, l0, status = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32)
         F = np.empty((n, din, din), np.float32) if fisher else None
         with self.ctx.lock:
-            check(self.lib.v21_mlp_fit(self.h, x.ctypes.data_as(_P), dt, n, _fptr(dp) if dp is not None else None, nd, C.byref(opts),
-                                       xh.ctypes.data_as(_P), _fptr(lnl), _fptr(l0), _fptr(F) if F is not None else None,
+            check(self.lib.v21_mlp_fit(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(opts),
+                                       xh.ctypes.data_as(_P), _fptr(lnl), _fptr(l0), _opt(F),
                                        status.ctypes.data_as(C.POINTER(C.c_int32)), precision_id(precision), flags))
         out = {"x_hat": xh, "lnl": lnl, "lnl_start": l0, "status": status}
         if fisher:
@@ -681,22 +713,18 @@ class Stack(_Owned):
         return out
 
     def fisher_dev(self, d_x, ldx, n, d_fisher, d_lnl=None, d_grad=None, precision="f32", flags=0):
-        check(self.lib.v21_mlp_fisher_dev(self.h, _P(d_x), ldx, n, _P(d_fisher), _P(d_lnl) if d_lnl else None,
-                                          _P(d_grad) if d_grad else None, precision_id(precision), flags))
+        check(self.lib.v21_mlp_fisher_dev(self.h, _P(d_x), ldx, n, _P(d_fisher), _opt(d_lnl), _opt(d_grad), precision_id(precision), flags))
 
     def fit_dev(self, d_x0, ldx, n, d_data, n_data, d_x_hat, d_lnl, d_lnl_start=None, d_fisher=None, d_status=None,
                 precision="f32", flags=0, **opts):
         o = self.fit_opts(**opts)
-        check(self.lib.v21_mlp_fit_dev(self.h, _P(d_x0), ldx, n, _P(d_data) if d_data else None, n_data, C.byref(o), _P(d_x_hat),
-                                       _P(d_lnl), _P(d_lnl_start) if d_lnl_start else None, _P(d_fisher) if d_fisher else None,
-                                       _P(d_status) if d_status else None, precision_id(precision), flags))
+        check(self.lib.v21_mlp_fit_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), _P(d_x_hat), _P(d_lnl),
+                                       _opt(d_lnl_start), _opt(d_fisher), _opt(d_status), precision_id(precision), flags))
 
     def last_jac_route(self):
         """(route name of the last Jacobian / log-likelihood call, {route name: calls since creation})."""
-        r = C.c_int(0)
-        cnt = (C.c_longlong * 4)()
-        check(self.lib.v21_mlp_last_jac_route(self.h, C.byref(r), cnt))
-        return JAC_ROUTES.get(r.value, "none"), {JAC_ROUTES[i]: int(cnt[i]) for i in JAC_ROUTES if cnt[i]}
+        (last,), (counts,) = _last_route(self.lib.v21_mlp_last_jac_route, self.h, [JAC_ROUTES], slots=4)
+        return last, counts
 
     def forward_clocked(self, d_x, ldx, n, d_y, ldy, d_stamps, precision="f16", flags=0):
         """forward_dev through the clock-stamped instantiation of the headline stack's kernel (include/v21.h:
@@ -707,12 +735,13 @@ class Stack(_Owned):
         check(self.lib.v21_mlp_forward_dev(self.h, _P(d_x), ldx, n, _P(d_y), ldy, precision_id(precision), flags))
 
 
+def _prebuild(dims, act, kernel, directory):
+    check(load_library().v21_jit_prebuild(*_layers(dims, act), kernel, directory.encode() if directory else None))
+
+
 def jit_prebuild_train(dims, act, precision, directory=None):
     """jit_prebuild for the fused TRAINING kernel of (dims, act, f16 | bf16) (include/v21.h: v21_trainer_jit)."""
-    lib = load_library()
-    L = len(act)
-    check(lib.v21_jit_prebuild(L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act]),
-                               precision_id(precision) | 16, directory.encode() if directory else None))
+    _prebuild(dims, act, precision_id(precision) | 16, directory)
 
 
 def jit_prebuild(dims, act, precision, directory=None):
@@ -720,10 +749,7 @@ def jit_prebuild(dims, act, precision, directory=None):
     Needs hiprtc but no GPU.  Call it from a process that has not loaded ANOTHER LLVM (importing torch does: hiprtc then
     finds that copy's option table, which lacks the AMDGPU flags, and LLVM ends the process) -- a build step, as
     __graft_entry__.build() uses it; at run time the library compiles in a child process of its own (csrc/jitc_main.cpp)."""
-    lib = load_library()
-    L = len(act)
-    check(lib.v21_jit_prebuild(L, (C.c_int * (L + 1))(*[int(d) for d in dims]), (C.c_int * L)(*[int(a) for a in act]),
-                               precision_id(precision), directory.encode() if directory else None))
+    _prebuild(dims, act, precision_id(precision), directory)
 
 
 class Trainer(_Owned):
@@ -736,6 +762,8 @@ class Trainer(_Owned):
         self.h = h
         self._own(self.lib.v21_trainer_destroy, [stack])
         self.max_batch = int(max_batch)
+        self._resident = {}   # set_data: split -> (shape, hash) of the buffers the device holds
+        self.n_train = None   # rows of the training split, once set_data(0, ...) has run
 
     def set_adam(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7):
         cfg = Adam(lr, beta1, beta2, eps)
@@ -761,25 +789,19 @@ class Trainer(_Owned):
         # One pass of the hash is ~2 ms for the reference's 44 MB against ~6.5 ms of pageable upload.
         from .preprocess import _digest
         key = tuple((a.shape, _digest(a.reshape(-1).view(np.uint8).data)) if a is not None else None for a in (x, y, rw))
-        if getattr(self, "_resident", None) is None:
-            self._resident = {}
         if self._resident.get(which) == key:
             return
         self._resident.pop(which, None)
-        check(self.lib.v21_trainer_set_data(self.h, which, _fptr(x), _fptr(y) if y is not None else None,
-                                            _fptr(rw), x.shape[0]))
+        check(self.lib.v21_trainer_set_data(self.h, which, _fptr(x), _opt(y), _fptr(rw), x.shape[0]))
         self._resident[which] = key
         if which == 0:
             self.n_train = int(x.shape[0])
 
     def run_epoch(self, perm, batch):
         loss = C.c_double(0)
-        pp = None
-        if perm is not None:
-            perm = _row_table(perm, getattr(self, "n_train", None), "Trainer.run_epoch")
-            pp = perm.ctypes.data_as(C.POINTER(C.c_int32))
+        rows = _row_table(perm, self.n_train, "Trainer.run_epoch")
         with self.ctx.lock:
-            check(self.lib.v21_trainer_run_epoch(self.h, pp, int(batch), C.byref(loss)))
+            check(self.lib.v21_trainer_run_epoch(self.h, rows, int(batch), C.byref(loss)))
         return loss.value
 
     def evaluate(self, which, batch):
@@ -796,7 +818,7 @@ class Trainer(_Owned):
         return x.value, y.value, rw.value, n.value
 
     def step_dev(self, d_x, d_y, d_rw, n_rows, global_rows=None):
-        check(self.lib.v21_trainer_step_dev(self.h, _P(d_x), _P(d_y) if d_y else None, _P(d_rw), int(n_rows),
+        check(self.lib.v21_trainer_step_dev(self.h, _P(d_x), _opt(d_y), _P(d_rw), int(n_rows),
                                             int(global_rows if global_rows is not None else n_rows)))
 
     def last_step_loss(self):
@@ -814,8 +836,7 @@ class Trainer(_Owned):
         n = self.stack.num_params
         m = None if m is None else np.ascontiguousarray(m, np.float32)
         v = None if v is None else np.ascontiguousarray(v, np.float32)
-        check(self.lib.v21_trainer_set_state(self.h, int(it), _fptr(m) if m is not None else None,
-                                             _fptr(v) if v is not None else None, n))
+        check(self.lib.v21_trainer_set_state(self.h, int(it), _opt(m), _opt(v), n))
 
     def set_vae(self, kl_weight, sample=True, seed=0):
         """Variational mode of a stack with an ACT_GAUSS layer (include/v21.h: v21_trainer_set_vae)."""
@@ -882,12 +903,9 @@ class Trainer(_Owned):
     def last_route(self):
         """((forward route, update route) of the last eager step, {(fwd or upd) route name: steps since creation}) -- written
         where the kernels are launched (include/v21.h: v21_trainer_last_route)."""
-        f, u = C.c_int(0), C.c_int(0)
-        fc, uc = (C.c_longlong * 8)(), (C.c_longlong * 8)()
-        check(self.lib.v21_trainer_last_route(self.h, C.byref(f), C.byref(u), fc, uc))
-        counts = {TRAIN_FWD_ROUTES[i]: int(fc[i]) for i in TRAIN_FWD_ROUTES if fc[i]}
-        counts.update({"upd:" + TRAIN_UPD_ROUTES[i]: int(uc[i]) for i in TRAIN_UPD_ROUTES if uc[i]})
-        return (TRAIN_FWD_ROUTES.get(f.value, "none"), TRAIN_UPD_ROUTES.get(u.value, "none")), counts
+        last, (counts, upd) = _last_route(self.lib.v21_trainer_last_route, self.h, [TRAIN_FWD_ROUTES, TRAIN_UPD_ROUTES])
+        counts.update(("upd:" + k, v) for k, v in upd.items())
+        return tuple(last), counts
 
     def enable_stamps(self, on=True):
         """Cycle stamps of the chain kernel's phases (diagnostics; off by default: they cost 2-3 us per step)."""
@@ -908,7 +926,7 @@ class Joint(_Owned):
     """Autoencoder + latent emulator stepping together on the same rows (v21_joint_*; BASELINE configs[2])."""
 
     def __init__(self, ae_trainer, em_trainer, latent_layer):
-        self.lib = ae_trainer.lib
+        self.lib, self.ctx = ae_trainer.lib, ae_trainer.ctx
         self.trainers = (ae_trainer, em_trainer)  # keep them alive
         h = _P()
         check(self.lib.v21_joint_create(ae_trainer.h, em_trainer.h, int(latent_layer), C.byref(h)))
@@ -918,17 +936,16 @@ class Joint(_Owned):
     def run_epoch(self, perm, batch):
         """-> (autoencoder epoch loss, emulator epoch loss)"""
         out = (C.c_double * 2)()
-        pp = None
-        if perm is not None:
-            perm = _row_table(perm, getattr(self.trainers[0], "n_train", None), "Joint.run_epoch")
-            pp = perm.ctypes.data_as(C.POINTER(C.c_int32))
-        check(self.lib.v21_joint_run_epoch(self.h, pp, int(batch), out))
+        rows = _row_table(perm, self.trainers[0].n_train, "Joint.run_epoch")
+        with self.ctx.lock:
+            check(self.lib.v21_joint_run_epoch(self.h, rows, int(batch), out))
         return float(out[0]), float(out[1])
 
     def evaluate(self):
         """-> (autoencoder validation loss, emulator validation loss against the current encoder's latents)"""
         out = (C.c_double * 2)()
-        check(self.lib.v21_joint_eval(self.h, out))
+        with self.ctx.lock:
+            check(self.lib.v21_joint_eval(self.h, out))
         return float(out[0]), float(out[1])
 
 
@@ -947,10 +964,7 @@ class Sweep(_Owned):
 
     def run_epoch(self, perm, batch):
         losses = (C.c_double * len(self.trainers))()
-        pp = None
-        if perm is not None:
-            perm = _row_table(perm, getattr(self.trainers[0], "n_train", None), "Sweep.run_epoch")
-            pp = perm.ctypes.data_as(C.POINTER(C.c_int32))
+        rows = _row_table(perm, self.trainers[0].n_train, "Sweep.run_epoch")
         with self.ctx.lock:
-            check(self.lib.v21_sweep_run_epoch(self.h, pp, int(batch), losses))
+            check(self.lib.v21_sweep_run_epoch(self.h, rows, int(batch), losses))
         return [float(v) for v in losses]

@@ -12,13 +12,22 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import preprocess as pp
+from . import _native as nat, engine, preprocess as pp
 from .callbacks import TqdmCallback
 from .engine import ChainedModel, Dense, GaussianLatent, Input, Model, Sequential, sequential_from_arrays
 from .losses import mean_squared_error, relative_mse_loss  # noqa: F401  (public, as in the reference)
 
 PATH = os.path.dirname(os.path.abspath(__file__)) + "/"
-_native = None
+
+
+def _with_tqdm(verbose, *callback_lists):
+    """``verbose="tqdm"``: a progress bar on (a copy of) every callback list and no printing.  -> (verbose, *lists)"""
+    lists = [list(c) for c in callback_lists]  # (copies: the reference appends to its default-argument lists)
+    if verbose == "tqdm":
+        for c in lists:
+            c.append(TqdmCallback())
+        verbose = 0
+    return (verbose, *lists)
 
 
 def _gen_model(in_dim, hidden_dims, out_dim, activation_func, name=None, variational=False):
@@ -182,57 +191,38 @@ class _EmulatorBase:
             setattr(self, k, v)
         self.par_labels = list(_EmulatorBase.par_labels)
 
-    def _predict_stack(self, model, params, devices=None):
-        """par_transform -> device stack -> unpreproc, squeezing a single row (emulator.py:401-407 / :788-795).
-        Both transforms run inside the library: float32 and float64 parameter arrays are handed over RAW and take the
-        reference's branch for their dtype there (include/v21.h: v21_affine_in; few rows: on the host while they are
-        padded, many: in float64 on the device, so a 65,536-row call is bound by the 118 MB of results over PCIe and not
-        by a 4-ms numpy transform); the un-preprocessing rides in the last layer's epilogue.  Any other dtype is
-        transformed by ``preprocess.par_transform`` first."""
-        from . import _native as nat
+    def _stack_rows(self, model, params, host_fallback):
+        """(stack, flags, rows) for evaluating ``model`` on raw parameters with both transforms inside the library (include/
+        v21.h: v21_affine_in; the un-preprocessing rides in the last layer's epilogue): float32 and float64 rows are handed
+        over RAW and take the reference's branch for their dtype there, integer rows as float64 (documented deviation: the
+        reference truncates the fx floor in integer arrays).  What the library's input transform does not take -- another
+        float dtype, more than 8 columns -- goes through ``preprocess.par_transform`` on the host with ``host_fallback``,
+        and is cast to float64 without."""
         x = np.asarray(params)
         if x.ndim == 1:
             x = x[None, :]
+        if not np.issubdtype(x.dtype, np.floating) or not host_fallback and x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)
         st = model._ensure_stack()
-        ss = pp.SignalStats.of(self.signal_train)
-        if getattr(st, "_out_stats", None) is not ss:  # a new record whenever the training set changed (even in place)
-            st.set_output_transform(ss.std, ss.mean)
-            st._out_stats = ss
-        flags = nat.FWD_OUT_TRANSFORM
-        if not np.issubdtype(x.dtype, np.floating):
-            x = x.astype(np.float64)  # (documented deviation: the reference truncates the fx floor in integer arrays)
-        if x.dtype in (np.float32, np.float64) and x.shape[-1] <= 8:
-            ps = pp.ParamStats.of(self.par_train)
-            if getattr(st, "_in_stats", None) is not ps:
-                st.set_input_transform(ps.log_mask, ps.zero_floor, ps.lo, ps.hi)
-                st._in_stats = ps
-            flags |= nat.FWD_IN_TRANSFORM
-        else:
-            x = pp.par_transform(x, self.par_train)
+        st.use_output_stats(pp.SignalStats.of(self.signal_train))  # a new record whenever the training set changed (even in place)
+        if host_fallback and not (x.dtype in (np.float32, np.float64) and x.shape[-1] <= 8):
+            return st, nat.FWD_OUT_TRANSFORM, pp.par_transform(x, self.par_train)
+        st.use_input_stats(pp.ParamStats.of(self.par_train))
+        return st, nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM, x
+
+    def _predict_stack(self, model, params, devices=None):
+        """par_transform -> device stack -> unpreproc, squeezing a single row (emulator.py:401-407 / :788-795).  Few rows are
+        transformed on the host while they are padded, many in float64 on the device, so a 65,536-row call is bound by the
+        118 MB of results over PCIe and not by a 4-ms numpy transform."""
+        _, flags, x = self._stack_rows(model, params, host_fallback=True)
         pred = model.predict(x, devices=devices, flags=flags)
         return pred[0, :] if pred.shape[0] == 1 else pred
 
     def _diff_stack(self, params):
-        """(stack, flags, rows) of the model ``predict`` evaluates, with both transforms set, for the derivatives below:
-        float32 / float64 rows are handed over raw (the library differentiates par_transform for their dtype), any
-        other dtype is cast to float64 first."""
-        from . import _native as nat
+        """(model, stack, flags, rows) of the model ``predict`` evaluates, with both transforms set, for the derivatives
+        below (the library differentiates par_transform for the rows' dtype)."""
         model = self._predict_chain() if hasattr(self, "_predict_chain") else self.emulator
-        x = np.asarray(params)
-        if x.ndim == 1:
-            x = x[None, :]
-        if x.dtype not in (np.float32, np.float64):
-            x = x.astype(np.float64)
-        st = model._ensure_stack()
-        ss = pp.SignalStats.of(self.signal_train)
-        if getattr(st, "_out_stats", None) is not ss:
-            st.set_output_transform(ss.std, ss.mean)
-            st._out_stats = ss
-        ps = pp.ParamStats.of(self.par_train)
-        if getattr(st, "_in_stats", None) is not ps:
-            st.set_input_transform(ps.log_mask, ps.zero_floor, ps.lo, ps.hi)
-            st._in_stats = ps
-        return model, st, nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM, x
+        return (model,) + self._stack_rows(model, params, host_fallback=False)
 
     def jacobian(self, params, return_signal=False):
         """d signal / d params in mK per raw parameter unit (not in the reference: there, tf.GradientTape around
@@ -257,7 +247,7 @@ class _EmulatorBase:
         nb = st.dims[-1]
         d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
         w = self._band_weights(nb, sigma, flow, fhigh)
-        self._set_record(st, d, w)
+        st.use_likelihood(d, w)
         out = st.loglike(x, model.precision, flags, grad=grad)
         if grad:
             lnl, g = out
@@ -280,14 +270,6 @@ class _EmulatorBase:
             w = np.where(sel, w, np.float32(0))
         return w
 
-    @staticmethod
-    def _set_record(st, d, w):
-        """the stack's likelihood record (data d, weights w), uploaded only when it changed (``st._lk_record``)"""
-        rec = getattr(st, "_lk_record", None)
-        if rec is None or not (np.array_equal(rec[0], d) and np.array_equal(rec[1], w)):
-            st.set_likelihood(d, w)
-            st._lk_record = (d.copy(), w.copy())
-
     def fisher(self, params, sigma, flow=None, fhigh=None):
         """Fisher matrix F = J^T diag(1 / sigma^2) J of the signal at ``params`` in raw parameter units (not in the
         reference), over the bins of the band [flow, fhigh] as ``log_likelihood`` selects them; computed and reduced on
@@ -295,9 +277,8 @@ class _EmulatorBase:
         model, st, flags, x = self._diff_stack(params)
         nb = st.dims[-1]
         w = self._band_weights(nb, sigma, flow, fhigh)
-        rec = getattr(st, "_lk_record", None)
-        d = rec[0] if rec is not None else np.zeros(nb, np.float32)  # (the data are not read: keep the record's)
-        self._set_record(st, d, w)
+        d = st.lk_record[0] if st.lk_record is not None else np.zeros(nb, np.float32)  # (the data are not read: keep the record's)
+        st.use_likelihood(d, w)
         F = st.fisher(x, model.precision, flags)
         return F[0] if x.shape[0] == 1 else F
 
@@ -332,7 +313,7 @@ class _EmulatorBase:
                 raise ValueError("p0 must be (%d,) or (S, %d), got %r" % (din, din, np.shape(p0)))
         M, S = dat.shape[0], starts.shape[0]
         w = self._band_weights(nb, sigma, flow, fhigh)
-        self._set_record(st, dat[0], w)
+        st.use_likelihood(dat[0], w)
         x0 = np.ascontiguousarray(np.tile(starts, (M, 1)))
         r = st.fit(x0, model.precision, flags, data=dat, max_iter=max_iter, fisher=return_fisher)
         xh = r["x_hat"].reshape(M, S, din)
@@ -381,10 +362,7 @@ class DirectEmulator(_EmulatorBase):
         X_val = pp.par_transform(self.par_val, self.par_train)
         y_train = pp.preproc(self.signal_train, self.signal_train)
         y_val = pp.preproc(self.signal_val, self.signal_train)
-        callbacks = list(callbacks)  # (the reference appends to its default-argument list)
-        if verbose == "tqdm":
-            callbacks.append(TqdmCallback())
-            verbose = 0
+        verbose, callbacks = _with_tqdm(verbose, callbacks)
         hist = self.emulator.fit(x=X_train, y=y_train, batch_size=batch_size, epochs=epochs,
                                  validation_data=(X_val, y_val), validation_batch_size=batch_size,
                                  callbacks=callbacks, verbose=verbose)
@@ -483,11 +461,7 @@ class AutoEncoderEmulator(_EmulatorBase):
             return self._train_joint(epochs, ae_callbacks, em_callbacks, verbose, batch_size)
         y_train = pp.preproc(self.signal_train, self.signal_train)
         y_val = pp.preproc(self.signal_val, self.signal_train)
-        ae_callbacks, em_callbacks = list(ae_callbacks), list(em_callbacks)
-        if verbose == "tqdm":
-            ae_callbacks.append(TqdmCallback())
-            em_callbacks.append(TqdmCallback())
-            verbose = 0
+        verbose, ae_callbacks, em_callbacks = _with_tqdm(verbose, ae_callbacks, em_callbacks)
         hist = self.autoencoder.fit(x=y_train, y=y_train, batch_size=batch_size, epochs=epochs,
                                     validation_data=(y_val, y_val), callbacks=ae_callbacks, verbose=verbose)
         ae_loss, ae_val_loss = hist.history["loss"], hist.history["val_loss"]
@@ -512,11 +486,9 @@ class AutoEncoderEmulator(_EmulatorBase):
         2,048 rows).  A variational autoencoder (``AutoEncoder(variational=True)``) is fine: the emulator learns
         z_mean, what ``encoder.predict`` returns.
         With a data-parallel communicator on the context every rank trains on its share of every batch."""
-        from . import _native as nat, callbacks as cb_mod, engine
         ae, em = self.autoencoder, self.emulator
         for m in (ae, em):
-            if m.optimizer is None or m.loss is None:
-                raise RuntimeError("You must compile your model before training: model.compile(optimizer=, loss=)")
+            engine._check_compiled(m)
         lat = em.layers[-1].units
         if not np.array_equal(em._row_weight(np.zeros((2, lat), np.float32)), em._row_weight(np.ones((2, lat), np.float32))):
             raise ValueError("joint training needs a target-independent emulator loss (mean_squared_error)")
@@ -525,11 +497,7 @@ class AutoEncoderEmulator(_EmulatorBase):
         X_train = np.ascontiguousarray(pp.par_transform(self.par_train, self.par_train), dtype=np.float32)
         X_val = np.ascontiguousarray(pp.par_transform(self.par_val, self.par_train), dtype=np.float32)
         n = y_train.shape[0]
-        ae_callbacks, em_callbacks = list(ae_callbacks), list(em_callbacks)
-        if verbose == "tqdm":
-            ae_callbacks.append(TqdmCallback())
-            em_callbacks.append(TqdmCallback())
-            verbose = 0
+        verbose, ae_callbacks, em_callbacks = _with_tqdm(verbose, ae_callbacks, em_callbacks)
         tra, tre = ae._ensure_trainer(batch_size), em._ensure_trainer(batch_size)
         tra.set_data(0, y_train, None, ae._row_weight(y_train))
         tra.set_data(1, y_val, None, ae._row_weight(y_val))
@@ -538,39 +506,27 @@ class AutoEncoderEmulator(_EmulatorBase):
         zdv = np.zeros((X_val.shape[0], lat), np.float32)
         tre.set_data(1, X_val, zdv, em._row_weight(zdv))  # (targets: the encoder's latents of y_val, formed on the device)
         joint = nat.Joint(tra, tre, latent_layer=len(ae.encoder.layers) - 1)
-        dp = tra.ctx.nranks > 1
-        if dp:  # data parallel: the replicas must start equal and shuffle alike (as engine.Model.fit does)
-            from . import parallel
-
-            def bcast(a):
-                return parallel.broadcast_array(a, device=tra.ctx.device)
-            for m, tr in ((ae, tra), (em, tre)):
-                m._stack.set_weights(bcast(m._stack.get_weights()))
-                it, mm, vv = tr.get_state()
-                tr.set_state(int(bcast(np.array([it], np.int64))[0]), bcast(mm), bcast(vv))
-            if getattr(ae, "_vae_seed", None) is not None:
-                ae._vae_seed = int(bcast(np.array([ae._vae_seed], np.uint64))[0])
+        bcast = None
+        if tra.ctx.nranks > 1:  # data parallel: the replicas must start equal and shuffle alike (as engine.Model.fit does)
+            bcast = engine._broadcast_start(ae, tra)
+            engine._broadcast_start(em, tre)
+            if ae._vae_seed is not None:  # (this loop does not refresh the variational settings per epoch)
                 tra.set_vae(ae.kl_weight, ae.sample_latent, ae._vae_seed)
-        hists = [cb_mod.History(), cb_mod.History()]
-        params = {"epochs": epochs, "steps": -(-n // batch_size), "verbose": verbose}
-        cbs = [cb_mod.CallbackList([hists[0]] + ae_callbacks, ae, params), cb_mod.CallbackList([hists[1]] + em_callbacks, em, params)]
-        for m in (ae, em):
-            m.stop_training = False
-            m._dirty_host = True
-        for c in cbs:
-            c.on_train_begin()
+        run_a = engine._Run(ae, tra, ae_callbacks, epochs, n, batch_size, verbose)
+        run_e = engine._Run(em, tre, em_callbacks, epochs, n, batch_size, verbose)
+        engine._Run.begin([run_a, run_e])
         ae_running = em_running = True
         for epoch in range(epochs):
             if not em_running and not ae_running:
                 break
             if ae_running:
-                cbs[0].on_epoch_begin(epoch)
+                run_a.cbs.on_epoch_begin(epoch)
             if em_running:
-                cbs[1].on_epoch_begin(epoch)
+                run_e.cbs.on_epoch_begin(epoch)
             tra.set_lr(float(ae.optimizer.lr) if ae_running else 0.0)
             tre.set_lr(float(em.optimizer.lr))
             perm = engine._rng.permutation(n).astype(np.int32)
-            if dp:
+            if bcast is not None:
                 perm = bcast(perm)
             if em_running:
                 la, le = joint.run_epoch(perm, batch_size)
@@ -581,24 +537,18 @@ class AutoEncoderEmulator(_EmulatorBase):
             # validation signals (the reference's encoder.predict(signal_val), emulator.py:754, without leaving the device)
             va, ve = joint.evaluate() if em_running else (tra.evaluate(1, batch_size), None)
             if ae_running:
-                logs = {"loss": la, "val_loss": va}
-                cbs[0].on_epoch_end(epoch, logs)
-                if ae.stop_training:
-                    ae_running = False  # frozen from here on: the reference's phase 2
+                run_a.cbs.on_epoch_end(epoch, {"loss": la, "val_loss": va})
+                ae_running = not ae.stop_training  # once stopped, frozen from here on: the reference's phase 2
             if em_running:
-                logs = {"loss": le, "val_loss": ve}
-                cbs[1].on_epoch_end(epoch, logs)
-                if em.stop_training:
-                    em_running = False
+                run_e.cbs.on_epoch_end(epoch, {"loss": le, "val_loss": ve})
+                em_running = not em.stop_training
             if verbose in (1, 2):
                 print("Epoch %d/%d - ae loss %.4e - emulator loss %s" % (epoch + 1, epochs, la, "%.4e" % le if le is not None else "-"))
-        for c in cbs:
-            c.on_train_end()
-        ae.optimizer.iterations = tra.get_state()[0]
-        em.optimizer.iterations = tre.get_state()[0]
-        ae._sync_host(); em._sync_host()
+        run_a.finish()
+        run_e.finish()
         self._chain_model = None
-        return hists[0].history["loss"], hists[0].history["val_loss"], hists[1].history["loss"], hists[1].history["val_loss"]
+        ha, he = run_a.history.history, run_e.history.history
+        return ha["loss"], ha["val_loss"], he["loss"], he["val_loss"]
 
     def _predict_chain(self):
         blocks = [self.emulator, self.autoencoder.decoder]

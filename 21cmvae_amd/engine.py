@@ -97,6 +97,122 @@ class Input:
         self.dim = int(shape[-1] if isinstance(shape, (tuple, list)) else shape)
 
 
+# ---- the parts the epoch loops share: Model.fit, sweep.fit_models, emulator.AutoEncoderEmulator._train_joint ----------
+def _check_compiled(model):
+    if model.optimizer is None or model.loss is None:
+        raise RuntimeError("You must compile your model before training: model.compile(optimizer=, loss=)")
+
+
+def _f32_pair(x, y, alias_ok=False):
+    """(inputs, targets) of a fit -> (x, y, upload): float32 x and y, and what the trainer is given as targets -- None when
+    y repeats x (an autoencoder: the device then reads its targets from the inputs), else y.  alias_ok: `y is x` settles that
+    without a comparison (training data; validation data are always compared)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    same = y.shape == x.shape and (alias_ok and y is x or np.array_equal(x, y))
+    return x, y, None if same else y
+
+
+def _broadcast_start(model, tr):
+    """Data parallel (parallel.init_engine_comm on the trainer's context): every rank holds the whole training set and
+    trains on its share of each global batch, so the replicas must START equal and SHUFFLE alike -- rank 0's weights,
+    optimizer state and noise seed are broadcast over the process group here; the caller sends each epoch's permutation
+    through the function this returns."""
+    from . import parallel
+
+    def bcast(a):  # (the context's GPU, not torch's per-thread current device)
+        return parallel.broadcast_array(a, device=tr.ctx.device)
+
+    model._stack.set_weights(bcast(model._stack.get_weights()))
+    it, mm, vv = tr.get_state()
+    tr.set_state(int(bcast(np.array([it], np.int64))[0]), bcast(mm), bcast(vv))
+    if model._vae_seed is not None:
+        model._vae_seed = int(bcast(np.array([model._vae_seed], np.uint64))[0])
+    return bcast
+
+
+class _Run:
+    """One model's side of an epoch loop: its trainer, its History and its callbacks, with Keras' bookkeeping."""
+
+    def __init__(self, model, trainer, callbacks, epochs, n, batch_size, verbose):
+        self.model, self.trainer, self.verbose = model, trainer, verbose
+        self.history = cb_mod.History()
+        self.cbs = cb_mod.CallbackList([self.history] + list(callbacks or []), model,
+                                       {"epochs": epochs, "steps": -(-n // batch_size), "verbose": verbose})
+
+    @staticmethod
+    def begin(runs):
+        for r in runs:
+            r.model.stop_training = False
+            r.model._dirty_host = True
+        for r in runs:
+            r.cbs.on_train_begin()
+
+    def epoch_begin(self, epoch):
+        m = self.model
+        self.cbs.on_epoch_begin(epoch)
+        self.trainer.set_lr(float(m.optimizer.lr))
+        if m._vae_seed is not None:  # a callback may anneal kl_weight between epochs
+            self.trainer.set_vae(m.kl_weight, m.sample_latent, m._vae_seed)
+
+    def epoch_end(self, epoch, loss, val_batch, head):
+        """The epoch's logs (validation pass with batches of val_batch; None: no validation data), print, callbacks.
+        -> False when the model has been told to stop."""
+        logs = {"loss": loss}
+        self.model._dirty_host = True
+        if val_batch is not None:
+            logs["val_loss"] = self.trainer.evaluate(1, min(val_batch, self.trainer.max_batch))
+        if self.verbose in (1, 2):
+            print(head + " - ".join("%s: %.4e" % kv for kv in logs.items()))
+        self.cbs.on_epoch_end(epoch, logs)
+        return not self.model.stop_training
+
+    def finish(self):
+        self.cbs.on_train_end()
+        self.model.optimizer.iterations = self.trainer.get_state()[0]
+        self.model._sync_host()
+
+
+class _LookAheadShuffle:
+    """fit()'s epoch permutations.  The next epoch's permutation is drawn while this epoch runs on the GPU (run_epoch blocks
+    inside the library with the GIL released; drawing 24,562 indices takes ~0.25 ms, 4 % of an f32 epoch of the reference
+    recipe during which the GPU sat idle) -- by a PRIVATE generator started from a snapshot of the shared one, which is not
+    touched.  The shared generator advances only when that permutation is consumed, and it is consumed only if nothing (a
+    callback, a nested fit(), set_random_seed) has touched the shared generator in between; otherwise the look-ahead is
+    dropped and the permutation is drawn the ordinary way.  Either way the stream of random numbers is what it would be
+    without the look-ahead (an unused look-ahead never touched the shared generator: nothing to undo)."""
+
+    def __init__(self, n, shuffle):
+        self.n = n
+        self.pool = ThreadPoolExecutor(1) if shuffle else None
+        self.ahead = None  # (future -> (perm, generator state after the draw), the shared generator, its state at the snapshot)
+
+    def _draw(self, state):
+        g = np.random.Generator(type(_rng.bit_generator)())
+        g.bit_generator.state = state
+        return g.permutation(self.n).astype(np.int32), g.bit_generator.state
+
+    def next(self):
+        """this epoch's permutation (None: no shuffling)"""
+        if self.pool is None:
+            return None
+        ahead, self.ahead = self.ahead, None
+        if ahead is not None and ahead[1] is _rng and _rng.bit_generator.state == ahead[2]:
+            perm, after = ahead[0].result()
+            _rng.bit_generator.state = after
+            return perm
+        return _rng.permutation(self.n).astype(np.int32)
+
+    def look_ahead(self):
+        if self.pool is not None:
+            snap = _rng.bit_generator.state
+            self.ahead = (self.pool.submit(self._draw, snap), _rng, snap)
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+
+
 class Model:
     """Base class: a chain of Dense layers evaluated and trained on the device.
 
@@ -117,6 +233,10 @@ class Model:
         # variational mode (stacks holding a GaussianLatent layer): loss_i = recon_i + kl_weight * KL_i
         self.kl_weight = 0.0
         self.sample_latent = True
+        self._vae_seed = None       # of the training noise; drawn when the first trainer of such a stack is made
+        self._row_weight = None     # compile(): targets -> per-row loss weights
+        self._restore_state = None  # (m, v) Adam moments of a loaded file (h5lite.load_model), for the next trainer
+        self._replicas = {}         # predict(devices=): (slot, ordinal) -> (signature, Stack)
 
     # -- structure ---------------------------------------------------------------
     def _chain(self):
@@ -232,6 +352,14 @@ class Model:
             self._stack = None
 
     # -- inference -----------------------------------------------------------------
+    def _rows_and_stack(self, x):
+        x = np.asarray(x)
+        if x.ndim == 1:
+            x = x[None, :]
+        if not self.built:
+            self.build((None, x.shape[-1]))
+        return x, self._ensure_stack()
+
     def predict(self, x, batch_size=None, verbose=0, precision=None, devices=None, flags=0, **_):
         """numpy (n, in) -> numpy float32 (n, out).  float64 input is cast to float32 on
         the way in, as Keras does [K]; rows are independent, so ``batch_size`` is
@@ -239,23 +367,17 @@ class Model:
         -- the rows are cut into contiguous blocks, one per entry, evaluated concurrently on
         replicas of the stack (weights copied once per change) and put back in order; no
         collective is involved."""
-        x = np.asarray(x)
-        if x.ndim == 1:
-            x = x[None, :]
-        if not self.built:
-            self.build((None, x.shape[-1]))
-        st = self._ensure_stack()
+        x, st = self._rows_and_stack(x)
         if not devices or len(devices) == 1 and int(devices[0]) == st.ctx.device:
             return st.forward(x, precision or self.precision, flags=flags)
         return self._predict_on_devices(st, x, precision or self.precision, [int(d) for d in devices], flags)
 
     def _predict_on_devices(self, st, x, precision, devices, flags):
-        from concurrent.futures import ThreadPoolExecutor
-        reps = self.__dict__.setdefault("_replicas", {})
+        reps = self._replicas
         # trained weights newer than the host copies: pulled back ONCE (that bumps the layer versions, hence the
         # signature below), so the replicas are refreshed once per change and not on every call after a fit()
         self._sync_host()
-        sig = (id(st), self._stack_sig, id(getattr(st, "_out_stats", None)), id(getattr(st, "_in_stats", None)))
+        sig = (id(st), self._stack_sig, id(st.out_stats), id(st.in_stats))
         flat = None
         stacks = []
         for slot, d in enumerate(devices):  # one replica per LIST ENTRY (an ordinal may appear twice)
@@ -267,11 +389,10 @@ class Model:
                 same = ent is not None and ent[1].dims == st.dims and ent[1].act == st.act
                 rs = ent[1] if same else _native.Stack(_native.Context(d), st.dims, st.act)
                 rs.set_weights(flat)
-                if getattr(st, "_out_stats", None) is not None:
-                    rs.set_output_transform(st._out_stats.std, st._out_stats.mean)
-                if getattr(st, "_in_stats", None) is not None:
-                    ps = st._in_stats
-                    rs.set_input_transform(ps.log_mask, ps.zero_floor, ps.lo, ps.hi)
+                if st.out_stats is not None:
+                    rs.use_output_stats(st.out_stats)
+                if st.in_stats is not None:
+                    rs.use_input_stats(st.in_stats)
                 reps[key] = ent = (sig, rs)
             stacks.append(ent[1])
         n = x.shape[0]
@@ -289,12 +410,7 @@ class Model:
         reference, whose Keras model is differentiated with tf.GradientTape).  The result is a transposed VIEW of the
         library's (n, in, out) buffer (include/v21.h: v21_mlp_jacobian); ``np.ascontiguousarray`` it where the layout
         matters.  A ReLU at exactly zero has derivative 0, as the forward's mask (z > 0) implies."""
-        x = np.asarray(x)
-        if x.ndim == 1:
-            x = x[None, :]
-        if not self.built:
-            self.build((None, x.shape[-1]))
-        st = self._ensure_stack()
+        x, st = self._rows_and_stack(x)
         return st.jacobian(x, precision or self.precision).transpose(0, 2, 1)
 
     # -- training ------------------------------------------------------------------
@@ -317,7 +433,7 @@ class Model:
             carried = old.get_state() if old is not None else None
             self._trainer = _native.Trainer(stack, self.precision, max(batch, 1))
             self._trainer_sig = sig
-            mv = getattr(self, "_restore_state", None)  # Adam moments of a loaded file (h5lite.load_model)
+            mv = self._restore_state
             if carried is not None:
                 self._trainer.set_state(*carried)
             elif mv is not None and mv[0] is not None and mv[0].size == stack.num_params:
@@ -328,7 +444,7 @@ class Model:
         o = self.optimizer
         self._trainer.set_adam(float(o.lr), o.beta_1, o.beta_2, o.epsilon)
         if any(isinstance(l, GaussianLatent) for l in self._dense_layers()):
-            if getattr(self, "_vae_seed", None) is None:
+            if self._vae_seed is None:
                 self._vae_seed = int(_rng.integers(0, 2**63))
             self._trainer.set_vae(self.kl_weight, self.sample_latent, self._vae_seed)
         return self._trainer
@@ -338,97 +454,38 @@ class Model:
         """Keras fit(): per epoch a fresh shuffle, batches of ``batch_size`` with the partial
         last batch kept, epoch loss = sample-weighted mean of batch losses, validation
         pass, ``callbacks.on_epoch_end(epoch, logs)``, ``stop_training`` honoured."""
-        if self.optimizer is None or self.loss is None:
-            raise RuntimeError("You must compile your model before training: model.compile(optimizer=, loss=)")
+        _check_compiled(self)
         batch_size = 32 if batch_size is None else int(batch_size)
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        y = np.ascontiguousarray(y, dtype=np.float32)
+        x, y, targets = _f32_pair(x, y, alias_ok=True)
         if not self.built:
             self.build((None, x.shape[-1]))
         n = x.shape[0]
         tr = self._ensure_trainer(batch_size)
-        same = y.shape == x.shape and (y is x or np.array_equal(x, y))
-        tr.set_data(0, x, None if same else y, self._row_weight(y))
-        vb = int(validation_batch_size or batch_size)
+        tr.set_data(0, x, targets, self._row_weight(y))
+        vb = None
         if validation_data is not None:
-            xv = np.ascontiguousarray(validation_data[0], dtype=np.float32)
-            yv = np.ascontiguousarray(validation_data[1], dtype=np.float32)
-            same_v = yv.shape == xv.shape and np.array_equal(xv, yv)
-            tr.set_data(1, xv, None if same_v else yv, self._row_weight(yv))
-        dp = tr.ctx.nranks > 1
-        if dp:
-            # Data parallel (parallel.init_engine_comm on this context): every rank holds the whole training set and
-            # trains on its share of each global batch, so the replicas must START equal and SHUFFLE alike --
-            # rank 0's weights, optimizer state and, per epoch, permutation are broadcast over the process group.
-            from . import parallel
-
-            def bcast(a):  # (the context's GPU, not torch's per-thread current device)
-                return parallel.broadcast_array(a, device=tr.ctx.device)
-
-            self._stack.set_weights(bcast(self._stack.get_weights()))
-            it, mm, vv = tr.get_state()
-            tr.set_state(int(bcast(np.array([it], np.int64))[0]), bcast(mm), bcast(vv))
-            if getattr(self, "_vae_seed", None) is not None:
-                self._vae_seed = int(bcast(np.array([self._vae_seed], np.uint64))[0])
-        history = cb_mod.History()
-        cbs = cb_mod.CallbackList([history] + list(callbacks or []), self,
-                                  {"epochs": epochs, "steps": -(-n // batch_size), "verbose": verbose})
-        self.stop_training = False
-        self._dirty_host = True
-        cbs.on_train_begin()
-
-        def draw():
-            return _rng.permutation(n).astype(np.int32)
-
-        def draw_ahead(state):
-            # a PRIVATE generator started from a snapshot of the shared one: the shared stream is not touched here
-            g = np.random.Generator(type(_rng.bit_generator)())
-            g.bit_generator.state = state
-            return g.permutation(n).astype(np.int32), g.bit_generator.state
-
-        # The next epoch's permutation is drawn while this epoch runs on the GPU (run_epoch blocks inside the library with
-        # the GIL released; drawing 24,562 indices takes ~0.25 ms, 4 % of an f32 epoch of the reference recipe during
-        # which the GPU sat idle) -- from a COPY of the shared generator.  The shared generator advances only when that
-        # permutation is consumed, and it is consumed only if nothing (a callback, a nested fit(), set_random_seed)
-        # has touched the shared generator in between; otherwise the look-ahead is dropped and the permutation is drawn
-        # the ordinary way.  Either way the stream of random numbers is what it would be without the look-ahead.
-        pool = ThreadPoolExecutor(1) if shuffle else None
-        ahead = None  # (future -> (perm, generator state after the draw), the shared generator, its state at the snapshot)
+            vb = int(validation_batch_size or batch_size)
+            xv, yv, targets_v = _f32_pair(validation_data[0], validation_data[1])
+            tr.set_data(1, xv, targets_v, self._row_weight(yv))
+        bcast = _broadcast_start(self, tr) if tr.ctx.nranks > 1 else None
+        run = _Run(self, tr, callbacks, epochs, n, batch_size, verbose)
+        _Run.begin([run])
+        shuffler = _LookAheadShuffle(n, shuffle)
         try:
             for epoch in range(initial_epoch, epochs):
-                cbs.on_epoch_begin(epoch)
-                tr.set_lr(float(self.optimizer.lr))
-                if getattr(self, "_vae_seed", None) is not None:  # a callback may anneal kl_weight between epochs
-                    tr.set_vae(self.kl_weight, self.sample_latent, self._vae_seed)
-                perm = None
-                if shuffle:
-                    if ahead is not None and ahead[1] is _rng and _rng.bit_generator.state == ahead[2]:
-                        perm, after = ahead[0].result()
-                        _rng.bit_generator.state = after
-                    else:
-                        perm = draw()
-                    ahead = None
-                if dp and perm is not None:
+                run.epoch_begin(epoch)
+                perm = shuffler.next()
+                if bcast is not None and perm is not None:
                     perm = bcast(perm)
-                if shuffle and epoch + 1 < epochs:
-                    snap = _rng.bit_generator.state
-                    ahead = (pool.submit(draw_ahead, snap), _rng, snap)
-                logs = {"loss": tr.run_epoch(perm, batch_size)}
-                self._dirty_host = True
-                if validation_data is not None:
-                    logs["val_loss"] = tr.evaluate(1, min(vb, tr.max_batch))
-                if verbose in (1, 2):
-                    print("Epoch %d/%d - " % (epoch + 1, epochs) + " - ".join("%s: %.4e" % kv for kv in logs.items()))
-                cbs.on_epoch_end(epoch, logs)
-                if self.stop_training:
+                if epoch + 1 < epochs:
+                    shuffler.look_ahead()
+                loss = tr.run_epoch(perm, batch_size)
+                if not run.epoch_end(epoch, loss, vb, "Epoch %d/%d - " % (epoch + 1, epochs)):
                     break
         finally:
-            if pool is not None:
-                pool.shutdown(wait=True)  # (an unused look-ahead never touched the shared generator: nothing to undo)
-        cbs.on_train_end()
-        self.optimizer.iterations = tr.get_state()[0]
-        self._sync_host()
-        return history
+            shuffler.close()
+        run.finish()
+        return run.history
 
     def evaluate(self, x, y, batch_size=None, verbose=0, **_):
         """Mean per-sample loss over (x, y).  The batch size does not change the result (rows are

@@ -176,7 +176,7 @@ def test_fit_recovers_truths_on_trained_weights(shipped):
     for k in range(4):
         xh = res.params[k, best[k]]
         u = pp.par_transform(xh, ae.par_train)[0]
-        ae._set_record(st, spectra[k], np.ones(451, np.float32))
+        st.use_likelihood(spectra[k], np.ones(451, np.float32))
         _, g = st.loglike(u[None, :].astype(np.float32), "f32", nat.FWD_OUT_TRANSFORM)
         F = st.fisher(u[None, :].astype(np.float32), "f32", nat.FWD_OUT_TRANSFORM)[0]
         g, scale = g[0].astype(np.float64), np.sqrt(np.maximum(np.diag(F), 1e-30))

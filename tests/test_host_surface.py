@@ -259,3 +259,312 @@ def test_native_handles_are_destroyed_children_first_whatever_order_python_final
     assert order == ["t1"]
     t2.__del__()
     assert order == ["t1", "t2", "stack"]
+
+
+# ---- the three epoch loops (engine.Model.fit, sweep.fit_models, AutoEncoderEmulator._train_joint) call for call ----------
+# No GPU: trainers, _native.Sweep and _native.Joint are stand-ins that write every call onto ONE tape, in order, and so do
+# the callbacks.  The expected tapes below are written out by hand; the only computed entries are the permutations, drawn
+# from a reference generator of the same seed (one draw at the head of every shuffled epoch).
+class _TapeTrainer:
+    """Stands in for _native.Trainer: epoch k (from 0) returns loss base + k + 1, every validation pass base + 0.5."""
+    max_batch = 1 << 20
+
+    class ctx:
+        nranks, rank, device = 1, 0, 0
+
+    def __init__(self, tape, name, base=0.0):
+        self.tape, self.name, self.base, self.epochs = tape, name, base, 0
+
+    def next_loss(self):
+        self.epochs += 1
+        return self.base + self.epochs
+
+    def set_data(self, which, x, y, rw):
+        assert x.dtype == np.float32 and (y is None or y.dtype == np.float32) and len(rw) == len(x)
+        self.tape.append((self.name, "set_data", which, x.shape, None if y is None else y.shape))
+
+    def set_lr(self, lr): self.tape.append((self.name, "set_lr", lr))
+    def set_vae(self, kl, sample, seed): self.tape.append((self.name, "set_vae", kl, sample, seed))
+    def set_state(self, it, m=None, v=None): self.tape.append((self.name, "set_state", it))
+    def get_state(self): return 100 + self.epochs, None, None
+
+    def run_epoch(self, perm, batch):
+        self.tape.append((self.name, "run_epoch", None if perm is None else tuple(int(i) for i in perm), batch))
+        return self.next_loss()
+
+    def evaluate(self, which, batch):
+        self.tape.append((self.name, "evaluate", which, batch))
+        return self.base + 0.5
+
+
+class _TapeCallback:
+    """Writes every event with a copy of its logs; stop_after: the epoch after which it stops its model; kl: {epoch: the
+    kl_weight it sets at that epoch's end} (an annealing schedule)."""
+
+    def __init__(self, tape, name, stop_after=None, kl=None):
+        self.tape, self.name, self.stop_after, self.kl = tape, name, stop_after, kl or {}
+
+    def set_model(self, m): self.model = m
+    def on_train_begin(self, logs=None): self.tape.append((self.name, "train_begin"))
+    def on_train_end(self, logs=None): self.tape.append((self.name, "train_end"))
+    def on_epoch_begin(self, epoch, logs=None): self.tape.append((self.name, "epoch_begin", epoch))
+
+    def on_epoch_end(self, epoch, logs=None):
+        self.tape.append((self.name, "epoch_end", epoch, dict(logs)))
+        if epoch == self.stop_after:
+            self.model.stop_training = True
+        if epoch in self.kl:
+            self.model.kl_weight = self.kl[epoch]
+
+
+def _perms(seed, n, count):
+    ref = np.random.default_rng(seed)
+    return [tuple(int(i) for i in ref.permutation(n).astype(np.int32)) for _ in range(count)], ref
+
+
+def _taped_model(eng, monkeypatch, tape, name, layers, lr, base=0.0, loss="mse"):
+    m = eng.Sequential(layers)
+    m.compile(optimizer=pkg("optimizers").Adam(lr), loss=loss)
+    tr = _TapeTrainer(tape, name, base)
+    monkeypatch.setattr(m, "_ensure_trainer", lambda b: tr)
+    return m, tr
+
+
+def test_fit_epoch_loop_call_for_call(monkeypatch):
+    eng = pkg("engine")
+    x = np.arange(18, dtype=np.float64).reshape(6, 3); y = np.ones((6, 2)); xv = np.zeros((4, 3)); yv = np.ones((4, 2))
+
+    # (a) validation data, shuffled, every epoch run; float64 arrays arrive as float32
+    tape = []
+    m, tr = _taped_model(eng, monkeypatch, tape, "t", [eng.Input((3,)), eng.Dense(4, "relu"), eng.Dense(2)], 0.5)
+    eng.set_random_seed(11)
+    P, ref = _perms(11, 6, 2)
+    h = m.fit(x, y, batch_size=4, epochs=2, validation_data=(xv, yv), callbacks=[_TapeCallback(tape, "cb")])
+    assert tape == [
+        ("t", "set_data", 0, (6, 3), (6, 2)), ("t", "set_data", 1, (4, 3), (4, 2)),
+        ("cb", "train_begin"),
+        ("cb", "epoch_begin", 0), ("t", "set_lr", 0.5), ("t", "run_epoch", P[0], 4), ("t", "evaluate", 1, 4),
+        ("cb", "epoch_end", 0, {"loss": 1.0, "val_loss": 0.5}),
+        ("cb", "epoch_begin", 1), ("t", "set_lr", 0.5), ("t", "run_epoch", P[1], 4), ("t", "evaluate", 1, 4),
+        ("cb", "epoch_end", 1, {"loss": 2.0, "val_loss": 0.5}),
+        ("cb", "train_end")]
+    assert h.history == {"loss": [1.0, 2.0], "val_loss": [0.5, 0.5]} and h.epoch == [0, 1]
+    assert m.optimizer.iterations == 102 and m.stop_training is False
+    assert eng._rng.bit_generator.state == ref.bit_generator.state
+
+    # (b) no validation data, shuffle=False, early stopping, a larger validation batch size that nothing uses
+    tape.clear()
+    m, tr = _taped_model(eng, monkeypatch, tape, "t", [eng.Input((3,)), eng.Dense(2)], 0.25)
+    h = m.fit(x, y, batch_size=4, epochs=5, shuffle=False, validation_batch_size=64, callbacks=[_TapeCallback(tape, "cb", stop_after=1)])
+    assert tape == [
+        ("t", "set_data", 0, (6, 3), (6, 2)),
+        ("cb", "train_begin"),
+        ("cb", "epoch_begin", 0), ("t", "set_lr", 0.25), ("t", "run_epoch", None, 4), ("cb", "epoch_end", 0, {"loss": 1.0}),
+        ("cb", "epoch_begin", 1), ("t", "set_lr", 0.25), ("t", "run_epoch", None, 4), ("cb", "epoch_end", 1, {"loss": 2.0}),
+        ("cb", "train_end")]
+    assert h.history == {"loss": [1.0, 2.0]} and m.stop_training is True and m.optimizer.iterations == 102
+
+    # (c) targets that repeat the inputs are not uploaded: `y is x` settles that for the training data without a comparison
+    # (so even with a NaN inside), validation data are compared by value (a NaN never equals itself); validation_batch_size
+    # and initial_epoch are honoured
+    tape.clear()
+    s = np.arange(18, dtype=np.float32).reshape(6, 3); s[2, 1] = np.nan
+    sv = np.zeros((4, 3), np.float32); svn = sv.copy(); svn[0, 0] = np.nan
+    for val, val_targets in ((sv, None), (svn, (4, 3))):
+        tape.clear()
+        m, tr = _taped_model(eng, monkeypatch, tape, "t", [eng.Input((3,)), eng.Dense(3)], 0.5)
+        m.fit(s, s, batch_size=4, epochs=3, initial_epoch=2, shuffle=False, validation_data=(val, val), validation_batch_size=2)
+        assert tape == [
+            ("t", "set_data", 0, (6, 3), None), ("t", "set_data", 1, (4, 3), val_targets),
+            ("t", "set_lr", 0.5), ("t", "run_epoch", None, 4), ("t", "evaluate", 1, 2)]
+    tape.clear()
+    m, tr = _taped_model(eng, monkeypatch, tape, "t", [eng.Input((3,)), eng.Dense(3)], 0.5)
+    m.fit(s, s.copy(), batch_size=4, epochs=1, shuffle=False)   # equal shape, compared by value: the NaN makes them differ
+    assert tape[0] == ("t", "set_data", 0, (6, 3), (6, 3))
+
+    # (d) a stack with a GaussianLatent layer: the variational settings are refreshed at the head of every epoch, so a
+    # callback can anneal kl_weight
+    tape.clear()
+    m, tr = _taped_model(eng, monkeypatch, tape, "t", [eng.Input((3,)), eng.GaussianLatent(2), eng.Dense(3)], 0.5)
+    m._vae_seed, m.kl_weight = 77, 0.25
+    eng.set_random_seed(12)
+    P, ref = _perms(12, 6, 2)
+    m.fit(s, s, batch_size=6, epochs=2, callbacks=[_TapeCallback(tape, "cb", kl={0: 0.75})])
+    assert tape == [
+        ("t", "set_data", 0, (6, 3), None),
+        ("cb", "train_begin"),
+        ("cb", "epoch_begin", 0), ("t", "set_lr", 0.5), ("t", "set_vae", 0.25, True, 77), ("t", "run_epoch", P[0], 6),
+        ("cb", "epoch_end", 0, {"loss": 1.0}),
+        ("cb", "epoch_begin", 1), ("t", "set_lr", 0.5), ("t", "set_vae", 0.75, True, 77), ("t", "run_epoch", P[1], 6),
+        ("cb", "epoch_end", 1, {"loss": 2.0}),
+        ("cb", "train_end")]
+
+    # not compiled: refused before anything is touched
+    with pytest.raises(RuntimeError, match="compile your model"):
+        eng.Sequential([eng.Input((3,)), eng.Dense(2)]).fit(x, y)
+
+
+class _TapeSweep:
+    """Stands in for _native.Sweep"""
+
+    def __init__(self, trainers):
+        self.trainers = list(trainers)
+        self.tape = self.trainers[0].tape
+        self.tape.append(("sweep", "create", tuple(t.name for t in self.trainers)))
+
+    def run_epoch(self, perm, batch):
+        self.tape.append(("sweep", "run_epoch", tuple(t.name for t in self.trainers), None if perm is None else tuple(int(i) for i in perm), batch))
+        return [t.next_loss() for t in self.trainers]
+
+
+def test_sweep_epoch_loop_call_for_call(monkeypatch):
+    eng, sweep = pkg("engine"), pkg("sweep")
+    monkeypatch.setattr(pkg("_native"), "Sweep", _TapeSweep)
+    x = np.arange(18, dtype=np.float64).reshape(6, 3); y = np.ones((6, 3)); xv = np.zeros((4, 3)); yv = np.ones((4, 3))
+
+    def models(tape):
+        out = []
+        for k, mid in enumerate((eng.Dense(4, "relu"), eng.Dense(5, "relu"), eng.GaussianLatent(2))):
+            out.append(_taped_model(eng, monkeypatch, tape, "t%d" % k, [eng.Input((3,)), mid, eng.Dense(3)], 0.5 / (1 << k), base=10.0 * k)[0])
+        out[2]._vae_seed, out[2].kl_weight = 5, 0.125
+        return out
+
+    # (a) validation data, shuffled; model 0 -- the holder of the training set -- stops after the first epoch: the training
+    # set moves to model 1 and a new group is formed; model 2 is variational
+    tape = []
+    ms = models(tape)
+    eng.set_random_seed(21)
+    P, ref = _perms(21, 6, 3)
+    cbs = [[_TapeCallback(tape, "cb0", stop_after=0)], [_TapeCallback(tape, "cb1")], None]
+    hs = sweep.fit_models(ms, x, y, batch_size=4, epochs=3, validation_data=(xv, yv), callbacks=cbs, validation_batch_size=2)
+    assert tape == [
+        ("t0", "set_data", 1, (4, 3), (4, 3)), ("t1", "set_data", 1, (4, 3), (4, 3)), ("t2", "set_data", 1, (4, 3), (4, 3)),
+        ("cb0", "train_begin"), ("cb1", "train_begin"),
+        ("t0", "set_data", 0, (6, 3), (6, 3)), ("sweep", "create", ("t0", "t1", "t2")),
+        ("cb0", "epoch_begin", 0), ("t0", "set_lr", 0.5),
+        ("cb1", "epoch_begin", 0), ("t1", "set_lr", 0.25),
+        ("t2", "set_lr", 0.125), ("t2", "set_vae", 0.125, True, 5),
+        ("sweep", "run_epoch", ("t0", "t1", "t2"), P[0], 4),
+        ("t0", "evaluate", 1, 2), ("cb0", "epoch_end", 0, {"loss": 1.0, "val_loss": 0.5}),
+        ("t1", "evaluate", 1, 2), ("cb1", "epoch_end", 0, {"loss": 11.0, "val_loss": 10.5}),
+        ("t2", "evaluate", 1, 2),
+        ("t1", "set_data", 0, (6, 3), (6, 3)), ("sweep", "create", ("t1", "t2")),
+        ("cb1", "epoch_begin", 1), ("t1", "set_lr", 0.25),
+        ("t2", "set_lr", 0.125), ("t2", "set_vae", 0.125, True, 5),
+        ("sweep", "run_epoch", ("t1", "t2"), P[1], 4),
+        ("t1", "evaluate", 1, 2), ("cb1", "epoch_end", 1, {"loss": 12.0, "val_loss": 10.5}),
+        ("t2", "evaluate", 1, 2),
+        ("cb1", "epoch_begin", 2), ("t1", "set_lr", 0.25),
+        ("t2", "set_lr", 0.125), ("t2", "set_vae", 0.125, True, 5),
+        ("sweep", "run_epoch", ("t1", "t2"), P[2], 4),
+        ("t1", "evaluate", 1, 2), ("cb1", "epoch_end", 2, {"loss": 13.0, "val_loss": 10.5}),
+        ("t2", "evaluate", 1, 2),
+        ("cb0", "train_end"), ("cb1", "train_end")]
+    assert [h.history for h in hs] == [{"loss": [1.0], "val_loss": [0.5]}, {"loss": [11.0, 12.0, 13.0], "val_loss": [10.5] * 3},
+                                       {"loss": [21.0, 22.0, 23.0], "val_loss": [20.5] * 3}]
+    assert [m.optimizer.iterations for m in ms] == [101, 103, 103] and [m.stop_training for m in ms] == [True, False, False]
+    assert eng._rng.bit_generator.state == ref.bit_generator.state
+
+    # (b) no validation data, shuffle=False, autoencoder targets (y is x: not uploaded), a middle model stops
+    tape = []
+    ms = models(tape)
+    xs = np.arange(18, dtype=np.float32).reshape(6, 3)
+    hs = sweep.fit_models(ms, xs, xs, batch_size=6, epochs=2, shuffle=False, callbacks=[None, [_TapeCallback(tape, "cb1", stop_after=0)], None])
+    assert tape == [
+        ("cb1", "train_begin"),
+        ("t0", "set_data", 0, (6, 3), None), ("sweep", "create", ("t0", "t1", "t2")),
+        ("t0", "set_lr", 0.5), ("cb1", "epoch_begin", 0), ("t1", "set_lr", 0.25), ("t2", "set_lr", 0.125), ("t2", "set_vae", 0.125, True, 5),
+        ("sweep", "run_epoch", ("t0", "t1", "t2"), None, 6),
+        ("cb1", "epoch_end", 0, {"loss": 11.0}),
+        ("sweep", "create", ("t0", "t2")),
+        ("t0", "set_lr", 0.5), ("t2", "set_lr", 0.125), ("t2", "set_vae", 0.125, True, 5),
+        ("sweep", "run_epoch", ("t0", "t2"), None, 6),
+        ("cb1", "train_end")]
+    assert [h.history for h in hs] == [{"loss": [1.0, 2.0]}, {"loss": [11.0]}, {"loss": [21.0, 22.0]}]
+
+    m = eng.Sequential([eng.Input((3,)), eng.Dense(3)])
+    with pytest.raises(RuntimeError, match="compile your model"):
+        sweep.fit_models([ms[0], m], xs, xs)
+
+
+class _TapeJoint:
+    """Stands in for _native.Joint"""
+
+    def __init__(self, ae_trainer, em_trainer, latent_layer):
+        self.trainers, self.tape = (ae_trainer, em_trainer), ae_trainer.tape
+        self.tape.append(("joint", "create", ae_trainer.name, em_trainer.name, latent_layer))
+
+    def run_epoch(self, perm, batch):
+        self.tape.append(("joint", "run_epoch", tuple(int(i) for i in perm), batch))
+        return self.trainers[0].next_loss(), self.trainers[1].next_loss()
+
+    def evaluate(self):
+        self.tape.append(("joint", "evaluate"))
+        return self.trainers[0].base + 0.5, self.trainers[1].base + 0.5
+
+
+@pytest.mark.parametrize("variational", [False, True])
+def test_joint_epoch_loop_call_for_call(monkeypatch, variational):
+    eng, emu, optm, synth = pkg("engine"), pkg("emulator"), pkg("optimizers"), pkg("synth")
+    monkeypatch.setattr(pkg("_native"), "Joint", _TapeJoint)
+    data = synth.make_dataset(n_train=10, n_val=4, n_test=2, seed=6)
+
+    def emulator(tape):
+        e = emu.AutoEncoderEmulator(latent_dim=3, enc_hidden_dims=[8], dec_hidden_dims=[8], em_hidden_dims=[8], variational=variational,
+                                    kl_weight=0.5, **data)
+        e.autoencoder.compile(optimizer=optm.Adam(0.5), loss=emu.relative_mse_loss(e.signal_train))
+        e.emulator.compile(optimizer=optm.Adam(0.25), loss="mse")
+        tra, tre = _TapeTrainer(tape, "ae"), _TapeTrainer(tape, "em", base=10.0)
+        monkeypatch.setattr(e.autoencoder, "_ensure_trainer", lambda b: tra)
+        monkeypatch.setattr(e.emulator, "_ensure_trainer", lambda b: tre)
+        e.autoencoder._vae_seed = 9 if variational else None   # (what the patched _ensure_trainer would have drawn)
+        return e
+
+    head = [("ae", "set_data", 0, (10, 451), None), ("ae", "set_data", 1, (4, 451), None),
+            ("em", "set_data", 0, (10, 7), (10, 3)), ("em", "set_data", 1, (4, 7), (4, 3)),
+            ("joint", "create", "ae", "em", 1),
+            ("cba", "train_begin"), ("cbe", "train_begin")]
+
+    # (a) the autoencoder stops after the second epoch and is frozen (learning rate 0) while the emulator goes on; the
+    # emulator stops after the third; the fourth epoch never starts.  This loop does not refresh the variational settings.
+    tape = []
+    e = emulator(tape)
+    eng.set_random_seed(31)
+    P, ref = _perms(31, 10, 3)
+    out = e.train(4, ae_callbacks=[_TapeCallback(tape, "cba", stop_after=1)], em_callbacks=[_TapeCallback(tape, "cbe", stop_after=2)],
+                  verbose=0, joint=True, batch_size=4)
+    assert tape == head + [
+        ("cba", "epoch_begin", 0), ("cbe", "epoch_begin", 0), ("ae", "set_lr", 0.5), ("em", "set_lr", 0.25),
+        ("joint", "run_epoch", P[0], 4), ("joint", "evaluate"),
+        ("cba", "epoch_end", 0, {"loss": 1.0, "val_loss": 0.5}), ("cbe", "epoch_end", 0, {"loss": 11.0, "val_loss": 10.5}),
+        ("cba", "epoch_begin", 1), ("cbe", "epoch_begin", 1), ("ae", "set_lr", 0.5), ("em", "set_lr", 0.25),
+        ("joint", "run_epoch", P[1], 4), ("joint", "evaluate"),
+        ("cba", "epoch_end", 1, {"loss": 2.0, "val_loss": 0.5}), ("cbe", "epoch_end", 1, {"loss": 12.0, "val_loss": 10.5}),
+        ("cbe", "epoch_begin", 2), ("ae", "set_lr", 0.0), ("em", "set_lr", 0.25),
+        ("joint", "run_epoch", P[2], 4), ("joint", "evaluate"),
+        ("cbe", "epoch_end", 2, {"loss": 13.0, "val_loss": 10.5}),
+        ("cba", "train_end"), ("cbe", "train_end")]
+    assert out == ([1.0, 2.0], [0.5, 0.5], [11.0, 12.0, 13.0], [10.5, 10.5, 10.5])
+    assert e.autoencoder.optimizer.iterations == 103 and e.emulator.optimizer.iterations == 103
+    assert eng._rng.bit_generator.state == ref.bit_generator.state
+
+    # (b) the emulator stops first: the autoencoder goes on alone, on its own trainer; every epoch run
+    tape = []
+    e = emulator(tape)
+    eng.set_random_seed(32)
+    P, ref = _perms(32, 10, 2)
+    out = e.train(2, ae_callbacks=[_TapeCallback(tape, "cba")], em_callbacks=[_TapeCallback(tape, "cbe", stop_after=0)],
+                  verbose=0, joint=True, batch_size=4)
+    assert tape == head + [
+        ("cba", "epoch_begin", 0), ("cbe", "epoch_begin", 0), ("ae", "set_lr", 0.5), ("em", "set_lr", 0.25),
+        ("joint", "run_epoch", P[0], 4), ("joint", "evaluate"),
+        ("cba", "epoch_end", 0, {"loss": 1.0, "val_loss": 0.5}), ("cbe", "epoch_end", 0, {"loss": 11.0, "val_loss": 10.5}),
+        ("cba", "epoch_begin", 1), ("ae", "set_lr", 0.5), ("em", "set_lr", 0.25),
+        ("ae", "run_epoch", P[1], 4), ("ae", "evaluate", 1, 4),
+        ("cba", "epoch_end", 1, {"loss": 2.0, "val_loss": 0.5}),
+        ("cba", "train_end"), ("cbe", "train_end")]
+    assert out == ([1.0, 2.0], [0.5, 0.5], [11.0], [10.5])
+
+    e = emu.AutoEncoderEmulator(latent_dim=3, enc_hidden_dims=[8], dec_hidden_dims=[8], em_hidden_dims=[8], **data)
+    with pytest.raises(RuntimeError, match="compile your model"):
+        e.train(1, verbose=0, joint=True)
