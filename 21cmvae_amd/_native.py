@@ -61,6 +61,23 @@ FIT_DEFAULTS = {"max_iter": 50, "lambda0": 1e-3, "xtol": 1e-7, "check_every": 8}
 FIT_STATUS = {0: "iteration limit", 1: "converged", 2: "no improving step", 3: "no information"}
 
 
+class SampleOpts(C.Structure):
+    """v21_sample_opts (include/v21_types.h)"""
+    _fields_ = [("n_steps", C.c_int), ("n_warmup", C.c_int), ("thin", C.c_int), ("eps0", C.c_double), ("ridge", C.c_double),
+                ("target_accept", C.c_double), ("seed", C.c_ulonglong), ("chain0", C.c_longlong), ("step0", C.c_longlong)]
+
+
+SAMPLE_DEFAULTS = {"n_steps": 1000, "n_warmup": 200, "thin": 1, "eps0": 1.0, "ridge": 1.0, "target_accept": 0.574, "seed": 0,
+                   "chain0": 0, "step0": 0}
+SAMPLE_OUTPUTS = ("samples", "samples_lnl", "x_last", "lnl_last", "eps_last", "accept_rate", "mean_u", "cov_u", "last_prop_u",
+                  "last_log_alpha")
+
+
+class SampleOut(C.Structure):
+    """v21_sample_out (include/v21_types.h): host or device addresses, NULL = not asked for"""
+    _fields_ = [(k, C.c_void_p) for k in SAMPLE_OUTPUTS]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 # name -> (restype, argtypes); every symbol include/v21.h declares
@@ -128,6 +145,10 @@ SIGNATURES = {
     "v21_mlp_fit": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(FitOpts), _P, _F, _F, _F, C.POINTER(C.c_int32),
                               C.c_int, C.c_int]),
     "v21_mlp_fit_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(FitOpts), _P, _P, _P, _P, _P, C.c_int, C.c_int]),
+    "v21_mlp_sample": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(SampleOpts), _P, C.POINTER(SampleOut),
+                                 C.c_int, C.c_int]),
+    "v21_mlp_sample_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(SampleOpts), _P, C.POINTER(SampleOut),
+                                     C.c_int, C.c_int]),
     "v21_trainer_last_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "v21_route_name": (C.c_char_p, [C.c_int, C.c_int]),
     "v21_trainer_get_data_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
@@ -720,6 +741,83 @@ class Stack(_Owned):
         o = self.fit_opts(**opts)
         check(self.lib.v21_mlp_fit_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), _P(d_x_hat), _P(d_lnl),
                                        _opt(d_lnl_start), _opt(d_fisher), _opt(d_status), precision_id(precision), flags))
+
+    @staticmethod
+    def sample_opts(n_steps=None, n_warmup=None, thin=None, eps0=None, ridge=None, target_accept=None, seed=None, chain0=None,
+                    step0=None):
+        """v21_sample_opts with the defaults of SAMPLE_DEFAULTS for None; ValueError for what the library would refuse"""
+        o = dict(SAMPLE_DEFAULTS)
+        o.update({k: v for k, v in (("n_steps", n_steps), ("n_warmup", n_warmup), ("thin", thin), ("eps0", eps0), ("ridge", ridge),
+                                    ("target_accept", target_accept), ("seed", seed), ("chain0", chain0), ("step0", step0))
+                  if v is not None})
+        for k in ("n_steps", "n_warmup", "thin", "chain0", "step0", "seed"):
+            if int(o[k]) != o[k] or int(o[k]) < 0:
+                raise ValueError("sample: %s = %r (a non-negative integer)" % (k, o[k]))
+        if int(o["n_steps"]) >= 2 ** 31 or int(o["n_warmup"]) >= 2 ** 31 or int(o["thin"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64:
+            raise ValueError("sample: count out of range")
+        if int(o["step0"]) + int(o["n_warmup"]) + int(o["n_steps"]) >= 2 ** 32:
+            raise ValueError("sample: step0 + n_warmup + n_steps must stay below 2^32")
+        for k in ("eps0", "ridge"):
+            if not (float(o[k]) > 0 and np.isfinite(float(o[k]))):
+                raise ValueError("sample: %s = %r (positive and finite)" % (k, o[k]))
+        if not 0.0 < float(o["target_accept"]) < 1.0:
+            raise ValueError("sample: target_accept = %r (inside (0, 1))" % (o["target_accept"],))
+        return SampleOpts(int(o["n_steps"]), int(o["n_warmup"]), int(o["thin"]), float(o["eps0"]), float(o["ridge"]),
+                          float(o["target_accept"]), int(o["seed"]), int(o["chain0"]), int(o["step0"]))
+
+    def sample(self, x0, precision="f32", flags=0, data=None, eps_start=None, samples=True, diagnostics=False, **opts):
+        """Posterior sampling: one Fisher-preconditioned MALA chain per start row, on the device (include/v21.h:
+        v21_mlp_sample; needs the input transform and a likelihood record).  The target is ln L of the record under a
+        uniform prior on the training box in par_transform's coordinates u (log-uniform in a log10 column's raw value).
+        x0: (n, in) raw starts, float32 or float64; data as for fit; eps_start: None or (n,) per-chain step sizes
+        (instead of eps0); opts: n_steps, n_warmup, thin, eps0, ridge, target_accept, seed, chain0, step0 (SAMPLE_DEFAULTS).
+        -> dict x_last (n, in) in x0's dtype, lnl_last (n,) float32, eps_last, accept_rate (n,), mean_u (n, in), cov_u
+        (n, in, in) float64 -- the per-chain moments of u over the n_steps kept transitions -- and, with samples and
+        thin > 0, samples (n, n_steps // thin, in) in x0's dtype and samples_lnl; with diagnostics, last_prop_u (n, in)
+        float32 and last_log_alpha (n,) float64 of the last transition."""
+        x, dt = self._rows(x0)
+        n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
+        if din > 8:
+            raise ValueError("sample: %d parameters (at most 8)" % din)
+        nd, dp = 0, None
+        if data is not None:
+            dp = np.ascontiguousarray(data, dtype=np.float32)
+            if dp.ndim == 1:
+                dp = dp[None, :]
+            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
+                raise ValueError("sample: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
+            nd = dp.shape[0]
+            if n % nd:
+                raise ValueError("sample: %d chains are not a multiple of %d data rows" % (n, nd))
+        o = self.sample_opts(**opts)
+        es = None
+        if eps_start is not None:
+            es = np.ascontiguousarray(eps_start, dtype=np.float64)
+            if es.shape != (n,) or not np.all(es > 0):
+                raise ValueError("sample: eps_start must be (%d,) positive step sizes" % n)
+        keep = o.n_steps // o.thin if o.thin > 0 else 0
+        res = {"x_last": np.empty_like(x), "lnl_last": np.empty(n, np.float32), "eps_last": np.empty(n, np.float64),
+               "accept_rate": np.empty(n, np.float64), "mean_u": np.empty((n, din), np.float64),
+               "cov_u": np.empty((n, din, din), np.float64)}
+        if samples and keep > 0:
+            res["samples"] = np.empty((n, keep, din), x.dtype)
+            res["samples_lnl"] = np.empty((n, keep), np.float32)
+        if diagnostics:
+            res["last_prop_u"] = np.empty((n, din), np.float32)
+            res["last_log_alpha"] = np.empty(n, np.float64)
+        out = SampleOut(**{k: v.ctypes.data for k, v in res.items()})
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_sample(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(o),
+                                          es.ctypes.data_as(_P) if es is not None else None, C.byref(out), precision_id(precision), flags))
+        return res
+
+    def sample_dev(self, d_x0, ldx, n, d_data, n_data, out, d_eps_start=None, precision="f32", flags=0, **opts):
+        """v21_mlp_sample_dev: out is a dict of device addresses by the names of SAMPLE_OUTPUTS (x_last required; samples
+        float32); asynchronous on the context's stream."""
+        o = self.sample_opts(**opts)
+        so = SampleOut(**{k: int(v) for k, v in out.items() if v})
+        check(self.lib.v21_mlp_sample_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), _opt(d_eps_start), C.byref(so),
+                                          precision_id(precision), flags))
 
     def last_jac_route(self):
         """(route name of the last Jacobian / log-likelihood call, {route name: calls since creation})."""

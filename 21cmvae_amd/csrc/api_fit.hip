@@ -8,8 +8,8 @@
 #include "fit_kernels.h"
 
 // F (n, din, din), and lnl / grad (nullable) of the n prepped rows on `route`; row n of the call reads data row
-// (row0 + n) / rpd of pitch ld_data
-static int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, const float* d_data, long long ld_data,
+// (row0 + n) / rpd of pitch ld_data (api_internal.h: the sampler's evaluations are this call too)
+int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, const float* d_data, long long ld_data,
                       long long rpd, long long row0, int prec, int flags) {
   const int din = m->dims[0], dout = m->dims[m->L];
   auto kern = din <= kFitMaxIn ? jac_fisher_kernel<kFitMaxIn> : jac_fisher_kernel<kFisherMaxIn>;

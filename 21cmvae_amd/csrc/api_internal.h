@@ -43,6 +43,7 @@ constexpr int kStampSlots = 64;
 #include "routes.h"
 
 namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip)
+namespace v21 { struct SampleRow; }  // sample_kernels.h (api_sample.hip)
 using namespace v21;
 
 // ---- errors: v21_last_error() returns the calling thread's last message (api_base.hip)
@@ -211,6 +212,8 @@ struct v21_mlp {
   Dev<FitRow> fit;       // fit state (fit_kernels.h), then F / ln L / gradient of its rows, running rows per iteration, data
   Dev<float> fF, fl, fg, fdata;
   Dev<int> fit_cnt;
+  Dev<SampleRow> smp;    // chain state of a sample call (sample_kernels.h; its evaluations land in fF / fl / fg)
+  Dev<double> smp_out;   // the host form's chunk: its results, and its per-chain start step sizes
   bool has_lk = false;
   int last_jac_route = 0;
   long long jac_route_count[4] = {0, 0, 0, 0};
@@ -250,6 +253,10 @@ int jac_prep(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n
 // there by reduce(y, jac, r0, rows) (y: nullptr unless want_y; r0: the slice's first row)
 int jac_slices(v21_mlp* m, int route, long long n, bool want_y, int prec, int flags,
                const std::function<int(const float*, const float*, long long, long long)>& reduce);
+// api_fit.hip, shared with api_sample.hip: F (n, din, din), and lnl / grad (nullable), of the n prepped rows on `route`;
+// row n of the call reads data row (row0 + n) / rpd of pitch ld_data
+int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, const float* d_data, long long ld_data,
+               long long rpd, long long row0, int prec, int flags);
 // a host form's rows, chunk by chunk: upload (m->hin) and prep them, run(r0, rows, out) on the chunk (out: m->hout of
 // out_floats per row, and never fewer than a Jacobian row's y and jac, so that no host form regrows what another left),
 // then sync

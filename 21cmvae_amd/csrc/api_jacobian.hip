@@ -74,7 +74,7 @@ int jac_args(v21_mlp* m, bool ptrs, long long n, long long ldx, long long ldy, i
   flags &= 0xFF;
   if (m->dims[0] > e.max_in) return fail(V21_ERR_UNSUPPORTED, "%s: %d inputs (at most %d)", e.name, m->dims[0], e.max_in);
   if (n == 0 && !e.fit) return V21_OK;
-  if (e.fit && !m->has_tin) return fail(V21_ERR_STATE, "fit: no input transform (v21_mlp_set_input_transform): it defines the box");
+  if (e.fit && !m->has_tin) return fail(V21_ERR_STATE, "%s: no input transform (v21_mlp_set_input_transform): it defines the box", e.name);
   if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
   if ((flags & V21_FWD_IN_TRANSFORM) && !m->has_tin) return fail(V21_ERR_STATE, "input transform requested but not set");
   if ((flags & V21_FWD_OUT_TRANSFORM) && !m->has_tout) return fail(V21_ERR_STATE, "output transform requested but not set");

@@ -1,0 +1,146 @@
+// api_sample.hip -- posterior sampling on the device (include/v21.h: v21_mlp_sample[_dev]): n independent chains of a
+// Fisher-preconditioned Metropolis-adjusted Langevin sampler (sample_kernels.h) in the fit's coordinates.  The loop is
+// the fit's without its read-back: the chain state stays on the device, every transition is one Fisher evaluation of the
+// pending proposals (fisher_run of api_fit.hip, on u without the input transform) and one sample_step_kernel launch,
+// and the host only launches.
+#include "api_internal.h"
+#include "sample_kernels.h"
+
+static v21_sample_opts sample_defaults() {
+  v21_sample_opts o;
+  o.n_steps = 1000;
+  o.n_warmup = 200;
+  o.thin = 1;
+  o.eps0 = 1.0;
+  o.ridge = 1.0;
+  o.target_accept = 0.574;
+  o.seed = 0;
+  o.chain0 = 0;
+  o.step0 = 0;
+  return o;
+}
+
+static long long sample_keep(const v21_sample_opts& o) { return o.thin > 0 ? o.n_steps / o.thin : 0; }
+
+// the chains of n start rows prepped transformed (their fac is overwritten); `out`: device pointers, samples and x_last
+// of x_dtype; the call's first chain is global chain `chain0`, its row `row0` of the call (data rows as in fit_run)
+static int sample_run(v21_mlp* m, int route, long long n, const float* d_data, long long ld_data, long long rpd, long long row0,
+                      const v21_sample_opts& o, long long chain0, const double* d_eps_start, int prec, int flags, const v21_sample_out& out,
+                      int x_dtype) {
+  hipStream_t st = m->ctx->stream;
+  const int din = m->dims[0];
+  CHK(m->smp.reserve((size_t)n));
+  CHK(m->fF.reserve((size_t)n * din * din));
+  CHK(m->fl.reserve((size_t)n));
+  CHK(m->fg.reserve((size_t)n * din));
+  SampleRow* cs = m->smp.get();
+  float *F = m->fF.get(), *l = m->fl.get(), *g = m->fg.get();
+  const dim3 grid((unsigned)((n + 255) / 256));
+  SampleArgs a{};
+  a.n = n; a.din = din;
+  a.total = (long long)o.n_warmup + o.n_steps; a.n_warmup = o.n_warmup;
+  a.thin = o.thin; a.n_keep = sample_keep(o);
+  a.ridge = o.ridge; a.target = o.target_accept;
+  a.seed = o.seed; a.chain0 = (uint64_t)chain0; a.step0 = (uint64_t)o.step0;
+  a.samples = out.samples; a.samples_lnl = out.samples_lnl;
+  a.t = m->tin;
+  hipLaunchKernelGGL(sample_init_kernel, grid, dim3(256), 0, st, cs, m->jxt.get(), m->jfac.get(), n, din, o.eps0, d_eps_start);
+  HIPCHK(hipGetLastError());
+  for (long long it = 0; it <= a.total; ++it) {
+    CHK(fisher_run(m, route, n, F, l, g, d_data, ld_data, rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
+    if (x_dtype == V21_DTYPE_F64)
+      hipLaunchKernelGGL(sample_step_kernel<double>, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
+    else
+      hipLaunchKernelGGL(sample_step_kernel<float>, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
+    HIPCHK(hipGetLastError());
+  }
+  SampleOutDev od{out.x_last, out.lnl_last, out.eps_last, out.accept_rate, out.mean_u, out.cov_u, out.last_prop_u, out.last_log_alpha};
+  if (x_dtype == V21_DTYPE_F64)
+    hipLaunchKernelGGL(sample_finish_kernel<double>, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din,
+                       (long long)o.n_steps, m->tin, od);
+  else
+    hipLaunchKernelGGL(sample_finish_kernel<float>, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din,
+                       (long long)o.n_steps, m->tin, od);
+  HIPCHK(hipGetLastError());
+  return V21_OK;
+}
+
+// as fit_check: has_data: a data matrix of n_data rows was handed in (at least one, dividing n)
+static int sample_check(long long n, bool has_data, long long n_data, const v21_sample_opts& o) {
+  if (has_data && (n_data < 1 || n % n_data != 0)) return fail(V21_ERR_ARG, "sample: n = %lld rows, n_data = %lld", n, n_data);
+  if (o.n_steps < 0 || o.n_warmup < 0 || o.thin < 0 || !(o.eps0 > 0.0) || !std::isfinite(o.eps0) || !(o.ridge > 0.0) || !std::isfinite(o.ridge) ||
+      !(o.target_accept > 0.0 && o.target_accept < 1.0))
+    return fail(V21_ERR_ARG, "sample: options n_steps %d n_warmup %d thin %d eps0 %g ridge %g target_accept %g", o.n_steps, o.n_warmup, o.thin,
+                o.eps0, o.ridge, o.target_accept);
+  if (o.chain0 < 0 || o.step0 < 0 || o.step0 + (long long)o.n_warmup + o.n_steps >= (1LL << 32))
+    return fail(V21_ERR_ARG, "sample: options chain0 %lld step0 %lld (step0 + n_warmup + n_steps < 2^32)", o.chain0, o.step0);
+  return V21_OK;
+}
+
+static constexpr JacEntry kSample{"sample", kFitMaxIn, true, true};
+
+extern "C" int v21_mlp_sample_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                  const v21_sample_opts* opts, const double* d_eps_start, const v21_sample_out* out, int precision, int flags) {
+  const v21_sample_opts o = opts ? *opts : sample_defaults();
+  CHK(jac_args(m, d_x0 && out && out->x_last, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kSample));
+  CHK(sample_check(n, d_data != nullptr, n_data, o));
+  if (n == 0) return V21_OK;
+  const float* data = d_data ? d_data : m->lk_data.get();
+  const long long ld = d_data ? m->dims[m->L] : 0, rpd = d_data ? n / n_data : 1;
+  const int route = jac_route(m, flags, m->dims[m->L]);
+  CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
+  return sample_run(m, route, n, data, ld, rpd, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32);
+}
+
+extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_sample_opts* opts,
+                              const double* eps_start, const v21_sample_out* out, int precision, int flags) {
+  const v21_sample_opts o = opts ? *opts : sample_defaults();
+  CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kSample));
+  CHK(sample_check(n, data != nullptr, n_data, o));
+  if (n == 0) return V21_OK;
+  const int din = m->dims[0], dout = m->dims[m->L];
+  hipStream_t st = m->ctx->stream;
+  if (data) {
+    CHK(m->fdata.reserve((size_t)n_data * dout));
+    HIPCHK(hipMemcpyAsync(m->fdata.p, data, (size_t)n_data * dout * sizeof(float), hipMemcpyHostToDevice, st));
+  }
+  const float* d_data = data ? m->fdata.get() : m->lk_data.get();
+  const long long ld = data ? dout : 0, rpd = data ? n / n_data : 1;
+  const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
+  const long long keep = sample_keep(o);
+  const int route = jac_route(m, flags, dout);
+  // a chunk's staging, in 8-byte units per chain: the start step sizes, then every result that was asked for
+  const long long chunk = std::min<long long>(n, kJacHostChunk);
+  const long long w_smp = out->samples ? keep * din : 0, w_sl = out->samples_lnl ? (keep + 1) / 2 : 0;
+  const long long per = 1 + w_smp + w_sl + din + 1 + 1 + 1 + din + (long long)din * din + din + 1;
+  CHK(m->smp_out.reserve((size_t)(chunk * per)));
+  return jac_chunks(m, x0, x_dtype, n, 1, din * din + din + 3, [&](long long r0, long long rows, float*) -> int {
+    double* p = m->smp_out.get();
+    auto take = [&](long long units) { double* q = p; p += rows * units; return q; };
+    double* d_eps = take(1);
+    v21_sample_out d{};
+    d.samples = out->samples ? take(w_smp) : nullptr;
+    d.samples_lnl = out->samples_lnl ? (float*)take(w_sl) : nullptr;
+    d.x_last = take(din);
+    d.lnl_last = (float*)take(1);
+    d.eps_last = take(1);
+    d.accept_rate = take(1);
+    d.mean_u = take(din);
+    d.cov_u = take((long long)din * din);
+    d.last_prop_u = (float*)take(din);
+    d.last_log_alpha = take(1);
+    if (eps_start) HIPCHK(hipMemcpyAsync(d_eps, eps_start + r0, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, st));
+    CHK(sample_run(m, route, rows, d_data, ld, rpd, r0, o, o.chain0 + r0, eps_start ? d_eps : nullptr, precision, flags, d, x_dtype));
+    if (out->samples) CHK(to_host(m, (char*)out->samples + r0 * keep * din * esz, d.samples, (size_t)rows * keep * din * esz));
+    if (out->samples_lnl) CHK(to_host(m, out->samples_lnl + r0 * keep, d.samples_lnl, (size_t)rows * keep * sizeof(float)));
+    CHK(to_host(m, (char*)out->x_last + r0 * din * esz, d.x_last, (size_t)rows * din * esz));
+    if (out->lnl_last) CHK(to_host(m, out->lnl_last + r0, d.lnl_last, (size_t)rows * sizeof(float)));
+    if (out->eps_last) CHK(to_host(m, out->eps_last + r0, d.eps_last, (size_t)rows * sizeof(double)));
+    if (out->accept_rate) CHK(to_host(m, out->accept_rate + r0, d.accept_rate, (size_t)rows * sizeof(double)));
+    if (out->mean_u) CHK(to_host(m, out->mean_u + r0 * din, d.mean_u, (size_t)rows * din * sizeof(double)));
+    if (out->cov_u) CHK(to_host(m, out->cov_u + r0 * din * din, d.cov_u, (size_t)rows * din * din * sizeof(double)));
+    if (out->last_prop_u) CHK(to_host(m, out->last_prop_u + r0 * din, d.last_prop_u, (size_t)rows * din * sizeof(float)));
+    if (out->last_log_alpha) CHK(to_host(m, out->last_log_alpha + r0, d.last_log_alpha, (size_t)rows * sizeof(double)));
+    return V21_OK;
+  });
+}

@@ -161,6 +161,37 @@ def _grid(redshifts_, frequencies):
 FitResult = namedtuple("FitResult", ["params", "lnl", "status", "fisher"])
 
 
+# sample_posterior's result.  params / lnl: None with thin = 0; mean_u, cov_u: pooled over the chains of a spectrum, in
+# par_transform's coordinates u, from the device's per-chain moments (as r_hat is: none of the three needs the samples)
+PosteriorSamples = namedtuple("PosteriorSamples", ["params", "lnl", "accept_rate", "step_size", "r_hat", "mean_u", "cov_u"])
+
+
+def pooled_moments(mean_c, cov_c):
+    """Mean and covariance of the pooled samples of equally long chains from their per-chain means (..., C, d) and
+    covariances (..., C, d, d) (both divided by the chain length): the mean of the means, and the mean within-chain
+    covariance plus the covariance of the means."""
+    mean_c, cov_c = np.asarray(mean_c, np.float64), np.asarray(cov_c, np.float64)
+    mean = mean_c.mean(axis=-2)
+    dm = mean_c - mean[..., None, :]
+    return mean, cov_c.mean(axis=-3) + np.einsum("...ci,...cj->...ij", dm, dm) / mean_c.shape[-2]
+
+
+def r_hat_from_moments(mean_c, cov_c, n):
+    """Gelman-Rubin potential scale reduction per coordinate from per-chain means (..., C, d) and covariances (..., C, d, d)
+    of chains of n samples each (covariances divided by n, as the device returns them): W = the mean unbiased within-chain
+    variance, B / n = the unbiased variance of the chain means, R = sqrt(((n - 1) / n W + B / n) / W).  NaN where it is
+    undefined (one chain, one sample, or W = 0)."""
+    mean_c = np.asarray(mean_c, np.float64)
+    var_c = np.diagonal(np.asarray(cov_c, np.float64), axis1=-2, axis2=-1)
+    C = mean_c.shape[-2]
+    if C < 2 or n < 2:
+        return np.full(mean_c.shape[:-2] + mean_c.shape[-1:], np.nan)
+    W = var_c.mean(axis=-2) * n / (n - 1.0)
+    B_over_n = mean_c.var(axis=-2, ddof=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sqrt(((n - 1.0) / n * W + B_over_n) / W)
+
+
 class _EmulatorBase:
     par_labels = ["fstar", "Vc", "fx", "tau", "alpha", "nu_min", "Rmfp"]
 
@@ -329,6 +360,60 @@ class _EmulatorBase:
             xh, lnl, status = xh[0], lnl[0], status[0]
             F = F[0] if F is not None else None
         return FitResult(xh, lnl, status, F)
+
+    def sample_posterior(self, data, sigma, n_chains=64, n_steps=1000, n_warmup=200, thin=1, p0=None, flow=None, fhigh=None, seed=0,
+                         eps=None, return_lnl=False):
+        """Posterior samples of the parameters given observed signal(s) (not in the reference): ``n_chains`` independent
+        Markov chains per spectrum, run entirely on the device -- a Metropolis-adjusted Langevin sampler preconditioned
+        with the Fisher matrix at the current point (include/v21.h: v21_mlp_sample) -- of the Gaussian ln L of
+        ``log_likelihood`` under a UNIFORM PRIOR ON THE TRAINING BOX in par_transform's coordinates u in [-1, 1]^7: uniform
+        in the linear columns, log-uniform in the log10 columns, zero outside the box.
+        ``data``: (451,) or (M, 451) mK.  Starts: ``p0`` ((7,) or (n_chains, 7) raw parameters, the same for every
+        spectrum), or by default the best ``fit_parameters`` start per spectrum; either way every chain is jittered
+        (seeded, 0.02 in u, clipped into the box).  Each chain runs ``n_warmup`` transitions adapting its step size
+        (initially ``eps``, default 1) to an acceptance rate of 0.574, then ``n_steps`` kept ones of which every
+        ``thin``-th is stored (``thin = 0``: none, moments only).
+        Returns ``PosteriorSamples``: params (M, n_chains, n_steps // thin, 7) raw, lnl (the same without the last axis;
+        None unless ``return_lnl``), accept_rate and step_size (M, n_chains), r_hat (M, 7) -- the between / within-chain
+        potential scale reduction in u -- and the pooled mean_u (M, 7) / cov_u (M, 7, 7), all three from the per-chain
+        moments the device accumulates in float64; the M axis is dropped for one spectrum.  Bounds: a log column's lower
+        bound comes back as 10^lo (the fx zero floor 1e-6, not 0)."""
+        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
+        nb, din = st.dims[-1], st.dims[0]
+        dat = np.asarray(data, np.float32)
+        one = dat.ndim == 1
+        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
+        if dat.ndim != 2 or dat.shape[1] != nb:
+            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        M, C = dat.shape[0], int(n_chains)
+        if C < 1:
+            raise ValueError("n_chains must be >= 1")
+        opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
+        nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
+        if p0 is None:
+            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed).params, np.float64, ndmin=2)
+            u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], C, axis=1)
+        else:
+            starts = np.array(p0, np.float64, ndmin=2)
+            if starts.ndim != 2 or starts.shape[1] != din or starts.shape[0] not in (1, C):
+                raise ValueError("p0 must be (%d,) or (%d, %d), got %r" % (din, C, din, np.shape(p0)))
+            u0 = np.broadcast_to(pp.par_transform(starts, self.par_train)[None], (M, C, din))
+        rng = np.random.default_rng(seed)
+        u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=(M, C, din)), -1.0, 1.0)
+        x0 = np.ascontiguousarray(pp.par_untransform(u0.reshape(M * C, din), self.par_train))
+        st.use_likelihood(dat[0], self._band_weights(nb, sigma, flow, fhigh))
+        r = st.sample(x0, model.precision, flags, data=dat, **opts)
+        K = r["samples"].shape[1] if "samples" in r else 0
+        params = r["samples"].reshape(M, C, K, din) if K else None
+        lnl = r["samples_lnl"].reshape(M, C, K) if K and return_lnl else None
+        acc, step = r["accept_rate"].reshape(M, C), r["eps_last"].reshape(M, C)
+        mean_c, cov_c = r["mean_u"].reshape(M, C, din), r["cov_u"].reshape(M, C, din, din)
+        rh = r_hat_from_moments(mean_c, cov_c, int(n_steps))
+        mean, cov = pooled_moments(mean_c, cov_c)
+        if one:
+            params, lnl = (params[0] if params is not None else None), (lnl[0] if lnl is not None else None)
+            acc, step, rh, mean, cov = acc[0], step[0], rh[0], mean[0], cov[0]
+        return PosteriorSamples(params, lnl, acc, step, rh, mean, cov)
 
     def save(self):
         raise NotImplementedError("Not implemented yet.")

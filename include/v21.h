@@ -231,6 +231,41 @@ int v21_mlp_fit_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, con
                     const v21_fit_opts* opts, float* d_x_hat, float* d_lnl, float* d_lnl_start, float* d_fisher, int32_t* d_status,
                     int precision, int flags);
 
+/* ---- posterior sampling: n independent Markov chains on the device, each a Metropolis-adjusted Langevin sampler whose
+ * metric is the Fisher matrix at the current point ("simplified manifold MALA"), of the posterior of v21_mlp_loglike's
+ * ln L under a UNIFORM PRIOR ON THE TRAINING BOX in the fit's coordinates u = par_transform(x) in [-1, 1]^in_dim -- that
+ * is, log-uniform in the raw value of a log10 column.  Needs the input transform and a likelihood record; in_dim <= 8.
+ *   One transition, with G(u) = F(u) + ridge I = L L^T (float64 Cholesky), d = in_dim, step size e:
+ *     mu(u) = u + e^2 / 2 G(u)^-1 g(u);   proposal u' = mu(u) + e L(u)^-T xi, xi ~ N(0, I_d), rounded to float32
+ *     log q(b | a) = -|L(a)^T (b - mu(a))|^2 / (2 e^2) + sum_i log L_ii(a) - d / 2 log(2 pi e^2)
+ *     log alpha = lnL(u') - lnL(u) + log q(u | u') - log q(u' | u);   accepted iff log(uniform) < log alpha.
+ *   ln L, g and F at a proposal come from one Fisher evaluation on u, as a fit's do.  The derivative of the metric that
+ *   full manifold MALA carries in its drift is left out; the acceptance uses the q above, so the chain is exact.  A
+ *   proposal with a coordinate outside [-1, 1] is rejected (never clamped or reflected; its evaluation is not read), and
+ *   so is one whose G has no finite Cholesky factor.  With all-zero weights G = ridge I: a random walk on the box.
+ *   A call runs n_warmup + n_steps transitions.  In transition t = 1 .. n_warmup of the call a chain adapts its own step
+ *   size, log e += t^-0.6 (min(1, alpha) - target_accept); afterwards e is frozen.  Only the n_steps transitions after
+ *   the warm-up enter samples (every thin-th of them, n_steps / thin rounded down per chain; transitions beyond the last
+ *   whole multiple of thin still enter the moments), mean_u / cov_u and accept_rate.
+ *   Random numbers: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), key =
+ *   (seed & 0xffffffff, seed >> 32), counter = (c & 0xffffffff, c >> 32, s, block) with c = chain0 + the chain's row in
+ *   the call and s = step0 + the transition's index in the call (warm-up included): a draw depends on nothing else, so
+ *   chains do not depend on how a run is split over calls, chunks or GPUs.  A word w gives the uniform (w + 0.5) 2^-32.
+ *   Blocks 0 and 1 give xi: block b's words (w0, w1, w2, w3) give xi[4b] = r cos(t), xi[4b + 1] = r sin(t) with
+ *   r = sqrt(-2 ln U(w0)), t = 2 pi U(w1), and xi[4b + 2], xi[4b + 3] likewise from (w2, w3) (Box-Muller, float64;
+ *   components >= in_dim are not used).  Word 0 of block 2 gives the uniform of the acceptance test.
+ *   x0: start rows in raw units (clamped into the box; accepted whatever their ln L).  data / n_data: as for a fit (chain
+ *   n samples data row n / (n / n_data)).  eps_start (nullable, n float64): per-chain step sizes instead of eps0 --
+ *   with x_last, eps_last, n_warmup = 0 and step0 advanced by the transitions done, a call continues an earlier one
+ *   (exactly, when x_last is float64: the state is the float32 u).  opts and results: v21_types.h.  The route is the
+ *   Jacobian's; v21_mlp_last_jac_route counts a sample call once, whatever its transitions and chunks.
+ * The host form works in chunks of 8,192 chains and returns when the results are in place; the _dev form never
+ * synchronises. */
+int v21_mlp_sample(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_sample_opts* opts,
+                   const double* eps_start, const v21_sample_out* out, int precision, int flags);
+int v21_mlp_sample_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                       const v21_sample_opts* opts, const double* d_eps_start, const v21_sample_out* out, int precision, int flags);
+
 /* ---- trainer: replaces Model.compile + Model.fit (emulator.py:369-378, :739-747,
  * :756-764; optimizer/loss from notebooks/Training.ipynb cells 4 and 10). ------- */
 typedef struct {

@@ -17,4 +17,30 @@ typedef struct {
   double xtol;      /* [1e-7] converged when the projected step's largest |component| (u units) is <= xtol */
   int check_every;  /* [8] the host reads the count of running rows every check_every iterations */
 } v21_fit_opts;
+/* options of v21_mlp_sample[_dev] (a NULL pointer: the defaults in brackets) */
+typedef struct {
+  int n_steps;          /* [1000] transitions after the warm-up: they enter the samples, the moments and accept_rate */
+  int n_warmup;         /* [200] transitions before them, in which every chain adapts its step size; never kept */
+  int thin;             /* [1] every thin-th kept transition is stored, n_steps / thin (rounded down) per chain; 0: none */
+  double eps0;          /* [1] initial step size of every chain (u units of the Fisher metric), > 0 */
+  double ridge;         /* [1] added to the diagonal of the Fisher matrix to form the metric, > 0 */
+  double target_accept; /* [0.574] acceptance rate the warm-up steers the step size to, in (0, 1) */
+  unsigned long long seed;  /* [0] the Philox key */
+  long long chain0;     /* [0] global index of the call's first chain, >= 0 */
+  long long step0;      /* [0] global index of the call's first transition, >= 0; step0 + n_warmup + n_steps < 2^32 */
+} v21_sample_opts;
+/* results of v21_mlp_sample[_dev]: host pointers for the host form, device pointers for _dev; every one but x_last may
+ * be NULL.  n chains, K = n_steps / thin stored states each; "x type" is x0's dtype (_dev: float32). */
+typedef struct {
+  void* samples;          /* (n, K, in_dim) x type: the stored states, raw units */
+  float* samples_lnl;     /* (n, K): ln L at them */
+  void* x_last;           /* (n, in_dim) x type: the state after the last transition, raw units */
+  float* lnl_last;        /* (n): ln L there */
+  double* eps_last;       /* (n): the step size after the warm-up */
+  double* accept_rate;    /* (n): accepted / kept transitions */
+  double* mean_u;         /* (n, in_dim): per-chain mean of u over the kept transitions */
+  double* cov_u;          /* (n, in_dim, in_dim): per-chain covariance of u over them (divided by n_steps) */
+  float* last_prop_u;     /* (n, in_dim): the proposal of the last transition, u units */
+  double* last_log_alpha; /* (n): its log acceptance ratio (-inf: outside the box or no Cholesky factor) */
+} v21_sample_out;
 #endif /* V21_TYPES_H */
