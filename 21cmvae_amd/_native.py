@@ -149,6 +149,10 @@ SIGNATURES = {
                                  C.c_int, C.c_int]),
     "v21_mlp_sample_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(SampleOpts), _P, C.POINTER(SampleOut),
                                      C.c_int, C.c_int]),
+    "v21_nuisance_whiten": (C.c_int, [C.POINTER(C.c_double), _F, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "v21_mlp_set_nuisance": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, C.c_int32]),
+    "v21_mlp_nuisance_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "v21_mlp_nuisance_coef": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int]),
     "v21_trainer_last_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "v21_route_name": (C.c_char_p, [C.c_int, C.c_int]),
     "v21_trainer_get_data_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
@@ -204,6 +208,21 @@ def route_jacobian(dims, act, precision, n, flags=0):
     r = C.c_int(0)
     check(load_library().v21_route_jacobian(*_layers(dims, act), precision_id(precision), int(n), int(flags), C.byref(r)))
     return JAC_ROUTES[r.value]
+
+
+def nuisance_whiten(basis, inv_var):
+    """The W-orthonormalised nuisance basis (include/v21.h: v21_nuisance_whiten; pure host arithmetic: no GPU).  basis
+    (K, out) float64, inv_var (out,) float32 -> (Q (K, out), R (K, K)) float64 with Q diag(inv_var) Q^T = I and
+    sqrt(W) basis^T = sqrt(W) Q^T R; EngineError for a rank-deficient basis, K outside 1 .. 8, or too few weighted bins."""
+    A = np.ascontiguousarray(basis, dtype=np.float64)
+    w = np.ascontiguousarray(inv_var, dtype=np.float32).ravel()
+    if A.ndim != 2 or A.shape[1] != w.size:
+        raise ValueError("nuisance: basis must be (K, %d), got %r" % (w.size, np.shape(basis)))
+    K, D = A.shape
+    q, r = np.zeros((max(K, 1), D), np.float64), np.zeros((max(K, 1), max(K, 1)), np.float64)
+    dp = C.POINTER(C.c_double)
+    check(load_library().v21_nuisance_whiten(A.ctypes.data_as(dp), _fptr(w), K, D, q.ctypes.data_as(dp), r.ctypes.data_as(dp)))
+    return q, r
 
 
 def route_train(dims, act, precision, max_batch, rows, nranks=1, rt_ready=False):
@@ -545,7 +564,7 @@ class Stack(_Owned):
         check(self.lib.v21_mlp_num_params(h, C.byref(n)))
         self.num_params = n.value
         # what the device holds, as use_output_stats / use_input_stats / use_likelihood left it (None: nothing, or set directly)
-        self.out_stats = self.in_stats = self.lk_record = None
+        self.out_stats = self.in_stats = self.lk_record = self.nu_record = None
 
     def set_weights(self, flat):
         flat = np.ascontiguousarray(flat, dtype=np.float32).ravel()
@@ -600,6 +619,19 @@ class Stack(_Owned):
         if rec is None or not (np.array_equal(rec[0], d) and np.array_equal(rec[1], w)):
             self.set_likelihood(d, w)
             self.lk_record = (d.copy(), w.copy())
+
+    def use_nuisance(self, basis):
+        """set_nuisance(basis) (None: no nuisance modes), uploaded only when it changed; kept on the host as `nu_record`.
+        After use_likelihood: the library re-whitens the basis it holds whenever the record changes."""
+        rec = self.nu_record
+        if basis is None:
+            if rec is not None or self.nuisance_modes():
+                self.set_nuisance(None)
+            return
+        basis = np.asarray(basis, np.float64)
+        if rec is None or not np.array_equal(rec, basis):
+            self.set_nuisance(basis)
+            self.nu_record = basis.copy()
 
     def has_fused(self, precision="f32"):
         y = C.c_int(0)
@@ -656,6 +688,7 @@ class Stack(_Owned):
         """Gaussian likelihood record: data d and inverse variances 1 / sigma^2 per output bin (copied; None clears)."""
         self.lk_record = None
         if data is None:
+            self.nu_record = None  # (the library clears both records)
             check(self.lib.v21_mlp_set_likelihood(self.h, None, None, 0))
             return
         d = np.ascontiguousarray(data, dtype=np.float32).ravel()
@@ -664,8 +697,38 @@ class Stack(_Owned):
             raise ValueError("likelihood: expected %d bins, got %d / %d" % (self.dims[-1], d.size, w.size))
         check(self.lib.v21_mlp_set_likelihood(self.h, _fptr(d), _fptr(w), d.size))
 
+    def set_nuisance(self, basis):
+        """Linear nuisance modes with a flat prior, integrated out of every likelihood quantity of this stack (include/v21.h:
+        v21_mlp_set_nuisance): basis (K, out) float64, 1 <= K <= 8 (copied; None clears).  Needs a likelihood record."""
+        self.nu_record = None
+        if basis is None:
+            check(self.lib.v21_mlp_set_nuisance(self.h, None, 0, 0))
+            return
+        A = np.ascontiguousarray(basis, dtype=np.float64)
+        if A.ndim != 2 or A.shape[1] != self.dims[-1]:
+            raise ValueError("nuisance: basis must be (K, %d), got %r" % (self.dims[-1], np.shape(basis)))
+        check(self.lib.v21_mlp_set_nuisance(self.h, A.ctypes.data_as(C.POINTER(C.c_double)), A.shape[0], A.shape[1]))
+
+    def nuisance_modes(self):
+        """the number of nuisance modes the library holds for this stack (0: none)"""
+        k = C.c_int32(0)
+        check(self.lib.v21_mlp_nuisance_info(self.h, C.byref(k)))
+        return k.value
+
+    def nuisance_coef(self, x, precision="f32", flags=0):
+        """host (n, in) -> (n, K) float64: the best-fit amplitudes of the nuisance modes for the record's raw data at every
+        row (include/v21.h: v21_mlp_nuisance_coef)."""
+        x, dt = self._rows(x)
+        K = self.nuisance_modes()
+        coef = np.empty((x.shape[0], max(K, 1)), np.float64)
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_nuisance_coef(self.h, x.ctypes.data_as(_P), dt, x.shape[0], coef.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 precision_id(precision), flags))
+        return coef
+
     def loglike(self, x, precision="f32", flags=0, grad=True):
-        """host (n, in) -> lnl (n,) [, grad (n, in)]: ln L = -1/2 sum w (d - out)^2 of the record set_likelihood left."""
+        """host (n, in) -> lnl (n,) [, grad (n, in)]: ln L = -1/2 sum w (d - out)^2 of the record set_likelihood left (with
+        nuisance modes set: marginalised over them, as are fisher, fit and sample)."""
         x, dt = self._rows(x)
         n = x.shape[0]
         lnl = np.empty(n, np.float32)

@@ -11,6 +11,7 @@
 // (row0 + n) / rpd of pitch ld_data (api_internal.h: the sampler's evaluations are this call too)
 int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, const float* d_data, long long ld_data,
                       long long rpd, long long row0, int prec, int flags) {
+  if (m->nu_k) return marg_run(m, route, n, d_F, d_lnl, d_grad, nullptr, d_data, ld_data, rpd, row0, prec, flags);
   const int din = m->dims[0], dout = m->dims[m->L];
   auto kern = din <= kFitMaxIn ? jac_fisher_kernel<kFitMaxIn> : jac_fisher_kernel<kFisherMaxIn>;
   return jac_slices(m, route, n, d_lnl || d_grad, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {
@@ -72,7 +73,7 @@ static int fit_run(v21_mlp* m, int route, long long n, const float* d_data, long
   HIPCHK(hipGetLastError());
   if (!d_F) return V21_OK;
   CHK(jac_prep(m, x_hat, x_dtype, din, n, 1));
-  return fisher_run(m, route, n, d_F, nullptr, nullptr, m->lk_data.get(), 0, 1, 0, prec, flags | V21_FWD_IN_TRANSFORM);
+  return fisher_run(m, route, n, d_F, nullptr, nullptr, m->lk_read(), 0, 1, 0, prec, flags | V21_FWD_IN_TRANSFORM);
 }
 
 // has_data: a data matrix of n_data rows was handed in (at least one, dividing n); without one n_data is ignored
@@ -99,7 +100,7 @@ extern "C" int v21_mlp_fisher_dev(v21_mlp* m, const float* d_x, int64_t ldx, int
   CHK(jac_args(m, d_x && d_fisher, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFisher));
   if (n == 0) return V21_OK;
   CHK(jac_prep(m, d_x, V21_DTYPE_F32, ldx, n, flags & V21_FWD_IN_TRANSFORM));
-  return fisher_run(m, jac_route(m, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, m->lk_data.get(), 0, 1, 0, precision,
+  return fisher_run(m, jac_route(m, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, m->lk_read(), 0, 1, 0, precision,
                     flags);
 }
 
@@ -113,7 +114,7 @@ extern "C" int v21_mlp_fisher(v21_mlp* m, const void* x, int x_dtype, int64_t n,
   return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, din * din + din + 3, [&](long long r0, long long rows, float* dF) {
     float* dl = lnl ? dF + rows * din * din : nullptr;
     float* dg = grad ? dF + rows * (din * din + 1) : nullptr;
-    CHK(fisher_run(m, route, rows, dF, dl, dg, m->lk_data.get(), 0, 1, 0, precision, flags));
+    CHK(fisher_run(m, route, rows, dF, dl, dg, m->lk_read(), 0, 1, 0, precision, flags));
     CHK(to_host(m, fisher + r0 * din * din, dF, (size_t)rows * din * din * sizeof(float)));
     if (lnl) CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
     return grad ? to_host(m, grad + r0 * din, dg, (size_t)rows * din * sizeof(float)) : V21_OK;
@@ -128,7 +129,8 @@ extern "C" int v21_mlp_fit_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64
   CHK(jac_args(m, d_x0 && d_x_hat && d_lnl, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFit));
   CHK(fit_check(n, d_data != nullptr, n_data, o));
   if (n == 0) return V21_OK;
-  const float* data = d_data ? d_data : m->lk_data.get();
+  const float* data = m->lk_read();
+  if (d_data) CHK(nuis_project(m, d_data, n_data, &data));
   const long long ld = d_data ? m->dims[m->L] : 0, rpd = d_data ? n / n_data : 1;
   const int route = fit_route(m, flags, d_fisher != nullptr);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
@@ -146,7 +148,8 @@ extern "C" int v21_mlp_fit(v21_mlp* m, const void* x0, int x_dtype, int64_t n, c
     CHK(m->fdata.reserve((size_t)n_data * dout));
     HIPCHK(hipMemcpyAsync(m->fdata.p, data, (size_t)n_data * dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
   }
-  const float* d_data = data ? m->fdata.get() : m->lk_data.get();
+  const float* d_data = m->lk_read();
+  if (data) CHK(nuis_project(m, m->fdata.get(), n_data, &d_data));
   const long long ld = data ? dout : 0, rpd = data ? n / n_data : 1;
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   const int route = fit_route(m, flags, fisher != nullptr);

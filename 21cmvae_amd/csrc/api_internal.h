@@ -159,6 +159,13 @@ struct ChainLayout {
   void layer(AdamLayer& a, int l) const { a.fw_off = fw_off[l]; a.bw_off = bw_off[l]; a.KS = frags(a.K); a.NS = frags(a.N); }
 };
 
+// ---- a nuisance record as the host builds it (api_nuisance.hip): Q (K, out) and R (K, K) of v21_nuisance_whiten, Q W d of
+// the record's raw data (K), and what the device holds: Q in float32 and the projected data d - Q^T (Q W d)
+struct NuisRecord {
+  std::vector<double> q, r, cd;
+  std::vector<float> qf, proj;
+};
+
 // ---- dense stack (api_forward.hip)
 struct v21_mlp {
   v21_ctx* ctx = nullptr;
@@ -215,6 +222,18 @@ struct v21_mlp {
   Dev<SampleRow> smp;    // chain state of a sample call (sample_kernels.h; its evaluations land in fF / fl / fg)
   Dev<double> smp_out;   // the host form's chunk: its results, and its per-chain start step sizes
   bool has_lk = false;
+  // linear nuisance modes marginalised in those reductions (api_nuisance.hip): nu_k modes (0: none), the float64 basis
+  // as it was handed in, the record built from it, and the host copy of the likelihood record both are re-whitened from.
+  // On the device: Q in float32 (the reductions) and float64 (nuis_project_kernel), the record's projected data BESIDE
+  // the raw data, and the projected rows of a fit or sample call's data matrix.
+  int nu_k = 0;
+  std::vector<double> nu_basis;
+  NuisRecord nu;
+  std::vector<float> lk_h_data, lk_h_w;
+  Dev<float> nu_qf, lk_proj, nu_ws;
+  Dev<double> nu_qd;
+  // the data the record's reductions read
+  const float* lk_read() const { return nu_k ? lk_proj.get() : lk_data.get(); }
   int last_jac_route = 0;
   long long jac_route_count[4] = {0, 0, 0, 0};
 };
@@ -257,6 +276,15 @@ int jac_slices(v21_mlp* m, int route, long long n, bool want_y, int prec, int fl
 // row n of the call reads data row (row0 + n) / rpd of pitch ld_data
 int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, const float* d_data, long long ld_data,
                long long rpd, long long row0, int prec, int flags);
+// api_nuisance.hip: the record of `k` modes from the host copies of basis, weights and data (no device work; V21_ERR_ARG as
+// v21_nuisance_whiten) and its upload (synchronises); with a nuisance record, the reductions of fisher_run / the
+// log-likelihood entries (d_F nullable; d_b: the (n, k) sums b, nullable) and the rows of a caller's (n_data, out_dim)
+// data matrix projected into m->nu_ws (*out: those, or d_data itself without a nuisance record)
+int nuis_build(const double* basis, const float* w, const float* d, int k, int dout, NuisRecord& rec);
+int nuis_upload(v21_mlp* m, const NuisRecord& rec);
+int marg_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, float* d_b, const float* d_data,
+             long long ld_data, long long rpd, long long row0, int prec, int flags);
+int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float** out);
 // a host form's rows, chunk by chunk: upload (m->hin) and prep them, run(r0, rows, out) on the chunk (out: m->hout of
 // out_floats per row, and never fewer than a Jacobian row's y and jac, so that no host form regrows what another left),
 // then sync

@@ -51,18 +51,27 @@ extern "C" int v21_mlp_last_jac_route(v21_mlp* m, int* route, long long counts[4
 
 extern "C" int v21_mlp_set_likelihood(v21_mlp* m, const float* data, const float* inv_var, int32_t n) {
   if (!m) return fail(V21_ERR_ARG, "null mlp");
-  if (!data || !inv_var) { m->has_lk = false; return V21_OK; }
+  if (!data || !inv_var) { m->has_lk = false; m->nu_k = 0; return V21_OK; }
   const int dout = m->dims[m->L];
   if (n != dout) return fail(V21_ERR_ARG, "likelihood: %d bins, stack output = %d", (int)n, dout);
   for (int k = 0; k < n; ++k)
     if (!(inv_var[k] >= 0.f) || !std::isfinite(inv_var[k])) return fail(V21_ERR_ARG, "likelihood: inv_var[%d] = %g", k, (double)inv_var[k]);
+  // (a nuisance record is re-whitened with the new weights first: a basis they make rank-deficient changes nothing)
+  NuisRecord rec;
+  if (m->nu_k) CHK(nuis_build(m->nu_basis.data(), inv_var, data, m->nu_k, dout, rec));
   CHK(use(m->ctx));
   CHK(m->lk_data.reserve((size_t)dout));
   CHK(m->lk_w.reserve((size_t)dout));
   HIPCHK(hipMemcpyAsync(m->lk_data.p, data, (size_t)dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
   HIPCHK(hipMemcpyAsync(m->lk_w.p, inv_var, (size_t)dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
   HIPCHK(hipStreamSynchronize(m->ctx->stream));
+  m->lk_h_data.assign(data, data + dout);
+  m->lk_h_w.assign(inv_var, inv_var + dout);
   m->has_lk = true;
+  if (m->nu_k) {
+    CHK(nuis_upload(m, rec));
+    m->nu = std::move(rec);
+  }
   return V21_OK;
 }
 
@@ -192,9 +201,11 @@ int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, lon
   return V21_OK;
 }
 
-// lnl / grad (nullable) of the n prepped rows: the fused route reduces its Jacobian slice by slice (jac_loglike_kernel),
+// lnl / grad (nullable) of the n prepped rows; with a nuisance record both routes reduce their Jacobian slice by slice
+// with jac_marg_kernel (api_nuisance.hip), without one the fused route reduces its Jacobian slice by slice (jac_loglike_kernel),
 // the generic kernel reduces in its likelihood mode
 static int loglike_run(v21_mlp* m, int route, long long n, float* d_lnl, float* d_grad, int prec, int flags) {
+  if (m->nu_k) return marg_run(m, route, n, nullptr, d_lnl, d_grad, nullptr, m->lk_proj.get(), 0, 1, 0, prec, flags);
   if (route != JAC_FUSED) return jac_run(m, route, 0, n, nullptr, m->dims[m->L], nullptr, d_lnl, d_grad, prec, flags);
   const int din = m->dims[0], dout = m->dims[m->L];
   return jac_slices(m, route, n, true, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {

@@ -85,7 +85,8 @@ extern "C" int v21_mlp_sample_dev(v21_mlp* m, const float* d_x0, int64_t ldx, in
   CHK(jac_args(m, d_x0 && out && out->x_last, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kSample));
   CHK(sample_check(n, d_data != nullptr, n_data, o));
   if (n == 0) return V21_OK;
-  const float* data = d_data ? d_data : m->lk_data.get();
+  const float* data = m->lk_read();
+  if (d_data) CHK(nuis_project(m, d_data, n_data, &data));
   const long long ld = d_data ? m->dims[m->L] : 0, rpd = d_data ? n / n_data : 1;
   const int route = jac_route(m, flags, m->dims[m->L]);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
@@ -104,7 +105,8 @@ extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n
     CHK(m->fdata.reserve((size_t)n_data * dout));
     HIPCHK(hipMemcpyAsync(m->fdata.p, data, (size_t)n_data * dout * sizeof(float), hipMemcpyHostToDevice, st));
   }
-  const float* d_data = data ? m->fdata.get() : m->lk_data.get();
+  const float* d_data = m->lk_read();
+  if (data) CHK(nuis_project(m, m->fdata.get(), n_data, &d_data));
   const long long ld = data ? dout : 0, rpd = data ? n / n_data : 1;
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   const long long keep = sample_keep(o);

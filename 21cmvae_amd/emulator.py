@@ -12,7 +12,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _native as nat, engine, preprocess as pp
+from . import _native as nat, engine, foregrounds as fg, preprocess as pp
 from .callbacks import TqdmCallback
 from .engine import ChainedModel, Dense, GaussianLatent, Input, Model, Sequential, sequential_from_arrays
 from .losses import mean_squared_error, relative_mse_loss  # noqa: F401  (public, as in the reference)
@@ -192,6 +192,23 @@ def r_hat_from_moments(mean_c, cov_c, n):
         return np.sqrt(((n - 1.0) / n * W + B_over_n) / W)
 
 
+def foreground_basis(frequencies, nb, foreground, flow, fhigh):
+    """The (K, nb) float64 nuisance basis ``foreground=`` stands for: None -> None (no marginalisation); an int -> that many
+    LinLog terms (foregrounds.linlog_basis) over the bins of the band [flow, fhigh], zero outside; a (K, nb) array -> itself."""
+    if foreground is None:
+        return None
+    if isinstance(foreground, (int, np.integer)) and not isinstance(foreground, bool):
+        if frequencies is None:
+            raise ValueError("No frequency array is given, cannot select a frequency band.")
+        if not 1 <= int(foreground) <= 8:
+            raise ValueError("foreground: %d terms (1 .. 8)" % int(foreground))
+        return fg.band_basis(frequencies, int(foreground), flow, fhigh)
+    A = np.array(foreground, np.float64, ndmin=2)
+    if A.ndim != 2 or A.shape[1] != nb or not 1 <= A.shape[0] <= 8:
+        raise ValueError("foreground must be None, a number of LinLog terms or a (K, %d) basis with K <= 8, got %r" % (nb, np.shape(foreground)))
+    return A
+
+
 class _EmulatorBase:
     par_labels = ["fstar", "Vc", "fx", "tau", "alpha", "nu_min", "Rmfp"]
 
@@ -268,22 +285,50 @@ class _EmulatorBase:
             y, J = y[0], J[0]
         return (y, J) if return_signal else J
 
-    def log_likelihood(self, params, data, sigma, flow=None, fhigh=None, grad=False):
+    def log_likelihood(self, params, data, sigma, flow=None, fhigh=None, grad=False, foreground=None):
         """Gaussian ln L = -1/2 sum_k (data_k - signal_k)^2 / sigma_k^2 over the bins of the band [flow, fhigh] of
         ``self.frequencies`` (as ``error`` selects them; bins outside get weight 0), and with grad=True its gradient
         with respect to the raw parameters -- both reduced on the device (not in the reference).  ``sigma``: a scalar or
         one value per bin, mK.  One value (and a (7,) gradient) for a parameter vector, (N,) (and (N, 7)) for N.  The
-        data / sigma record is kept on the device per stack: a sampler's repeated call uploads only its parameters."""
+        data / sigma record is kept on the device per stack: a sampler's repeated call uploads only its parameters.
+        ``foreground`` (here and in ``fisher``, ``fit_parameters``, ``sample_posterior``): None, or linear foreground modes
+        whose amplitudes get a flat prior and are integrated out analytically on the device (include/v21.h:
+        v21_mlp_set_nuisance) -- an int K for K LinLog terms (``foregrounds.linlog_basis``) over the selected band, or
+        any (K, 451) basis, K <= 8.  ln L is then the profile likelihood over the amplitudes, unchanged by adding any
+        combination of the modes to ``data``, which may carry the full foreground (10^6 mK and more) in float32."""
         model, st, flags, x = self._diff_stack(params)
         nb = st.dims[-1]
         d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
         w = self._band_weights(nb, sigma, flow, fhigh)
-        st.use_likelihood(d, w)
+        self._use_record(st, d, w, foreground, flow, fhigh)
         out = st.loglike(x, model.precision, flags, grad=grad)
         if grad:
             lnl, g = out
             return (lnl[0], g[0]) if x.shape[0] == 1 else (lnl, g)
         return out[0] if x.shape[0] == 1 else out
+
+    def _use_record(self, st, d, w, foreground, flow, fhigh):
+        """the likelihood record (d, w) and the nuisance basis of ``foreground`` (None: none) on the stack"""
+        A = foreground_basis(self.frequencies, st.dims[-1], foreground, flow, fhigh)
+        if A is None or st.nu_record is None or not np.array_equal(st.nu_record, A):
+            st.use_nuisance(None)  # (before the record: the new weights need not suit the basis the stack still holds)
+        st.use_likelihood(d, w)
+        st.use_nuisance(A)
+
+    def foreground_amplitudes(self, params, data, sigma, foreground, flow=None, fhigh=None):
+        """Best-fit amplitudes of the foreground modes for ``data`` at ``params`` (the maximum over the amplitudes that
+        ``log_likelihood(..., foreground=)`` profiles out): ``(a_hat, foreground_model)`` in float64, a_hat (K,) and the
+        model a_hat @ basis (451,) in mK for one parameter vector, (N, K) and (N, 451) for N."""
+        model, st, flags, x = self._diff_stack(params)
+        nb = st.dims[-1]
+        A = foreground_basis(self.frequencies, nb, foreground, flow, fhigh)
+        if A is None:
+            raise ValueError("foreground_amplitudes needs a foreground")
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
+        self._use_record(st, d, self._band_weights(nb, sigma, flow, fhigh), A, flow, fhigh)
+        a = st.nuisance_coef(x, model.precision, flags)
+        fgm = a @ A
+        return (a[0], fgm[0]) if x.shape[0] == 1 else (a, fgm)
 
     def _band_weights(self, nb, sigma, flow, fhigh):
         """float32 1 / sigma^2 per bin, 0 outside the band [flow, fhigh] of ``self.frequencies`` (as ``error`` selects it)"""
@@ -301,7 +346,7 @@ class _EmulatorBase:
             w = np.where(sel, w, np.float32(0))
         return w
 
-    def fisher(self, params, sigma, flow=None, fhigh=None):
+    def fisher(self, params, sigma, flow=None, fhigh=None, foreground=None):
         """Fisher matrix F = J^T diag(1 / sigma^2) J of the signal at ``params`` in raw parameter units (not in the
         reference), over the bins of the band [flow, fhigh] as ``log_likelihood`` selects them; computed and reduced on
         the device.  (7, 7) for one parameter vector, (N, 7, 7) for N.  Its inverse is the Gaussian forecast covariance."""
@@ -309,12 +354,12 @@ class _EmulatorBase:
         nb = st.dims[-1]
         w = self._band_weights(nb, sigma, flow, fhigh)
         d = st.lk_record[0] if st.lk_record is not None else np.zeros(nb, np.float32)  # (the data are not read: keep the record's)
-        st.use_likelihood(d, w)
+        self._use_record(st, d, w, foreground, flow, fhigh)
         F = st.fisher(x, model.precision, flags)
         return F[0] if x.shape[0] == 1 else F
 
     def fit_parameters(self, data, sigma, p0=None, n_starts=8, max_iter=50, flow=None, fhigh=None, seed=0, return_all=False,
-                       return_fisher=False):
+                       return_fisher=False, foreground=None):
         """Maximum-likelihood parameters of observed signal(s) (not in the reference): a projected Levenberg-Marquardt fit
         per (spectrum, start) on the device, inside the training box, of the Gaussian ln L of ``log_likelihood``.
         ``data``: (451,) or (M, 451) mK.  Starts: ``p0`` ((7,) or (S, 7) raw parameters, the same for every spectrum), or
@@ -344,7 +389,7 @@ class _EmulatorBase:
                 raise ValueError("p0 must be (%d,) or (S, %d), got %r" % (din, din, np.shape(p0)))
         M, S = dat.shape[0], starts.shape[0]
         w = self._band_weights(nb, sigma, flow, fhigh)
-        st.use_likelihood(dat[0], w)
+        self._use_record(st, dat[0], w, foreground, flow, fhigh)
         x0 = np.ascontiguousarray(np.tile(starts, (M, 1)))
         r = st.fit(x0, model.precision, flags, data=dat, max_iter=max_iter, fisher=return_fisher)
         xh = r["x_hat"].reshape(M, S, din)
@@ -362,7 +407,7 @@ class _EmulatorBase:
         return FitResult(xh, lnl, status, F)
 
     def sample_posterior(self, data, sigma, n_chains=64, n_steps=1000, n_warmup=200, thin=1, p0=None, flow=None, fhigh=None, seed=0,
-                         eps=None, return_lnl=False):
+                         eps=None, return_lnl=False, foreground=None):
         """Posterior samples of the parameters given observed signal(s) (not in the reference): ``n_chains`` independent
         Markov chains per spectrum, run entirely on the device -- a Metropolis-adjusted Langevin sampler preconditioned
         with the Fisher matrix at the current point (include/v21.h: v21_mlp_sample) -- of the Gaussian ln L of
@@ -391,7 +436,7 @@ class _EmulatorBase:
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
         if p0 is None:
-            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed).params, np.float64, ndmin=2)
+            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
             u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], C, axis=1)
         else:
             starts = np.array(p0, np.float64, ndmin=2)
@@ -401,7 +446,7 @@ class _EmulatorBase:
         rng = np.random.default_rng(seed)
         u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=(M, C, din)), -1.0, 1.0)
         x0 = np.ascontiguousarray(pp.par_untransform(u0.reshape(M * C, din), self.par_train))
-        st.use_likelihood(dat[0], self._band_weights(nb, sigma, flow, fhigh))
+        self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
         r = st.sample(x0, model.precision, flags, data=dat, **opts)
         K = r["samples"].shape[1] if "samples" in r else 0
         params = r["samples"].reshape(M, C, K, din) if K else None

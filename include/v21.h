@@ -266,6 +266,36 @@ int v21_mlp_sample(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const f
 int v21_mlp_sample_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
                        const v21_sample_opts* opts, const double* d_eps_start, const v21_sample_out* out, int precision, int flags);
 
+/* ---- linear nuisance modes (foregrounds) integrated out of the likelihood record.  Data model: d = y(x) + A^T a + noise,
+ * A the (n_modes, out_dim) basis, 1 <= n_modes <= 8, with a FLAT PRIOR on the amplitudes a, which are integrated out
+ * analytically.  With W = diag(w) the record's inverse variances, Q the W-orthonormalised basis (span Q = span A on the
+ * bins with w > 0, Q W Q^T = I), r = d - y, b = Q W r (n_modes values) and B = Q W J^T (n_modes x in_dim), J = jac:
+ *     lnL_m = -1/2 (r^T W r - |b|^2)      g_m = J W r - B^T b      F_m = J W J^T - B^T B
+ * (constants that do not depend on x dropped, as in v21_mlp_loglike).  lnL_m is the profile likelihood
+ * max_a lnL(d - A^T a), and it does not change when any A^T a is added to d.
+ *   v21_nuisance_whiten  Q (n_modes, out_dim) and R (n_modes, n_modes, upper triangular, row-major) in float64 with
+ *     sqrt(W) A^T = (sqrt(W) Q^T) R, by modified Gram-Schmidt applied twice to the column-normalised weighted basis;
+ *     Q is zero where w == 0.  V21_ERR_ARG: n_modes outside 1 .. 8, a diagonal of R below 1e-10 of its mode's norm
+ *     (a rank-deficient basis), fewer than n_modes + 1 bins with w > 0.  Pure host arithmetic: no context, no GPU.
+ *   v21_mlp_set_nuisance  attaches the basis (float64, copied; NULL clears) to the likelihood record (required:
+ *     V21_ERR_STATE without one; V21_ERR_ARG as v21_nuisance_whiten, the handle then keeps what it had).  From then on
+ *     v21_mlp_loglike, v21_mlp_fisher, v21_mlp_fit and v21_mlp_sample (and their _dev forms) compute lnL_m, g_m and F_m
+ *     in place of lnL, its gradient and J W J^T; F_m stays exactly symmetric.  The handle keeps the basis, Q, R and,
+ *     beside the raw data, the projected data d - Q^T (Q W d) (float64, rounded to float32 once) that the reductions
+ *     read: W - W Q^T Q W annihilates A, and float32 sums then see residuals of the signal's size.  A data matrix of a
+ *     fit or sample call is projected the same way on the device, once per call.  A later v21_mlp_set_likelihood
+ *     re-whitens with its weights (V21_ERR_ARG, nothing changed, if they make the basis rank-deficient); with NULL it
+ *     clears both records.  Without a nuisance record every entry launches what it launched before.  in_dim <= 15
+ *     (V21_ERR_UNSUPPORTED otherwise, v21_mlp_loglike included).
+ *   v21_mlp_nuisance_info  n_modes of the handle's nuisance record, 0 without one.
+ *   v21_mlp_nuisance_coef  the best-fit amplitudes of the record's raw data at every row, coef[n, :] = a_hat(x_n) =
+ *     R^-1 (Q W (d_raw - y(x_n))), (n, n_modes) float64; Q W y is reduced on the device in float32, the rest is float64
+ *     on the host.  V21_ERR_STATE without a nuisance record. */
+int v21_nuisance_whiten(const double* basis, const float* inv_var, int32_t n_modes, int32_t out_dim, double* q, double* r);
+int v21_mlp_set_nuisance(v21_mlp* mlp, const double* basis, int32_t n_modes, int32_t out_dim);
+int v21_mlp_nuisance_info(v21_mlp* mlp, int32_t* n_modes);
+int v21_mlp_nuisance_coef(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, double* coef, int precision, int flags);
+
 /* ---- trainer: replaces Model.compile + Model.fit (emulator.py:369-378, :739-747,
  * :756-764; optimizer/loss from notebooks/Training.ipynb cells 4 and 10). ------- */
 typedef struct {
