@@ -32,6 +32,9 @@ One thing differs between routes, the ReLU decision the backward pass uses (`mas
                packed pair, so a pre-activation that underflows to +0 passes no gradient).
 route_model() names the model of each training route.
 
+jvp() is the forward-mode pass of the fused 16-bit Jacobian (csrc/fused_jac.h), rounded where that kernel rounds -- its
+own section below lists the sites -- with JAC_MUTATIONS the catalogue of its tangents (tests/test_jac16_*.py).
+
 `acc="f32"` is the DEVICE MODEL the CPU self-tests use: the same computation with numpy's f32 accumulation standing in
 for the kernels' summation order.  MUTATIONS is the catalogue of plausible kernel mistakes the new checks must refuse;
 the CPU tests apply it to the device model, the GPU tests to the device's own returned arrays (apply_* below: the
@@ -202,6 +205,133 @@ def masks16(Ws, bs, act, xt, prec, with_z=False):
     _, _, zs = forward(Ws, bs, act, xt, prec, keep=True)
     out = [z > 0 if a == RELU else None for z, a in zip(zs, act)]
     return (out, zs) if with_z else out
+
+
+# ---- forward-mode tangents: the fused 16-bit Jacobian (csrc/fused_jac.h) --------------------------------------
+# Where fused_jac<Arch, Prec> rounds (read off the kernel):
+#   * layer-0 operand: the primal column holds the transformed f32 row rounded to 16 bits (P::pack2, fused_jac.h:97-108);
+#     the tangent columns are exact unit vectors, so the layer-0 tangents are rows of round16(W0), exact in f32;
+#   * weights: round16(W) of the forward's packed stream; the f32 bias is the accumulator's initial value on the primal
+#     columns only (:245), products are summed in f32 (MFMA);
+#   * hidden layers: the ReLU decision is z > 0 on the PRIMAL's f32 sum (:145-148) and masks primal and tangents alike;
+#     then primal AND tangents are rounded to 16 bits by P::pack2 (:150-151) -- a linear hidden layer (S3's 224 -> 9)
+#     included;
+#   * output layer: nothing is rounded; tangents are multiplied by out_std (the f32 the handle holds) and then by the f32
+#     chain-rule factor of the input transform (:176-179); y takes the forward's epilogue (half_ref.forward).
+# The mutation catalogue of the tangents, in the scheme of MUTATIONS: the mistake is made inside the reference and the
+# difference it makes is added to the device's own J (apply_jac_mutation).  jac_mutation_site() fixes the layer.
+JAC_MUTATIONS = {
+    "tan_rtz": ("f16", "bf16"),          # the middle hidden layer's tangents rounded toward zero, not to nearest
+    "tan_tile": ("f16", "bf16"),         # its units 16..31, last input's tangent only, scaled by 1 + 2^-8 before rounding
+    "fac16": ("f16", "bf16"),            # the chain-rule factor rounded to 16 bits before the output multiply (needs fac)
+    "out_tile": ("f16", "bf16"),         # bins 32..63 of the last input's Jacobian row scaled by 1 + 2^-8 (the epilogue)
+    "prim_unrounded": ("f16", "bf16"),   # the layer-0 primal operand left in f32: moves the masks and y
+}
+# What the Jacobian's median check is NOT asked to refuse, and why (tests/test_jac16_cpu.py holds the numbers):
+#   prim_unrounded -- it changes the PRIMAL: y moves by ~1e-5 / 1e-4 of its scale (f16 / bf16) in the median row, which the
+#             primal's bit-identity with fused_fwd (tests/test_jacobian_gpu.py) and the forward's own rounding check
+#             (tests/test_half_ref_gpu.py) refuse outright.  On J it acts only through the ReLU units the moved primal
+#             switches: whole rows at a time, none in most rows of most cells -- the per-cell MEDIAN of a stack is 0 or
+#             far below 16x the device model (the CPU module asserts which), so the entry is kept for the primal and left
+#             out of jac_mutations().
+JAC_CHECK_SKIPS = ("prim_unrounded",)
+
+
+def jac_mutation_site(act):
+    """the hidden layer the tangent entries edit: the middle hidden ReLU layer (mutation_site's rule).  Never layer 0 on
+    a stack with two or more hidden ReLU layers -- layer 0's tangents are rows of round16(W0), which no rounding moves."""
+    return mutation_site(act, 0)[0]
+
+
+def jac_mutations(prec, with_fac, act=None):
+    """names of JAC_MUTATIONS the Jacobian's median check must refuse for a call: fac16 only with an input transform (a
+    factor of 1 rounds to 1), the hidden-layer entries only on a stack with a hidden ReLU layer above layer 0"""
+    no_site = act is not None and not jac_mutation_site(act)
+    return [m for m, precs in JAC_MUTATIONS.items() if prec in precs and m not in JAC_CHECK_SKIPS
+            and (with_fac or m != "fac16") and not (no_site and m in ("tan_rtz", "tan_tile"))]
+
+
+def jvp(Ws, bs, act, xt, prec, acc="f64", flips=None, masks=None, fac=None, std=None, mut=None):
+    """(y (n, out), J (n, in, out) = d y / d xt, pre-activations per layer) of rows xt (after par_transform), rounded
+    where fused_jac rounds (above): acc "f64" sums exactly (the reference), "f32" is the CPU device model.  prec None:
+    jacobian_ref.jvp bit for bit.  flips / masks as in jacobian_ref.jvp.  fac (n, in), std: the output layer's tangents
+    times std times fac (the kernel's order), both as the kernel holds them (f32 values); y stays in the network's units.
+    mut: an entry of JAC_MUTATIONS."""
+    h = np.asarray(xt, np.float64)
+    if prec is not None and mut != "prim_unrounded":
+        h = round16(np.asarray(xt, np.float32).astype(np.float64), prec)
+    elif prec is not None:
+        h = np.asarray(xt, np.float32).astype(np.float64)
+    n, din = h.shape
+    T = np.repeat(np.eye(din)[None], n, axis=0)
+    zs = []
+    L = len(act)
+    site = jac_mutation_site(act) if mut in ("tan_rtz", "tan_tile") else None
+    for l, ((W, b), a) in enumerate(zip(_layer_params(Ws, bs, act), act)):
+        Wr = round16(W, prec)
+        z = _mm(h, Wr, acc) + b
+        Tz = _mm(T, Wr, acc)
+        if acc == "f32":
+            z = z.astype(np.float32).astype(np.float64)
+        zs.append(z)
+        if a == RELU:
+            m = z > 0 if masks is None else masks[l]
+            if flips is not None and flips[l] is not None:
+                m = m ^ flips[l]
+            h = np.where(m, z, 0.0)
+            T = Tz * m[:, None, :]
+        else:
+            h, T = z, Tz
+        if l < L - 1:
+            if mut == "tan_tile" and l == site:
+                T = T.copy()
+                T[:, din - 1, 16:32] *= 1 + 2.0 ** -8
+            h = round16(h, prec)
+            T = round16_toward_zero(T, prec) if (mut == "tan_rtz" and l == site) else round16(T, prec)
+    if std is not None:
+        T = T * float(std)
+    if fac is not None:
+        f = np.asarray(fac, np.float64)
+        T = T * (round16(f, prec) if mut == "fac16" else f)[:, :, None]
+    if mut == "out_tile":
+        T = T.copy()
+        T[:, din - 1, 32:64] *= 1 + 2.0 ** -8
+    return h, T, zs
+
+
+def apply_jac_mutation(name, J, Ws, bs, act, xt, prec, fac=None, std=None, Jref=None):
+    """J (a device result of rows xt) edited as if fused_jac made mistake `name`: J + (reference with it - without it)"""
+    if Jref is None:
+        Jref = jvp(Ws, bs, act, xt, prec, fac=fac, std=std)[1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.asarray(J, np.float64) + (jvp(Ws, bs, act, xt, prec, fac=fac, std=std, mut=name)[1] - Jref)
+
+
+def jac_cell_errors(J, Jref, tile=32):
+    """(n, in, ceil(out / tile)): ||J - Jref||_2 / ||Jref||_2 over the bins of every (row, input, 32-bin output tile)
+    cell; a cell that is not finite counts as infinitely wrong"""
+    J, Jref = np.asarray(J, np.float64), np.asarray(Jref, np.float64)
+    n, din, dout = Jref.shape
+    nt = -(-dout // tile)
+    pad = nt * tile - dout
+    with np.errstate(invalid="ignore", over="ignore"):
+        d2 = np.pad((J - Jref) ** 2, ((0, 0), (0, 0), (0, pad))).reshape(n, din, nt, tile).sum(-1)
+    r2 = np.pad(Jref ** 2, ((0, 0), (0, 0), (0, pad))).reshape(n, din, nt, tile).sum(-1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.sqrt(d2) / np.sqrt(np.maximum(r2, 1e-300))
+    return np.where(np.isfinite(e), e, np.inf)
+
+
+JAC_POOL_BELOW = 31   # rows: a median over fewer could be decided by one row with a unit at its kink
+
+
+def jac_worst_cell_median(J, Jref, tile=32):
+    """the Jacobian check's statistic: the median over rows of every cell's error, the worst cell of them; calls of fewer
+    than JAC_POOL_BELOW rows: the median of all the call's cell errors pooled"""
+    e = jac_cell_errors(J, Jref, tile)
+    if e.shape[0] < JAC_POOL_BELOW:
+        return float(np.median(e))
+    return float(np.median(e, axis=0).max())
 
 
 # ---- one optimizer step: loss and full gradient ---------------------------------------------------------------------------

@@ -160,6 +160,19 @@ HALF_STEP_TOL = {
 # pre-processed units.  Measured on the MI355X over every route and case of that module: f16 2.0e-8 / 2.2e-5 / 1.6e-4,
 # bf16 1.6e-8 / 2.8e-6 / 8.8e-4; bounds at most 4x those.
 FWD16_TOL = {"f16": (8e-8, 8e-5, 6e-4), "bf16": (6e-8, 1e-5, 3.5e-3)}
+# The fused 16-bit Jacobian against the rounding reference (tests/test_jac16_gpu.py; half_ref.jvp): the worst (input, 32-bin
+# output tile) cell's median over rows of ||dJ||_2 / ||J_ref||_2 (half_ref.jac_worst_cell_median).  Measured on the MI355X
+# over every case of that module (S1, S2, S3, S4; 1 .. 4,099 rows; with and without the transforms): f16 <= 1.86e-7 (S4, 31
+# rows), bf16 <= 8.56e-8 (S3, 31 rows); the f32-accumulation model on the CPU: 2.3e-7 / 8.0e-8.  Bounds at most 4x the
+# device's worst, and at most 1/4 of the least any catalogue entry makes on any case (f16 fac16 2.9e-4, bf16 tan_tile 1.0e-3).
+JAC16_TOL = {"f16": 7e-7, "bf16": 3.4e-7}
+# ln L, its gradient and F of the fused 16-bit route against the float64 reductions of the rounding reference's y and J:
+# medians over rows of |d ln L| / |ln L|, of |d g_j| over the sum of its terms' magnitudes (per input j, the worst input)
+# and of F's relative Frobenius error.  Measured (D1, S3, S4, 600 rows, and the marginalised D1 case): ln L f16 <= 5.2e-8,
+# bf16 <= 4.4e-8; g 4.2e-8 / 3.0e-8; F 5.8e-8 / 4.4e-8.  At most 4x those; tan_rtz / fac16 move g to >= 1.7e-5 / 1.3e-4
+# and F to >= 2.7e-4 / 2.0e-3.
+LNL16_TOL = {"f16": dict(lnl=2e-7, grad=1.6e-7), "bf16": dict(lnl=1.7e-7, grad=1.1e-7)}
+FISHER16_TOL = {"f16": 2.3e-7, "bf16": 1.7e-7}
 HALF_MUTATE_MAX_ROWS = 16384    # steps up to this size also show the mutation catalogue refused (float64 time on the host)
 
 

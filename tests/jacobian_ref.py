@@ -101,6 +101,41 @@ def jacobian(Ws, bs, act, x, tin=None, tout=None, flips=None, mask_prec=None):
     return y * std + mean, J * fac[:, :, None] * std
 
 
+def jvp16(Ws, bs, act, xt, prec, **kw):
+    """half_ref.jvp: the forward-mode pass that rounds where fused_jac rounds (prec None: jvp above, bit for bit)"""
+    return half_ref.jvp(Ws, bs, act, xt, prec, **kw)
+
+
+def operands16(x, tin=None, tout=None):
+    """what fused_jac is handed for raw rows x: (xt float32 -- the float64 transform rounded once, csrc/par_transform.h --,
+    fac as the float32 jac_prep_kernel stores, the float32 std of the output transform or None)"""
+    if tin is not None:
+        xt, fac = transform(x, *tin)
+        if np.asarray(x).dtype == np.float32:  # par_transform_f32: the log10 of a float32 row is a float32
+            lm, lo, span = np.asarray(tin[0], bool), np.asarray(tin[2], np.float64), np.asarray(tin[3], np.float64) - np.asarray(tin[2], np.float64)
+            t = np.asarray(x, np.float64).copy()
+            for j, zf in enumerate(tin[1]):
+                if zf > 0:
+                    t[np.asarray(x)[:, j] == 0, j] = float(np.float32(zf))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                q = np.where(lm, np.log10(np.where(lm, t, 1.0)).astype(np.float32).astype(np.float64), t)
+            xt = (q - lo) / span * 2 - 1
+    else:
+        xt, fac = np.asarray(x, np.float64), np.ones(np.shape(x))
+    std = None if tout is None else float(np.float32(tout[0]))
+    return xt.astype(np.float32), fac.astype(np.float32).astype(np.float64), std
+
+
+def jacobian16(Ws, bs, act, x, prec, tin=None, tout=None, acc="f64", mut=None):
+    """(y, J (n, in, out)) of raw rows x as fused_jac<., prec> forms them (half_ref.jvp), float64: tin / tout as in
+    jacobian; y as half_ref.forward forms it.  acc "f32": the CPU device model; mut: an entry of half_ref.JAC_MUTATIONS."""
+    xt, fac, std = operands16(x, tin, tout)
+    y, J, _ = half_ref.jvp(Ws, bs, act, xt, prec, acc=acc, fac=fac if tin is not None else None, std=std, mut=mut)
+    if tout is not None:
+        y = y * float(tout[0]) + np.asarray(tout[1], np.float64)
+    return y, J
+
+
 def loglike(y, jac, data, inv_var):
     """lnl (n,), grad (n, in) of ln L = -1/2 sum w (d - y)^2 from outputs and their Jacobian."""
     r = np.asarray(data, np.float64) - np.asarray(y, np.float64)
@@ -137,5 +172,5 @@ def rel_frobenius(got, ref):
     return np.sqrt(np.sum((got - ref) ** 2, axis=ax)) / np.maximum(np.sqrt(np.sum(ref ** 2, axis=ax)), 1e-300)
 
 
-__all__ = ["jvp", "masks16", "round16", "jacobian", "loglike", "transform", "forward", "oracle_outputs", "near_kinks", "rel_frobenius",
+__all__ = ["jvp", "jvp16", "operands16", "jacobian16", "masks16", "round16", "jacobian", "loglike", "transform", "forward", "oracle_outputs", "near_kinks", "rel_frobenius",
            "min_relative_preactivation", "ora"]
