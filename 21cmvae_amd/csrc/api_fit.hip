@@ -1,25 +1,30 @@
 // api_fit.hip -- Fisher matrices and batched maximum-likelihood fits (include/v21.h: v21_mlp_fisher[_dev],
 // v21_mlp_fit[_dev]).  Both run the Jacobian kernels of api_jacobian.hip (fused_jac<Arch, Prec> or jac_generic_kernel,
-// Jacobian mode) into the likelihood workspace slice by slice, and reduce each slice there with jac_fisher_kernel
-// (fit_kernels.h): 4 din^2 (+ 4 (1 + din)) bytes per row leave the workspace.  A fit is a projected
+// Jacobian mode) into the likelihood workspace slice by slice, and reduce each slice there with jac_reduce_kernel
+// (reduce_run): 4 din^2 (+ 4 (1 + din)) bytes per row leave the workspace.  A fit is a projected
 // Levenberg-Marquardt iteration per row in the transformed coordinates u in [-1, 1]^din (fit_lm_kernel); the host
 // only launches, and reads one int (the running rows) every check_every iterations.
 #include "api_internal.h"
 #include "fit_kernels.h"
 
-// F (n, din, din), and lnl / grad (nullable) of the n prepped rows on `route`; row n of the call reads data row
-// (row0 + n) / rpd of pitch ld_data (api_internal.h: the sampler's evaluations are this call too)
-int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, const float* d_data, long long ld_data,
-                      long long rpd, long long row0, int prec, int flags) {
-  if (m->nu_k) return marg_run(m, route, n, d_F, d_lnl, d_grad, nullptr, d_data, ld_data, rpd, row0, prec, flags);
-  const int din = m->dims[0], dout = m->dims[m->L];
-  auto kern = din <= kFitMaxIn ? jac_fisher_kernel<kFitMaxIn> : jac_fisher_kernel<kFisherMaxIn>;
-  return jac_slices(m, route, n, d_lnl || d_grad, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, m->ctx->stream, wy, wj, d_data, ld_data, rpd, row0 + r0,
-                       m->lk_w.get(), d_F + r0 * din * din, d_lnl ? d_lnl + r0 : nullptr, d_grad ? d_grad + r0 * din : nullptr,
-                       rows, din, dout);
-    return V21_OK;
-  });
+int call_data_args(const char* what, long long n, bool has_data, long long n_data) {
+  if (has_data && (n_data < 1 || n % n_data != 0)) return fail(V21_ERR_ARG, "%s: n = %lld rows, n_data = %lld", what, n, n_data);
+  return V21_OK;
+}
+
+int call_data(v21_mlp* m, long long n, const float* data, bool on_host, long long n_data, CallData* out) {
+  *out = {m->lk_read(), 0, 1};
+  if (!data) return V21_OK;
+  const int dout = m->dims[m->L];
+  if (on_host) {
+    CHK(m->fdata.reserve((size_t)n_data * dout));
+    HIPCHK(hipMemcpyAsync(m->fdata.p, data, (size_t)n_data * dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
+    data = m->fdata.get();
+  }
+  CHK(nuis_project(m, data, n_data, &out->d));
+  out->ld = dout;
+  out->rpd = n / n_data;
+  return V21_OK;
 }
 
 static v21_fit_opts fit_defaults() {
@@ -35,9 +40,8 @@ static v21_fit_opts fit_defaults() {
 // lnl_start and status (both nullable) and, with d_F, the Fisher matrix at x_hat in raw units: the rows as they are
 // handed back, transformed as v21_mlp_fisher transforms them.  Evaluations run on u (no input transform, fac = 1) with
 // the caller's output transform.
-static int fit_run(v21_mlp* m, int route, long long n, const float* d_data, long long ld_data, long long rpd, long long row0,
-                   const v21_fit_opts& o, int prec, int flags, void* x_hat, int x_dtype, float* d_lnl, float* d_lnl0, int* d_status,
-                   float* d_F) {
+static int fit_run(v21_mlp* m, int route, long long n, const CallData& data, long long row0, const v21_fit_opts& o, int prec, int flags,
+                   void* x_hat, int x_dtype, float* d_lnl, float* d_lnl0, int* d_status, float* d_F) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0];
   CHK(m->fit.reserve((size_t)n));
@@ -53,7 +57,7 @@ static int fit_run(v21_mlp* m, int route, long long n, const float* d_data, long
   hipLaunchKernelGGL(fit_init_kernel, grid, dim3(256), 0, st, fs, m->jxt.get(), m->jfac.get(), n, din, o.lambda0);
   HIPCHK(hipGetLastError());
   for (int it = 0; it <= o.max_iter; ++it) {
-    CHK(fisher_run(m, route, n, F, l, g, d_data, ld_data, rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
+    CHK(reduce_run(m, route, n, F, l, g, nullptr, data.d, data.ld, data.rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
     hipLaunchKernelGGL(fit_lm_kernel, grid, dim3(256), 0, st, fs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, n,
                        din, it == 0 ? 1 : 0, o.xtol, cnt + it);
     HIPCHK(hipGetLastError());
@@ -64,21 +68,15 @@ static int fit_run(v21_mlp* m, int route, long long n, const float* d_data, long
       if (running == 0) break;
     }
   }
-  if (x_dtype == V21_DTYPE_F64)
-    hipLaunchKernelGGL(fit_finish_kernel<double>, grid, dim3(256), 0, st, (const FitRow*)fs, (double*)x_hat, d_lnl, d_lnl0, d_status, n, din,
-                       m->tin);
-  else
-    hipLaunchKernelGGL(fit_finish_kernel<float>, grid, dim3(256), 0, st, (const FitRow*)fs, (float*)x_hat, d_lnl, d_lnl0, d_status, n, din,
-                       m->tin);
+  const auto finish = x_dtype == V21_DTYPE_F64 ? fit_finish_kernel<double> : fit_finish_kernel<float>;
+  hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const FitRow*)fs, x_hat, d_lnl, d_lnl0, d_status, n, din, m->tin);
   HIPCHK(hipGetLastError());
   if (!d_F) return V21_OK;
   CHK(jac_prep(m, x_hat, x_dtype, din, n, 1));
-  return fisher_run(m, route, n, d_F, nullptr, nullptr, m->lk_read(), 0, 1, 0, prec, flags | V21_FWD_IN_TRANSFORM);
+  return reduce_run(m, route, n, d_F, nullptr, nullptr, nullptr, m->lk_read(), 0, 1, 0, prec, flags | V21_FWD_IN_TRANSFORM);
 }
 
-// has_data: a data matrix of n_data rows was handed in (at least one, dividing n); without one n_data is ignored
-static int fit_check(long long n, bool has_data, long long n_data, const v21_fit_opts& o) {
-  if (has_data && (n_data < 1 || n % n_data != 0)) return fail(V21_ERR_ARG, "fit: n = %lld rows, n_data = %lld", n, n_data);
+static int fit_check(const v21_fit_opts& o) {
   if (o.max_iter < 0 || o.check_every < 1 || !(o.lambda0 > 0.0) || !(o.xtol >= 0.0))
     return fail(V21_ERR_ARG, "fit: options max_iter %d check_every %d lambda0 %g xtol %g", o.max_iter, o.check_every, o.lambda0, o.xtol);
   return V21_OK;
@@ -92,7 +90,7 @@ static int fit_route(v21_mlp* m, int flags, bool fisher) {
   return route;
 }
 
-static constexpr JacEntry kFisher{"Fisher", kFisherMaxIn, true, false}, kFit{"fit", kFitMaxIn, true, true};
+static constexpr JacEntry kFisher{"Fisher", kJacMaxIn, true, false}, kFit{"fit", kFitMaxIn, true, true};
 
 // ---- Fisher matrices
 extern "C" int v21_mlp_fisher_dev(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_fisher, float* d_lnl, float* d_grad,
@@ -100,7 +98,7 @@ extern "C" int v21_mlp_fisher_dev(v21_mlp* m, const float* d_x, int64_t ldx, int
   CHK(jac_args(m, d_x && d_fisher, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFisher));
   if (n == 0) return V21_OK;
   CHK(jac_prep(m, d_x, V21_DTYPE_F32, ldx, n, flags & V21_FWD_IN_TRANSFORM));
-  return fisher_run(m, jac_route(m, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, m->lk_read(), 0, 1, 0, precision,
+  return reduce_run(m, jac_route(m, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, nullptr, m->lk_read(), 0, 1, 0, precision,
                     flags);
 }
 
@@ -114,7 +112,7 @@ extern "C" int v21_mlp_fisher(v21_mlp* m, const void* x, int x_dtype, int64_t n,
   return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, din * din + din + 3, [&](long long r0, long long rows, float* dF) {
     float* dl = lnl ? dF + rows * din * din : nullptr;
     float* dg = grad ? dF + rows * (din * din + 1) : nullptr;
-    CHK(fisher_run(m, route, rows, dF, dl, dg, m->lk_read(), 0, 1, 0, precision, flags));
+    CHK(reduce_run(m, route, rows, dF, dl, dg, nullptr, m->lk_read(), 0, 1, 0, precision, flags));
     CHK(to_host(m, fisher + r0 * din * din, dF, (size_t)rows * din * din * sizeof(float)));
     if (lnl) CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
     return grad ? to_host(m, grad + r0 * din, dg, (size_t)rows * din * sizeof(float)) : V21_OK;
@@ -127,37 +125,33 @@ extern "C" int v21_mlp_fit_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64
                                int32_t* d_status, int precision, int flags) {
   const v21_fit_opts o = opts ? *opts : fit_defaults();
   CHK(jac_args(m, d_x0 && d_x_hat && d_lnl, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFit));
-  CHK(fit_check(n, d_data != nullptr, n_data, o));
+  CHK(call_data_args("fit", n, d_data != nullptr, n_data));
+  CHK(fit_check(o));
   if (n == 0) return V21_OK;
-  const float* data = m->lk_read();
-  if (d_data) CHK(nuis_project(m, d_data, n_data, &data));
-  const long long ld = d_data ? m->dims[m->L] : 0, rpd = d_data ? n / n_data : 1;
+  CallData data;
+  CHK(call_data(m, n, d_data, false, n_data, &data));
   const int route = fit_route(m, flags, d_fisher != nullptr);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
-  return fit_run(m, route, n, data, ld, rpd, 0, o, precision, flags, d_x_hat, V21_DTYPE_F32, d_lnl, d_lnl_start, (int*)d_status, d_fisher);
+  return fit_run(m, route, n, data, 0, o, precision, flags, d_x_hat, V21_DTYPE_F32, d_lnl, d_lnl_start, (int*)d_status, d_fisher);
 }
 
 extern "C" int v21_mlp_fit(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_fit_opts* opts,
                            void* x_hat, float* lnl, float* lnl_start, float* fisher, int32_t* status, int precision, int flags) {
   const v21_fit_opts o = opts ? *opts : fit_defaults();
   CHK(jac_args(m, x0 && x_hat && lnl, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kFit));
-  CHK(fit_check(n, data != nullptr, n_data, o));
+  CHK(call_data_args("fit", n, data != nullptr, n_data));
+  CHK(fit_check(o));
   if (n == 0) return V21_OK;
-  const int din = m->dims[0], dout = m->dims[m->L];
-  if (data) {
-    CHK(m->fdata.reserve((size_t)n_data * dout));
-    HIPCHK(hipMemcpyAsync(m->fdata.p, data, (size_t)n_data * dout * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-  }
-  const float* d_data = m->lk_read();
-  if (data) CHK(nuis_project(m, m->fdata.get(), n_data, &d_data));
-  const long long ld = data ? dout : 0, rpd = data ? n / n_data : 1;
+  CallData cd;
+  CHK(call_data(m, n, data, true, n_data, &cd));
+  const int din = m->dims[0];
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   const int route = fit_route(m, flags, fisher != nullptr);
   return jac_chunks(m, x0, x_dtype, n, 1, din * din + din + 3, [&](long long r0, long long rows, float* dF) {
     float* dl = dF + rows * din * din;
     float* dl0 = dl + rows;
     int* ds = (int*)(dl0 + rows);
-    CHK(fit_run(m, route, rows, d_data, ld, rpd, r0, o, precision, flags, m->hin.p, x_dtype, dl, dl0, ds, fisher ? dF : nullptr));
+    CHK(fit_run(m, route, rows, cd, r0, o, precision, flags, m->hin.p, x_dtype, dl, dl0, ds, fisher ? dF : nullptr));
     CHK(to_host(m, (char*)x_hat + r0 * din * esz, m->hin.p, (size_t)rows * din * esz));
     CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
     if (lnl_start) CHK(to_host(m, lnl_start + r0, dl0, (size_t)rows * sizeof(float)));

@@ -42,7 +42,7 @@ constexpr int kStampSlots = 64;
 #include "dw_adam.h"
 #include "routes.h"
 
-namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip)
+namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip); both row states are built on rowmath.h
 namespace v21 { struct SampleRow; }  // sample_kernels.h (api_sample.hip)
 using namespace v21;
 
@@ -272,18 +272,24 @@ int jac_prep(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n
 // there by reduce(y, jac, r0, rows) (y: nullptr unless want_y; r0: the slice's first row)
 int jac_slices(v21_mlp* m, int route, long long n, bool want_y, int prec, int flags,
                const std::function<int(const float*, const float*, long long, long long)>& reduce);
-// api_fit.hip, shared with api_sample.hip: F (n, din, din), and lnl / grad (nullable), of the n prepped rows on `route`;
-// row n of the call reads data row (row0 + n) / rpd of pitch ld_data
-int fisher_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, const float* d_data, long long ld_data,
-               long long rpd, long long row0, int prec, int flags);
+// the reduction of every consumer (jac_reduce_kernel, reduce_kernels.h; marginalised when the handle has a nuisance
+// record, at most kJacMaxIn inputs): F (n, din, din), lnl, grad and the (n, nu_k) sums b -- each nullable, b only with
+// a nuisance record -- of the n prepped rows on `route`; row n of the call reads data row (row0 + n) / rpd of pitch
+// ld_data (the fit's and the sampler's evaluations are this call too)
+int reduce_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, float* d_b, const float* d_data,
+               long long ld_data, long long rpd, long long row0, int prec, int flags);
+// api_fit.hip, shared with api_sample.hip: the data a fit or sample call (`what`) of n rows reduces against.  Without a
+// data matrix the record's (n_data ignored); else n_data rows (at least one, dividing n: call_data_args, V21_ERR_ARG,
+// before the call's options are checked and before any device work), from the host staged in m->fdata, projected when
+// a nuisance record is set (call_data, n > 0); row r reads data row r / rpd of pitch ld
+struct CallData { const float* d; long long ld, rpd; };
+int call_data_args(const char* what, long long n, bool has_data, long long n_data);
+int call_data(v21_mlp* m, long long n, const float* data, bool on_host, long long n_data, CallData* out);
 // api_nuisance.hip: the record of `k` modes from the host copies of basis, weights and data (no device work; V21_ERR_ARG as
-// v21_nuisance_whiten) and its upload (synchronises); with a nuisance record, the reductions of fisher_run / the
-// log-likelihood entries (d_F nullable; d_b: the (n, k) sums b, nullable) and the rows of a caller's (n_data, out_dim)
-// data matrix projected into m->nu_ws (*out: those, or d_data itself without a nuisance record)
+// v21_nuisance_whiten) and its upload (synchronises); the rows of a caller's (n_data, out_dim) data matrix projected
+// into m->nu_ws (*out: those, or d_data itself without a nuisance record)
 int nuis_build(const double* basis, const float* w, const float* d, int k, int dout, NuisRecord& rec);
 int nuis_upload(v21_mlp* m, const NuisRecord& rec);
-int marg_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, float* d_b, const float* d_data,
-             long long ld_data, long long rpd, long long row0, int prec, int flags);
 int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float** out);
 // a host form's rows, chunk by chunk: upload (m->hin) and prep them, run(r0, rows, out) on the chunk (out: m->hout of
 // out_floats per row, and never fewer than a Jacobian row's y and jac, so that no host form regrows what another left),

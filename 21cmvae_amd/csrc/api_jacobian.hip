@@ -3,10 +3,12 @@
 // The reference's Keras model is differentiated with tf.GradientTape; here one launch pushes the primal and the in_dim
 // tangents through the stack together (forward mode: 7 inputs against 451 outputs).  Routes: csrc/routes.h
 // (decide_jacobian) -- fused_jac<Arch, Prec> (fused_jac.h) for the stacks of archs.h, jac_generic_kernel
-// (jac_generic.h) for every other.
+// (jac_generic.h) for every other.  What leaves the device of a Jacobian that stays there -- ln L, its gradient, Fisher
+// matrices, marginalised or not -- is reduced by jac_reduce_kernel (reduce_kernels.h; reduce_run).
 #include "api_internal.h"
 #include "fused_jac.h"
 #include "jac_generic.h"
+#include "reduce_kernels.h"
 
 namespace v21 {
 #define V21_DECL(a)                                                                \
@@ -201,19 +203,36 @@ int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, lon
   return V21_OK;
 }
 
-// lnl / grad (nullable) of the n prepped rows; with a nuisance record both routes reduce their Jacobian slice by slice
-// with jac_marg_kernel (api_nuisance.hip), without one the fused route reduces its Jacobian slice by slice (jac_loglike_kernel),
-// the generic kernel reduces in its likelihood mode
-static int loglike_run(v21_mlp* m, int route, long long n, float* d_lnl, float* d_grad, int prec, int flags) {
-  if (m->nu_k) return marg_run(m, route, n, nullptr, d_lnl, d_grad, nullptr, m->lk_proj.get(), 0, 1, 0, prec, flags);
-  if (route != JAC_FUSED) return jac_run(m, route, 0, n, nullptr, m->dims[m->L], nullptr, d_lnl, d_grad, prec, flags);
-  const int din = m->dims[0], dout = m->dims[m->L];
-  return jac_slices(m, route, n, true, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {
-    hipLaunchKernelGGL(jac_loglike_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, m->ctx->stream, wy, wj,
-                       m->lk_data.get(), m->lk_w.get(), d_lnl + r0, d_grad ? d_grad + r0 * din : nullptr,
-                       rows, din, dout);
+// jac_reduce_kernel<NI, NK, FISHER> for din inputs, nk nuisance modes (0: no record) and F asked for or not
+typedef void (*reduce_kernel)(const float*, const float*, const float*, long long, long long, long long, const float*, const float*, int,
+                              float*, float*, float*, float*, long long, int, int);
+static reduce_kernel reduce_pick(int din, int nk, bool fisher) {
+#define V21_NK(NI, NK) {jac_reduce_kernel<NI, NK, false>, jac_reduce_kernel<NI, NK, true>}
+#define V21_NI(NI) {V21_NK(NI, 0), V21_NK(NI, 4), V21_NK(NI, 8)}
+  static const reduce_kernel table[2][3][2] = {V21_NI(8), V21_NI(kJacMaxIn)};
+#undef V21_NI
+#undef V21_NK
+  return table[din > 8][(nk + 3) / 4][fisher];
+}
+
+int reduce_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, float* d_b, const float* d_data,
+               long long ld_data, long long rpd, long long row0, int prec, int flags) {
+  const int din = m->dims[0], dout = m->dims[m->L], nk = m->nu_k;
+  if (nk && din > kJacMaxIn) return fail(V21_ERR_UNSUPPORTED, "nuisance modes: %d inputs (at most %d)", din, kJacMaxIn);
+  const reduce_kernel kern = reduce_pick(din, nk, d_F != nullptr);
+  return jac_slices(m, route, n, d_lnl || d_grad || d_b, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, m->ctx->stream, wy, wj, d_data, ld_data, rpd, row0 + r0,
+                       (const float*)m->lk_w.get(), (const float*)m->nu_qf.get(), nk, d_F ? d_F + r0 * din * din : nullptr,
+                       d_lnl ? d_lnl + r0 : nullptr, d_grad ? d_grad + r0 * din : nullptr, d_b ? d_b + r0 * nk : nullptr, rows, din, dout);
     return V21_OK;
   });
+}
+
+// lnl / grad (nullable) of the n prepped rows: the generic kernel reduces in its own likelihood mode, the fused route's
+// Jacobian -- and, with a nuisance record, either route's -- is reduced slice by slice (reduce_run)
+static int loglike_run(v21_mlp* m, int route, long long n, float* d_lnl, float* d_grad, int prec, int flags) {
+  if (!m->nu_k && route != JAC_FUSED) return jac_run(m, route, 0, n, nullptr, m->dims[m->L], nullptr, d_lnl, d_grad, prec, flags);
+  return reduce_run(m, route, n, nullptr, d_lnl, d_grad, nullptr, m->lk_read(), 0, 1, 0, prec, flags);
 }
 
 static constexpr JacEntry kJacobian{"Jacobian", INT_MAX, false, false}, kLoglike{"log-likelihood", INT_MAX, true, false};

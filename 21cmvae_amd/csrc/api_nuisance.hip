@@ -2,8 +2,8 @@
 // reductions (include/v21.h: v21_nuisance_whiten, v21_mlp_set_nuisance, v21_mlp_nuisance_info, v21_mlp_nuisance_coef).
 // The host side orthonormalises the basis under the record's weights in float64 and projects the record's data once
 // (float32 cannot form r^T W r - |b|^2 from data that carry the foreground); the reductions of a handle with a nuisance
-// record (loglike, fisher, fit, sample) then run jac_marg_kernel (nuisance_kernels.h) in place of jac_fisher_kernel /
-// jac_loglike_kernel, and a caller's data matrix is projected by nuis_project_kernel once per call.
+// record (loglike, fisher, fit, sample) then run jac_reduce_kernel's NK > 0 instantiations (reduce_kernels.h; reduce_run
+// of api_jacobian.hip), and a caller's data matrix is projected by nuis_project_kernel (nuisance_kernels.h) once per call.
 #include "api_internal.h"
 #include "nuisance_kernels.h"
 
@@ -128,26 +128,7 @@ int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float*
   return V21_OK;
 }
 
-template <bool FISHER>
-static auto marg_kernel(int din, int nk) {
-  if (din <= 8) return nk <= 4 ? jac_marg_kernel<8, 4, FISHER> : jac_marg_kernel<8, 8, FISHER>;
-  return nk <= 4 ? jac_marg_kernel<15, 4, FISHER> : jac_marg_kernel<15, 8, FISHER>;
-}
-
-int marg_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, float* d_grad, float* d_b, const float* d_data,
-             long long ld_data, long long rpd, long long row0, int prec, int flags) {
-  const int din = m->dims[0], dout = m->dims[m->L], nk = m->nu_k;
-  if (din > 15) return fail(V21_ERR_UNSUPPORTED, "nuisance modes: %d inputs (at most 15)", din);
-  auto kern = d_F ? marg_kernel<true>(din, nk) : marg_kernel<false>(din, nk);
-  return jac_slices(m, route, n, d_lnl || d_grad || d_b, prec, flags, [&](const float* wy, const float* wj, long long r0, long long rows) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, m->ctx->stream, wy, wj, d_data, ld_data, rpd, row0 + r0,
-                       m->lk_w.get(), m->nu_qf.get(), nk, d_F ? d_F + r0 * din * din : nullptr, d_lnl ? d_lnl + r0 : nullptr,
-                       d_grad ? d_grad + r0 * din : nullptr, d_b ? d_b + r0 * nk : nullptr, rows, din, dout);
-    return V21_OK;
-  });
-}
-
-static constexpr JacEntry kCoef{"nuisance amplitudes", 15, true, false};
+static constexpr JacEntry kCoef{"nuisance amplitudes", kJacMaxIn, true, false};
 
 // a_hat[n, :] = R^-1 (Q W (d_raw - y[n])): the kernel's b is taken against the projected data, Q W d_raw is the record's
 extern "C" int v21_mlp_nuisance_coef(v21_mlp* m, const void* x, int x_dtype, int64_t n, double* coef, int precision, int flags) {
@@ -158,7 +139,7 @@ extern "C" int v21_mlp_nuisance_coef(v21_mlp* m, const void* x, int x_dtype, int
   const int route = jac_route(m, flags, m->dims[m->L]);
   std::vector<float> b((size_t)n * K);
   CHK(jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, K, [&](long long r0, long long rows, float* out) {
-    CHK(marg_run(m, route, rows, nullptr, nullptr, nullptr, out, m->lk_proj.get(), 0, 1, 0, precision, flags));
+    CHK(reduce_run(m, route, rows, nullptr, nullptr, nullptr, out, m->lk_proj.get(), 0, 1, 0, precision, flags));
     return to_host(m, b.data() + r0 * K, out, (size_t)rows * K * sizeof(float));
   }));
   const double* R = m->nu.r.data();

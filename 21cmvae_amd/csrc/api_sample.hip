@@ -1,7 +1,7 @@
 // api_sample.hip -- posterior sampling on the device (include/v21.h: v21_mlp_sample[_dev]): n independent chains of a
 // Fisher-preconditioned Metropolis-adjusted Langevin sampler (sample_kernels.h) in the fit's coordinates.  The loop is
 // the fit's without its read-back: the chain state stays on the device, every transition is one Fisher evaluation of the
-// pending proposals (fisher_run of api_fit.hip, on u without the input transform) and one sample_step_kernel launch,
+// pending proposals (reduce_run of api_jacobian.hip, on u without the input transform) and one sample_step_kernel launch,
 // and the host only launches.
 #include "api_internal.h"
 #include "sample_kernels.h"
@@ -24,9 +24,8 @@ static long long sample_keep(const v21_sample_opts& o) { return o.thin > 0 ? o.n
 
 // the chains of n start rows prepped transformed (their fac is overwritten); `out`: device pointers, samples and x_last
 // of x_dtype; the call's first chain is global chain `chain0`, its row `row0` of the call (data rows as in fit_run)
-static int sample_run(v21_mlp* m, int route, long long n, const float* d_data, long long ld_data, long long rpd, long long row0,
-                      const v21_sample_opts& o, long long chain0, const double* d_eps_start, int prec, int flags, const v21_sample_out& out,
-                      int x_dtype) {
+static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, long long row0, const v21_sample_opts& o, long long chain0,
+                      const double* d_eps_start, int prec, int flags, const v21_sample_out& out, int x_dtype) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0];
   CHK(m->smp.reserve((size_t)n));
@@ -46,28 +45,23 @@ static int sample_run(v21_mlp* m, int route, long long n, const float* d_data, l
   a.t = m->tin;
   hipLaunchKernelGGL(sample_init_kernel, grid, dim3(256), 0, st, cs, m->jxt.get(), m->jfac.get(), n, din, o.eps0, d_eps_start);
   HIPCHK(hipGetLastError());
+  // (samples and x_last are of x_dtype: one pair of instantiations, picked once)
+  const bool f64 = x_dtype == V21_DTYPE_F64;
+  const auto step = f64 ? sample_step_kernel<double> : sample_step_kernel<float>;
+  const auto finish = f64 ? sample_finish_kernel<double> : sample_finish_kernel<float>;
   for (long long it = 0; it <= a.total; ++it) {
-    CHK(fisher_run(m, route, n, F, l, g, d_data, ld_data, rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    if (x_dtype == V21_DTYPE_F64)
-      hipLaunchKernelGGL(sample_step_kernel<double>, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
-    else
-      hipLaunchKernelGGL(sample_step_kernel<float>, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
+    CHK(reduce_run(m, route, n, F, l, g, nullptr, data.d, data.ld, data.rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
+    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
     HIPCHK(hipGetLastError());
   }
   SampleOutDev od{out.x_last, out.lnl_last, out.eps_last, out.accept_rate, out.mean_u, out.cov_u, out.last_prop_u, out.last_log_alpha};
-  if (x_dtype == V21_DTYPE_F64)
-    hipLaunchKernelGGL(sample_finish_kernel<double>, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din,
-                       (long long)o.n_steps, m->tin, od);
-  else
-    hipLaunchKernelGGL(sample_finish_kernel<float>, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din,
-                       (long long)o.n_steps, m->tin, od);
+  hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din, (long long)o.n_steps, m->tin,
+                     od);
   HIPCHK(hipGetLastError());
   return V21_OK;
 }
 
-// as fit_check: has_data: a data matrix of n_data rows was handed in (at least one, dividing n)
-static int sample_check(long long n, bool has_data, long long n_data, const v21_sample_opts& o) {
-  if (has_data && (n_data < 1 || n % n_data != 0)) return fail(V21_ERR_ARG, "sample: n = %lld rows, n_data = %lld", n, n_data);
+static int sample_check(const v21_sample_opts& o) {
   if (o.n_steps < 0 || o.n_warmup < 0 || o.thin < 0 || !(o.eps0 > 0.0) || !std::isfinite(o.eps0) || !(o.ridge > 0.0) || !std::isfinite(o.ridge) ||
       !(o.target_accept > 0.0 && o.target_accept < 1.0))
     return fail(V21_ERR_ARG, "sample: options n_steps %d n_warmup %d thin %d eps0 %g ridge %g target_accept %g", o.n_steps, o.n_warmup, o.thin,
@@ -83,31 +77,27 @@ extern "C" int v21_mlp_sample_dev(v21_mlp* m, const float* d_x0, int64_t ldx, in
                                   const v21_sample_opts* opts, const double* d_eps_start, const v21_sample_out* out, int precision, int flags) {
   const v21_sample_opts o = opts ? *opts : sample_defaults();
   CHK(jac_args(m, d_x0 && out && out->x_last, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kSample));
-  CHK(sample_check(n, d_data != nullptr, n_data, o));
+  CHK(call_data_args("sample", n, d_data != nullptr, n_data));
+  CHK(sample_check(o));
   if (n == 0) return V21_OK;
-  const float* data = m->lk_read();
-  if (d_data) CHK(nuis_project(m, d_data, n_data, &data));
-  const long long ld = d_data ? m->dims[m->L] : 0, rpd = d_data ? n / n_data : 1;
+  CallData data;
+  CHK(call_data(m, n, d_data, false, n_data, &data));
   const int route = jac_route(m, flags, m->dims[m->L]);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
-  return sample_run(m, route, n, data, ld, rpd, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32);
+  return sample_run(m, route, n, data, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32);
 }
 
 extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_sample_opts* opts,
                               const double* eps_start, const v21_sample_out* out, int precision, int flags) {
   const v21_sample_opts o = opts ? *opts : sample_defaults();
   CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kSample));
-  CHK(sample_check(n, data != nullptr, n_data, o));
+  CHK(call_data_args("sample", n, data != nullptr, n_data));
+  CHK(sample_check(o));
   if (n == 0) return V21_OK;
+  CallData cd;
+  CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0], dout = m->dims[m->L];
   hipStream_t st = m->ctx->stream;
-  if (data) {
-    CHK(m->fdata.reserve((size_t)n_data * dout));
-    HIPCHK(hipMemcpyAsync(m->fdata.p, data, (size_t)n_data * dout * sizeof(float), hipMemcpyHostToDevice, st));
-  }
-  const float* d_data = m->lk_read();
-  if (data) CHK(nuis_project(m, m->fdata.get(), n_data, &d_data));
-  const long long ld = data ? dout : 0, rpd = data ? n / n_data : 1;
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   const long long keep = sample_keep(o);
   const int route = jac_route(m, flags, dout);
@@ -132,7 +122,7 @@ extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n
     d.last_prop_u = (float*)take(din);
     d.last_log_alpha = take(1);
     if (eps_start) HIPCHK(hipMemcpyAsync(d_eps, eps_start + r0, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, st));
-    CHK(sample_run(m, route, rows, d_data, ld, rpd, r0, o, o.chain0 + r0, eps_start ? d_eps : nullptr, precision, flags, d, x_dtype));
+    CHK(sample_run(m, route, rows, cd, r0, o, o.chain0 + r0, eps_start ? d_eps : nullptr, precision, flags, d, x_dtype));
     if (out->samples) CHK(to_host(m, (char*)out->samples + r0 * keep * din * esz, d.samples, (size_t)rows * keep * din * esz));
     if (out->samples_lnl) CHK(to_host(m, out->samples_lnl + r0 * keep, d.samples_lnl, (size_t)rows * keep * sizeof(float)));
     CHK(to_host(m, (char*)out->x_last + r0 * din * esz, d.x_last, (size_t)rows * din * esz));

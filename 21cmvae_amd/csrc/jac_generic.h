@@ -1,8 +1,6 @@
 // jac_generic.h -- the parameter Jacobian's kernels outside the fused route (api_jacobian.hip):
 //   jac_prep_kernel     the input transform of every route (par_transform.h, the forward's own functions: the primal
 //                       sees the bits the forward's prologue computes) and its chain-rule factor per (row, column);
-//   jac_loglike_kernel  ln L and its gradient from y and the Jacobian on the device (the fused route's likelihood mode:
-//                       8 floats per row leave the device instead of 1 + in_dim rows of out_dim);
 //   jac_generic_kernel  primal + tangents of ANY stack (any hidden_dims and in_dim, > 512 wide, V21_ACT_GAUSS heads
 //                       evaluated as z = z_mean like the deterministic forward) in f32 arithmetic.  One workgroup per
 //                       (row, group of up to 7 tangents); the G columns of a layer's activation live in LDS, every
@@ -44,43 +42,6 @@ __global__ void jac_prep_kernel(float* __restrict__ xt, float* __restrict__ fac,
     xt[i] = par_transform_f32(x, t.log_mask[j], t.zero_floor[j], t.lo[j], t.span[j]);
     const float tf = (t.zero_floor[j] > 0.0 && x == 0.f) ? (float)t.zero_floor[j] : x;
     fac[i] = par_transform_grad((double)tf, t.log_mask[j], t.span[j]);
-  }
-}
-
-// one wave per row (block 256 = 4 rows, grid ceil(n_rows / 4)): lnl[n] = -1/2 sum_k w_k (d_k - y_k)^2,
-// grad[n, j] = sum_k w_k (d_k - y_k) jac[n, j, k]; bins with w == 0 are skipped (whatever d holds there).  Lanes walk the
-// bins (coalesced rows of jac), the sums are reduced across the wave by shuffles: no LDS, no barrier.
-constexpr int kJacMaxIn = 15;
-__global__ void __launch_bounds__(256) jac_loglike_kernel(const float* __restrict__ y, const float* __restrict__ jac,
-                                                          const float* __restrict__ data, const float* __restrict__ wv,
-                                                          float* __restrict__ lnl, float* __restrict__ grad, long long n_rows,
-                                                          int din, int dout) {
-  const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (n >= n_rows) return;  // (whole waves: the shuffles below run with every lane of a live wave)
-  float lp = 0.f, gp[kJacMaxIn] = {};
-  for (int k = lane; k < dout; k += 64) {
-    const float w = wv[k];
-    if (w == 0.f) continue;
-    const float r = data[k] - y[n * dout + k], wr = w * r;
-    lp += wr * r;
-#pragma unroll
-    for (int j = 0; j < kJacMaxIn; ++j)
-      if (j < din) gp[j] += wr * jac[(n * din + j) * dout + k];
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    lp += __shfl_xor(lp, o);
-#pragma unroll
-    for (int j = 0; j < kJacMaxIn; ++j)
-      if (j < din) gp[j] += __shfl_xor(gp[j], o);
-  }
-  if (lane == 0) {
-    lnl[n] = -0.5f * lp;
-    if (grad)
-#pragma unroll
-      for (int j = 0; j < kJacMaxIn; ++j)
-        if (j < din) grad[n * din + j] = gp[j];
   }
 }
 

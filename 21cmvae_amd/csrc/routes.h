@@ -253,8 +253,9 @@ enum JacRoute {
   JAC_FUSED = 1,    // fused_jac<Arch, Prec> compiled into the library (archs.h S1-S4; fused_jac.h)
   JAC_GENERIC = 2,  // any other stack, any in_dim, variational stacks: jac_generic_kernel (jac_generic.h), f32 arithmetic
 };
+constexpr int kJacMaxIn = 15;  // the fused Jacobian's in_dim limit, and that of the reduction of its rows (reduce_kernels.h)
 inline int decide_jacobian(bool fused_compiled, int in_dim, int flags, long long ldy) {
-  const bool fused = fused_compiled && in_dim <= 15 && !(flags & V21_FWD_FORCE_GENERIC) && ldy < (1ll << 21);
+  const bool fused = fused_compiled && in_dim <= kJacMaxIn && !(flags & V21_FWD_FORCE_GENERIC) && ldy < (1ll << 21);
   return fused ? JAC_FUSED : JAC_GENERIC;
 }
 

@@ -1,0 +1,140 @@
+// rowmath.h -- what the per-row step kernels of the fit (fit_kernels.h) and the sampler (sample_kernels.h) share: one
+// thread per row, float64 in registers, in the transformed coordinates u in [-1, 1]^din (the training box par_transform
+// maps to), din <= kFitMaxIn.  Packed layouts: a symmetric matrix as its upper triangle by rows (element (i, j), i <= j, at
+// i NI - i (i - 1) / 2 + (j - i)), a Cholesky factor L as its lower triangle by rows (L[i][j] at i (i + 1) / 2 + j); rows
+// and columns >= din are those of the identity, so every loop runs over NI = kFitMaxIn with constant indices.
+//   EvalPoint               a point with its evaluation (ln L, gradient, Fisher matrix): the head of the row states;
+//   widen_row / widen_upper / widen_eval  a row of din floats, a Fisher matrix, and an evaluation row's gradient and
+//                           Fisher matrix, to float64 registers;
+//   chol_factor             L of F + diag(addend), the caller's addend and pivot test;
+//   solve_lower / _upper    L z = g and L^T x = z;
+//   box_clamp / box_to_raw  a start row into the box, and a coordinate back to raw units.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/v21_types.h"
+
+namespace v21 {
+
+constexpr int kFitMaxIn = 8;
+constexpr int kFitPacked = kFitMaxIn * (kFitMaxIn + 1) / 2;
+
+// din floats in float64 registers, zeros past din
+__device__ inline void widen_row(const float* v, int din, double* v64) {
+#pragma unroll
+  for (int i = 0; i < kFitMaxIn; ++i) v64[i] = i < din ? (double)v[i] : 0.0;
+}
+// a Fisher matrix to packed float64 registers, zeros past din; at(i, j, p): where the source holds element (i, j), i <= j,
+// whose packed position is p
+template <class At>
+__device__ inline void widen_upper(const float* F, int din, double* F64, At at) {
+  int p = 0;
+#pragma unroll
+  for (int i = 0; i < kFitMaxIn; ++i)
+#pragma unroll
+    for (int j = i; j < kFitMaxIn; ++j, ++p) F64[p] = j < din ? (double)F[at(i, j, p)] : 0.0;
+}
+
+struct EvalPoint {
+  float u[kFitMaxIn];   // the point
+  float g[kFitMaxIn];   // gradient of ln L there (u coordinates)
+  float F[kFitPacked];  // Fisher matrix there, upper triangle by rows
+  float lnl;            // ln L there
+
+  // an evaluation row as the new point: up (din), g_new (din), F_new (din, din)
+  __device__ void take(const float* up, float lnl_new, const float* g_new, const float* F_new, int din) {
+    lnl = lnl_new;
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < kFitMaxIn; ++i) {
+      if (i < din) {
+        u[i] = up[i];
+        g[i] = g_new[i];
+      }
+#pragma unroll
+      for (int j = i; j < kFitMaxIn; ++j, ++p)
+        if (j < din) F[p] = F_new[i * din + j];
+    }
+  }
+  // the point in float64 registers, zeros past din
+  __device__ void widen_u(int din, double* u64) const { widen_row(u, din, u64); }
+  // its gradient and packed Fisher matrix in float64 registers, zeros past din
+  __device__ void widen(int din, double* g64, double* F64) const {
+    widen_row(g, din, g64);
+    widen_upper(F, din, F64, [](int, int, int p) { return p; });
+  }
+};
+
+// an evaluation row that is not (yet) taken as the point, the sampler's proposal: g_new (din) and F_new (din, din) in
+// float64 registers as EvalPoint::widen leaves them
+__device__ inline void widen_eval(const float* g_new, const float* F_new, int din, double* g64, double* F64) {
+  widen_row(g_new, din, g64);
+  widen_upper(F_new, din, F64, [din](int i, int j, int) { return i * din + j; });
+}
+
+// Cholesky factor Lm of A = F + diag(addend(i)); false: pivot_ok(pivot) failed for a row < din (Lm is then not used)
+template <class Addend, class PivotOk>
+__device__ inline bool chol_factor(const double* F, int din, double* Lm, Addend addend, PivotOk pivot_ok) {
+  constexpr int NI = kFitMaxIn;
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      // A[i][j] = A[j][i]: the upper triangle's element (j, i)
+      const int pu = j * NI - j * (j - 1) / 2 + (i - j);
+      double sum = F[pu];
+      if (i == j) sum += addend(i);
+#pragma unroll
+      for (int k = 0; k < j; ++k) sum -= Lm[i * (i + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
+      if (i == j) {
+        if (i < din && !pivot_ok(sum)) ok = false;
+        Lm[i * (i + 1) / 2 + i] = i < din ? sqrt(sum) : 1.0;
+      } else {
+        Lm[i * (i + 1) / 2 + j] = i < din ? sum / Lm[j * (j + 1) / 2 + j] : 0.0;
+      }
+    }
+  }
+  return ok;
+}
+// L z = g (forward substitution)
+__device__ inline void solve_lower(const double* Lm, const double* g, double* z) {
+  constexpr int NI = kFitMaxIn;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    double sum = g[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) sum -= Lm[i * (i + 1) / 2 + k] * z[k];
+    z[i] = sum / Lm[i * (i + 1) / 2 + i];
+  }
+}
+// L^T x = z (back substitution)
+__device__ inline void solve_upper(const double* Lm, const double* z, double* x) {
+  constexpr int NI = kFitMaxIn;
+#pragma unroll
+  for (int i = NI - 1; i >= 0; --i) {
+    double sum = z[i];
+#pragma unroll
+    for (int k = i + 1; k < NI; ++k) sum -= Lm[k * (k + 1) / 2 + i] * x[k];
+    x[i] = sum / Lm[i * (i + 1) / 2 + i];
+  }
+}
+
+// a transformed start row (pitch din, the row the next evaluation reads) into the box: clamp(xt, -1, 1), NaN -> -1 (a
+// log column's non-positive raw value); fac = 1 (the evaluations run on u, without the input transform)
+__device__ inline void box_clamp(float* up, float* fac, int din) {
+  for (int j = 0; j < din; ++j) {
+    const float v = up[j];
+    up[j] = v >= -1.f ? (v <= 1.f ? v : 1.f) : -1.f;
+    fac[j] = 1.f;
+  }
+}
+// u (transformed) -> raw, float64, the inverse of par_transform: lo + (u + 1) span / 2, then 10^ for a log column (its
+// lower bound comes back as 10^lo, e.g. the zero floor, never 0)
+__device__ inline double box_to_raw(double u, int j, const v21_affine_in& t) {
+  double v = t.lo[j] + (u + 1.0) * t.span[j] / 2.0;
+  if (t.log_mask[j]) v = pow(10.0, v);
+  return v;
+}
+
+}  // namespace v21

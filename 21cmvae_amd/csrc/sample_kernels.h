@@ -2,10 +2,10 @@
 // whose metric is the Fisher matrix at the current point ("simplified manifold MALA"), one thread per chain, in the
 // transformed coordinates u in [-1, 1]^din of the fit (fit_kernels.h) under a uniform prior on that box.
 //   sample_init_kernel    clamps the transformed start rows into the box and resets the chain state;
-//   sample_step_kernel    consumes the evaluation (ln L, gradient, Fisher matrix: jac_fisher_kernel) of the pending
+//   sample_step_kernel    consumes the evaluation (ln L, gradient, Fisher matrix: jac_reduce_kernel) of the pending
 //                         proposal: accepts or rejects it, adapts the step size in warm-up, accumulates the moments,
 //                         stores a thinned sample in raw units, then draws and writes the next proposal;
-//   sample_finish_kernel  the last state back to raw parameters (float64 inverse of par_transform) and the results.
+//   sample_finish_kernel  the last state back to raw parameters and the results.
 // The transition, with G(u) = F(u) + ridge I = L L^T, d = din and step size e:
 //   mu(u) = u + e^2 / 2 G(u)^-1 g(u);   u' = float32(mu(u) + e L(u)^-T xi),  xi ~ N(0, I_d)
 //   log q(b | a) = -|L(a)^T (b - mu(a))|^2 / (2 e^2) + sum_i log L_ii(a) - d / 2 log(2 pi e^2)
@@ -13,14 +13,13 @@
 // (the metric's derivative term of full manifold MALA is left out; the acceptance uses the q that was really drawn
 // from, at the float32 u' that is really evaluated, so the chain is exact).  A proposal with a coordinate outside
 // [-1, 1], or whose G has no finite Cholesky factor, is rejected: log alpha = -inf, its evaluation is not read.
-// Cholesky, solves and log-densities are float64 in registers.  Random numbers: Philox4x32-10, include/v21.h.
+// Cholesky, solves (rowmath.h) and log-densities are float64 in registers.  Random numbers: Philox4x32-10, include/v21.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
-#include "../../include/v21_types.h"
-#include "fit_kernels.h"
+#include "rowmath.h"
 
 namespace v21 {
 
@@ -50,16 +49,13 @@ constexpr double kSampleTwoPi = 6.283185307179586476925286766559;
 
 // per-chain state
 struct SampleRow {
-  float u[kFitMaxIn];            // current point
-  float g[kFitMaxIn];            // gradient of ln L there (u coordinates)
-  float F[kFitMaxIn * (kFitMaxIn + 1) / 2];  // Fisher matrix there, upper triangle by rows
-  float lnl;                     // ln L there
+  EvalPoint p;                   // current point
   int reject;                    // the pending proposal left the box (or could not be drawn): rejected unread
   double eps;                    // step size
   double lq_fwd;                 // log q(pending proposal | current point)
   double log_alpha;              // of the last transition decided
   double su[kFitMaxIn];          // moments of the kept transitions: sum u, sum u u^T (upper triangle), accepted
-  double suu[kFitMaxIn * (kFitMaxIn + 1) / 2];
+  double suu[kFitPacked];
   long long accepted;
 };
 
@@ -76,58 +72,21 @@ struct SampleArgs {
   v21_affine_in t;
 };
 
-// u (transformed) -> raw, float64: lo + (u + 1) span / 2, then 10^ for a log column (fit_finish_kernel)
-__device__ inline double sample_raw(double u, int j, const v21_affine_in& t) {
-  double v = t.lo[j] + (u + 1.0) * t.span[j] / 2.0;
-  if (t.log_mask[j]) v = pow(10.0, v);
-  return v;
-}
-
-// Cholesky factor L (lower, by rows: L[i][j] at i (i + 1) / 2 + j) of G = F + ridge I, F the upper triangle by rows;
-// rows >= din are those of the identity.  false: a pivot is not positive and finite.
+// Cholesky factor of G = F + ridge I (rowmath.h); false: a pivot is not positive and finite
 __device__ inline bool sample_chol(const double* F, double ridge, int din, double* Lm) {
-  constexpr int NI = kFitMaxIn;
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-#pragma unroll
-    for (int j = 0; j <= i; ++j) {
-      const int pu = j * NI - j * (j - 1) / 2 + (i - j);
-      double sum = F[pu];
-      if (i == j) sum += ridge;
-#pragma unroll
-      for (int k = 0; k < j; ++k) sum -= Lm[i * (i + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
-      if (i == j) {
-        if (i < din && !(sum > 0.0 && sum < 1.79e308)) ok = false;
-        Lm[i * (i + 1) / 2 + i] = i < din ? sqrt(sum) : 1.0;
-      } else {
-        Lm[i * (i + 1) / 2 + j] = i < din ? sum / Lm[j * (j + 1) / 2 + j] : 0.0;
-      }
-    }
-  }
-  return ok;
+  return chol_factor(F, din, Lm, [&](int) { return ridge; }, [](double pivot) { return pivot > 0.0 && pivot < 1.79e308; });
 }
 // mu = u + e^2 / 2 G^-1 g (two triangular solves) and sum_i log L_ii
 __device__ inline double sample_drift(const double* Lm, const double* u, const double* g, double eps, int din, double* mu) {
   constexpr int NI = kFitMaxIn;
   double z[NI], ld = 0.0;
+  solve_lower(Lm, g, z);
+  solve_upper(Lm, z, mu);
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    double sum = g[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) sum -= Lm[i * (i + 1) / 2 + k] * z[k];
-    z[i] = sum / Lm[i * (i + 1) / 2 + i];
     if (i < din) ld += log(Lm[i * (i + 1) / 2 + i]);
+    mu[i] = u[i] + 0.5 * eps * eps * mu[i];
   }
-#pragma unroll
-  for (int i = NI - 1; i >= 0; --i) {
-    double sum = z[i];
-#pragma unroll
-    for (int k = i + 1; k < NI; ++k) sum -= Lm[k * (k + 1) / 2 + i] * mu[k];
-    mu[i] = sum / Lm[i * (i + 1) / 2 + i];
-  }
-#pragma unroll
-  for (int i = 0; i < NI; ++i) mu[i] = u[i] + 0.5 * eps * eps * mu[i];
   return ld;
 }
 // log q(b | a) from a's factor, drift and log-determinant term
@@ -144,26 +103,22 @@ __device__ inline double sample_logq(const double* Lm, const double* mu, double 
   return -q / (2.0 * eps * eps) + ld - 0.5 * din * log(kSampleTwoPi * eps * eps);
 }
 
-// one thread per chain: u_prop (pitch din, the rows the next evaluation reads) = clamp(xt, -1, 1), NaN -> -1; fac = 1
-// (fit_init_kernel); the step size from eps_start (nullable: eps0)
+// one thread per chain: u_prop (pitch din, the rows the next evaluation reads) into the box (box_clamp), the state reset;
+// the step size from eps_start (nullable: eps0)
 static __global__ void __launch_bounds__(256) sample_init_kernel(SampleRow* __restrict__ st, float* __restrict__ up, float* __restrict__ fac,
                                                                  long long n, int din, double eps0, const double* __restrict__ eps_start) {
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
-  for (int j = 0; j < din; ++j) {
-    const float v = up[row * din + j];
-    up[row * din + j] = v >= -1.f ? (v <= 1.f ? v : 1.f) : -1.f;
-    fac[row * din + j] = 1.f;
-  }
+  box_clamp(up + row * din, fac + row * din, din);
   SampleRow& s = st[row];
   double e = eps_start ? eps_start[row] : eps0;
   s.eps = e > 0.0 && e < 1.79e308 ? e : eps0;
-  s.lnl = 0.f;
+  s.p.lnl = 0.f;
   s.reject = 0;
   s.lq_fwd = 0.0;
   s.log_alpha = 0.0;
   for (int i = 0; i < kFitMaxIn; ++i) s.su[i] = 0.0;
-  for (int i = 0; i < kFitMaxIn * (kFitMaxIn + 1) / 2; ++i) s.suu[i] = 0.0;
+  for (int i = 0; i < kFitPacked; ++i) s.suu[i] = 0.0;
   s.accepted = 0;
 }
 
@@ -174,12 +129,13 @@ template <class T>
 __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict__ st, float* __restrict__ up, const float* __restrict__ lnl_new,
                                                           const float* __restrict__ g_new, const float* __restrict__ F_new, long long it,
                                                           const SampleArgs a) {
-  constexpr int NI = kFitMaxIn, NP = NI * (NI + 1) / 2;
+  constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= a.n) return;
   const int din = a.din;
   SampleRow& s = st[row];
   float* upr = up + row * din;
+  const float *gn = g_new + row * din, *Fn = F_new + row * din * din;
   double eps = s.eps;
   double F[NP], g[NI], u[NI], Lm[NP], mu[NI];
   bool have_factor = false;  // Lm, mu and ld below belong to the current point
@@ -189,23 +145,14 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
     // the proposal's side of the acceptance ratio
     double log_alpha = -INFINITY;
     if (!s.reject) {
-      double up64[NI], uc[NI];
-      {
-        const float* Fn = F_new + row * din * din;
-        int p = 0;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          g[i] = i < din ? (double)g_new[row * din + i] : 0.0;
-          up64[i] = i < din ? (double)upr[i] : 0.0;
-          uc[i] = i < din ? (double)s.u[i] : 0.0;
-#pragma unroll
-          for (int j = i; j < NI; ++j, ++p) F[p] = j < din ? (double)Fn[i * din + j] : 0.0;
-        }
-      }
+      double up64[NI];
+      widen_row(upr, din, up64);
+      widen_eval(gn, Fn, din, g, F);
+      s.p.widen_u(din, u);
       if (sample_chol(F, a.ridge, din, Lm)) {
         ld = sample_drift(Lm, up64, g, eps, din, mu);
-        const double lq_rev = sample_logq(Lm, mu, ld, uc, eps, din);
-        log_alpha = (double)lnl_new[row] - (double)s.lnl + lq_rev - s.lq_fwd;
+        const double lq_rev = sample_logq(Lm, mu, ld, u, eps, din);
+        log_alpha = (double)lnl_new[row] - (double)s.p.lnl + lq_rev - s.lq_fwd;
         if (log_alpha != log_alpha) log_alpha = -INFINITY;
         uint32_t w[4];
         sample_block(a.seed, a.chain0 + (uint64_t)row, (uint32_t)(a.step0 + (uint64_t)(it - 1)), 2u, w);
@@ -222,24 +169,9 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
       if (accept) have_factor = false;  // (the drift of the next proposal takes the new step size: rebuilt below)
     }
   }
-  if (accept) {
-    s.lnl = lnl_new[row];
-    const float* Fn = F_new + row * din * din;
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      if (i < din) {
-        s.u[i] = upr[i];
-        s.g[i] = g_new[row * din + i];
-      }
-#pragma unroll
-      for (int j = i; j < NI; ++j, ++p)
-        if (j < din) s.F[p] = Fn[i * din + j];
-    }
-  }
+  if (accept) s.p.take(upr, lnl_new[row], gn, Fn, din);
   // the current point
-#pragma unroll
-  for (int i = 0; i < NI; ++i) u[i] = i < din ? (double)s.u[i] : 0.0;
+  s.p.widen_u(din, u);
   if (it > a.n_warmup) {
     // a kept transition: moments, and every thin-th state in raw units
     int p = 0;
@@ -255,32 +187,26 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
     if (a.thin > 0 && k % a.thin == 0 && k / a.thin <= a.n_keep) {
       const long long slot = row * a.n_keep + (k / a.thin - 1);
       if (a.samples)
-        for (int j = 0; j < din; ++j) ((T*)a.samples)[slot * din + j] = (T)sample_raw(u[j], j, a.t);
-      if (a.samples_lnl) a.samples_lnl[slot] = s.lnl;
+        for (int j = 0; j < din; ++j) ((T*)a.samples)[slot * din + j] = (T)box_to_raw(u[j], j, a.t);
+      if (a.samples_lnl) a.samples_lnl[slot] = s.p.lnl;
     }
   }
   if (it == a.total) return;
   // the proposal of transition `it`
   if (!have_factor) {
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      g[i] = i < din ? (double)s.g[i] : 0.0;
-#pragma unroll
-      for (int j = i; j < NI; ++j, ++p) F[p] = j < din ? (double)s.F[p] : 0.0;
-    }
+    s.p.widen(din, g, F);
     if (!sample_chol(F, a.ridge, din, Lm)) {
       // (only a start whose evaluation is not finite: the chain stays where it is)
       s.reject = 1;
       s.lq_fwd = 0.0;
 #pragma unroll
       for (int i = 0; i < NI; ++i)
-        if (i < din) upr[i] = s.u[i];
+        if (i < din) upr[i] = s.p.u[i];
       return;
     }
     ld = sample_drift(Lm, u, g, eps, din, mu);
   }
-  double xi[NI];
+  double xi[NI] = {};
   const uint64_t chain = a.chain0 + (uint64_t)row;
   const uint32_t step = (uint32_t)(a.step0 + (uint64_t)it);
 #pragma unroll
@@ -294,21 +220,15 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
         xi[4 * b + 2 * h] = r * cos(th);
         xi[4 * b + 2 * h + 1] = r * sin(th);
       }
-    } else {
-#pragma unroll
-      for (int h = 0; h < 4; ++h) xi[4 * b + h] = 0.0;
     }
   }
-  // u' = mu + eps L^-T xi (back substitution), rounded to the float32 that is evaluated
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+    if (i >= din) xi[i] = 0.0;  // (the rest of the last block's draws)
+  // u' = mu + eps L^-T xi, rounded to the float32 that is evaluated
   double v[NI], ub[NI];
   bool inside = true;
-#pragma unroll
-  for (int i = NI - 1; i >= 0; --i) {
-    double sum = i < din ? xi[i] : 0.0;
-#pragma unroll
-    for (int k = i + 1; k < NI; ++k) sum -= Lm[k * (k + 1) / 2 + i] * v[k];
-    v[i] = sum / Lm[i * (i + 1) / 2 + i];
-  }
+  solve_upper(Lm, xi, v);
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const float f = (float)(mu[i] + eps * v[i]);
@@ -323,10 +243,10 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
   s.lq_fwd = inside ? sample_logq(Lm, mu, ld, ub, eps, din) : 0.0;
 #pragma unroll
   for (int i = 0; i < NI; ++i)
-    if (i < din) upr[i] = finite ? (float)ub[i] : s.u[i];
+    if (i < din) upr[i] = finite ? (float)ub[i] : s.p.u[i];
 }
 
-// one thread per chain: the last state in raw units (float64 inverse transform, as fit_finish_kernel) and the per-chain
+// one thread per chain: the last state in raw units (box_to_raw) and the per-chain
 // results (nullable): with K kept transitions, mean_u = sum u / K, cov_u = sum u u^T / K - mean_u mean_u^T (both
 // triangles), accept_rate = accepted / K (K == 0: the current point, zeros, 0)
 struct SampleOutDev {
@@ -342,13 +262,13 @@ __global__ void __launch_bounds__(256) sample_finish_kernel(const SampleRow* __r
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   const SampleRow& s = st[row];
-  for (int j = 0; j < din; ++j) ((T*)o.x_last)[row * din + j] = (T)sample_raw((double)s.u[j], j, t);
-  if (o.lnl_last) o.lnl_last[row] = s.lnl;
+  for (int j = 0; j < din; ++j) ((T*)o.x_last)[row * din + j] = (T)box_to_raw((double)s.p.u[j], j, t);
+  if (o.lnl_last) o.lnl_last[row] = s.p.lnl;
   if (o.eps_last) o.eps_last[row] = s.eps;
   if (o.accept_rate) o.accept_rate[row] = kept > 0 ? (double)s.accepted / (double)kept : 0.0;
   const double inv = kept > 0 ? 1.0 / (double)kept : 0.0;
   if (o.mean_u)
-    for (int j = 0; j < din; ++j) o.mean_u[row * din + j] = kept > 0 ? s.su[j] * inv : (double)s.u[j];
+    for (int j = 0; j < din; ++j) o.mean_u[row * din + j] = kept > 0 ? s.su[j] * inv : (double)s.p.u[j];
   if (o.cov_u) {
     int p = 0;
     for (int i = 0; i < kFitMaxIn; ++i)

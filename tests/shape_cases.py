@@ -1,6 +1,6 @@
 """The table of stack shapes of tests/test_shapes_cpu.py and tests/test_shapes_gpu.py, and its builders.
 
-Every other test of the Jacobian-side kernels (jac_generic.h, fit_kernels.h, nuisance_kernels.h, sample_kernels.h) runs 7 or
+Every other test of the Jacobian-side kernels (jac_generic.h, reduce_kernels.h, fit_kernels.h, nuisance_kernels.h, sample_kernels.h) runs 7 or
 9 inputs against 451 outputs.  The stacks here are tiny and chosen for the branches those shapes never reach: more than
 one tangent group on grid.y of jac_generic_kernel and a short last group, its LDS paths (the shrink loop, the 256-float
 floor of the likelihood mode's block reduction, a row pitch set by in_dim or out_dim), the lane tails of the reductions
@@ -49,8 +49,8 @@ CASES = [
     Case("i5gauss", [5, 32, 6, 16, 63], [1, 2, 1, 0], (1,), False),
     # [7, 3000, 5]: 2 (7 + 1) 3000 floats exceed 160 KB, the shrink loop stops at tc = 5: tangent groups 5 + 2
     Case("i7w3000", [7, 3000, 5], [1, 0], (), False),
-    # in_dim = 8: tangent groups 7 + 1 (blockIdx.y = 1 with a single tangent), NI = 8 without padding in jac_fisher_kernel<8>,
-    # jac_marg_kernel<8, ., .>, fit_lm_kernel and the sampler (the fit limit, two full Philox blocks); out_dim = 64: every
+    # in_dim = 8: tangent groups 7 + 1 (blockIdx.y = 1 with a single tangent), NI = 8 without padding in
+    # jac_reduce_kernel<8, ., .>, fit_lm_kernel and the sampler (the fit limit, two full Philox blocks); out_dim = 64: every
     # lane runs the bin loop exactly once
     Case("i8o64", [8, 33, 64], [1, 0], (4, 8), True),
     # the one 451-bin case, at in_dim = 8, two hidden layers
@@ -63,7 +63,7 @@ CASES = [
     # in_dim = 15 with out_dim = 65: groups 7 + 7 + 1, NI = 15 without padding (the Fisher limit), 120 accumulators
     Case("i15o65", [15, 40, 65], [1, 0], (4, 8), False),
     # in_dim = 16, maxw = in_dim: the LDS row pitch is set by the input; groups 7 + 7 + 2; past the Fisher limit --
-    # Jacobian and loglike are still served, every reduction of fit_kernels.h / nuisance_kernels.h is refused
+    # Jacobian and loglike are still served, every reduction of reduce_kernels.h is refused
     Case("i16o3", [16, 8, 3], [1, 0], (), False),
     # in_dim = 17: groups 7 + 7 + 3; out_dim = 64
     Case("i17o64", [17, 31, 64], [1, 0], (), False),

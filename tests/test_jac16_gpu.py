@@ -151,7 +151,7 @@ def test_loglike_and_fisher_match_rounding_reference(ctx, name, prec):
 
 
 def test_marginalised_reductions_match_rounding_reference(ctx):
-    """jac_marg_kernel (the sampler's reduction, 4x the plain one) on D1 in f16 with K = 5 foreground modes, 64 rows: F,
+    """jac_reduce_kernel with nuisance modes (the sampler's reduction, 4x the plain one) on D1 in f16 with K = 5 foreground modes, 64 rows: F,
     ln L and g against marg_ref fed the rounding reference's y and J, medians over rows (g: per input, the worst input).
     Every error is relative to the sum of the magnitudes of the terms the kernel sums, as tests/test_marg_gpu.py scales
     them: the kernel works on the PROJECTED data d~ = d - Q^T (Q W d) (nuis_project_kernel), so ln L_m = -1/2 (r~ W r~ -

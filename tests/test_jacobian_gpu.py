@@ -274,6 +274,33 @@ def test_loglike(ctx, name, prec):
     st.set_likelihood(None, None)
 
 
+@pytest.mark.parametrize("K", [0, 5])
+@pytest.mark.parametrize("prec", ["f32", "f16"])
+def test_loglike_is_fisher_without_F(ctx, prec, K):
+    """on the fused route loglike and fisher(lnl, grad) are one reduction (jac_reduce_kernel) that differs only in whether
+    F is formed: ln L and its gradient agree bit for bit, without a nuisance record and with K = 5 modes (5 rows: one
+    full workgroup of the reduction and one row)"""
+    nat = pkg("_native")
+    st, dims, act, Ws, bs, tin, tout = stack_of(ctx, "D1")
+    flags = nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM
+    x = rows_for(dims, 5, 23, np.float32)
+    rng = np.random.default_rng(4)
+    data = (jr.jacobian(Ws, bs, act, x[:1], tin, tout)[0][0] + rng.normal(size=dims[-1]) * 0.05 * tout[0]).astype(np.float32)
+    w = np.where(rng.uniform(size=dims[-1]) < 0.25, 0.0, 1.0 / (0.05 * tout[0]) ** 2).astype(np.float32)
+    st.set_likelihood(data, w)
+    try:
+        if K:
+            st.set_nuisance(pkg("foregrounds").linlog_basis(np.linspace(50.0, 200.0, dims[-1]), K))
+        lnl, g = st.loglike(x, prec, flags)
+        assert st.last_jac_route()[0] == "fused"
+        _, lnl_f, g_f = st.fisher(x, prec, flags, lnl=True, grad=True)
+        assert np.all(np.isfinite(lnl)) and np.all(np.isfinite(g))
+        assert np.array_equal(lnl.view(np.uint32), lnl_f.view(np.uint32))
+        assert np.array_equal(g.view(np.uint32), g_f.view(np.uint32))
+    finally:
+        st.set_likelihood(None, None)
+
+
 @pytest.mark.parametrize("name", ["NB", "W6", "VG"])
 def test_generic_route_parity(ctx, name):
     nat = pkg("_native")

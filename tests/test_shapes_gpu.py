@@ -1,5 +1,5 @@
 """The Jacobian-side kernels over the shapes of tests/shape_cases.py: jac_generic_kernel (Jacobian and likelihood mode),
-jac_fisher_kernel<8 / 15>, the jac_marg_kernel instantiations and nuis_project_kernel, fit_lm_kernel and the sample_*
+the jac_reduce_kernel<8 / 15, 0 / 4 / 8, with / without F> instantiations and nuis_project_kernel, fit_lm_kernel and the sample_*
 kernels, each against its float64 reference (jacobian_ref, fit_ref, marg_ref, sample_ref) at in_dim 1 .. 17 and out_dim
 1 .. 451, the 65,535-row launch split of the generic route and the documented refusals.  Every bound is the one the
 project already uses for the same quantity (check_rows, test_loglike, test_fisher_against_own_jacobian, check_reduction,
@@ -170,7 +170,7 @@ def test_likelihood_mode_of_the_generic_kernel(ctx):
 
 
 def test_fisher_lnl_and_gradient(ctx):
-    """jac_fisher_kernel<8> (in_dim <= 8, unpadded at 8) and <15> (9 .. 15, unpadded at 15) against fit_ref.fisher_ref of
+    """jac_reduce_kernel<8, 0, true> (in_dim <= 8, unpadded at 8) and <15, 0, true> (9 .. 15, unpadded at 15) against fit_ref.fisher_ref of
     the device's own Jacobian at 1e-5 relative Frobenius, exactly symmetric; lnl and grad against loglike at the bounds of
     test_fisher_against_own_jacobian (1e-6 of the value / of the sum of the terms' magnitudes).  Measured worst on the
     MI355X: F 0.010 of 1e-5, lnl 0.099 and grad 0.12 of 1e-6."""
@@ -224,7 +224,7 @@ def test_in_dim_limits(ctx):
     st.set_nuisance(sc.basis(3, 1))  # (the record itself does not depend on in_dim)
     assert status_of(lambda: st.fisher(x, "f32", flags)) == UNSUPPORTED
     assert status_of(lambda: st.nuisance_coef(x, "f32", flags)) == UNSUPPORTED
-    assert status_of(lambda: st.loglike(x, "f32", flags)) == UNSUPPORTED  # (marginalised: jac_marg_kernel's limit)
+    assert status_of(lambda: st.loglike(x, "f32", flags)) == UNSUPPORTED  # (marginalised: jac_reduce_kernel's limit)
     st.set_nuisance(None)
     l2, g2 = st.loglike(x, "f32", flags)
     assert same(l2, lnl) and same(g2, g)
@@ -266,7 +266,7 @@ def test_a_layer_too_wide_for_the_lds_is_refused(ctx):
 
 
 def test_marginalised_reductions(ctx):
-    """the eight jac_marg_kernel<8 | 15, 4 | 8, with / without F> instantiations over the table's out_dim and K in {1, 4, 5,
+    """the eight jac_reduce_kernel<8 | 15, 4 | 8, with / without F> instantiations over the table's out_dim and K in {1, 4, 5,
     8}: fisher, loglike and nuisance_coef against marg_ref fed the device's own y and J, bounds and scales of
     test_marg_gpu.check_reduction; clearing the record restores the earlier bits; a basis on fewer than K + 1 live bins
     is refused and leaves the handle as it was.  Measured worst on the MI355X, as fractions of the scales: F 1.6e-7, lnl
@@ -296,7 +296,7 @@ def test_marginalised_reductions(ctx):
             assert coef.shape == (n, K) and coef.dtype == np.float64
             ref, ls, gs, ct = reference(y, jac, data, w, A)
             check_reduction(tag, F, lnl, g, coef, ref, ls, gs, ct, worst)
-            l_ll, g_ll = st.loglike(x, "f32", flags)  # (jac_marg_kernel without F)
+            l_ll, g_ll = st.loglike(x, "f32", flags)  # (jac_reduce_kernel without F)
             np.testing.assert_allclose(lnl, l_ll, rtol=1e-6, atol=0, err_msg=tag)
             scale = np.einsum("nk,njk->nj", np.abs(w64 * (data - y.astype(np.float64))), np.abs(jac.astype(np.float64)))
             assert np.all(np.abs(g - g_ll) <= 1e-6 * scale), (tag, np.max(np.abs(g - g_ll) / scale))
