@@ -78,6 +78,19 @@ class SampleOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in SAMPLE_OUTPUTS]
 
 
+class TemperOpts(C.Structure):
+    """v21_temper_opts (include/v21_types.h)"""
+    _fields_ = [("n_temps", C.c_int), ("betas", C.c_double * 32), ("swap_every", C.c_int)]
+
+
+TEMPER_OUTPUTS = ("mean_lnl", "var_lnl", "swap_accept")
+
+
+class TemperOut(C.Structure):
+    """v21_temper_out (include/v21_types.h): host or device addresses, NULL = not asked for"""
+    _fields_ = [(k, C.c_void_p) for k in TEMPER_OUTPUTS]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 # name -> (restype, argtypes); every symbol include/v21.h declares
@@ -149,6 +162,10 @@ SIGNATURES = {
                                  C.c_int, C.c_int]),
     "v21_mlp_sample_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(SampleOpts), _P, C.POINTER(SampleOut),
                                      C.c_int, C.c_int]),
+    "v21_mlp_sample_tempered": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(SampleOpts), C.POINTER(TemperOpts), _P,
+                                          C.POINTER(SampleOut), C.POINTER(TemperOut), C.c_int, C.c_int]),
+    "v21_mlp_sample_tempered_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(SampleOpts), C.POINTER(TemperOpts), _P,
+                                              C.POINTER(SampleOut), C.POINTER(TemperOut), C.c_int, C.c_int]),
     "v21_nuisance_whiten": (C.c_int, [C.POINTER(C.c_double), _F, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "v21_mlp_set_nuisance": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, C.c_int32]),
     "v21_mlp_nuisance_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
@@ -838,6 +855,16 @@ class Stack(_Owned):
         (n, in, in) float64 -- the per-chain moments of u over the n_steps kept transitions -- and, with samples and
         thin > 0, samples (n, n_steps // thin, in) in x0's dtype and samples_lnl; with diagnostics, last_prop_u (n, in)
         float32 and last_log_alpha (n,) float64 of the last transition."""
+        x, dt, n, dp, nd, o, es, res = self._sample_call(x0, data, eps_start, samples, diagnostics, opts)
+        out = SampleOut(**{k: v.ctypes.data for k, v in res.items()})
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_sample(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(o),
+                                          es.ctypes.data_as(_P) if es is not None else None, C.byref(out), precision_id(precision), flags))
+        return res
+
+    def _sample_call(self, x0, data, eps_start, samples, diagnostics, opts):
+        """what the host forms of sample and sample_tempered share: the rows, the data matrix, the options, the start
+        step sizes and the result arrays of v21_sample_out -> (x, dtype id, n, data, n_data, opts, eps_start, results)"""
         x, dt = self._rows(x0)
         n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
         if din > 8:
@@ -868,11 +895,7 @@ class Stack(_Owned):
         if diagnostics:
             res["last_prop_u"] = np.empty((n, din), np.float32)
             res["last_log_alpha"] = np.empty(n, np.float64)
-        out = SampleOut(**{k: v.ctypes.data for k, v in res.items()})
-        with self.ctx.lock:
-            check(self.lib.v21_mlp_sample(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(o),
-                                          es.ctypes.data_as(_P) if es is not None else None, C.byref(out), precision_id(precision), flags))
-        return res
+        return x, dt, n, dp, nd, o, es, res
 
     def sample_dev(self, d_x0, ldx, n, d_data, n_data, out, d_eps_start=None, precision="f32", flags=0, **opts):
         """v21_mlp_sample_dev: out is a dict of device addresses by the names of SAMPLE_OUTPUTS (x_last required; samples
@@ -881,6 +904,61 @@ class Stack(_Owned):
         so = SampleOut(**{k: int(v) for k, v in out.items() if v})
         check(self.lib.v21_mlp_sample_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), _opt(d_eps_start), C.byref(so),
                                           precision_id(precision), flags))
+
+    @staticmethod
+    def temper_opts(n_temps=1, betas=None, swap_every=0, n=None, n_data=0):
+        """v21_temper_opts: n_temps rungs at the inverse temperatures betas (None: 1 for one rung), a swap event every
+        swap_every transitions (0: never); ValueError for what the library would refuse -- with n (and n_data, 0: the
+        record's data) also the rows of a call that are no whole ladders, or whose ladders would straddle two data rows"""
+        if int(n_temps) != n_temps or not 1 <= int(n_temps) <= 32:
+            raise ValueError("sample_tempered: n_temps = %r (1 .. 32)" % (n_temps,))
+        T = int(n_temps)
+        if betas is None:
+            if T != 1:
+                raise ValueError("sample_tempered: %d rungs need their betas" % T)
+            betas = [1.0]
+        b = np.asarray(betas, np.float64)
+        if b.shape != (T,):
+            raise ValueError("sample_tempered: betas must be (%d,), got %r" % (T, b.shape))
+        if not np.all((b >= 0.0) & (b <= 1.0)) or not np.all(b[1:] < b[:-1]):
+            raise ValueError("sample_tempered: betas = %r (inside [0, 1], strictly decreasing)" % (b.tolist(),))
+        if int(swap_every) != swap_every or not 0 <= int(swap_every) < 2 ** 31:
+            raise ValueError("sample_tempered: swap_every = %r (a non-negative integer)" % (swap_every,))
+        if n is not None and (n % T or (n_data and (n // n_data) % T)):
+            raise ValueError("sample_tempered: %d rows%s are no whole ladders of %d" % (n, " over %d data rows" % n_data if n_data else "", T))
+        return TemperOpts(T, (C.c_double * 32)(*b.tolist()), int(swap_every))
+
+    def sample_tempered(self, x0, n_temps=1, betas=None, swap_every=0, precision="f32", flags=0, data=None, eps_start=None, samples=True,
+                        diagnostics=False, **opts):
+        """Parallel-tempered posterior sampling (include/v21.h: v21_mlp_sample_tempered): n_temps consecutive rows of x0
+        form one ladder, row r at inverse temperature betas[r % n_temps]; every swap_every transitions neighbouring rungs
+        of a ladder propose to exchange their states.  Everything else as ``sample``, whose results come back for every
+        row (a row is a rung: with betas[0] = 1 the rows 0, n_temps, 2 n_temps .. are the posterior chains), and beside
+        them mean_lnl, var_lnl (the un-tempered ln L over the kept transitions) and swap_accept (the pair of this row and
+        the next), all (n,) float64.  With data, the rows of one spectrum must be whole ladders."""
+        self.temper_opts(n_temps, betas, swap_every)
+        x, dt, n, dp, nd, o, es, res = self._sample_call(x0, data, eps_start, samples, diagnostics, opts)
+        t = self.temper_opts(n_temps, betas, swap_every, n, nd)
+        out = SampleOut(**{k: v.ctypes.data for k, v in res.items()})
+        tres = {k: np.empty(n, np.float64) for k in TEMPER_OUTPUTS}
+        tout = TemperOut(**{k: v.ctypes.data for k, v in tres.items()})
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_sample_tempered(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(o), C.byref(t),
+                                                   es.ctypes.data_as(_P) if es is not None else None, C.byref(out), C.byref(tout),
+                                                   precision_id(precision), flags))
+        res.update(tres)
+        return res
+
+    def sample_tempered_dev(self, d_x0, ldx, n, d_data, n_data, out, tout=None, n_temps=1, betas=None, swap_every=0, d_eps_start=None,
+                            precision="f32", flags=0, **opts):
+        """v21_mlp_sample_tempered_dev: out as for sample_dev, tout a dict of device addresses by the names of
+        TEMPER_OUTPUTS (or None); asynchronous on the context's stream."""
+        o = self.sample_opts(**opts)
+        t = self.temper_opts(n_temps, betas, swap_every)
+        so = SampleOut(**{k: int(v) for k, v in out.items() if v})
+        to = TemperOut(**{k: int(v) for k, v in (tout or {}).items() if v})
+        check(self.lib.v21_mlp_sample_tempered_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), C.byref(t), _opt(d_eps_start),
+                                                   C.byref(so), C.byref(to), precision_id(precision), flags))
 
     def last_jac_route(self):
         """(route name of the last Jacobian / log-likelihood call, {route name: calls since creation})."""

@@ -43,7 +43,7 @@ constexpr int kStampSlots = 64;
 #include "routes.h"
 
 namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip); both row states are built on rowmath.h
-namespace v21 { struct SampleRow; }  // sample_kernels.h (api_sample.hip)
+namespace v21 { struct SampleRow; struct TemperRow; }  // sample_kernels.h (api_sample.hip)
 using namespace v21;
 
 // ---- errors: v21_last_error() returns the calling thread's last message (api_base.hip)
@@ -221,6 +221,7 @@ struct v21_mlp {
   Dev<int> fit_cnt;
   Dev<SampleRow> smp;    // chain state of a sample call (sample_kernels.h; its evaluations land in fF / fl / fg)
   Dev<double> smp_out;   // the host form's chunk: its results, and its per-chain start step sizes
+  Dev<TemperRow> tmp;    // a tempered sample call's sums of ln L and swap counts per row
   bool has_lk = false;
   // linear nuisance modes marginalised in those reductions (api_nuisance.hip): nu_k modes (0: none), the float64 basis
   // as it was handed in, the record built from it, and the host copy of the likelihood record both are re-whitened from.
@@ -293,9 +294,9 @@ int nuis_upload(v21_mlp* m, const NuisRecord& rec);
 int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float** out);
 // a host form's rows, chunk by chunk: upload (m->hin) and prep them, run(r0, rows, out) on the chunk (out: m->hout of
 // out_floats per row, and never fewer than a Jacobian row's y and jac, so that no host form regrows what another left),
-// then sync
+// then sync.  chunk_rows: the rows of a chunk (a tempered sample call's is a whole number of ladders)
 int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, long long out_floats,
-               const std::function<int(long long, long long, float*)>& run);
+               const std::function<int(long long, long long, float*)>& run, long long chunk_rows = kJacHostChunk);
 // device -> host on the context's stream (the host forms' results; jac_chunks syncs)
 static inline int to_host(v21_mlp* m, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->ctx->stream));

@@ -186,15 +186,15 @@ int jac_slices(v21_mlp* m, int route, long long n, bool want_y, int prec, int fl
 }
 
 int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, long long out_floats,
-               const std::function<int(long long, long long, float*)>& run) {
+               const std::function<int(long long, long long, float*)>& run, long long chunk_rows) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0], dout = m->dims[m->L];
-  const long long chunk = std::min(n, kJacHostChunk);
+  const long long chunk = std::min(n, chunk_rows);
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   CHK(m->hin.reserve((size_t)chunk * din));
   CHK(m->hout.reserve((size_t)chunk * std::max(out_floats, (long long)dout * (1 + din))));
-  for (long long r0 = 0; r0 < n; r0 += kJacHostChunk) {
-    const long long rows = std::min(kJacHostChunk, n - r0);
+  for (long long r0 = 0; r0 < n; r0 += chunk_rows) {
+    const long long rows = std::min(chunk_rows, n - r0);
     HIPCHK(hipMemcpyAsync(m->hin.p, (const char*)x + r0 * din * esz, (size_t)rows * din * esz, hipMemcpyHostToDevice, st));
     CHK(jac_prep(m, m->hin.p, x_dtype, din, rows, tin));
     CHK(run(r0, rows, m->hout.get()));

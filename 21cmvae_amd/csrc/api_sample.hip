@@ -2,7 +2,9 @@
 // Fisher-preconditioned Metropolis-adjusted Langevin sampler (sample_kernels.h) in the fit's coordinates.  The loop is
 // the fit's without its read-back: the chain state stays on the device, every transition is one Fisher evaluation of the
 // pending proposals (reduce_run of api_jacobian.hip, on u without the input transform) and one sample_step_kernel launch,
-// and the host only launches.
+// and the host only launches.  The tempered entries (v21_mlp_sample_tempered[_dev]) run the same loop with
+// sample_step_tempered_kernel in the step kernel's place: T consecutive rows form a ladder of inverse temperatures whose
+// rungs exchange their points inside that kernel.
 #include "api_internal.h"
 #include "sample_kernels.h"
 
@@ -23,9 +25,12 @@ static v21_sample_opts sample_defaults() {
 static long long sample_keep(const v21_sample_opts& o) { return o.thin > 0 ? o.n_steps / o.thin : 0; }
 
 // the chains of n start rows prepped transformed (their fac is overwritten); `out`: device pointers, samples and x_last
-// of x_dtype; the call's first chain is global chain `chain0`, its row `row0` of the call (data rows as in fit_run)
+// of x_dtype; the call's first chain is global chain `chain0`, its row `row0` of the call (data rows as in fit_run).
+// tp: the ladder of a tempered call (n a multiple of its n_temps) and its results `to`, device pointers; nullptr:
+// independent chains
 static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, long long row0, const v21_sample_opts& o, long long chain0,
-                      const double* d_eps_start, int prec, int flags, const v21_sample_out& out, int x_dtype) {
+                      const double* d_eps_start, int prec, int flags, const v21_sample_out& out, int x_dtype,
+                      const v21_temper_opts* tp = nullptr, const v21_temper_out* to = nullptr) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0];
   CHK(m->smp.reserve((size_t)n));
@@ -48,16 +53,37 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   // (samples and x_last are of x_dtype: one pair of instantiations, picked once)
   const bool f64 = x_dtype == V21_DTYPE_F64;
   const auto step = f64 ? sample_step_kernel<double> : sample_step_kernel<float>;
+  const auto tstep = f64 ? sample_step_tempered_kernel<double> : sample_step_tempered_kernel<float>;
   const auto finish = f64 ? sample_finish_kernel<double> : sample_finish_kernel<float>;
+  TemperArgs ta{};
+  TemperRow* tr = nullptr;
+  dim3 tgrid(1);
+  if (tp) {
+    // whole ladders per workgroup; the rows' tempered sums start at zero
+    ta.T = tp->n_temps; ta.swap_every = tp->swap_every; ta.rows_per_wg = 256 / tp->n_temps * tp->n_temps;
+    for (int k = 0; k < tp->n_temps; ++k) ta.betas[k] = tp->betas[k];
+    tgrid = dim3((unsigned)((n + ta.rows_per_wg - 1) / ta.rows_per_wg));
+    CHK(m->tmp.reserve((size_t)n));
+    tr = m->tmp.get();
+    HIPCHK(hipMemsetAsync(tr, 0, (size_t)n * sizeof(TemperRow), st));
+  }
   for (long long it = 0; it <= a.total; ++it) {
     CHK(reduce_run(m, route, n, F, l, g, nullptr, data.d, data.ld, data.rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
+    if (tp)
+      hipLaunchKernelGGL(tstep, tgrid, dim3(256), 0, st, cs, tr, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, ta);
+    else
+      hipLaunchKernelGGL(step, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
     HIPCHK(hipGetLastError());
   }
   SampleOutDev od{out.x_last, out.lnl_last, out.eps_last, out.accept_rate, out.mean_u, out.cov_u, out.last_prop_u, out.last_log_alpha};
   hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din, (long long)o.n_steps, m->tin,
                      od);
   HIPCHK(hipGetLastError());
+  if (tp && to && (to->mean_lnl || to->var_lnl || to->swap_accept)) {
+    hipLaunchKernelGGL(sample_finish_tempered_kernel, grid, dim3(256), 0, st, (const SampleRow*)cs, (const TemperRow*)tr, n,
+                       (long long)o.n_steps, TemperOutDev{to->mean_lnl, to->var_lnl, to->swap_accept});
+    HIPCHK(hipGetLastError());
+  }
   return V21_OK;
 }
 
@@ -87,13 +113,11 @@ extern "C" int v21_mlp_sample_dev(v21_mlp* m, const float* d_x0, int64_t ldx, in
   return sample_run(m, route, n, data, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32);
 }
 
-extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_sample_opts* opts,
-                              const double* eps_start, const v21_sample_out* out, int precision, int flags) {
-  const v21_sample_opts o = opts ? *opts : sample_defaults();
-  CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kSample));
-  CHK(call_data_args("sample", n, data != nullptr, n_data));
-  CHK(sample_check(o));
-  if (n == 0) return V21_OK;
+// the host forms: chunks of chunk_rows chains (a whole number of ladders for a tempered call), each staged in
+// m->smp_out, run by sample_run and copied back
+static int sample_host(v21_mlp* m, const void* x0, int x_dtype, long long n, const float* data, long long n_data, const v21_sample_opts& o,
+                       const double* eps_start, const v21_sample_out* out, int precision, int flags, long long chunk_rows,
+                       const v21_temper_opts* tp, const v21_temper_out* tout) {
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0], dout = m->dims[m->L];
@@ -102,9 +126,9 @@ extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n
   const long long keep = sample_keep(o);
   const int route = jac_route(m, flags, dout);
   // a chunk's staging, in 8-byte units per chain: the start step sizes, then every result that was asked for
-  const long long chunk = std::min<long long>(n, kJacHostChunk);
+  const long long chunk = std::min<long long>(n, chunk_rows);
   const long long w_smp = out->samples ? keep * din : 0, w_sl = out->samples_lnl ? (keep + 1) / 2 : 0;
-  const long long per = 1 + w_smp + w_sl + din + 1 + 1 + 1 + din + (long long)din * din + din + 1;
+  const long long per = 1 + w_smp + w_sl + din + 1 + 1 + 1 + din + (long long)din * din + din + 1 + (tp ? 3 : 0);
   CHK(m->smp_out.reserve((size_t)(chunk * per)));
   return jac_chunks(m, x0, x_dtype, n, 1, din * din + din + 3, [&](long long r0, long long rows, float*) -> int {
     double* p = m->smp_out.get();
@@ -121,8 +145,10 @@ extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n
     d.cov_u = take((long long)din * din);
     d.last_prop_u = (float*)take(din);
     d.last_log_alpha = take(1);
+    v21_temper_out t{};
+    if (tp) { t.mean_lnl = take(1); t.var_lnl = take(1); t.swap_accept = take(1); }
     if (eps_start) HIPCHK(hipMemcpyAsync(d_eps, eps_start + r0, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, st));
-    CHK(sample_run(m, route, rows, cd, r0, o, o.chain0 + r0, eps_start ? d_eps : nullptr, precision, flags, d, x_dtype));
+    CHK(sample_run(m, route, rows, cd, r0, o, o.chain0 + r0, eps_start ? d_eps : nullptr, precision, flags, d, x_dtype, tp, &t));
     if (out->samples) CHK(to_host(m, (char*)out->samples + r0 * keep * din * esz, d.samples, (size_t)rows * keep * din * esz));
     if (out->samples_lnl) CHK(to_host(m, out->samples_lnl + r0 * keep, d.samples_lnl, (size_t)rows * keep * sizeof(float)));
     CHK(to_host(m, (char*)out->x_last + r0 * din * esz, d.x_last, (size_t)rows * din * esz));
@@ -133,6 +159,74 @@ extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n
     if (out->cov_u) CHK(to_host(m, out->cov_u + r0 * din * din, d.cov_u, (size_t)rows * din * din * sizeof(double)));
     if (out->last_prop_u) CHK(to_host(m, out->last_prop_u + r0 * din, d.last_prop_u, (size_t)rows * din * sizeof(float)));
     if (out->last_log_alpha) CHK(to_host(m, out->last_log_alpha + r0, d.last_log_alpha, (size_t)rows * sizeof(double)));
+    if (tout && tout->mean_lnl) CHK(to_host(m, tout->mean_lnl + r0, t.mean_lnl, (size_t)rows * sizeof(double)));
+    if (tout && tout->var_lnl) CHK(to_host(m, tout->var_lnl + r0, t.var_lnl, (size_t)rows * sizeof(double)));
+    if (tout && tout->swap_accept) CHK(to_host(m, tout->swap_accept + r0, t.swap_accept, (size_t)rows * sizeof(double)));
     return V21_OK;
-  });
+  }, chunk_rows);
+}
+
+extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_sample_opts* opts,
+                              const double* eps_start, const v21_sample_out* out, int precision, int flags) {
+  const v21_sample_opts o = opts ? *opts : sample_defaults();
+  CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kSample));
+  CHK(call_data_args("sample", n, data != nullptr, n_data));
+  CHK(sample_check(o));
+  if (n == 0) return V21_OK;
+  return sample_host(m, x0, x_dtype, n, data, n_data, o, eps_start, out, precision, flags, kJacHostChunk, nullptr, nullptr);
+}
+
+// ---- parallel tempering (include/v21.h: v21_mlp_sample_tempered[_dev])
+static v21_temper_opts temper_defaults() {
+  v21_temper_opts t{};
+  t.n_temps = 1;
+  t.betas[0] = 1.0;
+  t.swap_every = 0;
+  return t;
+}
+
+// the ladder, and how the call's n rows (with data: the n / n_data rows of a spectrum) divide into ladders
+static int temper_check(const v21_temper_opts& t, long long n, bool has_data, long long n_data) {
+  if (t.n_temps < 1 || t.n_temps > 32) return fail(V21_ERR_ARG, "sample_tempered: n_temps = %d (1 .. 32)", t.n_temps);
+  for (int k = 0; k < t.n_temps; ++k)
+    if (!(t.betas[k] >= 0.0 && t.betas[k] <= 1.0) || (k > 0 && !(t.betas[k] < t.betas[k - 1])))
+      return fail(V21_ERR_ARG, "sample_tempered: betas[%d] = %g (inside [0, 1], strictly decreasing)", k, t.betas[k]);
+  if (t.swap_every < 0) return fail(V21_ERR_ARG, "sample_tempered: swap_every = %d", t.swap_every);
+  if (n % t.n_temps != 0) return fail(V21_ERR_ARG, "sample_tempered: n = %lld rows are no whole ladders of %d", n, t.n_temps);
+  if (has_data && (n / n_data) % t.n_temps != 0)
+    return fail(V21_ERR_ARG, "sample_tempered: %lld rows per data row are no whole ladders of %d", n / n_data, t.n_temps);
+  return V21_OK;
+}
+
+static constexpr JacEntry kSampleTempered{"sample_tempered", kFitMaxIn, true, true};
+
+extern "C" int v21_mlp_sample_tempered_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                           const v21_sample_opts* opts, const v21_temper_opts* temper, const double* d_eps_start,
+                                           const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags) {
+  const v21_sample_opts o = opts ? *opts : sample_defaults();
+  const v21_temper_opts t = temper ? *temper : temper_defaults();
+  CHK(jac_args(m, d_x0 && out && out->x_last, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kSampleTempered));
+  CHK(call_data_args("sample_tempered", n, d_data != nullptr, n_data));
+  CHK(sample_check(o));
+  CHK(temper_check(t, n, d_data != nullptr, n_data));
+  if (n == 0) return V21_OK;
+  CallData data;
+  CHK(call_data(m, n, d_data, false, n_data, &data));
+  const int route = jac_route(m, flags, m->dims[m->L]);
+  CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
+  return sample_run(m, route, n, data, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32, &t, tout);
+}
+
+extern "C" int v21_mlp_sample_tempered(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
+                                       const v21_sample_opts* opts, const v21_temper_opts* temper, const double* eps_start,
+                                       const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags) {
+  const v21_sample_opts o = opts ? *opts : sample_defaults();
+  const v21_temper_opts t = temper ? *temper : temper_defaults();
+  CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kSampleTempered));
+  CHK(call_data_args("sample_tempered", n, data != nullptr, n_data));
+  CHK(sample_check(o));
+  CHK(temper_check(t, n, data != nullptr, n_data));
+  if (n == 0) return V21_OK;
+  // (no ladder straddles two chunks: the largest multiple of n_temps that is not above the host chunk)
+  return sample_host(m, x0, x_dtype, n, data, n_data, o, eps_start, out, precision, flags, kJacHostChunk / t.n_temps * t.n_temps, &t, tout);
 }

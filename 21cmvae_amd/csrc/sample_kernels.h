@@ -5,7 +5,10 @@
 //   sample_step_kernel    consumes the evaluation (ln L, gradient, Fisher matrix: jac_reduce_kernel) of the pending
 //                         proposal: accepts or rejects it, adapts the step size in warm-up, accumulates the moments,
 //                         stores a thinned sample in raw units, then draws and writes the next proposal;
-//   sample_finish_kernel  the last state back to raw parameters and the results.
+//   sample_finish_kernel  the last state back to raw parameters and the results;
+//   sample_step_tempered_kernel / sample_finish_tempered_kernel  the same chains as the rungs of parallel-tempered ladders
+//                         (below, "parallel tempering"): the step kernel's three parts with ln L, g and F scaled by the
+//                         row's inverse temperature, and between them the swap event among the threads of a workgroup.
 // The transition, with G(u) = F(u) + ridge I = L L^T, d = din and step size e:
 //   mu(u) = u + e^2 / 2 G(u)^-1 g(u);   u' = float32(mu(u) + e L(u)^-T xi),  xi ~ N(0, I_d)
 //   log q(b | a) = -|L(a)^T (b - mu(a))|^2 / (2 e^2) + sum_i log L_ii(a) - d / 2 log(2 pi e^2)
@@ -122,24 +125,32 @@ static __global__ void __launch_bounds__(256) sample_init_kernel(SampleRow* __re
   s.accepted = 0;
 }
 
-// one thread per chain, after evaluation number `it` of the call (lnl_new, g_new, F_new at u_prop, u coordinates):
-// it == 0 is the start's, accepted whatever its value; it >= 1 is the proposal's of transition it - 1, which is decided
-// here.  Unless it == a.total the proposal of transition `it` is then drawn and written to u_prop.  T: the samples' type.
-template <class T>
-__global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict__ st, float* __restrict__ up, const float* __restrict__ lnl_new,
-                                                          const float* __restrict__ g_new, const float* __restrict__ F_new, long long it,
-                                                          const SampleArgs a) {
+// ---- the three parts of a step, shared by sample_step_kernel and sample_step_tempered_kernel.  TEMPER: ln L, g and F
+// enter the drift, the metric and log alpha multiplied by the row's inverse temperature beta (include/v21.h); without
+// it beta is not read and the arithmetic is the untempered one, operation for operation.
+// beta v, exactly 0 at beta = 0 whatever v holds
+__device__ __forceinline__ double temper_mul(double beta, double v) { return beta == 0.0 ? 0.0 : beta * v; }
+template <bool TEMPER>
+__device__ __forceinline__ void temper_eval(double beta, double* g, double* F) {
+  if constexpr (TEMPER) {
+#pragma unroll
+    for (int i = 0; i < kFitMaxIn; ++i) g[i] = temper_mul(beta, g[i]);
+#pragma unroll
+    for (int p = 0; p < kFitPacked; ++p) F[p] = temper_mul(beta, F[p]);
+  }
+}
+
+// the decision of the pending proposal after evaluation number `it` of the call (lnl_new, gn, Fn: the row's, at upr):
+// it == 0 is the start's, accepted whatever its value; it >= 1 is the proposal's of transition it - 1.  Adapts the
+// step size in warm-up and takes an accepted proposal as the current point.  -> accepted; have_factor: Lm, mu and ld
+// belong to the current point at the current step size
+template <bool TEMPER>
+__device__ __forceinline__ bool sample_decide(SampleRow& s, const float* upr, const float* lnl_new, const float* gn, const float* Fn,
+                                              long long it, long long row, const SampleArgs& a, double beta, double& eps, double* Lm,
+                                              double* mu, double& ld, bool& have_factor) {
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
-  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= a.n) return;
   const int din = a.din;
-  SampleRow& s = st[row];
-  float* upr = up + row * din;
-  const float *gn = g_new + row * din, *Fn = F_new + row * din * din;
-  double eps = s.eps;
-  double F[NP], g[NI], u[NI], Lm[NP], mu[NI];
-  bool have_factor = false;  // Lm, mu and ld below belong to the current point
-  double ld = 0.0;
+  double F[NP], g[NI], u[NI];
   bool accept = it == 0;
   if (it > 0) {
     // the proposal's side of the acceptance ratio
@@ -148,11 +159,15 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
       double up64[NI];
       widen_row(upr, din, up64);
       widen_eval(gn, Fn, din, g, F);
+      temper_eval<TEMPER>(beta, g, F);
       s.p.widen_u(din, u);
       if (sample_chol(F, a.ridge, din, Lm)) {
         ld = sample_drift(Lm, up64, g, eps, din, mu);
         const double lq_rev = sample_logq(Lm, mu, ld, u, eps, din);
-        log_alpha = (double)lnl_new[row] - (double)s.p.lnl + lq_rev - s.lq_fwd;
+        if constexpr (TEMPER)
+          log_alpha = temper_mul(beta, (double)*lnl_new - (double)s.p.lnl) + lq_rev - s.lq_fwd;
+        else
+          log_alpha = (double)*lnl_new - (double)s.p.lnl + lq_rev - s.lq_fwd;
         if (log_alpha != log_alpha) log_alpha = -INFINITY;
         uint32_t w[4];
         sample_block(a.seed, a.chain0 + (uint64_t)row, (uint32_t)(a.step0 + (uint64_t)(it - 1)), 2u, w);
@@ -169,11 +184,17 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
       if (accept) have_factor = false;  // (the drift of the next proposal takes the new step size: rebuilt below)
     }
   }
-  if (accept) s.p.take(upr, lnl_new[row], gn, Fn, din);
-  // the current point
-  s.p.widen_u(din, u);
+  if (accept) s.p.take(upr, *lnl_new, gn, Fn, din);
+  return accept;
+}
+
+// a kept transition (it > n_warmup) at the current point u: moments, and every thin-th state in raw units.  T: the
+// samples' type.
+template <class T>
+__device__ __forceinline__ void sample_keep(SampleRow& s, const double* u, bool accept, long long it, long long row, const SampleArgs& a) {
+  constexpr int NI = kFitMaxIn;
+  const int din = a.din;
   if (it > a.n_warmup) {
-    // a kept transition: moments, and every thin-th state in raw units
     int p = 0;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -191,10 +212,18 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
       if (a.samples_lnl) a.samples_lnl[slot] = s.p.lnl;
     }
   }
-  if (it == a.total) return;
-  // the proposal of transition `it`
+}
+
+// the proposal of transition `it` from the current point u, written to upr
+template <bool TEMPER>
+__device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const double* u, long long it, long long row, const SampleArgs& a,
+                                            double beta, double eps, double* Lm, double* mu, double ld, bool have_factor) {
+  constexpr int NI = kFitMaxIn, NP = kFitPacked;
+  const int din = a.din;
   if (!have_factor) {
+    double F[NP], g[NI];
     s.p.widen(din, g, F);
+    temper_eval<TEMPER>(beta, g, F);
     if (!sample_chol(F, a.ridge, din, Lm)) {
       // (only a start whose evaluation is not finite: the chain stays where it is)
       s.reject = 1;
@@ -246,6 +275,116 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
     if (i < din) upr[i] = finite ? (float)ub[i] : s.p.u[i];
 }
 
+// one thread per chain, after evaluation number `it` of the call (lnl_new, g_new, F_new at u_prop, u coordinates):
+// the pending proposal is decided (sample_decide), a kept transition accumulated and stored (sample_keep) and, unless
+// it == a.total, the proposal of transition `it` drawn and written to u_prop (sample_draw).  T: the samples' type.
+template <class T>
+__global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict__ st, float* __restrict__ up, const float* __restrict__ lnl_new,
+                                                          const float* __restrict__ g_new, const float* __restrict__ F_new, long long it,
+                                                          const SampleArgs a) {
+  constexpr int NI = kFitMaxIn, NP = kFitPacked;
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= a.n) return;
+  const int din = a.din;
+  SampleRow& s = st[row];
+  float* upr = up + row * din;
+  double eps = s.eps;
+  double u[NI], Lm[NP], mu[NI];
+  bool have_factor = false;  // Lm, mu and ld below belong to the current point
+  double ld = 0.0;
+  const bool accept =
+      sample_decide<false>(s, upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, 1.0, eps, Lm, mu, ld, have_factor);
+  // the current point
+  s.p.widen_u(din, u);
+  sample_keep<T>(s, u, accept, it, row, a);
+  if (it == a.total) return;
+  sample_draw<false>(s, upr, u, it, row, a, 1.0, eps, Lm, mu, ld, have_factor);
+}
+
+// ---- parallel tempering (include/v21.h: v21_mlp_sample_tempered): T consecutive rows are the rungs of one ladder, row r
+// at inverse temperature betas[r % T].  A 256-thread workgroup takes floor(256 / T) whole ladders (rows_per_wg rows;
+// its other threads and the rows past n only meet the barriers), so the partners of a swap are threads of one
+// workgroup.  A swap event exchanges the EvalPoints of the swapping pairs through global memory: both rows of a pair
+// form the same decision from the two stored ln L and the lower row's Philox word, a swapping row reads its partner's
+// point into registers, a barrier follows, then it writes that point over its own.
+struct TemperArgs {
+  int T, swap_every, rows_per_wg;
+  double betas[32];
+};
+// what a row accumulates beside SampleRow's moments, over the kept transitions: sum ln L, sum ln L^2 (un-tempered, after
+// the swap event) and, as the lower row of a pair, the swaps proposed and accepted
+struct TemperRow {
+  double sl, sll;
+  long long proposed, swapped;
+};
+
+template <class T>
+__global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st, TemperRow* __restrict__ tr, float* __restrict__ up,
+                                                                   const float* __restrict__ lnl_new, const float* __restrict__ g_new,
+                                                                   const float* __restrict__ F_new, long long it, const SampleArgs a,
+                                                                   const TemperArgs ta) {
+  constexpr int NI = kFitMaxIn, NP = kFitPacked;
+  const long long row = (long long)blockIdx.x * ta.rows_per_wg + threadIdx.x;
+  // (no thread returns before the last barrier: one that is not `active` skips the work between them)
+  const bool active = (int)threadIdx.x < ta.rows_per_wg && row < a.n;
+  const int din = a.din;
+  const int k = (int)threadIdx.x % ta.T;  // the rung: rows_per_wg and the call's first row are multiples of T
+  const double beta = ta.betas[k];
+  float* upr = up + row * din;
+  double eps = 0.0, ld = 0.0;
+  double u[NI], Lm[NP], mu[NI];
+  bool have_factor = false, accept = false;
+  if (active) {
+    eps = st[row].eps;
+    accept = sample_decide<true>(st[row], upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, beta, eps, Lm, mu, ld,
+                                 have_factor);
+  }
+  // the swap event that follows transition S = step0 + it - 1: the same branch for every thread of the launch
+  const uint64_t s1 = a.step0 + (uint64_t)it;  // S + 1
+  if (it > 0 && ta.swap_every > 0 && s1 % (uint64_t)ta.swap_every == 0) {
+    __syncthreads();  // (the points the decisions above took are in place)
+    constexpr int NW = (int)(sizeof(EvalPoint) / sizeof(float));  // (word by word: the partner's point stays in registers)
+    static_assert(sizeof(EvalPoint) == NW * sizeof(float), "EvalPoint is floats throughout");
+    float other[NW];
+    bool swap = false;
+    const int lo_k = (k & 1) == (int)((s1 / (uint64_t)ta.swap_every - 1) & 1) ? k : k - 1;  // the lower rung of this row's pair
+    if (active && lo_k >= 0 && lo_k + 1 < ta.T) {
+      const long long lo = row - (k - lo_k);
+      const double rhs = (ta.betas[lo_k] - ta.betas[lo_k + 1]) * ((double)st[lo + 1].p.lnl - (double)st[lo].p.lnl);
+      uint32_t w[4];
+      sample_block(a.seed, a.chain0 + (uint64_t)lo, (uint32_t)(s1 - 1), 3u, w);
+      swap = log(sample_uniform(w[0])) < rhs;  // (a NaN right-hand side refuses)
+      if (swap) {
+        const float* src = (const float*)&st[k == lo_k ? lo + 1 : lo].p;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) other[i] = src[i];
+      }
+      if (k == lo_k && it > a.n_warmup) {
+        tr[row].proposed += 1;
+        if (swap) tr[row].swapped += 1;
+      }
+    }
+    __syncthreads();  // (every partner's point is in registers)
+    if (swap) {
+      float* dst = (float*)&st[row].p;
+#pragma unroll
+      for (int i = 0; i < NW; ++i) dst[i] = other[i];
+      have_factor = false;  // (the factor in registers belonged to the point that left)
+    }
+  }
+  if (!active) return;
+  SampleRow& s = st[row];
+  s.p.widen_u(din, u);
+  if (it > a.n_warmup) {
+    const double l = (double)s.p.lnl;
+    tr[row].sl += l;
+    tr[row].sll += l * l;
+  }
+  sample_keep<T>(s, u, accept, it, row, a);
+  if (it == a.total) return;
+  sample_draw<true>(s, upr, u, it, row, a, beta, eps, Lm, mu, ld, have_factor);
+}
+
 // one thread per chain: the last state in raw units (box_to_raw) and the per-chain
 // results (nullable): with K kept transitions, mean_u = sum u / K, cov_u = sum u u^T / K - mean_u mean_u^T (both
 // triangles), accept_rate = accepted / K (K == 0: the current point, zeros, 0)
@@ -282,6 +421,23 @@ __global__ void __launch_bounds__(256) sample_finish_kernel(const SampleRow* __r
   if (o.last_prop_u)
     for (int j = 0; j < din; ++j) o.last_prop_u[row * din + j] = up[row * din + j];
   if (o.last_log_alpha) o.last_log_alpha[row] = s.log_alpha;
+}
+
+// one thread per row: the tempered results (nullable) over `kept` transitions: mean_lnl = sum ln L / K, var_lnl = sum
+// ln L^2 / K - mean_lnl^2, swap_accept = swapped / proposed (kept == 0: the current ln L, 0; nothing proposed: 0)
+struct TemperOutDev {
+  double *mean_lnl, *var_lnl, *swap_accept;
+};
+static __global__ void __launch_bounds__(256) sample_finish_tempered_kernel(const SampleRow* __restrict__ st, const TemperRow* __restrict__ tr,
+                                                                            long long n, long long kept, const TemperOutDev o) {
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  const TemperRow& t = tr[row];
+  const double inv = kept > 0 ? 1.0 / (double)kept : 0.0;
+  const double mean = kept > 0 ? t.sl * inv : (double)st[row].p.lnl;
+  if (o.mean_lnl) o.mean_lnl[row] = mean;
+  if (o.var_lnl) o.var_lnl[row] = kept > 0 ? t.sll * inv - mean * mean : 0.0;
+  if (o.swap_accept) o.swap_accept[row] = t.proposed > 0 ? (double)t.swapped / (double)t.proposed : 0.0;
 }
 
 }  // namespace v21

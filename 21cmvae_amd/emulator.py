@@ -166,6 +166,32 @@ FitResult = namedtuple("FitResult", ["params", "lnl", "status", "fisher"])
 PosteriorSamples = namedtuple("PosteriorSamples", ["params", "lnl", "accept_rate", "step_size", "r_hat", "mean_u", "cov_u"])
 
 
+# sample_tempered's result: the fields of PosteriorSamples from the beta = 1 rows (one chain per ladder), then the ladder,
+# the per-rung means of ln L, the swap rates pooled over ladders and the evidence with its ladder-to-ladder error
+TemperedSamples = namedtuple("TemperedSamples", PosteriorSamples._fields + ("betas", "mean_lnl", "swap_rate", "log_evidence",
+                                                                           "log_evidence_err"))
+
+
+def default_betas(n_temps):
+    """The default ladder of ``sample_tempered``: beta_k = ((T - 1 - k) / (T - 1))^5, k = 0 .. T - 1 ([1.0] for T = 1) -- a
+    power law that crowds the rungs toward beta = 0, where E_beta[ln L] changes fastest; the first rung is the posterior,
+    the last exactly the prior."""
+    T = int(n_temps)
+    if T < 1:
+        raise ValueError("n_temps must be >= 1")
+    if T == 1:
+        return np.ones(1)
+    return ((T - 1.0 - np.arange(T)) / (T - 1.0)) ** 5
+
+
+def log_evidence(betas, mean_lnl):
+    """Thermodynamic integration by the trapezoid rule: sum_k (beta_k - beta_k+1) (E_k + E_k+1) / 2 over the trailing
+    axis of mean_lnl (..., T), E_k = E_beta_k[ln L] at the decreasing inverse temperatures betas (T,).  With betas from 1
+    to 0 this is ln Z up to the rule's discretisation error; 0 for a single rung."""
+    b, E = np.asarray(betas, np.float64), np.asarray(mean_lnl, np.float64)
+    return np.sum((b[:-1] - b[1:]) * (E[..., :-1] + E[..., 1:]) / 2.0, axis=-1)
+
+
 def pooled_moments(mean_c, cov_c):
     """Mean and covariance of the pooled samples of equally long chains from their per-chain means (..., C, d) and
     covariances (..., C, d, d) (both divided by the chain length): the mean of the means, and the mean within-chain
@@ -459,6 +485,77 @@ class _EmulatorBase:
             params, lnl = (params[0] if params is not None else None), (lnl[0] if lnl is not None else None)
             acc, step, rh, mean, cov = acc[0], step[0], rh[0], mean[0], cov[0]
         return PosteriorSamples(params, lnl, acc, step, rh, mean, cov)
+
+    def sample_tempered(self, data, sigma, n_ladders=16, n_temps=8, betas=None, swap_every=5, n_steps=1000, n_warmup=200, thin=1,
+                        p0=None, flow=None, fhigh=None, seed=0, eps=None, return_lnl=False, foreground=None):
+        """Parallel-tempered posterior samples and the Bayesian evidence (not in the reference): ``n_ladders`` ladders per
+        spectrum, each of ``n_temps`` chains of ``sample_posterior``'s sampler at the inverse temperatures ``betas``
+        (default ``default_betas(n_temps)``, from 1 down to 0), run entirely on the device (include/v21.h:
+        v21_mlp_sample_tempered).  A chain at beta samples L^beta under the same uniform prior on the training box; every
+        ``swap_every`` transitions neighbouring rungs of a ladder propose to exchange their states, so what the hot rungs
+        find -- other modes, the far end of a degeneracy -- reaches the beta = 1 chain.  Starts as in ``sample_posterior``
+        (``p0``: (7,) or (n_ladders, 7)), every rung of a ladder from the same jittered start.
+        Returns ``TemperedSamples``: the seven fields of ``PosteriorSamples`` from the beta = 1 rows (``n_ladders`` chains
+        per spectrum), then betas (T,), mean_lnl (M, n_ladders, T) -- the mean of ln L over the kept transitions of every
+        rung --, swap_rate (M, T - 1) -- accepted / proposed swaps of each neighbouring pair, pooled over ladders --,
+        log_evidence (M,) and log_evidence_err (M,); the M axis is dropped for one spectrum.
+        THE EVIDENCE.  log_evidence estimates ln Z, Z = integral of L(u) du / 2^d over the training box (d = 7: the mean of
+        L under the prior), L with the constants ``log_likelihood`` drops (ln L = -chi^2 / 2, without the Gaussian's
+        normalisation).  It is the mean over ladders of each ladder's own trapezoid (``log_evidence``) of its rungs' mean
+        ln L over beta; log_evidence_err is the scatter of those over ladders (std with ddof 1 / sqrt(n_ladders); nan for
+        one ladder) -- the ladders are independent, so it needs no autocorrelation estimate -- and does NOT contain the
+        trapezoid's discretisation bias, which only more rungs reduce.  ln Z is comparable between emulators, bands and
+        noise levels at the same data and the same foreground basis (add the dropped -sum ln(sigma sqrt(2 pi)) over the
+        band's bins where sigma or the band differ).  It is NOT comparable across different numbers of marginalised
+        foreground modes: their flat prior is improper.  nan with ``n_temps = 1``."""
+        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
+        nb, din = st.dims[-1], st.dims[0]
+        dat = np.asarray(data, np.float32)
+        one = dat.ndim == 1
+        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
+        if dat.ndim != 2 or dat.shape[1] != nb:
+            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        M, C, T = dat.shape[0], int(n_ladders), int(n_temps)
+        if C < 1:
+            raise ValueError("n_ladders must be >= 1")
+        b = default_betas(T) if betas is None else np.asarray(betas, np.float64)
+        opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
+        nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
+        nat.Stack.temper_opts(T, b, swap_every)
+        if p0 is None:
+            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
+            u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], C, axis=1)
+        else:
+            starts = np.array(p0, np.float64, ndmin=2)
+            if starts.ndim != 2 or starts.shape[1] != din or starts.shape[0] not in (1, C):
+                raise ValueError("p0 must be (%d,) or (%d, %d), got %r" % (din, C, din, np.shape(p0)))
+            u0 = np.broadcast_to(pp.par_transform(starts, self.par_train)[None], (M, C, din))
+        rng = np.random.default_rng(seed)
+        u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=(M, C, din)), -1.0, 1.0)
+        x0 = pp.par_untransform(u0.reshape(M * C, din), self.par_train)
+        x0 = np.ascontiguousarray(np.repeat(x0, T, axis=0))  # (every rung of a ladder from its ladder's start)
+        self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
+        r = st.sample_tempered(x0, T, b, swap_every, model.precision, flags, data=dat, **opts)
+        cold = lambda a: a.reshape((M, C, T) + a.shape[1:])[:, :, 0]  # the beta = 1 rows
+        K = r["samples"].shape[1] if "samples" in r else 0
+        params = cold(r["samples"]) if K else None
+        lnl = cold(r["samples_lnl"]) if K and return_lnl else None
+        acc, step = cold(r["accept_rate"]), cold(r["eps_last"])
+        mean_c, cov_c = cold(r["mean_u"]), cold(r["cov_u"])
+        rh = r_hat_from_moments(mean_c, cov_c, int(n_steps))
+        mean, cov = pooled_moments(mean_c, cov_c)
+        E = r["mean_lnl"].reshape(M, C, T)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            # (pooled over ladders: every ladder proposes a pair equally often, so the mean of the ratios is the ratio)
+            swap = r["swap_accept"].reshape(M, C, T)[:, :, :T - 1].mean(axis=1)
+            lz_c = log_evidence(b, E)
+            lz = lz_c.mean(axis=1) if T > 1 else np.full(M, np.nan)
+            lz_err = lz_c.std(axis=1, ddof=1) / np.sqrt(C) if T > 1 and C > 1 else np.full(M, np.nan)
+        if one:
+            params, lnl = (params[0] if params is not None else None), (lnl[0] if lnl is not None else None)
+            acc, step, rh, mean, cov = acc[0], step[0], rh[0], mean[0], cov[0]
+            E, swap, lz, lz_err = E[0], swap[0], lz[0], lz_err[0]
+        return TemperedSamples(params, lnl, acc, step, rh, mean, cov, b, E, swap, lz, lz_err)
 
     def save(self):
         raise NotImplementedError("Not implemented yet.")

@@ -266,6 +266,46 @@ int v21_mlp_sample(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const f
 int v21_mlp_sample_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
                        const v21_sample_opts* opts, const double* d_eps_start, const v21_sample_out* out, int precision, int flags);
 
+/* ---- parallel tempering (replica exchange) of the sampler above: the modes a single chain cannot leave, and the evidence.
+ *   Rows and rungs.  A call has n rows; T = n_temps consecutive rows form one ladder (n % T == 0).  Row r is rung
+ *   k = r % T of ladder r / T and has beta = betas[k], inside [0, 1] and strictly decreasing in k.  The temperature belongs
+ *   to the row; states move between rows.  Step size, moments, counters and stored samples stay with the row, that is,
+ *   with the rung: rows with k = 0 and betas[0] = 1 are posterior chains, a row at beta = 0 samples the prior (the box).
+ *   Tempered transition.  That of v21_mlp_sample with ln L, g and F replaced by beta ln L, beta g and beta F wherever
+ *   they enter the drift, the metric and log alpha: G = beta F + ridge I and
+ *     log alpha = beta (lnL' - lnL) + log q(u | u') - log q(u' | u).
+ *   At beta = 0 the three products are exactly 0 whatever the evaluation holds, non-finite values included.  The state
+ *   keeps the un-tempered float32 ln L, g and F; samples_lnl and lnl_last are un-tempered, last_log_alpha is tempered.
+ *   Swap events.  Let S = step0 + (index of the transition in the call), the Philox step word.  With swap_every > 0 a
+ *   swap event follows the decision of transition S whenever (S + 1) % swap_every == 0 (warm-up transitions included);
+ *   its number is e = (S + 1) / swap_every - 1.  It proposes the pairs (k, k + 1) with k % 2 == e % 2 in every ladder.
+ *   Pair (k, k + 1) swaps iff log U < (beta_k - beta_k+1) (lnL_k+1 - lnL_k), formed in float64 from the stored float32
+ *   ln L, with U from word 0 of Philox block 3 of the lower row's chain at step S (blocks 0 .. 2 are the transition's); a
+ *   NaN right-hand side refuses.  On a swap the two rows exchange their point with its evaluation (u, ln L, g, F) and
+ *   nothing else: nothing is re-evaluated.
+ *   Order inside one transition: (1) the pending proposal is decided, (2) the step size adapted in warm-up, (3) the swap
+ *   event run, if any, (4) moments accumulated and the thinned sample stored -- both see the state after the swap --
+ *   (5) the next proposal drawn from that state.
+ *   Per row, beside the results of v21_sample_out, in float64 over the kept transitions (v21_temper_out): the mean and
+ *   the variance (divided by n_steps, as cov_u) of the un-tempered ln L after the swap event, and swap_accept = swaps
+ *   accepted / proposed with this row as the lower one of the pair (0 where none was proposed).  Averaged over ladders,
+ *   mean_lnl of rung k estimates E_beta_k[ln L], whose integral over beta from 0 to 1 is ln Z with Z = the integral of L
+ *   over the box divided by its volume 2^in_dim.
+ *   Invariance.  A draw depends only on (seed, chain, step, block) and a swap event only on S: results do not depend on
+ *   how a run is split over calls, host chunks or devices, provided no ladder is split.
+ *   temper: NULL = one rung at beta = 1 without swaps.  V21_ERR_ARG, the handle left usable: n_temps outside 1 .. 32, a
+ *   beta outside [0, 1] or not below its predecessor, swap_every < 0, n % n_temps != 0, or data given and
+ *   (n / n_data) % n_temps != 0 (a ladder would straddle two spectra).  Everything else -- in_dim <= 8, the input
+ *   transform and a likelihood record required, nuisance records, eps_start, continuation, the route counted once per
+ *   call -- as v21_mlp_sample; with n_temps = 1 every result of v21_sample_out equals that call's bit for bit.
+ * The host form works in chunks of the largest multiple of n_temps that is not above 8,192 rows. */
+int v21_mlp_sample_tempered(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
+                            const v21_sample_opts* opts, const v21_temper_opts* temper, const double* eps_start,
+                            const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags);
+int v21_mlp_sample_tempered_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                const v21_sample_opts* opts, const v21_temper_opts* temper, const double* d_eps_start,
+                                const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags);
+
 /* ---- linear nuisance modes (foregrounds) integrated out of the likelihood record.  Data model: d = y(x) + A^T a + noise,
  * A the (n_modes, out_dim) basis, 1 <= n_modes <= 8, with a FLAT PRIOR on the amplitudes a, which are integrated out
  * analytically.  With W = diag(w) the record's inverse variances, Q the W-orthonormalised basis (span Q = span A on the

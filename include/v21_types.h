@@ -43,4 +43,18 @@ typedef struct {
   float* last_prop_u;     /* (n, in_dim): the proposal of the last transition, u units */
   double* last_log_alpha; /* (n): its log acceptance ratio (-inf: outside the box or no Cholesky factor) */
 } v21_sample_out;
+/* the ladder of v21_mlp_sample_tempered[_dev] (a NULL pointer: one rung at beta = 1, no swaps).  The array is inline:
+ * no pointer crosses the ABI. */
+typedef struct {
+  int n_temps;          /* T, 1 .. 32: consecutive rows form one ladder, row r is rung r % T */
+  double betas[32];     /* inverse temperatures of the rungs, inside [0, 1], strictly decreasing; the first n_temps are read */
+  int swap_every;       /* a swap event after every swap_every-th transition (counted globally, from step0); 0: never */
+} v21_temper_opts;
+/* results of v21_mlp_sample_tempered[_dev] beside v21_sample_out, per row, every one nullable (host / device as there) */
+typedef struct {
+  double* mean_lnl;     /* (n): mean of the un-tempered ln L over the kept transitions (after their swap events) */
+  double* var_lnl;      /* (n): its variance over them (divided by n_steps) */
+  double* swap_accept;  /* (n): swaps accepted / proposed over the kept transitions with this row as the lower of the pair; 0
+                         * where none was proposed */
+} v21_temper_out;
 #endif /* V21_TYPES_H */
