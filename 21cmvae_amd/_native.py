@@ -153,6 +153,11 @@ SIGNATURES = {
     "v21_mlp_loglike_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int]),
     "v21_route_jacobian": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
     "v21_mlp_last_jac_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "v21_mlp_loglike_fwd": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, _F, C.c_int, C.c_int]),
+    "v21_mlp_loglike_fwd_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_int]),
+    "v21_route_loglike_fwd": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int)]),
+    "v21_mlp_last_lnl_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "v21_mlp_fisher": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, _F, _F, C.c_int, C.c_int]),
     "v21_mlp_fisher_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int]),
     "v21_mlp_fit": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(FitOpts), _P, _F, _F, _F, C.POINTER(C.c_int32),
@@ -225,6 +230,18 @@ def route_jacobian(dims, act, precision, n, flags=0):
     r = C.c_int(0)
     check(load_library().v21_route_jacobian(*_layers(dims, act), precision_id(precision), int(n), int(flags), C.byref(r)))
     return JAC_ROUTES[r.value]
+
+
+LNL_ROUTES = {1: "fused", 2: "two_launch"}
+
+
+def route_loglike_fwd(dims, act, precision, n, n_data=0, n_modes=0, flags=0):
+    """The route v21_mlp_loglike_fwd[_dev] takes for n rows of this stack against n_data data rows (0: the likelihood
+    record) with n_modes nuisance modes (pure host logic: no GPU).  -> name of LNL_ROUTES."""
+    r = C.c_int(0)
+    check(load_library().v21_route_loglike_fwd(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_modes),
+                                               int(flags), C.byref(r)))
+    return LNL_ROUTES[r.value]
 
 
 def nuisance_whiten(basis, inv_var):
@@ -753,6 +770,40 @@ class Stack(_Owned):
         with self.ctx.lock:
             check(self.lib.v21_mlp_loglike(self.h, x.ctypes.data_as(_P), dt, n, _fptr(lnl), _opt(g), precision_id(precision), flags))
         return (lnl, g) if grad else lnl
+
+    def loglike_fwd(self, x, precision="f32", flags=0, data=None):
+        """host (n, in) -> lnl (n,) float32 without a gradient and without a Jacobian (include/v21.h: v21_mlp_loglike_fwd):
+        against the record set_likelihood left, or against data (n_data, out) with n % n_data == 0, row i scored against
+        data row i // (n // n_data); the inverse variances are the record's either way."""
+        x, dt = self._rows(x)
+        n, dout = x.shape[0], self.dims[-1]
+        nd, dp = 0, None
+        if data is not None:
+            dp = np.ascontiguousarray(data, dtype=np.float32)
+            if dp.ndim == 1:
+                dp = dp[None, :]
+            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
+                raise ValueError("loglike_fwd: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
+            nd = dp.shape[0]
+            if n % nd:
+                raise ValueError("loglike_fwd: %d rows are not a multiple of %d data rows" % (n, nd))
+        lnl = np.empty(n, np.float32)
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_loglike_fwd(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, _fptr(lnl), precision_id(precision), flags))
+        return lnl
+
+    def loglike_fwd_dev(self, d_x, ldx, n, d_lnl, d_data=None, n_data=0, precision="f32", flags=0):
+        """v21_mlp_loglike_fwd_dev: device addresses, asynchronous on the context's stream"""
+        check(self.lib.v21_mlp_loglike_fwd_dev(self.h, _P(d_x), ldx, n, _opt(d_data), n_data, _P(d_lnl), precision_id(precision), flags))
+
+    def last_lnl_route(self):
+        """(route name of the last loglike_fwd / loglike_fwd_dev call, {route name: calls since creation})."""
+        (last,), (counts,) = _last_route(self.lib.v21_mlp_last_lnl_route, self.h, [LNL_ROUTES], slots=4)
+        return last, counts
+
+    def route_loglike_fwd(self, precision, n, n_data=0, flags=0):
+        """the route a loglike_fwd call of n rows against n_data data rows (0: the record) takes on this stack now"""
+        return route_loglike_fwd(self.dims, self.act, precision, n, n_data, self.nuisance_modes(), flags)
 
     def jacobian_dev(self, d_x, ldx, n, d_y, ldy, d_jac, precision="f32", flags=0):
         check(self.lib.v21_mlp_jacobian_dev(self.h, _P(d_x), ldx, n, _opt(d_y), ldy, _P(d_jac), precision_id(precision), flags))

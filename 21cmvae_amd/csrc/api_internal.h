@@ -237,6 +237,9 @@ struct v21_mlp {
   const float* lk_read() const { return nu_k ? lk_proj.get() : lk_data.get(); }
   int last_jac_route = 0;
   long long jac_route_count[4] = {0, 0, 0, 0};
+  // forward-only ln L (api_loglike.hip; routes.h: LnlRoute): the route of the last call and the calls per route
+  int last_lnl_route = 0;
+  long long lnl_route_count[4] = {0, 0, 0, 0};
 };
 // the layout of this stack's chain streams in `fmt`
 static inline ChainLayout chain_layout(const v21_mlp* m, ChainFmt fmt) {
@@ -254,13 +257,15 @@ static inline ChainLayout chain_layout(const v21_mlp* m, ChainFmt fmt) {
 }
 // api_forward.hip: fused_fwd's packed weight stream of this stack (built on first use)
 int mlp_fused_stream(v21_mlp* m, int prec, const unsigned char** stream);
-// api_jacobian.hip, shared with api_fit.hip.  The host forms work in chunks of kJacHostChunk rows; the likelihood
+// api_jacobian.hip, shared with api_fit.hip and api_loglike.hip.  The host forms work in chunks of kJacHostChunk rows; the likelihood
 // workspace holds kLkSlice rows.
 constexpr long long kJacHostChunk = 8192, kLkSlice = 16384;
 constexpr long long kNoPitch = LLONG_MAX;  // jac_args: the pitch of rows a call does not have
 // what an entry point is checked for beyond its arguments: its in_dim limit, whether it reads the likelihood record,
 // and whether it is a fit (input transform required, state checked even for n == 0)
 struct JacEntry { const char* name; int max_in; bool like, fit; };
+// archs.h holds this stack: it has compiled fused kernels (forward, ln L variant, Jacobian)
+bool jac_fused_compiled(int L, const int* dims, const int* act);
 // the checks of all eight entry points: the pointers they require (ptrs), n >= 0, pitches (ldx, ldy; host rows:
 // kNoPitch) and x_dtype, the entry's in_dim limit, then -- from here on only for n > 0, except for a fit -- precision and
 // the state the call needs.  Leaves flags with their defined bits only and, for n > 0, the context's device current.

@@ -25,7 +25,7 @@ typedef hipError_t (*jac_launcher)(const JacArgs&, hipStream_t);
 static const jac_launcher g_jac[][3] = {V21_ARCH_LIST(V21_ENTRY)};
 #undef V21_ENTRY
 
-static bool jac_fused_compiled(int L, const int* dims, const int* act) {
+bool jac_fused_compiled(int L, const int* dims, const int* act) {
 #define V21_MATCH(a)                                                                              \
   if (L == Arch##a::L && std::equal(dims, dims + L + 1, Arch##a::dims) && std::equal(act, act + L, Arch##a::act)) \
     return true;

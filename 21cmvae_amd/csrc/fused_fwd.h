@@ -87,6 +87,12 @@ struct FusedArgs {
   int in_transform;
   v21_affine_in tin;
   unsigned long long* dbg;      // diagnostic builds only (V21_FUSED_STAMP): cycle stamps
+  // ln L variants only (traits with LNL, below): y is then lnl (n_rows floats, ldy = 1) and workgroup g is scored
+  // against data row (lnl_wg0 + g) / lnl_wgpd of pitch lnl_ld (0: one shared record) with the inverse variances lnl_w
+  const float* lnl_d;
+  const float* lnl_w;
+  long long lnl_ld;
+  unsigned lnl_wg0, lnl_wgpd;
 };
 
 // ---- precision traits ------------------------------------------------------------
@@ -165,6 +171,13 @@ struct PrecBF16x2sp : PrecBF16x2 { static constexpr bool SPREAD_DMA = true; };
 // untimed repeat of the K launches through v21_debug_forward_clocked): the shipped kernels' ISA is untouched.
 struct PrecF16x2spClk : PrecF16x2sp { static constexpr bool CLOCK_STAMPS = true; };
 struct PrecBF16x2spClk : PrecBF16x2sp { static constexpr bool CLOCK_STAMPS = true; };
+// K12: the ln L variants -- the same stream, ring and arithmetic, but the output layer's epilogue, instead of storing y,
+// sums w (d - y)^2 per row in registers and the kernel ends with one cross-lane reduction and 4 bytes per row.
+struct PrecF32Lnl : PrecF32 { static constexpr bool LNL = true; };
+struct PrecF16x2spLnl : PrecF16x2sp { static constexpr bool LNL = true; };
+struct PrecBF16x2spLnl : PrecBF16x2sp { static constexpr bool LNL = true; };
+template <class P, class = void> struct lnl_of { static constexpr bool value = false; };
+template <class P> struct lnl_of<P, std::void_t<decltype(P::LNL)>> { static constexpr bool value = P::LNL; };
 template <class P, class = void> struct clk_of { static constexpr bool value = false; };
 template <class P> struct clk_of<P, std::void_t<decltype(P::CLOCK_STAMPS)>> { static constexpr bool value = P::CLOCK_STAMPS; };
 template <class P, class = void> struct spread_of { static constexpr bool value = false; };
@@ -174,6 +187,7 @@ template <class P> struct spread_of<P, std::void_t<decltype(P::SPREAD_DMA)>> { s
 // Arch::L layers, Arch::dims[L+1], Arch::act[L] (1 = ReLU).  The last layer is the
 // "output orientation" layer and must be linear.
 template <class Arch, class P> struct Geo {
+  using Prec = P;
   static constexpr int L = Arch::L;
   static constexpr int FPI = P::FPI;
   static constexpr int BLK = P::BLK, RING = P::RING, WAVES = P::WAVES;
@@ -344,7 +358,8 @@ __device__ __forceinline__ void ring_boundary(const unsigned char* gstream, unsi
     // during the consumption of block B-kRing+2; counting only stores issued after that
     // whole block (a lower bound of the true number) keeps the wait on the safe side.
     constexpr int S_issue = (B < kRing) ? 0 : (B - kRing + 2 + (SPREAD ? 1 : 0)) * kBlkFrags;
-    constexpr int SA = G::stores_before_step(S, CT, D) - G::stores_before_step(S_issue, CT, D);
+    // (an ln L variant issues no store inside the loop, and its d / w loads have landed before the ring prologue)
+    constexpr int SA = lnl_of<typename G::Prec>::value ? 0 : G::stores_before_step(S, CT, D) - G::stores_before_step(S_issue, CT, D);
     constexpr int N = (GA + SA) > 63 ? 63 : (GA + SA);
 #ifdef V21_FUSED_STAMP
     { unsigned long long t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
@@ -402,6 +417,61 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_fwd(const FusedAr
   }
   const long long wg_row0 = (long long)blockIdx.x * (kWaves * CT * 32);
   const long long row0 = wg_row0 + wave * (CT * 32);
+
+  // ---- ln L variants: the data row d of this workgroup and the inverse variances w at this lane's bins 32 nt + r live
+  // in registers through the output layer: one register per tile, d in the lanes of half h = 0 and w in those of
+  // h = 1 (both halves own the same bins; lnl_pair hands each lane both values of a tile with one v_permlane32_swap).
+  // The hidden layers, where both operand buffers are full, have no room for them, so they are asked for at the aux
+  // item of the output layer's first tile (lnl_load) and waited for before that layer's first MFMA (lnl_pin), by a
+  // wait the COMPILER places: it knows nothing of the DMAs in flight, so that wait drains them too, once per
+  // workgroup, and from there on the ring's counted waits see no operation but their own.  Until then they over-wait,
+  // never under-wait: the loads are younger operations that the counts leave out.  Nothing is read past out_dim.
+  // lnl_acc[i]: sum over the tiles of w (d - y)^2 of accumulator register i's row.  (The lane index is formed anew
+  // where it is needed: a register kept from the top of the kernel is one too many in the 352-wide layers.)
+  constexpr bool LNL = lnl_of<P>::value;
+  constexpr int NTO = G::nt_of(L - 1), NTL = LNL ? NTO : 1;
+  float lnl_x[NTL];
+  unsigned lnl_live = 0;  // bit nt: bin 32 nt + r is inside out_dim and has w != 0
+  float lnl_d = 0.f, lnl_w = 0.f;  // d and w of the tile whose epilogue is running
+  f32x16 lnl_acc;
+  static_assert(!LNL || (CT == 1 && NTO <= 32), "ln L variant: one column tile per wave, at most 32 output tiles");
+  auto lnl_lane = [&]() __attribute__((always_inline)) {
+    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  };
+  auto lnl_pair = [&](float x, float& d, float& w) __attribute__((always_inline)) {
+    // (x, x) -> ([x of h = 0 | x of h = 0], [x of h = 1 | x of h = 1])
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    const auto p2 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    d = __builtin_bit_cast(float, (unsigned)p2[0]);
+    w = __builtin_bit_cast(float, (unsigned)p2[1]);
+  };
+  auto lnl_load = [&]() __attribute__((always_inline)) {
+    const int ln = lnl_lane(), lr = ln & 31;
+    const unsigned drow = (a.lnl_wg0 + blockIdx.x) / a.lnl_wgpd;  // (workgroup-uniform)
+    const float* src = (ln >> 5) ? a.lnl_w : a.lnl_d + (long long)drow * a.lnl_ld;
+    static_for<NTO>([&](auto nt_) __attribute__((always_inline)) {
+      constexpr int nt = decltype(nt_)::value;
+      float v = 0.f;
+      if (32 * nt + 31 < NOUT || 32 * nt + lr < NOUT) v = src[32 * nt + lr];
+      lnl_x[nt] = v;
+    });
+  };
+  auto lnl_pin = [&]() __attribute__((always_inline)) {
+    // the empty statements use the loaded registers: the compiler's wait for them is placed here
+    static_for<NTO>([&](auto nt_) __attribute__((always_inline)) {
+      constexpr int nt = decltype(nt_)::value;
+      asm volatile("" : "+v"(lnl_x[nt]));
+      float d, w;
+      lnl_pair(lnl_x[nt], d, w);
+      lnl_live |= (w != 0.f ? 1u : 0u) << nt;  // (0 was put where the bin is past out_dim)
+    });
+#pragma unroll
+    for (int i = 0; i < 16; ++i) lnl_acc[i] = 0.f;
+  };
+  // the stream item at which the loads are issued: the aux fragment of the output layer's first tile, DEPTH items ahead
+  // of the wait (one tile earlier the last hidden layer's operands still fill the registers: S1 spilled 7 of them)
+  constexpr int LNL_S_LOAD = G::tile_base(L - 1, 0);
+  constexpr int LNL_C_PIN = G::tile_base(L - 1, 0) + 1;  // the output layer's first k-step
 
   // Operand registers of the two layers in flight, as 32-bit words (4 per item).
   unsigned bufA[CT][KSM][4], bufB[CT][KSM][4];
@@ -504,6 +574,7 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_fwd(const FusedAr
       const float obias = auxb[GT & 1][0], omean = auxb[GT & 1][1] * a.out_mean_scale;
       unsigned voff = ovoff + (unsigned)(32 * nt) * 4u;
       if (32 * nt + r >= NOUT) voff = 0xFFFFFFF0u;  // column past out_dim -> dropped
+      if constexpr (LNL && pr == 0) lnl_pair(lnl_x[nt], lnl_d, lnl_w);  // (a tile's chunks run in order)
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int i = 2 * pr + u;
@@ -515,7 +586,14 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_fwd(const FusedAr
           // exact mode: (acc + bias) * std + mean, each rounded to f32 as numpy does
           y = (acc[GT & 1][ct][i] + obias) * a.out_std + omean;
         }
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), orsrc, voff, soff, 0);
+        if constexpr (LNL) {
+          // the bin's term by SELECT: a bin that is not live adds nothing whatever d holds there (inf, NaN)
+          const float res = lnl_d - y, wr = lnl_w * res;
+          const float sum = __builtin_fmaf(wr, res, lnl_acc[i]);
+          lnl_acc[i] = ((lnl_live >> nt) & 1u) ? sum : lnl_acc[i];
+        } else {
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), orsrc, voff, soff, 0);
+        }
       }
     }
   };
@@ -535,6 +613,7 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_fwd(const FusedAr
     // ---- load side: item S
     if constexpr (S < TOTAL) {
       ring_boundary<G, CT, D, S, SPREAD>(a.stream, smem, wave, lane, a.dbg);
+      if constexpr (LNL && S == LNL_S_LOAD) lnl_load();
       if constexpr (SPREAD && S / kBlkFrags >= 2) {
         // refill of slot (B-2), spread over the block being consumed: EVERY wave issues its piece o/W of block
         // B+kRing-2 at offsets o = 0, W, 2W, ... (W = waves) -- one DMA per W k-steps instead of a burst of
@@ -571,6 +650,7 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_fwd(const FusedAr
     if constexpr (S >= D) {
       constexpr int C = S - D;
       constexpr Item it = G::item_at(C);
+      if constexpr (LNL && C == LNL_C_PIN) lnl_pin();
       if constexpr (it.ks >= 0) {
         constexpr int GT = G::gtile(it.l, it.nt);
         constexpr int GP = GT > 0 ? GT - 1 : 0;  // previous tile: its epilogue is pending
@@ -611,6 +691,34 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_fwd(const FusedAr
   });
   epilogue_range(std::integral_constant<int, G::n_tiles() - 1>{}, std::integral_constant<int, 0>{},
                  std::integral_constant<int, NCH>{});
+  if constexpr (LNL) {
+    // Register i of lane half h holds row (i & 3) + 8 (i >> 2) + 4 h summed over this lane's bins; the 32 lanes of the
+    // half hold the rest.  Butterfly over lane bits 4 .. 1 that halves the registers at every step (the lane whose bit
+    // is set keeps the upper half of them and hands over the lower), then bit 0: 8 + 4 + 2 + 1 + 1 cross-lane moves
+    // (ds_bpermute: the LDS crossbar, no LDS memory).  Lanes r and r ^ 1 end with register i = r >> 1.
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = lnl_acc[i];
+    const int ln = lnl_lane(), lr = ln & 31, lh = ln >> 5;
+    auto xlane = [&](float x, int m) __attribute__((always_inline)) {
+      return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((ln ^ m) << 2, __builtin_bit_cast(int, x)));
+    };
+    static_for<4>([&](auto s_) __attribute__((always_inline)) {
+      constexpr int c = 8 >> decltype(s_)::value, m = 16 >> decltype(s_)::value;
+      const bool up = (lr & m) != 0;
+#pragma unroll
+      for (int j = 0; j < c; ++j) {
+        const float keep = up ? v[c + j] : v[j], send = up ? v[j] : v[c + j];
+        v[j] = keep + xlane(send, m);
+      }
+    });
+    const float total = v[0] + xlane(v[0], 1);
+    const int i = lr >> 1;
+    const unsigned row = (unsigned)(wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh);
+    // (rows past n_rows fall outside the workgroup's buffer resource, ldy = 1; odd lanes hold copies)
+    const unsigned loff = (lr & 1) ? 0xFFFFFFF0u : row * 4u;
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, -0.5f * total), orsrc, loff, 0, 0);
+  }
   if constexpr (clk_of<P>::value) {
     // after the wave's last output store has been ISSUED (the stores drain behind it; the next launch's start stamp
     // cannot precede them on an in-order stream)

@@ -176,4 +176,51 @@ __global__ void __launch_bounds__(256) jac_reduce_kernel(const float* __restrict
   }
 }
 
+// The forward-only sibling (api_loglike.hip, the two-launch route): ln L of rows of y alone -- no Jacobian is read or
+// exists.  The same lanes, bins, skip of w == 0 bins, arithmetic and shuffle order as jac_reduce_kernel's ln L, so that
+// on equal y both give equal bits; with a nuisance record (NK > 0) lnl = -1/2 (r^T W r - b^T b) from the stored Q, the
+// float32 sums combined in float64 and rounded once.  y: (n_rows, ldy) of one slice whose first row is row0 of the call.
+template <int NK>
+__global__ void __launch_bounds__(256) lnl_reduce_kernel(const float* __restrict__ y, long long ldy, const float* __restrict__ data,
+                                                         long long ld_data, long long rows_per_data, long long row0,
+                                                         const float* __restrict__ wv, const float* __restrict__ q, int nk,
+                                                         float* __restrict__ lnl, long long n_rows, int dout) {
+  const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (n >= n_rows) return;  // (whole waves)
+  const float* d = data + ((row0 + n) / rows_per_data) * ld_data;
+  float lp = 0.f;
+  NuisSums<1, NK> ns;
+  for (int k = lane; k < dout; k += 64) {
+    const float w = wv[k];
+    if (w == 0.f) continue;
+    const float r = d[k] - y[n * ldy + k], wr = w * r;
+    lp += wr * r;
+    if constexpr (NK > 0) {
+#pragma unroll
+      for (int m = 0; m < NK; ++m)
+        if (m < nk) ns.b[m] += q[(long long)m * dout + k] * wr;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    lp += __shfl_xor(lp, o);
+    if constexpr (NK > 0) {
+#pragma unroll
+      for (int m = 0; m < NK; ++m)
+        if (m < nk) ns.b[m] += __shfl_xor(ns.b[m], o);
+    }
+  }
+  if (lane != 0) return;
+  if constexpr (NK > 0) {
+    double s = 0.0;
+#pragma unroll
+    for (int m = 0; m < NK; ++m)
+      if (m < nk) s += (double)ns.b[m] * (double)ns.b[m];
+    lnl[n] = (float)(-0.5 * ((double)lp - s));
+  } else {
+    lnl[n] = -0.5f * lp;
+  }
+}
+
 }  // namespace v21

@@ -259,4 +259,27 @@ inline int decide_jacobian(bool fused_compiled, int in_dim, int flags, long long
   return fused ? JAC_FUSED : JAC_GENERIC;
 }
 
+// ---- forward-only Gaussian log-likelihood (v21_mlp_loglike_fwd[_dev]): ln L without its gradient, the call an outside
+// sampler makes.  Its own enum and counters: the Jacobian's routes above are untouched by it.
+enum LnlRoute {
+  LNL_NONE = 0,
+  LNL_FUSED = 1,  // the ln L variant of fused_fwd<Arch, Prec> (fused_fwd.h: traits with LNL): chi-square reduced in the epilogue
+  LNL_TWO = 2,    // the forward on its own route into the likelihood workspace, then lnl_reduce_kernel (reduce_kernels.h)
+};
+constexpr int kLnlWgRows = 128;  // rows per workgroup of the ln L variants: one data row per workgroup
+// fused_compiled: archs.h holds the stack (no ReLU end, no Gauss layer); n_modes: the handle's nuisance modes; rpd: rows
+// per data row of the call's data matrix (0: the record); n: the rows of the whole call.  Uniformity is decided HERE, once
+// per call: the host form cuts a call into chunks of lnl_host_chunk rows, whole spectra that start on a workgroup boundary
+// whenever rpd is a multiple of kLnlWgRows, so a chunk never needs a decision of its own.
+inline long long lnl_host_chunk(long long chunk_rows, long long rpd) {
+  return rpd > 0 && rpd <= chunk_rows ? chunk_rows / rpd * rpd : chunk_rows;
+}
+inline int decide_loglike_fwd(bool fused_compiled, int in_dim, int n_modes, long long rpd, long long n, int flags) {
+  const bool forced = (flags & (V21_FWD_FORCE_GENERIC | V21_FWD_FORCE_CHAIN | V21_FWD_FORCE_JIT)) != 0;
+  const bool tin_ok = !(flags & V21_FWD_IN_TRANSFORM) || in_dim <= 8;
+  const bool uniform = rpd == 0 || rpd % kLnlWgRows == 0;  // one data row per workgroup
+  const bool range = n / kLnlWgRows < (1ll << 31);         // (32-bit workgroup numbers)
+  return fused_compiled && !forced && tin_ok && n_modes == 0 && uniform && range ? LNL_FUSED : LNL_TWO;
+}
+
 }  // namespace v21

@@ -235,6 +235,54 @@ def foreground_basis(frequencies, nb, foreground, flow, fhigh):
     return A
 
 
+class LogPosterior:
+    """ln L of one observed signal under the uniform prior on the training box, for an outside sampler (made by
+    ``log_posterior``).  The box is [-1, 1]^7 in par_transform's coordinates u: uniform in the linear columns, log-uniform
+    in the log10 columns.  The prior's constant is left out, as ln L's is: inside the box the value is ln L.
+    ``lp(theta)``: theta (7,) or (n, 7) raw parameters -> a float or (n,) float64; -inf for every row with a coordinate
+    outside the box (or not finite), and such rows are never sent to the device.
+    ``lp.prior_transform(cube)``: (7,) or (n, 7) points of the unit cube -> raw parameters, uniform in u
+    (``preprocess.par_untransform``) -- the form nested samplers ask for.
+    The data / sigma record is uploaded when the object is made and again only if another call replaced it."""
+
+    def __init__(self, em, data, sigma, flow=None, fhigh=None, foreground=None):
+        self.em = em
+        self.ndim = len(em.par_labels)
+        model, st, flags, _ = em._diff_stack(np.zeros((1, self.ndim)))
+        nb = st.dims[-1]
+        self._d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
+        self._w = em._band_weights(nb, sigma, flow, fhigh)
+        self._fg, self._band = foreground, (flow, fhigh)
+        self._record(st)
+
+    def _record(self, st):
+        self.em._use_record(st, self._d, self._w, self._fg, *self._band)
+
+    def inside(self, theta):
+        """(n,) bool: the rows of raw parameters inside the training box"""
+        x = np.array(theta, np.float64, ndmin=2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            u = pp.par_transform(x, self.em.par_train)
+        return np.all(np.isfinite(u) & (np.abs(u) <= 1.0), axis=1)
+
+    def __call__(self, theta):
+        x = np.array(theta, np.float64, ndmin=2)
+        if x.ndim != 2 or x.shape[1] != self.ndim:
+            raise ValueError("expected parameters of shape (%d,) or (n, %d), got %r" % (self.ndim, self.ndim, np.shape(theta)))
+        ok = self.inside(x)
+        out = np.full(x.shape[0], -np.inf, np.float64)
+        if ok.any():
+            model, st, flags, rows = self.em._diff_stack(x[ok])
+            self._record(st)
+            out[ok] = st.loglike_fwd(rows, model.precision, flags)
+        return float(out[0]) if np.ndim(theta) == 1 else out
+
+    def prior_transform(self, cube):
+        c = np.array(cube, np.float64, ndmin=2)
+        x = pp.par_untransform(2.0 * c - 1.0, self.em.par_train)
+        return x[0] if np.ndim(cube) == 1 else x
+
+
 class _EmulatorBase:
     par_labels = ["fstar", "Vc", "fx", "tau", "alpha", "nu_min", "Rmfp"]
 
@@ -311,7 +359,7 @@ class _EmulatorBase:
             y, J = y[0], J[0]
         return (y, J) if return_signal else J
 
-    def log_likelihood(self, params, data, sigma, flow=None, fhigh=None, grad=False, foreground=None):
+    def log_likelihood(self, params, data, sigma, flow=None, fhigh=None, grad=False, foreground=None, forward_only=False):
         """Gaussian ln L = -1/2 sum_k (data_k - signal_k)^2 / sigma_k^2 over the bins of the band [flow, fhigh] of
         ``self.frequencies`` (as ``error`` selects them; bins outside get weight 0), and with grad=True its gradient
         with respect to the raw parameters -- both reduced on the device (not in the reference).  ``sigma``: a scalar or
@@ -321,7 +369,17 @@ class _EmulatorBase:
         whose amplitudes get a flat prior and are integrated out analytically on the device (include/v21.h:
         v21_mlp_set_nuisance) -- an int K for K LinLog terms (``foregrounds.linlog_basis``) over the selected band, or
         any (K, 451) basis, K <= 8.  ln L is then the profile likelihood over the amplitudes, unchanged by adding any
-        combination of the modes to ``data``, which may carry the full foreground (10^6 mK and more) in float32."""
+        combination of the modes to ``data``, which may carry the full foreground (10^6 mK and more) in float32.
+        ``forward_only=True`` (only with grad=False): the same ln L from the forward-only entry (include/v21.h:
+        v21_mlp_loglike_fwd) -- no Jacobian is formed; on the compiled stacks chi-square is reduced inside the forward
+        kernel.  It agrees with the default to float32 rounding of the sums, not bit for bit.  With it ``data`` may also be
+        (M, 451): 2-D params (R, 7) are then ALWAYS scored against every spectrum (also when R is a multiple of M); 3-D
+        params (M, R, 7) block m against spectrum m -- reshape a flat (M R, 7) array to that; the result is (M, R).
+        Without ``forward_only`` nothing changes."""
+        if forward_only:
+            if grad:
+                raise ValueError("log_likelihood: forward_only computes no gradient (grad must be False)")
+            return self._log_likelihood_fwd(params, data, sigma, flow, fhigh, foreground)
         model, st, flags, x = self._diff_stack(params)
         nb = st.dims[-1]
         d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
@@ -332,6 +390,43 @@ class _EmulatorBase:
             lnl, g = out
             return (lnl[0], g[0]) if x.shape[0] == 1 else (lnl, g)
         return out[0] if x.shape[0] == 1 else out
+
+    def _log_likelihood_fwd(self, params, data, sigma, flow, fhigh, foreground):
+        """log_likelihood(forward_only=True): one spectrum as the default call, (M, 451) spectra -> (M, R)"""
+        dat = np.asarray(data, np.float32)
+        p = np.asarray(params)
+        nb, din = int(np.shape(self.signal_train)[-1]), len(self.par_labels)
+        if dat.ndim > 2 or (dat.ndim == 2 and (dat.shape[1] != nb or dat.shape[0] < 1)):
+            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        if dat.ndim < 2:
+            if p.ndim > 2:
+                raise ValueError("log_likelihood: per-spectrum parameters (M, R, %d) need data of shape (M, %d)" % (din, nb))
+            model, st, flags, x = self._diff_stack(p)
+            d = np.ascontiguousarray(np.broadcast_to(dat, (nb,)))
+            self._use_record(st, d, self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
+            out = st.loglike_fwd(x, model.precision, flags)
+            return out[0] if x.shape[0] == 1 else out
+        M = dat.shape[0]
+        if p.ndim == 3:
+            if p.shape[0] != M:
+                raise ValueError("log_likelihood: per-spectrum parameters must be (%d, R, %d), got %r" % (M, din, np.shape(params)))
+            rows = p.reshape(M * p.shape[1], p.shape[2])
+        elif p.ndim <= 2:
+            rows = np.tile(p[None, :] if p.ndim == 1 else p, (M, 1))
+        else:
+            raise ValueError("log_likelihood: parameters must be (%d,), (R, %d) or (%d, R, %d), got %r" % (din, din, M, din, np.shape(params)))
+        R = rows.shape[0] // M
+        model, st, flags, x = self._diff_stack(rows)
+        dat = np.ascontiguousarray(dat)
+        self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
+        return st.loglike_fwd(x, model.precision, flags, data=dat).reshape(M, R)
+
+    def log_posterior(self, data, sigma, flow=None, fhigh=None, foreground=None):
+        """The log-posterior of the parameters given one observed signal, as an object to hand to an outside sampler
+        (nested, ensemble, importance; not in the reference): a ``LogPosterior``.  ``lp(theta)``: float64 ln L of
+        ``log_likelihood(forward_only=True)`` under the uniform prior on the training box in par_transform's coordinates,
+        -inf outside the box; ``lp.prior_transform(cube)``: the unit cube -> raw parameters, uniform in those coordinates."""
+        return LogPosterior(self, data, sigma, flow, fhigh, foreground)
 
     def _use_record(self, st, d, w, foreground, flow, fhigh):
         """the likelihood record (d, w) and the nuisance basis of ``foreground`` (None: none) on the stack"""

@@ -198,6 +198,35 @@ int v21_mlp_loglike_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, 
 int v21_route_jacobian(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int* route);
 int v21_mlp_last_jac_route(v21_mlp* mlp, int* route, long long counts[4]);
 
+/* ---- forward-only log-likelihood: lnl[n] = -1/2 sum_k w_k (d_k - y_k)^2 WITHOUT its gradient -- the call nested
+ * samplers, ensemble samplers and importance sampling make.  No Jacobian is formed.
+ *   data == NULL: every row is scored against the likelihood record (v21_mlp_set_likelihood, required either way: the
+ *     inverse variances are always the record's).  Otherwise data is (n_data, out_dim) float32 with n % n_data == 0
+ *     and row n is scored against data row n / (n / n_data), as in v21_mlp_fit (V21_ERR_ARG otherwise).  Bins with
+ *     w == 0 do not influence the result whatever d holds there (inf and NaN included), and with a nuisance record
+ *     (v21_mlp_set_nuisance) the result is lnL_m = -1/2 (r^T W r - |b|^2), as v21_mlp_loglike's.
+ *   flags: V21_FWD_IN_TRANSFORM / V21_FWD_OUT_TRANSFORM and the forward's route flags, as for v21_mlp_forward_dev.
+ * Routes (v21_route_loglike_fwd; csrc/routes.h: 1 = fused, 2 = two-launch).  Fused: the ln L variant of
+ *   fused_fwd<Arch, Prec> for the stacks of archs.h -- y is computed with the forward's fused-route arithmetic bit for
+ *   bit (for any n: there is no few-row route here) and reduced in the output layer's epilogue, 4 bytes per row leave
+ *   the kernel.  It takes a call whose data are uniform per 128-row workgroup: the record, or n / n_data a multiple of
+ *   128; no nuisance record, no forward route flag.  Two-launch: everything else -- stacks outside archs.h, stacks
+ *   ending in a ReLU, V21_ACT_GAUSS, nuisance records, other data layouts: the forward on the route its own decision
+ *   gives for these rows and flags (counted by v21_mlp_last_route; a call of more than V21_SMALL_BATCH_ROWS rows keeps
+ *   all its slices off the few-row route) into the likelihood workspace in slices of 16,384 rows, y only, then one
+ *   row reduction.  n = 0 is a no-op.  The _dev form never synchronises; the host form works in chunks of 8,192 rows,
+ *   rounded down to whole spectra when data is given, and returns when the results are in place.
+ *   v21_route_loglike_fwd: the route of a call of n rows against n_data data rows (0: the record) for a handle with
+ *   n_modes nuisance modes -- pure host logic.  v21_mlp_last_lnl_route: the route of the last of these calls and the
+ *   calls per route (counts[4], indexed by route); v21_mlp_last_jac_route is not touched by them. */
+int v21_mlp_loglike_fwd(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, const float* data, int64_t n_data, float* lnl,
+                        int precision, int flags);
+int v21_mlp_loglike_fwd_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                            float* d_lnl, int precision, int flags);
+int v21_route_loglike_fwd(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_modes,
+                          int flags, int* route);
+int v21_mlp_last_lnl_route(v21_mlp* mlp, int* route, long long counts[4]);
+
 /* ---- Fisher matrices and batched maximum-likelihood fits, on the Jacobian of the block above.
  *   v21_mlp_fisher[_dev]  fisher[n, i, j] = sum_k w_k jac[n, i, k] jac[n, j, k], (n, in_dim, in_dim) float32, exactly
  *     symmetric, with w the inverse variances of the likelihood record (v21_mlp_set_likelihood, required) and jac as
