@@ -91,6 +91,23 @@ class TemperOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in TEMPER_OUTPUTS]
 
 
+class EnsembleOpts(C.Structure):
+    """v21_ensemble_opts (include/v21_types.h)"""
+    _fields_ = [("n_walkers", C.c_int), ("a", C.c_double), ("n_steps", C.c_int), ("n_warmup", C.c_int), ("thin", C.c_int),
+                ("seed", C.c_ulonglong), ("chain0", C.c_longlong), ("step0", C.c_longlong)]
+
+
+ENSEMBLE_DEFAULTS = {"n_walkers": 64, "a": 2.0, "n_steps": 1000, "n_warmup": 500, "thin": 1, "seed": 0, "chain0": 0, "step0": 0}
+ENSEMBLE_OUTPUTS = ("samples", "samples_lnl", "x_last", "lnl_last", "accept_rate", "mean_u", "cov_u", "last_prop_u", "last_log_alpha",
+                    "last_partner")
+ENSEMBLE_MAX_WALKERS = 512
+
+
+class EnsembleOut(C.Structure):
+    """v21_ensemble_out (include/v21_types.h): host or device addresses, NULL = not asked for"""
+    _fields_ = [(k, C.c_void_p) for k in ENSEMBLE_OUTPUTS]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 # name -> (restype, argtypes); every symbol include/v21.h declares
@@ -171,6 +188,12 @@ SIGNATURES = {
                                           C.POINTER(SampleOut), C.POINTER(TemperOut), C.c_int, C.c_int]),
     "v21_mlp_sample_tempered_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(SampleOpts), C.POINTER(TemperOpts), _P,
                                               C.POINTER(SampleOut), C.POINTER(TemperOut), C.c_int, C.c_int]),
+    "v21_mlp_sample_ensemble": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(EnsembleOpts), C.POINTER(EnsembleOut),
+                                          C.c_int, C.c_int]),
+    "v21_mlp_sample_ensemble_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(EnsembleOpts), C.POINTER(EnsembleOut),
+                                              C.c_int, C.c_int]),
+    "v21_route_ensemble": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "v21_nuisance_whiten": (C.c_int, [C.POINTER(C.c_double), _F, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "v21_mlp_set_nuisance": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, C.c_int32]),
     "v21_mlp_nuisance_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
@@ -242,6 +265,16 @@ def route_loglike_fwd(dims, act, precision, n, n_data=0, n_modes=0, flags=0):
     check(load_library().v21_route_loglike_fwd(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_modes),
                                                int(flags), C.byref(r)))
     return LNL_ROUTES[r.value]
+
+
+def route_ensemble(dims, act, precision, n, n_walkers, n_data=0, n_modes=0, flags=0, host_form=False):
+    """The route v21_mlp_sample_ensemble[_dev] takes for n rows in ensembles of n_walkers against n_data data rows (0: the
+    likelihood record) with n_modes nuisance modes, and the rows of a host chunk (the _dev form: n) (pure host logic: no
+    GPU; EngineError for the shapes the library refuses).  -> (name of LNL_ROUTES, chunk rows)."""
+    r, c = C.c_int(0), C.c_int64(0)
+    check(load_library().v21_route_ensemble(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_walkers),
+                                            int(n_modes), int(flags), 1 if host_form else 0, C.byref(r), C.byref(c)))
+    return LNL_ROUTES[r.value], int(c.value)
 
 
 def nuisance_whiten(basis, inv_var):
@@ -1010,6 +1043,86 @@ class Stack(_Owned):
         to = TemperOut(**{k: int(v) for k, v in (tout or {}).items() if v})
         check(self.lib.v21_mlp_sample_tempered_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), C.byref(t), _opt(d_eps_start),
                                                    C.byref(so), C.byref(to), precision_id(precision), flags))
+
+    @staticmethod
+    def ensemble_opts(n_walkers=None, a=None, n_steps=None, n_warmup=None, thin=None, seed=None, chain0=None, step0=None, n=None,
+                      n_data=0, in_dim=None):
+        """v21_ensemble_opts with the defaults of ENSEMBLE_DEFAULTS for None; ValueError for what the library would refuse
+        -- with in_dim also an ensemble too small for its dimension, with n (and n_data, 0: the record's data) also the
+        rows of a call that are no whole ensembles, or whose ensembles would straddle two data rows"""
+        o = dict(ENSEMBLE_DEFAULTS)
+        o.update({k: v for k, v in (("n_walkers", n_walkers), ("a", a), ("n_steps", n_steps), ("n_warmup", n_warmup), ("thin", thin),
+                                    ("seed", seed), ("chain0", chain0), ("step0", step0)) if v is not None})
+        for k in ("n_walkers", "n_steps", "n_warmup", "thin", "chain0", "step0", "seed"):
+            if int(o[k]) != o[k] or int(o[k]) < 0:
+                raise ValueError("sample_ensemble: %s = %r (a non-negative integer)" % (k, o[k]))
+        if int(o["n_steps"]) >= 2 ** 31 or int(o["n_warmup"]) >= 2 ** 31 or int(o["thin"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64:
+            raise ValueError("sample_ensemble: count out of range")
+        if int(o["step0"]) + int(o["n_warmup"]) + int(o["n_steps"]) >= 2 ** 32:
+            raise ValueError("sample_ensemble: step0 + n_warmup + n_steps must stay below 2^32")
+        if not (float(o["a"]) > 1.0 and np.isfinite(float(o["a"]))):
+            raise ValueError("sample_ensemble: a = %r (above 1 and finite)" % (o["a"],))
+        W = int(o["n_walkers"])
+        lo = 2 * (int(in_dim) + 1) if in_dim is not None else 2
+        if W % 2 or not lo <= W <= ENSEMBLE_MAX_WALKERS:
+            raise ValueError("sample_ensemble: n_walkers = %d (even, %d .. %d)" % (W, lo, ENSEMBLE_MAX_WALKERS))
+        if n is not None and (n % W or (n_data and (n // n_data) % W)):
+            raise ValueError("sample_ensemble: %d rows%s are no whole ensembles of %d" % (n, " over %d data rows" % n_data if n_data else "", W))
+        return EnsembleOpts(W, float(o["a"]), int(o["n_steps"]), int(o["n_warmup"]), int(o["thin"]), int(o["seed"]), int(o["chain0"]),
+                            int(o["step0"]))
+
+    def sample_ensemble(self, x0, n_walkers=64, precision="f32", flags=0, data=None, samples=True, diagnostics=False, **opts):
+        """Posterior sampling with the affine-invariant ensemble sampler (Goodman & Weare's stretch move) on forward-only
+        ln L, on the device (include/v21.h: v21_mlp_sample_ensemble; needs the input transform and a likelihood record).
+        n_walkers consecutive rows of x0 form one ensemble (even, at least 2 (in + 1), at most 512); the target is
+        ``sample``'s.  x0: (n, in) raw starts, float32 or float64; data as for fit (the rows of one spectrum must be whole
+        ensembles); opts: a, n_steps, n_warmup, thin, seed, chain0, step0 (ENSEMBLE_DEFAULTS).
+        -> dict x_last (n, in) in x0's dtype, lnl_last (n,) float32, accept_rate (n,), mean_u (n, in), cov_u (n, in, in)
+        float64 -- the per-walker moments of u over the n_steps kept sweeps -- and, with samples and thin > 0, samples
+        (n, n_steps // thin, in) in x0's dtype and samples_lnl; with diagnostics, last_prop_u (n, in) float32,
+        last_log_alpha (n,) float64 and last_partner (n,) int32 of the last sweep."""
+        x, dt = self._rows(x0)
+        n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
+        if din > 8:
+            raise ValueError("sample_ensemble: %d parameters (at most 8)" % din)
+        nd, dp = 0, None
+        if data is not None:
+            dp = np.ascontiguousarray(data, dtype=np.float32)
+            if dp.ndim == 1:
+                dp = dp[None, :]
+            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
+                raise ValueError("sample_ensemble: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
+            nd = dp.shape[0]
+            if n % nd:
+                raise ValueError("sample_ensemble: %d rows are not a multiple of %d data rows" % (n, nd))
+        o = self.ensemble_opts(n_walkers, n=n, n_data=nd, in_dim=din, **opts)
+        keep = o.n_steps // o.thin if o.thin > 0 else 0
+        res = {"x_last": np.empty_like(x), "lnl_last": np.empty(n, np.float32), "accept_rate": np.empty(n, np.float64),
+               "mean_u": np.empty((n, din), np.float64), "cov_u": np.empty((n, din, din), np.float64)}
+        if samples and keep > 0:
+            res["samples"] = np.empty((n, keep, din), x.dtype)
+            res["samples_lnl"] = np.empty((n, keep), np.float32)
+        if diagnostics:
+            res["last_prop_u"] = np.empty((n, din), np.float32)
+            res["last_log_alpha"] = np.empty(n, np.float64)
+            res["last_partner"] = np.empty(n, np.int32)
+        out = EnsembleOut(**{k: v.ctypes.data for k, v in res.items()})
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_sample_ensemble(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(o), C.byref(out),
+                                                   precision_id(precision), flags))
+        return res
+
+    def sample_ensemble_dev(self, d_x0, ldx, n, d_data, n_data, out, n_walkers=64, precision="f32", flags=0, **opts):
+        """v21_mlp_sample_ensemble_dev: out is a dict of device addresses by the names of ENSEMBLE_OUTPUTS (x_last required;
+        samples float32); asynchronous on the context's stream."""
+        o = self.ensemble_opts(n_walkers, **opts)
+        so = EnsembleOut(**{k: int(v) for k, v in out.items() if v})
+        check(self.lib.v21_mlp_sample_ensemble_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), C.byref(so),
+                                                   precision_id(precision), flags))
+
+    def route_ensemble(self, precision, n, n_walkers, n_data=0, flags=0, host_form=False):
+        """(route, chunk rows) a sample_ensemble call of n rows in ensembles of n_walkers takes on this stack now"""
+        return route_ensemble(self.dims, self.act, precision, n, n_walkers, n_data, self.nuisance_modes(), flags, host_form)
 
     def last_jac_route(self):
         """(route name of the last Jacobian / log-likelihood call, {route name: calls since creation})."""

@@ -1,0 +1,176 @@
+// api_ensemble.hip -- the affine-invariant ensemble sampler on the device (include/v21.h: v21_mlp_sample_ensemble[_dev],
+// v21_route_ensemble): Goodman & Weare's stretch move (ensemble_kernels.h) on forward-only ln L.  The loop is the
+// sampler's (api_sample.hip) with the Fisher evaluation replaced by lnl_run of api_loglike.hip: the walkers stay on the
+// device, every half-move is one evaluation of the n / 2 pending proposals in their compacted layout (on u, without the
+// input transform) and one ensemble_step_kernel launch, and the host only launches.  Routes: csrc/routes.h
+// (decide_ensemble), decided once per call and counted once by v21_mlp_last_lnl_route.
+#include "api_internal.h"
+#include "ensemble_kernels.h"
+
+static v21_ensemble_opts ensemble_defaults() {
+  v21_ensemble_opts o;
+  o.n_walkers = 64;
+  o.a = 2.0;
+  o.n_steps = 1000;
+  o.n_warmup = 500;
+  o.thin = 1;
+  o.seed = 0;
+  o.chain0 = 0;
+  o.step0 = 0;
+  return o;
+}
+
+static long long ensemble_keep(const v21_ensemble_opts& o) { return o.thin > 0 ? o.n_steps / o.thin : 0; }
+
+// the stretch scale and the counts (sample_check's ranges)
+static int ensemble_check(const v21_ensemble_opts& o) {
+  if (!(o.a > 1.0) || !std::isfinite(o.a)) return fail(V21_ERR_ARG, "sample_ensemble: a = %g (above 1 and finite)", o.a);
+  v21_sample_opts s{};
+  s.n_steps = o.n_steps; s.n_warmup = o.n_warmup; s.thin = o.thin;
+  s.eps0 = 1.0; s.ridge = 1.0; s.target_accept = 0.5;
+  s.seed = o.seed; s.chain0 = o.chain0; s.step0 = o.step0;
+  return sample_check(s);
+}
+
+// how the call's n rows (with data: the n / n_data rows of a spectrum) divide into ensembles of W walkers in din dimensions
+static int ensemble_shape(int W, int din, long long n, bool has_data, long long n_data) {
+  if (W < 2 || W % 2 != 0 || W < 2 * (din + 1) || W > kEnsMaxWalkers)
+    return fail(V21_ERR_ARG, "sample_ensemble: n_walkers = %d (even, %d .. %d for %d parameters)", W, 2 * (din + 1), kEnsMaxWalkers, din);
+  if (n % W != 0) return fail(V21_ERR_ARG, "sample_ensemble: n = %lld rows are no whole ensembles of %d", n, W);
+  if (has_data && n > 0 && (n / n_data) % W != 0)
+    return fail(V21_ERR_ARG, "sample_ensemble: %lld rows per data row are no whole ensembles of %d", n / n_data, W);
+  return V21_OK;
+}
+
+extern "C" int v21_route_ensemble(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
+                                  int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows) {
+  if (!dims || !act || !route) return fail(V21_ERR_ARG, "null argument");
+  if (n_layers < 1 || n_layers > 16) return fail(V21_ERR_ARG, "n_layers %d out of range", n_layers);
+  for (int l = 0; l <= n_layers; ++l)
+    if (dims[l] < 1) return fail(V21_ERR_ARG, "dims[%d] = %d", l, dims[l]);
+  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
+  if (n < 0 || n_data < 0 || n_modes < 0 || n_modes > 8) return fail(V21_ERR_ARG, "n = %lld, n_data = %lld, n_modes = %d", (long long)n, (long long)n_data, n_modes);
+  if (dims[0] > kFitMaxIn) return fail(V21_ERR_UNSUPPORTED, "sample_ensemble: %d inputs (at most %d)", dims[0], kFitMaxIn);
+  CHK(call_data_args("sample_ensemble", n, n_data > 0, n_data));
+  CHK(ensemble_shape(n_walkers, dims[0], n, n_data > 0, n_data));
+  const EnsRoute r = decide_ensemble(jac_fused_compiled(n_layers, dims, act), dims[0], n_modes, n_data > 0 ? n / n_data : 0, n, n_walkers,
+                                     flags & 0xFF, host_form != 0, kJacHostChunk);
+  *route = r.route;
+  if (chunk_rows) *chunk_rows = r.chunk;
+  return V21_OK;
+}
+
+// the route of one entry-point call, counted once
+static EnsRoute ensemble_route(v21_mlp* m, long long rpd, long long n, int W, int flags, bool host_form) {
+  const EnsRoute r = decide_ensemble(m->fused_id >= 0, m->dims[0], m->nu_k, rpd, n, W, flags, host_form, kJacHostChunk);
+  m->last_lnl_route = r.route;
+  m->lnl_route_count[r.route] += 1;
+  return r;
+}
+
+// the ensembles of n start rows prepped transformed in m->jxt; `out`: device pointers, samples and x_last of x_dtype; the
+// call's first row is global chain `chain0`, its row `row0` of a call of n_call rows (data rows as in fit_run)
+static int ensemble_run(v21_mlp* m, int route, long long n, long long n_call, const CallData& data, long long row0, const v21_ensemble_opts& o,
+                        long long chain0, int prec, int flags, const v21_ensemble_out& out, int x_dtype) {
+  hipStream_t st = m->ctx->stream;
+  const int din = m->dims[0];
+  const long long half = n / 2;
+  CHK(m->ens.reserve((size_t)n));
+  CHK(m->ens_prop.reserve((size_t)half * din));
+  CHK(m->ens_lnl.reserve((size_t)half));
+  EnsRow* rows = m->ens.get();
+  float *prop = m->ens_prop.get(), *lnl = m->ens_lnl.get();
+  EnsArgs a{};
+  a.n = n; a.din = din; a.W = o.n_walkers; a.H = o.n_walkers / 2; a.epw = 256 / a.H;
+  a.total = (long long)o.n_warmup + o.n_steps; a.n_warmup = o.n_warmup;
+  a.thin = o.thin; a.n_keep = ensemble_keep(o);
+  a.a = o.a;
+  a.seed = o.seed; a.chain0 = (uint64_t)chain0; a.step0 = (uint64_t)o.step0;
+  a.samples = out.samples; a.samples_lnl = out.samples_lnl; a.last_prop_u = out.last_prop_u;
+  a.t = m->tin;
+  const long long ensembles = n / a.W;
+  const dim3 grid((unsigned)((ensembles + a.epw - 1) / a.epw));
+  // (samples and x_last are of x_dtype: one pair of instantiations, picked once)
+  const bool f64 = x_dtype == V21_DTYPE_F64;
+  const auto step = f64 ? ensemble_step_kernel<double> : ensemble_step_kernel<float>;
+  const auto finish = f64 ? ensemble_finish_kernel<double> : ensemble_finish_kernel<float>;
+  // the proposals' data: rows-per-data and the call's first row in the compacted layout
+  const CallData hd{data.d, data.ld, data.ld ? data.rpd / 2 : 1};
+  const long long last = 2 * a.total + 2;
+  for (long long k = 0; k <= last; ++k) {
+    if (k > 0) CHK(lnl_run(m, route, prop, din, half, n_call / 2, hd, row0 / 2, lnl, prec, flags & ~V21_FWD_IN_TRANSFORM));
+    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), prop, (const float*)lnl, k, a);
+    HIPCHK(hipGetLastError());
+  }
+  EnsOutDev od{out.x_last, out.lnl_last, out.accept_rate, out.mean_u, out.cov_u, out.last_log_alpha, out.last_partner};
+  hipLaunchKernelGGL(finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const EnsRow*)rows, n, din, (long long)o.n_steps, m->tin, od);
+  HIPCHK(hipGetLastError());
+  return V21_OK;
+}
+
+static constexpr JacEntry kEnsemble{"sample_ensemble", kFitMaxIn, true, true};
+
+extern "C" int v21_mlp_sample_ensemble_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                           const v21_ensemble_opts* opts, const v21_ensemble_out* out, int precision, int flags) {
+  const v21_ensemble_opts o = opts ? *opts : ensemble_defaults();
+  CHK(jac_args(m, d_x0 && out && out->x_last, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kEnsemble));
+  CHK(call_data_args("sample_ensemble", n, d_data != nullptr, n_data));
+  CHK(ensemble_check(o));
+  CHK(ensemble_shape(o.n_walkers, m->dims[0], n, d_data != nullptr, n_data));
+  if (n == 0) return V21_OK;
+  CallData data;
+  CHK(call_data(m, n, d_data, false, n_data, &data));
+  const EnsRoute r = ensemble_route(m, d_data ? data.rpd : 0, n, o.n_walkers, flags, false);
+  CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
+  return ensemble_run(m, r.route, n, n, data, 0, o, o.chain0, precision, flags, *out, V21_DTYPE_F32);
+}
+
+// the host form: chunks of whole ensembles (routes.h: decide_ensemble), each staged in m->smp_out, run by ensemble_run
+// and copied back
+extern "C" int v21_mlp_sample_ensemble(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
+                                       const v21_ensemble_opts* opts, const v21_ensemble_out* out, int precision, int flags) {
+  const v21_ensemble_opts o = opts ? *opts : ensemble_defaults();
+  CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kEnsemble));
+  CHK(call_data_args("sample_ensemble", n, data != nullptr, n_data));
+  CHK(ensemble_check(o));
+  CHK(ensemble_shape(o.n_walkers, m->dims[0], n, data != nullptr, n_data));
+  if (n == 0) return V21_OK;
+  CallData cd;
+  CHK(call_data(m, n, data, true, n_data, &cd));
+  const int din = m->dims[0];
+  const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
+  const long long keep = ensemble_keep(o);
+  const EnsRoute r = ensemble_route(m, data ? cd.rpd : 0, n, o.n_walkers, flags, true);
+  // a chunk's staging, in 8-byte units per row: every result that was asked for
+  const long long chunk = std::min<long long>(n, r.chunk);
+  const long long w_smp = out->samples ? keep * din : 0, w_sl = out->samples_lnl ? (keep + 1) / 2 : 0;
+  const long long per = w_smp + w_sl + din + 1 + 1 + din + (long long)din * din + din + 1 + 1;
+  CHK(m->smp_out.reserve((size_t)(chunk * per)));
+  return jac_chunks(m, x0, x_dtype, n, 1, 1, [&](long long r0, long long rows, float*) -> int {
+    double* p = m->smp_out.get();
+    auto take = [&](long long units) { double* q = p; p += rows * units; return q; };
+    v21_ensemble_out d{};
+    d.samples = out->samples ? take(w_smp) : nullptr;
+    d.samples_lnl = out->samples_lnl ? (float*)take(w_sl) : nullptr;
+    d.x_last = take(din);
+    d.lnl_last = (float*)take(1);
+    d.accept_rate = take(1);
+    d.mean_u = take(din);
+    d.cov_u = take((long long)din * din);
+    d.last_prop_u = (float*)take(din);
+    d.last_log_alpha = take(1);
+    d.last_partner = (int*)take(1);
+    CHK(ensemble_run(m, r.route, rows, n, cd, r0, o, o.chain0 + r0, precision, flags, d, x_dtype));
+    if (out->samples) CHK(to_host(m, (char*)out->samples + r0 * keep * din * esz, d.samples, (size_t)rows * keep * din * esz));
+    if (out->samples_lnl) CHK(to_host(m, out->samples_lnl + r0 * keep, d.samples_lnl, (size_t)rows * keep * sizeof(float)));
+    CHK(to_host(m, (char*)out->x_last + r0 * din * esz, d.x_last, (size_t)rows * din * esz));
+    if (out->lnl_last) CHK(to_host(m, out->lnl_last + r0, d.lnl_last, (size_t)rows * sizeof(float)));
+    if (out->accept_rate) CHK(to_host(m, out->accept_rate + r0, d.accept_rate, (size_t)rows * sizeof(double)));
+    if (out->mean_u) CHK(to_host(m, out->mean_u + r0 * din, d.mean_u, (size_t)rows * din * sizeof(double)));
+    if (out->cov_u) CHK(to_host(m, out->cov_u + r0 * din * din, d.cov_u, (size_t)rows * din * din * sizeof(double)));
+    if (out->last_prop_u) CHK(to_host(m, out->last_prop_u + r0 * din, d.last_prop_u, (size_t)rows * din * sizeof(float)));
+    if (out->last_log_alpha) CHK(to_host(m, out->last_log_alpha + r0, d.last_log_alpha, (size_t)rows * sizeof(double)));
+    if (out->last_partner) CHK(to_host(m, out->last_partner + r0, d.last_partner, (size_t)rows * sizeof(int)));
+    return V21_OK;
+  }, r.chunk);
+}

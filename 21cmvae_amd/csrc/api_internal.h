@@ -44,6 +44,7 @@ constexpr int kStampSlots = 64;
 
 namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip); both row states are built on rowmath.h
 namespace v21 { struct SampleRow; struct TemperRow; }  // sample_kernels.h (api_sample.hip)
+namespace v21 { struct EnsRow; }  // ensemble_kernels.h (api_ensemble.hip)
 using namespace v21;
 
 // ---- errors: v21_last_error() returns the calling thread's last message (api_base.hip)
@@ -222,6 +223,8 @@ struct v21_mlp {
   Dev<SampleRow> smp;    // chain state of a sample call (sample_kernels.h; its evaluations land in fF / fl / fg)
   Dev<double> smp_out;   // the host form's chunk: its results, and its per-chain start step sizes
   Dev<TemperRow> tmp;    // a tempered sample call's sums of ln L and swap counts per row
+  Dev<EnsRow> ens;       // walker state of an ensemble call (ensemble_kernels.h) ...
+  Dev<float> ens_prop, ens_lnl;  // ... and the compacted proposals of one half-move (n / 2 rows) with their ln L
   bool has_lk = false;
   // linear nuisance modes marginalised in those reductions (api_nuisance.hip): nu_k modes (0: none), the float64 basis
   // as it was handed in, the record built from it, and the host copy of the likelihood record both are re-whitened from.
@@ -302,6 +305,13 @@ int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float*
 // then sync.  chunk_rows: the rows of a chunk (a tempered sample call's is a whole number of ladders)
 int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, long long out_floats,
                const std::function<int(long long, long long, float*)>& run, long long chunk_rows = kJacHostChunk);
+// api_loglike.hip, shared with api_ensemble.hip: lnl of the n device rows d_x (pitch ldx; raw, or transformed already with
+// V21_FWD_IN_TRANSFORM cleared) that start at row0 of a call of n_call rows, on `route` (routes.h: LnlRoute), on the
+// context's stream
+int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n, long long n_call, const CallData& cd, long long row0,
+            float* d_lnl, int prec, int flags);
+// api_sample.hip, shared with api_ensemble.hip: the ranges of a sample call's options (V21_ERR_ARG)
+int sample_check(const v21_sample_opts& o);
 // device -> host on the context's stream (the host forms' results; jac_chunks syncs)
 static inline int to_host(v21_mlp* m, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->ctx->stream));

@@ -54,9 +54,9 @@ typedef void (*lnl_reduce)(const float*, long long, const float*, long long, lon
                            long long, int);
 
 // lnl of the n device rows d_x (pitch ldx; raw, or transformed already with V21_FWD_IN_TRANSFORM cleared) that start at
-// row0 of a call of n_call rows, on `route`, on the context's stream
-static int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n, long long n_call, const CallData& cd, long long row0,
-                   float* d_lnl, int prec, int flags) {
+// row0 of a call of n_call rows, on `route`, on the context's stream (api_internal.h: the ensemble sampler's evaluation too)
+int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n, long long n_call, const CallData& cd, long long row0,
+            float* d_lnl, int prec, int flags) {
   hipStream_t st = m->ctx->stream;
   const int dout = m->dims[m->L];
   if (route == LNL_FUSED) {

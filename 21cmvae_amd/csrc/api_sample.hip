@@ -87,7 +87,7 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   return V21_OK;
 }
 
-static int sample_check(const v21_sample_opts& o) {
+int sample_check(const v21_sample_opts& o) {
   if (o.n_steps < 0 || o.n_warmup < 0 || o.thin < 0 || !(o.eps0 > 0.0) || !std::isfinite(o.eps0) || !(o.ridge > 0.0) || !std::isfinite(o.ridge) ||
       !(o.target_accept > 0.0 && o.target_accept < 1.0))
     return fail(V21_ERR_ARG, "sample: options n_steps %d n_warmup %d thin %d eps0 %g ridge %g target_accept %g", o.n_steps, o.n_warmup, o.thin,

@@ -282,4 +282,30 @@ inline int decide_loglike_fwd(bool fused_compiled, int in_dim, int n_modes, long
   return fused_compiled && !forced && tin_ok && n_modes == 0 && uniform && range ? LNL_FUSED : LNL_TWO;
 }
 
+// ---- the ensemble sampler (v21_mlp_sample_ensemble[_dev]): every evaluation of a call scores the n / 2 proposals of one
+// half-move in their compacted layout (ensemble_kernels.h), on u.  One decision per call: the route is
+// decide_loglike_fwd's for that half layout -- the record, or H (ensembles per spectrum) = rpd / 2 a multiple of
+// kLnlWgRows -- and the host form's chunk is whole ensembles of W walkers, whole spectra when they fit; a fused call
+// against a data matrix also needs every chunk's half layout to start on a workgroup boundary (chunks of whole multiples
+// of lcm(W, 2 kLnlWgRows) rows): where no such chunk fits, the whole call goes two-launch.  rpd: rows per data row (0: the
+// record); chunk_rows: the host forms' chunk (kJacHostChunk).  chunk: the rows of a host chunk (the _dev form: n).
+constexpr int kEnsMaxWalkers = 512;  // an ensemble's two sets are decided and read inside one 256-thread workgroup
+struct EnsRoute { int route; long long chunk; };
+inline EnsRoute decide_ensemble(bool fused_compiled, int in_dim, int n_modes, long long rpd, long long n, int W, int flags, bool host_form,
+                                long long chunk_rows) {
+  EnsRoute r;
+  r.route = decide_loglike_fwd(fused_compiled, in_dim, n_modes, rpd / 2, n / 2, flags & ~V21_FWD_IN_TRANSFORM);
+  r.chunk = n;
+  if (!host_form) return r;
+  long long unit = W;
+  if (r.route == LNL_FUSED && rpd > 0) {
+    long long a = W, b = 2 * kLnlWgRows;
+    while (b) { const long long t = a % b; a = b; b = t; }
+    unit = (long long)W / a * (2 * kLnlWgRows);
+    if (unit > chunk_rows) { r.route = LNL_TWO; unit = W; }
+  }
+  r.chunk = lnl_host_chunk(chunk_rows / unit * unit, rpd);
+  return r;
+}
+
 }  // namespace v21

@@ -581,6 +581,59 @@ class _EmulatorBase:
             acc, step, rh, mean, cov = acc[0], step[0], rh[0], mean[0], cov[0]
         return PosteriorSamples(params, lnl, acc, step, rh, mean, cov)
 
+    def sample_ensemble(self, data, sigma, n_walkers=64, n_ensembles=4, n_steps=1000, n_warmup=500, thin=1, a=2.0, p0=None, flow=None,
+                        fhigh=None, seed=0, return_lnl=False, foreground=None):
+        """Posterior samples from the affine-invariant ensemble sampler (not in the reference): ``n_ensembles`` independent
+        ensembles of ``n_walkers`` walkers per spectrum, moved by Goodman & Weare's stretch move with scale ``a`` entirely
+        on the device (include/v21.h: v21_mlp_sample_ensemble), on the forward-only ln L of ``log_likelihood`` under
+        ``sample_posterior``'s prior -- uniform on the training box in par_transform's coordinates.  It needs no gradient
+        and no Fisher matrix, so it also serves posteriors on which ``sample_posterior``'s metric is singular or misleading.
+        ``n_walkers``: even, 16 .. 512 for the 7 parameters.  Starts as ``sample_posterior`` chooses them: ``p0`` ((7,) or
+        (n_walkers, 7) raw parameters, the same for every ensemble and spectrum) or the best ``fit_parameters`` start per
+        spectrum, every walker jittered (seeded, 0.02 in u, clipped into the box).  ``n_warmup`` sweeps are burn-in
+        (nothing is adapted), then ``n_steps`` kept ones of which every ``thin``-th is stored (``thin = 0``: none).
+        Returns ``PosteriorSamples``: params (M, n_ensembles, n_walkers, n_steps // thin, 7) raw, lnl (the same without the
+        last axis; None unless ``return_lnl``), accept_rate (M, n_ensembles, n_walkers), step_size None (the move has none),
+        r_hat (M, 7) taken BETWEEN ENSEMBLES -- the walkers of one ensemble are not independent chains, so each ensemble's
+        walkers are pooled (``pooled_moments``) and the ensembles compared (``r_hat_from_moments``; NaN for one ensemble) --
+        and the pooled mean_u (M, 7) / cov_u (M, 7, 7); the M axis is dropped for one spectrum."""
+        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
+        nb, din = st.dims[-1], st.dims[0]
+        dat = np.asarray(data, np.float32)
+        one = dat.ndim == 1
+        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
+        if dat.ndim != 2 or dat.shape[1] != nb:
+            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        M, E, W = dat.shape[0], int(n_ensembles), int(n_walkers)
+        if E < 1:
+            raise ValueError("n_ensembles must be >= 1")
+        opts = dict(a=a, n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed)
+        nat.Stack.ensemble_opts(W, in_dim=din, **opts)  # (argument errors before any device work)
+        if p0 is None:
+            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
+            u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], E * W, axis=1).reshape(M, E, W, din)
+        else:
+            starts = np.array(p0, np.float64, ndmin=2)
+            if starts.ndim != 2 or starts.shape[1] != din or starts.shape[0] not in (1, W):
+                raise ValueError("p0 must be (%d,) or (%d, %d), got %r" % (din, W, din, np.shape(p0)))
+            u0 = np.broadcast_to(pp.par_transform(starts, self.par_train)[None, None], (M, E, W, din))
+        rng = np.random.default_rng(seed)
+        u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=(M, E, W, din)), -1.0, 1.0)
+        x0 = np.ascontiguousarray(pp.par_untransform(u0.reshape(M * E * W, din), self.par_train))
+        self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
+        r = st.sample_ensemble(x0, W, model.precision, flags, data=dat, **opts)
+        K = r["samples"].shape[1] if "samples" in r else 0
+        params = r["samples"].reshape(M, E, W, K, din) if K else None
+        lnl = r["samples_lnl"].reshape(M, E, W, K) if K and return_lnl else None
+        acc = r["accept_rate"].reshape(M, E, W)
+        mean_e, cov_e = pooled_moments(r["mean_u"].reshape(M, E, W, din), r["cov_u"].reshape(M, E, W, din, din))
+        rh = r_hat_from_moments(mean_e, cov_e, int(n_steps) * W)
+        mean, cov = pooled_moments(mean_e, cov_e)
+        if one:
+            params, lnl = (params[0] if params is not None else None), (lnl[0] if lnl is not None else None)
+            acc, rh, mean, cov = acc[0], rh[0], mean[0], cov[0]
+        return PosteriorSamples(params, lnl, acc, None, rh, mean, cov)
+
     def sample_tempered(self, data, sigma, n_ladders=16, n_temps=8, betas=None, swap_every=5, n_steps=1000, n_warmup=200, thin=1,
                         p0=None, flow=None, fhigh=None, seed=0, eps=None, return_lnl=False, foreground=None):
         """Parallel-tempered posterior samples and the Bayesian evidence (not in the reference): ``n_ladders`` ladders per

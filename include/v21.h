@@ -335,6 +335,53 @@ int v21_mlp_sample_tempered_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, in
                                 const v21_sample_opts* opts, const v21_temper_opts* temper, const double* d_eps_start,
                                 const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags);
 
+/* ---- the affine-invariant ensemble sampler (Goodman & Weare 2010, the stretch move) on forward-only ln L: no gradient
+ * and no Fisher matrix, so it also serves targets whose Fisher metric is singular or misleading.
+ *   Target.  That of v21_mlp_sample: ln L is v21_mlp_loglike_fwd's (nuisance records and the w == 0 rule included) under
+ *   the uniform prior on the training box in u = par_transform(x) in [-1, 1]^d.  Needs the input transform and a
+ *   likelihood record; d = in_dim <= 8.
+ *   Rows, ensembles, sets.  A call has n rows; W = n_walkers consecutive rows form one ensemble: W even,
+ *   2 (d + 1) <= W <= 512, n % W == 0 and, with a data matrix, (n / n_data) % W == 0.  H = W / 2; walker i = r % W of row r
+ *   belongs to set h = i / H and has index j = i % H in it.
+ *   One sweep.  Sweep S = step0 + its index in the call (warm-up included) is two half-moves, h = 0 then h = 1; half-move
+ *   h updates every walker of set h from the CURRENT positions of set 1 - h of the same ensemble.  For walker i at x_i:
+ *     random words (w0, w1, w2) of Philox block 0 of (seed, c = chain0 + row, S) -- function, key and counter mapping as
+ *     documented for v21_mlp_sample, a word w giving the uniform U(w) = (w + 0.5) 2^-32;
+ *     stretch factor z = ((a - 1) U(w0) + 1)^2 / a, so that g(z) is proportional to 1 / sqrt(z) on [1 / a, a];
+ *     partner k = floor(H w1 / 2^32) (the high word of H x w1) within set 1 - h, at x_k;
+ *     proposal y = float32(x_k + z (x_i - x_k)), formed in float64 and rounded once;
+ *     log alpha = (d - 1) ln z + lnL(y) - lnL(x_i), in float64 from the stored float32 ln L;
+ *     accepted iff ln U(w2) < log alpha.
+ *   A y with a coordinate outside [-1, 1] is rejected and its evaluation is not read: log alpha is reported as -inf; y is
+ *   never clamped or reflected.  A NaN log alpha rejects (and is reported as -inf).
+ *   Stretch scale and warm-up.  a is not adapted; the n_warmup sweeps are burn-in and are only discarded.
+ *   Start.  x0 in raw units, clamped into the box; every start is accepted whatever its ln L.
+ *   Evaluation.  Every ln L of a call -- the starts' too -- is that of the n / 2 proposals of one half-move in a compacted
+ *   layout (row e H + j: walker j of the moving set of ensemble e), on u without the input transform, on ONE route decided
+ *   once per call (v21_route_ensemble; csrc/routes.h: 1 = fused, 2 = two-launch): v21_mlp_loglike_fwd's decision for that
+ *   layout, i.e. fused for the stacks of archs.h against the record, or when H (ensembles per spectrum) is a multiple of
+ *   128; no nuisance record, no forward route flag.  v21_mlp_last_lnl_route counts an ensemble call once, whatever its
+ *   sweeps and chunks; v21_mlp_last_jac_route is not touched.
+ *   Results per row (v21_ensemble_out, v21_types.h): samples (raw units, x0's dtype: the walker's state after its own
+ *   half-move of every thin-th kept sweep), samples_lnl, x_last, lnl_last, accept_rate, mean_u / cov_u (float64 over the
+ *   n_steps kept sweeps, divided by n_steps as v21_mlp_sample's), last_prop_u, last_log_alpha, last_partner.
+ *   Invariance.  A draw depends only on (seed, chain, S): results do not depend on how a run is split over calls, host
+ *   chunks or devices, provided no ensemble is split -- by step0, n_warmup = 0 and a float64 x_last (exactly: the state is
+ *   the float32 u), and by chain0.
+ *   V21_ERR_ARG, the handle left usable: W odd, W < 2 (d + 1), W > 512, n % W != 0, a spectrum's rows not being whole
+ *   ensembles, a <= 1 or not finite, and the counts outside v21_mlp_sample's ranges.  n = 0 is a no-op.
+ * The host form works in chunks of whole ensembles not above 8,192 rows (whole spectra when they fit; a fused call
+ * against a data matrix in multiples of lcm(W, 256) rows, so that every chunk's proposals start on a 128-row boundary --
+ * where no such chunk fits the call goes two-launch) and returns when the results are in place; the _dev form never
+ * synchronises.  v21_route_ensemble: the route and (chunk_rows, nullable) the host form's chunk (the _dev form: n) of a
+ * call of n rows against n_data data rows (0: the record) for a handle with n_modes nuisance modes -- pure host logic. */
+int v21_mlp_sample_ensemble(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
+                            const v21_ensemble_opts* opts, const v21_ensemble_out* out, int precision, int flags);
+int v21_mlp_sample_ensemble_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                const v21_ensemble_opts* opts, const v21_ensemble_out* out, int precision, int flags);
+int v21_route_ensemble(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
+                       int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows);
+
 /* ---- linear nuisance modes (foregrounds) integrated out of the likelihood record.  Data model: d = y(x) + A^T a + noise,
  * A the (n_modes, out_dim) basis, 1 <= n_modes <= 8, with a FLAT PRIOR on the amplitudes a, which are integrated out
  * analytically.  With W = diag(w) the record's inverse variances, Q the W-orthonormalised basis (span Q = span A on the

@@ -57,4 +57,29 @@ typedef struct {
   double* swap_accept;  /* (n): swaps accepted / proposed over the kept transitions with this row as the lower of the pair; 0
                          * where none was proposed */
 } v21_temper_out;
+/* options of v21_mlp_sample_ensemble[_dev] (a NULL pointer: the defaults in brackets) */
+typedef struct {
+  int n_walkers;        /* [64] W: consecutive rows form one ensemble; even, 2 (in_dim + 1) <= W <= 512 */
+  double a;             /* [2] stretch scale, > 1 and finite; never adapted */
+  int n_steps;          /* [1000] sweeps after the warm-up: they enter the samples, the moments and accept_rate */
+  int n_warmup;         /* [500] sweeps before them: burn-in, only discarded */
+  int thin;             /* [1] every thin-th kept sweep is stored, n_steps / thin (rounded down) per walker; 0: none */
+  unsigned long long seed;  /* [0] the Philox key */
+  long long chain0;     /* [0] global index of the call's first row, >= 0 */
+  long long step0;      /* [0] global index of the call's first sweep, >= 0; step0 + n_warmup + n_steps < 2^32 */
+} v21_ensemble_opts;
+/* results of v21_mlp_sample_ensemble[_dev]: host pointers for the host form, device pointers for _dev; every one but
+ * x_last may be NULL.  n rows (walkers), K = n_steps / thin stored states each; "x type" is x0's dtype (_dev: float32). */
+typedef struct {
+  void* samples;          /* (n, K, in_dim) x type: the walker's state after its own half-move of every thin-th kept sweep */
+  float* samples_lnl;     /* (n, K): ln L at them */
+  void* x_last;           /* (n, in_dim) x type: the state after the last sweep, raw units */
+  float* lnl_last;        /* (n): ln L there */
+  double* accept_rate;    /* (n): accepted / kept sweeps */
+  double* mean_u;         /* (n, in_dim): per-walker mean of u over the kept sweeps */
+  double* cov_u;          /* (n, in_dim, in_dim): per-walker covariance of u over them (divided by n_steps) */
+  float* last_prop_u;     /* (n, in_dim): the walker's proposal of the last sweep, u units (no sweep: its clamped start) */
+  double* last_log_alpha; /* (n): its log acceptance ratio (-inf: outside the box; no sweep: 0) */
+  int* last_partner;      /* (n): its partner, as the row index within the ensemble (no sweep: -1) */
+} v21_ensemble_out;
 #endif /* V21_TYPES_H */
