@@ -371,6 +371,51 @@ def _opt(a):
     return _P(a) if a else None
 
 
+def _data_rows(what, data, n, dout):
+    """The data matrix of a `what` call of n rows -> (float32 (n_data, dout) array, n_data), or (None, 0) for None (the
+    record's data); one spectrum may come as (dout,).  ValueError unless n_data >= 1 divides n."""
+    if data is None:
+        return None, 0
+    dp = np.ascontiguousarray(data, dtype=np.float32)
+    if dp.ndim == 1:
+        dp = dp[None, :]
+    if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
+        raise ValueError("%s: data must be (n_data, %d), got %r" % (what, dout, np.shape(data)))
+    if n % dp.shape[0]:
+        raise ValueError("%s: %d rows are not a multiple of %d data rows" % (what, n, dp.shape[0]))
+    return dp, dp.shape[0]
+
+
+def _count_opts(what, o, more=()):
+    """The counts of a sampler's options o (and the keys `more`): ValueError for what the library would refuse"""
+    for k in tuple(more) + ("n_steps", "n_warmup", "thin", "chain0", "step0", "seed"):
+        if int(o[k]) != o[k] or int(o[k]) < 0:
+            raise ValueError("%s: %s = %r (a non-negative integer)" % (what, k, o[k]))
+    if int(o["n_steps"]) >= 2 ** 31 or int(o["n_warmup"]) >= 2 ** 31 or int(o["thin"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64:
+        raise ValueError("%s: count out of range" % what)
+    if int(o["step0"]) + int(o["n_warmup"]) + int(o["n_steps"]) >= 2 ** 32:
+        raise ValueError("%s: step0 + n_warmup + n_steps must stay below 2^32" % what)
+
+
+def _sample_results(x, o, samples, diagnostics, rows=(), diag_rows=()):
+    """The result arrays every sampler's host form returns for the start rows x under the options o, by the names of its
+    out struct; rows / diag_rows: (name, dtype) of the sampler's own (n,) results, always / with diagnostics"""
+    n, din = x.shape
+    keep = o.n_steps // o.thin if o.thin > 0 else 0
+    res = {"x_last": np.empty_like(x), "lnl_last": np.empty(n, np.float32)}
+    res.update({k: np.empty(n, t) for k, t in rows})
+    res.update({"accept_rate": np.empty(n, np.float64), "mean_u": np.empty((n, din), np.float64),
+                "cov_u": np.empty((n, din, din), np.float64)})
+    if samples and keep > 0:
+        res["samples"] = np.empty((n, keep, din), x.dtype)
+        res["samples_lnl"] = np.empty((n, keep), np.float32)
+    if diagnostics:
+        res["last_prop_u"] = np.empty((n, din), np.float32)
+        res["last_log_alpha"] = np.empty(n, np.float64)
+        res.update({k: np.empty(n, t) for k, t in diag_rows})
+    return res
+
+
 def _last_route(fn, h, tables, slots=8):
     """fn(h, int* route per table, long long counts[slots] per table) -> ([name of the last route per table],
     [{route name: calls since creation, zero counts left out} per table])."""
@@ -809,17 +854,8 @@ class Stack(_Owned):
         against the record set_likelihood left, or against data (n_data, out) with n % n_data == 0, row i scored against
         data row i // (n // n_data); the inverse variances are the record's either way."""
         x, dt = self._rows(x)
-        n, dout = x.shape[0], self.dims[-1]
-        nd, dp = 0, None
-        if data is not None:
-            dp = np.ascontiguousarray(data, dtype=np.float32)
-            if dp.ndim == 1:
-                dp = dp[None, :]
-            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
-                raise ValueError("loglike_fwd: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
-            nd = dp.shape[0]
-            if n % nd:
-                raise ValueError("loglike_fwd: %d rows are not a multiple of %d data rows" % (n, nd))
+        n = x.shape[0]
+        dp, nd = _data_rows("loglike_fwd", data, n, self.dims[-1])
         lnl = np.empty(n, np.float32)
         with self.ctx.lock:
             check(self.lib.v21_mlp_loglike_fwd(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, _fptr(lnl), precision_id(precision), flags))
@@ -874,16 +910,7 @@ class Stack(_Owned):
         n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
         if din > 8:
             raise ValueError("fit: %d parameters (at most 8)" % din)
-        nd, dp = 0, None
-        if data is not None:
-            dp = np.ascontiguousarray(data, dtype=np.float32)
-            if dp.ndim == 1:
-                dp = dp[None, :]
-            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
-                raise ValueError("fit: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
-            nd = dp.shape[0]
-            if n % nd:
-                raise ValueError("fit: %d rows are not a multiple of %d data rows" % (n, nd))
+        dp, nd = _data_rows("fit", data, n, dout)
         opts = self.fit_opts(max_iter, lambda0, xtol, check_every)
         xh = np.empty_like(x)
         lnl, l0, status = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32)
@@ -914,13 +941,7 @@ class Stack(_Owned):
         o.update({k: v for k, v in (("n_steps", n_steps), ("n_warmup", n_warmup), ("thin", thin), ("eps0", eps0), ("ridge", ridge),
                                     ("target_accept", target_accept), ("seed", seed), ("chain0", chain0), ("step0", step0))
                   if v is not None})
-        for k in ("n_steps", "n_warmup", "thin", "chain0", "step0", "seed"):
-            if int(o[k]) != o[k] or int(o[k]) < 0:
-                raise ValueError("sample: %s = %r (a non-negative integer)" % (k, o[k]))
-        if int(o["n_steps"]) >= 2 ** 31 or int(o["n_warmup"]) >= 2 ** 31 or int(o["thin"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64:
-            raise ValueError("sample: count out of range")
-        if int(o["step0"]) + int(o["n_warmup"]) + int(o["n_steps"]) >= 2 ** 32:
-            raise ValueError("sample: step0 + n_warmup + n_steps must stay below 2^32")
+        _count_opts("sample", o)
         for k in ("eps0", "ridge"):
             if not (float(o[k]) > 0 and np.isfinite(float(o[k]))):
                 raise ValueError("sample: %s = %r (positive and finite)" % (k, o[k]))
@@ -939,46 +960,32 @@ class Stack(_Owned):
         (n, in, in) float64 -- the per-chain moments of u over the n_steps kept transitions -- and, with samples and
         thin > 0, samples (n, n_steps // thin, in) in x0's dtype and samples_lnl; with diagnostics, last_prop_u (n, in)
         float32 and last_log_alpha (n,) float64 of the last transition."""
-        x, dt, n, dp, nd, o, es, res = self._sample_call(x0, data, eps_start, samples, diagnostics, opts)
+        x, dt, n, dp, nd, o, es, res = self._sample_call("sample", x0, data, lambda *_: self.sample_opts(**opts), samples, diagnostics, eps_start)
         out = SampleOut(**{k: v.ctypes.data for k, v in res.items()})
         with self.ctx.lock:
             check(self.lib.v21_mlp_sample(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(o),
                                           es.ctypes.data_as(_P) if es is not None else None, C.byref(out), precision_id(precision), flags))
         return res
 
-    def _sample_call(self, x0, data, eps_start, samples, diagnostics, opts):
-        """what the host forms of sample and sample_tempered share: the rows, the data matrix, the options, the start
-        step sizes and the result arrays of v21_sample_out -> (x, dtype id, n, data, n_data, opts, eps_start, results)"""
+    def _sample_call(self, what, x0, data, opts, samples, diagnostics, eps_start=None):
+        """what the host forms of the three samplers share: the rows, the data matrix, the options -- opts(n, n_data,
+        in_dim) -> the options struct --, the start step sizes and the result arrays of the out struct
+        -> (x, dtype id, n, data, n_data, opts, eps_start, results)"""
         x, dt = self._rows(x0)
-        n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
+        n, din = x.shape[0], self.dims[0]
         if din > 8:
-            raise ValueError("sample: %d parameters (at most 8)" % din)
-        nd, dp = 0, None
-        if data is not None:
-            dp = np.ascontiguousarray(data, dtype=np.float32)
-            if dp.ndim == 1:
-                dp = dp[None, :]
-            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
-                raise ValueError("sample: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
-            nd = dp.shape[0]
-            if n % nd:
-                raise ValueError("sample: %d chains are not a multiple of %d data rows" % (n, nd))
-        o = self.sample_opts(**opts)
+            raise ValueError("%s: %d parameters (at most 8)" % (what, din))
+        dp, nd = _data_rows(what, data, n, self.dims[-1])
+        o = opts(n, nd, din)
         es = None
         if eps_start is not None:
             es = np.ascontiguousarray(eps_start, dtype=np.float64)
             if es.shape != (n,) or not np.all(es > 0):
-                raise ValueError("sample: eps_start must be (%d,) positive step sizes" % n)
-        keep = o.n_steps // o.thin if o.thin > 0 else 0
-        res = {"x_last": np.empty_like(x), "lnl_last": np.empty(n, np.float32), "eps_last": np.empty(n, np.float64),
-               "accept_rate": np.empty(n, np.float64), "mean_u": np.empty((n, din), np.float64),
-               "cov_u": np.empty((n, din, din), np.float64)}
-        if samples and keep > 0:
-            res["samples"] = np.empty((n, keep, din), x.dtype)
-            res["samples_lnl"] = np.empty((n, keep), np.float32)
-        if diagnostics:
-            res["last_prop_u"] = np.empty((n, din), np.float32)
-            res["last_log_alpha"] = np.empty(n, np.float64)
+                raise ValueError("%s: eps_start must be (%d,) positive step sizes" % (what, n))
+        if isinstance(o, EnsembleOpts):
+            res = _sample_results(x, o, samples, diagnostics, diag_rows=[("last_partner", np.int32)])
+        else:
+            res = _sample_results(x, o, samples, diagnostics, rows=[("eps_last", np.float64)])
         return x, dt, n, dp, nd, o, es, res
 
     def sample_dev(self, d_x0, ldx, n, d_data, n_data, out, d_eps_start=None, precision="f32", flags=0, **opts):
@@ -1021,7 +1028,7 @@ class Stack(_Owned):
         them mean_lnl, var_lnl (the un-tempered ln L over the kept transitions) and swap_accept (the pair of this row and
         the next), all (n,) float64.  With data, the rows of one spectrum must be whole ladders."""
         self.temper_opts(n_temps, betas, swap_every)
-        x, dt, n, dp, nd, o, es, res = self._sample_call(x0, data, eps_start, samples, diagnostics, opts)
+        x, dt, n, dp, nd, o, es, res = self._sample_call("sample", x0, data, lambda *_: self.sample_opts(**opts), samples, diagnostics, eps_start)
         t = self.temper_opts(n_temps, betas, swap_every, n, nd)
         out = SampleOut(**{k: v.ctypes.data for k, v in res.items()})
         tres = {k: np.empty(n, np.float64) for k in TEMPER_OUTPUTS}
@@ -1053,13 +1060,7 @@ class Stack(_Owned):
         o = dict(ENSEMBLE_DEFAULTS)
         o.update({k: v for k, v in (("n_walkers", n_walkers), ("a", a), ("n_steps", n_steps), ("n_warmup", n_warmup), ("thin", thin),
                                     ("seed", seed), ("chain0", chain0), ("step0", step0)) if v is not None})
-        for k in ("n_walkers", "n_steps", "n_warmup", "thin", "chain0", "step0", "seed"):
-            if int(o[k]) != o[k] or int(o[k]) < 0:
-                raise ValueError("sample_ensemble: %s = %r (a non-negative integer)" % (k, o[k]))
-        if int(o["n_steps"]) >= 2 ** 31 or int(o["n_warmup"]) >= 2 ** 31 or int(o["thin"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64:
-            raise ValueError("sample_ensemble: count out of range")
-        if int(o["step0"]) + int(o["n_warmup"]) + int(o["n_steps"]) >= 2 ** 32:
-            raise ValueError("sample_ensemble: step0 + n_warmup + n_steps must stay below 2^32")
+        _count_opts("sample_ensemble", o, more=("n_walkers",))
         if not (float(o["a"]) > 1.0 and np.isfinite(float(o["a"]))):
             raise ValueError("sample_ensemble: a = %r (above 1 and finite)" % (o["a"],))
         W = int(o["n_walkers"])
@@ -1081,31 +1082,8 @@ class Stack(_Owned):
         float64 -- the per-walker moments of u over the n_steps kept sweeps -- and, with samples and thin > 0, samples
         (n, n_steps // thin, in) in x0's dtype and samples_lnl; with diagnostics, last_prop_u (n, in) float32,
         last_log_alpha (n,) float64 and last_partner (n,) int32 of the last sweep."""
-        x, dt = self._rows(x0)
-        n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
-        if din > 8:
-            raise ValueError("sample_ensemble: %d parameters (at most 8)" % din)
-        nd, dp = 0, None
-        if data is not None:
-            dp = np.ascontiguousarray(data, dtype=np.float32)
-            if dp.ndim == 1:
-                dp = dp[None, :]
-            if dp.ndim != 2 or dp.shape[1] != dout or dp.shape[0] < 1:
-                raise ValueError("sample_ensemble: data must be (n_data, %d), got %r" % (dout, np.shape(data)))
-            nd = dp.shape[0]
-            if n % nd:
-                raise ValueError("sample_ensemble: %d rows are not a multiple of %d data rows" % (n, nd))
-        o = self.ensemble_opts(n_walkers, n=n, n_data=nd, in_dim=din, **opts)
-        keep = o.n_steps // o.thin if o.thin > 0 else 0
-        res = {"x_last": np.empty_like(x), "lnl_last": np.empty(n, np.float32), "accept_rate": np.empty(n, np.float64),
-               "mean_u": np.empty((n, din), np.float64), "cov_u": np.empty((n, din, din), np.float64)}
-        if samples and keep > 0:
-            res["samples"] = np.empty((n, keep, din), x.dtype)
-            res["samples_lnl"] = np.empty((n, keep), np.float32)
-        if diagnostics:
-            res["last_prop_u"] = np.empty((n, din), np.float32)
-            res["last_log_alpha"] = np.empty(n, np.float64)
-            res["last_partner"] = np.empty(n, np.int32)
+        x, dt, n, dp, nd, o, _, res = self._sample_call(
+            "sample_ensemble", x0, data, lambda n, nd, din: self.ensemble_opts(n_walkers, n=n, n_data=nd, in_dim=din, **opts), samples, diagnostics)
         out = EnsembleOut(**{k: v.ctypes.data for k, v in res.items()})
         with self.ctx.lock:
             check(self.lib.v21_mlp_sample_ensemble(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(o), C.byref(out),

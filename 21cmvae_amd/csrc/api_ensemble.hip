@@ -20,16 +20,10 @@ static v21_ensemble_opts ensemble_defaults() {
   return o;
 }
 
-static long long ensemble_keep(const v21_ensemble_opts& o) { return o.thin > 0 ? o.n_steps / o.thin : 0; }
-
-// the stretch scale and the counts (sample_check's ranges)
+// the stretch scale and the counts
 static int ensemble_check(const v21_ensemble_opts& o) {
   if (!(o.a > 1.0) || !std::isfinite(o.a)) return fail(V21_ERR_ARG, "sample_ensemble: a = %g (above 1 and finite)", o.a);
-  v21_sample_opts s{};
-  s.n_steps = o.n_steps; s.n_warmup = o.n_warmup; s.thin = o.thin;
-  s.eps0 = 1.0; s.ridge = 1.0; s.target_accept = 0.5;
-  s.seed = o.seed; s.chain0 = o.chain0; s.step0 = o.step0;
-  return sample_check(s);
+  return sample_counts("sample_ensemble", o.n_steps, o.n_warmup, o.thin, o.chain0, o.step0);
 }
 
 // how the call's n rows (with data: the n / n_data rows of a spectrum) divide into ensembles of W walkers in din dimensions
@@ -83,7 +77,7 @@ static int ensemble_run(v21_mlp* m, int route, long long n, long long n_call, co
   EnsArgs a{};
   a.n = n; a.din = din; a.W = o.n_walkers; a.H = o.n_walkers / 2; a.epw = 256 / a.H;
   a.total = (long long)o.n_warmup + o.n_steps; a.n_warmup = o.n_warmup;
-  a.thin = o.thin; a.n_keep = ensemble_keep(o);
+  a.thin = o.thin; a.n_keep = sample_keep(o.n_steps, o.thin);
   a.a = o.a;
   a.seed = o.seed; a.chain0 = (uint64_t)chain0; a.step0 = (uint64_t)o.step0;
   a.samples = out.samples; a.samples_lnl = out.samples_lnl; a.last_prop_u = out.last_prop_u;
@@ -125,8 +119,8 @@ extern "C" int v21_mlp_sample_ensemble_dev(v21_mlp* m, const float* d_x0, int64_
   return ensemble_run(m, r.route, n, n, data, 0, o, o.chain0, precision, flags, *out, V21_DTYPE_F32);
 }
 
-// the host form: chunks of whole ensembles (routes.h: decide_ensemble), each staged in m->smp_out, run by ensemble_run
-// and copied back
+// the host form: chunks of whole ensembles (routes.h: decide_ensemble), each staged in m->smp_out (ChunkStage), run by
+// ensemble_run and copied back
 extern "C" int v21_mlp_sample_ensemble(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
                                        const v21_ensemble_opts* opts, const v21_ensemble_out* out, int precision, int flags) {
   const v21_ensemble_opts o = opts ? *opts : ensemble_defaults();
@@ -138,39 +132,15 @@ extern "C" int v21_mlp_sample_ensemble(v21_mlp* m, const void* x0, int x_dtype, 
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0];
-  const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
-  const long long keep = ensemble_keep(o);
   const EnsRoute r = ensemble_route(m, data ? cd.rpd : 0, n, o.n_walkers, flags, true);
-  // a chunk's staging, in 8-byte units per row: every result that was asked for
-  const long long chunk = std::min<long long>(n, r.chunk);
-  const long long w_smp = out->samples ? keep * din : 0, w_sl = out->samples_lnl ? (keep + 1) / 2 : 0;
-  const long long per = w_smp + w_sl + din + 1 + 1 + din + (long long)din * din + din + 1 + 1;
-  CHK(m->smp_out.reserve((size_t)(chunk * per)));
+  ChunkStage sg;
+  v21_ensemble_out d{};
+  stage_sampler_out(sg, *out, d, sample_keep(o.n_steps, o.thin), din, x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float));
+  sg.add(out->last_partner, &d.last_partner, sizeof(int));
+  CHK(m->smp_out.reserve(sg.units(std::min<long long>(n, r.chunk))));
   return jac_chunks(m, x0, x_dtype, n, 1, 1, [&](long long r0, long long rows, float*) -> int {
-    double* p = m->smp_out.get();
-    auto take = [&](long long units) { double* q = p; p += rows * units; return q; };
-    v21_ensemble_out d{};
-    d.samples = out->samples ? take(w_smp) : nullptr;
-    d.samples_lnl = out->samples_lnl ? (float*)take(w_sl) : nullptr;
-    d.x_last = take(din);
-    d.lnl_last = (float*)take(1);
-    d.accept_rate = take(1);
-    d.mean_u = take(din);
-    d.cov_u = take((long long)din * din);
-    d.last_prop_u = (float*)take(din);
-    d.last_log_alpha = take(1);
-    d.last_partner = (int*)take(1);
+    CHK(sg.place(m, r0, rows));
     CHK(ensemble_run(m, r.route, rows, n, cd, r0, o, o.chain0 + r0, precision, flags, d, x_dtype));
-    if (out->samples) CHK(to_host(m, (char*)out->samples + r0 * keep * din * esz, d.samples, (size_t)rows * keep * din * esz));
-    if (out->samples_lnl) CHK(to_host(m, out->samples_lnl + r0 * keep, d.samples_lnl, (size_t)rows * keep * sizeof(float)));
-    CHK(to_host(m, (char*)out->x_last + r0 * din * esz, d.x_last, (size_t)rows * din * esz));
-    if (out->lnl_last) CHK(to_host(m, out->lnl_last + r0, d.lnl_last, (size_t)rows * sizeof(float)));
-    if (out->accept_rate) CHK(to_host(m, out->accept_rate + r0, d.accept_rate, (size_t)rows * sizeof(double)));
-    if (out->mean_u) CHK(to_host(m, out->mean_u + r0 * din, d.mean_u, (size_t)rows * din * sizeof(double)));
-    if (out->cov_u) CHK(to_host(m, out->cov_u + r0 * din * din, d.cov_u, (size_t)rows * din * din * sizeof(double)));
-    if (out->last_prop_u) CHK(to_host(m, out->last_prop_u + r0 * din, d.last_prop_u, (size_t)rows * din * sizeof(float)));
-    if (out->last_log_alpha) CHK(to_host(m, out->last_log_alpha + r0, d.last_log_alpha, (size_t)rows * sizeof(double)));
-    if (out->last_partner) CHK(to_host(m, out->last_partner + r0, d.last_partner, (size_t)rows * sizeof(int)));
-    return V21_OK;
+    return sg.fetch(m, r0, rows);
   }, r.chunk);
 }

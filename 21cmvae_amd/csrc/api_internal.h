@@ -221,7 +221,7 @@ struct v21_mlp {
   Dev<float> fF, fl, fg, fdata;
   Dev<int> fit_cnt;
   Dev<SampleRow> smp;    // chain state of a sample call (sample_kernels.h; its evaluations land in fF / fl / fg)
-  Dev<double> smp_out;   // the host form's chunk: its results, and its per-chain start step sizes
+  Dev<double> smp_out;   // the samplers' host forms' chunk: its results, and its per-chain start step sizes (ChunkStage)
   Dev<TemperRow> tmp;    // a tempered sample call's sums of ln L and swap counts per row
   Dev<EnsRow> ens;       // walker state of an ensemble call (ensemble_kernels.h) ...
   Dev<float> ens_prop, ens_lnl;  // ... and the compacted proposals of one half-move (n / 2 rows) with their ln L
@@ -310,12 +310,63 @@ int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, lon
 // context's stream
 int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n, long long n_call, const CallData& cd, long long row0,
             float* d_lnl, int prec, int flags);
-// api_sample.hip, shared with api_ensemble.hip: the ranges of a sample call's options (V21_ERR_ARG)
-int sample_check(const v21_sample_opts& o);
+// api_sample.hip, shared with api_ensemble.hip: the ranges of the counts in the options of entry `what` (V21_ERR_ARG),
+// and the states a row stores
+int sample_counts(const char* what, int n_steps, int n_warmup, int thin, long long chain0, long long step0);
+static inline long long sample_keep(int n_steps, int thin) { return thin > 0 ? n_steps / thin : 0; }
 // device -> host on the context's stream (the host forms' results; jac_chunks syncs)
 static inline int to_host(v21_mlp* m, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->ctx->stream));
   return V21_OK;
+}
+// A sampler's host form stages every chunk in m->smp_out.  The arrays of the call are listed once: add(host, dev, bytes)
+// for an array of `bytes` per row -- host: the caller's (null: not asked for, no slot), dev: where the chunk's device
+// pointer goes (null without a slot), in: an input, copied to the device instead of back.  From that one list come a
+// chunk's size (units), its device pointers with the uploads (place) and the copies back (fetch).
+struct ChunkStage {
+  struct Slot { char* host; void* dev; size_t bytes; bool in; };
+  std::vector<Slot> slots;
+  template <class T>
+  void add(const T* host, T** dev, size_t bytes, bool in = false) {
+    *dev = nullptr;
+    if (host) slots.push_back({(char*)host, dev, bytes, in});
+  }
+  static size_t units_of(const Slot& s, long long rows) { return ((size_t)rows * s.bytes + 7) / 8; }  // (every slot starts on 8 bytes)
+  size_t units(long long rows) const {
+    size_t u = 0;
+    for (const Slot& s : slots) u += units_of(s, rows);
+    return u;
+  }
+  int place(v21_mlp* m, long long r0, long long rows) const {
+    double* p = m->smp_out.get();
+    for (const Slot& s : slots) {
+      memcpy(s.dev, &p, sizeof p);
+      if (s.in) HIPCHK(hipMemcpyAsync(p, s.host + r0 * s.bytes, (size_t)rows * s.bytes, hipMemcpyHostToDevice, m->ctx->stream));
+      p += units_of(s, rows);
+    }
+    return V21_OK;
+  }
+  int fetch(v21_mlp* m, long long r0, long long rows) const {
+    const double* p = m->smp_out.get();
+    for (const Slot& s : slots) {
+      if (!s.in) CHK(to_host(m, s.host + r0 * s.bytes, p, (size_t)rows * s.bytes));
+      p += units_of(s, rows);
+    }
+    return V21_OK;
+  }
+};
+// the results v21_sample_out and v21_ensemble_out share, `keep` states per row, samples and x_last of esz bytes per element
+template <class Out>
+static void stage_sampler_out(ChunkStage& sg, const Out& host, Out& dev, long long keep, int din, size_t esz) {
+  sg.add(host.samples, &dev.samples, keep * din * esz);
+  sg.add(host.samples_lnl, &dev.samples_lnl, keep * sizeof(float));
+  sg.add(host.x_last, &dev.x_last, din * esz);
+  sg.add(host.lnl_last, &dev.lnl_last, sizeof(float));
+  sg.add(host.accept_rate, &dev.accept_rate, sizeof(double));
+  sg.add(host.mean_u, &dev.mean_u, din * sizeof(double));
+  sg.add(host.cov_u, &dev.cov_u, (size_t)din * din * sizeof(double));
+  sg.add(host.last_prop_u, &dev.last_prop_u, din * sizeof(float));
+  sg.add(host.last_log_alpha, &dev.last_log_alpha, sizeof(double));
 }
 
 // ---- trainer (api_trainer.hip)

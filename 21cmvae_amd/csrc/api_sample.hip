@@ -22,8 +22,6 @@ static v21_sample_opts sample_defaults() {
   return o;
 }
 
-static long long sample_keep(const v21_sample_opts& o) { return o.thin > 0 ? o.n_steps / o.thin : 0; }
-
 // the chains of n start rows prepped transformed (their fac is overwritten); `out`: device pointers, samples and x_last
 // of x_dtype; the call's first chain is global chain `chain0`, its row `row0` of the call (data rows as in fit_run).
 // tp: the ladder of a tempered call (n a multiple of its n_temps) and its results `to`, device pointers; nullptr:
@@ -43,7 +41,7 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   SampleArgs a{};
   a.n = n; a.din = din;
   a.total = (long long)o.n_warmup + o.n_steps; a.n_warmup = o.n_warmup;
-  a.thin = o.thin; a.n_keep = sample_keep(o);
+  a.thin = o.thin; a.n_keep = sample_keep(o.n_steps, o.thin);
   a.ridge = o.ridge; a.target = o.target_accept;
   a.seed = o.seed; a.chain0 = (uint64_t)chain0; a.step0 = (uint64_t)o.step0;
   a.samples = out.samples; a.samples_lnl = out.samples_lnl;
@@ -87,13 +85,18 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   return V21_OK;
 }
 
-int sample_check(const v21_sample_opts& o) {
-  if (o.n_steps < 0 || o.n_warmup < 0 || o.thin < 0 || !(o.eps0 > 0.0) || !std::isfinite(o.eps0) || !(o.ridge > 0.0) || !std::isfinite(o.ridge) ||
-      !(o.target_accept > 0.0 && o.target_accept < 1.0))
-    return fail(V21_ERR_ARG, "sample: options n_steps %d n_warmup %d thin %d eps0 %g ridge %g target_accept %g", o.n_steps, o.n_warmup, o.thin,
-                o.eps0, o.ridge, o.target_accept);
-  if (o.chain0 < 0 || o.step0 < 0 || o.step0 + (long long)o.n_warmup + o.n_steps >= (1LL << 32))
-    return fail(V21_ERR_ARG, "sample: options chain0 %lld step0 %lld (step0 + n_warmup + n_steps < 2^32)", o.chain0, o.step0);
+int sample_counts(const char* what, int n_steps, int n_warmup, int thin, long long chain0, long long step0) {
+  if (n_steps < 0 || n_warmup < 0 || thin < 0)
+    return fail(V21_ERR_ARG, "%s: options n_steps %d n_warmup %d thin %d", what, n_steps, n_warmup, thin);
+  if (chain0 < 0 || step0 < 0 || step0 + (long long)n_warmup + n_steps >= (1LL << 32))
+    return fail(V21_ERR_ARG, "%s: options chain0 %lld step0 %lld (step0 + n_warmup + n_steps < 2^32)", what, chain0, step0);
+  return V21_OK;
+}
+
+static int sample_check(const v21_sample_opts& o) {
+  CHK(sample_counts("sample", o.n_steps, o.n_warmup, o.thin, o.chain0, o.step0));
+  if (!(o.eps0 > 0.0) || !std::isfinite(o.eps0) || !(o.ridge > 0.0) || !std::isfinite(o.ridge) || !(o.target_accept > 0.0 && o.target_accept < 1.0))
+    return fail(V21_ERR_ARG, "sample: options eps0 %g ridge %g target_accept %g", o.eps0, o.ridge, o.target_accept);
   return V21_OK;
 }
 
@@ -114,55 +117,31 @@ extern "C" int v21_mlp_sample_dev(v21_mlp* m, const float* d_x0, int64_t ldx, in
 }
 
 // the host forms: chunks of chunk_rows chains (a whole number of ladders for a tempered call), each staged in
-// m->smp_out, run by sample_run and copied back
+// m->smp_out (ChunkStage), run by sample_run and copied back
 static int sample_host(v21_mlp* m, const void* x0, int x_dtype, long long n, const float* data, long long n_data, const v21_sample_opts& o,
                        const double* eps_start, const v21_sample_out* out, int precision, int flags, long long chunk_rows,
                        const v21_temper_opts* tp, const v21_temper_out* tout) {
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0], dout = m->dims[m->L];
-  hipStream_t st = m->ctx->stream;
-  const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
-  const long long keep = sample_keep(o);
   const int route = jac_route(m, flags, dout);
-  // a chunk's staging, in 8-byte units per chain: the start step sizes, then every result that was asked for
-  const long long chunk = std::min<long long>(n, chunk_rows);
-  const long long w_smp = out->samples ? keep * din : 0, w_sl = out->samples_lnl ? (keep + 1) / 2 : 0;
-  const long long per = 1 + w_smp + w_sl + din + 1 + 1 + 1 + din + (long long)din * din + din + 1 + (tp ? 3 : 0);
-  CHK(m->smp_out.reserve((size_t)(chunk * per)));
+  ChunkStage sg;
+  double* d_eps = nullptr;
+  v21_sample_out d{};
+  v21_temper_out t{};
+  sg.add(eps_start, &d_eps, sizeof(double), true);
+  stage_sampler_out(sg, *out, d, sample_keep(o.n_steps, o.thin), din, x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float));
+  sg.add(out->eps_last, &d.eps_last, sizeof(double));
+  if (tp && tout) {
+    sg.add(tout->mean_lnl, &t.mean_lnl, sizeof(double));
+    sg.add(tout->var_lnl, &t.var_lnl, sizeof(double));
+    sg.add(tout->swap_accept, &t.swap_accept, sizeof(double));
+  }
+  CHK(m->smp_out.reserve(sg.units(std::min<long long>(n, chunk_rows))));
   return jac_chunks(m, x0, x_dtype, n, 1, din * din + din + 3, [&](long long r0, long long rows, float*) -> int {
-    double* p = m->smp_out.get();
-    auto take = [&](long long units) { double* q = p; p += rows * units; return q; };
-    double* d_eps = take(1);
-    v21_sample_out d{};
-    d.samples = out->samples ? take(w_smp) : nullptr;
-    d.samples_lnl = out->samples_lnl ? (float*)take(w_sl) : nullptr;
-    d.x_last = take(din);
-    d.lnl_last = (float*)take(1);
-    d.eps_last = take(1);
-    d.accept_rate = take(1);
-    d.mean_u = take(din);
-    d.cov_u = take((long long)din * din);
-    d.last_prop_u = (float*)take(din);
-    d.last_log_alpha = take(1);
-    v21_temper_out t{};
-    if (tp) { t.mean_lnl = take(1); t.var_lnl = take(1); t.swap_accept = take(1); }
-    if (eps_start) HIPCHK(hipMemcpyAsync(d_eps, eps_start + r0, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, st));
-    CHK(sample_run(m, route, rows, cd, r0, o, o.chain0 + r0, eps_start ? d_eps : nullptr, precision, flags, d, x_dtype, tp, &t));
-    if (out->samples) CHK(to_host(m, (char*)out->samples + r0 * keep * din * esz, d.samples, (size_t)rows * keep * din * esz));
-    if (out->samples_lnl) CHK(to_host(m, out->samples_lnl + r0 * keep, d.samples_lnl, (size_t)rows * keep * sizeof(float)));
-    CHK(to_host(m, (char*)out->x_last + r0 * din * esz, d.x_last, (size_t)rows * din * esz));
-    if (out->lnl_last) CHK(to_host(m, out->lnl_last + r0, d.lnl_last, (size_t)rows * sizeof(float)));
-    if (out->eps_last) CHK(to_host(m, out->eps_last + r0, d.eps_last, (size_t)rows * sizeof(double)));
-    if (out->accept_rate) CHK(to_host(m, out->accept_rate + r0, d.accept_rate, (size_t)rows * sizeof(double)));
-    if (out->mean_u) CHK(to_host(m, out->mean_u + r0 * din, d.mean_u, (size_t)rows * din * sizeof(double)));
-    if (out->cov_u) CHK(to_host(m, out->cov_u + r0 * din * din, d.cov_u, (size_t)rows * din * din * sizeof(double)));
-    if (out->last_prop_u) CHK(to_host(m, out->last_prop_u + r0 * din, d.last_prop_u, (size_t)rows * din * sizeof(float)));
-    if (out->last_log_alpha) CHK(to_host(m, out->last_log_alpha + r0, d.last_log_alpha, (size_t)rows * sizeof(double)));
-    if (tout && tout->mean_lnl) CHK(to_host(m, tout->mean_lnl + r0, t.mean_lnl, (size_t)rows * sizeof(double)));
-    if (tout && tout->var_lnl) CHK(to_host(m, tout->var_lnl + r0, t.var_lnl, (size_t)rows * sizeof(double)));
-    if (tout && tout->swap_accept) CHK(to_host(m, tout->swap_accept + r0, t.swap_accept, (size_t)rows * sizeof(double)));
-    return V21_OK;
+    CHK(sg.place(m, r0, rows));
+    CHK(sample_run(m, route, rows, cd, r0, o, o.chain0 + r0, d_eps, precision, flags, d, x_dtype, tp, &t));
+    return sg.fetch(m, r0, rows);
   }, chunk_rows);
 }
 

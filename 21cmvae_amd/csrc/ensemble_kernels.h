@@ -4,8 +4,8 @@
 // H = W / 2 walkers; a sweep is two half-moves, and half-move h moves every walker of set h along the line to a
 // partner drawn from the current positions of set 1 - h.
 //   ensemble_step_kernel    one launch per half-move, after the evaluation of the pending proposals: it DECIDES them
-//                           (accepts or rejects, accumulates the moments, stores a thinned sample in raw units), meets
-//                           a barrier, then DRAWS the other set's proposals from the positions just decided;
+//                           (accepts or rejects, keeps the sweep: Moments of rowmath.h), meets a barrier, then DRAWS the
+//                           other set's proposals from the positions just decided;
 //   ensemble_finish_kernel  the last state back to raw parameters and the per-row results.
 // The proposals of one half-move lie compacted in a buffer of n / 2 rows (row e H + j: walker j of the moving set of
 // ensemble e): every ln L of a call, the starts' included, is evaluated in that layout on one route.
@@ -21,6 +21,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rowmath.h"
@@ -37,10 +38,9 @@ struct EnsRow {
   int pad_;
   double lz;             // (din - 1) ln z of the pending proposal
   double log_alpha;      // of the last half-move decided
-  double su[kFitMaxIn];  // moments of the kept sweeps: sum u, sum u u^T (upper triangle), accepted
-  double suu[kFitPacked];
-  long long accepted;
+  Moments m;             // of the kept sweeps
 };
+static_assert(offsetof(EnsRow, m) + sizeof(Moments) == sizeof(EnsRow), "the moments are the tail of the row state");
 
 // what one call's step launches share
 struct EnsArgs {
@@ -100,22 +100,8 @@ __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const fl
       // a kept sweep: moments, and every thin-th state in raw units
       double u[NI];
       widen_row(s.u, din, u);
-      int q = 0;
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        if (i < din) s.su[i] += u[i];
-#pragma unroll
-        for (int c = i; c < NI; ++c, ++q)
-          if (c < din) s.suu[q] += u[i] * u[c];
-      }
-      if (accept) s.accepted += 1;
-      const long long kept = sweep - a.n_warmup + 1;
-      if (a.thin > 0 && kept % a.thin == 0 && kept / a.thin <= a.n_keep) {
-        const long long at = row * a.n_keep + (kept / a.thin - 1);
-        if (a.samples)
-          for (int i = 0; i < din; ++i) ((XT*)a.samples)[at * din + i] = (XT)box_to_raw(u[i], i, a.t);
-        if (a.samples_lnl) a.samples_lnl[at] = s.lnl;
-      }
+      s.m.add(u, din, accept);
+      Moments::store<XT>(row, sweep - a.n_warmup + 1, a.thin, a.n_keep, a.samples, a.samples_lnl, u, din, s.lnl, a.t);
     }
     if (k + 2 > last && a.last_prop_u)  // (the walker's last decision of the call)
       for (int i = 0; i < din; ++i) a.last_prop_u[row * din + i] = y[i];
@@ -128,20 +114,15 @@ __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const fl
     EnsRow& s = st[row];
     float* y = prop + p * din;
     if (k < 2) {
-      // the start into the box (NaN -> -1, as box_clamp), the state reset
+      // the start into the box, the state reset
       const float* x0 = start + row * din;
-      for (int i = 0; i < din; ++i) {
-        const float v = x0[i];
-        y[i] = v >= -1.f ? (v <= 1.f ? v : 1.f) : -1.f;
-      }
+      for (int i = 0; i < din; ++i) y[i] = box_clamp1(x0[i]);
       s.lnl = 0.f;
       s.reject = 0;
       s.partner = -1;
       s.lz = 0.0;
       s.log_alpha = 0.0;
-      for (int i = 0; i < NI; ++i) s.su[i] = 0.0;
-      for (int i = 0; i < kFitPacked; ++i) s.suu[i] = 0.0;
-      s.accepted = 0;
+      s.m.clear();
     } else {
       const long long sweep = (k - 2) / 2;
       uint32_t w[4];
@@ -170,9 +151,8 @@ __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const fl
   }
 }
 
-// one thread per row: the last state in raw units (box_to_raw) and the per-row results (nullable): with K kept sweeps,
-// mean_u = sum u / K, cov_u = sum u u^T / K - mean_u mean_u^T (both triangles), accept_rate = accepted / K (K == 0: the
-// current position, zeros, 0)
+// one thread per row: the last state in raw units (raw_row) and the per-row results (nullable; the moments' over `kept`
+// sweeps: Moments::finish)
 struct EnsOutDev {
   void* x_last;
   float* lnl_last;
@@ -185,22 +165,9 @@ __global__ void __launch_bounds__(256) ensemble_finish_kernel(const EnsRow* __re
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   const EnsRow& s = st[row];
-  for (int j = 0; j < din; ++j) ((XT*)o.x_last)[row * din + j] = (XT)box_to_raw((double)s.u[j], j, t);
+  raw_row<XT>(o.x_last, row, din, s.u, t);
   if (o.lnl_last) o.lnl_last[row] = s.lnl;
-  if (o.accept_rate) o.accept_rate[row] = kept > 0 ? (double)s.accepted / (double)kept : 0.0;
-  const double inv = kept > 0 ? 1.0 / (double)kept : 0.0;
-  if (o.mean_u)
-    for (int j = 0; j < din; ++j) o.mean_u[row * din + j] = kept > 0 ? s.su[j] * inv : (double)s.u[j];
-  if (o.cov_u) {
-    int p = 0;
-    for (int i = 0; i < kFitMaxIn; ++i)
-      for (int j = i; j < kFitMaxIn; ++j, ++p)
-        if (j < din) {
-          const double c = kept > 0 ? s.suu[p] * inv - (s.su[i] * inv) * (s.su[j] * inv) : 0.0;
-          o.cov_u[(row * din + i) * din + j] = c;
-          o.cov_u[(row * din + j) * din + i] = c;
-        }
-  }
+  s.m.finish(row, din, kept, s.u, o.mean_u, o.cov_u, o.accept_rate);
   if (o.last_log_alpha) o.last_log_alpha[row] = s.log_alpha;
   if (o.last_partner) o.last_partner[row] = s.partner;
 }

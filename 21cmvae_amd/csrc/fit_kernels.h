@@ -111,14 +111,14 @@ static __global__ void __launch_bounds__(256) fit_lm_kernel(FitRow* __restrict__
     if (i < din) u[i] = s.p.u[i];
 }
 
-// one thread per row: x_hat (of type T) = the accepted point in raw units (box_to_raw), and the per-row results (nullable)
+// one thread per row: x_hat (of type T) = the accepted point in raw units (raw_row), and the per-row results (nullable)
 template <class T>
 __global__ void __launch_bounds__(256) fit_finish_kernel(const FitRow* __restrict__ st, void* __restrict__ x_hat, float* __restrict__ lnl,
                                   float* __restrict__ lnl0, int* __restrict__ status, long long n, int din, const v21_affine_in t) {
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   const FitRow& s = st[row];
-  for (int j = 0; j < din; ++j) ((T*)x_hat)[row * din + j] = (T)box_to_raw((double)s.p.u[j], j, t);
+  raw_row<T>(x_hat, row, din, s.p.u, t);
   if (lnl) lnl[row] = s.p.lnl;
   if (lnl0) lnl0[row] = s.lnl0;
   if (status) status[row] = s.status < 0 ? 0 : s.status;

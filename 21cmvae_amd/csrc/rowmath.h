@@ -1,5 +1,5 @@
-// rowmath.h -- what the per-row step kernels of the fit (fit_kernels.h) and the sampler (sample_kernels.h) share: one
-// thread per row, float64 in registers, in the transformed coordinates u in [-1, 1]^din (the training box par_transform
+// rowmath.h -- what the per-row step kernels of the fit (fit_kernels.h) and the samplers (sample_kernels.h,
+// ensemble_kernels.h) share: one thread per row, float64 in registers, in the transformed coordinates u in [-1, 1]^din (the training box par_transform
 // maps to), din <= kFitMaxIn.  Packed layouts: a symmetric matrix as its upper triangle by rows (element (i, j), i <= j, at
 // i NI - i (i - 1) / 2 + (j - i)), a Cholesky factor L as its lower triangle by rows (L[i][j] at i (i + 1) / 2 + j); rows
 // and columns >= din are those of the identity, so every loop runs over NI = kFitMaxIn with constant indices.
@@ -8,7 +8,10 @@
 //                           Fisher matrix, to float64 registers;
 //   chol_factor             L of F + diag(addend), the caller's addend and pivot test;
 //   solve_lower / _upper    L z = g and L^T x = z;
-//   box_clamp / box_to_raw  a start row into the box, and a coordinate back to raw units.
+//   box_clamp1 / box_clamp  a coordinate, and a start row, into the box;
+//   box_to_raw / raw_row    a coordinate, and a row of a result, back to raw units;
+//   Moments                 the bookkeeping of a sampler's kept transitions, the tail of its row state: the sums of u and
+//                           u u^T and the accepted count, the thinned store of a state, the per-row results.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -120,12 +123,13 @@ __device__ inline void solve_upper(const double* Lm, const double* z, double* x)
   }
 }
 
-// a transformed start row (pitch din, the row the next evaluation reads) into the box: clamp(xt, -1, 1), NaN -> -1 (a
-// log column's non-positive raw value); fac = 1 (the evaluations run on u, without the input transform)
+// a coordinate into the box: clamp(v, -1, 1), NaN -> -1 (a log column's non-positive raw value)
+__device__ inline float box_clamp1(float v) { return v >= -1.f ? (v <= 1.f ? v : 1.f) : -1.f; }
+// a transformed start row (pitch din, the row the next evaluation reads) into the box; fac = 1 (the evaluations run on
+// u, without the input transform)
 __device__ inline void box_clamp(float* up, float* fac, int din) {
   for (int j = 0; j < din; ++j) {
-    const float v = up[j];
-    up[j] = v >= -1.f ? (v <= 1.f ? v : 1.f) : -1.f;
+    up[j] = box_clamp1(up[j]);
     fac[j] = 1.f;
   }
 }
@@ -136,5 +140,65 @@ __device__ inline double box_to_raw(double u, int j, const v21_affine_in& t) {
   if (t.log_mask[j]) v = pow(10.0, v);
   return v;
 }
+// row `row` of x (n, din) of type T = the point u in raw units
+template <class T>
+__device__ inline void raw_row(void* x, long long row, int din, const float* u, const v21_affine_in& t) {
+  for (int j = 0; j < din; ++j) ((T*)x)[row * din + j] = (T)box_to_raw((double)u[j], j, t);
+}
+
+// ---- the kept transitions of a sampler's row (a chain, a rung, a walker)
+struct Moments {
+  double su[kFitMaxIn];    // sum u
+  double suu[kFitPacked];  // sum u u^T, upper triangle by rows
+  long long accepted;
+
+  __device__ void clear() {
+    for (int i = 0; i < kFitMaxIn; ++i) su[i] = 0.0;
+    for (int i = 0; i < kFitPacked; ++i) suu[i] = 0.0;
+    accepted = 0;
+  }
+  // one kept transition that ended at u
+  __device__ __forceinline__ void add(const double* u, int din, bool accept) {
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < kFitMaxIn; ++i) {
+      if (i < din) su[i] += u[i];
+#pragma unroll
+      for (int j = i; j < kFitMaxIn; ++j, ++p)
+        if (j < din) suu[p] += u[i] * u[j];
+    }
+    if (accept) accepted += 1;
+  }
+  // the state (u, lnl) after kept transition k = 1, 2 .. of `row`: every thin-th (thin = 0: none) of the first n_keep thin
+  // goes to samples (n, n_keep, din; raw units, type T) and samples_lnl (n, n_keep), both nullable
+  template <class T>
+  __device__ __forceinline__ static void store(long long row, long long k, long long thin, long long n_keep, void* samples,
+                                               float* samples_lnl, const double* u, int din, const float& lnl, const v21_affine_in& t) {
+    if (thin > 0 && k % thin == 0 && k / thin <= n_keep) {
+      const long long slot = row * n_keep + (k / thin - 1);
+      if (samples)
+        for (int j = 0; j < din; ++j) ((T*)samples)[slot * din + j] = (T)box_to_raw(u[j], j, t);
+      if (samples_lnl) samples_lnl[slot] = lnl;
+    }
+  }
+  // the per-row results (nullable) over K = kept transitions: mean_u = sum u / K, cov_u = sum u u^T / K - mean_u mean_u^T
+  // (both triangles), accept_rate = accepted / K (K == 0: the current point u, zeros, 0)
+  __device__ void finish(long long row, int din, long long kept, const float* u, double* mean_u, double* cov_u, double* accept_rate) const {
+    if (accept_rate) accept_rate[row] = kept > 0 ? (double)accepted / (double)kept : 0.0;
+    const double inv = kept > 0 ? 1.0 / (double)kept : 0.0;
+    if (mean_u)
+      for (int j = 0; j < din; ++j) mean_u[row * din + j] = kept > 0 ? su[j] * inv : (double)u[j];
+    if (cov_u) {
+      int p = 0;
+      for (int i = 0; i < kFitMaxIn; ++i)
+        for (int j = i; j < kFitMaxIn; ++j, ++p)
+          if (j < din) {
+            const double c = kept > 0 ? suu[p] * inv - (su[i] * inv) * (su[j] * inv) : 0.0;
+            cov_u[(row * din + i) * din + j] = c;
+            cov_u[(row * din + j) * din + i] = c;
+          }
+    }
+  }
+};
 
 }  // namespace v21

@@ -3,8 +3,8 @@
 // transformed coordinates u in [-1, 1]^din of the fit (fit_kernels.h) under a uniform prior on that box.
 //   sample_init_kernel    clamps the transformed start rows into the box and resets the chain state;
 //   sample_step_kernel    consumes the evaluation (ln L, gradient, Fisher matrix: jac_reduce_kernel) of the pending
-//                         proposal: accepts or rejects it, adapts the step size in warm-up, accumulates the moments,
-//                         stores a thinned sample in raw units, then draws and writes the next proposal;
+//                         proposal: accepts or rejects it, adapts the step size in warm-up, keeps the transition
+//                         (rowmath.h: Moments), then draws and writes the next proposal;
 //   sample_finish_kernel  the last state back to raw parameters and the results;
 //   sample_step_tempered_kernel / sample_finish_tempered_kernel  the same chains as the rungs of parallel-tempered ladders
 //                         (below, "parallel tempering"): the step kernel's three parts with ln L, g and F scaled by the
@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rowmath.h"
@@ -57,10 +58,9 @@ struct SampleRow {
   double eps;                    // step size
   double lq_fwd;                 // log q(pending proposal | current point)
   double log_alpha;              // of the last transition decided
-  double su[kFitMaxIn];          // moments of the kept transitions: sum u, sum u u^T (upper triangle), accepted
-  double suu[kFitPacked];
-  long long accepted;
+  Moments m;                     // of the kept transitions
 };
+static_assert(offsetof(SampleRow, m) + sizeof(Moments) == sizeof(SampleRow), "the moments are the tail of the row state");
 
 // what one sample call's step launches share
 struct SampleArgs {
@@ -120,9 +120,7 @@ static __global__ void __launch_bounds__(256) sample_init_kernel(SampleRow* __re
   s.reject = 0;
   s.lq_fwd = 0.0;
   s.log_alpha = 0.0;
-  for (int i = 0; i < kFitMaxIn; ++i) s.su[i] = 0.0;
-  for (int i = 0; i < kFitPacked; ++i) s.suu[i] = 0.0;
-  s.accepted = 0;
+  s.m.clear();
 }
 
 // ---- the three parts of a step, shared by sample_step_kernel and sample_step_tempered_kernel.  TEMPER: ln L, g and F
@@ -192,25 +190,9 @@ __device__ __forceinline__ bool sample_decide(SampleRow& s, const float* upr, co
 // samples' type.
 template <class T>
 __device__ __forceinline__ void sample_keep(SampleRow& s, const double* u, bool accept, long long it, long long row, const SampleArgs& a) {
-  constexpr int NI = kFitMaxIn;
-  const int din = a.din;
   if (it > a.n_warmup) {
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      if (i < din) s.su[i] += u[i];
-#pragma unroll
-      for (int j = i; j < NI; ++j, ++p)
-        if (j < din) s.suu[p] += u[i] * u[j];
-    }
-    if (accept) s.accepted += 1;
-    const long long k = it - a.n_warmup;  // kept transitions so far
-    if (a.thin > 0 && k % a.thin == 0 && k / a.thin <= a.n_keep) {
-      const long long slot = row * a.n_keep + (k / a.thin - 1);
-      if (a.samples)
-        for (int j = 0; j < din; ++j) ((T*)a.samples)[slot * din + j] = (T)box_to_raw(u[j], j, a.t);
-      if (a.samples_lnl) a.samples_lnl[slot] = s.p.lnl;
-    }
+    s.m.add(u, a.din, accept);
+    Moments::store<T>(row, it - a.n_warmup, a.thin, a.n_keep, a.samples, a.samples_lnl, u, a.din, s.p.lnl, a.t);
   }
 }
 
@@ -385,9 +367,8 @@ __global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st
   sample_draw<true>(s, upr, u, it, row, a, beta, eps, Lm, mu, ld, have_factor);
 }
 
-// one thread per chain: the last state in raw units (box_to_raw) and the per-chain
-// results (nullable): with K kept transitions, mean_u = sum u / K, cov_u = sum u u^T / K - mean_u mean_u^T (both
-// triangles), accept_rate = accepted / K (K == 0: the current point, zeros, 0)
+// one thread per chain: the last state in raw units (raw_row) and the per-chain results (nullable; the moments'
+// over `kept` transitions: Moments::finish)
 struct SampleOutDev {
   void* x_last;
   float* lnl_last;
@@ -401,23 +382,10 @@ __global__ void __launch_bounds__(256) sample_finish_kernel(const SampleRow* __r
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   const SampleRow& s = st[row];
-  for (int j = 0; j < din; ++j) ((T*)o.x_last)[row * din + j] = (T)box_to_raw((double)s.p.u[j], j, t);
+  raw_row<T>(o.x_last, row, din, s.p.u, t);
   if (o.lnl_last) o.lnl_last[row] = s.p.lnl;
   if (o.eps_last) o.eps_last[row] = s.eps;
-  if (o.accept_rate) o.accept_rate[row] = kept > 0 ? (double)s.accepted / (double)kept : 0.0;
-  const double inv = kept > 0 ? 1.0 / (double)kept : 0.0;
-  if (o.mean_u)
-    for (int j = 0; j < din; ++j) o.mean_u[row * din + j] = kept > 0 ? s.su[j] * inv : (double)s.p.u[j];
-  if (o.cov_u) {
-    int p = 0;
-    for (int i = 0; i < kFitMaxIn; ++i)
-      for (int j = i; j < kFitMaxIn; ++j, ++p)
-        if (j < din) {
-          const double c = kept > 0 ? s.suu[p] * inv - (s.su[i] * inv) * (s.su[j] * inv) : 0.0;
-          o.cov_u[(row * din + i) * din + j] = c;
-          o.cov_u[(row * din + j) * din + i] = c;
-        }
-  }
+  s.m.finish(row, din, kept, s.p.u, o.mean_u, o.cov_u, o.accept_rate);
   if (o.last_prop_u)
     for (int j = 0; j < din; ++j) o.last_prop_u[row * din + j] = up[row * din + j];
   if (o.last_log_alpha) o.last_log_alpha[row] = s.log_alpha;

@@ -479,6 +479,53 @@ class _EmulatorBase:
         F = st.fisher(x, model.precision, flags)
         return F[0] if x.shape[0] == 1 else F
 
+    def _spectra(self, data):
+        """(model, stack, flags) of ``_diff_stack`` and observed signal(s) (451,) or (M, 451) as contiguous float32 (M, 451),
+        with whether there was one"""
+        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
+        nb = st.dims[-1]
+        dat = np.asarray(data, np.float32)
+        one = dat.ndim == 1
+        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
+        if dat.ndim != 2 or dat.shape[1] != nb:
+            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        return model, st, flags, dat, one
+
+    def _sampler_starts(self, st, dat, per, p0, sigma, flow, fhigh, seed, foreground):
+        """The samplers' raw start rows (M prod(per), din), ``per`` the shape of one spectrum's starts: ``p0`` ((din,) or
+        (per[-1], din), the same for every spectrum) or the best ``fit_parameters`` start per spectrum, every row jittered
+        (seeded, 0.02 in u, clipped into the box); then the call's likelihood record is set on the stack"""
+        din, shape = st.dims[0], (dat.shape[0],) + tuple(per) + (st.dims[0],)
+        if p0 is None:
+            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
+            u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], int(np.prod(per)), axis=1).reshape(shape)
+        else:
+            starts = np.array(p0, np.float64, ndmin=2)
+            if starts.ndim != 2 or starts.shape[1] != din or starts.shape[0] not in (1, per[-1]):
+                raise ValueError("p0 must be (%d,) or (%d, %d), got %r" % (din, per[-1], din, np.shape(p0)))
+            u0 = np.broadcast_to(pp.par_transform(starts, self.par_train), shape)
+        rng = np.random.default_rng(seed)
+        u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=shape), -1.0, 1.0)
+        x0 = pp.par_untransform(u0.reshape(-1, din), self.par_train)
+        self._use_record(st, dat[0], self._band_weights(st.dims[-1], sigma, flow, fhigh), foreground, flow, fhigh)
+        return x0
+
+    @staticmethod
+    def _posterior_samples(r, view, n_kept, return_lnl, one):
+        """``PosteriorSamples`` from a sampler's result arrays r; view: a per-row array (n, ...) -> (M, chains, ...), or
+        (M, ensembles, walkers, ...) whose walkers are pooled before the ensembles are compared; n_kept: kept transitions"""
+        K = r["samples"].shape[1] if "samples" in r else 0
+        params = view(r["samples"]) if K else None
+        lnl = view(r["samples_lnl"]) if K and return_lnl else None
+        acc, step = view(r["accept_rate"]), (view(r["eps_last"]) if "eps_last" in r else None)
+        mean_c, cov_c = view(r["mean_u"]), view(r["cov_u"])
+        if mean_c.ndim == 4:
+            n_kept *= mean_c.shape[2]
+            mean_c, cov_c = pooled_moments(mean_c, cov_c)
+        rh = r_hat_from_moments(mean_c, cov_c, n_kept)
+        out = (params, lnl, acc, step, rh) + pooled_moments(mean_c, cov_c)
+        return PosteriorSamples(*[a[0] if one and a is not None else a for a in out])
+
     def fit_parameters(self, data, sigma, p0=None, n_starts=8, max_iter=50, flow=None, fhigh=None, seed=0, return_all=False,
                        return_fisher=False, foreground=None):
         """Maximum-likelihood parameters of observed signal(s) (not in the reference): a projected Levenberg-Marquardt fit
@@ -490,14 +537,8 @@ class _EmulatorBase:
         1 converged, 2 no improving step, 3 no information (all weights zero), 0 ``max_iter`` reached.  ``fisher``: the
         Fisher matrix at the result in raw units.  Bounds: a log column's lower bound comes back as 10^lo (the fx zero
         floor 1e-6, not 0)."""
-        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
-        nb = st.dims[-1]
-        dat = np.asarray(data, np.float32)
-        one = dat.ndim == 1
-        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
-        if dat.ndim != 2 or dat.shape[1] != nb:
-            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
-        din = st.dims[0]
+        model, st, flags, dat, one = self._spectra(data)
+        nb, din = st.dims[-1], st.dims[0]
         if p0 is None:
             if int(n_starts) < 1:
                 raise ValueError("n_starts must be >= 1")
@@ -544,42 +585,15 @@ class _EmulatorBase:
         potential scale reduction in u -- and the pooled mean_u (M, 7) / cov_u (M, 7, 7), all three from the per-chain
         moments the device accumulates in float64; the M axis is dropped for one spectrum.  Bounds: a log column's lower
         bound comes back as 10^lo (the fx zero floor 1e-6, not 0)."""
-        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
-        nb, din = st.dims[-1], st.dims[0]
-        dat = np.asarray(data, np.float32)
-        one = dat.ndim == 1
-        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
-        if dat.ndim != 2 or dat.shape[1] != nb:
-            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        model, st, flags, dat, one = self._spectra(data)
         M, C = dat.shape[0], int(n_chains)
         if C < 1:
             raise ValueError("n_chains must be >= 1")
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
-        if p0 is None:
-            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
-            u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], C, axis=1)
-        else:
-            starts = np.array(p0, np.float64, ndmin=2)
-            if starts.ndim != 2 or starts.shape[1] != din or starts.shape[0] not in (1, C):
-                raise ValueError("p0 must be (%d,) or (%d, %d), got %r" % (din, C, din, np.shape(p0)))
-            u0 = np.broadcast_to(pp.par_transform(starts, self.par_train)[None], (M, C, din))
-        rng = np.random.default_rng(seed)
-        u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=(M, C, din)), -1.0, 1.0)
-        x0 = np.ascontiguousarray(pp.par_untransform(u0.reshape(M * C, din), self.par_train))
-        self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
+        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground))
         r = st.sample(x0, model.precision, flags, data=dat, **opts)
-        K = r["samples"].shape[1] if "samples" in r else 0
-        params = r["samples"].reshape(M, C, K, din) if K else None
-        lnl = r["samples_lnl"].reshape(M, C, K) if K and return_lnl else None
-        acc, step = r["accept_rate"].reshape(M, C), r["eps_last"].reshape(M, C)
-        mean_c, cov_c = r["mean_u"].reshape(M, C, din), r["cov_u"].reshape(M, C, din, din)
-        rh = r_hat_from_moments(mean_c, cov_c, int(n_steps))
-        mean, cov = pooled_moments(mean_c, cov_c)
-        if one:
-            params, lnl = (params[0] if params is not None else None), (lnl[0] if lnl is not None else None)
-            acc, step, rh, mean, cov = acc[0], step[0], rh[0], mean[0], cov[0]
-        return PosteriorSamples(params, lnl, acc, step, rh, mean, cov)
+        return self._posterior_samples(r, lambda a: a.reshape((M, C) + a.shape[1:]), int(n_steps), return_lnl, one)
 
     def sample_ensemble(self, data, sigma, n_walkers=64, n_ensembles=4, n_steps=1000, n_warmup=500, thin=1, a=2.0, p0=None, flow=None,
                         fhigh=None, seed=0, return_lnl=False, foreground=None):
@@ -597,42 +611,16 @@ class _EmulatorBase:
         r_hat (M, 7) taken BETWEEN ENSEMBLES -- the walkers of one ensemble are not independent chains, so each ensemble's
         walkers are pooled (``pooled_moments``) and the ensembles compared (``r_hat_from_moments``; NaN for one ensemble) --
         and the pooled mean_u (M, 7) / cov_u (M, 7, 7); the M axis is dropped for one spectrum."""
-        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
-        nb, din = st.dims[-1], st.dims[0]
-        dat = np.asarray(data, np.float32)
-        one = dat.ndim == 1
-        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
-        if dat.ndim != 2 or dat.shape[1] != nb:
-            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        model, st, flags, dat, one = self._spectra(data)
+        din = st.dims[0]
         M, E, W = dat.shape[0], int(n_ensembles), int(n_walkers)
         if E < 1:
             raise ValueError("n_ensembles must be >= 1")
         opts = dict(a=a, n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed)
         nat.Stack.ensemble_opts(W, in_dim=din, **opts)  # (argument errors before any device work)
-        if p0 is None:
-            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
-            u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], E * W, axis=1).reshape(M, E, W, din)
-        else:
-            starts = np.array(p0, np.float64, ndmin=2)
-            if starts.ndim != 2 or starts.shape[1] != din or starts.shape[0] not in (1, W):
-                raise ValueError("p0 must be (%d,) or (%d, %d), got %r" % (din, W, din, np.shape(p0)))
-            u0 = np.broadcast_to(pp.par_transform(starts, self.par_train)[None, None], (M, E, W, din))
-        rng = np.random.default_rng(seed)
-        u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=(M, E, W, din)), -1.0, 1.0)
-        x0 = np.ascontiguousarray(pp.par_untransform(u0.reshape(M * E * W, din), self.par_train))
-        self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
+        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (E, W), p0, sigma, flow, fhigh, seed, foreground))
         r = st.sample_ensemble(x0, W, model.precision, flags, data=dat, **opts)
-        K = r["samples"].shape[1] if "samples" in r else 0
-        params = r["samples"].reshape(M, E, W, K, din) if K else None
-        lnl = r["samples_lnl"].reshape(M, E, W, K) if K and return_lnl else None
-        acc = r["accept_rate"].reshape(M, E, W)
-        mean_e, cov_e = pooled_moments(r["mean_u"].reshape(M, E, W, din), r["cov_u"].reshape(M, E, W, din, din))
-        rh = r_hat_from_moments(mean_e, cov_e, int(n_steps) * W)
-        mean, cov = pooled_moments(mean_e, cov_e)
-        if one:
-            params, lnl = (params[0] if params is not None else None), (lnl[0] if lnl is not None else None)
-            acc, rh, mean, cov = acc[0], rh[0], mean[0], cov[0]
-        return PosteriorSamples(params, lnl, acc, None, rh, mean, cov)
+        return self._posterior_samples(r, lambda a: a.reshape((M, E, W) + a.shape[1:]), int(n_steps), return_lnl, one)
 
     def sample_tempered(self, data, sigma, n_ladders=16, n_temps=8, betas=None, swap_every=5, n_steps=1000, n_warmup=200, thin=1,
                         p0=None, flow=None, fhigh=None, seed=0, eps=None, return_lnl=False, foreground=None):
@@ -656,13 +644,7 @@ class _EmulatorBase:
         noise levels at the same data and the same foreground basis (add the dropped -sum ln(sigma sqrt(2 pi)) over the
         band's bins where sigma or the band differ).  It is NOT comparable across different numbers of marginalised
         foreground modes: their flat prior is improper.  nan with ``n_temps = 1``."""
-        model, st, flags, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
-        nb, din = st.dims[-1], st.dims[0]
-        dat = np.asarray(data, np.float32)
-        one = dat.ndim == 1
-        dat = np.ascontiguousarray(dat.reshape(1, -1) if one else dat)
-        if dat.ndim != 2 or dat.shape[1] != nb:
-            raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
+        model, st, flags, dat, one = self._spectra(data)
         M, C, T = dat.shape[0], int(n_ladders), int(n_temps)
         if C < 1:
             raise ValueError("n_ladders must be >= 1")
@@ -670,28 +652,11 @@ class _EmulatorBase:
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
         nat.Stack.temper_opts(T, b, swap_every)
-        if p0 is None:
-            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
-            u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], C, axis=1)
-        else:
-            starts = np.array(p0, np.float64, ndmin=2)
-            if starts.ndim != 2 or starts.shape[1] != din or starts.shape[0] not in (1, C):
-                raise ValueError("p0 must be (%d,) or (%d, %d), got %r" % (din, C, din, np.shape(p0)))
-            u0 = np.broadcast_to(pp.par_transform(starts, self.par_train)[None], (M, C, din))
-        rng = np.random.default_rng(seed)
-        u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=(M, C, din)), -1.0, 1.0)
-        x0 = pp.par_untransform(u0.reshape(M * C, din), self.par_train)
+        x0 = self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground)
         x0 = np.ascontiguousarray(np.repeat(x0, T, axis=0))  # (every rung of a ladder from its ladder's start)
-        self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
         r = st.sample_tempered(x0, T, b, swap_every, model.precision, flags, data=dat, **opts)
-        cold = lambda a: a.reshape((M, C, T) + a.shape[1:])[:, :, 0]  # the beta = 1 rows
-        K = r["samples"].shape[1] if "samples" in r else 0
-        params = cold(r["samples"]) if K else None
-        lnl = cold(r["samples_lnl"]) if K and return_lnl else None
-        acc, step = cold(r["accept_rate"]), cold(r["eps_last"])
-        mean_c, cov_c = cold(r["mean_u"]), cold(r["cov_u"])
-        rh = r_hat_from_moments(mean_c, cov_c, int(n_steps))
-        mean, cov = pooled_moments(mean_c, cov_c)
+        # (the beta = 1 rows)
+        ps = self._posterior_samples(r, lambda a: a.reshape((M, C, T) + a.shape[1:])[:, :, 0], int(n_steps), return_lnl, one)
         E = r["mean_lnl"].reshape(M, C, T)
         with np.errstate(invalid="ignore", divide="ignore"):
             # (pooled over ladders: every ladder proposes a pair equally often, so the mean of the ratios is the ratio)
@@ -700,10 +665,8 @@ class _EmulatorBase:
             lz = lz_c.mean(axis=1) if T > 1 else np.full(M, np.nan)
             lz_err = lz_c.std(axis=1, ddof=1) / np.sqrt(C) if T > 1 and C > 1 else np.full(M, np.nan)
         if one:
-            params, lnl = (params[0] if params is not None else None), (lnl[0] if lnl is not None else None)
-            acc, step, rh, mean, cov = acc[0], step[0], rh[0], mean[0], cov[0]
             E, swap, lz, lz_err = E[0], swap[0], lz[0], lz_err[0]
-        return TemperedSamples(params, lnl, acc, step, rh, mean, cov, b, E, swap, lz, lz_err)
+        return TemperedSamples(*ps, b, E, swap, lz, lz_err)
 
     def save(self):
         raise NotImplementedError("Not implemented yet.")
