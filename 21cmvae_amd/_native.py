@@ -108,6 +108,22 @@ class EnsembleOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ENSEMBLE_OUTPUTS]
 
 
+class NestedOpts(C.Structure):
+    """v21_nested_opts (include/v21_types.h)"""
+    _fields_ = [("n_live", C.c_int), ("n_repeats", C.c_int), ("n_iter", C.c_int), ("gamma", C.c_double), ("seed", C.c_ulonglong),
+                ("iter0", C.c_longlong), ("chain0", C.c_longlong)]
+
+
+NESTED_DEFAULTS = {"n_live": 256, "n_repeats": 0, "n_iter": 100, "gamma": 0.0, "seed": 0, "iter0": 0, "chain0": 0}
+NESTED_OUTPUTS = ("dead_u", "dead_lnl", "lstar", "live_u", "live_lnl", "accept_rate", "last_partner", "last_prop_u")
+NESTED_MIN_LIVE, NESTED_MAX_LIVE = 16, 512
+
+
+class NestedOut(C.Structure):
+    """v21_nested_out (include/v21_types.h): host or device addresses, NULL = not asked for"""
+    _fields_ = [(k, C.c_void_p) for k in NESTED_OUTPUTS]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 # name -> (restype, argtypes); every symbol include/v21.h declares
@@ -194,6 +210,12 @@ SIGNATURES = {
                                               C.c_int, C.c_int]),
     "v21_route_ensemble": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "v21_mlp_sample_nested": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(NestedOpts), C.POINTER(NestedOut), C.c_int,
+                                        C.c_int]),
+    "v21_mlp_sample_nested_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(NestedOpts), C.POINTER(NestedOut),
+                                            C.c_int, C.c_int]),
+    "v21_route_nested": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "v21_nuisance_whiten": (C.c_int, [C.POINTER(C.c_double), _F, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "v21_mlp_set_nuisance": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, C.c_int32]),
     "v21_mlp_nuisance_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
@@ -274,6 +296,16 @@ def route_ensemble(dims, act, precision, n, n_walkers, n_data=0, n_modes=0, flag
     r, c = C.c_int(0), C.c_int64(0)
     check(load_library().v21_route_ensemble(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_walkers),
                                             int(n_modes), int(flags), 1 if host_form else 0, C.byref(r), C.byref(c)))
+    return LNL_ROUTES[r.value], int(c.value)
+
+
+def route_nested(dims, act, precision, n, n_live, n_data=0, n_modes=0, flags=0, host_form=False):
+    """The route v21_mlp_sample_nested[_dev] takes for n rows in runs of n_live live points against n_data data rows (0: the
+    likelihood record) with n_modes nuisance modes, and the rows of a host chunk (the _dev form: n) (pure host logic: no
+    GPU; EngineError for the shapes the library refuses).  -> (name of LNL_ROUTES, chunk rows)."""
+    r, c = C.c_int(0), C.c_int64(0)
+    check(load_library().v21_route_nested(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_live),
+                                          int(n_modes), int(flags), 1 if host_form else 0, C.byref(r), C.byref(c)))
     return LNL_ROUTES[r.value], int(c.value)
 
 
@@ -1101,6 +1133,79 @@ class Stack(_Owned):
     def route_ensemble(self, precision, n, n_walkers, n_data=0, flags=0, host_form=False):
         """(route, chunk rows) a sample_ensemble call of n rows in ensembles of n_walkers takes on this stack now"""
         return route_ensemble(self.dims, self.act, precision, n, n_walkers, n_data, self.nuisance_modes(), flags, host_form)
+
+    @staticmethod
+    def nested_opts(n_live=None, n_repeats=None, n_iter=None, gamma=None, seed=None, iter0=None, chain0=None, n=None, n_data=0,
+                    in_dim=None):
+        """v21_nested_opts with the defaults of NESTED_DEFAULTS for None; ValueError for what the library would refuse --
+        with in_dim also a move counter that would overflow at the default n_repeats, with n (and n_data, 0:
+        the record's data) also the rows of a call that are no whole runs, or whose runs would straddle two data rows"""
+        o = dict(NESTED_DEFAULTS)
+        o.update({k: v for k, v in (("n_live", n_live), ("n_repeats", n_repeats), ("n_iter", n_iter), ("gamma", gamma), ("seed", seed),
+                                    ("iter0", iter0), ("chain0", chain0)) if v is not None})
+        for k in ("n_live", "n_repeats", "n_iter", "seed", "iter0", "chain0"):
+            if int(o[k]) != o[k] or int(o[k]) < 0:
+                raise ValueError("sample_nested: %s = %r (a non-negative integer)" % (k, o[k]))
+        if int(o["n_repeats"]) >= 2 ** 31 or int(o["n_iter"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64 or int(o["iter0"]) >= 2 ** 32:
+            raise ValueError("sample_nested: count out of range")
+        rep = int(o["n_repeats"]) or 3 * (int(in_dim) if in_dim is not None else 1)
+        if (int(o["iter0"]) + int(o["n_iter"])) * rep >= 2 ** 32:
+            raise ValueError("sample_nested: (iter0 + n_iter) n_repeats must stay below 2^32")
+        if not 0.0 <= float(o["gamma"]) <= 1e6:
+            raise ValueError("sample_nested: gamma = %r (0 .. 1e6; 0: the default)" % (o["gamma"],))
+        N = int(o["n_live"])
+        if N % 2 or not NESTED_MIN_LIVE <= N <= NESTED_MAX_LIVE:
+            raise ValueError("sample_nested: n_live = %d (even, %d .. %d)" % (N, NESTED_MIN_LIVE, NESTED_MAX_LIVE))
+        if n is not None and (n % N or (n_data and (n // n_data) % N)):
+            raise ValueError("sample_nested: %d rows%s are no whole runs of %d" % (n, " over %d data rows" % n_data if n_data else "", N))
+        return NestedOpts(N, int(o["n_repeats"]), int(o["n_iter"]), float(o["gamma"]), int(o["seed"]), int(o["iter0"]), int(o["chain0"]))
+
+    def sample_nested(self, u0=None, n=None, n_live=256, precision="f32", flags=0, data=None, dead=True, diagnostics=False, **opts):
+        """Nested sampling on forward-only ln L, on the device (include/v21.h: v21_mlp_sample_nested; needs a likelihood
+        record): n_live consecutive rows are one run, the live points of one spectrum (even, 16 .. 512; an evidence needs 8 in or more).
+        Everything is in u = par_transform's coordinates, the prior uniform on [-1, 1]^in.  u0: (n, in) live points to
+        start from (float32 or float64; a run continues exactly from an earlier live_u with iter0 moved on), or None with
+        n: drawn uniform from the seed.  data as for fit (the rows of one spectrum must be whole runs); opts: n_repeats,
+        n_iter, gamma, seed, iter0, chain0 (NESTED_DEFAULTS).
+        -> dict live_u (n, in) in u0's dtype (float64 for None), live_lnl (n,) float32, accept_rate (runs, n_live / 2) and,
+        with dead, dead_u (n_iter, runs, n_live / 2, in), dead_lnl, lstar (n_iter, runs); with diagnostics, last_partner
+        (runs, n_live / 2, 2) int32 and last_prop_u (runs, n_live / 2, in) float32 of the last move."""
+        din = self.dims[0]
+        if din > 8:
+            raise ValueError("sample_nested: %d parameters (at most 8)" % din)
+        if u0 is None:
+            if n is None:
+                raise ValueError("sample_nested: start rows or their number")
+            x, dt, n = None, 1, int(n)
+        else:
+            x, dt = self._rows(u0)
+            n = x.shape[0]
+        dp, nd = _data_rows("sample_nested", data, n, self.dims[-1])
+        o = self.nested_opts(n_live, n=n, n_data=nd, in_dim=din, **opts)
+        runs, k, T, ut = n // o.n_live, o.n_live // 2, o.n_iter, (np.float64 if x is None else x.dtype)
+        res = {"live_u": np.empty((n, din), ut), "live_lnl": np.empty(n, np.float32), "accept_rate": np.empty((runs, k), np.float64)}
+        if dead:
+            res.update({"dead_u": np.empty((T, runs, k, din), ut), "dead_lnl": np.empty((T, runs, k), np.float32),
+                        "lstar": np.empty((T, runs), np.float32)})
+        if diagnostics:
+            res.update({"last_partner": np.empty((runs, k, 2), np.int32), "last_prop_u": np.empty((runs, k, din), np.float32)})
+        out = NestedOut(**{key: v.ctypes.data for key, v in res.items()})
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_sample_nested(self.h, x.ctypes.data_as(_P) if x is not None else None, dt, n, _opt(dp), nd, C.byref(o),
+                                                 C.byref(out), precision_id(precision), flags))
+        return res
+
+    def sample_nested_dev(self, d_u0, ldx, n, d_data, n_data, out, n_live=256, precision="f32", flags=0, **opts):
+        """v21_mlp_sample_nested_dev: d_u0 a device address or None (drawn starts), out a dict of device addresses by the
+        names of NESTED_OUTPUTS (live_u required; dead_u and live_u float32); asynchronous on the context's stream."""
+        o = self.nested_opts(n_live, in_dim=self.dims[0], **opts)
+        so = NestedOut(**{k: int(v) for k, v in out.items() if v})
+        check(self.lib.v21_mlp_sample_nested_dev(self.h, _P(d_u0) if d_u0 else None, ldx, n, _opt(d_data), n_data, C.byref(o), C.byref(so),
+                                                 precision_id(precision), flags))
+
+    def route_nested(self, precision, n, n_live, n_data=0, flags=0, host_form=False):
+        """(route, chunk rows) a sample_nested call of n rows in runs of n_live takes on this stack now"""
+        return route_nested(self.dims, self.act, precision, n, n_live, n_data, self.nuisance_modes(), flags, host_form)
 
     def last_jac_route(self):
         """(route name of the last Jacobian / log-likelihood call, {route name: calls since creation})."""

@@ -45,6 +45,7 @@ constexpr int kStampSlots = 64;
 namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip); both row states are built on rowmath.h
 namespace v21 { struct SampleRow; struct TemperRow; }  // sample_kernels.h (api_sample.hip)
 namespace v21 { struct EnsRow; }  // ensemble_kernels.h (api_ensemble.hip)
+namespace v21 { struct NestRow; }  // nested_kernels.h (api_nested.hip)
 using namespace v21;
 
 // ---- errors: v21_last_error() returns the calling thread's last message (api_base.hip)
@@ -225,6 +226,7 @@ struct v21_mlp {
   Dev<TemperRow> tmp;    // a tempered sample call's sums of ln L and swap counts per row
   Dev<EnsRow> ens;       // walker state of an ensemble call (ensemble_kernels.h) ...
   Dev<float> ens_prop, ens_lnl;  // ... and the compacted proposals of one half-move (n / 2 rows) with their ln L
+  Dev<NestRow> nst;      // live points of a nested call (nested_kernels.h; its proposals share ens_prop / ens_lnl)
   bool has_lk = false;
   // linear nuisance modes marginalised in those reductions (api_nuisance.hip): nu_k modes (0: none), the float64 basis
   // as it was handed in, the record built from it, and the host copy of the likelihood record both are re-whitened from.
@@ -305,7 +307,7 @@ int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float*
 // then sync.  chunk_rows: the rows of a chunk (a tempered sample call's is a whole number of ladders)
 int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, long long out_floats,
                const std::function<int(long long, long long, float*)>& run, long long chunk_rows = kJacHostChunk);
-// api_loglike.hip, shared with api_ensemble.hip: lnl of the n device rows d_x (pitch ldx; raw, or transformed already with
+// api_loglike.hip, shared with api_ensemble.hip and api_nested.hip: lnl of the n device rows d_x (pitch ldx; raw, or transformed already with
 // V21_FWD_IN_TRANSFORM cleared) that start at row0 of a call of n_call rows, on `route` (routes.h: LnlRoute), on the
 // context's stream
 int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n, long long n_call, const CallData& cd, long long row0,

@@ -192,6 +192,46 @@ def log_evidence(betas, mean_lnl):
     return np.sum((b[:-1] - b[1:]) * (E[..., :-1] + E[..., 1:]) / 2.0, axis=-1)
 
 
+# nested_sample's result, per spectrum.  params / lnl / log_weights: (n_runs, P, ..) with P = n_iter n_live / 2 dead points
+# (iteration-major, ascending ln L within an iteration) followed by the n_live live points; the weights are normalised
+# over the POOLED runs.  log_evidence_err: the formula's for one run, the runs' scatter / sqrt(n_runs) for several.
+# stopped: "dlogz" or "max_iter".  mean_u, cov_u: the weighted moments in par_transform's coordinates u
+NestedSamples = namedtuple("NestedSamples", ["params", "lnl", "log_weights", "log_evidence", "log_evidence_err", "information", "n_iter",
+                                             "n_evals", "accept_rate", "mean_u", "cov_u", "stopped"])
+
+
+def nested_evidence(dead_lnl, live_lnl, n_live):
+    """The evidence from a nested run's record, in float64.  dead_lnl (..., T, k): ln L of the k = n_live / 2 points each of
+    T iterations deleted, ascending within an iteration; live_lnl (..., n_live): the live points left; leading axes are
+    independent runs.  Deleting the k lowest of N = n_live points one after the other shrinks the prior volume X by
+    E[-ln t] = 1 / (N - i) at the i-th, so with s_k = sum_{i<k} 1 / (N - i) the volume after the death of rank r of
+    iteration t is ln X_{t,r} = -t s_k - sum_{i<=r} 1 / (N - i); that dead point weighs L_{t,r} (X_prev - X_{t,r}) (X = 1
+    before the first death) and the live points X_T mean(L_live).
+    -> (log_evidence (...), log_evidence_err, information, log_weights (..., T k + n_live)): ln Z; its error
+    sqrt(H v_k / s_k), v_k = sum_{i<k} 1 / (N - i)^2 -- ln X spreads by v_k per iteration of s_k nats, 1.44 / N per nat at
+    k = N / 2 against 1 / N for one death at a time --; H = sum w ln L - ln Z, the information; and the normalised log
+    weights, dead points iteration-major first, then the live points."""
+    dl, ll = np.asarray(dead_lnl, np.float64), np.asarray(live_lnl, np.float64)
+    N = int(n_live)
+    T, k = dl.shape[-2:]
+    if ll.shape[-1] != N or 2 * k != N or dl.shape[:-2] != ll.shape[:-1]:
+        raise ValueError("nested_evidence: dead_lnl (..., T, %d) and live_lnl (..., %d) expected, got %r and %r" % (N // 2, N, dl.shape, ll.shape))
+    step = 1.0 / (N - np.arange(k))
+    cum = np.cumsum(step)
+    s_k, v_k = cum[-1], np.sum(step ** 2)
+    before = -np.arange(T)[:, None] * s_k - np.concatenate([[0.0], cum[:-1]])  # ln X_prev (T, k)
+    lw_dead = dl + before + np.log(-np.expm1(-step))
+    lw = np.concatenate([lw_dead.reshape(dl.shape[:-2] + (T * k,)), ll - T * s_k - np.log(N)], axis=-1)
+    both = np.concatenate([dl.reshape(dl.shape[:-2] + (T * k,)), ll], axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = np.max(lw, axis=-1, keepdims=True)
+        lz = m + np.log(np.sum(np.exp(lw - m), axis=-1, keepdims=True))
+        lw = lw - lz
+        w = np.exp(lw)
+        H = np.sum(np.where(w > 0, w * np.where(w > 0, both, 0.0), 0.0), axis=-1) - lz[..., 0]
+    return lz[..., 0], np.sqrt(np.maximum(H, 0.0) * v_k / s_k), H, lw
+
+
 def pooled_moments(mean_c, cov_c):
     """Mean and covariance of the pooled samples of equally long chains from their per-chain means (..., C, d) and
     covariances (..., C, d, d) (both divided by the chain length): the mean of the means, and the mean within-chain
@@ -667,6 +707,82 @@ class _EmulatorBase:
         if one:
             E, swap, lz, lz_err = E[0], swap[0], lz[0], lz_err[0]
         return TemperedSamples(*ps, b, E, swap, lz, lz_err)
+
+    def nested_sample(self, data, sigma, n_live=256, n_runs=1, n_repeats=None, dlogz=0.01, max_iter=2000, flow=None, fhigh=None,
+                      foreground=None, seed=0, return_lnl=True):
+        """Nested sampling of the posterior given observed signal(s) (not in the reference): the Bayesian evidence with its
+        error and weighted posterior samples in one run, without a gradient, entirely on the device (include/v21.h:
+        v21_mlp_sample_nested) on the forward-only ln L of ``log_likelihood`` under ``sample_posterior``'s prior -- uniform
+        on the training box in par_transform's coordinates.  ``n_runs`` independent runs per spectrum of ``n_live`` live
+        points each (even, 56 .. 512 for the 7 parameters), drawn uniform in the box from ``seed``.  An iteration deletes
+        the lower half of the live points and replaces each by a copy of a survivor moved ``n_repeats`` times (default
+        3 x 7) by the difference of two other survivors, inside the deleted points' highest ln L.  The library is called in
+        blocks of 16 iterations until, in every run, what the live points could still add falls below ``dlogz`` --
+        logaddexp(ln Z, ln X_T + max live ln L) - ln Z < dlogz -- or ``max_iter`` iterations are done; ``stopped`` says
+        which ("dlogz" or "max_iter").  CHECK ``accept_rate``: the default ``n_repeats`` is measured on Gaussian-like
+        posteriors, where a quarter of the moves is accepted; on the shipped model a tenth is, and ln Z at the default
+        reads 0.4 (sigma = 1 mK) to 1.3 nats (0.05 mK) above the value it converges to at 3 to 9 times the moves (DESIGN §3
+        K14).  Where the acceptance is near 0.1, run again with ``n_repeats`` tripled and compare.
+        Returns ``NestedSamples``: params (M, n_runs, P, 7) raw -- the P = n_iter n_live / 2 dead points then the n_live
+        live points of every run --, lnl and log_weights (M, n_runs, P) (lnl None unless ``return_lnl``; the weights
+        normalised over the pooled runs, each run's by its own Z), log_evidence, log_evidence_err, information (M,), n_iter,
+        n_evals (ln L evaluations per spectrum), accept_rate (M, n_runs), the weighted mean_u (M, 7) / cov_u (M, 7, 7) and
+        stopped; the M axis is dropped for one spectrum.  With one run log_evidence_err is ``nested_evidence``'s
+        sqrt(H v_k / s_k); with several, log_evidence is the mean of the runs' ln Z and log_evidence_err their scatter
+        (std with ddof 1) / sqrt(n_runs), as ``sample_tempered`` reports its ladders.
+        THE EVIDENCE.  log_evidence estimates ln Z, Z = integral of L(u) du / 2^d over the training box (d = 7: the mean of
+        L under the prior), L with the constants ``log_likelihood`` drops (ln L = -chi^2 / 2, without the Gaussian's
+        normalisation) -- the definition of ``sample_tempered``, so the two are directly comparable; this one has no
+        discretisation bias in beta.  ln Z is comparable between emulators, bands and noise levels at the same data and
+        the same foreground basis (add the dropped -sum ln(sigma sqrt(2 pi)) over the band's bins where sigma or the band
+        differ).  It is NOT comparable across different numbers of marginalised foreground modes: their flat prior is
+        improper."""
+        model, st, flags, dat, one = self._spectra(data)
+        din = st.dims[0]
+        M, R, N = dat.shape[0], int(n_runs), int(n_live)
+        if R < 1:
+            raise ValueError("n_runs must be >= 1")
+        if N < 8 * din:
+            raise ValueError("n_live = %d: an evidence needs at least %d live points for %d parameters" % (N, 8 * din, din))
+        if int(max_iter) < 1 or not float(dlogz) > 0.0:
+            raise ValueError("max_iter must be >= 1 and dlogz positive")
+        n, k, block = M * R * N, N // 2, 16
+        opts = dict(n_repeats=n_repeats, seed=seed)
+        nat.Stack.nested_opts(N, n_iter=int(max_iter), in_dim=din, **opts)  # (argument errors before any device work)
+        rep = int(n_repeats) if n_repeats else 3 * din
+        self._use_record(st, dat[0], self._band_weights(st.dims[-1], sigma, flow, fhigh), foreground, flow, fhigh)
+        s_k = np.sum(1.0 / (N - np.arange(k)))
+        u, T, dead_u, dead_l, acc, stopped = None, 0, [], [], 0.0, "max_iter"
+        while T < int(max_iter):
+            it = min(block, int(max_iter) - T)
+            r = st.sample_nested(u, n, N, model.precision, flags, data=dat, n_iter=it, iter0=T, **opts)
+            u, T = r["live_u"], T + it
+            dead_u.append(r["dead_u"])
+            dead_l.append(r["dead_lnl"])
+            acc = acc + it * r["accept_rate"].mean(axis=1)
+            dl = np.concatenate(dead_l).reshape(T, M, R, k).transpose(1, 2, 0, 3)
+            ll = r["live_lnl"].astype(np.float64).reshape(M, R, N)
+            lz, err, H, lw = nested_evidence(dl, ll, N)
+            if np.all(np.logaddexp(lz, -T * s_k + ll.max(axis=-1)) - lz < float(dlogz)):
+                stopped = "dlogz"
+                break
+        du = np.concatenate(dead_u).reshape(T, M, R, k, din).transpose(1, 2, 0, 3, 4).reshape(M, R, T * k, din)
+        pts = np.concatenate([du, u.reshape(M, R, N, din)], axis=2)
+        lnl = np.concatenate([dl.reshape(M, R, T * k), ll], axis=2)
+        m = lz.max(axis=1, keepdims=True)
+        lw = lw + (lz - (m + np.log(np.sum(np.exp(lz - m), axis=1, keepdims=True))))[:, :, None]
+        w = np.exp(lw).reshape(M, -1)
+        flat = pts.reshape(M, -1, din)
+        mean = np.einsum("mp,mpi->mi", w, flat)
+        cen = flat - mean[:, None, :]
+        cov = np.einsum("mp,mpi,mpj->mij", w, cen, cen)
+        params = pp.par_untransform(pts.reshape(-1, din), self.par_train).reshape(pts.shape)
+        lz_err = lz.std(axis=1, ddof=1) / np.sqrt(R) if R > 1 else err[:, 0]
+        out = [params, lnl if return_lnl else None, lw, lz.mean(axis=1), lz_err, H.mean(axis=1), T, R * (N + k * T * rep),
+               (acc / T).reshape(M, R), mean, cov, stopped]
+        if one:
+            out = [a[0] if isinstance(a, np.ndarray) else a for a in out]
+        return NestedSamples(*out)
 
     def save(self):
         raise NotImplementedError("Not implemented yet.")

@@ -382,6 +382,49 @@ int v21_mlp_sample_ensemble_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, in
 int v21_route_ensemble(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
                        int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows);
 
+/* ---- nested sampling on forward-only ln L: the evidence and weighted posterior samples, no gradient.
+ *   Target.  ln L is v21_mlp_loglike_fwd's (nuisance records and the w == 0 rule included) under the uniform prior on
+ *   the box u in [-1, 1]^d, u = par_transform's coordinates.  EVERYTHING here is in u: the start rows, the dead and the
+ *   live points; the caller maps to raw units (the evaluations run on u, without the input transform: the flag
+ *   V21_FWD_IN_TRANSFORM is ignored and no input transform is needed).  Needs a likelihood record; d = in_dim <= 8.
+ *   Rows and runs.  A call has n rows; N = n_live consecutive rows form one run, the live points of one spectrum: N even,
+ *   16 <= N <= 512 (what one workgroup ranks), n % N == 0 and, with a data matrix, (n / n_data) % N == 0.  k = N / 2.  Runs
+ *   are independent.  The library moves any such run; an EVIDENCE needs N >= 8 d (tests/nested_ref.py has the table:
+ *   16 live points in 7 dimensions scatter by 3 nats from run to run), which the emulator classes enforce.
+ *   Start.  x0 (n, d) in u, clamped into the box (NaN -> -1), or NULL: coordinate i of row r is float32(2 U(w) - 1) of
+ *   word i % 4 of Philox block 2 + i / 4 of (seed, chain0 + r, step 0) -- function, key, counter and U as documented for
+ *   v21_mlp_sample.  A NaN ln L is stored as -inf, here and only here (a proposal's NaN rejects).
+ *   Iteration t = iter0 + its index in the call:
+ *     rank    the N live ln L ascending, ties on the row index; the k lowest are the DEAD points at ranks r = 0 .. k - 1,
+ *             L* is the ln L at rank k - 1; the survivor of rank r >= k moves to row r of its run;
+ *     record  dead_u[t, run, r], dead_lnl[t, run, r], lstar[t, run];
+ *     restart row j < k becomes a copy (u and ln L) of survivor floor(k w0 / 2^32), w0 of block 1 of (seed, chain0 +
+ *             row, step t);
+ *     move    n_repeats times, s = 0 ..: row j < k at x proposes y = x + gamma (x_a - x_b) in float32 (difference,
+ *             product, sum, each rounded), a = floor(k w0 / 2^32), b = (a + 1 + floor((k - 1) w1 / 2^32)) mod k survivor
+ *             indices (rows k + a, k + b) from block 0 of (seed, chain0 + row, step t n_repeats + s); accepted iff every
+ *             coordinate of y lies in [-1, 1] and ln L(y) > L*, strictly, on the float32 values.  Survivors do not move.
+ *   After the last move the N rows are the next live set: live_u / live_lnl, and x0 = live_u, iter0 + n_iter continue the
+ *   run exactly (the start's ln L is evaluated again, on the same route: the same bits).
+ *   Evidence.  Assembled by the caller from dead_lnl and live_lnl: after the death of rank r of iteration t the prior
+ *   volume is ln X = -t s_k - sum_{i <= r} 1 / (N - i), s_k = sum_{i < k} 1 / (N - i).
+ *   Evaluation.  Every ln L of a call -- the starts' too, in two halves (rows e N + h k + j, h = 0, 1) -- is that of n / 2
+ *   rows in a compacted layout (row e k + j: moving slot j of run e) on ONE route decided once per call
+ *   (v21_route_nested: v21_route_ensemble's decision and chunk rule with N in the place of W).  v21_mlp_last_lnl_route
+ *   counts a call once.  A call makes 2 + n_iter n_repeats evaluations of n / 2 rows.
+ *   Invariance.  A draw depends only on (seed, global row, global step): results do not depend on how the iterations are
+ *   split over calls (iter0), nor on host chunks or on how the runs are split over calls or devices (chain0).
+ *   V21_ERR_ARG, the handle left usable: N odd or out of range, n % N != 0, a spectrum's rows not being whole runs, a
+ *   negative count, gamma negative, above 1e6 or not finite, (iter0 + n_iter) n_repeats >= 2^32.  n = 0 is a no-op.
+ * The host form works in chunks of whole runs as v21_mlp_sample_ensemble's does and returns when the results are in
+ * place; the _dev form never synchronises.  Results: v21_nested_out (v21_types.h). */
+int v21_mlp_sample_nested(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
+                          const v21_nested_opts* opts, const v21_nested_out* out, int precision, int flags);
+int v21_mlp_sample_nested_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                              const v21_nested_opts* opts, const v21_nested_out* out, int precision, int flags);
+int v21_route_nested(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_live,
+                     int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows);
+
 /* ---- linear nuisance modes (foregrounds) integrated out of the likelihood record.  Data model: d = y(x) + A^T a + noise,
  * A the (n_modes, out_dim) basis, 1 <= n_modes <= 8, with a FLAT PRIOR on the amplitudes a, which are integrated out
  * analytically.  With W = diag(w) the record's inverse variances, Q the W-orthonormalised basis (span Q = span A on the

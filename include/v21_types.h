@@ -82,4 +82,27 @@ typedef struct {
   double* last_log_alpha; /* (n): its log acceptance ratio (-inf: outside the box; no sweep: 0) */
   int* last_partner;      /* (n): its partner, as the row index within the ensemble (no sweep: -1) */
 } v21_ensemble_out;
+/* options of v21_mlp_sample_nested[_dev] (a NULL pointer: the defaults in brackets) */
+typedef struct {
+  int n_live;           /* [256] N: consecutive rows form one run, its live points; even, 16 <= N <= 512 */
+  int n_repeats;        /* [0] difference moves per iteration, >= 0; 0: 3 in_dim */
+  int n_iter;           /* [100] iterations of this call, >= 0; each records N / 2 dead points per run */
+  double gamma;         /* [0] scale of the difference move, finite, 0 <= gamma <= 1e6; 0: 2.38 / sqrt(2 in_dim) */
+  unsigned long long seed;  /* [0] the Philox key */
+  long long iter0;      /* [0] global index of the call's first iteration, >= 0; (iter0 + n_iter) n_repeats < 2^32 */
+  long long chain0;     /* [0] global index of the call's first row, >= 0 */
+} v21_nested_opts;
+/* results of v21_mlp_sample_nested[_dev]: host pointers for the host form, device pointers for _dev; every one but live_u
+ * may be NULL.  n rows in R = n / N runs, k = N / 2, T = n_iter; everything in u = par_transform's coordinates; "x type"
+ * is x_dtype (_dev: float32). */
+typedef struct {
+  void* dead_u;           /* (T, R, k, in_dim) x type: the dead points of iteration t in ascending order of ln L */
+  float* dead_lnl;        /* (T, R, k): ln L at them */
+  float* lstar;           /* (T, R): the threshold of iteration t, dead_lnl[t, r, k - 1] */
+  void* live_u;           /* (n, in_dim) x type: the live points after the last move -- the state a next call starts from */
+  float* live_lnl;        /* (n): ln L at them (a NaN evaluation: -inf) */
+  double* accept_rate;    /* (R, k): accepted / decided proposals of moving slot j of each run in this call (no move: 0) */
+  int* last_partner;      /* (R, k, 2): the survivor indices a, b of its last proposal (no move: -1) */
+  float* last_prop_u;     /* (R, k, in_dim): its last proposal (no move: the second half of the start rows) */
+} v21_nested_out;
 #endif /* V21_TYPES_H */
