@@ -11,7 +11,7 @@ from . import preprocess  # noqa: F401  (numpy only; needs no GPU)
 
 
 def __getattr__(name):  # emulator/engine import the C-ABI binding lazily
-    if name in ("emulator", "engine", "callbacks", "optimizers", "losses", "h5lite", "synth", "_native", "foregrounds"):
+    if name in ("emulator", "engine", "callbacks", "optimizers", "losses", "h5lite", "synth", "_native", "foregrounds", "priors"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

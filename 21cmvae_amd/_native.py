@@ -218,6 +218,7 @@ SIGNATURES = {
                                    C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "v21_nuisance_whiten": (C.c_int, [C.POINTER(C.c_double), _F, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "v21_mlp_set_nuisance": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, C.c_int32]),
+    "v21_mlp_set_prior": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
     "v21_mlp_nuisance_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "v21_mlp_nuisance_coef": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int]),
     "v21_trainer_last_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -708,7 +709,7 @@ class Stack(_Owned):
         check(self.lib.v21_mlp_num_params(h, C.byref(n)))
         self.num_params = n.value
         # what the device holds, as use_output_stats / use_input_stats / use_likelihood left it (None: nothing, or set directly)
-        self.out_stats = self.in_stats = self.lk_record = self.nu_record = None
+        self.out_stats = self.in_stats = self.lk_record = self.nu_record = self.prior_record = None
 
     def set_weights(self, flat):
         flat = np.ascontiguousarray(flat, dtype=np.float32).ravel()
@@ -776,6 +777,20 @@ class Stack(_Owned):
         if rec is None or not np.array_equal(rec, basis):
             self.set_nuisance(basis)
             self.nu_record = basis.copy()
+
+    def use_prior(self, prior):
+        """set_prior(kind, mu, sd) from a (kind, mu, sd) triple (None: no prior), set only when it changed; kept on the
+        host by value as `prior_record`"""
+        rec = self.prior_record
+        if prior is None:
+            if rec is not None:
+                self.set_prior(None)
+                self.prior_record = None
+            return
+        new = (np.array(prior[0], np.int32), np.array(prior[1], np.float64), np.array(prior[2], np.float64))
+        if rec is None or not all(np.array_equal(a, b) for a, b in zip(rec, new)):
+            self.set_prior(*new)
+            self.prior_record = new
 
     def has_fused(self, precision="f32"):
         y = C.c_int(0)
@@ -852,6 +867,22 @@ class Stack(_Owned):
         if A.ndim != 2 or A.shape[1] != self.dims[-1]:
             raise ValueError("nuisance: basis must be (K, %d), got %r" % (self.dims[-1], np.shape(basis)))
         check(self.lib.v21_mlp_set_nuisance(self.h, A.ctypes.data_as(C.POINTER(C.c_double)), A.shape[0], A.shape[1]))
+
+    def set_prior(self, kind, mu=None, sd=None):
+        """The samplers' prior in the transformed coordinates u (include/v21.h: v21_mlp_set_prior): per input column
+        kind 0 (uniform on [-1, 1]) or 1 (normal(mu, sd) truncated to it); copied.  None clears: uniform everywhere."""
+        self.prior_record = None
+        if kind is None:
+            check(self.lib.v21_mlp_set_prior(self.h, None, None, None, 0))
+            return
+        kind = np.ascontiguousarray(kind, dtype=np.int32).ravel()
+        mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64).ravel()
+        sd = None if sd is None else np.ascontiguousarray(sd, dtype=np.float64).ravel()
+        for a in (mu, sd):
+            if a is not None and a.size != kind.size:
+                raise ValueError("set_prior: kind, mu and sd must have one entry per input column")
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        check(self.lib.v21_mlp_set_prior(self.h, kind.ctypes.data_as(C.POINTER(C.c_int32)), dp(mu), dp(sd), kind.size))
 
     def nuisance_modes(self):
         """the number of nuisance modes the library holds for this stack (0: none)"""

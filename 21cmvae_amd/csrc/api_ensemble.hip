@@ -84,16 +84,18 @@ static int ensemble_run(v21_mlp* m, int route, long long n, long long n_call, co
   a.t = m->tin;
   const long long ensembles = n / a.W;
   const dim3 grid((unsigned)((ensembles + a.epw - 1) / a.epw));
-  // (samples and x_last are of x_dtype: one pair of instantiations, picked once)
-  const bool f64 = x_dtype == V21_DTYPE_F64;
-  const auto step = f64 ? ensemble_step_kernel<double> : ensemble_step_kernel<float>;
+  // (samples and x_last are of x_dtype, the prior record (api_prior.hip) is there or not: one set of instantiations,
+  // picked once)
+  const bool f64 = x_dtype == V21_DTYPE_F64, pri = m->has_prior;
+  const auto step = pri ? (f64 ? ensemble_step_kernel<double, true> : ensemble_step_kernel<float, true>)
+                        : (f64 ? ensemble_step_kernel<double, false> : ensemble_step_kernel<float, false>);
   const auto finish = f64 ? ensemble_finish_kernel<double> : ensemble_finish_kernel<float>;
   // the proposals' data: rows-per-data and the call's first row in the compacted layout
   const CallData hd{data.d, data.ld, data.ld ? data.rpd / 2 : 1};
   const long long last = 2 * a.total + 2;
   for (long long k = 0; k <= last; ++k) {
     if (k > 0) CHK(lnl_run(m, route, prop, din, half, n_call / 2, hd, row0 / 2, lnl, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), prop, (const float*)lnl, k, a);
+    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), prop, (const float*)lnl, k, a, m->prior);
     HIPCHK(hipGetLastError());
   }
   EnsOutDev od{out.x_last, out.lnl_last, out.accept_rate, out.mean_u, out.cov_u, out.last_log_alpha, out.last_partner};

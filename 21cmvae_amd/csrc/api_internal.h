@@ -41,6 +41,7 @@ constexpr int kStampSlots = 64;
 #endif
 #include "dw_adam.h"
 #include "routes.h"
+#include "rowmath.h"
 
 namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip); both row states are built on rowmath.h
 namespace v21 { struct SampleRow; struct TemperRow; }  // sample_kernels.h (api_sample.hip)
@@ -228,6 +229,10 @@ struct v21_mlp {
   Dev<float> ens_prop, ens_lnl;  // ... and the compacted proposals of one half-move (n / 2 rows) with their ln L
   Dev<NestRow> nst;      // live points of a nested call (nested_kernels.h; its proposals share ens_prop / ens_lnl)
   bool has_lk = false;
+  // the samplers' prior record (api_prior.hip: v21_mlp_set_prior), as their step kernels take it by value; without one
+  // (has_prior false: never set, cleared, or every column uniform) they run their PRIOR = false instantiations
+  bool has_prior = false;
+  PriorArgs prior{};
   // linear nuisance modes marginalised in those reductions (api_nuisance.hip): nu_k modes (0: none), the float64 basis
   // as it was handed in, the record built from it, and the host copy of the likelihood record both are re-whitened from.
   // On the device: Q in float32 (the reductions) and float64 (nuis_project_kernel), the record's projected data BESIDE

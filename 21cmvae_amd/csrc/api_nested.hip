@@ -86,9 +86,11 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
   a.seed = o.seed; a.chain0 = (uint64_t)chain0; a.iter0 = o.iter0;
   a.dead_u = out.dead_u; a.dead_lnl = out.dead_lnl; a.lstar = out.lstar;
   const dim3 grid((unsigned)((a.runs + a.rpw - 1) / a.rpw));
-  // (dead_u and live_u are of x_dtype: one pair of instantiations, picked once)
-  const bool f64 = x_dtype == V21_DTYPE_F64;
-  const auto step = f64 ? nested_step_kernel<double> : nested_step_kernel<float>;
+  // (dead_u and live_u are of x_dtype, the prior record (api_prior.hip) is there or not: one set of instantiations,
+  // picked once)
+  const bool f64 = x_dtype == V21_DTYPE_F64, pri = m->has_prior;
+  const auto step = pri ? (f64 ? nested_step_kernel<double, true> : nested_step_kernel<float, true>)
+                        : (f64 ? nested_step_kernel<double, false> : nested_step_kernel<float, false>);
   const auto finish = f64 ? nested_finish_kernel<double> : nested_finish_kernel<float>;
   // the proposals' data: rows-per-data and the call's first row in the compacted layout
   const CallData hd{data.d, data.ld, data.ld ? data.rpd / 2 : 1};
@@ -97,6 +99,7 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
   // decides move mv, opens the next iteration after an iteration's last move, and draws move mv + 1
   for (long long q = 0; q < 3 + moves; ++q) {
     NestLaunch l{-1, 0, -1, 0, -1, -1};
+    const long long dec = q >= 3 ? q - 3 : 0;  // the move a deciding launch decides (the prior's acceptance draw)
     if (q == 0) l.start = 0;
     else if (q == 1) { l.take = 0; l.start = 1; }
     else if (q == 2) { l.take = 1; if (T > 0) { l.bt = 0; l.dm = 0; } }
@@ -109,7 +112,7 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
       }
     }
     if (q > 0) CHK(lnl_run(m, route, prop, din, half, n_call / 2, hd, row0 / 2, lnl, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, d_start, prop, (const float*)lnl, l, a);
+    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, d_start, prop, (const float*)lnl, l, a, m->prior, dec);
     HIPCHK(hipGetLastError());
   }
   NestOutDev od{out.live_u, out.live_lnl, out.accept_rate, out.last_partner, out.last_prop_u};

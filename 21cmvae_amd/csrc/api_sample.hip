@@ -4,7 +4,8 @@
 // pending proposals (reduce_run of api_jacobian.hip, on u without the input transform) and one sample_step_kernel launch,
 // and the host only launches.  The tempered entries (v21_mlp_sample_tempered[_dev]) run the same loop with
 // sample_step_tempered_kernel in the step kernel's place: T consecutive rows form a ladder of inverse temperatures whose
-// rungs exchange their points inside that kernel.
+// rungs exchange their points inside that kernel.  A handle with a prior record (api_prior.hip) launches the PRIOR
+// instantiations of both step kernels.
 #include "api_internal.h"
 #include "sample_kernels.h"
 
@@ -48,10 +49,12 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   a.t = m->tin;
   hipLaunchKernelGGL(sample_init_kernel, grid, dim3(256), 0, st, cs, m->jxt.get(), m->jfac.get(), n, din, o.eps0, d_eps_start);
   HIPCHK(hipGetLastError());
-  // (samples and x_last are of x_dtype: one pair of instantiations, picked once)
-  const bool f64 = x_dtype == V21_DTYPE_F64;
-  const auto step = f64 ? sample_step_kernel<double> : sample_step_kernel<float>;
-  const auto tstep = f64 ? sample_step_tempered_kernel<double> : sample_step_tempered_kernel<float>;
+  // (samples and x_last are of x_dtype, the prior record is there or not: one set of instantiations, picked once)
+  const bool f64 = x_dtype == V21_DTYPE_F64, pri = m->has_prior;
+  const auto step = pri ? (f64 ? sample_step_kernel<double, true> : sample_step_kernel<float, true>)
+                        : (f64 ? sample_step_kernel<double, false> : sample_step_kernel<float, false>);
+  const auto tstep = pri ? (f64 ? sample_step_tempered_kernel<double, true> : sample_step_tempered_kernel<float, true>)
+                         : (f64 ? sample_step_tempered_kernel<double, false> : sample_step_tempered_kernel<float, false>);
   const auto finish = f64 ? sample_finish_kernel<double> : sample_finish_kernel<float>;
   TemperArgs ta{};
   TemperRow* tr = nullptr;
@@ -68,9 +71,10 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   for (long long it = 0; it <= a.total; ++it) {
     CHK(reduce_run(m, route, n, F, l, g, nullptr, data.d, data.ld, data.rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
     if (tp)
-      hipLaunchKernelGGL(tstep, tgrid, dim3(256), 0, st, cs, tr, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, ta);
+      hipLaunchKernelGGL(tstep, tgrid, dim3(256), 0, st, cs, tr, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, ta,
+                         m->prior);
     else
-      hipLaunchKernelGGL(step, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a);
+      hipLaunchKernelGGL(step, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, m->prior);
     HIPCHK(hipGetLastError());
   }
   SampleOutDev od{out.x_last, out.lnl_last, out.eps_last, out.accept_rate, out.mean_u, out.cov_u, out.last_prop_u, out.last_log_alpha};

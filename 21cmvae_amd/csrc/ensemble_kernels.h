@@ -1,8 +1,9 @@
 // ensemble_kernels.h -- the affine-invariant ensemble sampler on the device (api_ensemble.hip; include/v21.h:
 // v21_mlp_sample_ensemble): Goodman & Weare's stretch move on forward-only ln L, in the transformed coordinates
-// u in [-1, 1]^din of the fit under a uniform prior on that box.  W consecutive rows form one ensemble of two sets of
-// H = W / 2 walkers; a sweep is two half-moves, and half-move h moves every walker of set h along the line to a
-// partner drawn from the current positions of set 1 - h.
+// u in [-1, 1]^din of the fit under the handle's prior on that box (rowmath.h: PriorArgs; uniform without a record;
+// with one, PRIOR, the acceptance gains ln p(y) - ln p(x) and nothing else changes).  W consecutive rows form one
+// ensemble of two sets of H = W / 2 walkers; a sweep is two half-moves, and half-move h moves every walker of set h
+// along the line to a partner drawn from the current positions of set 1 - h.
 //   ensemble_step_kernel    one launch per half-move, after the evaluation of the pending proposals: it DECIDES them
 //                           (accepts or rejects, keeps the sweep: Moments of rowmath.h), meets a barrier, then DRAWS the
 //                           other set's proposals from the positions just decided;
@@ -17,7 +18,10 @@
 // is read from global memory after the barrier, as the tempered sampler's swap does (sample_kernels.h): writer and reader
 // share a CU and its L1, the barrier's workgroup-scope release / acquire orders them.  No thread returns before the
 // barrier; threads past the workgroup's ensembles or past n skip the work on both sides of it.
-// No LDS, no atomics; float64 in registers.  Random numbers: Philox4x32-10 of sample_kernels.h, block 0.
+// Acceptance of walker x's proposal y = x_k + z (x - x_k), iff log(uniform) < log alpha:
+//   log alpha = (din - 1) ln z + ln L(y) - ln L(x)   [PRIOR: + ln p(y) - ln p(x)]
+// No LDS, no atomics; float64 in registers.  Random numbers: Philox4x32-10 of sample_kernels.h, block 0 at step = the
+// sweep: w0 the stretch, w1 the partner, w2 the acceptance uniform.  The prior draws nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,10 +61,12 @@ struct EnsArgs {
 };
 
 // one thread per (ensemble, j): launch k of the call (above).  start: the transformed start rows (n, din), read by
-// k = 0, 1; prop: the compacted proposals (n / 2, din); lnl_new: their evaluation (n / 2).  XT: the samples' type.
-template <class XT>
+// k = 0, 1; prop: the compacted proposals (n / 2, din); lnl_new: their evaluation (n / 2).  XT: the samples' type;
+// PRIOR: the handle holds a prior record, pr (else not read).
+template <class XT, bool PRIOR>
 __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const float* __restrict__ start, float* __restrict__ prop,
-                                                            const float* __restrict__ lnl_new, long long k, const EnsArgs a) {
+                                                            const float* __restrict__ lnl_new, long long k, const EnsArgs a,
+                                                            const PriorArgs pr) {
   constexpr int NI = kFitMaxIn;
   const int din = a.din, H = a.H, W = a.W;
   const int slot = (int)threadIdx.x / H, j = (int)threadIdx.x % H;
@@ -83,6 +89,7 @@ __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const fl
       accept = false;
       if (!s.reject) {
         log_alpha = s.lz + ((double)lnl_y - (double)s.lnl);
+        if constexpr (PRIOR) log_alpha += prior_logp(pr, y, din) - prior_logp(pr, s.u, din);
         if (log_alpha != log_alpha) log_alpha = -INFINITY;
         uint32_t w[4];
         sample_block(a.seed, a.chain0 + (uint64_t)row, (uint32_t)(a.step0 + (uint64_t)sweep), 0u, w);

@@ -1,10 +1,14 @@
 // nested_kernels.h -- the nested sampler on the device (api_nested.hip; include/v21.h: v21_mlp_sample_nested): evidence
 // and weighted posterior samples from forward-only ln L, in the transformed coordinates u in [-1, 1]^din under the
-// uniform prior on that box.  N consecutive rows are one RUN, the live points of one spectrum; k = N / 2.  Iteration t
+// handle's prior on that box (rowmath.h: PriorArgs; uniform without a record).  N consecutive rows are one RUN, the live points of one spectrum; k = N / 2.  Iteration t
 // ranks the run's ln L (ascending, ties on the row index), records the k lowest as DEAD, keeps the k highest -- the
 // survivors, which then lie in rows k .. N - 1 in rank order --, restarts every dead row as a copy of a drawn survivor
 // and moves those k rows n_repeats times by the difference move y = x + gamma (x_a - x_b), a and b distinct survivors,
 // accepted iff y is inside the box and ln L(y) > L*, the ln L of rank k - 1.  Survivors do not move within an iteration.
+// With a prior record (PRIOR) the move is a Metropolis move on the prior restricted to L > L*: it is accepted iff, beside
+// the two conditions above, log(U) < ln p(y) - ln p(x); drawn starts are draws of the prior (below), and GIVEN starts are
+// clamped into the box as they are -- that they are draws of the prior is the caller's business.  The shrinkage
+// bookkeeping is the uniform prior's: the prior mass above L* shrinks as the volume did.
 //   nested_step_kernel    one launch per evaluation of the n / 2 compacted proposals (row e k + j: moving slot j of run
 //                         e): it DECIDES them, on an iteration boundary RANKS / RECORDS / RESTARTS, meets a barrier, then
 //                         DRAWS the next proposals from the positions just settled;
@@ -21,7 +25,10 @@
 // Random numbers: Philox4x32-10 of sample_kernels.h keyed by the seed, counter (global row of the slot, step, block):
 //   block 0, step = global move t n_repeats + s:  a = floor(k w0 / 2^32), b = (a + 1 + floor((k - 1) w1 / 2^32)) mod k;
 //   block 1, step = global iteration t:           the restart source floor(k w0 / 2^32);
-//   blocks 2 and 3, step 0:                       a drawn start, coordinate i from word i: float(2 U(w) - 1).
+//   blocks 2 and 3, step 0:                       a drawn start, coordinate i from word i: float(2 U(w) - 1); a normal
+//                                                 column of a prior record: float(mu + sd z), z the truncated standard
+//                                                 normal's inverse CDF at U(w) (nest_tnorm_z);
+//   block 4, step = that of block 0 (PRIOR only): the prior's acceptance uniform U(w0).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,11 +74,22 @@ struct NestLaunch {
 
 __device__ inline float nest_key(float l) { return l != l ? -INFINITY : l; }
 
+// z with Phi(z) = Phi(a) + U (Phi(b) - Phi(a)), a < b the standardised box ends, float64; where the box's middle lies
+// above the mode (a + b > 0) the mirrored problem is solved, so that Phi is always taken in the tail nearer the mode
+__device__ inline double nest_tnorm_z(double a, double b, double U) {
+  const bool mirror = a + b > 0.0;
+  const double pa = normcdf(mirror ? -a : a), pb = normcdf(mirror ? -b : b);
+  const double z = normcdfinv(mirror ? pa - U * (pa - pb) : pa + U * (pb - pa));
+  return mirror ? -z : z;
+}
+
 // one thread per (run, j).  start: the start rows (n, din) in u, or nullptr (drawn); prop: the compacted proposals
-// (n / 2, din); lnl_new: their evaluation.  XT: the dead record's type.
-template <class XT>
+// (n / 2, din); lnl_new: their evaluation.  XT: the dead record's type; PRIOR: the handle holds a prior record, pr, and
+// `dec` is the local move a deciding launch decides (neither is read without it).
+template <class XT, bool PRIOR>
 __global__ void __launch_bounds__(256) nested_step_kernel(NestRow* st, const float* __restrict__ start, float* __restrict__ prop,
-                                                          const float* __restrict__ lnl_new, const NestLaunch l, const NestArgs a) {
+                                                          const float* __restrict__ lnl_new, const NestLaunch l, const NestArgs a,
+                                                          const PriorArgs pr, const long long dec) {
   constexpr int NI = kFitMaxIn;
   __shared__ float key[512];
   __shared__ float ls[256 / (kNestMinLive / 2)];
@@ -96,7 +114,15 @@ __global__ void __launch_bounds__(256) nested_step_kernel(NestRow* st, const flo
     // ---- decide the pending proposal of moving slot j: strictly above L*, on the float32 values; a NaN rejects
     NestRow& s = st[base + j];
     const float lnl_y = lnl_new[p];
-    if (!s.reject && lnl_y > s.lstar) {
+    bool take = !s.reject && lnl_y > s.lstar;
+    if constexpr (PRIOR) {
+      if (take) {
+        uint32_t w[4];
+        sample_block(a.seed, a.chain0 + (uint64_t)(base + j), (uint32_t)(a.iter0 * a.R + dec), 4u, w);
+        take = log(sample_uniform(w[0])) < prior_logp(pr, prop + p * din, din) - prior_logp(pr, s.u, din);
+      }
+    }
+    if (take) {
 #pragma unroll
       for (int i = 0; i < NI; ++i)
         if (i < din) s.u[i] = prop[p * din + i];
@@ -183,7 +209,7 @@ __global__ void __launch_bounds__(256) nested_step_kernel(NestRow* st, const flo
     s.pb = pb;
   }
   if (active && l.start >= 0) {
-    // ---- pass start half `start` on to its evaluation: given rows into the box, or drawn uniform in it
+    // ---- pass start half `start` on to its evaluation: given rows into the box, or drawn from the prior on it
     const long long row = base + (long long)l.start * k + j;
     if (start) {
       for (int i = 0; i < din; ++i) prop[p * din + i] = box_clamp1(start[row * din + i]);
@@ -195,7 +221,18 @@ __global__ void __launch_bounds__(256) nested_step_kernel(NestRow* st, const flo
           sample_block(a.seed, a.chain0 + (uint64_t)row, 0u, 2u + (uint32_t)b, w);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            if (4 * b + i < din) prop[p * din + 4 * b + i] = (float)(2.0 * sample_uniform(w[i]) - 1.0);
+            if (4 * b + i < din) {
+              const int c = 4 * b + i;
+              float v = (float)(2.0 * sample_uniform(w[i]) - 1.0);
+              if constexpr (PRIOR) {
+                if (pr.kind[c]) {
+                  const double sd = 1.0 / sqrt(pr.w[c]);
+                  const double z = nest_tnorm_z((-1.0 - pr.mu[c]) / sd, (1.0 - pr.mu[c]) / sd, sample_uniform(w[i]));
+                  v = box_clamp1((float)(pr.mu[c] + sd * z));
+                }
+              }
+              prop[p * din + c] = v;
+            }
         }
       }
     }

@@ -10,6 +10,7 @@
 //   solve_lower / _upper    L z = g and L^T x = z;
 //   box_clamp1 / box_clamp  a coordinate, and a start row, into the box;
 //   box_to_raw / raw_row    a coordinate, and a row of a result, back to raw units;
+//   PriorArgs               the samplers' prior record as their step kernels take it;
 //   Moments                 the bookkeeping of a sampler's kept transitions, the tail of its row state: the sums of u and
 //                           u u^T and the accepted count, the thinned store of a state, the per-row results.
 #pragma once
@@ -21,6 +22,14 @@ namespace v21 {
 
 constexpr int kFitMaxIn = 8;
 constexpr int kFitPacked = kFitMaxIn * (kFitMaxIn + 1) / 2;
+
+// the handle's prior record (include/v21.h: v21_mlp_set_prior; api_prior.hip) as the step kernels of the four samplers
+// receive it, by value: per input column its kind (0: uniform on [-1, 1], 1: normal(mu, sd) truncated to it), mu,
+// w = 1 / sd^2 and wmu = mu / sd^2.  Columns >= din are never read.  Its arithmetic: sample_kernels.h.
+struct PriorArgs {
+  int kind[kFitMaxIn];
+  double mu[kFitMaxIn], w[kFitMaxIn], wmu[kFitMaxIn];
+};
 
 // din floats in float64 registers, zeros past din
 __device__ inline void widen_row(const float* v, int din, double* v64) {

@@ -1,6 +1,7 @@
 // sample_kernels.h -- posterior sampling on the device (api_sample.hip): a batched Metropolis-adjusted Langevin sampler
 // whose metric is the Fisher matrix at the current point ("simplified manifold MALA"), one thread per chain, in the
-// transformed coordinates u in [-1, 1]^din of the fit (fit_kernels.h) under a uniform prior on that box.
+// transformed coordinates u in [-1, 1]^din of the fit (fit_kernels.h) under the handle's prior on that box: uniform, or
+// with a prior record (include/v21.h: v21_mlp_set_prior; rowmath.h: PriorArgs) separable with truncated-normal columns.
 //   sample_init_kernel    clamps the transformed start rows into the box and resets the chain state;
 //   sample_step_kernel    consumes the evaluation (ln L, gradient, Fisher matrix: jac_reduce_kernel) of the pending
 //                         proposal: accepts or rejects it, adapts the step size in warm-up, keeps the transition
@@ -13,10 +14,17 @@
 //   mu(u) = u + e^2 / 2 G(u)^-1 g(u);   u' = float32(mu(u) + e L(u)^-T xi),  xi ~ N(0, I_d)
 //   log q(b | a) = -|L(a)^T (b - mu(a))|^2 / (2 e^2) + sum_i log L_ii(a) - d / 2 log(2 pi e^2)
 //   log alpha = lnL(u') - lnL(u) + log q(u | u') - log q(u' | u);   accept iff log(uniform) < log alpha
+// With a prior record (PRIOR) the target is L p, ln p(u) = -1/2 sum_i ((u_i - mu_i) / sd_i)^2 over the normal columns:
+//   g(u) = grad ln L(u) - (u - mu) / sd^2,  F(u) = Fisher(u) + diag(1 / sd^2),  log alpha += ln p(u') - ln p(u),
+// the additions made after a tempered rung's beta has scaled ln L's terms and not scaled themselves (a rung samples
+// L^beta p, the beta = 0 rung the prior).  The state and every stored ln L stay ln L alone.
 // (the metric's derivative term of full manifold MALA is left out; the acceptance uses the q that was really drawn
 // from, at the float32 u' that is really evaluated, so the chain is exact).  A proposal with a coordinate outside
 // [-1, 1], or whose G has no finite Cholesky factor, is rejected: log alpha = -inf, its evaluation is not read.
-// Cholesky, solves (rowmath.h) and log-densities are float64 in registers.  Random numbers: Philox4x32-10, include/v21.h.
+// Cholesky, solves (rowmath.h) and log-densities are float64 in registers.  Random numbers: Philox4x32-10, include/v21.h:
+//   blocks 0 and 1, step = the transition: the proposal's normals;  block 2, same step: the acceptance uniform (w0);
+//   block 3, step = the transition a swap event follows: the swap's uniform (w0), drawn for the pair's lower row.
+// The prior draws nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,6 +58,33 @@ __host__ __device__ inline void sample_block(uint64_t seed, uint64_t chain, uint
 __host__ __device__ inline double sample_uniform(uint32_t w) { return ((double)w + 0.5) * (1.0 / 4294967296.0); }
 
 constexpr double kSampleTwoPi = 6.283185307179586476925286766559;
+
+// ---- the prior record (rowmath.h: PriorArgs) in the step kernels of the four samplers.  PRIOR = false: none of it is
+// read, the arithmetic is the uniform prior's.
+// ln p(u), unnormalised: -1/2 sum_i w_i (u_i - mu_i)^2 over the normal columns
+template <class U>
+__device__ __forceinline__ double prior_logp(const PriorArgs& pr, const U* u, int din) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < kFitMaxIn; ++i)
+    if (i < din && pr.kind[i]) {
+      const double d = (double)u[i] - pr.mu[i];
+      s += pr.w[i] * d * d;
+    }
+  return -0.5 * s;
+}
+// g += grad ln p(u) = w mu - w u and F += diag(w), g and F (packed upper triangle, rowmath.h) those of u
+template <bool PRIOR>
+__device__ __forceinline__ void prior_eval(const PriorArgs& pr, const double* u, int din, double* g, double* F) {
+  if constexpr (PRIOR) {
+#pragma unroll
+    for (int i = 0; i < kFitMaxIn; ++i)
+      if (i < din && pr.kind[i]) {
+        g[i] += pr.wmu[i] - pr.w[i] * u[i];
+        F[i * kFitMaxIn - i * (i - 1) / 2] += pr.w[i];
+      }
+  }
+}
 
 // per-chain state
 struct SampleRow {
@@ -142,10 +177,10 @@ __device__ __forceinline__ void temper_eval(double beta, double* g, double* F) {
 // it == 0 is the start's, accepted whatever its value; it >= 1 is the proposal's of transition it - 1.  Adapts the
 // step size in warm-up and takes an accepted proposal as the current point.  -> accepted; have_factor: Lm, mu and ld
 // belong to the current point at the current step size
-template <bool TEMPER>
+template <bool TEMPER, bool PRIOR>
 __device__ __forceinline__ bool sample_decide(SampleRow& s, const float* upr, const float* lnl_new, const float* gn, const float* Fn,
-                                              long long it, long long row, const SampleArgs& a, double beta, double& eps, double* Lm,
-                                              double* mu, double& ld, bool& have_factor) {
+                                              long long it, long long row, const SampleArgs& a, double beta, const PriorArgs& pr,
+                                              double& eps, double* Lm, double* mu, double& ld, bool& have_factor) {
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const int din = a.din;
   double F[NP], g[NI], u[NI];
@@ -158,6 +193,7 @@ __device__ __forceinline__ bool sample_decide(SampleRow& s, const float* upr, co
       widen_row(upr, din, up64);
       widen_eval(gn, Fn, din, g, F);
       temper_eval<TEMPER>(beta, g, F);
+      prior_eval<PRIOR>(pr, up64, din, g, F);
       s.p.widen_u(din, u);
       if (sample_chol(F, a.ridge, din, Lm)) {
         ld = sample_drift(Lm, up64, g, eps, din, mu);
@@ -166,6 +202,7 @@ __device__ __forceinline__ bool sample_decide(SampleRow& s, const float* upr, co
           log_alpha = temper_mul(beta, (double)*lnl_new - (double)s.p.lnl) + lq_rev - s.lq_fwd;
         else
           log_alpha = (double)*lnl_new - (double)s.p.lnl + lq_rev - s.lq_fwd;
+        if constexpr (PRIOR) log_alpha += prior_logp(pr, up64, din) - prior_logp(pr, u, din);
         if (log_alpha != log_alpha) log_alpha = -INFINITY;
         uint32_t w[4];
         sample_block(a.seed, a.chain0 + (uint64_t)row, (uint32_t)(a.step0 + (uint64_t)(it - 1)), 2u, w);
@@ -197,15 +234,17 @@ __device__ __forceinline__ void sample_keep(SampleRow& s, const double* u, bool 
 }
 
 // the proposal of transition `it` from the current point u, written to upr
-template <bool TEMPER>
+template <bool TEMPER, bool PRIOR>
 __device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const double* u, long long it, long long row, const SampleArgs& a,
-                                            double beta, double eps, double* Lm, double* mu, double ld, bool have_factor) {
+                                            double beta, const PriorArgs& pr, double eps, double* Lm, double* mu, double ld,
+                                            bool have_factor) {
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const int din = a.din;
   if (!have_factor) {
     double F[NP], g[NI];
     s.p.widen(din, g, F);
     temper_eval<TEMPER>(beta, g, F);
+    prior_eval<PRIOR>(pr, u, din, g, F);
     if (!sample_chol(F, a.ridge, din, Lm)) {
       // (only a start whose evaluation is not finite: the chain stays where it is)
       s.reject = 1;
@@ -259,11 +298,12 @@ __device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const doub
 
 // one thread per chain, after evaluation number `it` of the call (lnl_new, g_new, F_new at u_prop, u coordinates):
 // the pending proposal is decided (sample_decide), a kept transition accumulated and stored (sample_keep) and, unless
-// it == a.total, the proposal of transition `it` drawn and written to u_prop (sample_draw).  T: the samples' type.
-template <class T>
+// it == a.total, the proposal of transition `it` drawn and written to u_prop (sample_draw).  T: the samples' type;
+// PRIOR: the handle holds a prior record, pr (else not read).
+template <class T, bool PRIOR>
 __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict__ st, float* __restrict__ up, const float* __restrict__ lnl_new,
                                                           const float* __restrict__ g_new, const float* __restrict__ F_new, long long it,
-                                                          const SampleArgs a) {
+                                                          const SampleArgs a, const PriorArgs pr) {
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= a.n) return;
@@ -275,12 +315,13 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
   bool have_factor = false;  // Lm, mu and ld below belong to the current point
   double ld = 0.0;
   const bool accept =
-      sample_decide<false>(s, upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, 1.0, eps, Lm, mu, ld, have_factor);
+      sample_decide<false, PRIOR>(s, upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, 1.0, pr, eps, Lm, mu, ld,
+                                  have_factor);
   // the current point
   s.p.widen_u(din, u);
   sample_keep<T>(s, u, accept, it, row, a);
   if (it == a.total) return;
-  sample_draw<false>(s, upr, u, it, row, a, 1.0, eps, Lm, mu, ld, have_factor);
+  sample_draw<false, PRIOR>(s, upr, u, it, row, a, 1.0, pr, eps, Lm, mu, ld, have_factor);
 }
 
 // ---- parallel tempering (include/v21.h: v21_mlp_sample_tempered): T consecutive rows are the rungs of one ladder, row r
@@ -288,7 +329,7 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
 // its other threads and the rows past n only meet the barriers), so the partners of a swap are threads of one
 // workgroup.  A swap event exchanges the EvalPoints of the swapping pairs through global memory: both rows of a pair
 // form the same decision from the two stored ln L and the lower row's Philox word, a swapping row reads its partner's
-// point into registers, a barrier follows, then it writes that point over its own.
+// point into registers, a barrier follows, then it writes that point over its own.  The prior cancels in the swap rule.
 struct TemperArgs {
   int T, swap_every, rows_per_wg;
   double betas[32];
@@ -300,11 +341,11 @@ struct TemperRow {
   long long proposed, swapped;
 };
 
-template <class T>
+template <class T, bool PRIOR>
 __global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st, TemperRow* __restrict__ tr, float* __restrict__ up,
                                                                    const float* __restrict__ lnl_new, const float* __restrict__ g_new,
                                                                    const float* __restrict__ F_new, long long it, const SampleArgs a,
-                                                                   const TemperArgs ta) {
+                                                                   const TemperArgs ta, const PriorArgs pr) {
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const long long row = (long long)blockIdx.x * ta.rows_per_wg + threadIdx.x;
   // (no thread returns before the last barrier: one that is not `active` skips the work between them)
@@ -318,8 +359,8 @@ __global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st
   bool have_factor = false, accept = false;
   if (active) {
     eps = st[row].eps;
-    accept = sample_decide<true>(st[row], upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, beta, eps, Lm, mu, ld,
-                                 have_factor);
+    accept = sample_decide<true, PRIOR>(st[row], upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, beta, pr, eps,
+                                        Lm, mu, ld, have_factor);
   }
   // the swap event that follows transition S = step0 + it - 1: the same branch for every thread of the launch
   const uint64_t s1 = a.step0 + (uint64_t)it;  // S + 1
@@ -364,7 +405,7 @@ __global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st
   }
   sample_keep<T>(s, u, accept, it, row, a);
   if (it == a.total) return;
-  sample_draw<true>(s, upr, u, it, row, a, beta, eps, Lm, mu, ld, have_factor);
+  sample_draw<true, PRIOR>(s, upr, u, it, row, a, beta, pr, eps, Lm, mu, ld, have_factor);
 }
 
 // one thread per chain: the last state in raw units (raw_row) and the per-chain results (nullable; the moments'

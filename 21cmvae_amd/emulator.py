@@ -16,6 +16,7 @@ from . import _native as nat, engine, foregrounds as fg, preprocess as pp
 from .callbacks import TqdmCallback
 from .engine import ChainedModel, Dense, GaussianLatent, Input, Model, Sequential, sequential_from_arrays
 from .losses import mean_squared_error, relative_mse_loss  # noqa: F401  (public, as in the reference)
+from .priors import Prior
 
 PATH = os.path.dirname(os.path.abspath(__file__)) + "/"
 
@@ -279,14 +280,17 @@ class LogPosterior:
     """ln L of one observed signal under the uniform prior on the training box, for an outside sampler (made by
     ``log_posterior``).  The box is [-1, 1]^7 in par_transform's coordinates u: uniform in the linear columns, log-uniform
     in the log10 columns.  The prior's constant is left out, as ln L's is: inside the box the value is ln L.
+    With ``prior`` (a ``priors.Prior`` or its dict) the value is ln L + ``Prior.log_density_u``, the prior's density
+    normalised on the box relative to the uniform one, and ``prior_transform`` goes through ``Prior.ppf_u``.
     ``lp(theta)``: theta (7,) or (n, 7) raw parameters -> a float or (n,) float64; -inf for every row with a coordinate
     outside the box (or not finite), and such rows are never sent to the device.
     ``lp.prior_transform(cube)``: (7,) or (n, 7) points of the unit cube -> raw parameters, uniform in u
     (``preprocess.par_untransform``) -- the form nested samplers ask for.
     The data / sigma record is uploaded when the object is made and again only if another call replaced it."""
 
-    def __init__(self, em, data, sigma, flow=None, fhigh=None, foreground=None):
+    def __init__(self, em, data, sigma, flow=None, fhigh=None, foreground=None, prior=None):
         self.em = em
+        self.prior = Prior.of(prior, em.par_train)
         self.ndim = len(em.par_labels)
         model, st, flags, _ = em._diff_stack(np.zeros((1, self.ndim)))
         nb = st.dims[-1]
@@ -315,11 +319,14 @@ class LogPosterior:
             model, st, flags, rows = self.em._diff_stack(x[ok])
             self._record(st)
             out[ok] = st.loglike_fwd(rows, model.precision, flags)
+            if self.prior is not None:
+                out[ok] += self.prior.log_density_u(pp.par_transform(x[ok], self.em.par_train), self.em.par_train)
         return float(out[0]) if np.ndim(theta) == 1 else out
 
     def prior_transform(self, cube):
         c = np.array(cube, np.float64, ndmin=2)
-        x = pp.par_untransform(2.0 * c - 1.0, self.em.par_train)
+        u = 2.0 * c - 1.0 if self.prior is None else self.prior.ppf_u(c, self.em.par_train)
+        x = pp.par_untransform(u, self.em.par_train)
         return x[0] if np.ndim(cube) == 1 else x
 
 
@@ -461,12 +468,21 @@ class _EmulatorBase:
         self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
         return st.loglike_fwd(x, model.precision, flags, data=dat).reshape(M, R)
 
-    def log_posterior(self, data, sigma, flow=None, fhigh=None, foreground=None):
+    def log_posterior(self, data, sigma, flow=None, fhigh=None, foreground=None, prior=None):
         """The log-posterior of the parameters given one observed signal, as an object to hand to an outside sampler
         (nested, ensemble, importance; not in the reference): a ``LogPosterior``.  ``lp(theta)``: float64 ln L of
         ``log_likelihood(forward_only=True)`` under the uniform prior on the training box in par_transform's coordinates,
-        -inf outside the box; ``lp.prior_transform(cube)``: the unit cube -> raw parameters, uniform in those coordinates."""
-        return LogPosterior(self, data, sigma, flow, fhigh, foreground)
+        -inf outside the box; ``lp.prior_transform(cube)``: the unit cube -> raw parameters, uniform in those coordinates.
+        ``prior``: as in ``sample_posterior``; ``lp(theta)`` then adds ``Prior.log_density_u`` and ``prior_transform``
+        draws from the prior."""
+        return LogPosterior(self, data, sigma, flow, fhigh, foreground, prior)
+
+    def _use_prior(self, st, prior):
+        """the samplers' prior record on the stack -- ``prior``: None (the record is cleared: a prior of another call
+        never leaks in), a ``priors.Prior`` or its dict -- set beside ``_use_record``; -> the Prior or None"""
+        pr = Prior.of(prior, self.par_train)
+        st.use_prior(None if pr is None else pr.to_u(self.par_train))
+        return pr
 
     def _use_record(self, st, d, w, foreground, flow, fhigh):
         """the likelihood record (d, w) and the nuisance basis of ``foreground`` (None: none) on the stack"""
@@ -609,12 +625,17 @@ class _EmulatorBase:
         return FitResult(xh, lnl, status, F)
 
     def sample_posterior(self, data, sigma, n_chains=64, n_steps=1000, n_warmup=200, thin=1, p0=None, flow=None, fhigh=None, seed=0,
-                         eps=None, return_lnl=False, foreground=None):
+                         eps=None, return_lnl=False, foreground=None, prior=None):
         """Posterior samples of the parameters given observed signal(s) (not in the reference): ``n_chains`` independent
         Markov chains per spectrum, run entirely on the device -- a Metropolis-adjusted Langevin sampler preconditioned
         with the Fisher matrix at the current point (include/v21.h: v21_mlp_sample) -- of the Gaussian ln L of
         ``log_likelihood`` under a UNIFORM PRIOR ON THE TRAINING BOX in par_transform's coordinates u in [-1, 1]^7: uniform
         in the linear columns, log-uniform in the log10 columns, zero outside the box.
+        ``prior`` (here and in ``sample_ensemble``, ``sample_tempered``, ``nested_sample``, ``log_posterior``): None, or a
+        ``priors.Prior`` / its dict ``{label: spec}`` that puts a normal, truncated to the box, on chosen columns --
+        ``("normal", mean, sd)`` in raw units on a linear column, ``("lognormal", mean_log10, sd_dex)`` on a log10 column;
+        the others stay uniform.  The sampler then targets L times that prior on the device (include/v21.h:
+        v21_mlp_set_prior); every returned ``lnl`` stays ln L.  The default starts remain maximum-likelihood fits.
         ``data``: (451,) or (M, 451) mK.  Starts: ``p0`` ((7,) or (n_chains, 7) raw parameters, the same for every
         spectrum), or by default the best ``fit_parameters`` start per spectrum; either way every chain is jittered
         (seeded, 0.02 in u, clipped into the box).  Each chain runs ``n_warmup`` transitions adapting its step size
@@ -626,21 +647,23 @@ class _EmulatorBase:
         moments the device accumulates in float64; the M axis is dropped for one spectrum.  Bounds: a log column's lower
         bound comes back as 10^lo (the fx zero floor 1e-6, not 0)."""
         model, st, flags, dat, one = self._spectra(data)
+        prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         M, C = dat.shape[0], int(n_chains)
         if C < 1:
             raise ValueError("n_chains must be >= 1")
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
         x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground))
+        self._use_prior(st, prior)
         r = st.sample(x0, model.precision, flags, data=dat, **opts)
         return self._posterior_samples(r, lambda a: a.reshape((M, C) + a.shape[1:]), int(n_steps), return_lnl, one)
 
     def sample_ensemble(self, data, sigma, n_walkers=64, n_ensembles=4, n_steps=1000, n_warmup=500, thin=1, a=2.0, p0=None, flow=None,
-                        fhigh=None, seed=0, return_lnl=False, foreground=None):
+                        fhigh=None, seed=0, return_lnl=False, foreground=None, prior=None):
         """Posterior samples from the affine-invariant ensemble sampler (not in the reference): ``n_ensembles`` independent
         ensembles of ``n_walkers`` walkers per spectrum, moved by Goodman & Weare's stretch move with scale ``a`` entirely
         on the device (include/v21.h: v21_mlp_sample_ensemble), on the forward-only ln L of ``log_likelihood`` under
-        ``sample_posterior``'s prior -- uniform on the training box in par_transform's coordinates.  It needs no gradient
+        ``sample_posterior``'s prior -- uniform on the training box in par_transform's coordinates, or ``prior``.  It needs no gradient
         and no Fisher matrix, so it also serves posteriors on which ``sample_posterior``'s metric is singular or misleading.
         ``n_walkers``: even, 16 .. 512 for the 7 parameters.  Starts as ``sample_posterior`` chooses them: ``p0`` ((7,) or
         (n_walkers, 7) raw parameters, the same for every ensemble and spectrum) or the best ``fit_parameters`` start per
@@ -652,6 +675,7 @@ class _EmulatorBase:
         walkers are pooled (``pooled_moments``) and the ensembles compared (``r_hat_from_moments``; NaN for one ensemble) --
         and the pooled mean_u (M, 7) / cov_u (M, 7, 7); the M axis is dropped for one spectrum."""
         model, st, flags, dat, one = self._spectra(data)
+        prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         din = st.dims[0]
         M, E, W = dat.shape[0], int(n_ensembles), int(n_walkers)
         if E < 1:
@@ -659,11 +683,12 @@ class _EmulatorBase:
         opts = dict(a=a, n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed)
         nat.Stack.ensemble_opts(W, in_dim=din, **opts)  # (argument errors before any device work)
         x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (E, W), p0, sigma, flow, fhigh, seed, foreground))
+        self._use_prior(st, prior)
         r = st.sample_ensemble(x0, W, model.precision, flags, data=dat, **opts)
         return self._posterior_samples(r, lambda a: a.reshape((M, E, W) + a.shape[1:]), int(n_steps), return_lnl, one)
 
     def sample_tempered(self, data, sigma, n_ladders=16, n_temps=8, betas=None, swap_every=5, n_steps=1000, n_warmup=200, thin=1,
-                        p0=None, flow=None, fhigh=None, seed=0, eps=None, return_lnl=False, foreground=None):
+                        p0=None, flow=None, fhigh=None, seed=0, eps=None, return_lnl=False, foreground=None, prior=None):
         """Parallel-tempered posterior samples and the Bayesian evidence (not in the reference): ``n_ladders`` ladders per
         spectrum, each of ``n_temps`` chains of ``sample_posterior``'s sampler at the inverse temperatures ``betas``
         (default ``default_betas(n_temps)``, from 1 down to 0), run entirely on the device (include/v21.h:
@@ -683,8 +708,12 @@ class _EmulatorBase:
         trapezoid's discretisation bias, which only more rungs reduce.  ln Z is comparable between emulators, bands and
         noise levels at the same data and the same foreground basis (add the dropped -sum ln(sigma sqrt(2 pi)) over the
         band's bins where sigma or the band differ).  It is NOT comparable across different numbers of marginalised
-        foreground modes: their flat prior is improper.  nan with ``n_temps = 1``."""
+        foreground modes: their flat prior is improper.  nan with ``n_temps = 1``.
+        With ``prior`` a chain at beta samples L^beta times the prior, the beta = 0 rung the prior itself, mean_lnl stays the
+        mean of ln L alone, and log_evidence is ln of the mean of L under the STATED, normalised prior.  It is comparable
+        across priors only as a Bayes factor between models, not as a goodness of fit."""
         model, st, flags, dat, one = self._spectra(data)
+        prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         M, C, T = dat.shape[0], int(n_ladders), int(n_temps)
         if C < 1:
             raise ValueError("n_ladders must be >= 1")
@@ -694,6 +723,7 @@ class _EmulatorBase:
         nat.Stack.temper_opts(T, b, swap_every)
         x0 = self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground)
         x0 = np.ascontiguousarray(np.repeat(x0, T, axis=0))  # (every rung of a ladder from its ladder's start)
+        self._use_prior(st, prior)
         r = st.sample_tempered(x0, T, b, swap_every, model.precision, flags, data=dat, **opts)
         # (the beta = 1 rows)
         ps = self._posterior_samples(r, lambda a: a.reshape((M, C, T) + a.shape[1:])[:, :, 0], int(n_steps), return_lnl, one)
@@ -709,7 +739,7 @@ class _EmulatorBase:
         return TemperedSamples(*ps, b, E, swap, lz, lz_err)
 
     def nested_sample(self, data, sigma, n_live=256, n_runs=1, n_repeats=None, dlogz=0.01, max_iter=2000, flow=None, fhigh=None,
-                      foreground=None, seed=0, return_lnl=True):
+                      foreground=None, seed=0, return_lnl=True, prior=None):
         """Nested sampling of the posterior given observed signal(s) (not in the reference): the Bayesian evidence with its
         error and weighted posterior samples in one run, without a gradient, entirely on the device (include/v21.h:
         v21_mlp_sample_nested) on the forward-only ln L of ``log_likelihood`` under ``sample_posterior``'s prior -- uniform
@@ -736,8 +766,12 @@ class _EmulatorBase:
         discretisation bias in beta.  ln Z is comparable between emulators, bands and noise levels at the same data and
         the same foreground basis (add the dropped -sum ln(sigma sqrt(2 pi)) over the band's bins where sigma or the band
         differ).  It is NOT comparable across different numbers of marginalised foreground modes: their flat prior is
-        improper."""
+        improper.
+        With ``prior`` the live points are drawn from it, a move is a Metropolis move on the prior inside the deleted
+        points' highest ln L, ``lnl`` stays ln L, and log_evidence is ln of the mean of L under the STATED, normalised
+        prior.  It is comparable across priors only as a Bayes factor between models, not as a goodness of fit."""
         model, st, flags, dat, one = self._spectra(data)
+        prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         din = st.dims[0]
         M, R, N = dat.shape[0], int(n_runs), int(n_live)
         if R < 1:
@@ -751,6 +785,7 @@ class _EmulatorBase:
         nat.Stack.nested_opts(N, n_iter=int(max_iter), in_dim=din, **opts)  # (argument errors before any device work)
         rep = int(n_repeats) if n_repeats else 3 * din
         self._use_record(st, dat[0], self._band_weights(st.dims[-1], sigma, flow, fhigh), foreground, flow, fhigh)
+        self._use_prior(st, prior)
         s_k = np.sum(1.0 / (N - np.arange(k)))
         u, T, dead_u, dead_l, acc, stopped = None, 0, [], [], 0.0, "max_iter"
         while T < int(max_iter):

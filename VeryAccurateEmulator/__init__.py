@@ -13,7 +13,7 @@ _sys.modules[__name__ + ".preprocess"] = preprocess
 
 
 def __getattr__(name):
-    if name in ("emulator", "engine", "callbacks", "optimizers", "losses", "foregrounds"):
+    if name in ("emulator", "engine", "callbacks", "optimizers", "losses", "foregrounds", "priors"):
         mod = _il.import_module("21cmvae_amd." + name)
         _sys.modules[__name__ + "." + name] = mod
         return mod

@@ -455,6 +455,35 @@ int v21_mlp_set_nuisance(v21_mlp* mlp, const double* basis, int32_t n_modes, int
 int v21_mlp_nuisance_info(v21_mlp* mlp, int32_t* n_modes);
 int v21_mlp_nuisance_coef(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, double* coef, int precision, int flags);
 
+/* ---- the samplers' prior.  Without a prior record the four samplers (v21_mlp_sample, v21_mlp_sample_tempered,
+ * v21_mlp_sample_ensemble, v21_mlp_sample_nested and their _dev forms) work under the uniform prior on the box
+ * u in [-1, 1]^in_dim of the input transform.  A record makes the prior separable in u, one entry per input column:
+ *     kind[i] = 0  uniform on [-1, 1] (mu[i] and sd[i] are not read);
+ *     kind[i] = 1  normal(mu[i], sd[i]) in u, truncated to [-1, 1].
+ * With ln p(u) = -1/2 sum_i ((u_i - mu_i) / sd_i)^2 over the normal columns (unnormalised, float64):
+ *   v21_mlp_sample            targets L p: the gradient gains -(u - mu) / sd^2, the metric diag(1 / sd^2), log alpha
+ *                             ln p(u') - ln p(u);
+ *   v21_mlp_sample_tempered   the same additions, not scaled by beta: the rung at beta samples L^beta p, the rung at
+ *                             beta = 0 the prior, and thermodynamic integration over mean_lnl (which stays the mean of
+ *                             ln L alone) gives ln Z with respect to the NORMALISED prior; the swap rule is unchanged;
+ *   v21_mlp_sample_ensemble   log alpha gains ln p(y) - ln p(x);
+ *   v21_mlp_sample_nested     a move is accepted iff it is inside the box, ln L(y) > L* and log(U) < ln p(y) - ln p(x),
+ *                             U = U(w0) of Philox block 4 at the move's step; a drawn start takes, in a normal column,
+ *                             mu + sd Phi^-1(Phi(a) + U (Phi(b) - Phi(a))), a, b the standardised box ends and U that of
+ *                             the word that draws the column without a record (float64, mirrored where a + b > 0 so
+ *                             that Phi is taken in the tail nearer the mode); GIVEN starts are clamped as before, and
+ *                             that they are draws of the prior is the caller's business.  The evidence is the mean of
+ *                             L under the normalised prior.
+ * Every ln L a sampler returns stays ln L.  v21_mlp_loglike, v21_mlp_fisher, v21_mlp_fit and v21_mlp_jacobian do not
+ * read the record.
+ *   v21_mlp_set_prior  kind, mu, sd: in_dim entries each (copied).  in_dim = 0 or kind = NULL clears the record; a
+ *     record whose kinds are all 0 is no record: the samplers then launch what they launched before.  V21_ERR_ARG, the
+ *     handle keeping what it had: in_dim is not the stack's (or above 8); a kind outside {0, 1}; for a normal column mu
+ *     or sd NULL, sd not finite or below 1e-3, mu not finite or more than 5 sd outside the box (past that the truncated
+ *     normal's mass in the box cannot be formed reliably, and such a prior contradicts the emulator's domain).  Pure
+ *     host bookkeeping: no GPU work. */
+int v21_mlp_set_prior(v21_mlp* mlp, const int32_t* kind, const double* mu, const double* sd, int32_t in_dim);
+
 /* ---- trainer: replaces Model.compile + Model.fit (emulator.py:369-378, :739-747,
  * :756-764; optimizer/loss from notebooks/Training.ipynb cells 4 and 10). ------- */
 typedef struct {
