@@ -39,7 +39,7 @@ def setup(ctx):
     """the headline stack with seeded weights, the transforms of a synthetic training set, one noisy spectrum as the record"""
     import jacobian_ref as jr
     from helpers import init_weights
-    from test_jacobian_cpu import transforms
+    from infer_cases import transforms
     nat = pkg("_native")
     dims, act = S1
     Ws, bs, _ = init_weights(dims, 3)

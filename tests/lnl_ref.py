@@ -9,7 +9,7 @@ import jacobian_ref as jr
 import shape_cases as sc
 from conftest import pkg
 from helpers import STACKS, init_weights
-from test_jacobian_cpu import ARCHS, VG, transforms, vg_weights
+from infer_cases import ARCHS, VG, transforms, vg_weights
 
 # The parity bound of the fused route: worst |lnl - ref| / |ref| over every case of test_fused_parity.  Measured on the
 # MI355X: worst 1.56e-7 (f32 2^-24 roundings of ~380 positive terms in 15-deep per-lane sums and
@@ -23,8 +23,8 @@ _stacks = {}
 
 
 def stack_of(ctx, name):
-    """the device handle of a named stack (helpers.STACKS, test_jacobian_cpu.ARCHS / VG) with seeded weights and both
-    transforms of test_jacobian_cpu.transforms(5) (the input transform on 7-input stacks) -> (st, dims, act, Ws, bs, tin, tout)"""
+    """the device handle of a named stack (helpers.STACKS, infer_cases.ARCHS / VG) with seeded weights and both
+    transforms of infer_cases.transforms(5) (the input transform on 7-input stacks) -> (st, dims, act, Ws, bs, tin, tout)"""
     if name not in _stacks:
         nat = pkg("_native")
         if name == "VG":

@@ -85,7 +85,7 @@ def has_tin(dims):
 
 
 def _weights(dims, act, seed):
-    """helpers.init_weights, or the recipe of test_jacobian_cpu.vg_weights for a stack with a Gauss layer (2 n columns)"""
+    """helpers.init_weights, or the recipe of infer_cases.vg_weights for a stack with a Gauss layer (2 n columns)"""
     if GAUSS not in act:
         Ws, bs, _ = init_weights(dims, seed)
         return Ws, bs

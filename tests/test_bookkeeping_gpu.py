@@ -8,8 +8,7 @@ import pytest
 import jacobian_ref as jr
 import shape_cases as sc
 from conftest import pkg
-from test_sample_gpu import same
-from test_shapes_gpu import device_stack, flags_of
+from infer_support import device_stack, flags_of, same
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +44,7 @@ def test_kept_transitions(ctx, sampler, name):
     nat = pkg("_native")
     case = sc.BY_NAME[name]
     st, rec = device_stack(ctx, case.dims, case.act)
-    tin, flags, din = rec["tin"], flags_of(nat, rec), case.dims[0]
+    tin, flags, din = rec["tin"], flags_of(nat, rec["tin"] is not None), case.dims[0]
     prob = sc.fit_problem(case)
     st.set_likelihood(prob["data"][0], prob["w"])
     n = rows_of(sampler, din)

@@ -12,7 +12,7 @@ import ensemble_ref as er
 import sample_ref as sr
 from conftest import pkg
 from helpers import STACKS
-from test_jacobian_cpu import ARCHS
+from infer_cases import ARCHS
 
 N_SE = 5.0
 MISS = 4 * N_SE  # what a wrong variant must miss by at least: "far more than the bound"

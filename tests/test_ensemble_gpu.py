@@ -17,36 +17,15 @@ import lnl_ref as lr
 import sample_ref as sr
 import shape_cases as sc
 from conftest import pkg
-from test_fit_gpu import fit_setup, u_of
-from test_lnl_gpu import ready
+from infer_cases import N_SE, SPREAD
+from infer_support import between_chain, fit_setup, flags_of, ready, run_dev, same, starts_near, u_of, ulp32
 
 pytestmark = pytest.mark.gpu
 
-N_SE = 5.0
-# the walkers' spread around the truth in u.  fit_setup's record (sigma = 0.02 std) is flat at 0.003 (ln L varies by 0.1
+# SPREAD, the walkers' spread around the truth in u: fit_setup's record (sigma = 0.02 std) is flat at 0.003 (ln L varies by 0.1
 # .. 0.2 over the walkers) and steep at 0.1; at 0.05 ln L varies by a few units, so that the likelihood term of log alpha
 # decides a fair share of the proposals and a fair share of them is accepted
-SPREAD = 0.05
-POISON = 0x7F
 KEYS = ("x_last", "lnl_last", "accept_rate", "mean_u", "cov_u", "samples", "samples_lnl", "last_prop_u", "last_log_alpha", "last_partner")
-
-
-def flags_of(nat):
-    return nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM
-
-
-def starts_near(truth, tin, n, seed, scale):
-    """n raw float64 starts: the truth jittered by `scale` in u, inside the box"""
-    u = np.clip(u_of(truth[None, :], tin) + scale * np.random.default_rng(seed).normal(size=(n, 7)), -0.999, 0.999)
-    return fr.untransform(u, tin[0], tin[2], tin[3])
-
-
-def same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def ulp32(a):
-    return np.spacing(np.abs(a).astype(np.float32)).astype(np.float64)
 
 
 # ---- one sweep against the float64 rebuild from the device's own evaluations
@@ -61,7 +40,7 @@ def test_one_sweep_against_reference(ctx, name, prec):
     """n_steps = 1 from given starts, D1 / S3 on the fused route and NB on the two-launch route.  last_partner and
     last_prop_u: bit-equal for both sets -- set 1's partners are set 0's positions AFTER its half-move, taken from the
     device's own decisions.  log alpha: within one float32 ulp of each of its two ln L, to first order (the rule of
-    test_sample_gpu.alpha_bound: the inputs are float32 numbers, the formula is float64).  The decisions agree wherever
+    infer_support.alpha_bound: the inputs are float32 numbers, the formula is float64).  The decisions agree wherever
     |ln U - log alpha| exceeds that bound; at most 0.5 % may be excused.  lnl_last: loglike_fwd of the same u, bit for bit."""
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx, name)
@@ -72,9 +51,9 @@ def test_one_sweep_against_reference(ctx, name, prec):
         n, H = W * E, W // 2
         seed, chain0, step0 = 100 + W, 11, 40
         x0 = starts_near(truths[0], tin, n, W, SPREAD)
-        u0 = st.sample_ensemble(x0, W, prec, flags_of(nat), n_steps=0, n_warmup=0, diagnostics=True)["last_prop_u"].astype(np.float64)
+        u0 = st.sample_ensemble(x0, W, prec, flags_of(nat, True), n_steps=0, n_warmup=0, diagnostics=True)["last_prop_u"].astype(np.float64)
         assert np.max(np.abs(u0 - u_of(x0, tin))) <= 2.0 ** -23
-        r = st.sample_ensemble(x0, W, prec, flags_of(nat), n_steps=1, n_warmup=0, a=a, seed=seed, chain0=chain0, step0=step0, diagnostics=True)
+        r = st.sample_ensemble(x0, W, prec, flags_of(nat, True), n_steps=1, n_warmup=0, a=a, seed=seed, chain0=chain0, step0=step0, diagnostics=True)
         assert st.last_lnl_route()[0] == ("two_launch" if name == "NB" else "fused")
         e, h, _ = er.layout(n, W)
         z, k, logu = er.draws(seed, chain0 + np.arange(n), step0, a, H)
@@ -124,41 +103,15 @@ def dev_ensemble(ctx, st, x0, data_rows, W, prec, flags, keys=KEYS, guard=0, **o
               "samples_lnl": ((n, keep), np.float32), "mean_u": ((n, din), np.float64), "cov_u": ((n, din, din), np.float64),
               "accept_rate": ((n,), np.float64), "last_prop_u": ((n, din), np.float32), "last_log_alpha": ((n,), np.float64),
               "last_partner": ((n,), np.int32)}
-    host = {k: np.empty(*shapes[k]) for k in keys}
-    bufs = []
-    try:
-        dx = ctx.malloc(max(x0.nbytes, 8))
-        bufs.append(dx)
-        dd = None
-        if data_rows is not None:
-            dd = ctx.malloc(data_rows.nbytes)
-            bufs.append(dd)
-            ctx.h2d(dd, data_rows)
-        out = {}
-        for k, arr in host.items():
-            nb = max(arr.nbytes + guard, 8)
-            out[k] = ctx.malloc(nb)
-            bufs.append(out[k])
-            ctx.memset(out[k], POISON, nb)
-        if x0.nbytes:
-            ctx.h2d(dx, x0)
-        st.sample_ensemble_dev(dx, din, n, dd, data_rows.shape[0] if data_rows is not None else 0, out, W, prec, flags, **opts)
-        ctx.sync()
-        for k, arr in host.items():
-            raw = np.empty(max(arr.nbytes + guard, 8), np.uint8)
-            ctx.d2h(raw, out[k])
-            arr.view(np.uint8).reshape(-1)[:] = raw[:arr.nbytes]
-            assert np.all(raw[arr.nbytes:arr.nbytes + guard] == POISON), k
-    finally:
-        for p in bufs:
-            ctx.free(p)
-    return host
+    n_data = data_rows.shape[0] if data_rows is not None else 0
+    call = lambda dx, dd, out: st.sample_ensemble_dev(dx, din, n, dd, n_data, out, W, prec, flags, **opts)
+    return run_dev(ctx, shapes, keys, call, x0, data_rows, guard)
 
 
 def test_split_invariance(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_of(nat)
+    flags = flags_of(nat, True)
     W = 16
     # the host form of 8,208 rows (513 ensembles: chunks of 8,192 and 16 rows) equals the _dev form
     n = 8208
@@ -195,7 +148,7 @@ def test_routes_and_counters(ctx):
     two-launch route's forward is the fused kernel too)."""
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_of(nat)
+    flags = flags_of(nat, True)
     x = starts_near(truths[0], tin, 520, 9, 0.01)
     counts = lambda: dict(st.last_lnl_route()[1])
     jac = st.last_jac_route()
@@ -227,7 +180,7 @@ def test_uniform_target_on_the_device(ctx):
     u0 = np.random.default_rng(4).uniform(-1, 1, size=(n, d))
     x0 = fr.untransform(u0, tin[0], tin[2], tin[3])
     opts = dict(n_steps=600, n_warmup=200, seed=5)
-    r = st.sample_ensemble(x0, W, "f16", flags_of(nat), thin=0, diagnostics=True, **opts)
+    r = st.sample_ensemble(x0, W, "f16", flags_of(nat, True), thin=0, diagnostics=True, **opts)
     assert "samples" not in r and all(np.all(np.isfinite(r[k])) for k in ("mean_u", "cov_u", "accept_rate", "x_last"))
     assert np.all(r["lnl_last"] == 0)
     z = er.draws(5, np.arange(n), 799, 2.0, W // 2)[0]
@@ -247,11 +200,6 @@ def test_uniform_target_on_the_device(ctx):
 
 
 # ---- statistics against the reference
-def between(a):
-    a = np.asarray(a, np.float64)
-    return a.mean(axis=0), a.var(axis=0, ddof=1) / a.shape[0]
-
-
 def test_statistics_against_reference(ctx):
     """NB, f32, 64 ensembles x 16 walkers, 100 + 200 sweeps on the device and in tests/ensemble_ref.py (same starts, same
     draws): per-ensemble pooled mean and second moments within 5 combined between-ensemble standard errors"""
@@ -261,14 +209,14 @@ def test_statistics_against_reference(ctx):
     W, E = 16, 64
     x0 = starts_near(truths[0], tin, W * E, 1, SPREAD)
     opts = dict(n_steps=200, n_warmup=100, seed=11)
-    r = st.sample_ensemble(x0, W, "f32", flags_of(nat), thin=0, **opts)
+    r = st.sample_ensemble(x0, W, "f32", flags_of(nat, True), thin=0, **opts)
     ref = er.ensemble_ref(er.forward_evaluator(Ws, bs, act, data[0], w, tout), u_of(x0, tin), W, thin=0, **opts)
     worst = {}
     pool = lambda q: q.reshape((E, W) + q.shape[1:]).mean(axis=1)
     sec = lambda q: q["cov_u"] + q["mean_u"][:, :, None] * q["mean_u"][:, None, :]
     for key, dv, rf in (("mean", pool(r["mean_u"]), pool(ref["mean_u"])), ("second moments", pool(sec(r)), pool(sec(ref))),
                         ("accept", pool(r["accept_rate"]), pool(ref["accept_rate"]))):
-        (md, vd), (mr, vr) = between(dv), between(rf)
+        (md, vd), (mr, vr) = between_chain(dv), between_chain(rf)
         zz = np.abs(md - mr) / np.sqrt(vd + vr)
         worst[key] = float(np.max(zz))
         assert np.all(zz < N_SE), (key, zz)
@@ -281,7 +229,7 @@ def test_statistics_against_reference(ctx):
 def test_edge_cases(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_of(nat)
+    flags = flags_of(nat, True)
     W = 16
     x0 = starts_near(truths[0], tin, 2 * W, 6, SPREAD)
     # n = 0: a no-op on both entries
@@ -353,7 +301,7 @@ def test_edge_cases(ctx):
 def test_argument_errors_leave_the_handle_usable(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_of(nat)
+    flags = flags_of(nat, True)
     lib, F, P = st.lib, C.POINTER(C.c_float), C.c_void_p
     x0 = np.ascontiguousarray(starts_near(truths[0], tin, 96, 40, 0.01).astype(np.float32))
     xl = np.empty_like(x0)

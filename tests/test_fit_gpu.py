@@ -8,44 +8,13 @@ import pytest
 import fit_ref as fr
 import jacobian_ref as jr
 from conftest import pkg
-from test_jacobian_gpu import check_rows, rows_for, stack_of
+from infer_support import FUSED, GENERIC, check_rows, fit_setup, flags_of, pick, rows_for, setup, u_of
 
 pytestmark = pytest.mark.gpu
 
-FUSED, GENERIC = ("D1", "DE", "S3", "S4"), ("NB", "W6")
 # (p99, max) of F's relative Frobenius error against the 16-bit primal's masks, at most 4x the worst MI355X values (p99:
 # f16 1.6e-3, bf16 1.2e-2; max: bf16 1.4e-2, f16 2.4e-2 outside the <= 0.5 % of rows with a unit at its kink)
 F16_BOUND = {"f16": (6e-3, 6e-2), "bf16": (5e-2, 6e-2)}
-
-
-def band_weights(dout, tout, seed=1):
-    """1 / sigma^2 on a band of bins, zero outside it and on a few scattered bins"""
-    rng = np.random.default_rng(seed)
-    w = np.full(dout, 1.0 / (0.05 * tout[0]) ** 2)
-    w[: dout // 5] = 0.0
-    w[rng.uniform(size=dout) < 0.1] = 0.0
-    return w.astype(np.float32)
-
-
-def setup(ctx, name, seed=1):
-    st, dims, act, Ws, bs, tin, tout = stack_of(ctx, name)
-    dout = dims[-1]
-    w = band_weights(dout, tout, seed)
-    x1 = rows_for(dims, 1, 99, np.float64)
-    data = (jr.jacobian(Ws, bs, act, x1, tin if dims[0] == 7 else None, tout)[0][0]
-            + np.random.default_rng(seed).normal(size=dout) * 0.05 * tout[0]).astype(np.float32)
-    st.set_likelihood(data, w)
-    return st, dims, act, Ws, bs, tin, tout, data, w
-
-
-def flags_of(nat, dims):
-    return (nat.FWD_IN_TRANSFORM if dims[0] == 7 else 0) | nat.FWD_OUT_TRANSFORM
-
-
-def pick(n):
-    """rows to compare: both ends, both sides of the 16,384-row slice boundary, a few more"""
-    edges = [i for i in (16383, 16384, 32767, 32768) if i < n]
-    return np.unique(np.r_[0, n - 1, edges, np.arange(0, n, max(1, n // 40))].astype(np.int64))
 
 
 def test_fisher_against_own_jacobian(ctx):
@@ -55,7 +24,7 @@ def test_fisher_against_own_jacobian(ctx):
     cases += [("D1", "f16", 65536)]
     for name, prec, n in cases:
         st, dims, act, Ws, bs, tin, tout, data, w = setup(ctx, name)
-        flags = flags_of(nat, dims)
+        flags = flags_of(nat, dims[0] == 7)
         x = rows_for(dims, n, 31 + n, np.float32)
         tag = "%s %s n=%d" % (name, prec, n)
         F, lnl, g = st.fisher(x, prec, flags, lnl=True, grad=True)
@@ -84,7 +53,7 @@ def test_fisher_against_float64(ctx, prec):
         if name == "NB" and prec != "f32":
             continue
         st, dims, act, Ws, bs, tin, tout, data, w = setup(ctx, name)
-        flags = flags_of(nat, dims)
+        flags = flags_of(nat, dims[0] == 7)
         tin_on = dims[0] == 7
         x = rows_for(dims, 600, 77, np.float64)
         F = st.fisher(x, prec, flags)
@@ -110,24 +79,6 @@ def test_fisher_against_float64(ctx, prec):
             assert np.sum(err > mx) <= max(1, int(0.005 * err.size)), (name, worst[name])
         st.set_likelihood(None, None)
     print("Fisher vs float64 %s: %s" % (prec, worst))
-
-
-def fit_setup(ctx, name="D1", seed=3, m=3):
-    """stack, its references, `m` spectra of truths drawn in the box (with noise), the record set to their weights"""
-    st, dims, act, Ws, bs, tin, tout = stack_of(ctx, name)
-    dout = dims[-1]
-    truths = pkg("synth").make_params(m, seed=seed, zero_fx_frac=0)
-    sig = 0.02 * tout[0]
-    rng = np.random.default_rng(seed)
-    data = (jr.jacobian(Ws, bs, act, truths, tin, tout)[0] + rng.normal(size=(m, dout)) * sig).astype(np.float32)
-    w = np.full(dout, 1.0 / sig ** 2, np.float32)
-    w[:40] = 0.0
-    st.set_likelihood(data[0], w)
-    return st, dims, act, Ws, bs, tin, tout, truths, data, w
-
-
-def u_of(x, tin):
-    return jr.transform(np.asarray(x, np.float64), *tin)[0]
 
 
 @pytest.mark.parametrize("prec", ["f32", "f16", "bf16"])

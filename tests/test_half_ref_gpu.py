@@ -1,6 +1,6 @@
 """Every 16-bit forward route against the float64 reference that rounds where the kernels round (tests/half_ref.py).
 
-The float64 oracle's bounds (test_forward_gpu.HALF_BOUNDS: max |d| 1e-3 f16, 1e-2 bf16) cover operand rounding, and so
+The float64 oracle's bounds (infer_cases.HALF_BOUNDS: max |d| 1e-3 f16, 1e-2 bf16) cover operand rounding, and so
 also a kernel that rounds a hidden layer toward zero or rounds its bias (max |d| 1.4e-4 / 1.3e-3 from a correct one).
 Against the rounding reference a correct kernel differs by its f32 summation order only, and in a few rows by the one-ulp
 hidden values that order moves across a 16-bit rounding midpoint -- so the checks bound the MEDIAN and the 99th percentile
@@ -19,8 +19,8 @@ import pytest
 import half_ref as hr
 from conftest import pkg
 from helpers import FWD16_TOL, STACKS
+from infer_cases import ARCHS as FUSED_STACKS, HALF_BOUNDS
 from oracle import ref_numpy as ora
-from test_forward_gpu import FUSED_STACKS, HALF_BOUNDS
 
 pytestmark = pytest.mark.gpu
 

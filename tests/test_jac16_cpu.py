@@ -15,7 +15,7 @@ import half_ref as hr
 import jacobian_ref as jr
 from conftest import pkg
 from helpers import FWD16_TOL, JAC16_TOL, STACKS, init_weights
-from test_jacobian_cpu import ARCHS, VG, transforms, vg_weights
+from infer_cases import ARCHS, VG, transforms, vg_weights
 
 _cache = {}
 

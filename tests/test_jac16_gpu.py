@@ -7,7 +7,7 @@ rounds a layer's tangents toward zero, scales a tile or rounds the chain-rule fa
 is left of a correct kernel is its f32 summation order, and in single rows the ReLU units that order decides the other
 way: so the check bounds MEDIANS over rows, one per (input, 32-bin output tile) cell of J, and asserts the worst cell
 (half_ref.jac_worst_cell_median; calls of fewer than 31 rows pool their cells); the p99 / max conditions stay as they are
-(test_jacobian_gpu.check_rows, called here).  Every entry of half_ref.JAC_MUTATIONS the check answers for, applied to the
+(infer_support.check_rows, called here).  Every entry of half_ref.JAC_MUTATIONS the check answers for, applied to the
 device's own J, must be refused -- and lie at least 4x beyond the bound.
 
 Bounds (helpers.JAC16_TOL, LNL16_TOL, FISHER16_TOL): at most 4x the worst measured on the MI355X over every case here, at
@@ -29,9 +29,7 @@ import half_ref as hr
 import jacobian_ref as jr
 from conftest import pkg
 from helpers import FISHER16_TOL, JAC16_TOL, LNL16_TOL
-from test_fit_gpu import flags_of, setup
-from test_jacobian_gpu import check_rows, rows_for, stack_of
-from test_marg_gpu import basis, reference
+from infer_support import basis, check_rows, flags_of, reference, rows_for, setup, stack_of
 
 pytestmark = pytest.mark.gpu
 
@@ -119,7 +117,7 @@ def test_loglike_and_fisher_match_rounding_reference(ctx, name, prec):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, data, w = setup(ctx, name)
     try:
-        flags = flags_of(nat, dims)
+        flags = flags_of(nat, dims[0] == 7)
         tin_on = dims[0] == 7
         ti = tin if tin_on else None
         x = rows_for(dims, 600, 77, np.float64)
@@ -161,7 +159,7 @@ def test_marginalised_reductions_match_rounding_reference(ctx):
     prec = "f16"
     st, dims, act, Ws, bs, tin, tout, data, w = setup(ctx, "D1")
     try:
-        flags = flags_of(nat, dims)
+        flags = flags_of(nat, dims[0] == 7)
         A = basis(5)
         st.set_nuisance(A)
         assert st.nuisance_modes() == 5

@@ -10,42 +10,8 @@ import pytest
 
 import jacobian_ref as jr
 from conftest import ROOT, pkg
-from helpers import STACKS, init_weights
-
-# a 7-input variational stack: 7 -> 64 -> (gauss 9) -> 32 -> 451
-VG = ([7, 64, 9, 32, 451], [1, 2, 1, 0])
-ARCHS = {"S1": STACKS["D1"], "S2": STACKS["DE"], "S3": ([7, 352, 352, 352, 224, 9, 32, 352, 451], [1, 1, 1, 1, 0, 1, 1, 0]),
-         "S4": ([9, 32, 352, 451], [1, 1, 0])}
-
-
-def vg_weights(seed):
-    dims, act = VG
-    rng = np.random.default_rng(seed)
-    Ws, bs = [], []
-    for l, (k, n) in enumerate(zip(dims[:-1], dims[1:])):
-        nw = 2 * n if act[l] == 2 else n
-        lim = np.sqrt(6.0 / (k + nw))
-        Ws.append(rng.uniform(-lim, lim, size=(k, nw)).astype(np.float32))
-        bs.append(rng.normal(scale=0.05, size=nw).astype(np.float32))
-    return Ws, bs
-
-
-def weights_of(name, seed=3):
-    if name == "VG":
-        return VG[0], VG[1], *vg_weights(seed)
-    dims, act = STACKS[name]
-    Ws, bs, _ = init_weights(dims, seed)
-    return dims, act, Ws, bs
-
-
-def transforms(seed, dtype=np.float64):
-    synth, pp = pkg("synth"), pkg("preprocess")
-    par_train = synth.make_params(2000, seed=seed, corners=True)
-    ps = pp.ParamStats(par_train)
-    sig = synth.make_signals(500, seed=seed + 1)
-    tin = (ps.log_mask, ps.zero_floor, ps.lo, ps.hi)
-    tout = (float(np.std(sig)), np.mean(sig, axis=0))
-    return tin, tout, synth.make_params(600, seed=seed + 7, zero_fx_frac=0).astype(dtype)
+from helpers import STACKS
+from infer_cases import ARCHS, VG, transforms, weights_of
 
 
 @pytest.mark.parametrize("name", ["D1", "NB", "VG"])

@@ -8,83 +8,18 @@ import pytest
 
 import jacobian_ref as jr
 from conftest import pkg
-from helpers import STACKS, init_weights
-from test_jacobian_cpu import ARCHS, VG, transforms, vg_weights
+from helpers import init_weights
+from infer_cases import transforms
+from infer_support import check_rows, rows_for, stack_of
 
 pytestmark = pytest.mark.gpu
 
 ROWS = [1, 3, 4, 5, 31, 33, 4099, 65536]
 CMP_ROWS = 2048
-BOUND = {"f32": None, "f16": (1e-2, 3e-2), "bf16": (5e-2, 1e-1)}  # (p99, max) against the 16-bit primal's masks
-
-_cache = {}
-
-
-def stack_of(ctx, name):
-    if name not in _cache:
-        nat = pkg("_native")
-        if name == "VG":
-            dims, act = VG
-            Ws, bs = vg_weights(3)
-        else:
-            dims, act = ARCHS[name] if name in ARCHS else STACKS[name]
-            Ws, bs, _ = init_weights(dims, 3)
-        st = nat.Stack(ctx, dims, act)
-        st.set_weights(jr.ora.flatten_params(Ws, bs))
-        tin, tout, _ = transforms(5)
-        if dims[0] == 7:
-            st.set_input_transform(*tin)
-        st.set_output_transform(tout[0], tout[1].astype(np.float32))
-        _cache[name] = (st, dims, act, Ws, bs, tin, tout)
-    return _cache[name]
-
-
-def rows_for(dims, n, seed, dtype):
-    if dims[0] == 7:
-        x = pkg("synth").make_params(max(n, 8), seed=seed)[:n]
-    else:
-        x = np.random.default_rng(seed).uniform(-1, 1, size=(n, dims[0]))
-    return x.astype(dtype)
 
 
 def subset(n):
     return np.arange(n) if n <= CMP_ROWS else np.unique(np.r_[0, n - 1, np.random.default_rng(n).choice(n, CMP_ROWS - 2, replace=False)])
-
-
-def check_rows(tag, prec, got, ref, Ws, bs, act, xt, tin_on, x, tin, tout):
-    err = jr.rel_frobenius(got, ref)
-    assert np.all(np.isfinite(err)), tag
-    if prec != "f32":
-        # 16-bit: the ReLU mask follows the device's 16-bit primal (z > 0 of the f16 / bf16 operands' sum), and a unit
-        # whose float64 pre-activation lies within that rounding of zero switches: one switched unit of a 224-wide last
-        # hidden layer moves J by ~1 / sqrt(224) ~ 7 %.  So the operand-rounding bounds hold against the
-        # float64 Jacobian WITH the 16-bit primal's masks (tests/jacobian_ref.py: masks16); against the plain float64
-        # Jacobian the switched rows are only reported.
-        _, Jm = jr.jacobian(Ws, bs, act, x, tin if tin_on else None, tout, mask_prec=prec)
-        em = jr.rel_frobenius(got, Jm)
-        p99, mx = BOUND[prec]
-        print("%s: vs 16-bit masks p99 %.2e max %.2e; vs float64 median %.2e, rows > %.0e: %d of %d"
-              % (tag, np.percentile(em, 99), em.max(), np.median(err), mx, int(np.sum(err > mx)), err.size))
-        assert np.percentile(em, 99) <= p99, (tag, np.percentile(em, 99))
-        # a row beyond the max bound (at most 0.5 %): the emulation sums the 16-bit operands in float64 and rounds each
-        # layer's output once, the device sums in f32 -- one layer output rounded to the neighbouring 16-bit value moves
-        # the next pre-activations by ~1 ulp (2^-11 / 2^-8) of their scale, so a unit the emulation puts within 2 ulp of
-        # zero may be decided the other way; such a unit must exist in the row
-        bad = np.flatnonzero(em > mx)
-        assert bad.size <= max(1, int(0.005 * em.size)), (tag, bad.size, em.max())
-        for i in bad:
-            xt1 = (jr.transform(x[i:i + 1], *tin)[0] if tin_on else x[i:i + 1].astype(np.float64)).astype(np.float32)
-            _, z16 = jr.masks16(Ws, bs, act, xt1, prec, with_z=True)
-            rel = 2.0 ** -10 if prec == "f16" else 2.0 ** -7
-            assert any(a == jr.RELU and np.any(np.abs(z) <= rel * np.max(np.abs(z))) for z, a in zip(z16, act)), (tag, i, em[i])
-        return
-    bad = np.flatnonzero(err > 1e-5)
-    assert bad.size <= max(1, int(0.005 * err.size)), (tag, bad.size, err.max())
-    for i in bad:  # each must come within the bound once the reference flips the units at their kink -- all of them
-        kinks = jr.near_kinks(Ws, bs, act, xt[i:i + 1])
-        assert any(k is not None and k.any() for k in kinks), (tag, i, err[i])
-        _, Jf = jr.jacobian(Ws, bs, act, x[i:i + 1], tin if tin_on else None, tout, kinks)
-        assert jr.rel_frobenius(got[i:i + 1], Jf)[0] <= 1e-5, (tag, i, err[i], jr.rel_frobenius(got[i:i + 1], Jf)[0])
 
 
 @pytest.mark.parametrize("prec", ["f32", "f16", "bf16"])

@@ -10,7 +10,7 @@ import lnl_ref as lr
 import shape_cases as sc
 from conftest import pkg
 from helpers import STACKS
-from test_jacobian_cpu import ARCHS, VG
+from infer_cases import ARCHS, VG
 
 
 def test_route_table():

@@ -14,15 +14,11 @@ import lnl_ref as lr
 import marg_ref as mr
 import shape_cases as sc
 from conftest import pkg
+from infer_support import POISON, device_stack, ready, same
 
 pytestmark = pytest.mark.gpu
 
-POISON = np.frombuffer(b"\x7f\x7f\x7f\x7f", np.uint32)[0]
 STATE = -4
-
-
-def same(a, b):
-    return np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))
 
 
 def case_of(ctx, name, prec, k, n):
@@ -206,40 +202,11 @@ def test_state_errors_and_empty_calls(ctx):
 
 
 # ---- the two-launch route
-_dev = {}
-
-
-def ready(st, prec):
-    """a stack outside archs.h that can have a run-time instantiated forward kernel has it before the comparison starts:
-    the forward inside the call and the forward of the reference then take one route"""
-    nat = pkg("_native")
-    try:
-        st.jit(prec, -1)
-    except nat.EngineError:
-        pass  # (not eligible: a Gauss layer)
-
-
-def device_stack(ctx, dims, act):
-    """a stack of shape_cases with its transforms set, as test_shapes_gpu.device_stack builds it"""
-    key = (tuple(dims), tuple(act))
-    if key not in _dev:
-        nat = pkg("_native")
-        rec = sc.make_stack(dims, act)
-        st = nat.Stack(ctx, dims, act)
-        st.set_weights(rec["flat"])
-        if rec["tin"] is not None:
-            st.set_input_transform(*rec["tin"])
-        st.set_output_transform(rec["tout"][0], rec["tout"][1].astype(np.float32))
-        _dev[key] = st
-    _dev[key].set_likelihood(None, None)
-    return _dev[key], sc.make_stack(dims, act)
-
-
 def test_two_launch_on_the_shape_table(ctx):
     """shape_cases i4o65, i5o130, i8o451, i5gauss, i8relu, i1o1 at shape_cases.ROWS, K = 0 and each of the case's modes.
     References on the device's own forward y widened to float64: jacobian_ref.loglike for K = 0 within 1e-5 of ln L (the
     bound of test_likelihood_mode_of_the_generic_kernel), marg_ref.profile_lnl for K > 0 within 1e-5 of the scale r^T W r
-    + |b|^2 of the PROJECTED data the device reduces (the bound and scale of test_marg_gpu.check_reduction, used by
+    + |b|^2 of the PROJECTED data the device reduces (the bound and scale of infer_support.check_reduction, used by
     test_marginalised_reductions).  Against the old
     loglike(grad=False) of the same stack (the generic Jacobian kernel's own f32 primal): within 2e-5 of ln L resp. of the
     scale -- the sum of the two routes' bounds.  Observed on the MI355X: K = 0 worst 1.08e-7 of ln L against the reference

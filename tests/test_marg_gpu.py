@@ -19,17 +19,10 @@ import jacobian_ref as jr
 import marg_ref as mr
 import sample_ref as sr
 from conftest import pkg
-from test_fit_gpu import FUSED, GENERIC, fit_setup, flags_of, pick, setup, u_of
-from test_jacobian_gpu import rows_for, stack_of
-from test_sample_gpu import alpha_bound, alpha_of, device_eval, same, starts_near
+from infer_support import (FUSED, GENERIC, NU, alpha_bound, alpha_of, basis, check_reduction, device_eval, fit_setup, flags_of, pick, reference,
+                           rows_for, same, setup, starts_near, u_of)
 
 pytestmark = pytest.mark.gpu
-
-NU = np.linspace(50.0, 200.0, 451)
-
-
-def basis(K):
-    return pkg("foregrounds").linlog_basis(NU, K)
 
 
 def foreground(amp75=2e6, K=5, seed=0):
@@ -41,33 +34,6 @@ def foreground(amp75=2e6, K=5, seed=0):
     return a @ A
 
 
-def reference(y, jac, d, w, A):
-    """marg_ref on the device's y and J with the float32 data as they are, and the scales of the projected residual"""
-    w64 = np.asarray(w, np.float64)
-    ref = mr.marg(y, jac, d, w64, A)
-    Q, R = mr.whiten(A, w64)
-    sc = mr.marg(y, jac, mr.project(d, Q, w64), w64, A)
-    Ri = np.abs(np.linalg.inv(R))
-    rt = np.abs(mr.project(d, Q, w64) - np.asarray(y, np.float64))
-    coef_tol = (1e-5 * (rt * w64) @ np.abs(Q).T) @ Ri.T + 1e-12 * np.abs((w64 * np.asarray(d, np.float64)) @ Q.T) @ Ri.T
-    return ref, sc["lnl_scale"], sc["grad_scale"], coef_tol
-
-
-def check_reduction(tag, F, lnl, g, coef, ref, lnl_scale, grad_scale, coef_tol, worst):
-    eF = np.sqrt(np.sum((F - ref["F"]) ** 2, axis=(1, 2))) / np.sqrt(np.sum(ref["F0"] ** 2, axis=(1, 2)))
-    el = np.abs(lnl - ref["lnl"]) / lnl_scale
-    eg = np.abs(g - ref["grad"]) / grad_scale
-    worst["F"], worst["lnl"], worst["grad"] = max(worst["F"], eF.max()), max(worst["lnl"], el.max()), max(worst["grad"], eg.max())
-    print("%s: F %.2e lnl %.2e grad %.2e (of 1e-5)" % (tag, eF.max(), el.max(), eg.max()))
-    assert eF.max() <= 1e-5, (tag, eF.max())
-    assert el.max() <= 1e-5, (tag, el.max())
-    assert eg.max() <= 1e-5, (tag, eg.max())
-    if coef is not None:
-        ec = np.abs(coef - ref["coef"]) / coef_tol
-        worst["coef"] = max(worst["coef"], ec.max())
-        assert ec.max() <= 1.0, (tag, ec.max())
-
-
 def test_reductions_against_own_jacobian(ctx):
     """measured worst on the MI355X, as fractions of the scales: F 1.5e-7, lnl 5.0e-8, grad 4.3e-8 (the bounds stay at 1e-5),
     the amplitudes at 0.0085 of their bound"""
@@ -77,7 +43,7 @@ def test_reductions_against_own_jacobian(ctx):
     worst = {"F": 0.0, "lnl": 0.0, "grad": 0.0, "coef": 0.0}
     for c, (name, prec, n) in enumerate(cases):
         st, dims, act, Ws, bs, tin, tout, data, w = setup(ctx, name)
-        flags = flags_of(nat, dims)
+        flags = flags_of(nat, dims[0] == 7)
         K = (3, 5, 8, 1, 4)[c % 5]
         A = basis(K)
         x = rows_for(dims, n, 31 + n, np.float32)
@@ -115,7 +81,7 @@ def test_reductions_against_own_jacobian(ctx):
 def test_record_state(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, data, w = setup(ctx, "NB")
-    flags = flags_of(nat, dims)
+    flags = flags_of(nat, dims[0] == 7)
     x = rows_for(dims, 4, 3, np.float32)
     A = basis(5)
     st.set_likelihood(None, None)

@@ -1,7 +1,7 @@
 """The nested sampler, host side (no GPU): ``nested_evidence`` on constructed records, the float64 reference
-(tests/nested_ref.py) on an analytic Gaussian in the box and on the two quadrature problems of tests/test_temper_cpu.py,
+(tests/nested_ref.py) on an analytic Gaussian in the box and on the two quadrature problems of tests/infer_cases.py,
 two deliberately wrong variants that the same bound catches, the route decision (v21_route_nested) and the refusals of
-``Stack.nested_opts``.  The quadrature cases are computed once and shared with tests/test_nested_gpu.py.
+``Stack.nested_opts``.  The quadrature cases (tests/infer_cases.py) are computed once and shared with tests/test_nested_gpu.py.
 
 Bound: N_SE = 5 standard errors of the mean over 64 independent runs (their scatter / 8).  Measured with the shipped
 defaults (n_repeats = 3 d, gamma = 2.38 / sqrt(2 d)), sigma = 0.1, seed 0: d = 7, N = 256 bias +0.056 +- 0.032; d = 7,
@@ -13,23 +13,13 @@ import math
 import numpy as np
 import pytest
 
-import ensemble_ref as er
 import nested_ref as nr
-import test_temper_cpu as tc
 from conftest import pkg
-from test_jacobian_cpu import ARCHS
+from infer_cases import ARCHS, N_SE, RUNS, SEED, quadrature_case, run_stats, z_of
 
-N_SE = 5.0
-RUNS, SIGMA, SEED = 64, 0.1, 0
-QUAD = {"i1": (32, 40), "i2": (64, 40)}  # live points, iterations: X_T = e^-27.7, nothing is left in the live points
+SIGMA = 0.1  # the analytic Gaussian's width in u
 
-_gauss, _quad = {}, {}
-
-
-def run_stats(r, N, runs, shrink="harmonic"):
-    """per-run (ln Z, error) of a reference or device result"""
-    ev = [nr.evidence(r["dead_lnl"][:, e], r["live_lnl"].reshape(runs, N)[e], N, shrink) for e in range(runs)]
-    return np.array([v[0] for v in ev]), np.array([v[1] for v in ev])
+_gauss = {}
 
 
 def gauss_run(d, N, **kw):
@@ -40,25 +30,6 @@ def gauss_run(d, N, **kw):
         u0 = nr.start_draws(SEED, np.arange(RUNS * N), d)
         _gauss[key] = nr.nested_ref(nr.gauss_lnl(SIGMA), u0, N, T, seed=SEED, **kw)
     return _gauss[key]
-
-
-def z_of(lz, truth):
-    return (lz.mean() - truth) / (lz.std(ddof=1) / math.sqrt(len(lz)))
-
-
-def quadrature_case(name):
-    """-> (problem, ln Z by the midpoint rule, the reference's result, its per-run ln Z); computed once"""
-    if name not in _quad:
-        p = tc.problem(name)
-        d, (N, T) = p["dims"][0], QUAD[name]
-        g = tc.lnl_grid(p, tc.GRID[name])
-        m = g.max()
-        lz_q = m + math.log(np.sum(np.exp(g - m))) - d * math.log(tc.GRID[name])
-        st = p["stack"]
-        ev = er.forward_evaluator(st["Ws"], st["bs"], st["act"], p["data"], p["w"], st["tout"])
-        r = nr.nested_ref(ev, nr.start_draws(SEED, np.arange(RUNS * N), d), N, T, seed=SEED)
-        _quad[name] = (p, lz_q, r, run_stats(r, N, RUNS)[0])
-    return _quad[name]
 
 
 # ---- nested_evidence

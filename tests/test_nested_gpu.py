@@ -12,27 +12,18 @@ import pytest
 
 import nested_ref as nr
 import shape_cases as sc
-import test_nested_cpu as ncpu
 from conftest import pkg
-from test_fit_gpu import fit_setup, u_of
-from test_lnl_gpu import ready
-from test_shapes_gpu import device_stack
+from infer_cases import N_SE, QUAD, RUNS, SEED, SPREAD, quadrature_case
+from infer_support import device_stack, fit_setup, ready, run_dev, same, starts_near
 
 pytestmark = pytest.mark.gpu
 
-N_SE = 5.0
-SPREAD = 0.05  # the live points' spread around the truth in u (tests/test_ensemble_gpu.py: ln L varies by a few units)
-POISON = 0x7F
 KEYS = ("dead_u", "dead_lnl", "lstar", "live_u", "live_lnl", "accept_rate", "last_partner", "last_prop_u")
-
-
-def same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
 def live_near(truth, tin, n, seed, scale=SPREAD):
     """n float64 live points in u: the truth jittered by `scale`, inside the box"""
-    return np.clip(u_of(truth[None, :], tin) + scale * np.random.default_rng(seed).normal(size=(n, 7)), -0.999, 0.999)
+    return starts_near(truth, tin, n, seed, scale, raw=False)
 
 
 def stats(r, N):
@@ -106,37 +97,9 @@ def dev_nested(ctx, st, u0, n, data_rows, N, prec, flags, keys=KEYS, guard=0, **
     shapes = {"dead_u": ((T, runs, k, din), np.float32), "dead_lnl": ((T, runs, k), np.float32), "lstar": ((T, runs), np.float32),
               "live_u": ((n, din), np.float32), "live_lnl": ((n,), np.float32), "accept_rate": ((runs, k), np.float64),
               "last_partner": ((runs, k, 2), np.int32), "last_prop_u": ((runs, k, din), np.float32)}
-    host = {key: np.empty(*shapes[key]) for key in keys}
-    bufs = []
-    try:
-        dx = None
-        if u0 is not None:
-            dx = ctx.malloc(max(u0.nbytes, 8))
-            bufs.append(dx)
-            if u0.nbytes:
-                ctx.h2d(dx, u0)
-        dd = None
-        if data_rows is not None:
-            dd = ctx.malloc(data_rows.nbytes)
-            bufs.append(dd)
-            ctx.h2d(dd, data_rows)
-        out = {}
-        for key, arr in host.items():
-            nb = max(arr.nbytes + guard, 8)
-            out[key] = ctx.malloc(nb)
-            bufs.append(out[key])
-            ctx.memset(out[key], POISON, nb)
-        st.sample_nested_dev(dx, din, n, dd, data_rows.shape[0] if data_rows is not None else 0, out, N, prec, flags, **opts)
-        ctx.sync()
-        for key, arr in host.items():
-            raw = np.empty(max(arr.nbytes + guard, 8), np.uint8)
-            ctx.d2h(raw, out[key])
-            arr.view(np.uint8).reshape(-1)[:] = raw[:arr.nbytes]
-            assert np.all(raw[arr.nbytes:arr.nbytes + guard] == POISON), key
-    finally:
-        for p in bufs:
-            ctx.free(p)
-    return host
+    n_data = data_rows.shape[0] if data_rows is not None else 0
+    call = lambda dx, dd, out: st.sample_nested_dev(dx, din, n, dd, n_data, out, N, prec, flags, **opts)
+    return run_dev(ctx, shapes, keys, call, u0, data_rows, guard)
 
 
 def test_continuation_and_splitting(ctx):
@@ -182,15 +145,15 @@ def test_continuation_and_splitting(ctx):
 # ---- the evidence
 @pytest.mark.parametrize("name", ["i1", "i2"])
 def test_evidence_against_quadrature_and_reference(ctx, name):
-    """the two quadrature problems of tests/test_temper_cpu.py on the device in f32, 64 runs from the drawn starts the
+    """the two quadrature problems of tests/infer_cases.py on the device in f32, 64 runs from the drawn starts the
     reference takes too: ln Z within 5 standard errors of the midpoint rule's and within 5 (both sides' errors) of
     tests/nested_ref.py's"""
     nat = pkg("_native")
-    p, lz_q, ref, lz_ref = ncpu.quadrature_case(name)
-    N, T = ncpu.QUAD[name]
+    p, lz_q, ref, lz_ref = quadrature_case(name)
+    N, T = QUAD[name]
     st, rec = device_stack(ctx, p["dims"], p["act"])
     st.set_likelihood(p["data"], p["w"])
-    r = st.sample_nested(None, ncpu.RUNS * N, N, "f32", nat.FWD_OUT_TRANSFORM, n_iter=T, seed=ncpu.SEED)
+    r = st.sample_nested(None, RUNS * N, N, "f32", nat.FWD_OUT_TRANSFORM, n_iter=T, seed=SEED)
     lz, err = stats(r, N)
     se, se_ref = lz.std(ddof=1) / 8, lz_ref.std(ddof=1) / 8
     z_q, z_r = (lz.mean() - lz_q) / se, (lz.mean() - lz_ref.mean()) / np.hypot(se, se_ref)

@@ -2,8 +2,8 @@
 float64 reference tests/prior_ref.py against closed forms, the statistical tests of tests/test_prior_gpu.py on the
 reference at the seeds and sizes they use there, and the binding's argument checks that need no device.
 
-The cases the GPU tests share are defined here: the mixed record of a d-column stack, the flat-likelihood runs, and the
-two evidence problems (tests/test_temper_cpu.py's quadrature problems under a Gaussian prior)."""
+The cases the GPU tests share are in tests/infer_cases.py: the mixed record of a d-column stack, the flat-likelihood runs,
+and the two evidence problems (the tempering tests' quadrature problems under a Gaussian prior)."""
 import ctypes as C
 import math
 
@@ -15,107 +15,17 @@ import ensemble_ref as er
 import nested_ref as nr
 import prior_ref as pr
 import sample_ref as sr
+import shape_cases as sc
 import temper_ref as tr
-import test_nested_cpu as ncpu
-import test_temper_cpu as tc
 from conftest import pkg
-
-N_SE = 5.0
-BETAS3 = np.array([1.0, 0.3, 0.0])
-
-
-def mixed_prior(d):
-    """the mixed record of a d-column stack: two normal columns, the second with mu outside the box by 2 sd, the rest
-    uniform (d = 1: the one column normal with mu outside the box by 2 sd)"""
-    kind, mu, sd = np.zeros(d, np.int32), np.zeros(d), np.ones(d)
-    if d == 1:
-        kind[0], mu[0], sd[0] = 1, 1.3, 0.15
-        return pr.as_prior(kind, mu, sd)
-    a, b = (1, 4) if d >= 5 else (0, d - 1)
-    kind[a], mu[a], sd[a] = 1, 0.3, 0.25
-    kind[b], mu[b], sd[b] = 1, -1.4, 0.2
-    return pr.as_prior(kind, mu, sd)
-
-
-# ---- the flat-likelihood runs of test_prior_gpu.test_the_prior_is_sampled: (chains or ladders or ensembles, options)
-FLAT_MALA = dict(d=7, chains=256, opts=dict(n_steps=600, n_warmup=150, thin=0, seed=5))
-FLAT_TEMPER = dict(d=2, ladders=256, swap_every=1, opts=dict(n_steps=600, n_warmup=150, thin=0, seed=6))
-FLAT_ENSEMBLE = dict(d=4, W=16, ensembles=64, opts=dict(n_steps=600, n_warmup=300, thin=0, seed=7))
+from infer_cases import (BETAS, BETAS3, FLAT_ENSEMBLE, FLAT_MALA, FLAT_TEMPER, N_SE, RUNS, SPREAD, evidence_quadrature, flat_starts, ladder_lz, mixed_prior,
+                         moment_z, near, nested_reference, problem, run_stats, second_moment, tempered_reference, z_of)
+from infer_support import alpha_bound_prior, alpha_of, posterior_eval
 
 
 def flat_ev(u):
     n, d = np.shape(u)
     return np.zeros(n), np.zeros((n, d)), np.zeros((n, d, d))
-
-
-def flat_starts(d, n, seed):
-    return tc.scattered_u(d, n, seed)
-
-
-def moment_z(mean_c, m2_c, prior):
-    """z of the per-chain (or per-ensemble) estimates of E[u] and E[u^2] against the prior's closed form"""
-    m, v = pr.moments(prior)
-    return sr.pooled_check(mean_c, m)[1], sr.pooled_check(m2_c, v + m * m)[1]
-
-
-def second_moment(r):
-    return np.diagonal(r["cov_u"], axis1=1, axis2=2) + r["mean_u"] ** 2
-
-
-# ---- the evidence problems: tc.problem(name) under a normal on every column, 0.05 off the truth and 0.05 wide.  (With a
-# column left uniform the 8-rung trapezoid of the 2-input problem is 0.26 nats off the integral, 20 standard errors: the
-# discretisation bias sample_tempered's docstring describes.  With both columns constrained it is below one.)
-def evidence_prior(name):
-    p = tc.problem(name)
-    d = p["dims"][0]
-    return pr.as_prior(np.ones(d, np.int32), np.round(p["truth_u"] + 0.05, 3), np.full(d, 0.05))
-
-
-_quad, _tref, _nref = {}, {}, {}
-
-
-def evidence_quadrature(name):
-    """-> (ln Z under the prior, ln Z under the uniform prior, E_beta[ln L] under L^beta p at tc.BETAS) by the midpoint rule"""
-    if name not in _quad:
-        p, prior = tc.problem(name), evidence_prior(name)
-        N, d = tc.GRID[name], p["dims"][0]
-        c = (np.arange(N) + 0.5) * (2.0 / N) - 1.0
-        pts = c[:, None] if d == 1 else np.stack(np.meshgrid(c, c, indexing="ij"), -1).reshape(-1, 2)
-        g, lp = tc.lnl_grid(p, N), pr.log_prior(prior, pts)
-        lse = lambda a: a.max() + math.log(np.sum(np.exp(a - a.max())))
-        E = []
-        for b in tc.BETAS:
-            a = b * g + lp
-            wt = np.exp(a - a.max())
-            E.append(np.sum(wt * g) / np.sum(wt))
-        _quad[name] = (lse(g + lp) - lse(lp), lse(g) - d * math.log(N), np.array(E))
-    return _quad[name]
-
-
-def tempered_reference(name):
-    """prior_ref.temper_ref on the problem at test_temper_cpu's ladder and run; computed once"""
-    if name not in _tref:
-        p = tc.problem(name)
-        _tref[name] = pr.temper_ref(p["ev"], evidence_prior(name), p["starts_u"], tc.BETAS, swap_every=tc.SWAP_EVERY, **tc.RUN)
-    return _tref[name]
-
-
-def nested_reference(name):
-    """prior_ref.nested_ref on the problem from starts drawn from the prior, at test_nested_cpu's sizes; -> (result, ln Z per run)"""
-    if name not in _nref:
-        p, prior = tc.problem(name), evidence_prior(name)
-        d, (N, T) = p["dims"][0], ncpu.QUAD[name]
-        st = p["stack"]
-        ev = er.forward_evaluator(st["Ws"], st["bs"], st["act"], p["data"], p["w"], st["tout"])
-        r = pr.nested_ref(ev, prior, pr.start_draws(prior, ncpu.SEED, np.arange(ncpu.RUNS * N), d), N, T, seed=ncpu.SEED)
-        _nref[name] = (r, ncpu.run_stats(r, N, ncpu.RUNS)[0])
-    return _nref[name]
-
-
-def ladder_lz(mean_lnl):
-    """per-ladder trapezoids of a tempered run's mean ln L -> (mean, standard error)"""
-    lz = tr.trapezoid(tc.BETAS, np.asarray(mean_lnl, np.float64).reshape(tc.LADDERS, tc.RUNGS))
-    return lz.mean(), lz.std(ddof=1) / math.sqrt(tc.LADDERS)
 
 
 # ---- the Prior class
@@ -269,7 +179,7 @@ def test_nested_reference_on_gaussian_times_gaussian(d, N):
     out = {}
     for use in (True, False):
         r = pr.nested_ref(nr.gauss_lnl(sigma), prior, u0, N, T, seed=1, use_prior=use)
-        out[use] = ncpu.z_of(ncpu.run_stats(r, N, runs)[0], truth)
+        out[use] = z_of(run_stats(r, N, runs)[0], truth)
     print("d=%d N=%d: closed form %.4f, z %.2f; without the prior's acceptance z %.2f" % (d, N, truth, out[True], out[False]))
     assert abs(out[True]) < N_SE
     assert abs(out[False]) > N_SE
@@ -305,13 +215,13 @@ def test_evidence_on_the_reference(name):
     lz_q, lz_flat, E_q = evidence_quadrature(name)
     r = tempered_reference(name)
     lz, se = ladder_lz(r["mean_lnl"])
-    bias = tr.trapezoid(tc.BETAS, E_q) - lz_q
+    bias = tr.trapezoid(BETAS, E_q) - lz_q
     print("%s tempered: ln Z %.4f +- %.4f, quadrature %.4f (z %+.2f), trapezoid of the quadrature %+.4f off it, uniform prior %.4f"
           % (name, lz, se, lz_q, (lz - lz_q) / se, bias, lz_flat))
     assert abs(lz - lz_q) < N_SE * se and abs(lz - lz_flat) > N_SE * se
-    assert abs(lz - tr.trapezoid(tc.BETAS, E_q)) < N_SE * se
+    assert abs(lz - tr.trapezoid(BETAS, E_q)) < N_SE * se
     rn, lzn = nested_reference(name)
-    se_n = lzn.std(ddof=1) / math.sqrt(ncpu.RUNS)
+    se_n = lzn.std(ddof=1) / math.sqrt(RUNS)
     print("%s nested: ln Z %.4f +- %.4f (z %+.2f), accept %.2f" % (name, lzn.mean(), se_n, (lzn.mean() - lz_q) / se_n, rn["accept_rate"].mean()))
     assert abs(lzn.mean() - lz_q) < N_SE * se_n and abs(lzn.mean() - lz_flat) > N_SE * se_n
 
@@ -321,38 +231,35 @@ def test_transition_cases_excuse_none_on_the_reference():
     their seeds and row counts: no decision lies within the bound of its uniform (0 excused), and the nested rebuild's
     smallest |ln U - (ln p(y) - ln p(x))| is far above float64 rounding.  (D1's evaluations exist only on the device: its
     cases assert the same cap there.)"""
-    import shape_cases as sc
-    import test_prior_gpu as pg
-    from test_sample_gpu import alpha_of
-    p = tc.problem("i2")
+    p = problem("i2")
     prior = mixed_prior(2)
     for n, betas in ((3, None), (257, None), (6, BETAS3), (258, BETAS3)):
         beta = np.ones(n) if betas is None else BETAS3[np.arange(n) % 3]
-        u0 = pg.near(p["truth_u"], n, 5, 0.03).astype(np.float32).astype(np.float64)
+        u0 = near(p["truth_u"], n, 5, 0.03).astype(np.float32).astype(np.float64)
         chains, eps = sc.CHAIN0 + np.arange(n), np.full(n, sc.EPS0)
         e0 = p["ev"](u0)
-        t0 = pg.posterior_eval(e0, u0, beta, prior)
+        t0 = posterior_eval(e0, u0, beta, prior)
         prop, _, _ = sr.propose(u0, t0[1], t0[2], eps, sr.normals(sc.SEED, chains, sc.STEP0, 2), sc.RIDGE)
         e1 = p["ev"](prop)
-        la = alpha_of(u0, t0, prop, pg.posterior_eval(e1, prop, beta, prior), eps, sc.RIDGE)
-        bound = pg.alpha_bound_prior(u0, e0, prop, e1, eps, sc.RIDGE, la, beta, prior) + 1e-12
+        la = alpha_of(u0, t0, prop, posterior_eval(e1, prop, beta, prior), eps, sc.RIDGE)
+        bound = alpha_bound_prior(u0, e0, prop, e1, eps, sc.RIDGE, la, beta, prior) + 1e-12
         logu = np.log(sr.accept_uniform(sc.SEED, chains, sc.STEP0))
         assert not np.any(np.abs(logu - la) <= bound), (n, betas is None)
     # the ensemble sweep: two ensembles of 16 walkers
     st = p["stack"]
     lnl_of = er.forward_evaluator(st["Ws"], st["bs"], st["act"], p["data"], p["w"], st["tout"])
     W, n = 16, 32
-    u = pg.near(p["truth_u"], n, W, pg.SPREAD).astype(np.float32).astype(np.float64)
+    u = near(p["truth_u"], n, W, SPREAD).astype(np.float32).astype(np.float64)
     r = er.ensemble_ref(pr.with_prior(lnl_of, prior), u, W, n_steps=1, n_warmup=0, seed=100 + W, chain0=11, step0=40)
     _, _, logu = er.draws(100 + W, 11 + np.arange(n), 40, 2.0, W // 2)
     fin = np.isfinite(r["last_log_alpha"])
     assert np.min(np.abs(logu - r["last_log_alpha"])[fin]) > 1e-3  # (a float32 ulp of ln L ~ 40 is 4e-6)
     # the nested rebuild on the 1-input stack
-    p1 = tc.problem("i1")
+    p1 = problem("i1")
     s1 = p1["stack"]
     ev1 = er.forward_evaluator(s1["Ws"], s1["bs"], s1["act"], p1["data"], p1["w"], s1["tout"])
     for runs in (1, 5):
-        ref = pr.nested_ref(ev1, mixed_prior(1), pg.near(p1["truth_u"], 16 * runs, 16 + runs, pg.SPREAD), 16, n_iter=2, n_repeats=2, seed=116,
+        ref = pr.nested_ref(ev1, mixed_prior(1), near(p1["truth_u"], 16 * runs, 16 + runs, SPREAD), 16, n_iter=2, n_repeats=2, seed=116,
                             chain0=176, iter0=40)
         assert ref["min_margin"] > 1e-9, (runs, ref["min_margin"])
 

@@ -5,8 +5,8 @@ continuation and host chunks with a record, argument errors, and the emulator cl
 
 The stacks: D1 (7 inputs, the fused routes; f32, f16, bf16) and the 1-, 2- and 4-input stacks of tests/shape_cases.py
 (the padded columns of kFitMaxIn, one Philox block; generic routes, f32).  The cases, seeds and sizes shared with the
-reference-only checks live in tests/test_prior_cpu.py.  Every test leaves its stack without a record: the handles are
-shared with the other test files."""
+reference-only checks (tests/test_prior_cpu.py) live in tests/infer_cases.py.  Every test leaves its stack without a record: the
+handles are shared with the other test files."""
 import contextlib
 import ctypes as C
 
@@ -15,43 +15,23 @@ import pytest
 
 import ensemble_ref as er
 import fit_ref as fr
+import infer_cases as ic
 import prior_ref as pr
 import sample_ref as sr
 import shape_cases as sc
 import temper_ref as tr
-import test_nested_cpu as ncpu
-import test_prior_cpu as pc
-import test_temper_cpu as tc
 from conftest import pkg
-from test_fit_gpu import fit_setup, u_of
-from test_lnl_gpu import ready
-from test_sample_gpu import alpha_of, device_eval
-from test_shapes_gpu import device_stack
-from test_temper_gpu import dev_tempered, shape_setup, starts_in_box
+from infer_cases import BETAS3, N_SE, SPREAD, near
+from infer_support import (alpha_bound_prior, alpha_of, dev_tempered, device_eval, device_stack, fit_setup, flags_of, posterior_eval, ready, same,
+                           shape_setup, starts_in_box, u_of, ulp32)
 
 pytestmark = pytest.mark.gpu
-
-N_SE = pc.N_SE
-BETAS3 = pc.BETAS3
-SPREAD = 0.05  # tests/test_ensemble_gpu.py: the walkers' and live points' spread around the truth in u
-
-
-def same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
 def same_results(a, b):
     assert a.keys() == b.keys()
     for k in a:
         assert same(a[k], b[k]), k
-
-
-def ulp32(a):
-    return np.spacing(np.abs(a).astype(np.float32)).astype(np.float64)
-
-
-def flags_all(nat):
-    return nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM
 
 
 @contextlib.contextmanager
@@ -65,8 +45,8 @@ def prior_on(st, prior):
 
 
 def small_setup(ctx, name):
-    """the 1- or 2-input quadrature problem of test_temper_cpu on the device -> (stack handle, problem, tin)"""
-    p = tc.problem(name)
+    """the 1- or 2-input quadrature problem of infer_cases on the device -> (stack handle, problem, tin)"""
+    p = ic.problem(name)
     st, rec = device_stack(ctx, p["dims"], p["act"])
     st.set_likelihood(p["data"], p["w"])
     return st, p, rec["tin"]
@@ -85,46 +65,10 @@ def setup(ctx, which):
     return st, tin, p["truth_u"]
 
 
-def near(truth_u, n, seed, scale):
-    return np.clip(truth_u[None, :] + scale * np.random.default_rng(seed).normal(size=(n, len(truth_u))), -0.999, 0.999)
-
-
 CASES = [("D1", "f32"), ("D1", "f16"), ("D1", "bf16"), ("i2", "f32")]
 
 
 # ---- 1. one transition against the reference
-def posterior_eval(e, u, beta, prior):
-    """an evaluation (lnl, g, F) of ln L at u as the transition at the rows' beta under the prior sees it"""
-    return (tr.tmul(beta, e[0]) + pr.log_prior(prior, u), tr.tmul(beta, e[1]) + pr.grad_log_prior(prior, u),
-            tr.tmul(beta, e[2]) + pr.precision(prior)[None])
-
-
-def alpha_bound_prior(u0, e0, prop, e1, eps, ridge, la, beta, prior):
-    """test_temper_gpu.alpha_bound_tempered with the prior's float64 terms inside the perturbed function: what one float32
-    ulp of every evaluated input (ln L, each gradient component, each Fisher entry, at both points) moves log alpha by,
-    to first order, summed in magnitude"""
-    d = u0.shape[1]
-
-    def moved(e):
-        with np.errstate(invalid="ignore"):
-            a = alpha_of(u0, posterior_eval(e[0], u0, beta, prior), prop, posterior_eval(e[1], prop, beta, prior), eps, ridge)
-            return np.abs(np.nan_to_num(a - la, nan=0.0, posinf=0.0, neginf=0.0))
-    bound = tr.tmul(beta, ulp32(e0[0]) + ulp32(e1[0]))
-    for side in (0, 1):
-        for j in range(d):
-            e = [[a.copy() for a in e0], [a.copy() for a in e1]]
-            e[side][1][:, j] += ulp32(e[side][1][:, j])
-            bound += moved(e)
-            for k in range(j, d):
-                e = [[a.copy() for a in e0], [a.copy() for a in e1]]
-                h = ulp32(e[side][2][:, j, k])
-                e[side][2][:, j, k] += h
-                if k != j:
-                    e[side][2][:, k, j] += h
-                bound += moved(e)
-    return bound
-
-
 def langevin_transition(st, nat, tin, x0, prec, prior, betas, tag):
     """one transition of sample (betas None) or sample_tempered under the record, rebuilt as
     test_temper_gpu.test_one_tempered_transition_against_reference rebuilds it: the proposal within one float32 ulp + 1e-12,
@@ -134,7 +78,7 @@ def langevin_transition(st, nat, tin, x0, prec, prior, betas, tag):
     n, d = x0.shape
     T = 1 if betas is None else len(betas)
     beta = np.ones(n) if betas is None else np.asarray(betas)[np.arange(n) % T]
-    flags = flags_all(nat)
+    flags = flags_of(nat, True)
     seed, chain0, step0, eps0, ridge = sc.SEED, sc.CHAIN0, sc.STEP0, sc.EPS0, sc.RIDGE
     u0 = st.sample(x0, prec, flags, n_steps=0, n_warmup=0, diagnostics=True)["last_prop_u"].astype(np.float64)
     opts = dict(n_steps=1, n_warmup=0, eps0=eps0, ridge=ridge, seed=seed, chain0=chain0, step0=step0, diagnostics=True)
@@ -178,7 +122,7 @@ def test_one_mala_transition_against_reference(ctx, which, prec):
     """3 rows (a partial workgroup) and 257 (a second one) under the mixed record"""
     nat = pkg("_native")
     st, tin, truth = setup(ctx, which)
-    prior = pc.mixed_prior(len(truth))
+    prior = ic.mixed_prior(len(truth))
     for n in (3, 257):
         langevin_transition(st, nat, tin, untransform(near(truth, n, 5, 0.03), tin), prec, prior, None, "MALA %s %s n=%d" % (which, prec, n))
     st.set_likelihood(None, None)
@@ -190,7 +134,7 @@ def test_one_tempered_transition_against_reference(ctx, which, prec):
     terms enter unscaled, also at beta = 0"""
     nat = pkg("_native")
     st, tin, truth = setup(ctx, which)
-    prior = pc.mixed_prior(len(truth))
+    prior = ic.mixed_prior(len(truth))
     for ladders in (2, 86):
         x0 = untransform(near(truth, 3 * ladders, 5, 0.03), tin)
         langevin_transition(st, nat, tin, x0, prec, prior, BETAS3, "tempered %s %s ladders=%d" % (which, prec, ladders))
@@ -207,15 +151,15 @@ def test_one_ensemble_sweep_against_reference(ctx, which, prec):
     st, tin, truth = setup(ctx, which)
     ready(st, prec)
     d = len(truth)
-    prior = pc.mixed_prior(d)
+    prior = ic.mixed_prior(d)
     a, W, E = 2.0, 16, 2
     n, H = W * E, W // 2
     seed, chain0, step0 = 100 + W, 11, 40
     lnl_of = lambda u: st.loglike_fwd(np.ascontiguousarray(u, np.float32), prec, nat.FWD_OUT_TRANSFORM)
     x0 = untransform(near(truth, n, W, SPREAD), tin)
-    u0 = st.sample_ensemble(x0, W, prec, flags_all(nat), n_steps=0, n_warmup=0, diagnostics=True)["last_prop_u"].astype(np.float64)
+    u0 = st.sample_ensemble(x0, W, prec, flags_of(nat, True), n_steps=0, n_warmup=0, diagnostics=True)["last_prop_u"].astype(np.float64)
     with prior_on(st, prior):
-        r = st.sample_ensemble(x0, W, prec, flags_all(nat), n_steps=1, n_warmup=0, a=a, seed=seed, chain0=chain0, step0=step0, diagnostics=True)
+        r = st.sample_ensemble(x0, W, prec, flags_of(nat, True), n_steps=1, n_warmup=0, a=a, seed=seed, chain0=chain0, step0=step0, diagnostics=True)
     e, h, _ = er.layout(n, W)
     z, k, logu = er.draws(seed, chain0 + np.arange(n), step0, a, H)
     acc_dev = r["accept_rate"] > 0.5
@@ -260,7 +204,7 @@ def test_nested_iterations_against_rebuild(ctx, which, prec, N):
     st, tin, truth = setup(ctx, which)
     ready(st, prec)
     d = len(truth)
-    prior = pc.mixed_prior(d)
+    prior = ic.mixed_prior(d)
     flags = nat.FWD_OUT_TRANSFORM
     lnl_of = lambda u: st.loglike_fwd(np.ascontiguousarray(u, np.float32), prec, flags)
     taken = taken_plain = 0.0
@@ -298,11 +242,11 @@ def test_flat_likelihood_mala(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
     st.set_likelihood(data[0], np.zeros(dims[-1], np.float32))
-    c = pc.FLAT_MALA
-    prior = pc.mixed_prior(c["d"])
+    c = ic.FLAT_MALA
+    prior = ic.mixed_prior(c["d"])
     with prior_on(st, prior):
-        r = st.sample(untransform(pc.flat_starts(c["d"], c["chains"], 4), tin), "f32", flags_all(nat), **c["opts"])
-    zm, zv = pc.moment_z(r["mean_u"], pc.second_moment(r), prior)
+        r = st.sample(untransform(ic.flat_starts(c["d"], c["chains"], 4), tin), "f32", flags_of(nat, True), **c["opts"])
+    zm, zv = ic.moment_z(r["mean_u"], ic.second_moment(r), prior)
     print("MALA: accept %.3f, z mean %s second moment %s" % (r["accept_rate"].mean(), zm.round(2), zv.round(2)))
     assert np.all(r["lnl_last"] == 0) and np.all(zm < N_SE) and np.all(zv < N_SE), (zm, zv)
     st.set_likelihood(None, None)
@@ -314,14 +258,14 @@ def test_flat_likelihood_tempered(ctx):
     nat = pkg("_native")
     st, p, tin = small_setup(ctx, "i2")
     st.set_likelihood(p["data"], np.zeros(p["dims"][-1], np.float32))
-    c = pc.FLAT_TEMPER
-    prior = pc.mixed_prior(c["d"])
-    x0 = untransform(np.repeat(pc.flat_starts(c["d"], c["ladders"], 4), 3, axis=0), tin)
+    c = ic.FLAT_TEMPER
+    prior = ic.mixed_prior(c["d"])
+    x0 = untransform(np.repeat(ic.flat_starts(c["d"], c["ladders"], 4), 3, axis=0), tin)
     with prior_on(st, prior):
-        r = st.sample_tempered(x0, 3, BETAS3, c["swap_every"], "f32", flags_all(nat), **c["opts"])
+        r = st.sample_tempered(x0, 3, BETAS3, c["swap_every"], "f32", flags_of(nat, True), **c["opts"])
     assert np.all(r["mean_lnl"] == 0) and np.all(r["lnl_last"] == 0)
     for k in range(3):
-        zm, zv = pc.moment_z(r["mean_u"][k::3], pc.second_moment(r)[k::3], prior)
+        zm, zv = ic.moment_z(r["mean_u"][k::3], ic.second_moment(r)[k::3], prior)
         print("tempered rung %d: accept %.3f, z mean %s second moment %s" % (k, r["accept_rate"][k::3].mean(), zm.round(2), zv.round(2)))
         assert np.all(zm < N_SE) and np.all(zv < N_SE), (k, zm, zv)
     st.set_likelihood(None, None)
@@ -332,12 +276,12 @@ def test_flat_likelihood_ensemble(ctx):
     nat = pkg("_native")
     st, rec, prob, flags = shape_setup(ctx, "i4o65")
     st.set_likelihood(prob["data"][0], np.zeros(65, np.float32))
-    c = pc.FLAT_ENSEMBLE
-    prior = pc.mixed_prior(c["d"])
-    x0 = untransform(pc.flat_starts(c["d"], c["W"] * c["ensembles"], 4), rec["tin"])
+    c = ic.FLAT_ENSEMBLE
+    prior = ic.mixed_prior(c["d"])
+    x0 = untransform(ic.flat_starts(c["d"], c["W"] * c["ensembles"], 4), rec["tin"])
     with prior_on(st, prior):
         r = st.sample_ensemble(x0, c["W"], "f32", flags, **c["opts"])
-    zm, zv = pc.moment_z(*er.ensemble_estimates(r["mean_u"], r["cov_u"], c["W"]), prior)
+    zm, zv = ic.moment_z(*er.ensemble_estimates(r["mean_u"], r["cov_u"], c["W"]), prior)
     print("ensemble: accept %.3f, z mean %s second moment %s" % (r["accept_rate"].mean(), zm.round(2), zv.round(2)))
     assert np.all(r["lnl_last"] == 0) and np.all(zm < N_SE) and np.all(zv < N_SE), (zm, zv)
     st.set_likelihood(None, None)
@@ -352,7 +296,7 @@ def test_flat_likelihood_nested(ctx, which, prec, N, runs):
     st, tin, truth = setup(ctx, which)
     d = len(truth)
     st.set_likelihood(np.zeros(st.dims[-1], np.float32), np.zeros(st.dims[-1], np.float32))
-    prior = pc.mixed_prior(d)
+    prior = ic.mixed_prior(d)
     with prior_on(st, prior):
         r = st.sample_nested(None, N * runs, N, prec, nat.FWD_OUT_TRANSFORM, n_iter=3, seed=3, diagnostics=True)
     plain = st.sample_nested(None, N * runs, N, prec, nat.FWD_OUT_TRANSFORM, n_iter=3, seed=3)
@@ -373,20 +317,20 @@ def test_flat_likelihood_nested(ctx, which, prec, N, runs):
 # ---- 3. the evidence
 @pytest.mark.parametrize("name", ["i1", "i2"])
 def test_evidence_tempered(ctx, name):
-    """test_temper_gpu.test_evidence_against_quadrature's problems, ladder and run under test_prior_cpu.evidence_prior: ln Z
+    """test_temper_gpu.test_evidence_against_quadrature's problems, ladder and run under infer_cases.evidence_prior: ln Z
     within 5 standard errors (the scatter over the 64 ladders) of the quadrature of L p over the box and of the trapezoid
     of the quadrature's E_beta[ln L], within 5 (both errors) of prior_ref.temper_ref at the same seeds, and more than 5 away
     from the uniform prior's evidence"""
     nat = pkg("_native")
     st, p, tin = small_setup(ctx, name)
-    lz_q, lz_flat, E_q = pc.evidence_quadrature(name)
-    with prior_on(st, pc.evidence_prior(name)):
-        r = st.sample_tempered(untransform(p["starts_u"], tin), tc.RUNGS, tc.BETAS, tc.SWAP_EVERY, "f32", flags_all(nat), **tc.RUN)
-    lz, se = pc.ladder_lz(r["mean_lnl"])
-    lz_r, se_r = pc.ladder_lz(pc.tempered_reference(name)["mean_lnl"])
+    lz_q, lz_flat, E_q = ic.evidence_quadrature(name)
+    with prior_on(st, ic.evidence_prior(name)):
+        r = st.sample_tempered(untransform(p["starts_u"], tin), ic.RUNGS, ic.BETAS, ic.SWAP_EVERY, "f32", flags_of(nat, True), **ic.RUN)
+    lz, se = ic.ladder_lz(r["mean_lnl"])
+    lz_r, se_r = ic.ladder_lz(ic.tempered_reference(name)["mean_lnl"])
     print("%s tempered: ln Z %.4f +- %.4f; quadrature %.4f (z %+.2f), its trapezoid z %+.2f; reference %.4f +- %.4f (z %+.2f); uniform prior %.4f"
-          % (name, lz, se, lz_q, (lz - lz_q) / se, (lz - tr.trapezoid(tc.BETAS, E_q)) / se, lz_r, se_r, (lz - lz_r) / np.hypot(se, se_r), lz_flat))
-    assert abs(lz - lz_q) < N_SE * se and abs(lz - tr.trapezoid(tc.BETAS, E_q)) < N_SE * se
+          % (name, lz, se, lz_q, (lz - lz_q) / se, (lz - tr.trapezoid(ic.BETAS, E_q)) / se, lz_r, se_r, (lz - lz_r) / np.hypot(se, se_r), lz_flat))
+    assert abs(lz - lz_q) < N_SE * se and abs(lz - tr.trapezoid(ic.BETAS, E_q)) < N_SE * se
     assert abs(lz - lz_r) < N_SE * np.hypot(se, se_r)
     assert abs(lz - lz_flat) > N_SE * se
     st.set_likelihood(None, None)
@@ -398,12 +342,12 @@ def test_evidence_nested(ctx, name):
     the device: the same four bounds"""
     nat, em = pkg("_native"), pkg("emulator")
     st, p, tin = small_setup(ctx, name)
-    N, T = ncpu.QUAD[name]
-    lz_q, lz_flat, _ = pc.evidence_quadrature(name)
-    with prior_on(st, pc.evidence_prior(name)):
-        r = st.sample_nested(None, ncpu.RUNS * N, N, "f32", nat.FWD_OUT_TRANSFORM, n_iter=T, seed=ncpu.SEED)
-    lz = em.nested_evidence(r["dead_lnl"].transpose(1, 0, 2), r["live_lnl"].reshape(ncpu.RUNS, N), N)[0]
-    lz_ref = pc.nested_reference(name)[1]
+    N, T = ic.QUAD[name]
+    lz_q, lz_flat, _ = ic.evidence_quadrature(name)
+    with prior_on(st, ic.evidence_prior(name)):
+        r = st.sample_nested(None, ic.RUNS * N, N, "f32", nat.FWD_OUT_TRANSFORM, n_iter=T, seed=ic.SEED)
+    lz = em.nested_evidence(r["dead_lnl"].transpose(1, 0, 2), r["live_lnl"].reshape(ic.RUNS, N), N)[0]
+    lz_ref = ic.nested_reference(name)[1]
     se, se_r = lz.std(ddof=1) / 8, lz_ref.std(ddof=1) / 8
     print("%s nested: ln Z %.4f +- %.4f; quadrature %.4f (z %+.2f); reference %.4f +- %.4f (z %+.2f); uniform prior %.4f; accept %.2f"
           % (name, lz.mean(), se, lz_q, (lz.mean() - lz_q) / se, lz_ref.mean(), se_r, (lz.mean() - lz_ref.mean()) / np.hypot(se, se_r), lz_flat,
@@ -432,10 +376,10 @@ def test_nothing_moves_without_a_record(ctx, which, prec):
     nat = pkg("_native")
     st, tin, truth = setup(ctx, which)
     d = len(truth)
-    flags = flags_all(nat)
+    flags = flags_of(nat, True)
     u0 = near(truth, 48, 3, SPREAD)
     x0 = untransform(u0, tin)
-    prior = pc.mixed_prior(d)
+    prior = ic.mixed_prior(d)
     none = sampler_calls(st, nat, x0, u0, prec, flags)
     others = lambda: {"loglike": st.loglike(x0, prec, flags), "loglike_fwd": st.loglike_fwd(x0, prec, flags),
                       "fisher": st.fisher(x0, prec, flags, lnl=True, grad=True), "fit": st.fit(x0, prec, flags, max_iter=5)}
@@ -471,7 +415,7 @@ def test_chunks_and_continuation(ctx):
     two equals the whole for the plain, the ensemble and the nested sampler too"""
     nat = pkg("_native")
     st, rec, prob, flags = shape_setup(ctx, "i4o65")
-    prior = pc.mixed_prior(4)
+    prior = ic.mixed_prior(4)
     T, n, betas = 3, 8220, [1.0, 0.3, 0.0]
     x64 = np.ascontiguousarray(np.tile(starts_in_box(rec, prob, 30, 12, 0.2), (n // 30, 1)))
     x32 = np.ascontiguousarray(x64.astype(np.float32))
@@ -522,7 +466,7 @@ def test_argument_errors_leave_the_handle_usable(ctx):
     def call(kind, mu, sd, n=None):
         k, m, s = np.asarray(kind, np.int32), np.asarray(mu, np.float64), np.asarray(sd, np.float64)
         return lib.v21_mlp_set_prior(st.h, k.ctypes.data_as(I), m.ctypes.data_as(D), s.ctypes.data_as(D), len(k) if n is None else n)
-    kind, mu, sd = pc.mixed_prior(4)
+    kind, mu, sd = ic.mixed_prior(4)
     try:
         assert call(kind, mu, sd) == 0
         before = run()

@@ -8,64 +8,12 @@ import numpy as np
 import pytest
 
 import fit_ref as fr
-import jacobian_ref as jr
 import sample_ref as sr
 from conftest import pkg
-from test_fit_gpu import fit_setup, u_of
-from test_jacobian_gpu import stack_of
+from infer_cases import N_SE
+from infer_support import alpha_bound, alpha_of, between_chain, device_eval, fit_setup, flags_of, run_dev, same, starts_near, u_of
 
 pytestmark = pytest.mark.gpu
-
-N_SE = 5.0
-
-
-def flags_of(nat):
-    return nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM
-
-
-def starts_near(truth, tin, n, seed, scale=0.03):
-    """n raw float64 starts: the truth jittered by `scale` in u, inside the box"""
-    u = np.clip(u_of(truth[None, :], tin) + scale * np.random.default_rng(seed).normal(size=(n, 7)), -0.999, 0.999)
-    return fr.untransform(u, tin[0], tin[2], tin[3])
-
-
-def device_eval(st, nat, u, prec):
-    """the device's own ln L, gradient and Fisher matrix at float32 points u (no input transform), as float64"""
-    F, lnl, g = st.fisher(np.ascontiguousarray(u, np.float32), prec, nat.FWD_OUT_TRANSFORM, lnl=True, grad=True)
-    return lnl.astype(np.float64), g.astype(np.float64), F.astype(np.float64)
-
-
-def alpha_of(u0, e0, prop, e1, eps, ridge):
-    """log alpha in float64 of the move u0 -> prop from the evaluations e = (lnl, g, F) at both"""
-    L0, ok0 = sr.factor(e0[2], ridge)
-    mu0, ld0 = sr.drift(L0, u0, e0[1], eps)
-    inside = ok0 & np.all(np.abs(prop) <= 1.0, axis=1)
-    return sr.log_alpha(u0, e0[0], sr.logq(L0, mu0, ld0, prop, eps), inside, prop, e1[0], e1[1], e1[2], eps, ridge)
-
-
-def alpha_bound(u0, e0, prop, e1, eps, ridge, la):
-    """what one float32 ulp of every input (ln L, each gradient component, each Fisher entry, at both points) moves log
-    alpha by, to first order, summed in magnitude: the inputs are float32 numbers, the formula is float64"""
-    ulp = lambda a: np.spacing(np.abs(a).astype(np.float32)).astype(np.float64)
-    bound = ulp(e0[0]) + ulp(e1[0])
-    d = u0.shape[1]
-
-    def moved(e):
-        with np.errstate(invalid="ignore"):  # (-inf - -inf: a rejected proposal stays rejected)
-            return np.abs(np.nan_to_num(alpha_of(u0, e[0], prop, e[1], eps, ridge) - la, nan=0.0, posinf=0.0, neginf=0.0))
-    for side in (0, 1):
-        for j in range(d):
-            e = [[a.copy() for a in e0], [a.copy() for a in e1]]
-            e[side][1][:, j] += ulp(e[side][1][:, j])
-            bound += moved(e)
-            for k in range(j, d):
-                e = [[a.copy() for a in e0], [a.copy() for a in e1]]
-                h = ulp(e[side][2][:, j, k])
-                e[side][2][:, j, k] += h
-                if k != j:
-                    e[side][2][:, k, j] += h
-                bound += moved(e)
-    return bound
 
 
 @pytest.mark.parametrize("prec", ["f32", "f16", "bf16"])
@@ -81,9 +29,9 @@ def test_one_transition_against_reference(ctx, name, prec):
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx, name)
     n, seed, chain0, step0, eps0, ridge = 4096, 1234, 7, 40, 0.7, 1.0
     x0 = starts_near(truths[0], tin, n, 5)
-    u0 = st.sample(x0, prec, flags_of(nat), n_steps=0, n_warmup=0, diagnostics=True)["last_prop_u"].astype(np.float64)
+    u0 = st.sample(x0, prec, flags_of(nat, True), n_steps=0, n_warmup=0, diagnostics=True)["last_prop_u"].astype(np.float64)
     assert np.max(np.abs(u0 - u_of(x0, tin))) <= 2.0 ** -23  # the start as the device holds it: float32 of the float64 transform
-    r = st.sample(x0, prec, flags_of(nat), n_steps=1, n_warmup=0, eps0=eps0, ridge=ridge, seed=seed, chain0=chain0, step0=step0,
+    r = st.sample(x0, prec, flags_of(nat, True), n_steps=1, n_warmup=0, eps0=eps0, ridge=ridge, seed=seed, chain0=chain0, step0=step0,
                   diagnostics=True)
     e0 = device_eval(st, nat, u0, prec)
     chains, eps = chain0 + np.arange(n), np.full(n, eps0)
@@ -115,7 +63,7 @@ def test_one_transition_against_reference(ctx, name, prec):
     st.set_likelihood(None, None)
 
 
-def dev_sample(ctx, st, x0, data_rows, prec, flags, keys=("x_last", "lnl_last", "samples", "mean_u"), **opts):
+def dev_sample(ctx, st, x0, data_rows, prec, flags, keys=("x_last", "lnl_last", "samples", "mean_u"), guard=0, **opts):
     """v21_mlp_sample_dev on float32 starts -> dict of host arrays"""
     n, din = x0.shape
     o = st.sample_opts(**opts)
@@ -123,36 +71,14 @@ def dev_sample(ctx, st, x0, data_rows, prec, flags, keys=("x_last", "lnl_last", 
     shapes = {"x_last": ((n, din), np.float32), "lnl_last": ((n,), np.float32), "samples": ((n, keep, din), np.float32),
               "samples_lnl": ((n, keep), np.float32), "mean_u": ((n, din), np.float64), "cov_u": ((n, din, din), np.float64),
               "eps_last": ((n,), np.float64), "accept_rate": ((n,), np.float64)}
-    host = {k: np.empty(*shapes[k]) for k in keys}
-    bufs = []
-    try:
-        dx, dd = ctx.malloc(x0.nbytes), ctx.malloc(data_rows.nbytes)
-        bufs += [dx, dd]
-        out = {}
-        for k, a in host.items():
-            out[k] = ctx.malloc(max(a.nbytes, 8))
-            bufs.append(out[k])
-        ctx.h2d(dx, x0)
-        ctx.h2d(dd, data_rows)
-        st.sample_dev(dx, din, n, dd, data_rows.shape[0], out, None, prec, flags, **opts)
-        ctx.sync()
-        for k, a in host.items():
-            if a.nbytes:
-                ctx.d2h(a, out[k])
-    finally:
-        for p in bufs:
-            ctx.free(p)
-    return host
-
-
-def same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+    call = lambda dx, dd, out: st.sample_dev(dx, din, n, dd, data_rows.shape[0], out, None, prec, flags, **opts)
+    return run_dev(ctx, shapes, keys, call, x0, data_rows, guard)
 
 
 def test_reproducible_and_chunk_independent(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_of(nat)
+    flags = flags_of(nat, True)
     opts = dict(n_steps=6, n_warmup=4, thin=2, seed=99, eps0=0.8)
     keys = ("x_last", "lnl_last", "eps_last", "accept_rate", "mean_u", "cov_u", "samples", "samples_lnl")
     x12 = starts_near(truths[0], tin, 12, 21)
@@ -194,12 +120,6 @@ def test_reproducible_and_chunk_independent(ctx):
     st.set_likelihood(None, None)
 
 
-def between_chain(a):
-    """(pooled value, squared standard error) of per-chain estimates (chains, ...)"""
-    a = np.asarray(a, np.float64)
-    return a.mean(axis=0), a.var(axis=0, ddof=1) / a.shape[0]
-
-
 def test_statistics_against_reference_sampler(ctx):
     """NB, f32, the likelihood of fit_setup (sigma = 0.02 std: on the CPU the reference's two half-ensembles of 512 chains
     agree within 1.1 standard errors in the mean and 3.4 in the worst of the 49 covariance entries, and it accepts 0.578
@@ -208,7 +128,7 @@ def test_statistics_against_reference_sampler(ctx):
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx, "NB")
     opts = dict(n_steps=200, n_warmup=100, seed=11)
     x0 = starts_near(truths[0], tin, 4096, 1, scale=0.01)
-    r = st.sample(x0, "f32", flags_of(nat), thin=0, **opts)
+    r = st.sample(x0, "f32", flags_of(nat, True), thin=0, **opts)
     assert "samples" not in r and np.all(np.isfinite(r["mean_u"])) and np.all(np.isfinite(r["cov_u"]))
     ev = sr.evaluator_batch(Ws, bs, act, data[0], w, tout)
     ref = sr.sample_ref(ev, u_of(x0[:1024], tin), thin=0, **opts)
@@ -235,7 +155,7 @@ def test_uniform_target_on_the_device(ctx):
     u0 = np.random.default_rng(4).uniform(-1, 1, size=(n, 7))
     x0 = fr.untransform(u0, tin[0], tin[2], tin[3])
     opts = dict(n_steps=600, n_warmup=150, seed=5)
-    r = st.sample(x0, "f32", flags_of(nat), thin=3, **opts)
+    r = st.sample(x0, "f32", flags_of(nat, True), thin=3, **opts)
     assert all(np.all(np.isfinite(r[k])) for k in r)
     acc = r["accept_rate"].mean()
     assert 0 < acc < 1 and np.all(r["lnl_last"] == 0)
@@ -247,13 +167,13 @@ def test_uniform_target_on_the_device(ctx):
     assert np.all(np.abs(us) <= 1 + 1e-12)
     # the moments of every transition (thin = 1, float64 samples) recomputed from the stored samples
     n1 = 64
-    r1 = st.sample(x0[:n1], "f32", flags_of(nat), thin=1, **opts)
+    r1 = st.sample(x0[:n1], "f32", flags_of(nat, True), thin=1, **opts)
     u1 = u_of(r1["samples"].reshape(-1, 7), tin).reshape(n1, 600, 7)
     np.testing.assert_allclose(r1["mean_u"], u1.mean(axis=1), atol=1e-13)
     np.testing.assert_allclose(r1["cov_u"], np.einsum("nki,nkj->nij", u1, u1) / 600 - np.einsum("ni,nj->nij", u1.mean(axis=1), u1.mean(axis=1)),
                                atol=1e-13)
     # thin does not change the chain: the same moments with thin = 3 and with no sample buffer at all
-    r0 = st.sample(x0[:n1], "f32", flags_of(nat), thin=0, **opts)
+    r0 = st.sample(x0[:n1], "f32", flags_of(nat, True), thin=0, **opts)
     assert "samples" not in r0
     for k in ("mean_u", "cov_u", "accept_rate", "x_last", "eps_last"):
         assert same(r0[k], r1[k]) and same(r0[k], r[k][:n1]), k
@@ -264,7 +184,7 @@ def test_uniform_target_on_the_device(ctx):
 def test_edge_cases(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_of(nat)
+    flags = flags_of(nat, True)
     x0 = pkg("synth").make_params(4, seed=30, zero_fx_frac=0)
     # n = 1
     r = st.sample(x0[:1], "f32", flags, data=data[:1], n_steps=5, n_warmup=5)
@@ -299,7 +219,7 @@ def test_edge_cases(ctx):
 def test_argument_errors_and_routes_counted(ctx):
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_of(nat)
+    flags = flags_of(nat, True)
     lib, F, P = st.lib, C.POINTER(C.c_float), C.c_void_p
     n = 6
     x0 = np.ascontiguousarray(pkg("synth").make_params(n, seed=40, zero_fx_frac=0).astype(np.float32))

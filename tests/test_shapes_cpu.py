@@ -10,7 +10,7 @@ import jacobian_ref as jr
 import marg_ref as mr
 import sample_ref as sr
 import shape_cases as sc
-from test_sample_gpu import alpha_bound, alpha_of
+from infer_support import alpha_bound, alpha_of
 
 IDS = [c.name for c in sc.CASES]
 FIT_CASES = [c for c in sc.CASES if c.fit]
@@ -149,7 +149,7 @@ def test_normals_at_every_in_dim(din):
 def test_one_transition_is_self_consistent_and_inside_the_caps(case):
     """the transition test_shapes_gpu rebuilds, on float64 evaluations rounded to float32: log q of the proposal is the
     density of the normals that drew it, the reverse move's log alpha is the negative of the forward's, and the share of
-    accept decisions the first-order bound (test_sample_gpu.alpha_bound) excuses stays under its cap of 0.5 % --
+    accept decisions the first-order bound (infer_support.alpha_bound) excuses stays under its cap of 0.5 % --
     reference figures: 0 of 384 at in_dim 1, 4, 5 and 8; every proposal inside the box; 0.97, 0.87, 0.84, 0.78 accepted."""
     prob = sc.fit_problem(case)
     din = case.dims[0]

@@ -2,8 +2,8 @@
 the jac_reduce_kernel<8 / 15, 0 / 4 / 8, with / without F> instantiations and nuis_project_kernel, fit_lm_kernel and the sample_*
 kernels, each against its float64 reference (jacobian_ref, fit_ref, marg_ref, sample_ref) at in_dim 1 .. 17 and out_dim
 1 .. 451, the 65,535-row launch split of the generic route and the documented refusals.  Every bound is the one the
-project already uses for the same quantity (check_rows, test_loglike, test_fisher_against_own_jacobian, check_reduction,
-test_fit_against_lm_ref, alpha_bound), imported or quoted; every test prints the fraction of its bound it used."""
+project already uses for the same quantity (infer_support.check_rows, check_reduction and alpha_bound, imported; test_loglike,
+test_fisher_against_own_jacobian and test_fit_against_lm_ref, quoted); every test prints the fraction of its bound it used."""
 import ctypes as C
 
 import numpy as np
@@ -14,35 +14,11 @@ import jacobian_ref as jr
 import sample_ref as sr
 import shape_cases as sc
 from conftest import pkg
-from test_jacobian_gpu import check_rows
-from test_marg_gpu import check_reduction, reference
-from test_sample_gpu import alpha_bound, alpha_of, device_eval, same
+from infer_support import POISON, alpha_bound, alpha_of, check_reduction, check_rows, device_eval, device_stack, flags_of, reference, same
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED, STATE, ARG = -3, -4, -1
-POISON = np.frombuffer(b"\x7f\x7f\x7f\x7f", np.uint32)[0]
-_dev = {}
-
-
-def device_stack(ctx, dims, act):
-    """the handle of a stack of the table with its transforms set (no input transform above 8 inputs), and its host record"""
-    key = (tuple(dims), tuple(act))
-    if key not in _dev:
-        nat = pkg("_native")
-        rec = sc.make_stack(dims, act)
-        st = nat.Stack(ctx, dims, act)
-        st.set_weights(rec["flat"])
-        if rec["tin"] is not None:
-            st.set_input_transform(*rec["tin"])
-        st.set_output_transform(rec["tout"][0], rec["tout"][1].astype(np.float32))
-        _dev[key] = st
-    _dev[key].set_likelihood(None, None)  # (no record of an earlier test, should that one have failed half way)
-    return _dev[key], sc.make_stack(dims, act)
-
-
-def flags_of(nat, rec):
-    return (nat.FWD_IN_TRANSFORM if rec["tin"] is not None else 0) | nat.FWD_OUT_TRANSFORM
 
 
 def status_of(call):
@@ -138,7 +114,7 @@ def test_likelihood_mode_of_the_generic_kernel(ctx):
     worst = {"lnl": 0.0, "grad": 0.0}
     for i, case in enumerate(sc.CASES):
         st, rec = device_stack(ctx, case.dims, case.act)
-        flags = flags_of(nat, rec)
+        flags = flags_of(nat, rec["tin"] is not None)
         data, w, w64 = likelihood(rec, 1)
         st.set_likelihood(data, w)
         for n in (5, sc.ROWS[i % len(sc.ROWS)]):
@@ -179,7 +155,7 @@ def test_fisher_lnl_and_gradient(ctx):
     for i, case in enumerate(c for c in sc.CASES if c.dims[0] <= 15):
         st, rec = device_stack(ctx, case.dims, case.act)
         din = case.dims[0]
-        flags = flags_of(nat, rec)
+        flags = flags_of(nat, rec["tin"] is not None)
         data, w, w64 = likelihood(rec, 2)
         st.set_likelihood(data, w)
         for n in (5, sc.ROWS[i % len(sc.ROWS)]):
@@ -210,7 +186,7 @@ def test_in_dim_limits(ctx):
     # 16 inputs: the Jacobian and loglike only
     case = sc.BY_NAME["i16o3"]
     st, rec = device_stack(ctx, case.dims, case.act)
-    flags = flags_of(nat, rec)
+    flags = flags_of(nat, rec["tin"] is not None)
     data, w, w64 = likelihood(rec, 1, 1)
     st.set_likelihood(data, w)
     x = sc.rows(case.dims, 5, 1)
@@ -236,7 +212,7 @@ def test_in_dim_limits(ctx):
     st.set_likelihood(data, w)
     x = sc.rows(case.dims, 5, 1)
     assert c_fit(st, x) == UNSUPPORTED and c_sample(st, x) == UNSUPPORTED
-    assert np.all(np.isfinite(st.fisher(x, "f32", flags_of(nat, rec))))
+    assert np.all(np.isfinite(st.fisher(x, "f32", flags_of(nat, rec["tin"] is not None))))
     st.set_likelihood(None, None)
 
 
@@ -246,7 +222,7 @@ def test_a_layer_too_wide_for_the_lds_is_refused(ctx):
     nat = pkg("_native")
     dims, act = sc.TOO_WIDE
     st, rec = device_stack(ctx, dims, act)
-    flags = flags_of(nat, rec)
+    flags = flags_of(nat, rec["tin"] is not None)
     x = sc.rows(dims, 3, 1)
     y0 = st.forward(x, "f32", flags)
     np.testing.assert_allclose(y0, jr.oracle_outputs(rec["Ws"], rec["bs"], act, x, rec["tin"], rec["tout"]), rtol=1e-5, atol=2e-5 * sc.OUT_STD)
@@ -268,7 +244,7 @@ def test_a_layer_too_wide_for_the_lds_is_refused(ctx):
 def test_marginalised_reductions(ctx):
     """the eight jac_reduce_kernel<8 | 15, 4 | 8, with / without F> instantiations over the table's out_dim and K in {1, 4, 5,
     8}: fisher, loglike and nuisance_coef against marg_ref fed the device's own y and J, bounds and scales of
-    test_marg_gpu.check_reduction; clearing the record restores the earlier bits; a basis on fewer than K + 1 live bins
+    infer_support.check_reduction; clearing the record restores the earlier bits; a basis on fewer than K + 1 live bins
     is refused and leaves the handle as it was.  Measured worst on the MI355X, as fractions of the scales: F 1.6e-7, lnl
     5.8e-8, grad 1.2e-7 (bounds 1e-5); the amplitudes at 0.012 of their bound."""
     nat = pkg("_native")
@@ -276,7 +252,7 @@ def test_marginalised_reductions(ctx):
     for i, case in enumerate(c for c in sc.CASES if c.modes):
         st, rec = device_stack(ctx, case.dims, case.act)
         din, dout = case.dims[0], case.dims[-1]
-        flags = flags_of(nat, rec)
+        flags = flags_of(nat, rec["tin"] is not None)
         for K in case.modes:
             data, w, w64 = likelihood(rec, 3, K)
             st.set_likelihood(data, w)
@@ -312,7 +288,7 @@ def test_marginalised_reductions(ctx):
     for name, K in (("i1o1", 1), ("i2o1", 1), ("i4o3", 4)):
         case = sc.BY_NAME[name]
         st, rec = device_stack(ctx, case.dims, case.act)
-        flags = flags_of(nat, rec)
+        flags = flags_of(nat, rec["tin"] is not None)
         data, w, _ = likelihood(rec, 3)
         st.set_likelihood(data, w)
         x = sc.rows(case.dims, 4, 2)
@@ -332,7 +308,7 @@ def test_foreground_scale_at_a_lane_tail(ctx):
     nat = pkg("_native")
     case = sc.BY_NAME["i4o65"]
     st, rec = device_stack(ctx, case.dims, case.act)
-    flags = flags_of(nat, rec)
+    flags = flags_of(nat, rec["tin"] is not None)
     prob = sc.fit_problem(case)
     w, K = prob["w"], 5
     A = sc.basis(65, K)
@@ -375,7 +351,7 @@ def test_fits(ctx, case):
     nat = pkg("_native")
     st, rec = device_stack(ctx, case.dims, case.act)
     tin, tout = rec["tin"], rec["tout"]
-    flags = flags_of(nat, rec)
+    flags = flags_of(nat, rec["tin"] is not None)
     prob = sc.fit_problem(case)
     data, w, x0 = prob["data"], prob["w"], prob["x0"]
     st.set_likelihood(data[0], w)
@@ -432,7 +408,7 @@ def test_sampler_transition(ctx, case):
     nat = pkg("_native")
     st, rec = device_stack(ctx, case.dims, case.act)
     tin = rec["tin"]
-    flags = flags_of(nat, rec)
+    flags = flags_of(nat, rec["tin"] is not None)
     din = case.dims[0]
     prob = sc.fit_problem(case)
     st.set_likelihood(prob["data"][0], prob["w"])
@@ -494,7 +470,7 @@ def test_launch_split_at_65535_rows(ctx):
     nat = pkg("_native")
     dims, act = sc.SPLIT
     st, rec = device_stack(ctx, dims, act)
-    flags = flags_of(nat, rec)
+    flags = flags_of(nat, rec["tin"] is not None)
     n, din, dout, g = sc.SPLIT_ROWS, 2, 3, 64
     data, w, w64 = likelihood(rec, 1)
     st.set_likelihood(data, w)
@@ -548,7 +524,7 @@ def test_guard_rows_of_fisher_and_fit(ctx):
         case = sc.BY_NAME[name]
         st, rec = device_stack(ctx, case.dims, case.act)
         din = case.dims[0]
-        flags = flags_of(nat, rec)
+        flags = flags_of(nat, rec["tin"] is not None)
         data, w, _ = likelihood(rec, 2)
         st.set_likelihood(data, w)
         x = sc.rows(case.dims, n, 6).astype(np.float32)

@@ -1,105 +1,15 @@
 """CPU: the parallel-tempered sampler's reference (tests/temper_ref.py) against grid quadrature -- the independent check of
 the algorithm that include/v21.h states for v21_mlp_sample_tempered -- and the host-only pieces of its Python surface.
-The problems, their constants and the quadrature are shared with tests/test_temper_gpu.py."""
+The problems, their constants and the quadrature live in tests/infer_cases.py, which tests/test_temper_gpu.py shares."""
 import numpy as np
 import pytest
 
-import jacobian_ref as jr
 import sample_ref as sr
 import shape_cases as sc
 import temper_ref as tr
 from conftest import pkg
-
-N_SE = 5.0  # tests/test_sample_gpu.py
-
-# The two quadrature problems: a 1-input stack of the table and a 2-input stack of the same make, one noisy spectrum of a
-# truth inside the box at SIGMA (in units of shape_cases.OUT_STD) on every bin.  Chosen on the reference: at SIGMA = 0.1,
-# data seed 17 and 200 + 600 transitions every |z| below stayed under 1.5 (at SIGMA = 0.05 and 200 + 400 the worst was 3.2).
-STACKS = {"i1": (sc.BY_NAME["i1o63"].dims, sc.BY_NAME["i1o63"].act), "i2": ([2, 16, 63], [sc.RELU, sc.LINEAR])}
-SIGMA, DATA_SEED = 0.1, 17
-LADDERS, RUNGS = 64, 8
-BETAS = ((RUNGS - 1.0 - np.arange(RUNGS)) / (RUNGS - 1.0)) ** 5
-RUN = dict(n_steps=600, n_warmup=200, thin=0, seed=3)
-SWAP_EVERY = 5
-GRID = {"i1": 16384, "i2": 1024}  # cells per axis of the midpoint rule (and half of it, for the convergence check)
-
-# the swap test: (rungs, ladders) -- 666, 513, 515 and 288 rows, a partial last workgroup at every T -- on i4o65 from
-# starts scattered over the box, ladders evenly spaced in beta
-SWAP_CASES = [(2, 333), (3, 171), (5, 103), (32, 9)]
-SWAP_SEED = 11
-
-_problems, _quad = {}, {}
-
-
-def swap_betas(T):
-    return np.linspace(1.0, 0.0, T)
-
-
-def scattered_u(d, n, seed):
-    """n starts uniform in [-0.9, 0.9]^d"""
-    return np.random.default_rng(seed).uniform(-0.9, 0.9, size=(n, d))
-
-
-def problem(name):
-    """-> dict dims, act, stack (shape_cases.make_stack), truth_u (d,), data float32 (out,), w float32 (out,), ev: the
-    float64 evaluator u (n, d) -> (lnl, g, F) of sample_ref, starts_u (LADDERS RUNGS, d): every rung of a ladder at its
-    ladder's start, the truth jittered by 0.02"""
-    if name not in _problems:
-        dims, act = STACKS[name]
-        st = sc.make_stack(dims, act)
-        rng = np.random.default_rng(DATA_SEED)
-        tu = rng.uniform(-0.5, 0.5, size=(1, dims[0]))
-        y = jr.jvp(st["Ws"], st["bs"], st["act"], tu)[0][0] * st["tout"][0] + st["tout"][1]
-        sig = SIGMA * sc.OUT_STD
-        data = (y + rng.normal(size=y.shape) * sig).astype(np.float32)
-        w = np.full(dims[-1], 1.0 / sig ** 2, np.float32)
-        u0 = np.clip(tu + 0.02 * np.random.default_rng(1).normal(size=(LADDERS, dims[0])), -1.0, 1.0)
-        _problems[name] = {"dims": dims, "act": act, "stack": st, "truth_u": tu[0], "data": data, "w": w,
-                           "ev": sr.evaluator_batch(st["Ws"], st["bs"], st["act"], data, w, st["tout"]),
-                           "starts_u": np.repeat(u0, RUNGS, axis=0)}
-    return _problems[name]
-
-
-def lnl_grid(p, N):
-    """ln L of the float64 oracle at the midpoints of N^d equal cells of the box"""
-    st, d = p["stack"], p["dims"][0]
-    c = (np.arange(N) + 0.5) * (2.0 / N) - 1.0
-    pts = c[:, None] if d == 1 else np.stack(np.meshgrid(c, c, indexing="ij"), -1).reshape(-1, 2)
-    dat, w = p["data"].astype(np.float64), p["w"].astype(np.float64)
-    out = []
-    for i in range(0, len(pts), 65536):
-        y = jr.jvp(st["Ws"], st["bs"], st["act"], pts[i:i + 65536])[0] * st["tout"][0] + st["tout"][1]
-        out.append(-0.5 * np.sum(w * (dat - y) ** 2, axis=-1))
-    return np.concatenate(out)
-
-
-def expectations(lnl, betas):
-    """E_beta[ln L] = sum ln L L^beta / sum L^beta over equal cells, per beta"""
-    out = []
-    for b in betas:
-        a = b * lnl
-        wt = np.exp(a - a.max())
-        out.append(np.sum(wt * lnl) / np.sum(wt))
-    return np.array(out)
-
-
-def quadrature(name):
-    """-> (E_beta[ln L] at BETAS on the fine grid, the same on a grid of twice the spacing); computed once"""
-    if name not in _quad:
-        p = problem(name)
-        _quad[name] = (expectations(lnl_grid(p, GRID[name]), BETAS), expectations(lnl_grid(p, GRID[name] // 2), BETAS))
-    return _quad[name]
-
-
-def ladder_check(mean_lnl, name):
-    """per-row mean ln L (LADDERS RUNGS,) against the quadrature -> (z per rung, z of the trapezoid, standard errors per
-    rung): the standard error is the scatter over ladders, the trapezoid's that of the ladders' own trapezoids"""
-    q, _ = quadrature(name)
-    E = np.asarray(mean_lnl, np.float64).reshape(LADDERS, RUNGS)
-    se = E.std(axis=0, ddof=1) / np.sqrt(LADDERS)
-    lz = tr.trapezoid(BETAS, E)
-    z_lz = (lz.mean() - tr.trapezoid(BETAS, q)) / (lz.std(ddof=1) / np.sqrt(LADDERS))
-    return (E.mean(axis=0) - q) / se, z_lz, se
+from infer_cases import (BETAS, LADDERS, N_SE, RUN, RUNGS, SWAP_CASES, SWAP_EVERY, SWAP_SEED, ladder_check, problem, quadrature, scattered_u,
+                         swap_betas)
 
 
 @pytest.mark.parametrize("name", ["i1", "i2"])

@@ -9,42 +9,19 @@ import numpy as np
 import pytest
 
 import fit_ref as fr
-import jacobian_ref as jr
+import infer_cases as ic
 import sample_ref as sr
 import shape_cases as sc
 import temper_ref as tr
-import test_temper_cpu as tc
 from conftest import pkg
-from test_fit_gpu import fit_setup, u_of
-from test_sample_gpu import N_SE, alpha_of, between_chain, device_eval, same, starts_near
-from test_shapes_gpu import device_stack
+from infer_cases import N_SE
+from infer_support import (alpha_of, between_chain, dev_tempered, device_eval, device_stack, fit_setup, flags_of, same, shape_setup,
+                           starts_in_box, starts_near, u_of, ulp32)
 
 pytestmark = pytest.mark.gpu
 
 SAMPLE_KEYS = ("x_last", "lnl_last", "eps_last", "accept_rate", "mean_u", "cov_u", "samples", "samples_lnl", "last_prop_u", "last_log_alpha")
 LADDER4 = np.array([1.0, 0.5, 0.1, 0.0])
-
-
-def flags_all(nat):
-    return nat.FWD_IN_TRANSFORM | nat.FWD_OUT_TRANSFORM
-
-
-def shape_setup(ctx, name):
-    """a stack of shape_cases with its first fit problem as the record -> (stack handle, host record, problem, flags)"""
-    case = sc.BY_NAME[name]
-    st, rec = device_stack(ctx, case.dims, case.act)
-    prob = sc.fit_problem(case)
-    st.set_likelihood(prob["data"][0], prob["w"])
-    return st, rec, prob, flags_all(pkg("_native"))
-
-
-def starts_in_box(rec, prob, n, seed, scale):
-    """n raw float64 starts: the first truth jittered by `scale` in u (scale None: test_temper_cpu.scattered_u)"""
-    d = rec["dims"][0]
-    u = tc.scattered_u(d, n, seed) if scale is None else np.clip(prob["truths_u"][:1] + scale * np.random.default_rng(seed).normal(size=(n, d)),
-                                                                 -0.999, 0.999)
-    tin = rec["tin"]
-    return fr.untransform(u, tin[0], tin[2], tin[3])
 
 
 def plain_and_tempered_inputs(ctx, which, n):
@@ -53,7 +30,7 @@ def plain_and_tempered_inputs(ctx, which, n):
         st, rec, prob, flags = shape_setup(ctx, "i4o65")
         return st, "f32", flags, starts_in_box(rec, prob, n, 7, 0.03), "generic"
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    return st, "f16", flags_all(pkg("_native")), starts_near(truths[0], tin, n, 5), "fused"
+    return st, "f16", flags_of(pkg("_native"), True), starts_near(truths[0], tin, n, 5), "fused"
 
 
 @pytest.mark.parametrize("swap_every", [0, 3])
@@ -93,25 +70,24 @@ def tempered(e, beta):
 
 
 def alpha_bound_tempered(u0, e0, prop, e1, eps, ridge, la, beta):
-    """test_sample_gpu.alpha_bound with the beta-scaling inside the perturbed function: what one float32 ulp of every
+    """infer_support.alpha_bound with the beta-scaling inside the perturbed function: what one float32 ulp of every
     un-tempered input (ln L, each gradient component, each Fisher entry, at both points) moves the tempered log alpha by,
     to first order, summed in magnitude"""
-    ulp = lambda a: np.spacing(np.abs(a).astype(np.float32)).astype(np.float64)
     d = u0.shape[1]
 
     def moved(e):
         with np.errstate(invalid="ignore"):
             return np.abs(np.nan_to_num(alpha_of(u0, tempered(e[0], beta), prop, tempered(e[1], beta), eps, ridge) - la, nan=0.0, posinf=0.0,
                                         neginf=0.0))
-    bound = tr.tmul(beta, ulp(e0[0]) + ulp(e1[0]))
+    bound = tr.tmul(beta, ulp32(e0[0]) + ulp32(e1[0]))
     for side in (0, 1):
         for j in range(d):
             e = [[a.copy() for a in e0], [a.copy() for a in e1]]
-            e[side][1][:, j] += ulp(e[side][1][:, j])
+            e[side][1][:, j] += ulp32(e[side][1][:, j])
             bound += moved(e)
             for k in range(j, d):
                 e = [[a.copy() for a in e0], [a.copy() for a in e1]]
-                h = ulp(e[side][2][:, j, k])
+                h = ulp32(e[side][2][:, j, k])
                 e[side][2][:, j, k] += h
                 if k != j:
                     e[side][2][:, k, j] += h
@@ -134,7 +110,7 @@ def test_one_tempered_transition_against_reference(ctx, which):
     n, T = 1000, 4
     if which == "D1":
         st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-        prec, flags, x0 = "f16", flags_all(nat), starts_near(truths[0], tin, n, 5)
+        prec, flags, x0 = "f16", flags_of(nat, True), starts_near(truths[0], tin, n, 5)
     else:
         st, rec, prob, flags = shape_setup(ctx, which)
         prec, tin, x0 = "f32", rec["tin"], starts_in_box(rec, prob, n, 7, 0.03)
@@ -175,7 +151,7 @@ def test_one_tempered_transition_against_reference(ctx, which):
     st.set_likelihood(None, None)
 
 
-@pytest.mark.parametrize("T,ladders", tc.SWAP_CASES)
+@pytest.mark.parametrize("T,ladders", ic.SWAP_CASES)
 def test_swaps_are_the_stated_permutation(ctx, T, ladders):
     """One kept transition without swaps (run A) and with swap_every = 1 (run B), at step0 = 0 (event 0: the even pairs)
     and step0 = 1 (event 1: the odd pairs): B's x_last and lnl_last are A's rows, bit for bit, permuted by the decision
@@ -185,8 +161,8 @@ def test_swaps_are_the_stated_permutation(ctx, T, ladders):
     the swap; swap_every = 2 at step0 = 0 has no event and equals A.  The last workgroup is partial at every T."""
     st, rec, prob, flags = shape_setup(ctx, "i4o65")
     n = T * ladders
-    betas = tc.swap_betas(T)
-    x0 = starts_in_box(rec, prob, n, tc.SWAP_SEED, None)
+    betas = ic.swap_betas(T)
+    x0 = starts_in_box(rec, prob, n, ic.SWAP_SEED, None)
     opts = dict(n_warmup=0, n_steps=1, seed=sc.SEED, chain0=sc.CHAIN0, eps0=0.5)
     for step0 in (0, 1):
         A = st.sample_tempered(x0, T, betas, 0, "f32", flags, step0=step0, **opts)
@@ -215,33 +191,6 @@ def test_swaps_are_the_stated_permutation(ctx, T, ladders):
     for k in A:
         assert same(A[k], B2[k]), k
     st.set_likelihood(None, None)
-
-
-def dev_tempered(ctx, st, x0, prec, flags, T, betas, swap_every, **opts):
-    """v21_mlp_sample_tempered_dev on float32 starts against the record -> x_last, lnl_last, mean_lnl, swap_accept"""
-    n, din = x0.shape
-    host = {"x_last": np.empty((n, din), np.float32), "lnl_last": np.empty(n, np.float32)}
-    thost = {"mean_lnl": np.empty(n, np.float64), "swap_accept": np.empty(n, np.float64)}
-    bufs = []
-    try:
-        dx = ctx.malloc(x0.nbytes)
-        bufs.append(dx)
-        out, tout = {}, {}
-        for d, h in ((out, host), (tout, thost)):
-            for k, a in h.items():
-                d[k] = ctx.malloc(a.nbytes)
-                bufs.append(d[k])
-        ctx.h2d(dx, x0)
-        st.sample_tempered_dev(dx, din, n, None, 0, out, tout, T, betas, swap_every, None, prec, flags, **opts)
-        ctx.sync()
-        for d, h in ((out, host), (tout, thost)):
-            for k, a in h.items():
-                ctx.d2h(a, d[k])
-    finally:
-        for p in bufs:
-            ctx.free(p)
-    host.update(thost)
-    return host
 
 
 def test_chunks_and_continuation(ctx):
@@ -295,20 +244,20 @@ def test_uniform_target(ctx):
 
 @pytest.mark.parametrize("name", ["i1", "i2"])
 def test_evidence_against_quadrature(ctx, name):
-    """the two quadrature problems of tests/test_temper_cpu.py with its constants, on the device in f32: every rung's mean
+    """the two quadrature problems of tests/infer_cases.py with their constants, on the device in f32: every rung's mean
     ln L within 5 standard errors (the scatter over the 64 ladders) of the quadrature value, ln Z within 5 of its own"""
     nat, em = pkg("_native"), pkg("emulator")
-    p = tc.problem(name)
+    p = ic.problem(name)
     st, rec = device_stack(ctx, p["dims"], p["act"])
     st.set_likelihood(p["data"], p["w"])
     tin = rec["tin"]
     x0 = fr.untransform(p["starts_u"], tin[0], tin[2], tin[3])
-    r = st.sample_tempered(x0, tc.RUNGS, tc.BETAS, tc.SWAP_EVERY, "f32", flags_all(nat), **tc.RUN)
-    z, z_lz, se = tc.ladder_check(r["mean_lnl"], name)
-    lz = em.log_evidence(tc.BETAS, r["mean_lnl"].reshape(tc.LADDERS, tc.RUNGS))
+    r = st.sample_tempered(x0, ic.RUNGS, ic.BETAS, ic.SWAP_EVERY, "f32", flags_of(nat, True), **ic.RUN)
+    z, z_lz, se = ic.ladder_check(r["mean_lnl"], name)
+    lz = em.log_evidence(ic.BETAS, r["mean_lnl"].reshape(ic.LADDERS, ic.RUNGS))
     print("%s: z per rung %s, ln Z %.4f +- %.4f (quadrature trapezoid %.4f, z %.2f), swap rates %s"
-          % (name, z.round(2), lz.mean(), lz.std(ddof=1) / 8, tr.trapezoid(tc.BETAS, tc.quadrature(name)[0]), z_lz,
-             r["swap_accept"].reshape(tc.LADDERS, tc.RUNGS).mean(axis=0).round(2)))
+          % (name, z.round(2), lz.mean(), lz.std(ddof=1) / 8, tr.trapezoid(ic.BETAS, ic.quadrature(name)[0]), z_lz,
+             r["swap_accept"].reshape(ic.LADDERS, ic.RUNGS).mean(axis=0).round(2)))
     assert np.all(np.abs(z) < N_SE), z
     assert abs(z_lz) < N_SE, z_lz
     st.set_likelihood(None, None)
@@ -337,7 +286,7 @@ def test_mean_lnl_against_reference_sampler(ctx, prec):
     x0 = np.repeat(starts_near(truths[0], tin, L, 1, scale=0.01), T, axis=0)
     kw = dict(opts)
     se = kw.pop("swap_every")
-    r = st.sample_tempered(x0, T, betas, se, prec, flags_all(nat), **kw)
+    r = st.sample_tempered(x0, T, betas, se, prec, flags_of(nat, True), **kw)
     assert st.last_jac_route()[0] == "fused"
     ref = d1_reference(Ws, bs, act, data[0], w, tout, u_of(x0, tin), betas, opts)
     (md, vd), (mr, vr) = between_chain(r["mean_lnl"].reshape(L, T)), between_chain(ref["mean_lnl"].reshape(L, T))
@@ -354,7 +303,7 @@ def test_argument_errors_and_routes_counted(ctx):
     counts once on the Jacobian's route whatever its transitions and chunks; n = 0 is a no-op"""
     nat = pkg("_native")
     st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
-    flags = flags_all(nat)
+    flags = flags_of(nat, True)
     lib, F, P = st.lib, C.POINTER(C.c_float), C.c_void_p
     n = 6
     x0 = np.ascontiguousarray(pkg("synth").make_params(n, seed=40, zero_fx_frac=0).astype(np.float32))
