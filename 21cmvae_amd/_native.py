@@ -57,6 +57,19 @@ class FitOpts(C.Structure):
     _fields_ = [("max_iter", C.c_int), ("lambda0", C.c_double), ("xtol", C.c_double), ("check_every", C.c_int)]
 
 
+class MapOpts(C.Structure):
+    """v21_map_opts (include/v21_types.h)"""
+    _fields_ = [("use_prior", C.c_int), ("hold", C.c_int * 8)]
+
+
+MAP_OUTPUTS = ("lnp", "laplace", "prec_u")
+
+
+class MapOut(C.Structure):
+    """v21_map_out (include/v21_types.h): host or device addresses, NULL = not asked for"""
+    _fields_ = [(k, C.c_void_p) for k in MAP_OUTPUTS]
+
+
 FIT_DEFAULTS = {"max_iter": 50, "lambda0": 1e-3, "xtol": 1e-7, "check_every": 8}
 FIT_STATUS = {0: "iteration limit", 1: "converged", 2: "no improving step", 3: "no information"}
 
@@ -196,6 +209,10 @@ SIGNATURES = {
     "v21_mlp_fit": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(FitOpts), _P, _F, _F, _F, C.POINTER(C.c_int32),
                               C.c_int, C.c_int]),
     "v21_mlp_fit_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(FitOpts), _P, _P, _P, _P, _P, C.c_int, C.c_int]),
+    "v21_mlp_fit_map": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(FitOpts), C.POINTER(MapOpts), _P, _F, _F, _F,
+                                  C.POINTER(C.c_int32), C.POINTER(MapOut), C.c_int, C.c_int]),
+    "v21_mlp_fit_map_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(FitOpts), C.POINTER(MapOpts), _P, _P, _P, _P,
+                                      _P, C.POINTER(MapOut), C.c_int, C.c_int]),
     "v21_mlp_sample": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(SampleOpts), _P, C.POINTER(SampleOut),
                                  C.c_int, C.c_int]),
     "v21_mlp_sample_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(SampleOpts), _P, C.POINTER(SampleOut),
@@ -986,6 +1003,63 @@ class Stack(_Owned):
         if fisher:
             out["fisher"] = F
         return out
+
+    @staticmethod
+    def map_opts(use_prior=False, hold=None, in_dim=8):
+        """v21_map_opts; ValueError for what the library would refuse.  hold: None, or one 0 / 1 (or bool) per input column"""
+        if use_prior not in (0, 1, False, True):
+            raise ValueError("fit_map: use_prior = %r (0 or 1)" % (use_prior,))
+        o = MapOpts(int(use_prior), (C.c_int * 8)())
+        if hold is not None:
+            h = np.asarray(hold)
+            if h.shape != (in_dim,):
+                raise ValueError("fit_map: hold must have one entry per input column (%d), got %r" % (in_dim, np.shape(hold)))
+            for i, v in enumerate(h.tolist()):
+                if v not in (0, 1, False, True):
+                    raise ValueError("fit_map: hold[%d] = %r (0 or 1)" % (i, v))
+                o.hold[i] = int(v)
+        return o
+
+    def fit_map(self, x0, precision="f32", flags=0, data=None, max_iter=None, lambda0=None, xtol=None, check_every=None,
+                fisher=False, use_prior=False, hold=None, outputs=MAP_OUTPUTS):
+        """``fit`` on ln L + ln p of the stack's prior record (use_prior; include/v21.h: v21_mlp_fit_map) with the columns
+        of ``hold`` (one 0 / 1 per input column) kept at their clamped start.  -> fit's dict and, of ``outputs``: lnp (n,)
+        float64 (unnormalised, over the free normal columns), laplace (n,) float64 (the Laplace approximation of
+        ln of the integral of L p over the free columns), prec_u (n, in, in) float32."""
+        x, dt = self._rows(x0)
+        n, din, dout = x.shape[0], self.dims[0], self.dims[-1]
+        if din > 8:
+            raise ValueError("fit_map: %d parameters (at most 8)" % din)
+        dp, nd = _data_rows("fit_map", data, n, dout)
+        opts = self.fit_opts(max_iter, lambda0, xtol, check_every)
+        mo = self.map_opts(use_prior, hold, din)
+        unknown = [k for k in outputs if k not in MAP_OUTPUTS]
+        if unknown:
+            raise ValueError("fit_map: unknown output %r (of %s)" % (unknown[0], ", ".join(MAP_OUTPUTS)))
+        xh = np.empty_like(x)
+        lnl, l0, status = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32)
+        F = np.empty((n, din, din), np.float32) if fisher else None
+        shapes = {"lnp": ((n,), np.float64), "laplace": ((n,), np.float64), "prec_u": ((n, din, din), np.float32)}
+        extra = {k: np.empty(*shapes[k]) for k in MAP_OUTPUTS if k in outputs}
+        mout = MapOut(*[extra[k].ctypes.data if k in extra else None for k in MAP_OUTPUTS])
+        with self.ctx.lock:
+            check(self.lib.v21_mlp_fit_map(self.h, x.ctypes.data_as(_P), dt, n, _opt(dp), nd, C.byref(opts), C.byref(mo),
+                                           xh.ctypes.data_as(_P), _fptr(lnl), _fptr(l0), _opt(F),
+                                           status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(mout), precision_id(precision), flags))
+        out = {"x_hat": xh, "lnl": lnl, "lnl_start": l0, "status": status}
+        if fisher:
+            out["fisher"] = F
+        out.update(extra)
+        return out
+
+    def fit_map_dev(self, d_x0, ldx, n, d_data, n_data, d_x_hat, d_lnl, d_lnl_start=None, d_fisher=None, d_status=None, out=None,
+                    use_prior=False, hold=None, precision="f32", flags=0, **opts):
+        """v21_mlp_fit_map_dev: device addresses (out: {name of MAP_OUTPUTS: address}), on the context's stream"""
+        o, mo = self.fit_opts(**opts), self.map_opts(use_prior, hold, self.dims[0])
+        mout = MapOut(*[(out or {}).get(k) for k in MAP_OUTPUTS])
+        check(self.lib.v21_mlp_fit_map_dev(self.h, _P(d_x0), ldx, n, _opt(d_data), n_data, C.byref(o), C.byref(mo), _P(d_x_hat),
+                                           _P(d_lnl), _opt(d_lnl_start), _opt(d_fisher), _opt(d_status), C.byref(mout),
+                                           precision_id(precision), flags))
 
     def fisher_dev(self, d_x, ldx, n, d_fisher, d_lnl=None, d_grad=None, precision="f32", flags=0):
         check(self.lib.v21_mlp_fisher_dev(self.h, _P(d_x), ldx, n, _P(d_fisher), _opt(d_lnl), _opt(d_grad), precision_id(precision), flags))

@@ -1,6 +1,6 @@
-// api_fit.hip -- Fisher matrices and batched maximum-likelihood fits (include/v21.h: v21_mlp_fisher[_dev],
-// v21_mlp_fit[_dev]).  Both run the Jacobian kernels of api_jacobian.hip (fused_jac<Arch, Prec> or jac_generic_kernel,
-// Jacobian mode) into the likelihood workspace slice by slice, and reduce each slice there with jac_reduce_kernel
+// api_fit.hip -- Fisher matrices and batched maximum-likelihood and MAP fits (include/v21.h: v21_mlp_fisher[_dev],
+// v21_mlp_fit[_dev], v21_mlp_fit_map[_dev]).  All run the Jacobian kernels of api_jacobian.hip (fused_jac<Arch, Prec> or
+// jac_generic_kernel, Jacobian mode) into the likelihood workspace slice by slice, and reduce each slice there with jac_reduce_kernel
 // (reduce_run): 4 din^2 (+ 4 (1 + din)) bytes per row leave the workspace.  A fit is a projected
 // Levenberg-Marquardt iteration per row in the transformed coordinates u in [-1, 1]^din (fit_lm_kernel); the host
 // only launches, and reads one int (the running rows) every check_every iterations.
@@ -39,9 +39,12 @@ static v21_fit_opts fit_defaults() {
 // the fit of n start rows prepped transformed (their fac is overwritten), then x_hat (x_dtype, pitch in_dim), lnl,
 // lnl_start and status (both nullable) and, with d_F, the Fisher matrix at x_hat in raw units: the rows as they are
 // handed back, transformed as v21_mlp_fisher transforms them.  Evaluations run on u (no input transform, fac = 1) with
-// the caller's output transform.
+// the caller's output transform.  map: null for the maximum-likelihood fit (fit_lm_kernel<false>, whatever the handle's
+// prior record says), else the MAP fit's prior and hold mask (fit_lm_kernel<true>) with its further results mo (device
+// pointers, each nullable).
 static int fit_run(v21_mlp* m, int route, long long n, const CallData& data, long long row0, const v21_fit_opts& o, int prec, int flags,
-                   void* x_hat, int x_dtype, float* d_lnl, float* d_lnl0, int* d_status, float* d_F) {
+                   void* x_hat, int x_dtype, float* d_lnl, float* d_lnl0, int* d_status, float* d_F, const FitMapArgs* map = nullptr,
+                   const v21_map_out* mo = nullptr) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0];
   CHK(m->fit.reserve((size_t)n));
@@ -58,8 +61,12 @@ static int fit_run(v21_mlp* m, int route, long long n, const CallData& data, lon
   HIPCHK(hipGetLastError());
   for (int it = 0; it <= o.max_iter; ++it) {
     CHK(reduce_run(m, route, n, F, l, g, nullptr, data.d, data.ld, data.rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    hipLaunchKernelGGL(fit_lm_kernel, grid, dim3(256), 0, st, fs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, n,
-                       din, it == 0 ? 1 : 0, o.xtol, cnt + it);
+    if (map)
+      hipLaunchKernelGGL((fit_lm_kernel<true, FitMapArgs>), grid, dim3(256), 0, st, fs, m->jxt.get(), (const float*)l, (const float*)g,
+                         (const float*)F, n, din, it == 0 ? 1 : 0, o.xtol, cnt + it, *map);
+    else
+      hipLaunchKernelGGL(fit_lm_kernel<false>, grid, dim3(256), 0, st, fs, m->jxt.get(), (const float*)l, (const float*)g,
+                         (const float*)F, n, din, it == 0 ? 1 : 0, o.xtol, cnt + it);
     HIPCHK(hipGetLastError());
     if (it < o.max_iter && (it + 1) % o.check_every == 0) {
       int running = -1;
@@ -68,8 +75,14 @@ static int fit_run(v21_mlp* m, int route, long long n, const CallData& data, lon
       if (running == 0) break;
     }
   }
-  const auto finish = x_dtype == V21_DTYPE_F64 ? fit_finish_kernel<double> : fit_finish_kernel<float>;
-  hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const FitRow*)fs, x_hat, d_lnl, d_lnl0, d_status, n, din, m->tin);
+  if (map) {
+    const auto finish = x_dtype == V21_DTYPE_F64 ? fit_map_finish_kernel<double> : fit_map_finish_kernel<float>;
+    hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const FitRow*)fs, x_hat, d_lnl, d_lnl0, d_status, mo ? mo->lnp : nullptr,
+                       mo ? mo->laplace : nullptr, mo ? mo->prec_u : nullptr, n, din, m->tin, *map);
+  } else {
+    const auto finish = x_dtype == V21_DTYPE_F64 ? fit_finish_kernel<double> : fit_finish_kernel<float>;
+    hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const FitRow*)fs, x_hat, d_lnl, d_lnl0, d_status, n, din, m->tin);
+  }
   HIPCHK(hipGetLastError());
   if (!d_F) return V21_OK;
   CHK(jac_prep(m, x_hat, x_dtype, din, n, 1));
@@ -90,7 +103,8 @@ static int fit_route(v21_mlp* m, int flags, bool fisher) {
   return route;
 }
 
-static constexpr JacEntry kFisher{"Fisher", kJacMaxIn, true, false}, kFit{"fit", kFitMaxIn, true, true};
+static constexpr JacEntry kFisher{"Fisher", kJacMaxIn, true, false}, kFit{"fit", kFitMaxIn, true, true},
+    kFitMap{"fit_map", kFitMaxIn, true, true};
 
 // ---- Fisher matrices
 extern "C" int v21_mlp_fisher_dev(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_fisher, float* d_lnl, float* d_grad,
@@ -119,43 +133,104 @@ extern "C" int v21_mlp_fisher(v21_mlp* m, const void* x, int x_dtype, int64_t n,
   });
 }
 
-// ---- fits
-extern "C" int v21_mlp_fit_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
-                               const v21_fit_opts* opts, float* d_x_hat, float* d_lnl, float* d_lnl_start, float* d_fisher,
-                               int32_t* d_status, int precision, int flags) {
+// ---- fits: maximum-likelihood (v21_mlp_fit[_dev]) and MAP (v21_mlp_fit_map[_dev]: the same fit on ln L + ln p with held
+// columns, then the Laplace evidence at the accepted point).  Both forms of both share one body each; is_map says which
+// entry it serves, and the plain entries launch what they always launched (fit_run without FitMapArgs).
+// the MAP options as the kernels take them (NULL: no prior, nothing held); V21_ERR_ARG before any device work
+static int fit_map_args(v21_mlp* m, const v21_map_opts* mopts, FitMapArgs* out) {
+  *out = FitMapArgs{};
+  if (!mopts) return V21_OK;
+  if (mopts->use_prior != 0 && mopts->use_prior != 1) return fail(V21_ERR_ARG, "fit_map: use_prior = %d (0 or 1)", mopts->use_prior);
+  for (int i = 0; i < kFitMaxIn; ++i) {
+    if (mopts->hold[i] != 0 && mopts->hold[i] != 1) return fail(V21_ERR_ARG, "fit_map: hold[%d] = %d (0 or 1)", i, mopts->hold[i]);
+    out->hold[i] = mopts->hold[i];
+  }
+  // (a handle without a record: the uniform prior, its PriorArgs all kind 0)
+  out->use_prior = mopts->use_prior;
+  if (out->use_prior) out->pr = m->prior;
+  return V21_OK;
+}
+
+static int fit_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data, const v21_fit_opts* opts,
+                   bool is_map, const v21_map_opts* mopts, float* d_x_hat, float* d_lnl, float* d_lnl_start, float* d_fisher,
+                   int32_t* d_status, const v21_map_out* mout, int precision, int flags) {
   const v21_fit_opts o = opts ? *opts : fit_defaults();
-  CHK(jac_args(m, d_x0 && d_x_hat && d_lnl, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFit));
-  CHK(call_data_args("fit", n, d_data != nullptr, n_data));
+  const JacEntry& entry = is_map ? kFitMap : kFit;
+  CHK(jac_args(m, d_x0 && d_x_hat && d_lnl, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, entry));
+  CHK(call_data_args(entry.name, n, d_data != nullptr, n_data));
   CHK(fit_check(o));
+  FitMapArgs map;
+  if (is_map) CHK(fit_map_args(m, mopts, &map));
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
   const int route = fit_route(m, flags, d_fisher != nullptr);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
-  return fit_run(m, route, n, data, 0, o, precision, flags, d_x_hat, V21_DTYPE_F32, d_lnl, d_lnl_start, (int*)d_status, d_fisher);
+  return fit_run(m, route, n, data, 0, o, precision, flags, d_x_hat, V21_DTYPE_F32, d_lnl, d_lnl_start, (int*)d_status, d_fisher,
+                 is_map ? &map : nullptr, mout);
 }
 
-extern "C" int v21_mlp_fit(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_fit_opts* opts,
-                           void* x_hat, float* lnl, float* lnl_start, float* fisher, int32_t* status, int precision, int flags) {
+static int fit_host(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_fit_opts* opts,
+                    bool is_map, const v21_map_opts* mopts, void* x_hat, float* lnl, float* lnl_start, float* fisher, int32_t* status,
+                    const v21_map_out* mout, int precision, int flags) {
   const v21_fit_opts o = opts ? *opts : fit_defaults();
-  CHK(jac_args(m, x0 && x_hat && lnl, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kFit));
-  CHK(call_data_args("fit", n, data != nullptr, n_data));
+  const JacEntry& entry = is_map ? kFitMap : kFit;
+  CHK(jac_args(m, x0 && x_hat && lnl, n, kNoPitch, kNoPitch, x_dtype, precision, flags, entry));
+  CHK(call_data_args(entry.name, n, data != nullptr, n_data));
   CHK(fit_check(o));
+  FitMapArgs map;
+  if (is_map) CHK(fit_map_args(m, mopts, &map));
   if (n == 0) return V21_OK;
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0];
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   const int route = fit_route(m, flags, fisher != nullptr);
+  // the MAP results of a chunk are staged as the samplers' are (m->smp_out), the fit's own in the chunk's m->hout
+  ChunkStage sg;
+  v21_map_out d{};
+  if (is_map && mout) {
+    sg.add(mout->lnp, &d.lnp, sizeof(double));
+    sg.add(mout->laplace, &d.laplace, sizeof(double));
+    sg.add(mout->prec_u, &d.prec_u, (size_t)din * din * sizeof(float));
+    CHK(m->smp_out.reserve(sg.units(std::min<long long>(n, kJacHostChunk))));
+  }
   return jac_chunks(m, x0, x_dtype, n, 1, din * din + din + 3, [&](long long r0, long long rows, float* dF) {
     float* dl = dF + rows * din * din;
     float* dl0 = dl + rows;
     int* ds = (int*)(dl0 + rows);
-    CHK(fit_run(m, route, rows, cd, r0, o, precision, flags, m->hin.p, x_dtype, dl, dl0, ds, fisher ? dF : nullptr));
+    CHK(sg.place(m, r0, rows));
+    CHK(fit_run(m, route, rows, cd, r0, o, precision, flags, m->hin.p, x_dtype, dl, dl0, ds, fisher ? dF : nullptr,
+                is_map ? &map : nullptr, &d));
     CHK(to_host(m, (char*)x_hat + r0 * din * esz, m->hin.p, (size_t)rows * din * esz));
     CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
     if (lnl_start) CHK(to_host(m, lnl_start + r0, dl0, (size_t)rows * sizeof(float)));
     if (status) CHK(to_host(m, status + r0, ds, (size_t)rows * sizeof(int)));
-    return fisher ? to_host(m, fisher + r0 * din * din, dF, (size_t)rows * din * din * sizeof(float)) : V21_OK;
+    if (fisher) CHK(to_host(m, fisher + r0 * din * din, dF, (size_t)rows * din * din * sizeof(float)));
+    return sg.fetch(m, r0, rows);
   });
+}
+
+extern "C" int v21_mlp_fit_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                               const v21_fit_opts* opts, float* d_x_hat, float* d_lnl, float* d_lnl_start, float* d_fisher,
+                               int32_t* d_status, int precision, int flags) {
+  return fit_dev(m, d_x0, ldx, n, d_data, n_data, opts, false, nullptr, d_x_hat, d_lnl, d_lnl_start, d_fisher, d_status, nullptr, precision,
+                 flags);
+}
+
+extern "C" int v21_mlp_fit(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_fit_opts* opts,
+                           void* x_hat, float* lnl, float* lnl_start, float* fisher, int32_t* status, int precision, int flags) {
+  return fit_host(m, x0, x_dtype, n, data, n_data, opts, false, nullptr, x_hat, lnl, lnl_start, fisher, status, nullptr, precision, flags);
+}
+
+extern "C" int v21_mlp_fit_map_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                   const v21_fit_opts* opts, const v21_map_opts* mopts, float* d_x_hat, float* d_lnl, float* d_lnl_start,
+                                   float* d_fisher, int32_t* d_status, const v21_map_out* mout, int precision, int flags) {
+  return fit_dev(m, d_x0, ldx, n, d_data, n_data, opts, true, mopts, d_x_hat, d_lnl, d_lnl_start, d_fisher, d_status, mout, precision, flags);
+}
+
+extern "C" int v21_mlp_fit_map(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_fit_opts* opts,
+                               const v21_map_opts* mopts, void* x_hat, float* lnl, float* lnl_start, float* fisher, int32_t* status,
+                               const v21_map_out* mout, int precision, int flags) {
+  return fit_host(m, x0, x_dtype, n, data, n_data, opts, true, mopts, x_hat, lnl, lnl_start, fisher, status, mout, precision, flags);
 }

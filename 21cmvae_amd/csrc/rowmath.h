@@ -10,7 +10,8 @@
 //   solve_lower / _upper    L z = g and L^T x = z;
 //   box_clamp1 / box_clamp  a coordinate, and a start row, into the box;
 //   box_to_raw / raw_row    a coordinate, and a row of a result, back to raw units;
-//   PriorArgs               the samplers' prior record as their step kernels take it;
+//   PriorArgs               the prior record as the step kernels take it;
+//   prior_logp / prior_eval its ln p, and its gradient and precision added to an evaluation;
 //   Moments                 the bookkeeping of a sampler's kept transitions, the tail of its row state: the sums of u and
 //                           u u^T and the accepted count, the thinned store of a state, the per-row results.
 #pragma once
@@ -24,12 +25,39 @@ constexpr int kFitMaxIn = 8;
 constexpr int kFitPacked = kFitMaxIn * (kFitMaxIn + 1) / 2;
 
 // the handle's prior record (include/v21.h: v21_mlp_set_prior; api_prior.hip) as the step kernels of the four samplers
-// receive it, by value: per input column its kind (0: uniform on [-1, 1], 1: normal(mu, sd) truncated to it), mu,
-// w = 1 / sd^2 and wmu = mu / sd^2.  Columns >= din are never read.  Its arithmetic: sample_kernels.h.
+// and of the MAP fit receive it, by value: per input column its kind (0: uniform on [-1, 1], 1: normal(mu, sd) truncated
+// to it), mu, w = 1 / sd^2 and wmu = mu / sd^2.  Columns >= din are never read.
 struct PriorArgs {
   int kind[kFitMaxIn];
   double mu[kFitMaxIn], w[kFitMaxIn], wmu[kFitMaxIn];
 };
+
+// ---- the prior record in the step kernels of the four samplers and of the MAP fit.  PRIOR = false: none of it is
+// read, the arithmetic is the uniform prior's.
+// ln p(u), unnormalised: -1/2 sum_i w_i (u_i - mu_i)^2 over the normal columns
+template <class U>
+__device__ __forceinline__ double prior_logp(const PriorArgs& pr, const U* u, int din) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < kFitMaxIn; ++i)
+    if (i < din && pr.kind[i]) {
+      const double d = (double)u[i] - pr.mu[i];
+      s += pr.w[i] * d * d;
+    }
+  return -0.5 * s;
+}
+// g += grad ln p(u) = w mu - w u and F += diag(w), g and F (packed upper triangle) those of u
+template <bool PRIOR>
+__device__ __forceinline__ void prior_eval(const PriorArgs& pr, const double* u, int din, double* g, double* F) {
+  if constexpr (PRIOR) {
+#pragma unroll
+    for (int i = 0; i < kFitMaxIn; ++i)
+      if (i < din && pr.kind[i]) {
+        g[i] += pr.wmu[i] - pr.w[i] * u[i];
+        F[i * kFitMaxIn - i * (i - 1) / 2] += pr.w[i];
+      }
+  }
+}
 
 // din floats in float64 registers, zeros past din
 __device__ inline void widen_row(const float* v, int din, double* v64) {

@@ -59,33 +59,6 @@ __host__ __device__ inline double sample_uniform(uint32_t w) { return ((double)w
 
 constexpr double kSampleTwoPi = 6.283185307179586476925286766559;
 
-// ---- the prior record (rowmath.h: PriorArgs) in the step kernels of the four samplers.  PRIOR = false: none of it is
-// read, the arithmetic is the uniform prior's.
-// ln p(u), unnormalised: -1/2 sum_i w_i (u_i - mu_i)^2 over the normal columns
-template <class U>
-__device__ __forceinline__ double prior_logp(const PriorArgs& pr, const U* u, int din) {
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < kFitMaxIn; ++i)
-    if (i < din && pr.kind[i]) {
-      const double d = (double)u[i] - pr.mu[i];
-      s += pr.w[i] * d * d;
-    }
-  return -0.5 * s;
-}
-// g += grad ln p(u) = w mu - w u and F += diag(w), g and F (packed upper triangle, rowmath.h) those of u
-template <bool PRIOR>
-__device__ __forceinline__ void prior_eval(const PriorArgs& pr, const double* u, int din, double* g, double* F) {
-  if constexpr (PRIOR) {
-#pragma unroll
-    for (int i = 0; i < kFitMaxIn; ++i)
-      if (i < din && pr.kind[i]) {
-        g[i] += pr.wmu[i] - pr.w[i] * u[i];
-        F[i * kFitMaxIn - i * (i - 1) / 2] += pr.w[i];
-      }
-  }
-}
-
 // per-chain state
 struct SampleRow {
   EvalPoint p;                   // current point

@@ -158,8 +158,32 @@ def _grid(redshifts_, frequencies):
     return redshifts_, frequencies
 
 
-# fit_parameters' result (fisher: None unless asked for)
-FitResult = namedtuple("FitResult", ["params", "lnl", "status", "fisher"])
+# fit_parameters' result (fisher: None unless asked for; log_prior: None without prior / fixed / return_evidence;
+# log_evidence, cov_u: None unless return_evidence)
+FitResult = namedtuple("FitResult", ["params", "lnl", "status", "fisher", "log_prior", "log_evidence", "cov_u"],
+                       defaults=(None, None, None))
+
+
+def _free_block_inverse(prec_u, free):
+    """(..., d, d) posterior precisions (float32 data) -> covariances: the inverse on the rows and columns of ``free`` (a
+    boolean mask), zeros on the others.  NaN on the free block of a matrix that is no usable precision: an entry not
+    finite, a diagonal entry not positive, or -- scaled to a unit diagonal, so that the columns' units do not count -- a
+    condition number above 1 / float32 epsilon (2^23), beyond which the inverse of float32 data carries no digit."""
+    A = np.asarray(prec_u, np.float64)
+    idx = np.flatnonzero(free)
+    out = np.zeros_like(A)
+    if idx.size:
+        blk = A[..., idx[:, None], idx[None, :]]
+        diag = np.diagonal(blk, axis1=-2, axis2=-1)
+        with np.errstate(all="ignore"):
+            ok = np.isfinite(blk).all(axis=(-1, -2)) & (diag > 0).all(axis=-1)
+            s = 1.0 / np.sqrt(np.where(ok[..., None], diag, 1.0))
+            C = np.where(ok[..., None, None], blk * s[..., :, None] * s[..., None, :], np.eye(idx.size))
+            ok &= np.linalg.cond(C) <= 2.0 ** 23
+        inv = np.full_like(blk, np.nan)
+        inv[ok] = np.linalg.inv(C[ok]) * s[ok][:, :, None] * s[ok][:, None, :]
+        out[..., idx[:, None], idx[None, :]] = inv
+    return out
 
 
 # sample_posterior's result.  params / lnl: None with thin = 0; mean_u, cov_u: pooled over the chains of a spectrum, in
@@ -547,13 +571,15 @@ class _EmulatorBase:
             raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
         return model, st, flags, dat, one
 
-    def _sampler_starts(self, st, dat, per, p0, sigma, flow, fhigh, seed, foreground):
+    def _sampler_starts(self, st, dat, per, p0, sigma, flow, fhigh, seed, foreground, prior=None):
         """The samplers' raw start rows (M prod(per), din), ``per`` the shape of one spectrum's starts: ``p0`` ((din,) or
-        (per[-1], din), the same for every spectrum) or the best ``fit_parameters`` start per spectrum, every row jittered
-        (seeded, 0.02 in u, clipped into the box); then the call's likelihood record is set on the stack"""
+        (per[-1], din), the same for every spectrum) or the best ``fit_parameters`` start per spectrum -- under the call's
+        ``prior`` its MAP fit --, every row jittered (seeded, 0.02 in u, clipped into the box); then the call's likelihood
+        record is set on the stack"""
         din, shape = st.dims[0], (dat.shape[0],) + tuple(per) + (st.dims[0],)
         if p0 is None:
-            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground).params, np.float64, ndmin=2)
+            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground, prior=prior).params,
+                              np.float64, ndmin=2)
             u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], int(np.prod(per)), axis=1).reshape(shape)
         else:
             starts = np.array(p0, np.float64, ndmin=2)
@@ -582,19 +608,57 @@ class _EmulatorBase:
         out = (params, lnl, acc, step, rh) + pooled_moments(mean_c, cov_c)
         return PosteriorSamples(*[a[0] if one and a is not None else a for a in out])
 
+    def _fixed_columns(self, fixed):
+        """``fit_parameters``' ``fixed`` ({label: raw value}, None: nothing) -> (hold mask (din,) bool, raw values (din,),
+        NaN where free).  ValueError, naming the column: an unknown label, a value outside the training box"""
+        labels = list(self.par_labels)
+        hold, val = np.zeros(len(labels), bool), np.full(len(labels), np.nan)
+        centre = pp.par_untransform(np.zeros((1, len(labels))), self.par_train)
+        for name, v in dict(fixed or {}).items():
+            if name not in labels:
+                raise ValueError("fixed: unknown parameter %r (one of %s)" % (name, ", ".join(labels)))
+            j = labels.index(name)
+            row = centre.copy()
+            row[0, j] = float(v)
+            with np.errstate(all="ignore"):
+                u = pp.par_transform(row, self.par_train)[0, j]
+            if not -1.0 <= u <= 1.0:
+                raise ValueError("fixed: %s = %r lies outside the training box" % (name, v))
+            hold[j], val[j] = True, float(v)
+        return hold, val
+
     def fit_parameters(self, data, sigma, p0=None, n_starts=8, max_iter=50, flow=None, fhigh=None, seed=0, return_all=False,
-                       return_fisher=False, foreground=None):
-        """Maximum-likelihood parameters of observed signal(s) (not in the reference): a projected Levenberg-Marquardt fit
-        per (spectrum, start) on the device, inside the training box, of the Gaussian ln L of ``log_likelihood``.
+                       return_fisher=False, foreground=None, prior=None, fixed=None, return_evidence=False):
+        """Maximum-likelihood or maximum-a-posteriori parameters of observed signal(s) (not in the reference): a projected
+        Levenberg-Marquardt fit per (spectrum, start) on the device, inside the training box, of the Gaussian ln L of
+        ``log_likelihood``.
         ``data``: (451,) or (M, 451) mK.  Starts: ``p0`` ((7,) or (S, 7) raw parameters, the same for every spectrum), or
         the box centre and ``n_starts - 1`` uniform points of the box (seeded; uniform in par_transform's coordinates).
         Returns a ``FitResult`` (params, lnl, status[, fisher]) of the best start per spectrum (the lowest start index
         among equals), or of every start with ``return_all`` ((M, S, ...); the M axis dropped for one spectrum).  status:
         1 converged, 2 no improving step, 3 no information (all weights zero), 0 ``max_iter`` reached.  ``fisher``: the
-        Fisher matrix at the result in raw units.  Bounds: a log column's lower bound comes back as 10^lo (the fx zero
-        floor 1e-6, not 0)."""
+        Fisher matrix at the result in raw units (of the likelihood alone).  Bounds: a log column's lower bound comes back
+        as 10^lo (the fx zero floor 1e-6, not 0).
+        ``prior``: as in ``sample_posterior``; the fit then maximises ln L + ln p (include/v21.h: v21_mlp_fit_map), and the
+        best start is the one with the highest ln L + ln p.  ``lnl`` stays ln L.
+        ``fixed``: ``{label: raw value}``; that column of every start is set to the value and held there: it is no
+        parameter of the fit, its prior is not read, and it comes back as the value to float32 rounding in u.
+        ValueError, naming the column: an unknown label, a value outside the training box.
+        With any of ``prior``, ``fixed``, ``return_evidence`` the result also has ``log_prior``: ln of the prior density
+        at the result over the free columns, normalised as ``Prior.log_density_u`` (relative to the uniform prior: 0
+        without a prior).  ``return_evidence`` adds ``log_evidence``, the Laplace approximation
+        ln L + ln p + d_free / 2 ln 2 pi - 1/2 ln det(F + P) at the result, with respect to the normalised prior on the
+        free columns (the definition ``sample_tempered`` and ``nested_sample`` use), and ``cov_u``, the inverse of F + P on
+        the free columns in u (zeros on held rows and columns).
+        THE LAPLACE VALUE assumes an interior mode and a smooth ln L.  At a mode on a face of the box it is not an
+        evidence, and the ReLU kinks of the emulator near the mode bias it: on a 2-parameter test problem it was 0.14
+        nats off the quadrature, on a 1-parameter one 4e-7.  NaN where F + P has no Cholesky factor.
+        Without the three keywords the call is the maximum-likelihood fit it always was."""
         model, st, flags, dat, one = self._spectra(data)
         nb, din = st.dims[-1], st.dims[0]
+        use_map = prior is not None or fixed is not None or bool(return_evidence)
+        prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
+        hold, held = self._fixed_columns(fixed)
         if p0 is None:
             if int(n_starts) < 1:
                 raise ValueError("n_starts must be >= 1")
@@ -605,24 +669,47 @@ class _EmulatorBase:
             starts = np.array(p0, np.float64, ndmin=2)
             if starts.ndim != 2 or starts.shape[1] != din:
                 raise ValueError("p0 must be (%d,) or (S, %d), got %r" % (din, din, np.shape(p0)))
+        starts[:, hold] = held[hold]
         M, S = dat.shape[0], starts.shape[0]
         w = self._band_weights(nb, sigma, flow, fhigh)
         self._use_record(st, dat[0], w, foreground, flow, fhigh)
         x0 = np.ascontiguousarray(np.tile(starts, (M, 1)))
-        r = st.fit(x0, model.precision, flags, data=dat, max_iter=max_iter, fisher=return_fisher)
+        lnp = None
+        if use_map:
+            self._use_prior(st, prior)
+            try:
+                r = st.fit_map(x0, model.precision, flags, data=dat, max_iter=max_iter, fisher=return_fisher,
+                               use_prior=prior is not None, hold=hold,
+                               outputs=("lnp", "laplace", "prec_u") if return_evidence else ("lnp",))
+            finally:
+                st.use_prior(None)  # (never leaks into the next call)
+            lnp = r["lnp"].reshape(M, S)
+        else:
+            r = st.fit(x0, model.precision, flags, data=dat, max_iter=max_iter, fisher=return_fisher)
         xh = r["x_hat"].reshape(M, S, din)
         lnl = r["lnl"].reshape(M, S)
         status = r["status"].reshape(M, S)
         F = r["fisher"].reshape(M, S, din, din) if return_fisher else None
+        extra = []
+        if use_map:
+            # the device's ln p and Laplace value are those of the unnormalised density: its integral over the free columns
+            norm = (prior or Prior(None, self.par_train, self.par_labels)).log_integral_u(~hold, self.par_train)
+            extra = [lnp - norm + np.count_nonzero(~hold) * np.log(2.0), None, None]
+            if return_evidence:
+                extra[1] = r["laplace"].reshape(M, S) - norm
+                extra[2] = _free_block_inverse(r["prec_u"].reshape(M, S, din, din), ~hold)
         if not return_all:
-            best = np.argmax(np.where(np.isnan(lnl), -np.inf, lnl), axis=1)  # (first maximum: the lowest start index)
+            obj = lnl if lnp is None else lnl.astype(np.float64) + lnp
+            best = np.argmax(np.where(np.isnan(obj), -np.inf, obj), axis=1)  # (first maximum: the lowest start index)
             i = np.arange(M)
             xh, lnl, status = xh[i, best], lnl[i, best], status[i, best]
             F = F[i, best] if F is not None else None
+            extra = [a[i, best] if a is not None else None for a in extra]
         if one:
             xh, lnl, status = xh[0], lnl[0], status[0]
             F = F[0] if F is not None else None
-        return FitResult(xh, lnl, status, F)
+            extra = [a[0] if a is not None else None for a in extra]
+        return FitResult(xh, lnl, status, F, *extra)
 
     def sample_posterior(self, data, sigma, n_chains=64, n_steps=1000, n_warmup=200, thin=1, p0=None, flow=None, fhigh=None, seed=0,
                          eps=None, return_lnl=False, foreground=None, prior=None):
@@ -635,7 +722,7 @@ class _EmulatorBase:
         ``priors.Prior`` / its dict ``{label: spec}`` that puts a normal, truncated to the box, on chosen columns --
         ``("normal", mean, sd)`` in raw units on a linear column, ``("lognormal", mean_log10, sd_dex)`` on a log10 column;
         the others stay uniform.  The sampler then targets L times that prior on the device (include/v21.h:
-        v21_mlp_set_prior); every returned ``lnl`` stays ln L.  The default starts remain maximum-likelihood fits.
+        v21_mlp_set_prior); every returned ``lnl`` stays ln L.  The default starts are then MAP fits (``fit_parameters(prior=...)``).
         ``data``: (451,) or (M, 451) mK.  Starts: ``p0`` ((7,) or (n_chains, 7) raw parameters, the same for every
         spectrum), or by default the best ``fit_parameters`` start per spectrum; either way every chain is jittered
         (seeded, 0.02 in u, clipped into the box).  Each chain runs ``n_warmup`` transitions adapting its step size
@@ -653,7 +740,7 @@ class _EmulatorBase:
             raise ValueError("n_chains must be >= 1")
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
-        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground))
+        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground, prior))
         self._use_prior(st, prior)
         r = st.sample(x0, model.precision, flags, data=dat, **opts)
         return self._posterior_samples(r, lambda a: a.reshape((M, C) + a.shape[1:]), int(n_steps), return_lnl, one)
@@ -682,7 +769,7 @@ class _EmulatorBase:
             raise ValueError("n_ensembles must be >= 1")
         opts = dict(a=a, n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed)
         nat.Stack.ensemble_opts(W, in_dim=din, **opts)  # (argument errors before any device work)
-        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (E, W), p0, sigma, flow, fhigh, seed, foreground))
+        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (E, W), p0, sigma, flow, fhigh, seed, foreground, prior))
         self._use_prior(st, prior)
         r = st.sample_ensemble(x0, W, model.precision, flags, data=dat, **opts)
         return self._posterior_samples(r, lambda a: a.reshape((M, E, W) + a.shape[1:]), int(n_steps), return_lnl, one)
@@ -721,7 +808,7 @@ class _EmulatorBase:
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
         nat.Stack.temper_opts(T, b, swap_every)
-        x0 = self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground)
+        x0 = self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground, prior)
         x0 = np.ascontiguousarray(np.repeat(x0, T, axis=0))  # (every rung of a ladder from its ladder's start)
         self._use_prior(st, prior)
         r = st.sample_tempered(x0, T, b, swap_every, model.precision, flags, data=dat, **opts)

@@ -46,6 +46,7 @@ class Prior:
     v21_mlp_set_prior takes (kind 0 uniform, 1 normal; mu = 0, sd = 1 where uniform).
     ``log_density_u(u)``: ln of the density normalised on the box RELATIVE TO THE UNIFORM PRIOR, ln[p(u) 2^d]
     -- 0 everywhere for an all-uniform prior, so an evidence keeps its definition as the mean of L under the prior.
+    ``log_integral_u(free)``: ln of the unnormalised density's integral over the box, over the columns of ``free``.
     ``ppf_u(cube)``: the unit cube -> u, column by column the inverse CDF."""
 
     def __init__(self, spec=None, par_train=None, labels=None):
@@ -109,6 +110,21 @@ class Prior:
             z = (q[:, j] - mu[j]) / sd[j]
             out += -0.5 * z * z - 0.5 * np.log(2.0 * np.pi) - np.log(sd[j]) - tnorm_log_mass((-1.0 - mu[j]) / sd[j], (1.0 - mu[j]) / sd[j]) + np.log(2.0)
         return out[0] if np.ndim(u) == 1 else out
+
+    def log_integral_u(self, free=None, par_train=None):
+        """ln of the integral over the box of exp(ln p), ln p = -1/2 sum ((u - mu) / sd)^2 the UNNORMALISED log density the
+        device works with, over the columns of ``free`` (a boolean mask; None: all): ln(sqrt(2 pi) sd [Phi(b) - Phi(a)])
+        per normal column, ln 2 per uniform one.  Subtracted from a Laplace value of the integral of L exp(ln p) it gives
+        the evidence with respect to the normalised prior on those columns (``fit_parameters``)."""
+        kind, mu, sd = self.to_u(par_train)
+        free = np.ones(len(kind), bool) if free is None else np.asarray(free, bool)
+        out = 0.0
+        for j in np.flatnonzero(free):
+            if kind[j]:
+                out += 0.5 * np.log(2.0 * np.pi) + np.log(sd[j]) + float(tnorm_log_mass((-1.0 - mu[j]) / sd[j], (1.0 - mu[j]) / sd[j]))
+            else:
+                out += np.log(2.0)
+        return float(out)
 
     def ppf_u(self, cube, par_train=None):
         kind, mu, sd = self.to_u(par_train)

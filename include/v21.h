@@ -260,6 +260,36 @@ int v21_mlp_fit_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, con
                     const v21_fit_opts* opts, float* d_x_hat, float* d_lnl, float* d_lnl_start, float* d_fisher, int32_t* d_status,
                     int precision, int flags);
 
+/* ---- MAP fits with held parameters, and the Laplace approximation of the evidence.  v21_mlp_fit_map[_dev] is
+ * v21_mlp_fit[_dev] -- arguments, iteration, constants, statuses, chunks -- with two changes, both in float64 in u:
+ *   Objective.  ln L(u) + ln p(u), ln p = -1/2 sum_i ((u_i - mu_i) / sd_i)^2 over the normal columns of the handle's prior
+ *     record (v21_mlp_set_prior) that are NOT held, when mopts->use_prior is 1 (without a record: the uniform prior); a
+ *     proposal is accepted when this sum rose.  The solve becomes (A + lambda diag(max(A_ii, tiny))) delta = g + grad ln p
+ *     with A = F + diag(1 / sd^2) on those columns.
+ *   Held columns.  mopts->hold[i] = 1: column i is no parameter.  It keeps the float32 u of its clamped start (its x_hat
+ *     entry is what max_iter = 0 returns for that start), its prior is never read, and in the system g_i = 0,
+ *     A_ij = A_ji = 0 (j != i), A_ii = 1, so that its delta is exactly 0.
+ *   status 3 (no information) is decided on the diagonal of A over the free columns: a flat likelihood under a normal
+ *     column moves to the prior's mode, clamped into the box; with every column held the clamped start comes back with
+ *     status 1 after 0 iterations.
+ *   lnl and lnl_start stay ln L alone; fisher stays v21_mlp_fisher at x_hat (likelihood only, raw units).
+ * Results beside the fit's (v21_map_out, each nullable), at the accepted point u_hat with lambda = 0:
+ *   lnp      ln p(u_hat), unnormalised, over the free normal columns;
+ *   laplace  ln L + ln p + d_free / 2 ln(2 pi) - 1/2 ln det A_free, d_free the free columns, the determinant from the
+ *            diagonal of A's Cholesky factor; NaN when a free pivot is not positive and finite.  Subtract ln of the
+ *            integral of exp(ln p) over the free columns (d_free ln 2 for uniform ones) for the evidence with respect to
+ *            the normalised prior, as the samplers define it.  It assumes an interior mode and a smooth ln L: at a mode
+ *            on a face of the box it is no evidence;
+ *   prec_u   A (n, in_dim, in_dim) float32, exactly symmetric, the held rows and columns those of the identity.
+ * With mopts NULL (or use_prior 0 and nothing held) every result of v21_mlp_fit[_dev] comes back bit for bit.
+ * V21_ERR_ARG, before any device work and with the handle left usable: use_prior or a hold entry outside {0, 1}. */
+int v21_mlp_fit_map(v21_mlp* mlp, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_fit_opts* opts,
+                    const v21_map_opts* mopts, void* x_hat, float* lnl, float* lnl_start, float* fisher, int32_t* status,
+                    const v21_map_out* mout, int precision, int flags);
+int v21_mlp_fit_map_dev(v21_mlp* mlp, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                        const v21_fit_opts* opts, const v21_map_opts* mopts, float* d_x_hat, float* d_lnl, float* d_lnl_start,
+                        float* d_fisher, int32_t* d_status, const v21_map_out* mout, int precision, int flags);
+
 /* ---- posterior sampling: n independent Markov chains on the device, each a Metropolis-adjusted Langevin sampler whose
  * metric is the Fisher matrix at the current point ("simplified manifold MALA"), of the posterior of v21_mlp_loglike's
  * ln L under a UNIFORM PRIOR ON THE TRAINING BOX in the fit's coordinates u = par_transform(x) in [-1, 1]^in_dim -- that

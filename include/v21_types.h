@@ -17,6 +17,21 @@ typedef struct {
   double xtol;      /* [1e-7] converged when the projected step's largest |component| (u units) is <= xtol */
   int check_every;  /* [8] the host reads the count of running rows every check_every iterations */
 } v21_fit_opts;
+/* what v21_mlp_fit_map[_dev] takes beside v21_fit_opts (a NULL pointer: no prior, nothing held).  The array is inline:
+ * no pointer crosses the ABI. */
+typedef struct {
+  int use_prior;    /* 1: the objective is ln L + ln p of the handle's prior record (v21_mlp_set_prior; none: uniform); 0: ln L */
+  int hold[8];      /* 1: the column keeps the float32 u of its clamped start and is no parameter of the fit; 0: free.  All 8
+                     * entries must be 0 or 1; those >= in_dim are not used */
+} v21_map_opts;
+/* results of v21_mlp_fit_map[_dev] beside the fit's: host pointers for the host form, device pointers for _dev; every one
+ * may be NULL */
+typedef struct {
+  double* lnp;      /* (n): ln p(u_hat), unnormalised, over the free normal columns (0 without them) */
+  double* laplace;  /* (n): the Laplace approximation of ln of the integral of L p over the free columns; NaN without a
+                     * positive and finite Cholesky pivot on every free column */
+  float* prec_u;    /* (n, in_dim, in_dim): F(u_hat) + diag(1 / sd^2) in u, held rows and columns those of the identity */
+} v21_map_out;
 /* options of v21_mlp_sample[_dev] (a NULL pointer: the defaults in brackets) */
 typedef struct {
   int n_steps;          /* [1000] transitions after the warm-up: they enter the samples, the moments and accept_rate */
