@@ -690,9 +690,10 @@ static int forward_chain(v21_mlp* m, const float* d_x, long long ldx, long long 
   a.out_std = tout ? m->out_std : 1.0f;
   a.out_mean = tout ? m->d_mean : nullptr;
   a.tin = ((flags & V21_FWD_IN_TRANSFORM) && m->has_tin) ? m->d_tin : nullptr;
-  if (pc) return launch_chain32_args(a, st);
-  a.ncons = (int)(((n + 31) / 32 + 7) / 8 * 8);
-  a.npref = chain_prefetchers(a.ncons, 1);
+  static const RouteEnv env = RouteEnv::read();  // (inference: latched by the first call; only V21_CHAIN_PREF enters these plans)
+  if (pc) return launch_chain32_args(a, st, false, env);
+  const ChainLaunch p = plan_chain16(n, 1, env);  // (routes.h)
+  a.ncons = p.ncons; a.npref = p.npref;
   const dim3 grid(a.ncons + 8 * a.npref), block(64 * kChainWaves);
   launch_chain_forward_mode(prec, grid, block, st, a);
   HIPCHK(hipGetLastError());

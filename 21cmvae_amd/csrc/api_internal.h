@@ -404,33 +404,24 @@ struct v21_trainer {
   Dev<float> d_evalsum;
   Dev<float> d_slab;  // split-K partial gradients: max_slices x (P + 4)
   int max_slices = 1;
-  // variational latent layer (V21_ACT_GAUSS, A13): gl = its index or -1
-  int gl = -1;
+  // variational latent layer (V21_ACT_GAUSS, A13)
   Dev<float> d_zs, d_dzs, d_dzst;  // [z_mean | z_log_var], its gradient, transposed
   Dev<float> d_klrow;
   float kl_weight = 0.f;
   int sample = 1;
   unsigned long long seed = 0;
-  // one-kernel forward + activation-gradient chain (train_chain.h; f16 / bf16 stacks up to 512 wide)
-  bool chain = false;
-  // the same chain in fp32 (train_chain32.h): f32 stacks up to 512 wide without a variational layer; d_fw / d_bw then
-  // hold fp32 fragments and the weight-gradient operands are d_ht / d_dzt
-  bool chain32 = false;
-  bool chain32s = false;  // ... with the 8-row kernel and its stream format (train_chain32s.h): trainers of small batches
+  // the chain kernels (routes.h: TrainerKind); on the fp32 ones d_fw / d_bw hold fp32 fragments, the gradient operands are d_ht / d_dzt
   Dev<int> d_jobs;  // train_chain32s.h: C32sJob rows
   Dev<unsigned char> d_fw, d_bw;  // the packed streams (+ kChainStreamSlack), allocated once at creation
   ChainLayout lay;                // ... and their layout in this trainer's format
   Dev<float> d_partial;
   Dev<unsigned long long> d_ticket;  // the batch loss as 2^-32 fixed point (16 bytes)
   std::vector<Dev<unsigned short>> d_ht16, d_dzt16;  // fragment-ordered weight-gradient operands (train_chain.h)
-  // large steps of f16 / bf16 trainers whose stack has a compiled fused training kernel (fused_train.h; archs.h: T1 ..):
-  // index into the registry of api_trainer.hip or -1, and that kernel's packed stream (rebuilt before every launch)
-  int train_arch = -1;
-  v21::JitKernel* train_jit = nullptr;  // r5: ... or its run-time instantiation for a stack outside archs.h (jit.hip; asked for at creation)
-  bool train16 = false;  // the fused training kernel on 16 rows per wave (fused_train16.h): the stream below is in ITS format
+  // large steps on a fused training kernel (fused_train.h): its run-time instantiation for a stack outside archs.h
+  // (jit.hip; asked for at creation), the kernel's packed stream and the stream's layout
+  v21::JitKernel* train_jit = nullptr;
   Dev<unsigned char> d_tstream;
-  int tstream_total = 0, tstream_padded = 0;
-  std::vector<int> ts_first;    // first fragment of every virtual layer (2 L - 1 of them)
+  TrainStream ts;
   bool ts_write = false;        // the Adam pass that ends the current step also rewrites d_tstream (the step took the fused kernel)
   long long n_chain_steps = 0, n_fused_steps = 0, n_stream_packs = 0, n_stream_adam = 0;  // v21_debug_trainer_counters
   // routes.h: what the trainer committed to at creation, the route of its last eager step (written where the kernels are
@@ -500,6 +491,14 @@ static int launch_nt(int prec, GROUP& grp, hipStream_t st) {
   HIPCHK(hipGetLastError());
   return V21_OK;
 }
+// one of the four <A, GAUSS> instantiations of a chain kernel family (A0 / A1: the two precisions, or 4 / 8 rows per workgroup)
+#define V21_CHAIN_LAUNCH(KERN, A0, A1, first, gauss, lds, grid, block, st, ...)                           \
+  do {                                                                                                     \
+    if ((first) && (gauss)) hipLaunchKernelGGL((KERN<A0, true>), grid, block, lds, st, __VA_ARGS__);      \
+    else if (first) hipLaunchKernelGGL((KERN<A0, false>), grid, block, lds, st, __VA_ARGS__);             \
+    else if (gauss) hipLaunchKernelGGL((KERN<A1, true>), grid, block, lds, st, __VA_ARGS__);              \
+    else hipLaunchKernelGGL((KERN<A1, false>), grid, block, lds, st, __VA_ARGS__);                        \
+  } while (0)
 float adam_alpha(const v21_adam& a, long long t);  // api_trainer.hip
 // Where a step's batch loss goes.  `slot` >= 0: entry `slot` of the epoch's loss table (v21_trainer::d_steploss), written by
 // the kernel that publishes the loss -- a device-to-device copy per step would be a launch of its own.  Otherwise the step
@@ -509,7 +508,6 @@ AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt = fal
 int chain_attr(int prec);  // api_trainer.hip
 ChainModel chain_model(v21_trainer* t);  // api_trainer.hip
 ChainModel chain_model32(v21_trainer* t);  // api_trainer.hip
-int chain_prefetchers(int ncons, int models);  // api_trainer.hip
 ChainStep chain_step(const float* x, long long ldx, const float* y, long long ldy, const float* rw, const int* d_idx, long long first, int rows, int brows, int dout, const v21_trainer* vae = nullptr, long long row0 = 0);  // api_trainer.hip
 void destroy_graphs(v21_trainer* t);  // api_trainer.hip
 void dw16_problems(v21_trainer* t, int rows, int brows, int* nslice_out, std::vector<Dw16Args>& probs);  // api_trainer.hip
@@ -517,7 +515,7 @@ int ensure_copies(v21_trainer* t, bool need_nt = true);  // api_trainer.hip
 int gather_batch(v21_trainer* t, const float* x, long long ldx, const float* y, long long ldy_src, const float* rw, const int* d_idx, long long first, int rows);  // api_trainer.hip
 float grad_opscale(int brows, int dout);  // api_trainer.hip
 void invalidate_streams(v21_mlp* m);  // api_forward.hip
-int launch_chain32_args(ChainArgs& a, hipStream_t st, bool small = false, int rows_per_wg = 0 /* 4 / 8: the caller decided (routes.h); 0: by the row count */);  // api_trainer.hip
+int launch_chain32_args(ChainArgs& a, hipStream_t st, bool small, const RouteEnv& e);  // api_trainer.hip: train_chain32[s]_kernel over a.rows rows, one model
 int launch_dw16(int prec, const std::vector<Dw16Args>& probs, hipStream_t st, const DwXRows* xr = nullptr);  // api_trainer.hip
 int launch_dw32_group(const std::vector<v21_trainer*>& trs, const Dw32Model* d_tab, int rows, long long step_index, int max_blocks, hipStream_t st, bool small_slabs = false);  // api_sweep.hip
 int launch_dw_adam_group(const std::vector<v21_trainer*>& tr, const DwAdamModel* d_tab, const std::vector<DwAdamModel>& h_tab, int rows, int brows, long long slot, hipStream_t st);  // api_trainer.hip

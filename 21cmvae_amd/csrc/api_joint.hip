@@ -26,15 +26,15 @@ extern "C" int v21_joint_create(v21_trainer* ae, v21_trainer* em, int latent_lay
   if (!ae || !em || !out) return fail(V21_ERR_ARG, "null argument");
   if (ae == em || ae->ctx != em->ctx || ae->prec != em->prec || ae->max_batch != em->max_batch)
     return fail(V21_ERR_ARG, "the two trainers must be distinct and share context, precision and max_batch");
-  const bool f32 = ae->chain32s && em->chain32s && em->gl < 0;
-  if (!f32 && (!ae->chain || !em->chain || em->gl >= 0))
+  const bool f32 = ae->kind.chain32s && em->kind.chain32s && em->kind.gl < 0;
+  if (!f32 && (!ae->kind.chain || !em->kind.chain || em->kind.gl >= 0))
     return fail(V21_ERR_UNSUPPORTED, "the joint step runs on the chain kernels: f16 / bf16 (widths <= %d, no variational layer in the emulator), or "
                 "f32 with max_batch <= %d (variational head: latent <= %d)", kChainMaxDim, kC32sMaxBatch, kChainMaxLatent);
   const v21_mlp* ma = ae->mlp;
   const v21_mlp* me = em->mlp;
   // the latent layer: linear, or the variational head (V21_ACT_GAUSS) -- the emulator then learns z_mean, what
   // encoder.predict returns (emulator.py:753-754)
-  if (latent_layer < 0 || latent_layer >= ma->L - 1 || ma->act[latent_layer] == V21_ACT_RELU || (ae->gl >= 0 && ae->gl != latent_layer))
+  if (latent_layer < 0 || latent_layer >= ma->L - 1 || ma->act[latent_layer] == V21_ACT_RELU || (ae->kind.gl >= 0 && ae->kind.gl != latent_layer))
     return fail(V21_ERR_ARG, "latent_layer %d must be the linear (or variational) layer below the autoencoder's output", latent_layer);
   if (ma->dims[latent_layer + 1] != me->dims[me->L] || ma->dims[latent_layer + 1] > 2 * kChainMaxLatent)
     return fail(V21_ERR_ARG, "latent width %d (autoencoder) vs emulator output %d (at most %d)", ma->dims[latent_layer + 1],
@@ -63,6 +63,24 @@ static std::vector<ChainModel> joint_table(const v21_joint* j, int sample) {
   if (!sample) tab[0].sample = 0;
   return tab;
 }
+// ONE launch carries `rows` rows through both models (train_chain_joint_kernel / train_chain32s_joint_kernel) in the shape
+// routes.h plans; models: what c32s_rows counts (2, or 1 to meet the row blocks of a trainer's own launch)
+static int joint_launch(const v21_joint* j, ChainStep& sa, ChainStep& sb, long long rows, int models, const RouteEnv& env) {
+  const v21_trainer* ta = j->ae;
+  hipStream_t st = ta->ctx->stream;
+  const ChainLaunch p = j->f32 ? plan_chain32s(rows, models, 0, env) : plan_chain16(rows, 2, env);
+  sa.ncons = sb.ncons = p.ncons; sa.npref = sb.npref = p.npref;
+  sb.y_from_lds = 1;
+  if (j->f32) {
+    sa.gs = sb.gs = 1.0f;  // fp32 operands: no scaling of the gradients
+    launch_joint32_kernel(p.rows_per_wg, ta->kind.gl >= 0, dim3(2 * p.ncons), dim3(64 * kC32sWaves), st, (const ChainModel*)j->d_tab, sa, sb);
+  } else {
+    sb.blk0 = p.ncons;  // the emulator's row blocks follow the autoencoder's in the grid
+    launch_joint_kernel(ta->prec, ta->kind.gl >= 0, dim3(2 * p.ncons + 8 * p.npref), dim3(64 * kChainWaves), st, (const ChainModel*)j->d_tab, sa, sb);
+  }
+  HIPCHK(hipGetLastError());
+  return V21_OK;
+}
 // one epoch: the autoencoder trainer holds the signals (set_data(0, signals, NULL, w)), the emulator trainer the
 // parameters of the SAME rows (set_data(0, params, any (n, latent) array, w_mse)); losses[0] = autoencoder,
 // losses[1] = emulator (Keras epoch losses)
@@ -82,7 +100,8 @@ extern "C" int v21_joint_run_epoch(v21_joint* j, const int32_t* perm, int batch,
   for (v21_trainer* t : {ta, te}) CHK(ensure_steploss(t, steps));
   CHK(upload_if_changed(joint_table(j, 1), j->h_tab, j->d_tab.get(), st));
   if (R == 1 && !j->f32) CHK(refresh_dw_adam_table({ta, te}, j->d_dwadam, j->h_dwadam, st));
-  bool group32 = j->f32 && R == 1 && batch <= kDw32MaxRows;
+  const RouteEnv env = RouteEnv::read();
+  bool group32 = decide_group32(j->f32, R, batch);  // (routes.h; then the tile check that needs the models)
   int max_blocks32 = 0;
   if (group32) {
     CHK(j->d_dw32.reserve(2));
@@ -99,22 +118,7 @@ extern "C" int v21_joint_run_epoch(v21_joint* j, const int32_t* perm, int batch,
       ChainStep sa = chain_step(ta->d_x[0], dsig, nullptr, dsig, ta->d_rw[0], d_idx, lo, rows, brows, dsig, nullptr, lo - first);
       ChainStep sb = chain_step(te->d_x[0], dpar, nullptr, dlat, te->d_rw[0], d_idx, lo, rows, brows, dlat, nullptr, lo - first);
       sa.step_off = (unsigned long long)s;  // the table holds the autoencoder's step counter as of the epoch's start (noise key)
-      sb.y_from_lds = 1;
-      if (j->f32) {
-        sa.gs = sb.gs = 1.0f;
-        const char* er = getenv("V21_C32S_ROWS");
-        const int force_rows = er ? atoi(er) : 0;
-        const int rpw = force_rows == 4 || force_rows == 8 ? force_rows : (2 * ((rows + 3) / 4) <= 256 ? 4 : 8);
-        sa.ncons = sb.ncons = ((rows + rpw - 1) / rpw + 7) / 8 * 8;
-        launch_joint32_kernel(rpw, ta->gl >= 0, dim3(2 * sa.ncons), dim3(64 * kC32sWaves), st, (const ChainModel*)j->d_tab, sa, sb);
-      } else {
-        sa.ncons = sb.ncons = ((rows + 31) / 32 + 7) / 8 * 8;
-        sb.blk0 = sa.ncons;  // the emulator's row blocks follow the autoencoder's in the grid
-        sa.npref = sb.npref = chain_prefetchers(2 * sa.ncons, 1);
-        launch_joint_kernel(ta->prec, ta->gl >= 0, dim3(2 * sa.ncons + 8 * sa.npref), dim3(64 * kChainWaves), st,
-                            (const ChainModel*)j->d_tab, sa, sb);
-      }
-      HIPCHK(hipGetLastError());
+      CHK(joint_launch(j, sa, sb, rows, 2, env));  // (both models' row blocks share the chip)
     }
     // then each model's gradients and Adam as after a chain step of its own: both models in one launch on a single rank
     if (group32) {
@@ -167,24 +171,8 @@ extern "C" int v21_joint_eval(v21_joint* j, double* losses) {
   ChainStep sa = chain_step(ta->d_x[1], dsig, nullptr, dsig, ta->d_rw[1], nullptr, 0, (int)n, (int)n, dsig);
   ChainStep sb = chain_step(te->d_x[1], dpar, nullptr, dlat, te->d_rw[1], nullptr, 0, (int)n, (int)n, dlat);
   sa.fwd_only = sb.fwd_only = 1;
-  sb.y_from_lds = 1;
-  if (j->f32) {
-    // (the row blocks v21_trainer_eval's launch takes for n rows: the same rows meet in the same partial sums, and the
-    //  autoencoder's validation loss is bit for bit the one it reports alone)
-    const char* er = getenv("V21_C32S_ROWS");
-    const int force_rows = er ? atoi(er) : 0;
-    const int rpw = force_rows == 4 || force_rows == 8 ? force_rows : (n <= kC32sRows4Max ? 4 : 8);
-    sa.gs = sb.gs = 1.0f;
-    sa.ncons = sb.ncons = (int)(((n + rpw - 1) / rpw + 7) / 8 * 8);
-    const dim3 grid(2 * sa.ncons), block(64 * kC32sWaves);
-    launch_joint32_kernel(rpw, ta->gl >= 0, grid, block, st, (const ChainModel*)j->d_tab, sa, sb);
-  } else {
-    sa.ncons = sb.ncons = (int)(((n + 31) / 32 + 7) / 8 * 8);
-    sb.blk0 = sa.ncons;
-    sa.npref = sb.npref = chain_prefetchers(2 * sa.ncons, 1);
-    const dim3 grid(2 * sa.ncons + 8 * sa.npref), block(64 * kChainWaves);
-    launch_joint_kernel(ta->prec, ta->gl >= 0, grid, block, st, (const ChainModel*)j->d_tab, sa, sb);
-  }
-  HIPCHK(hipGetLastError());
+  // models = 1, not 2: the row blocks v21_trainer_eval's launch takes for n rows -- the same rows meet in the same partial
+  // sums, and the autoencoder's validation loss is bit for bit the one it reports alone
+  CHK(joint_launch(j, sa, sb, n, 1, RouteEnv::read()));
   return read_tickets({ta, te}, n, losses);
 }

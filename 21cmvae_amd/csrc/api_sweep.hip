@@ -36,7 +36,6 @@ struct v21_sweep {
   // (scripts/diag/sweep_two_streams_probe.py) -- the kernels' own sum (44.6 + 101 us): what is left is enqueue jitter, not overlap.
   hipStream_t s2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_off = nullptr, ev_join = nullptr;
-  bool two_streams = false;  // this epoch
 };
 
 extern "C" int v21_sweep_create(v21_trainer** trainers, int count, v21_sweep** out) {
@@ -53,7 +52,7 @@ extern "C" int v21_sweep_create(v21_trainer** trainers, int count, v21_sweep** o
       return fail(V21_ERR_ARG, "model %d: context, precision and max_batch must match model 0", k);
     if (m->L != m0->L || m->act != m0->act || m->dims[0] != m0->dims[0] || m->dims[m->L] != m0->dims[m0->L])
       return fail(V21_ERR_ARG, "model %d: depth, activations and in/out width must match model 0", k);
-    if (t->gl >= 0 && !t->chain && !(t->chain32 && t->chain32s))
+    if (t->kind.gl >= 0 && !t->kind.chain && !(t->kind.chain32 && t->kind.chain32s))
       return fail(V21_ERR_UNSUPPORTED, "variational stacks are swept on the chain kernels only (f16 / bf16, or f32 with max_batch <= %d; latent <= %d)",
                   kC32sMaxBatch, kChainMaxLatent);
     for (int j = 0; j < k; ++j)
@@ -65,11 +64,11 @@ extern "C" int v21_sweep_create(v21_trainer** trainers, int count, v21_sweep** o
   s->tr.assign(trainers, trainers + count);
   CHK(s->d_adam.reserve(count));
   s->chain = true;
-  for (int k = 0; k < count; ++k) s->chain = s->chain && trainers[k]->chain;
+  for (int k = 0; k < count; ++k) s->chain = s->chain && trainers[k]->kind.chain;
   for (int k = 0; k < count; ++k) s->h_adam.push_back(adam_args(trainers[k], true, 0.f, s->chain));
   HIPCHK(hipMemcpyAsync(s->d_adam, s->h_adam.data(), s->h_adam.size() * sizeof(AdamArgs), hipMemcpyHostToDevice, s->ctx->stream));
   s->chain32s = !s->chain;
-  for (int k = 0; k < count; ++k) s->chain32s = s->chain32s && trainers[k]->chain32s && trainers[k]->mlp->L <= kNtMaxGroup;
+  for (int k = 0; k < count; ++k) s->chain32s = s->chain32s && trainers[k]->kind.chain32s && trainers[k]->mlp->L <= kNtMaxGroup;
   if (s->chain || s->chain32s) CHK(s->d_chain.reserve(count));
   if (s->chain32s) CHK(s->d_dw32.reserve(count));
   HIPCHK(hipStreamSynchronize(s->ctx->stream));
@@ -167,15 +166,9 @@ static int sweep_chain_launch(v21_sweep* s, const ChainStep& csp, int g0, int g1
   // one-dimensional grid: a model's row blocks share an XCD label (train_chain.h: train_chain_group_kernel)
   const dim3 grid(8 * csp.ncons * ((G + 7) / 8)), block(64 * kChainWaves);
   bool gauss = false;  // (train_chain.h: FEAT)
-  for (int k = g0; k < g1; ++k) gauss = gauss || s->tr[k]->gl >= 0;
+  for (int k = g0; k < g1; ++k) gauss = gauss || s->tr[k]->kind.gl >= 0;
   const ChainModel* tab = (const ChainModel*)s->d_chain + g0;
-  if (t0->prec == V21_PREC_F16) {
-    if (gauss) hipLaunchKernelGGL((train_chain_group_kernel<PrecF16, true>), grid, block, kChainLdsBytes, st, tab, csp, G);
-    else hipLaunchKernelGGL((train_chain_group_kernel<PrecF16, false>), grid, block, kChainLdsBytes, st, tab, csp, G);
-  } else {
-    if (gauss) hipLaunchKernelGGL((train_chain_group_kernel<PrecBF16, true>), grid, block, kChainLdsBytes, st, tab, csp, G);
-    else hipLaunchKernelGGL((train_chain_group_kernel<PrecBF16, false>), grid, block, kChainLdsBytes, st, tab, csp, G);
-  }
+  V21_CHAIN_LAUNCH(train_chain_group_kernel, PrecF16, PrecBF16, t0->prec == V21_PREC_F16, gauss, kChainLdsBytes, grid, block, st, tab, csp, G);
   HIPCHK(hipGetLastError());
   return V21_OK;
 }
@@ -191,7 +184,7 @@ static int sweep_dwadam_launch(v21_sweep* s, int g0, int g1, int rows, int brows
   const std::vector<DwAdamModel> hpart(s->h_dwadam.begin() + g0, s->h_dwadam.begin() + g1);
   return launch_dw_adam_group(part, s->d_dwadam + g0, hpart, rows, brows, step_index, st);
 }
-static int sweep_step_chain(v21_sweep* s, const ChainStep& cs, int brows, long long step_index) {
+static int sweep_step_chain(v21_sweep* s, const ChainStep& cs, int brows, long long step_index, const SweepShape& sh, const RouteEnv& env) {
   v21_trainer* t0 = s->tr[0];
   hipStream_t st = s->ctx->stream;
   const int G = (int)s->tr.size(), rows = cs.rows;
@@ -200,9 +193,9 @@ static int sweep_step_chain(v21_sweep* s, const ChainStep& cs, int brows, long l
     for (v21_trainer* t : s->tr) CHK(ensure_copies(t, false));
     CHK(chain_attr(t0->prec));
     ChainStep csp = cs;
-    csp.ncons = ((rows + 31) / 32 + 7) / 8 * 8;
-    csp.npref = 0;  // (no prefetcher workgroups in a sweep: measured slower in r2)
-    if (s->two_streams) {  // one rank: half A on the context's stream, half B on the second one, B one launch behind A
+    const ChainLaunch p = plan_chain16(rows, 0, env);  // (no prefetcher workgroups in a sweep)
+    csp.ncons = p.ncons; csp.npref = p.npref;
+    if (sh.two_streams) {  // one rank: half A on the context's stream, half B on the second one, B one launch behind A
       const int GA = (G + 1) / 2;
       CHK(sweep_chain_launch(s, csp, 0, GA, st));
       if (step_index == 0) CHK(sweep_offset(s));
@@ -275,43 +268,33 @@ static int sweep_chain32_launch(v21_sweep* s, const ChainStep& csp, int rpw, int
   const int G = g1 - g0;
   const dim3 grid(csp.ncons * G), block(64 * kC32sWaves);
   bool gauss = false;
-  for (int k = g0; k < g1; ++k) gauss = gauss || s->tr[k]->gl >= 0;
+  for (int k = g0; k < g1; ++k) gauss = gauss || s->tr[k]->kind.gl >= 0;
   const ChainModel* tab = (const ChainModel*)s->d_chain + g0;
-  if (rpw == 4) {
-    if (gauss) hipLaunchKernelGGL((train_chain32s_group_kernel<4, true>), grid, block, kC32sLdsBytes, st, tab, csp, G);
-    else hipLaunchKernelGGL((train_chain32s_group_kernel<4, false>), grid, block, kC32sLdsBytes, st, tab, csp, G);
-  } else {
-    if (gauss) hipLaunchKernelGGL((train_chain32s_group_kernel<8, true>), grid, block, kC32sLdsBytes, st, tab, csp, G);
-    else hipLaunchKernelGGL((train_chain32s_group_kernel<8, false>), grid, block, kC32sLdsBytes, st, tab, csp, G);
-  }
+  V21_CHAIN_LAUNCH(train_chain32s_group_kernel, 4, 8, rpw == 4, gauss, kC32sLdsBytes, grid, block, st, tab, csp, G);
   HIPCHK(hipGetLastError());
   return V21_OK;
 }
-static int sweep_step_chain32(v21_sweep* s, const ChainStep& cs, long long step_index, int max_blocks) {
+static int sweep_step_chain32(v21_sweep* s, const ChainStep& cs, long long step_index, int max_blocks, const SweepShape& sh, const RouteEnv& env) {
   hipStream_t st = s->ctx->stream;
   const int G = (int)s->tr.size(), rows = cs.rows;
   for (v21_trainer* t : s->tr) CHK(ensure_copies(t, false));
   CHK(chain_attr(V21_PREC_F32));
-  // 4 rows per workgroup while every model's row blocks fit the chip in one round (train_chain32s.h)
-  const int force_rows = RouteEnv::read().c32s_rows;
-  const int rpw = force_rows == 4 || force_rows == 8 ? force_rows : ((long long)G * ((rows + 3) / 4) <= 256 ? 4 : 8);
+  // 4 rows per workgroup while every model's row blocks fit the chip in one round (routes.h: c32s_rows)
+  const ChainLaunch p = plan_chain32s(rows, G, 0, env);
+  const int rpw = p.rows_per_wg;
   ChainStep csp = cs;
-  csp.ncons = ((rows + rpw - 1) / rpw + 7) / 8 * 8;
-  csp.npref = 0;
-  // (dw_adam32.h: SLAB -- from 8 members on the gradient launch is deep enough for four or five workgroups per CU to pay: r5,
-  //  f32, batch 256, 8 / 16 / 32 / 64 members 60 / 70-72 / 70 / 64-67 k -> 62-66 / 79 / 77-79 / 72-73 k model-steps/s)
-  const bool small_slabs = G >= 8;
-  if (s->two_streams) {  // (as sweep_step_chain: half B one launch behind half A)
+  csp.ncons = p.ncons; csp.npref = p.npref;
+  if (sh.two_streams) {  // (as sweep_step_chain: half B one launch behind half A)
     const int GA = (G + 1) / 2;
     const std::vector<v21_trainer*> pa(s->tr.begin(), s->tr.begin() + GA), pb(s->tr.begin() + GA, s->tr.end());
     CHK(sweep_chain32_launch(s, csp, rpw, 0, GA, st));
     if (step_index == 0) CHK(sweep_offset(s));
     CHK(sweep_chain32_launch(s, csp, rpw, GA, G, s->s2));
-    CHK(launch_dw32_group(pa, s->d_dw32, rows, step_index, max_blocks, st, small_slabs));
-    return launch_dw32_group(pb, s->d_dw32 + GA, rows, step_index, max_blocks, s->s2, small_slabs);
+    CHK(launch_dw32_group(pa, s->d_dw32, rows, step_index, max_blocks, st, sh.small_slabs));
+    return launch_dw32_group(pb, s->d_dw32 + GA, rows, step_index, max_blocks, s->s2, sh.small_slabs);
   }
   CHK(sweep_chain32_launch(s, csp, rpw, 0, G, st));
-  return launch_dw32_group(s->tr, s->d_dw32, rows, step_index, max_blocks, st, small_slabs);
+  return launch_dw32_group(s->tr, s->d_dw32, rows, step_index, max_blocks, st, sh.small_slabs);
 }
 
 extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch, double* losses) {
@@ -340,12 +323,14 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
     CHK(upload_if_changed(tab, s->h_chain, s->d_chain.get(), st));
     if (R == 1) CHK(refresh_dw_adam_table(s->tr, s->d_dwadam, s->h_dwadam, st));
   }
-  bool group32 = s->chain32s && R == 1 && batch <= kDw32MaxRows && !(getenv("V21_SWEEP32_GROUP") && getenv("V21_SWEEP32_GROUP")[0] == '0');
+  const RouteEnv env = RouteEnv::read();  // the epoch's shape (routes.h); the tile check in between needs the models
+  bool group32 = decide_group32(s->chain32s, R, batch, env.sweep32_group);
   int max_blocks32 = 0;
   if (group32) CHK(refresh_dw32_table(s->tr, s->d_dw32, s->h_dw32, &max_blocks32, &group32, st));
+  const SweepShape sh = decide_sweep(s->chain || group32, (int)s->tr.size(), R, env);
   if (!s->chain && !group32)
     for (v21_trainer* t : s->tr)
-      if (t->gl >= 0)
+      if (t->kind.gl >= 0)
         return fail(V21_ERR_UNSUPPORTED, "a sweep of variational f32 models takes the grouped chain launches only: one rank, batches of <= %d rows",
                     kDw32MaxRows);
   if (group32) {
@@ -357,8 +342,7 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
     CHK(upload_if_changed(tab, s->h_chain, s->d_chain.get(), st));
   }
   // r5: two half-groups on two streams (v21_sweep: s2) for the grouped chain launches of one rank; V21_SWEEP_STREAMS=1: one stream
-  s->two_streams = R == 1 && (s->chain || group32) && s->tr.size() >= 16 && RouteEnv::read().sweep_streams == 2;  // (below 16 members the second stream's hand-overs cost more than they hide: tiny members, 8 per group: 17.4 -> 23.6 us per step)
-  if (s->two_streams) {
+  if (sh.two_streams) {
     if (!s->s2) {
       HIPCHK(hipStreamCreateWithFlags(&s->s2, hipStreamNonBlocking));
       for (hipEvent_t* e : {&s->ev_fork, &s->ev_off, &s->ev_join}) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -375,7 +359,7 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
       ChainStep cs = chain_step(t0->d_x[0], din, t0->y_is_x[0] ? nullptr : t0->d_y[0], dout, t0->d_rw[0], d_idx, lo, rows,
                                 brows, dout, nullptr, lo - first);
       cs.step_off = (unsigned long long)sidx;  // the table holds every model's step counter as of the epoch's start
-      CHK(sweep_step_chain(s, cs, brows, sidx));
+      CHK(sweep_step_chain(s, cs, brows, sidx, sh, env));
       continue;
     }
     if (group32) {
@@ -383,7 +367,7 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
                                 brows, dout, nullptr, lo - first);
       cs.gs = 1.0f;  // fp32 operands: no scaling of the gradients
       cs.step_off = (unsigned long long)sidx;  // the table holds every model's step counter as of the epoch's start (noise key)
-      CHK(sweep_step_chain32(s, cs, sidx, max_blocks32));
+      CHK(sweep_step_chain32(s, cs, sidx, max_blocks32, sh, env));
       continue;
     }
     if (rows > 0)
@@ -391,7 +375,7 @@ extern "C" int v21_sweep_run_epoch(v21_sweep* s, const int32_t* perm, int batch,
     const float* yb = t0->y_is_x[0] ? t0->d_h[0] : t0->d_yb;
     CHK(sweep_step(s, yb, t0->y_is_x[0] ? p16(din) : p16(dout), rows, brows, sidx));
   }
-  if (s->two_streams) {  // half B's launches end before the losses are read (and before anything else touches its members)
+  if (sh.two_streams) {  // half B's launches end before the losses are read (and before anything else touches its members)
     HIPCHK(hipEventRecord(s->ev_join, s->s2));
     HIPCHK(hipStreamWaitEvent(st, s->ev_join, 0));
   }

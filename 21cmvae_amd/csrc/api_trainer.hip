@@ -47,13 +47,11 @@ void destroy_graphs(v21_trainer* t) {
 }
 
 // routes.h: the route of a step of `rows` rows of this trainer now, and the record of the step that takes it
-// a fused training kernel can be launched now: compiled in (archs.h), or instantiated at run time and arrived (jit.hip)
-static bool fused_train_ready(const v21_trainer* t) {
-  return t->train_arch >= 0 || (t->train_jit && v21::jit_state(t->train_jit) == v21::JIT_READY);
-}
-static StepRoute step_route(const v21_trainer* t, int rows) {
+static StepRoute step_route(const v21_trainer* t, int rows, const RouteEnv& e) {
   const v21_mlp* m = t->mlp;
-  return decide_step(t->kind, m->L, m->dims.data(), m->act.data(), rows, t->ctx->nranks, t->capturing, fused_train_ready(t), RouteEnv::read());
+  // a fused training kernel can be launched now: compiled in (archs.h), or instantiated at run time and arrived (jit.hip)
+  const bool fused_ready = t->kind.train_arch >= 0 || (t->train_jit && v21::jit_state(t->train_jit) == v21::JIT_READY);
+  return decide_step(t->kind, m->L, m->dims.data(), m->act.data(), rows, t->ctx->nranks, t->capturing, fused_ready, e);
 }
 static void note_route(v21_trainer* t, const StepRoute& r) {
   if (t->capturing) return;
@@ -137,9 +135,10 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
   v21_trainer* t = owner.get();
   t->mlp = m; t->ctx = m->ctx; t->prec = precision; t->max_batch = max_batch; t->P = m->nparams;
   const int L = m->L;
-  for (int l = 0; l < L; ++l)
-    if (m->act[l] == V21_ACT_GAUSS) t->gl = l;
-  if (t->gl == L - 1) return fail(V21_ERR_UNSUPPORTED, "a V21_ACT_GAUSS layer cannot be the last layer of a trained stack");
+  // what this trainer commits to: csrc/routes.h (the same function answers v21_route_train)
+  const RouteEnv env = RouteEnv::read();
+  t->kind = decide_trainer_kind(L, m->dims.data(), m->act.data(), precision, max_batch, env);
+  if (t->kind.gl == L - 1) return fail(V21_ERR_UNSUPPORTED, "a V21_ACT_GAUSS layer cannot be the last layer of a trained stack");
   if (m->act[L - 1] != V21_ACT_LINEAR) {  // (the loss gradient is taken w.r.t. the Dense output: no output non-linearity is differentiated)
     return fail(V21_ERR_UNSUPPORTED, "the output layer of a trained stack must be linear (the reference's output Dense has no activation, emulator.py:44)");
   }
@@ -167,8 +166,8 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
     t->wt_off.push_back(ot); ot += (long long)(m->nw(l) + 32) * p16(m->dims[l]);
     t->wp_off.push_back(op); op += (long long)(m->dims[l] + 32) * p16(m->nw(l));
   }
-  if (t->gl >= 0) {
-    const int W2 = m->nw(t->gl);
+  if (t->kind.gl >= 0) {
+    const int W2 = m->nw(t->kind.gl);
     CHK(t->d_zs.zeroed((size_t)(max_batch + 32) * p16(W2), st));
     CHK(t->d_dzs.zeroed((size_t)(max_batch + 32) * p16(W2), st));
     CHK(t->d_dzst.zeroed((size_t)(W2 + 32) * t->Bp, st));
@@ -180,113 +179,52 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
   CHK(t->d_wb.zeroed((size_t)max_batch + 32, st));
   CHK(t->d_rowloss.zeroed((size_t)max_batch + 32, st));
   CHK(t->d_evalsum.zeroed(4, st));
-  // what this trainer commits to: csrc/routes.h (the same function answers v21_route_train)
-  t->kind = decide_trainer_kind(L, m->dims.data(), m->act.data(), precision, max_batch, RouteEnv::read());
-  {  // the 16-bit chain kernel
-    const bool ok = t->kind.chain;
-    if (ok) {
-      CHK(alloc_chain_streams(t, CHAIN_FMT_16));
-      CHK(t->d_partial.zeroed((size_t)(max_batch + 31) / 32 + 4, st));
-      // 16-row groups per feature tile of the operand buffers, for whole 128-row blocks: the fused training kernel
-      // (fused_train.h) stores every group of a workgroup's 128 rows, pad rows included, and a group past BS would land in
-      // the NEXT feature tile's first rows (r4: with BS from 32-row blocks, a ragged step whose last 128-row block reached
-      // past it -- 777 rows of max_batch 777 -- had rows 0-63 of the following tile overwritten by whichever workgroup
-      // finished last; launch_fused_train checks the bound)
-      t->BS = ((long long)max_batch + 127) / 128 * 8 + 2;
-      for (auto* v : {&t->d_ht16, &t->d_dzt16}) *v = std::vector<Dev<unsigned short>>(L + 1);
-      const unsigned short one = precision == V21_PREC_F16 ? 0x3C00 : 0x3F80;
-      for (int l = 0; l < L; ++l) {
-        const int K = m->dims[l], N = m->nw(l);
-        const size_t na = (size_t)((K + 1 + 31) / 32) * t->BS * 512, nb = (size_t)((N + 31) / 32) * t->BS * 512;
-        CHK(t->d_ht16[l].zeroed(na, st));
-        CHK(t->d_dzt16[l + 1].zeroed(nb, st));
-        // feature K of the input operand: the constant row of ones that turns [dW; db] into one contraction
-        std::vector<unsigned short> tile((size_t)t->BS * 512, 0);
-        for (long long b = 0; b < t->BS * 16; ++b)
-          tile[(size_t)((b >> 4) * 64 + ((b >> 3) & 1) * 32 + (K & 31)) * 8 + (b & 7)] = one;
-        // (only element f%32 == K%32 of the last feature tile is set; the chain kernel writes features < K only)
-        HIPCHK(hipMemcpyAsync(t->d_ht16[l] + (size_t)(K >> 5) * t->BS * 512, tile.data(), tile.size() * 2, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-      }
-      t->chain = true;
-      // a compiled fused training kernel for this stack (large steps; no variational head), and which of the two: the
-      // packed weight stream is in the kernel's own format, so the choice is fixed here (routes.h: decide_trainer_kind)
-      t->train_arch = t->kind.train_arch;
-      if (t->kind.train_rt) {
-        // r5: no compiled kernel, but the template can be instantiated for this stack at run time (jit.hip: fused_train16 only).
-        // Asked for here when the trainer is large enough to ever take it; until the code object arrives -- and if it never
-        // does (no libhiprtc, a stack that spills) -- the steps stay on the chain kernel.  v21_trainer_jit waits for it.
-        const RouteEnv e = RouteEnv::read();
-        const int fused_rows = e.fused_train_rows >= 0 ? e.fused_train_rows : 8193;
-        if (max_batch >= fused_rows) t->train_jit = v21::jit_request(L, m->dims.data(), m->act.data(), precision | v21::kJitTrain16);
-        if (!t->train_jit) t->kind.train_rt = false;
-      }
-      if (t->train_arch >= 0 || t->kind.train_rt) {
-        t->train16 = t->kind.train16;
-        int total = 0;
-        for (int v = 0; v < 2 * L - 1; ++v) {
-          const int l = v < L ? v : 2 * L - 1 - v;
-          const int K = v < L ? m->dims[l] : m->dims[l + 1], N = v < L ? m->dims[l + 1] : m->dims[l];
-          t->ts_first.push_back(total);
-          total += t->train16 ? ((N + 15) / 16) * ((K + 31) / 32 + 1) : ((N + 31) / 32) * ((K + 15) / 16 + 1);
-        }
-        t->tstream_total = total;
-        t->tstream_padded = (total + 7) / 8 * 8;
-        CHK(t->d_tstream.zeroed((size_t)t->tstream_padded * 1024 + kChainStreamSlack, st));
-      }
-      if (!(getenv("V21_DW_BLOCKS") && getenv("V21_DW_BLOCKS")[0] == '0')) {
-        // tile order of dw16_adam_kernel: per layer the R x C tile grid in 8 blocks (rb x cb = 8, the shape with the least
-        // operand rows per block), the blocks handed to the XCDs largest first onto the least loaded XCD
-        std::vector<std::vector<int>> per(8);
-        int first = 0;
-        for (int l = 0; l < L; ++l) {
-          const int R = (m->dims[l] + 1 + 31) / 32, C = (m->nw(l) + 31) / 32;
-          int brb = 8, bcb = 1;
-          double best = 1e30;
-          for (int rb : {1, 2, 4, 8}) {
-            const int cb = 8 / rb;
-            const double cost = std::ceil((double)R / rb) + std::ceil((double)C / cb);
-            if (cost < best) { best = cost; brb = rb; bcb = cb; }
-          }
-          std::vector<std::vector<int>> blocks;
-          for (int i = 0; i < brb; ++i)
-            for (int j = 0; j < bcb; ++j) {
-              std::vector<int> b;
-              for (int ti = R * i / brb; ti < R * (i + 1) / brb; ++ti)
-                for (int tj = C * j / bcb; tj < C * (j + 1) / bcb; ++tj) b.push_back(first + ti * C + tj);
-              blocks.push_back(b);
-            }
-          std::sort(blocks.begin(), blocks.end(), [](const std::vector<int>& a, const std::vector<int>& b) { return a.size() > b.size(); });
-          for (auto& b : blocks) {
-            int xmin = 0;
-            for (int x = 1; x < 8; ++x) if (per[x].size() < per[xmin].size()) xmin = x;
-            per[xmin].insert(per[xmin].end(), b.begin(), b.end());
-          }
-          first += R * C;
-        }
-        size_t xper = 0;
-        for (auto& v : per) xper = std::max(xper, v.size());
-        std::vector<int> order(8 * xper, -1);
-        for (int x = 0; x < 8; ++x) std::copy(per[x].begin(), per[x].end(), order.begin() + x * xper);
-        CHK(t->d_dworder.reserve(order.size() + 4));
-        HIPCHK(hipMemcpyAsync(t->d_dworder, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        t->dw_xper = (int)xper;
-      }
+  if (t->kind.chain) {  // the 16-bit chain kernel
+    CHK(alloc_chain_streams(t, CHAIN_FMT_16));
+    CHK(t->d_partial.zeroed((size_t)(max_batch + 31) / 32 + 4, st));
+    // 16-row groups per feature tile of the operand buffers, for whole 128-row blocks: the fused training kernel
+    // (fused_train.h) stores every group of a workgroup's 128 rows, pad rows included, and a group past BS would land in
+    // the NEXT feature tile's first rows (r4: with BS from 32-row blocks, a ragged step whose last 128-row block reached
+    // past it -- 777 rows of max_batch 777 -- had rows 0-63 of the following tile overwritten by whichever workgroup
+    // finished last; launch_fused_train checks the bound)
+    t->BS = ((long long)max_batch + 127) / 128 * 8 + 2;
+    for (auto* v : {&t->d_ht16, &t->d_dzt16}) *v = std::vector<Dev<unsigned short>>(L + 1);
+    for (int l = 0; l < L; ++l) {
+      const int K = m->dims[l], N = m->nw(l);
+      CHK(t->d_ht16[l].zeroed((size_t)((K + 1 + 31) / 32) * t->BS * 512, st));
+      CHK(t->d_dzt16[l + 1].zeroed((size_t)((N + 31) / 32) * t->BS * 512, st));
+      const std::vector<unsigned short> tile = ones_tile16(K, t->BS, precision == V21_PREC_F16 ? 0x3C00 : 0x3F80);  // (routes.h)
+      HIPCHK(hipMemcpyAsync(t->d_ht16[l] + (size_t)(K >> 5) * t->BS * 512, tile.data(), tile.size() * 2, hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    // A fused training kernel for this stack (large steps; no variational head): compiled in, or -- r5 -- the template
+    // instantiated at run time (jit.hip: fused_train16 only), asked for here when the trainer is large enough to ever take
+    // it; until the code object arrives -- and if it never does (no libhiprtc, a stack that spills) -- the steps stay on the
+    // chain kernel.  v21_trainer_jit waits for it.  The packed weight stream is in the kernel's own format, so the choice
+    // between the two kernels is fixed here (routes.h: decide_trainer_kind).
+    if (t->kind.train_rt) {
+      const int fused_rows = env.fused_train_rows >= 0 ? env.fused_train_rows : 8193;
+      if (max_batch >= fused_rows) t->train_jit = v21::jit_request(L, m->dims.data(), m->act.data(), precision | v21::kJitTrain16);
+      if (!t->train_jit) t->kind.train_rt = false;
+    }
+    if (t->kind.fused()) {
+      t->ts = train_stream_layout(L, m->dims.data(), t->kind.train16);
+      CHK(t->d_tstream.zeroed((size_t)t->ts.padded * 1024 + kChainStreamSlack, st));
+    }
+    if (env.dw_blocks) {  // dw16_adam_kernel's tile order per XCD
+      const std::vector<int> order = dw_tile_order(L, m->dims.data(), m->act.data());
+      CHK(t->d_dworder.reserve(order.size() + 4));
+      HIPCHK(hipMemcpyAsync(t->d_dworder, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+      t->dw_xper = (int)order.size() / 8;
     }
   }
-  {  // the fp32 chain kernels (train_chain32.h; trainers of small batches -- the reference's 256 rows -- the 8-row kernel
-     // of train_chain32s.h, which also carries a variational head)
-    const bool ok = t->kind.chain32;
-    t->chain32s = t->kind.chain32s;
-    if (ok) {
-      CHK(alloc_chain_streams(t, t->chain32s ? CHAIN_FMT_32S : CHAIN_FMT_32));
-      t->chain32 = true;
-    }
-  }
+  // the fp32 chain kernels (train_chain32.h; trainers of small batches -- the reference's 256 rows -- the 8-row kernel of
+  // train_chain32s.h, which also carries a variational head)
+  if (t->kind.chain32) CHK(alloc_chain_streams(t, t->kind.chain32s ? CHAIN_FMT_32S : CHAIN_FMT_32));
   t->max_slices = std::max(1, (max_batch + 127) / 128);  // weight-gradient slices down to 8 batch steps
   CHK(t->d_slab.zeroed((size_t)t->max_slices * (t->P + 4), st));
-  if (t->chain32s) CHK(build_chain32s_jobs(t));
+  if (t->kind.chain32s) CHK(build_chain32s_jobs(t));
   *out = owner.release();
   return V21_OK;
 }
@@ -331,7 +269,7 @@ extern "C" int v21_trainer_set_data(v21_trainer* t, int which, const float* x, c
   HIPCHK(hipMemcpyAsync(t->d_x[which], x, (size_t)n * din * sizeof(float), hipMemcpyHostToDevice, st));
   if (which == 0) {  // the fused training kernels gather the training rows as 16-bit elements (ChainStep::x16)
     t->d_x16.release();
-    if ((t->train_arch >= 0 || t->kind.train_rt) && !(getenv("V21_TRAIN_X16") && getenv("V21_TRAIN_X16")[0] == '0')) {
+    if (t->kind.fused() && RouteEnv::read().train_x16) {
       t->ldx16 = (din + 31) / 32 * 32;
       const long long tot = (long long)n * t->ldx16;
       CHK(t->d_x16.reserve((size_t)tot));
@@ -386,20 +324,20 @@ AdamArgs adam_args(v21_trainer* t, bool do_adam, float alpha, bool skip_nt, cons
     AdamLayer& al = a.lt[l];
     al.w_off = m->w_off[l]; al.wt_off = t->wt_off[l]; al.wp_off = t->wp_off[l];
     al.K = m->dims[l]; al.N = m->nw(l); al.ldwt = p16(al.K); al.ldwp = p16(al.N);
-    if (t->chain || t->chain32) t->lay.layer(al, l);
+    if (!t->kind.per_layer()) t->lay.layer(al, l);
   }
-  if (t->chain) { a.fw = t->d_fw; a.bw = t->d_bw; a.cprec = t->prec == V21_PREC_F16 ? 1 : 2; }
-  if (t->chain32) { a.fw = t->d_fw; a.bw = t->d_bw; a.cprec = t->chain32s ? 4 : 3; }
+  if (t->kind.chain) { a.fw = t->d_fw; a.bw = t->d_bw; a.cprec = t->prec == V21_PREC_F16 ? 1 : 2; }
+  if (t->kind.chain32) { a.fw = t->d_fw; a.bw = t->d_bw; a.cprec = t->kind.chain32s ? 4 : 3; }
   if (t->ts_write && t->d_tstream) {  // fused_train.h's stream from the same pass (api_trainer.hip: train_on_rows)
-    a.ts = t->d_tstream; a.ts_bf16 = t->prec == V21_PREC_BF16; a.ts_fmt16 = t->train16 ? 1 : 0;
-    const int L = m->L, kstep = t->train16 ? 32 : 16;
-    for (int l = 0; l < L; ++l) {
+    a.ts = t->d_tstream; a.ts_bf16 = t->prec == V21_PREC_BF16; a.ts_fmt16 = t->kind.train16 ? 1 : 0;
+    const int L = m->L, kstep = t->kind.train16 ? 32 : 16;
+    for (int l = 0; l < L; ++l) {  // layer l's forward fragments, and those of the activation-gradient layer that carries its transpose
       AdamLayer& al = a.lt[l];
-      al.tsf = t->ts_first[l]; al.tkf = (m->dims[l] + kstep - 1) / kstep;
-      al.tsb = l >= 1 ? t->ts_first[2 * L - 1 - l] : -1; al.tkb = (m->dims[l + 1] + kstep - 1) / kstep;
+      al.tsf = t->ts.lt[l].first; al.tkf = (m->dims[l] + kstep - 1) / kstep;
+      al.tsb = l >= 1 ? t->ts.lt[2 * L - 1 - l].first : -1; al.tkb = (m->dims[l + 1] + kstep - 1) / kstep;
     }
   }
-  a.skip_nt = (skip_nt && (t->chain || t->chain32)) ? 1 : 0;
+  a.skip_nt = (skip_nt && (!t->kind.per_layer())) ? 1 : 0;
   if (do_adam && pub) {  // a single-rank f32 chain step: this launch publishes its loss
     a.loss_acc = t->d_ticket; a.loss_out = t->d_g + t->P; a.loss_out2 = t->d_steploss;
     a.loss_slot = pub->slot;
@@ -420,7 +358,7 @@ int reduce_and_update(v21_trainer* t, int fold, bool exchanged, const StepLoss* 
   v21_ctx* c = t->ctx;
   hipStream_t st = c->stream;
   const size_t P = t->P;
-  const bool chain_copies = t->chain || t->chain32;  // (the chain trainers never read the fp32 NT copies)
+  const bool chain_copies = !t->kind.per_layer();  // (the chain trainers never read the fp32 NT copies)
   // recorded, not run: iteration count, step size and loss slot come from the descriptors
   if (t->capturing) return adam_and_copies(t, true, 0.f, chain_copies, fold, pub);
   if (c->nranks > 1 && c->sharded) {
@@ -462,7 +400,7 @@ void weights_updated(v21_trainer* t, bool nt_ok) {
 int step_tail(v21_trainer* t, const StepLoss& loss) {
   if (t->capturing) return V21_OK;  // (recorded, not run: after_replay does the bookkeeping of each replay)
   if (loss.out && loss.slot < 0) HIPCHK(hipMemcpyAsync(loss.out, t->d_g + t->P, sizeof(float), hipMemcpyDeviceToDevice, t->ctx->stream));
-  weights_updated(t, !t->chain && !t->chain32);
+  weights_updated(t, t->kind.per_layer());
   return V21_OK;
 }
 // the loss of a step of >= 1 row: one rank, an epoch's per-step slot -- the kernel that publishes the batch loss writes
@@ -495,7 +433,7 @@ int ensure_copies(v21_trainer* t, bool need_nt) {
 
 static GaussArgs gauss_args(v21_trainer* t, int rows, bool sample, long long row0) {
   v21_mlp* m = t->mlp;
-  const int l = t->gl;
+  const int l = t->kind.gl;
   GaussArgs a{};
   a.zs = t->d_zs; a.ldz = p16(m->nw(l)); a.L = m->dims[l + 1]; a.n = rows;
   a.h = t->d_h[l + 1]; a.ldh = p16(m->dims[l + 1]); a.ht = nullptr; a.ldt = t->Bp;
@@ -588,7 +526,7 @@ static int per_layer_step(v21_trainer* t, const float* yb, long long ldy, int ro
   const NtSlices sl{r.nslice, r.k_chunk};  // weight gradients contract over the batch: slices -> slabs (routes.h: nt_slices)
   const float gs = grad_opscale(brows, dout);
   for (int l = L - 1; l >= 0; --l) {
-    const bool gauss = l == t->gl;  // gradient w.r.t. this layer's Dense output: dzs / dzst instead of dz[l+1]
+    const bool gauss = l == t->kind.gl;  // gradient w.r.t. this layer's Dense output: dzs / dzst instead of dz[l+1]
     if (gauss) {  // dz[l+1] = dL/dz  ->  dL/d[z_mean | z_log_var] (+ the KL term's own gradient)
       GaussArgs a = gauss_args(t, rows, true, row0);
       a.beta = t->kl_weight / (float)brows;
@@ -630,7 +568,7 @@ ChainModel chain_model(v21_trainer* t) {
   a.loss_acc = t->d_ticket;
   a.stamps = t->stamps_on ? t->d_stamps.get() : nullptr;
   a.zcap_layer = -1;
-  if (t->gl >= 0) { a.kl_weight = t->kl_weight; a.sample = t->sample; a.seed = t->seed; a.step = (unsigned long long)t->iter; }
+  if (t->kind.gl >= 0) { a.kl_weight = t->kl_weight; a.sample = t->sample; a.seed = t->seed; a.step = (unsigned long long)t->iter; }
   return a;
 }
 ChainStep chain_step(const float* x, long long ldx, const float* y, long long ldy, const float* rw,
@@ -657,25 +595,11 @@ static int chain_attr_of() {
   for (const void* f : fs) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLdsBytes));
   return V21_OK;
 }
-void launch_joint32_kernel(int rpw, bool gauss, dim3 grid, dim3 block, hipStream_t st, const ChainModel* tab, const ChainStep& sa,
-                                  const ChainStep& sb) {
-  if (rpw == 4) {
-    if (gauss) hipLaunchKernelGGL((train_chain32s_joint_kernel<4, true>), grid, block, kC32sLdsBytes, st, tab, sa, sb);
-    else hipLaunchKernelGGL((train_chain32s_joint_kernel<4, false>), grid, block, kC32sLdsBytes, st, tab, sa, sb);
-  } else {
-    if (gauss) hipLaunchKernelGGL((train_chain32s_joint_kernel<8, true>), grid, block, kC32sLdsBytes, st, tab, sa, sb);
-    else hipLaunchKernelGGL((train_chain32s_joint_kernel<8, false>), grid, block, kC32sLdsBytes, st, tab, sa, sb);
-  }
+void launch_joint32_kernel(int rpw, bool gauss, dim3 grid, dim3 block, hipStream_t st, const ChainModel* tab, const ChainStep& sa, const ChainStep& sb) {
+  V21_CHAIN_LAUNCH(train_chain32s_joint_kernel, 4, 8, rpw == 4, gauss, kC32sLdsBytes, grid, block, st, tab, sa, sb);
 }
-void launch_joint_kernel(int prec, bool gauss, dim3 grid, dim3 block, hipStream_t st, const ChainModel* tab, const ChainStep& sa,
-                                const ChainStep& sb) {
-  if (prec == V21_PREC_F16) {
-    if (gauss) hipLaunchKernelGGL((train_chain_joint_kernel<PrecF16, true>), grid, block, kChainLdsBytes, st, tab, sa, sb);
-    else hipLaunchKernelGGL((train_chain_joint_kernel<PrecF16, false>), grid, block, kChainLdsBytes, st, tab, sa, sb);
-  } else {
-    if (gauss) hipLaunchKernelGGL((train_chain_joint_kernel<PrecBF16, true>), grid, block, kChainLdsBytes, st, tab, sa, sb);
-    else hipLaunchKernelGGL((train_chain_joint_kernel<PrecBF16, false>), grid, block, kChainLdsBytes, st, tab, sa, sb);
-  }
+void launch_joint_kernel(int prec, bool gauss, dim3 grid, dim3 block, hipStream_t st, const ChainModel* tab, const ChainStep& sa, const ChainStep& sb) {
+  V21_CHAIN_LAUNCH(train_chain_joint_kernel, PrecF16, PrecBF16, prec == V21_PREC_F16, gauss, kChainLdsBytes, grid, block, st, tab, sa, sb);
 }
 // one model's chain launch: training / validation (FEAT 0 or kChainGauss) or FORWARD mode (kChainOut | kChainGauss)
 template <class P>
@@ -715,15 +639,6 @@ int chain_attr(int prec) {
   done[prec] = true;
   return V21_OK;
 }
-// prefetcher workgroups per XCD for a launch of `models` x `ncons` row-block workgroups: the CUs the row blocks leave idle
-int chain_prefetchers(int ncons, int models) {
-  if (models > 1) return 0;  // a sweep: measured slower with them (8 models, 24 prefetchers each: 106 k -> 95 k model-steps/s)
-  const int idle = 256 - ncons;
-  static const char* env = getenv("V21_CHAIN_PREF");  // (diagnosis: prefetcher workgroups per XCD, 0 = none)
-  if (env) return std::max(0, std::min(atoi(env), idle / 8));
-  // (per XCD: none 45.6 us per f16 step at 4,096 rows, 2-4 43.4-43.6, 8 43.8-43.9, 16 44.2; f32 at batch 256: 46.4 / 42.6-42.8 / 42.9 / 43.4)
-  return idle >= 8 ? std::min(4, idle / 8) : 0;
-}
 // Large steps (fused_train.h): the packed stream of the virtual stack -- forward layers, then the activation-gradient
 // layers with the transposed weights -- is rebuilt from the arena (the previous step's Adam moved it), then one launch
 // carries 128 rows per workgroup through forward pass, loss and activation gradients.
@@ -743,19 +658,15 @@ static int launch_fused_train(v21_trainer* t, const float* x, long long ldx, con
   t->n_stream_packs += 1;
   PackArgs pa{};
   pa.w = m->d_w; pa.mean = nullptr; pa.stream = t->d_tstream;
-  pa.L = 2 * L - 1; pa.total = t->tstream_total; pa.padded = t->tstream_padded;
-  pa.fpi = 16; pa.epi = 8; pa.esize = 2; pa.is_bf16 = t->prec == V21_PREC_BF16; pa.all_hidden = 1; pa.fmt16 = t->train16 ? 1 : 0;
-  int f = 0;
-  for (int v = 0; v < 2 * L - 1; ++v) {
+  pa.L = 2 * L - 1; pa.total = t->ts.total; pa.padded = t->ts.padded;
+  pa.fpi = 16; pa.epi = 8; pa.esize = 2; pa.is_bf16 = t->prec == V21_PREC_BF16; pa.all_hidden = 1; pa.fmt16 = t->kind.train16 ? 1 : 0;
+  for (int v = 0; v < 2 * L - 1; ++v) {  // (routes.h: train_stream_layout -- the table the stream was sized from)
+    const TrainStreamLayer& y = t->ts.lt[v];
     const int l = v < L ? v : 2 * L - 1 - v;
     PackLayer& pl = pa.lt[v];
-    pl.K = v < L ? m->dims[l] : m->dims[l + 1]; pl.N = v < L ? m->dims[l + 1] : m->dims[l];
-    if (t->train16) { pl.ks = (pl.K + 31) / 32; pl.nt = (pl.N + 15) / 16; }
-    else { pl.ks = (pl.K + 15) / 16; pl.nt = (pl.N + 31) / 32; }
+    pl.K = y.K; pl.N = y.N; pl.ks = y.ks; pl.nt = y.nt; pl.first = y.first;
     pl.w_off = m->w_off[l]; pl.b_off = m->b_off[l];
     pl.flags = v < L ? 0 : 3;  // activation-gradient layer: transposed weights, no bias
-    pl.first = f;
-    f += pl.nt * (pl.ks + 1);
   }
   hipLaunchKernelGGL(pack_stream_kernel, dim3((pa.padded + 3) / 4), dim3(256), 0, st, pa);
   HIPCHK(hipGetLastError());
@@ -764,7 +675,7 @@ static int launch_fused_train(v21_trainer* t, const float* x, long long ldx, con
   static_cast<ChainModel&>(a) = chain_model(t);
   static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, m->dims[L], nullptr, row0);
   a.stamps = t->stamps_on ? t->d_stamps.get() : nullptr;  // (written by diagnostic builds only: -DV21_T_STAMPS)
-  a.fw = t->d_tstream; a.fw_bytes = (long long)t->tstream_padded * 1024;
+  a.fw = t->d_tstream; a.fw_bytes = (long long)t->ts.padded * 1024;
   // rows of the resident training set: the kernels gather their 16-bit copy
   if (t->d_x16 && ldx == m->dims[0] && x >= t->d_x[0] && x < t->d_x[0] + (size_t)t->n[0] * ldx && (x - t->d_x[0]) % ldx == 0) {
     a.x16 = t->d_x16 + (size_t)((x - t->d_x[0]) / ldx) * t->ldx16; a.ldx16 = t->ldx16;
@@ -773,7 +684,7 @@ static int launch_fused_train(v21_trainer* t, const float* x, long long ldx, con
       a.lt[0].ht16 = nullptr;
     }
   }
-  if (t->train_arch < 0) {  // instantiated at run time (jit.hip)
+  if (t->kind.train_arch < 0) {  // instantiated at run time (jit.hip)
     const hipError_t e = v21::jit_launch_train(t->train_jit, t->ctx->device, a, st);
     if (e != hipSuccess) {
       (void)hipGetLastError();
@@ -784,20 +695,19 @@ static int launch_fused_train(v21_trainer* t, const float* x, long long ldx, con
     }
     return V21_OK;
   }
-  if (t->train16) HIPCHK(g_train[t->train_arch].fn16[t->prec == V21_PREC_F16 ? 0 : 1](a, st));
-  else HIPCHK(g_train[t->train_arch].fn[t->prec == V21_PREC_F16 ? 0 : 1](a, st));
+  if (t->kind.train16) HIPCHK(g_train[t->kind.train_arch].fn16[t->prec == V21_PREC_F16 ? 0 : 1](a, st));
+  else HIPCHK(g_train[t->kind.train_arch].fn[t->prec == V21_PREC_F16 ? 0 : 1](a, st));
   return V21_OK;
 }
 // a 16-bit trainer's chain launch over a.rows rows: a training step, or (fwd = kChainFwd) a validation pass
-static int launch_chain(v21_trainer* t, ChainArgs& a, int fwd) {
+static int launch_chain(v21_trainer* t, ChainArgs& a, int fwd, const RouteEnv& e) {
   CHK(chain_attr(t->prec));
-  a.ncons = ((a.rows + 31) / 32 + 7) / 8 * 8;  // whole rounds of the 8 XCDs
-  a.npref = chain_prefetchers(a.ncons, 1);
+  const ChainLaunch p = plan_chain16(a.rows, 1, e);
+  a.ncons = p.ncons; a.npref = p.npref;
   const dim3 grid(a.ncons + 8 * a.npref), block(64 * kChainWaves);
   // (train_chain.h: FEAT -- a trainer's launch never needs the joint step's or FORWARD mode's code, and the variational
   //  head's only when the stack has one; V21_CHAIN_PLAIN=0: everything through the variational instantiation)
-  static const bool plain_ok = !(getenv("V21_CHAIN_PLAIN") && getenv("V21_CHAIN_PLAIN")[0] == '0');
-  const int feat = fwd | (plain_ok && t->gl < 0 ? 0 : kChainGauss);
+  const int feat = fwd | (e.chain_plain && t->kind.gl < 0 ? 0 : kChainGauss);
   if (t->prec == V21_PREC_F16) launch_chain_kernel<PrecF16>(feat, grid, block, t->ctx->stream, a);
   else launch_chain_kernel<PrecBF16>(feat, grid, block, t->ctx->stream, a);
   HIPCHK(hipGetLastError());
@@ -828,8 +738,8 @@ ChainModel chain_model32(v21_trainer* t) {
   a.stamps = t->stamps_on ? t->d_stamps.get() : nullptr;
   a.zcap_layer = -1;
   a.jobs = t->d_jobs;
-  if (t->gl >= 0) {
-    a.lt[t->gl].gauss = 1;
+  if (t->kind.gl >= 0) {
+    a.lt[t->kind.gl].gauss = 1;
     a.kl_weight = t->kl_weight; a.sample = t->sample; a.seed = t->seed; a.step = (unsigned long long)t->iter;
   }
   return a;
@@ -848,29 +758,18 @@ static int build_chain32s_jobs(v21_trainer* t) {
   HIPCHK(hipStreamSynchronize(t->ctx->stream));
   return V21_OK;
 }
-int launch_chain32_args(ChainArgs& a, hipStream_t st, bool small, int rows_per_wg) {
+int launch_chain32_args(ChainArgs& a, hipStream_t st, bool small, const RouteEnv& e) {
   CHK(chain_attr(V21_PREC_F32));
-  if (small) {  // the 8-row kernel (train_chain32s.h), or its 4-row form
-    // (routes.h decides for a trainer's steps; evaluation passes and other callers: by the row count, V21_C32S_ROWS forces)
-    const int force_rows = rows_per_wg ? rows_per_wg : RouteEnv::read().c32s_rows;
-    const int rpw = force_rows == 4 || force_rows == 8 ? force_rows : (a.rows <= kC32sRows4Max ? 4 : 8);
-    a.ncons = (int)((((long long)a.rows + rpw - 1) / rpw + 7) / 8 * 8);
-    a.npref = chain_prefetchers(a.ncons, 1);
+  const ChainLaunch p = small ? plan_chain32s(a.rows, 1, 1, e) : plan_chain32(a.rows, e);
+  a.ncons = p.ncons; a.npref = p.npref;
+  if (small) {  // the 8-row kernel (train_chain32s.h), or its 4-row form: a step's plan is the one decide_step named in its route
     bool gauss = false;  // (train_chain32s.h: GAUSS -- the variational head's code only where the stack has one)
     for (int l = 0; l < a.L; ++l) gauss = gauss || a.lt[l].gauss;
     const dim3 grid(a.ncons + 8 * a.npref), block(64 * kC32sWaves);
-    if (rpw == 4) {
-      if (gauss) hipLaunchKernelGGL((train_chain32s_kernel<4, true>), grid, block, kC32sLdsBytes, st, a);
-      else hipLaunchKernelGGL((train_chain32s_kernel<4, false>), grid, block, kC32sLdsBytes, st, a);
-    } else {
-      if (gauss) hipLaunchKernelGGL((train_chain32s_kernel<8, true>), grid, block, kC32sLdsBytes, st, a);
-      else hipLaunchKernelGGL((train_chain32s_kernel<8, false>), grid, block, kC32sLdsBytes, st, a);
-    }
+    V21_CHAIN_LAUNCH(train_chain32s_kernel, 4, 8, p.rows_per_wg == 4, gauss, kC32sLdsBytes, grid, block, st, a);
     HIPCHK(hipGetLastError());
     return V21_OK;
   }
-  a.ncons = (int)((((long long)a.rows + kC32Rows - 1) / kC32Rows + 7) / 8 * 8);  // whole rounds of the 8 XCDs
-  a.npref = chain_prefetchers(a.ncons, 1);
   const dim3 grid(a.ncons + 8 * a.npref), block(64 * kC32Waves);
   // (train_chain32.h: FEAT -- FORWARD mode, validation, training)
   if (a.out) hipLaunchKernelGGL((train_chain32_kernel<kChainFwd | kChainOut>), grid, block, kC32LdsBytes, st, a);
@@ -941,7 +840,7 @@ int launch_dw16(int prec, const std::vector<Dw16Args>& probs, hipStream_t st, co
     if (xr) grp.xr = *xr;
     blocks *= grp.p[0].nz;
     if (blocks <= 0) continue;
-    const dim3 grid((blocks + 7) / 8 * 8);  // whole rounds of the 8 XCDs (the kernels remap block ids XCD-wise)
+    const dim3 grid(xcd_rounds(blocks));  // (the kernels remap block ids XCD-wise)
     if (big) {
       if (prec == V21_PREC_F16) hipLaunchKernelGGL(gemm_dw16_lds_kernel<PrecF16>, grid, dim3(kDwThreads), kDwLdsTotal, st, grp);
       else hipLaunchKernelGGL(gemm_dw16_lds_kernel<PrecBF16>, grid, dim3(kDwThreads), kDwLdsTotal, st, grp);
@@ -994,7 +893,7 @@ static int launch_dw_adam(v21_trainer* t, int rows, int brows, float alpha, int 
   st.alpha[0] = alpha;
   st.out_scale[0] = 1.0f / grad_opscale(brows, t->mlp->dims[t->mlp->L]);
   st.sc = step_ctx(t);
-  const dim3 grid(md.order ? 8 * md.xper : (md.nblk + 7) / 8 * 8);
+  const dim3 grid(md.order ? 8 * md.xper : xcd_rounds(md.nblk));
   if (t->prec == V21_PREC_F16) hipLaunchKernelGGL(dw16_adam_kernel<PrecF16>, grid, dim3(64 * kDwAdamWaves), 0, t->ctx->stream, md, st);
   else hipLaunchKernelGGL(dw16_adam_kernel<PrecBF16>, grid, dim3(64 * kDwAdamWaves), 0, t->ctx->stream, md, st);
   HIPCHK(hipGetLastError());
@@ -1023,7 +922,7 @@ int launch_dw_adam_group(const std::vector<v21_trainer*>& tr, const DwAdamModel*
     stp.out_scale[k] = 1.0f / grad_opscale(brows, t->mlp->dims[t->mlp->L]);
     maxblk = std::max(maxblk, h_tab[k].nblk);
   }
-  const dim3 grid((maxblk + 7) / 8 * 8, (unsigned)tr.size());
+  const dim3 grid(xcd_rounds(maxblk), (unsigned)tr.size());
   const bool small = stp.steps <= 32;  // (dw_adam.h: U)
   const bool f16 = tr[0]->prec == V21_PREC_F16;
   if (small) {
@@ -1073,7 +972,7 @@ int dw32_model(const v21_trainer* t, int tile, Dw32Model& md) {
   ad.omb1 = 1.0f - t->adam.beta1; ad.omb2 = 1.0f - t->adam.beta2; ad.eps = t->adam.eps;
   ad.loss_acc = t->d_ticket; ad.loss_out = t->d_g + t->P; ad.loss_out2 = t->d_steploss;
   ad.loss_slot = -1;
-  ad.fmt = t->chain32s ? 4 : 3;
+  ad.fmt = t->kind.chain32s ? 4 : 3;
   return blocks;
 }
 
@@ -1173,7 +1072,7 @@ static int update16(v21_trainer* t, const StepRoute& r, int rows, int brows, con
 static int empty_step(v21_trainer* t, float* loss_out) {
   CHK(zero_grad(t));
   phase_mark(t, 1); phase_mark(t, 2);
-  const bool bucketed = t->chain && dp_bucketed(t);
+  const bool bucketed = t->kind.chain && dp_bucketed(t);
   if (bucketed) {  // (the same two messages as the ranks with rows)
     const size_t lo1 = (size_t)t->mlp->w_off[dp_split_layer(t->mlp)];
     CHK(dp_exchange_bucket(t, 0, lo1, t->P + 1));
@@ -1192,22 +1091,23 @@ static int train_on_rows(v21_trainer* t, const float* x, long long ldx, const fl
   v21_mlp* m = t->mlp;
   const int L = m->L, din = m->dims[0], dout = m->dims[L];
   if (rows > t->max_batch) return fail(V21_ERR_ARG, "batch of %d rows exceeds max_batch %d", rows, t->max_batch);
-  const bool per_layer = !t->chain && !t->chain32;
+  const bool per_layer = t->kind.per_layer();
   if (per_layer && rows > 0) CHK(gather_batch(t, x, ldx, y, ldy, rw, d_idx, first, rows));  // (ahead of the step's first mark)
   phase_mark(t, 0);
   if (rows == 0) return empty_step(t, loss_out);
-  const StepRoute route = step_route(t, rows);
+  const RouteEnv env = RouteEnv::read();  // once per step: the route and every launch shape below come from it
+  const StepRoute route = step_route(t, rows, env);
   note_route(t, route);
   const StepLoss loss = step_loss(t, route, loss_out);
   if (per_layer) {
     CHK(per_layer_step(t, y ? t->d_yb : t->d_h[0], y ? p16(dout) : p16(din), rows, brows, route, loss, row0));
-  } else if (t->chain32) {  // TR_CHAIN32, TR_CHAIN32S_8 / _4
+  } else if (t->kind.chain32) {  // TR_CHAIN32, TR_CHAIN32S_8 / _4
     CHK(ensure_copies(t, false));
     ChainArgs a{};
     static_cast<ChainModel&>(a) = chain_model32(t);
     static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, dout, t, row0);
     a.gs = 1.0f;  // fp32 operands: no scaling of the gradients
-    CHK(launch_chain32_args(a, t->ctx->stream, t->chain32s, route.fwd == TR_CHAIN32S_4 ? 4 : 8));
+    CHK(launch_chain32_args(a, t->ctx->stream, t->kind.chain32s, env));
     phase_mark(t, 1);
     CHK(update32(t, route, rows, loss));
   } else {  // TR_CHAIN16, TR_FUSED64 / TR_FUSED128
@@ -1219,10 +1119,10 @@ static int train_on_rows(v21_trainer* t, const float* x, long long ldx, const fl
     DwXRows xrows{};  // x16 != nullptr: this step's layer-0 gradient operand is gathered from the resident rows
     if (fused) {
       // (the LDS-staged gradient kernel only: launch_dw16 takes it from 64 batch steps of 16 rows on)
-      const bool want_xr = route.upd == UP_DW16_SPLITK && (rows + 15) / 16 >= 64 && RouteEnv::read().dw_xrows;
+      const bool want_xr = route.upd == UP_DW16_SPLITK && (rows + 15) / 16 >= 64 && env.dw_xrows;
       const int fr = launch_fused_train(t, x, ldx, y, ldy, rw, d_idx, first, rows, brows, row0, ts_fresh, want_xr ? &xrows : nullptr);
       if (fr != V21_OK) {
-        if (t->train_arch >= 0) return fr;
+        if (t->kind.train_arch >= 0) return fr;
         // the run-time kernel could not be loaded (it spills: marked failed): this step and every later one take the chain
         xrows = DwXRows{};
         t->kind.train_rt = false; t->train_jit = nullptr;
@@ -1234,7 +1134,7 @@ static int train_on_rows(v21_trainer* t, const float* x, long long ldx, const fl
       ChainArgs a{};
       static_cast<ChainModel&>(a) = chain_model(t);
       static_cast<ChainStep&>(a) = chain_step(x, ldx, y, ldy, rw, d_idx, first, rows, brows, dout, t, row0);
-      CHK(launch_chain(t, a, 0));
+      CHK(launch_chain(t, a, 0, env));
       if (!t->capturing) t->n_chain_steps += 1;
     }
     phase_mark(t, 1);
@@ -1244,7 +1144,7 @@ static int train_on_rows(v21_trainer* t, const float* x, long long ldx, const fl
 }
 int chain32_update(v21_trainer* t, int rows, float* loss_out) {
   if (rows == 0) { phase_mark(t, 0); return empty_step(t, loss_out); }
-  const StepRoute route = step_route(t, rows);
+  const StepRoute route = step_route(t, rows, RouteEnv::read());
   note_route(t, route);  // (the joint launch ran this model's chain: the update route is what is recorded)
   const StepLoss loss = step_loss(t, route, loss_out);
   CHK(update32(t, route, rows, loss));
@@ -1273,7 +1173,7 @@ int gather_batch(v21_trainer* t, const float* x, long long ldx, const float* y, 
 // cursor-tick node and the boundary between two graph launches cost more than they save).
 // ---------------------------------------------------------------------------------
 static bool graph_eligible(const v21_trainer* t) {
-  return t->graph_mode == 1 && t->ctx->nranks == 1 && t->gl < 0;
+  return t->graph_mode == 1 && t->ctx->nranks == 1 && t->kind.gl < 0;
 }
 static int ensure_desc(v21_trainer* t, long long n) {
   if (t->d_desc.n >= (size_t)n) return V21_OK;
@@ -1305,7 +1205,7 @@ static int step_graph(v21_trainer* t, const float* x, long long ldx, const float
       // The lazy refresh of the packed weight copies is NOT part of the captured step (it was a no-op while the
       // step was recorded): an arena rewritten between two replays (v21_mlp_set_weights, a loaded file) must reach
       // the copies before the replayed kernels read them.
-      CHK(ensure_copies(t, !t->chain && !t->chain32));  // (the chain trainers never read the NT copies: after_replay's nt_ok)
+      CHK(ensure_copies(t, t->kind.per_layer()));  // (the chain trainers never read the NT copies: after_replay's nt_ok)
       *out = g.exec;
       return V21_OK;
     }
@@ -1316,9 +1216,9 @@ static int step_graph(v21_trainer* t, const float* x, long long ldx, const float
   }
   hipStream_t st = t->ctx->stream;
   // everything that may not happen inside a capture: lazy refreshes, function attributes
-  CHK(ensure_copies(t, !t->chain && !t->chain32));
-  if (t->chain) { CHK(chain_attr(t->prec)); CHK(dw16_attr(t->prec)); }
-  if (t->chain32) CHK(chain_attr(V21_PREC_F32));
+  CHK(ensure_copies(t, t->kind.per_layer()));
+  if (t->kind.chain) { CHK(chain_attr(t->prec)); CHK(dw16_attr(t->prec)); }
+  if (t->kind.chain32) CHK(chain_attr(V21_PREC_F32));
   hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) { (void)hipGetLastError(); t->graph_mode = 0; return V21_OK; }  // e.g. the legacy stream: run eagerly
   t->capturing = true;
@@ -1347,7 +1247,7 @@ static int step_graph(v21_trainer* t, const float* x, long long ldx, const float
 static void after_replay(v21_trainer* t) {
   t->iter += 1;
   t->desc_next += 1;
-  weights_updated(t, !t->chain && !t->chain32);
+  weights_updated(t, t->kind.per_layer());
 }
 
 // every entry of an epoch's row table names a row of the training set (an entry outside it is a GPU memory fault in the
@@ -1446,19 +1346,20 @@ extern "C" int v21_trainer_eval(v21_trainer* t, int which, int batch, double* lo
   const long long n = t->n[which];
   const int din = m->dims[0], dout = m->dims[m->L];
   if (batch < 1) return fail(V21_ERR_ARG, "batch must be >= 1");
-  if (t->chain || t->chain32) {
+  if (!t->kind.per_layer()) {
     // ONE forward-only launch of the chain kernel over all n rows (csrc/train_chain.h, train_chain32.h: fwd_only) instead
     // of 8 launches per batch of the per-layer path: the same arithmetic as the training loss of this precision, no noise
     // drawn (a variational head evaluates z = z_mean: include/v21.h)
     if (n > (1ll << 30)) return fail(V21_ERR_ARG, "too many rows for one validation launch");
     CHK(ensure_copies(t, false));
     ChainArgs a{};
-    static_cast<ChainModel&>(a) = t->chain32 ? chain_model32(t) : chain_model(t);
+    static_cast<ChainModel&>(a) = t->kind.chain32 ? chain_model32(t) : chain_model(t);
     a.sample = 0;
     static_cast<ChainStep&>(a) = chain_step(t->d_x[which], din, t->y_is_x[which] ? nullptr : t->d_y[which], dout,
                                             t->d_rw[which], nullptr, 0, (int)n, (int)n, dout);
     a.fwd_only = 1;
-    CHK(t->chain32 ? launch_chain32_args(a, st, t->chain32s) : launch_chain(t, a, kChainFwd));
+    const RouteEnv env = RouteEnv::read();
+    CHK(t->kind.chain32 ? launch_chain32_args(a, st, t->kind.chain32s, env) : launch_chain(t, a, kChainFwd, env));
     return read_tickets({t}, n, loss);
   }
   const int b = std::min(batch, t->max_batch);
@@ -1570,14 +1471,14 @@ extern "C" int v21_trainer_get_grad(v21_trainer* t, float* g, size_t n) {
 
 extern "C" int v21_trainer_set_vae(v21_trainer* t, float kl_weight, int sample, uint64_t seed) {
   if (!t) return fail(V21_ERR_ARG, "null trainer");
-  if (t->gl < 0) return fail(V21_ERR_STATE, "the stack has no V21_ACT_GAUSS layer");
+  if (t->kind.gl < 0) return fail(V21_ERR_STATE, "the stack has no V21_ACT_GAUSS layer");
   if (!(kl_weight >= 0.f)) return fail(V21_ERR_ARG, "kl_weight must be >= 0");
   t->kl_weight = kl_weight; t->sample = sample ? 1 : 0; t->seed = (unsigned long long)seed;
   return V21_OK;
 }
 extern "C" int v21_trainer_enable_stamps(v21_trainer* t, int enable) {
   if (!t) return fail(V21_ERR_ARG, "null trainer");
-  if (!t->chain && !t->chain32) return fail(V21_ERR_STATE, "this trainer does not use the chain kernel");
+  if (t->kind.per_layer()) return fail(V21_ERR_STATE, "this trainer does not use the chain kernel");
   if (t->capturing) return fail(V21_ERR_STATE, "not while steps are being recorded");
   t->stamps_on = enable != 0;
   return V21_OK;
@@ -1585,7 +1486,7 @@ extern "C" int v21_trainer_enable_stamps(v21_trainer* t, int enable) {
 extern "C" int v21_trainer_chain_stamps(v21_trainer* t, uint64_t* out, int n) {
   if (!t || !out) return fail(V21_ERR_ARG, "null argument");
   if (n < 1 || n > kStampSlots) return fail(V21_ERR_ARG, "n must be in [1,%d]", kStampSlots);
-  if (!t->chain && !t->chain32) return fail(V21_ERR_STATE, "this trainer does not use the chain kernel");
+  if (t->kind.per_layer()) return fail(V21_ERR_STATE, "this trainer does not use the chain kernel");
   if (!t->stamps_on) return fail(V21_ERR_STATE, "stamps are off (v21_trainer_enable_stamps)");
   CHK(use(t->ctx));
   HIPCHK(hipMemcpyAsync(out, t->d_stamps, (size_t)n * 8, hipMemcpyDeviceToHost, t->ctx->stream));
@@ -1597,7 +1498,7 @@ extern "C" int v21_trainer_chain_stamps(v21_trainer* t, uint64_t* out, int n) {
 // < 0 = the real ones) -- a test hands in a truncated stream and expects V21_ERR_STATE, not a launch
 extern "C" int v21_debug_check_chain_jobs(v21_trainer* t, long long fw_bytes, long long bw_bytes) {
   if (!t) return fail(V21_ERR_ARG, "null trainer");
-  if (!t->chain32s) return fail(V21_ERR_UNSUPPORTED, "the trainer does not run the small-batch f32 chain (no job table)");
+  if (!t->kind.chain32s) return fail(V21_ERR_UNSUPPORTED, "the trainer does not run the small-batch f32 chain (no job table)");
   const ChainModel a = chain_model32(t);
   std::vector<C32sJob> tab((size_t)2 * a.L * kC32sWaves);
   c32s_build_jobs(a, tab.data());
@@ -1609,11 +1510,11 @@ extern "C" int v21_debug_check_chain_jobs(v21_trainer* t, long long fw_bytes, lo
 extern "C" int v21_trainer_jit(v21_trainer* t, int wait_ms, int* status) {
   if (!t || !status) return fail(V21_ERR_ARG, "null argument");
   *status = -1;
-  if (t->train_arch >= 0) { *status = 1; return V21_OK; }  // compiled into the library (archs.h)
+  if (t->kind.train_arch >= 0) { *status = 1; return V21_OK; }  // compiled into the library (archs.h)
   if (!t->train_jit) {
     std::string why = "the trainer was created with fewer rows per step than the kernel's threshold, or run-time compilation is switched off (V21_JIT=0)";
     if (t->prec == V21_PREC_F32) why = "f32 trainers have no fused training kernel";
-    else if (!t->chain) why = "the trainer is not on the chain path";
+    else if (!t->kind.chain) why = "the trainer is not on the chain path";
     else v21::jit_train_eligible(t->mlp->L, t->mlp->dims.data(), t->mlp->act.data(), &why);
     return fail(V21_ERR_UNSUPPORTED, "no fused training kernel for this trainer: %s", why.c_str());
   }
@@ -1684,7 +1585,7 @@ extern "C" int v21_debug_trainer_counters(v21_trainer* t, long long out[4]) {
 extern "C" int v21_trainer_use_graph(v21_trainer* t, int enable) {
   if (!t) return fail(V21_ERR_ARG, "null trainer");
   CHK(use(t->ctx));
-  if (enable && (t->ctx->nranks > 1 || t->gl >= 0))
+  if (enable && (t->ctx->nranks > 1 || t->kind.gl >= 0))
     return fail(V21_ERR_UNSUPPORTED, "captured steps need one rank and a stack without a variational layer");
   if (!enable) { HIPCHK(hipStreamSynchronize(t->ctx->stream)); destroy_graphs(t); }
   t->graph_mode = enable ? 1 : 0;

@@ -1,16 +1,18 @@
-// routes.h -- WHICH kernels a call takes, decided in ONE place (r5).
+// routes.h -- WHICH kernels a call takes and in WHAT SHAPE a training launch goes out, decided in ONE place (r5).
 //
 // The library has several kernels for the same arithmetic (VERDICT r4 "route and switch sprawl": five forward routes, seven
-// training routes, chosen from precision, row count, stack and rank count).  Until r5 every dispatch site computed its
-// own conditions; now the dispatch sites of api_forward.hip / api_trainer.hip / api_sweep.hip / api_joint.hip ask the
-// pure functions below and switch on the answer, and the same functions answer the queries of include/v21.h
-// (v21_route_forward / v21_route_train: no GPU needed), which is what tests/test_routes.py checks against the table of
-// INTEGRATION.md section 6 -- on the CPU against the decision, on the GPU against what was launched
-// (v21_trainer_last_route / v21_mlp_last_route are written by the launch sites themselves).
+// training routes, chosen from precision, row count, stack and rank count).  The dispatch sites of api_forward.hip /
+// api_trainer.hip / api_sweep.hip / api_joint.hip ask the pure functions below (no HIP call, no handle) and switch on the
+// answer -- also for rows per workgroup, workgroup counts and a sweep's shape: a launch site forms its grid from a
+// ChainLaunch and decides nothing itself.  The same functions answer the queries of include/v21.h (v21_route_forward /
+// v21_route_train: no GPU needed), which is what tests/test_routes.py checks against the table of INTEGRATION.md section 6
+// -- on the CPU against the decision, on the GPU against what was launched (v21_trainer_last_route / v21_mlp_last_route
+// are written by the launch sites themselves).
 //
-// Every environment switch that can change a route is read HERE (RouteEnv) and listed in INTEGRATION.md section 6; the
-// defaults are what ships, the switches exist for the tests (which force every kernel onto small cases) and for A/B
-// measurements.  Replaces nothing in the reference: Keras has one path (emulator.py:369-378, 402).
+// Every environment switch that can change a route or a launch shape is read HERE (RouteEnv) and listed in INTEGRATION.md
+// sections 5 and 6; the defaults are what ships, the switches exist for the tests (which force every kernel onto small
+// cases) and for A/B measurements.  A step, an epoch of a sweep or joint pair and an evaluation pass read it once and hand
+// it down.  Replaces nothing in the reference: Keras has one path (emulator.py:369-378, 402).
 #pragma once
 #include <cstdlib>
 // internal forward flag (never part of include/v21.h; v21_mlp_forward masks caller flags to 0xFF): see decide_forward
@@ -53,7 +55,7 @@ enum TrainUpdRoute {
 // k_chunk rows; one slice: no slab to sum)
 struct StepRoute { int fwd = TR_NONE, upd = UP_NONE; int tile = 32, nslice = 1, k_chunk = 0; };
 
-// Every environment switch that changes a route.  Read per decision (a getenv is ~0.1 us; the tests set them per case).
+// Every environment switch that changes a route or a launch shape.  Read per decision (a getenv is ~0.1 us; the tests set them per case).
 struct RouteEnv {
   int train_chain = 1;        // V21_TRAIN_CHAIN=0: per-layer training path for every trainer
   int fused_train = 1;        // V21_FUSED_TRAIN=0: no fused training kernel
@@ -67,6 +69,11 @@ struct RouteEnv {
   int jit = 1;                // V21_JIT=0: no run-time compilation (cached code objects are still used)
   int dw_xrows = 0;           // V21_DW_XROWS=1: a fused large step does not flush its layer-0 operand, the gradient launch gathers the resident rows (fewer bytes, measured slower)
   int sweep_streams = 2;      // V21_SWEEP_STREAMS=1: a sweep's grouped launches on one stream (default 2: two half-groups, api_sweep.hip)
+  int sweep32_group = 1;      // V21_SWEEP32_GROUP=0: f32 sweeps take one grouped launch per layer and phase
+  int chain_plain = 1;        // V21_CHAIN_PLAIN=0: 16-bit trainers launch the chain's variational instantiation whatever the stack
+  int chain_pref = -1;        // V21_CHAIN_PREF=n: prefetcher workgroups per XCD beside a chain's row blocks (-1: chain_prefetchers' own rule)
+  int dw_blocks = 1;          // V21_DW_BLOCKS=0: dw16_adam_kernel walks contiguous tile runs per XCD (no dw_tile_order)
+  int train_x16 = 1;          // V21_TRAIN_X16=0: the fused training kernels gather fp32 rows (no 16-bit copy of the training set)
   static RouteEnv read() {
     RouteEnv e;
     auto flag = [](const char* n, int dflt) { const char* v = getenv(n); return v ? (v[0] == '0' ? 0 : 1) : dflt; };
@@ -83,6 +90,11 @@ struct RouteEnv {
     e.jit = flag("V21_JIT", 1);
     e.dw_xrows = flag("V21_DW_XROWS", 0);
     e.sweep_streams = num("V21_SWEEP_STREAMS", 2) == 1 ? 1 : 2;
+    e.sweep32_group = flag("V21_SWEEP32_GROUP", 1);
+    e.chain_plain = flag("V21_CHAIN_PLAIN", 1);
+    if (const char* v = getenv("V21_CHAIN_PREF")) e.chain_pref = std::max(0, atoi(v));
+    e.dw_blocks = flag("V21_DW_BLOCKS", 1);
+    e.train_x16 = flag("V21_TRAIN_X16", 1);
     return e;
   }
 };
@@ -127,6 +139,54 @@ inline StepRoute plan_update32(int L, const int* dims, const int* act, int rows,
   return r;
 }
 
+// ---- the shape of a chain-family launch.  The kernels map workgroup numbers XCD-major: a launch is whole rounds of the 8 XCDs
+inline int xcd_rounds(long long blocks) { return (int)((blocks + 7) / 8 * 8); }
+constexpr int kChipWgs = 256;  // one round of the chip: a workgroup per CU (train_chain32s.h: kC32sRows4Max = 4 kChipWgs)
+// Rows per workgroup of train_chain32s_kernel and its forms: 4 while the 4-row blocks of all `models` models of the launch fit the
+// chip in one round, else 8; V21_C32S_ROWS forces.  models: 1 trainer step / evaluation, G sweep, 2 joint epoch (1 joint evaluation: see there)
+inline int c32s_rows(long long rows, int models, const RouteEnv& e) {
+  if (e.c32s_rows == 4 || e.c32s_rows == 8) return e.c32s_rows;
+  return (long long)models * ((rows + 3) / 4) <= kChipWgs ? 4 : 8;
+}
+// prefetcher workgroups per XCD beside `blocks` row-block workgroups: the CUs the row blocks leave idle
+inline int chain_prefetchers(int blocks, const RouteEnv& e) {
+  const int idle = kChipWgs - blocks;
+  if (e.chain_pref >= 0) return std::max(0, std::min(e.chain_pref, idle / 8));  // (diagnosis)
+  // (per XCD: none 45.6 us per f16 step at 4,096 rows, 2-4 43.4-43.6, 8 43.8-43.9, 16 44.2; f32 at batch 256: 46.4 / 42.6-42.8 / 42.9 / 43.4)
+  return idle >= 8 ? std::min(4, idle / 8) : 0;
+}
+// ncons: row-block workgroups PER MODEL; npref: prefetcher workgroups per XCD.  One model's grid is ncons + 8 npref; the joint
+// grids and a sweep's 8 ncons ceil(G / 8) are the launch sites' arithmetic on these.  pref_models: the models whose row blocks the
+// prefetchers sit beside -- 1 in a trainer's own launch, 2 in the 16-bit joint launch, 0 = none: the f32 group and joint kernels have
+// none, and a sweep of any size takes none (measured slower with them: 8 models, 24 prefetchers each: 106 k -> 95 k model-steps/s)
+struct ChainLaunch { int rows_per_wg, ncons, npref; };
+inline ChainLaunch chain_launch(long long rows, int rpw, int pref_models, const RouteEnv& e) {
+  const int ncons = xcd_rounds((rows + rpw - 1) / rpw);
+  return ChainLaunch{rpw, ncons, pref_models ? chain_prefetchers(pref_models * ncons, e) : 0};
+}
+// train_chain_kernel and its forms (32-row blocks), train_chain32_kernel (one model), train_chain32s_kernel and its forms
+inline ChainLaunch plan_chain16(long long rows, int pref_models, const RouteEnv& e) { return chain_launch(rows, 32, pref_models, e); }
+inline ChainLaunch plan_chain32(long long rows, const RouteEnv& e) { return chain_launch(rows, kC32Rows, 1, e); }
+inline ChainLaunch plan_chain32s(long long rows, int models, int pref_models, const RouteEnv& e) {
+  return chain_launch(rows, c32s_rows(rows, models, e), pref_models, e);
+}
+
+// ---- the shape of a sweep's or joint pair's epoch.  f32 models on the small-batch chain (a sweep: every member, at most
+// kNtMaxGroup layers): one grouped chain launch + one grouped gradient / Adam launch per step (`enabled`: V21_SWEEP32_GROUP) -- the
+// answer BEFORE the per-member tile check: a model whose gradient launch would take 64 x 64 tiles (refresh_dw32_table) ungroups the epoch
+inline bool decide_group32(bool chain32s, int nranks, int batch, bool enabled = true) {
+  return chain32s && nranks == 1 && batch <= kDw32MaxRows && enabled;
+}
+// grouped: the sweep's steps are grouped chain launches (16-bit members, or group32 after the tile check).  two_streams: as two
+// half-groups on two streams (api_sweep.hip: v21_sweep::s2); small_slabs: the 128-row dwadam32_group_kernel (dw_adam32.h: SLAB)
+struct SweepShape { bool two_streams, small_slabs; };
+inline SweepShape decide_sweep(bool grouped, int members, int nranks, const RouteEnv& e) {
+  // (below 16 members the second stream's hand-overs cost more than they hide: tiny members, 8 per group: 17.4 -> 23.6 us per step)
+  // (dw_adam32.h: SLAB -- from 8 members on the gradient launch is deep enough for four or five workgroups per CU to pay: r5,
+  //  f32, batch 256, 8 / 16 / 32 / 64 members 60 / 70-72 / 70 / 64-67 k -> 62-66 / 79 / 77-79 / 72-73 k model-steps/s)
+  return SweepShape{nranks == 1 && grouped && members >= 16 && e.sweep_streams == 2, members >= 8};
+}
+
 // What a trainer commits to when it is created (buffers and packed stream formats depend on it).
 struct TrainerKind {
   bool chain = false;     // 16-bit chain path (train_chain.h) -- otherwise per-layer
@@ -136,6 +196,8 @@ struct TrainerKind {
   bool train_rt = false;  // the fused training kernel may be instantiated at run time for this stack (jit.hip)
   bool train16 = false;   // the fused training kernel on 16 rows per wave
   int gl = -1;            // the V21_ACT_GAUSS layer or -1
+  bool per_layer() const { return !chain && !chain32; }           // no chain kernel: one NT launch per layer and direction
+  bool fused() const { return train_arch >= 0 || train_rt; }      // a fused training kernel, compiled in or instantiated at run time
 };
 // defined in api_trainer.hip: the registry of compiled fused training kernels / eligibility for run-time instantiation
 int fused_train_arch_of(int L, const int* dims, const int* act);
@@ -185,14 +247,13 @@ inline StepRoute decide_step(const TrainerKind& k, int L, const int* dims, const
   if (k.chain32) {
     r = plan_update32(L, dims, act, rows, nranks, e);
     if (k.chain32s) {
-      const int rpw = e.c32s_rows == 4 || e.c32s_rows == 8 ? e.c32s_rows : (rows <= kC32sRows4Max ? 4 : 8);
-      r.fwd = rpw == 4 ? TR_CHAIN32S_4 : TR_CHAIN32S_8;
+      r.fwd = c32s_rows(rows, 1, e) == 4 ? TR_CHAIN32S_4 : TR_CHAIN32S_8;
     } else {
       r.fwd = TR_CHAIN32;
     }
     return r;
   }
-  if (!k.chain) {
+  if (k.per_layer()) {
     const NtSlices sl = nt_slices(rows, false);
     r.fwd = TR_PER_LAYER; r.upd = UP_PER_LAYER; r.nslice = sl.nslice; r.k_chunk = sl.k_chunk;
     return r;
@@ -202,13 +263,75 @@ inline StepRoute decide_step(const TrainerKind& k, int L, const int* dims, const
   // 80 us, 12,288 rows 72 against 83, 16,384 rows 78-82 against 90-92), 16,384 rows for one on the 128-row kernel
   // (24,576 rows 101 against 127 us, 32,768 rows 123-130 against 152-160; autoencoder stack, f16, whole steps, r4)
   const int fused_rows = e.fused_train_rows >= 0 ? e.fused_train_rows : (k.train16 ? 8193 : 16384);
-  const bool fused = (k.train_arch >= 0 || k.train_rt) && fused_ready && rows >= fused_rows && !capturing;
+  const bool fused = k.fused() && fused_ready && rows >= fused_rows && !capturing;
   r.fwd = fused ? (k.train16 ? TR_FUSED64 : TR_FUSED128) : TR_CHAIN16;
   // one rank, nothing to exchange: gradients, Adam and the packed copies in one launch -- up to the batch where its
   // 32 x 32 tiles, each pulling its operands over the WHOLE batch through one CU, lose to the 128 x 128 LDS-staged
   // split-K kernel + an Adam launch that sums the slabs
   r.upd = (nranks == 1 && (rows < e.dw_split_rows || capturing) && !fused) ? UP_DW16_ADAM : UP_DW16_SPLITK;
   return r;
+}
+
+// ---- host-built tables of a 16-bit chain trainer (v21_trainer_create), pure functions of the stack
+// The packed stream of the fused training kernels (fused_train.h / fused_train16.h): the virtual stack -- the L forward
+// layers, then the L - 1 activation-gradient layers from the top down -- in fragments of 1,024 bytes.  Virtual layer v:
+// K -> N over ks contraction steps (16 wide; 32 in the 16-rows-per-wave format) and nt feature tiles (32 wide; 16), its
+// fragments from `first` on.  The trainer sizes its buffer from this table; the packer and the Adam pass write by it.
+struct TrainStreamLayer { int K, N, ks, nt, first; };
+struct TrainStream { std::vector<TrainStreamLayer> lt; int total = 0, padded = 0; };  // fragments; padded to whole rounds of 8
+inline TrainStream train_stream_layout(int L, const int* dims, bool train16) {
+  TrainStream s;
+  for (int v = 0; v < 2 * L - 1; ++v) {
+    const int l = v < L ? v : 2 * L - 1 - v;
+    TrainStreamLayer y;
+    y.K = v < L ? dims[l] : dims[l + 1]; y.N = v < L ? dims[l + 1] : dims[l];
+    y.ks = train16 ? (y.K + 31) / 32 : (y.K + 15) / 16; y.nt = train16 ? (y.N + 15) / 16 : (y.N + 31) / 32;
+    y.first = s.total;
+    s.total += y.nt * (y.ks + 1);
+    s.lt.push_back(y);
+  }
+  s.padded = (s.total + 7) / 8 * 8;
+  return s;
+}
+// Tile order of dw16_adam_kernel: per layer the R x C grid of 32 x 32 tiles of [dW; db] in 8 blocks (rb x cb = 8, the shape
+// with the least operand rows per block), the blocks handed to the XCDs largest first onto the least loaded XCD.
+// Returns 8 runs of xper = size / 8 tile numbers (-1: none).
+inline std::vector<int> dw_tile_order(int L, const int* dims, const int* act) {
+  std::vector<std::vector<int>> per(8);
+  int first = 0;
+  for (int l = 0; l < L; ++l) {
+    const int R = (dims[l] + 1 + 31) / 32, C = (route_nw(dims, act, l) + 31) / 32;
+    int brb = 8, bcb = 1; double best = 1e30;
+    for (int rb : {1, 2, 4, 8}) {
+      const int cb = 8 / rb;
+      const double cost = std::ceil((double)R / rb) + std::ceil((double)C / cb);
+      if (cost < best) { best = cost; brb = rb; bcb = cb; }
+    }
+    std::vector<std::vector<int>> blocks(8);
+    for (int i = 0; i < brb; ++i)
+      for (int j = 0; j < bcb; ++j)
+        for (int ti = R * i / brb; ti < R * (i + 1) / brb; ++ti)
+          for (int tj = C * j / bcb; tj < C * (j + 1) / bcb; ++tj) blocks[i * bcb + j].push_back(first + ti * C + tj);
+    std::sort(blocks.begin(), blocks.end(), [](const std::vector<int>& a, const std::vector<int>& b) { return a.size() > b.size(); });
+    for (auto& b : blocks) {
+      int xmin = 0;
+      for (int x = 1; x < 8; ++x) if (per[x].size() < per[xmin].size()) xmin = x;
+      per[xmin].insert(per[xmin].end(), b.begin(), b.end());
+    }
+    first += R * C;
+  }
+  size_t xper = 0;
+  for (auto& v : per) xper = std::max(xper, v.size());
+  std::vector<int> order(8 * xper, -1);
+  for (int x = 0; x < 8; ++x) std::copy(per[x].begin(), per[x].end(), order.begin() + x * xper);
+  return order;
+}
+// Feature K of a layer's input operand in the chain's fragment order (train_chain.h): the constant row of ones that turns
+// [dW; db] into one contraction -- one feature tile of BS groups of 16 rows with element K % 32 of every row set to `one`
+inline std::vector<unsigned short> ones_tile16(int K, long long BS, unsigned short one) {
+  std::vector<unsigned short> tile((size_t)BS * 512, 0);
+  for (long long b = 0; b < BS * 16; ++b) tile[(size_t)((b >> 4) * 64 + ((b >> 3) & 1) * 32 + (K & 31)) * 8 + (b & 7)] = one;
+  return tile;  // (only element f % 32 == K % 32 of the last feature tile is set; the chain kernel writes features < K only)
 }
 
 // ---- forward.  jit: 0 = no run-time kernel for this stack (not eligible / switched off / failed), 1 = being compiled,
