@@ -38,11 +38,7 @@ static int ensemble_shape(int W, int din, long long n, bool has_data, long long 
 
 extern "C" int v21_route_ensemble(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
                                   int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows) {
-  if (!dims || !act || !route) return fail(V21_ERR_ARG, "null argument");
-  if (n_layers < 1 || n_layers > 16) return fail(V21_ERR_ARG, "n_layers %d out of range", n_layers);
-  for (int l = 0; l <= n_layers; ++l)
-    if (dims[l] < 1) return fail(V21_ERR_ARG, "dims[%d] = %d", l, dims[l]);
-  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
+  CHK(route_query_args(route, n_layers, dims, act, precision));
   if (n < 0 || n_data < 0 || n_modes < 0 || n_modes > 8) return fail(V21_ERR_ARG, "n = %lld, n_data = %lld, n_modes = %d", (long long)n, (long long)n_data, n_modes);
   if (dims[0] > kFitMaxIn) return fail(V21_ERR_UNSUPPORTED, "sample_ensemble: %d inputs (at most %d)", dims[0], kFitMaxIn);
   CHK(call_data_args("sample_ensemble", n, n_data > 0, n_data));

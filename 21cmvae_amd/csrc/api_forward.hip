@@ -1,36 +1,7 @@
 // api_forward.hip -- dense stacks (v21_mlp_*) and the forward routes of include/v21.h: the fused kernels compiled into
-// the library (fused_inst.hip) or instantiated at run time (jit.h), the table-driven one-launch forward (the chain
+// the library (compiled.h) or instantiated at run time (jit.h), the table-driven one-launch forward (the chain
 // kernels in FORWARD mode), the few-row latency route and the per-layer route.
 #include "api_internal.h"
-
-// ---------------------------------------------------------------------------------
-// fused-kernel registry
-// ---------------------------------------------------------------------------------
-namespace v21 {
-#define V21_DECL(a)                                                      \
-  hipError_t launch_fused_##a##_F32(const FusedArgs&, hipStream_t);      \
-  hipError_t launch_fused_##a##_F16x2sp(const FusedArgs&, hipStream_t);  \
-  hipError_t launch_fused_##a##_BF16x2sp(const FusedArgs&, hipStream_t);
-V21_ARCH_LIST(V21_DECL)
-#undef V21_DECL
-// the headline stack's 16-bit kernels with per-workgroup clock stamps (fused_fwd.h: CLOCK_STAMPS; v21_debug_forward_clocked)
-hipError_t launch_fused_S1_F16x2spClk(const FusedArgs&, hipStream_t);
-hipError_t launch_fused_S1_BF16x2spClk(const FusedArgs&, hipStream_t);
-}  // namespace v21
-
-typedef hipError_t (*fused_launcher)(const FusedArgs&, hipStream_t);
-struct FusedEntry {
-  int L;
-  const int* dims;
-  const int* act;
-  // per precision: f32 = one wave per SIMD on the exact f32 MFMA; f16 / bf16 = two workgroups per CU,
-  // one column tile per wave, ring refill spread over the block being consumed (fused_fwd.h: "x2sp")
-  fused_launcher fn[3];
-};
-#define V21_ENTRY(a) \
-  {Arch##a::L, Arch##a::dims, Arch##a::act, {launch_fused_##a##_F32, launch_fused_##a##_F16x2sp, launch_fused_##a##_BF16x2sp}},
-static const FusedEntry g_fused[] = {V21_ARCH_LIST(V21_ENTRY)};
-#undef V21_ENTRY
 
 // ---------------------------------------------------------------------------------
 // dense stack
@@ -44,34 +15,21 @@ static void stream_geometry(const v21_mlp* m, int prec, int* total, int* padded)
   *padded = (f + 7) / 8 * 8;  // whole DMA rounds of the 4- and 8-wave kernels (fused_fwd.h: Geo::padded)
 }
 
-// archs.h: the compiled fused forward kernel of this stack, or -1
-static int fused_id_of(int n_layers, const int* dims, const int* act) {
-  for (size_t i = 0; i < sizeof(g_fused) / sizeof(g_fused[0]); ++i) {
-    const FusedEntry& fe = g_fused[i];
-    if (fe.L != n_layers) continue;
-    bool same = true;
-    for (int k = 0; k <= n_layers && same; ++k) same = fe.dims[k] == dims[k];
-    for (int k = 0; k < n_layers && same; ++k) same = fe.act[k] == act[k];
-    if (same) return (int)i;
-  }
-  return -1;
-}
 // ---- routes (csrc/routes.h) through the C ABI: pure host logic, no GPU needed
-static int check_stack_desc(int n_layers, const int* dims, const int* act) {
-  if (!dims || !act) return fail(V21_ERR_ARG, "null argument");
+int route_query_args(bool ptrs, int n_layers, const int* dims, const int* act, int precision) {
+  if (!ptrs || !dims || !act) return fail(V21_ERR_ARG, "null argument");
   if (n_layers < 1 || n_layers > 16) return fail(V21_ERR_ARG, "n_layers %d out of range", n_layers);
   for (int l = 0; l <= n_layers; ++l)
     if (dims[l] < 1) return fail(V21_ERR_ARG, "dims[%d] = %d", l, dims[l]);
-  for (int l = 0; l < n_layers; ++l)
-    if (act[l] < 0 || act[l] > V21_ACT_GAUSS) return fail(V21_ERR_ARG, "act[%d] = %d unknown", l, act[l]);
+  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
   return V21_OK;
 }
 extern "C" int v21_route_forward(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int rt_ready, int* route) {
-  if (!route) return fail(V21_ERR_ARG, "null argument");
-  CHK(check_stack_desc(n_layers, dims, act));
-  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
+  CHK(route_query_args(route, n_layers, dims, act, precision));
+  for (int l = 0; l < n_layers; ++l)
+    if (act[l] < 0 || act[l] > V21_ACT_GAUSS) return fail(V21_ERR_ARG, "act[%d] = %d unknown", l, act[l]);
   const int out = dims[n_layers];
-  FwdQuery q{n_layers, dims, act, fused_id_of(n_layers, dims, act) >= 0, rt_ready ? 2 : 0, precision, (long long)n, flags & 0xFF, (long long)out};
+  FwdQuery q{n_layers, dims, act, compiled_index(g_infer, n_layers, dims, act) >= 0, rt_ready ? 2 : 0, precision, (long long)n, flags & 0xFF, (long long)out};
   if (q.jit == 2) {
     std::string why;
     if (!v21::jit_eligible(n_layers, dims, act, &why)) q.jit = 0;
@@ -124,7 +82,7 @@ extern "C" int v21_mlp_create(v21_ctx* ctx, int n_layers, const int* dims, const
   m->nparams = (size_t)o;
   m->maxdim = *std::max_element(m->dims.begin(), m->dims.end());
   CHK(m->d_w.zeroed(m->nparams + kArenaPad, ctx->stream));
-  m->fused_id = fused_id_of(n_layers, dims, act);
+  m->fused_id = compiled_index(g_infer, n_layers, dims, act);
   *out = m.release();
   return V21_OK;
 }
@@ -421,10 +379,10 @@ static int forward_rows(v21_mlp* m, const float* d_x, long long ldx, long long n
   }
   if (m->clk_stamps) {  // v21_debug_forward_clocked: the clock-stamped instantiation of the same kernel
     a.dbg = m->clk_stamps;
-    HIPCHK((precision == V21_PREC_F16 ? launch_fused_S1_F16x2spClk : launch_fused_S1_BF16x2spClk)(a, m->ctx->stream));
+    HIPCHK((precision == V21_PREC_F16 ? launch_Fwd_S1_F16x2spClk : launch_Fwd_S1_BF16x2spClk)(a, m->ctx->stream));
     return V21_OK;
   }
-  HIPCHK(g_fused[m->fused_id].fn[precision](a, m->ctx->stream));
+  HIPCHK(g_infer[m->fused_id].fwd[precision](a, m->ctx->stream));
   return V21_OK;
 }
 extern "C" int v21_mlp_forward_dev(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_y, int64_t ldy,
@@ -435,7 +393,7 @@ extern "C" int v21_mlp_forward_dev(v21_mlp* m, const float* d_x, int64_t ldx, in
 extern "C" int v21_debug_forward_clocked(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_y, int64_t ldy, int precision,
                                          int flags, unsigned long long* d_stamps) {
   if (!m || !d_stamps) return fail(V21_ERR_ARG, "null argument");
-  if (m->fused_id < 0 || g_fused[m->fused_id].dims != ArchS1::dims || (precision != V21_PREC_F16 && precision != V21_PREC_BF16))
+  if (m->fused_id < 0 || g_infer[m->fused_id].dims != ArchS1::dims || (precision != V21_PREC_F16 && precision != V21_PREC_BF16))
     return fail(V21_ERR_UNSUPPORTED, "clock-stamped kernels exist for the headline stack (archs.h S1) in f16 / bf16 only");
   if (flags & (V21_FWD_FORCE_GENERIC | V21_FWD_FORCE_CHAIN | V21_FWD_FORCE_JIT)) return fail(V21_ERR_ARG, "route flags do not apply");
   m->clk_stamps = d_stamps;

@@ -2,8 +2,10 @@
 // now api_base.hip (errors, contexts, memory, events, communicator, diagnostics), api_forward.hip (dense stacks and the
 // forward routes), api_trainer.hip (trainers, the step machinery, captured steps), api_sweep.hip and api_joint.hip --
 // all behind the unchanged include/v21.h).  Kernels live in the headers included below; a kernel template is
-// instantiated by the unit that launches it, non-template kernels have internal linkage.  Device memory of a handle is
-// owned by its Dev members (below): nothing here or in the units frees a handle's buffer by hand.
+// instantiated by the unit that launches it, non-template kernels have internal linkage.  The fused kernels of archs.h
+// are the exception: fused_inst.hip instantiates them, one object each, from the family traits of fused_families.h, and
+// the units reach them through the launcher tables of compiled.h.  Device memory of a handle is owned by its Dev
+// members (below): nothing here or in the units frees a handle's buffer by hand.
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -24,7 +26,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/v21.h"
 #pragma GCC visibility pop
-#include "archs.h"
+#include "compiled.h"
 #include "fused_fwd.h"
 #include "jit.h"
 #include "gemm.h"
@@ -265,6 +267,9 @@ static inline ChainLayout chain_layout(const v21_mlp* m, ChainFmt fmt) {
   y.fw_bytes = of * y.esize(); y.bw_bytes = ob * y.esize();
   return y;
 }
+// api_forward.hip: what every route query (v21_route_*) checks first -- its pointers, n_layers in 1 .. 16, widths >= 1,
+// precision 0 .. 2 (V21_ERR_ARG)
+int route_query_args(bool ptrs, int n_layers, const int* dims, const int* act, int precision);
 // api_forward.hip: fused_fwd's packed weight stream of this stack (built on first use)
 int mlp_fused_stream(v21_mlp* m, int prec, const unsigned char** stream);
 // api_jacobian.hip, shared with api_fit.hip and api_loglike.hip.  The host forms work in chunks of kJacHostChunk rows; the likelihood
@@ -274,7 +279,7 @@ constexpr long long kNoPitch = LLONG_MAX;  // jac_args: the pitch of rows a call
 // what an entry point is checked for beyond its arguments: its in_dim limit, whether it reads the likelihood record,
 // and whether it is a fit (input transform required, state checked even for n == 0)
 struct JacEntry { const char* name; int max_in; bool like, fit; };
-// archs.h holds this stack: it has compiled fused kernels (forward, ln L variant, Jacobian)
+// archs.h holds this stack: it has compiled fused kernels (a row of compiled.h's g_infer: forward, ln L variant, Jacobian)
 bool jac_fused_compiled(int L, const int* dims, const int* act);
 // the checks of all eight entry points: the pointers they require (ptrs), n >= 0, pitches (ldx, ldy; host rows:
 // kNoPitch) and x_dtype, the entry's in_dim limit, then -- from here on only for n > 0, except for a fit -- precision and

@@ -10,36 +10,10 @@
 #include "jac_generic.h"
 #include "reduce_kernels.h"
 
-namespace v21 {
-#define V21_DECL(a)                                                                \
-  hipError_t launch_jac_##a##_F32(const JacArgs&, hipStream_t);              \
-  hipError_t launch_jac_##a##_F16x2sp(const JacArgs&, hipStream_t);          \
-  hipError_t launch_jac_##a##_BF16x2sp(const JacArgs&, hipStream_t);
-V21_ARCH_LIST(V21_DECL)
-#undef V21_DECL
-}  // namespace v21
-
-typedef hipError_t (*jac_launcher)(const JacArgs&, hipStream_t);
-// in the order of V21_ARCH_LIST, i.e. of v21_mlp::fused_id (api_forward.hip: g_fused)
-#define V21_ENTRY(a) {launch_jac_##a##_F32, launch_jac_##a##_F16x2sp, launch_jac_##a##_BF16x2sp},
-static const jac_launcher g_jac[][3] = {V21_ARCH_LIST(V21_ENTRY)};
-#undef V21_ENTRY
-
-bool jac_fused_compiled(int L, const int* dims, const int* act) {
-#define V21_MATCH(a)                                                                              \
-  if (L == Arch##a::L && std::equal(dims, dims + L + 1, Arch##a::dims) && std::equal(act, act + L, Arch##a::act)) \
-    return true;
-  V21_ARCH_LIST(V21_MATCH)
-#undef V21_MATCH
-  return false;
-}
+bool jac_fused_compiled(int L, const int* dims, const int* act) { return compiled_index(g_infer, L, dims, act) >= 0; }
 
 extern "C" int v21_route_jacobian(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int* route) {
-  if (!dims || !act || !route) return fail(V21_ERR_ARG, "null argument");
-  if (n_layers < 1 || n_layers > 16) return fail(V21_ERR_ARG, "n_layers %d out of range", n_layers);
-  for (int l = 0; l <= n_layers; ++l)
-    if (dims[l] < 1) return fail(V21_ERR_ARG, "dims[%d] = %d", l, dims[l]);
-  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
+  CHK(route_query_args(route, n_layers, dims, act, precision));
   (void)n;
   *route = decide_jacobian(jac_fused_compiled(n_layers, dims, act), dims[0], flags & 0xFF, dims[n_layers]);
   return V21_OK;
@@ -132,7 +106,7 @@ static int jac_run(v21_mlp* m, int route, long long r0, long long n, float* y, l
     CHK(mlp_fused_stream(m, prec, &a.stream));
     a.out_std = tout ? m->out_std : 1.0f;
     a.out_mean_scale = tout ? 1.0f : 0.0f;
-    HIPCHK(g_jac[m->fused_id][prec](a, st));
+    HIPCHK(g_infer[m->fused_id].jac[prec](a, st));
     return V21_OK;
   }
   // the stack, tangents per workgroup and LDS size (and the kernel's LDS attribute, once per device)

@@ -1,35 +1,16 @@
 // api_loglike.hip -- the forward-only Gaussian log-likelihood (include/v21.h: v21_mlp_loglike_fwd[_dev],
 // v21_route_loglike_fwd, v21_mlp_last_lnl_route): ln L without its gradient, the call nested samplers, ensemble samplers
 // and importance sampling make.  Routes: csrc/routes.h (decide_loglike_fwd) -- the ln L variant of fused_fwd<Arch, Prec>
-// (fused_lnl_inst.hip), which reduces chi-square in the output layer's epilogue and writes 4 bytes per row, for the
+// (compiled.h: the Lnl family), which reduces chi-square in the output layer's epilogue and writes 4 bytes per row, for the
 // stacks of archs.h whose data are uniform per 128-row workgroup; for everything else the forward on its own route
 // into the likelihood workspace, y only, then lnl_reduce_kernel (reduce_kernels.h).  The host path is the Jacobian
 // side's: jac_args, call_data, jac_chunks, to_host and the lk_ws workspace (api_internal.h).
 #include "api_internal.h"
 #include "reduce_kernels.h"
 
-namespace v21 {
-#define V21_DECL(a)                                                        \
-  hipError_t launch_lnl_##a##_F32Lnl(const FusedArgs&, hipStream_t);       \
-  hipError_t launch_lnl_##a##_F16x2spLnl(const FusedArgs&, hipStream_t);   \
-  hipError_t launch_lnl_##a##_BF16x2spLnl(const FusedArgs&, hipStream_t);
-V21_ARCH_LIST(V21_DECL)
-#undef V21_DECL
-}  // namespace v21
-
-typedef hipError_t (*lnl_launcher)(const FusedArgs&, hipStream_t);
-// in the order of V21_ARCH_LIST, i.e. of v21_mlp::fused_id
-#define V21_ENTRY(a) {launch_lnl_##a##_F32Lnl, launch_lnl_##a##_F16x2spLnl, launch_lnl_##a##_BF16x2spLnl},
-static const lnl_launcher g_lnl[][3] = {V21_ARCH_LIST(V21_ENTRY)};
-#undef V21_ENTRY
-
 extern "C" int v21_route_loglike_fwd(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_modes,
                                      int flags, int* route) {
-  if (!dims || !act || !route) return fail(V21_ERR_ARG, "null argument");
-  if (n_layers < 1 || n_layers > 16) return fail(V21_ERR_ARG, "n_layers %d out of range", n_layers);
-  for (int l = 0; l <= n_layers; ++l)
-    if (dims[l] < 1) return fail(V21_ERR_ARG, "dims[%d] = %d", l, dims[l]);
-  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
+  CHK(route_query_args(route, n_layers, dims, act, precision));
   if (n < 0 || n_data < 0 || n_modes < 0 || n_modes > 8) return fail(V21_ERR_ARG, "n = %lld, n_data = %lld, n_modes = %d", (long long)n, (long long)n_data, n_modes);
   CHK(call_data_args("loglike_fwd", n, n_data > 0, n_data));
   *route = decide_loglike_fwd(jac_fused_compiled(n_layers, dims, act), dims[0], n_modes, n_data > 0 ? n / n_data : 0, n, flags & 0xFF);
@@ -71,7 +52,7 @@ int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n,
     a.lnl_d = cd.d; a.lnl_w = m->lk_w.get(); a.lnl_ld = cd.ld;
     a.lnl_wg0 = (unsigned)(row0 / kLnlWgRows);
     a.lnl_wgpd = cd.ld ? (unsigned)(cd.rpd / kLnlWgRows) : 1u;
-    HIPCHK(g_lnl[m->fused_id][prec](a, st));
+    HIPCHK(g_infer[m->fused_id].lnl[prec](a, st));
     return V21_OK;
   }
   // the forward's own route for these rows and flags, slice by slice into the workspace (y only), each slice reduced

@@ -2,32 +2,8 @@
 // fp32 chains), the exchange of data-parallel ranks, captured steps (hipGraph), the Keras-fit()-shaped epoch driver.
 #include "api_internal.h"
 
-// ---- compiled fused training kernels (fused_train.h, one translation unit each: fused_train_inst.hip)
-namespace v21 {
-#define V21_TDECL(a)                                                             \
-  hipError_t launch_fused_train_##a##_F16t(const ChainArgs&, hipStream_t);      \
-  hipError_t launch_fused_train_##a##_BF16t(const ChainArgs&, hipStream_t);     \
-  hipError_t launch_fused_train16_##a##_F16t16(const ChainArgs&, hipStream_t);  \
-  hipError_t launch_fused_train16_##a##_BF16t16(const ChainArgs&, hipStream_t);
-V21_TRAIN_ARCH_LIST(V21_TDECL)
-#undef V21_TDECL
-}  // namespace v21
-typedef hipError_t (*train_launcher)(const ChainArgs&, hipStream_t);
-struct TrainEntry { int L; const int* dims; const int* act; train_launcher fn[2]; /* f16, bf16 */ train_launcher fn16[2]; /* 16 rows per wave */ };
-#define V21_TENTRY(a) {Arch##a::L, Arch##a::dims, Arch##a::act, {launch_fused_train_##a##_F16t, launch_fused_train_##a##_BF16t}, \
-                       {launch_fused_train16_##a##_F16t16, launch_fused_train16_##a##_BF16t16}},
-static const TrainEntry g_train[] = {V21_TRAIN_ARCH_LIST(V21_TENTRY)};
-#undef V21_TENTRY
-// routes.h: which compiled fused training kernel serves this stack (-1: none)
-int v21::fused_train_arch_of(int L, const int* dims, const int* act) {
-  for (size_t e = 0; e < sizeof(g_train) / sizeof(g_train[0]); ++e) {
-    bool same = g_train[e].L == L;
-    for (int l = 0; same && l <= L; ++l) same = g_train[e].dims[l] == dims[l];
-    for (int l = 0; same && l < L; ++l) same = g_train[e].act[l] == act[l];
-    if (same) return (int)e;
-  }
-  return -1;
-}
+// routes.h: which compiled fused training kernel (compiled.h: g_train) serves this stack (-1: none)
+int v21::fused_train_arch_of(int L, const int* dims, const int* act) { return compiled_index(g_train, L, dims, act); }
 bool v21::fused_train_rt_eligible(int L, const int* dims, const int* act) { return v21::jit_train_eligible(L, dims, act, nullptr); }
 
 // ---------------------------------------------------------------------------------
@@ -1530,9 +1506,7 @@ extern "C" int v21_trainer_jit(v21_trainer* t, int wait_ms, int* status) {
 }
 extern "C" int v21_route_train(int n_layers, const int* dims, const int* act, int precision, int max_batch, int rows, int nranks,
                                int rt_ready, int* fwd, int* upd) {
-  if (!dims || !act || !fwd || !upd) return fail(V21_ERR_ARG, "null argument");
-  if (n_layers < 1 || n_layers > 16) return fail(V21_ERR_ARG, "n_layers %d out of range", n_layers);
-  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
+  CHK(route_query_args(fwd && upd, n_layers, dims, act, precision));
   if (max_batch < 1 || rows < 1 || rows > max_batch || nranks < 1) return fail(V21_ERR_ARG, "need 1 <= rows <= max_batch and nranks >= 1");
   const RouteEnv e = RouteEnv::read();
   const TrainerKind k = decide_trainer_kind(n_layers, dims, act, precision, max_batch, e);

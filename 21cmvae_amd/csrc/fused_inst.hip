@@ -1,35 +1,17 @@
-// fused_inst.hip -- one translation unit per (architecture, precision) of the fused
-// forward kernel; compiled with -DV21_ARCH=S1 -DV21_PREC=F16 etc. (see Makefile).
-#include "fused_fwd.h"
-#include "archs.h"
+// fused_inst.hip -- one translation unit per (family, stack, precision form) of the compiled fused kernels; compiled
+// with -DV21_FAMILY=Fwd -DV21_ARCH=S1 -DV21_PREC=F16x2sp etc. (see Makefile).  It instantiates the family's kernel
+// (fused_families.h) and defines the one launcher that compiled.h declares for it.
+#include "compiled.h"
+#include "fused_families.h"
 
-#define V21_CAT3(a, b, c) a##b##c
-#define V21_SYMNAME(a, p) V21_CAT3(launch_fused_, a, _##p)
 #define V21_XCAT(a, b) a##b
-#define V21_ARCH_T(a) V21_XCAT(Arch, a)
-#define V21_PREC_T(p) V21_XCAT(Prec, p)
-#define V21_EXPAND_SYM(a, p) V21_SYMNAME(a, p)
+#define V21_CAT(a, b) V21_XCAT(a, b)
+#define V21_EXPAND_LAUNCHER(f, a, p) V21_LAUNCHER(f, a, p)
 
 namespace v21 {
 
-hipError_t V21_EXPAND_SYM(V21_ARCH, V21_PREC)(const FusedArgs& a, hipStream_t st) {
-  using A = V21_ARCH_T(V21_ARCH);
-  using P = V21_PREC_T(V21_PREC);
-  auto kern = fused_fwd<A, P>;
-  static bool attr_done_dev[64] = {};  // the attribute belongs to (function, device): one process may drive several
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  bool& attr_done = attr_done_dev[dev & 63];
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_alloc<P>());
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  constexpr int rows = P::WAVES * P::CT * 32;
-  const long long nwg = (a.n_rows + rows - 1) / rows;
-  if (nwg <= 0) return hipSuccess;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * P::WAVES), fused_lds_alloc<P>(), st, a);
-  return hipGetLastError();
+hipError_t V21_EXPAND_LAUNCHER(V21_FAMILY, V21_ARCH, V21_PREC)(const V21_CAT(Family, V21_FAMILY)::Args& a, hipStream_t st) {
+  return launch<V21_CAT(Family, V21_FAMILY), V21_CAT(Arch, V21_ARCH), V21_CAT(Prec, V21_PREC)>(a, st);
 }
 
 }  // namespace v21

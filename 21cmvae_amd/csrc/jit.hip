@@ -3,7 +3,7 @@
 // the internal interface (kJitTrain16 | V21_PREC_F16 ...), so that the registry, the cache and the compiler process
 // (v21_jitc -> v21_jit_prebuild) serve both with the same code.
 #include "jit.h"
-#include "fused_train16.h"
+#include "fused_families.h"
 
 #include <dlfcn.h>
 #include <signal.h>
@@ -117,15 +117,14 @@ int train_depth(int L, const int* dims) {
   const int ks = (dims[L - 1] + 31) / 32;
   return ks - 1 < V21_TRAIN16_DEPTH ? ks - 1 : V21_TRAIN16_DEPTH;
 }
-struct Launch { int rows_per_wg, threads, lds; };
-template <class P> constexpr Launch launch_of() { return Launch{P::WAVES * P::CT * 32, 64 * P::WAVES, fused_lds_alloc<P>()}; }
+// the launch geometry of a run-time kernel: that of its family (fused_families.h), as the compiled kernels take it
+struct Launch { int threads, lds; long long (*workgroups)(long long rows); };
+template <class F, class P> constexpr Launch launch_of() { return Launch{F::template threads<P>(), F::template lds<P>(), &F::template workgroups<P>}; }
 Launch launch_geometry(int prec, bool wide) {
-  if (is_train(prec))
-    return base_prec(prec) == 1 ? Launch{kTrain16RowsPerWg, 64 * PrecF16t16::WAVES, fused_train16_lds<PrecF16t16>()}
-                                : Launch{kTrain16RowsPerWg, 64 * PrecBF16t16::WAVES, fused_train16_lds<PrecBF16t16>()};
-  if (prec == 0) return launch_of<PrecF32>();
-  if (prec == 1) return wide ? launch_of<PrecF16>() : launch_of<PrecF16x2sp>();
-  return wide ? launch_of<PrecBF16>() : launch_of<PrecBF16x2sp>();
+  if (is_train(prec)) return base_prec(prec) == 1 ? launch_of<FamilyTrain16, PrecF16t16>() : launch_of<FamilyTrain16, PrecBF16t16>();
+  if (prec == 0) return launch_of<FamilyFwd, PrecF32>();
+  if (prec == 1) return wide ? launch_of<FamilyFwd, PrecF16>() : launch_of<FamilyFwd, PrecF16x2sp>();
+  return wide ? launch_of<FamilyFwd, PrecBF16>() : launch_of<FamilyFwd, PrecBF16x2sp>();
 }
 
 unsigned long long fnv1a(const void* p, size_t n, unsigned long long h = 1469598103934665603ull) {
@@ -554,16 +553,15 @@ static hipError_t jit_launch_any(JitKernel* k, int device, void* arg_block, long
         (void)hipGetLastError();
         return e;
       }
-      // more than 64 KB of dynamic LDS needs the attribute (as the compiled-in kernels set it in fused_inst.hip)
+      // more than 64 KB of dynamic LDS needs the attribute (as fused_families.h: launch sets it for the compiled-in kernels)
       (void)hipFuncSetAttribute((const void*)n.fn, hipFuncAttributeMaxDynamicSharedMemorySize, g.lds);
       (void)hipGetLastError();
       it = k->loaded.emplace(device, n).first;
     }
     ld = it->second;
   }
-  long long nwg = (rows + g.rows_per_wg - 1) / g.rows_per_wg;
+  const long long nwg = g.workgroups(rows);
   if (nwg <= 0) return hipSuccess;
-  if (is_train(k->prec)) nwg = (nwg + 7) / 8 * 8;  // (whole rounds of the 8 XCDs: the kernel maps block numbers XCD-major and the surplus leaves)
   void* args[] = {arg_block};
   return hipModuleLaunchKernel(ld.fn, (unsigned)nwg, 1, 1, (unsigned)g.threads, 1, 1, (unsigned)g.lds, st, args, nullptr);
 }

@@ -17,6 +17,8 @@ STACKS = {
     "NB": ([7, 64, 128, 451], [1, 1, 0]),                       # notebooks/sample_notebook.ipynb: a custom stack
     "W6": ([7, 600, 451], [1, 0]),                              # wider than the chain kernels hold
     "VAE": ([451, 352, 9, 32, 352, 451], [1, 2, 1, 1, 0]),      # A13 (build-side)
+    "S3": ([7, 352, 352, 352, 224, 9, 32, 352, 451], [1, 1, 1, 1, 0, 1, 1, 0]),  # archs.h S3: latent emulator, then decoder
+    "S4": ([9, 32, 352, 451], [1, 1, 0]),                       # archs.h S4: the decoder alone
 }
 # (relative loss error, cosine of the full gradient, both against the float64 oracle)
 TOL = {"f32": (2e-5, 0.999999), "f16": (3e-3, 0.9995), "bf16": (3e-2, 0.995)}

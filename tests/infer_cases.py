@@ -23,8 +23,8 @@ SPREAD = 0.05  # the walkers' and live points' spread around the truth in u (tes
 # a 7-input variational stack: 7 -> 64 -> (gauss 9) -> 32 -> 451
 VG = ([7, 64, 9, 32, 451], [1, 2, 1, 0])
 # the four stacks with a fused kernel (csrc/archs.h) and their activations
-ARCHS = {"S1": helpers.STACKS["D1"], "S2": helpers.STACKS["DE"], "S3": ([7, 352, 352, 352, 224, 9, 32, 352, 451], [1, 1, 1, 1, 0, 1, 1, 0]),
-         "S4": ([9, 32, 352, 451], [1, 1, 0])}
+ARCHS = {"S1": helpers.STACKS["D1"], "S2": helpers.STACKS["DE"], "S3": helpers.STACKS["S3"],
+         "S4": helpers.STACKS["S4"]}
 # Reduced-precision bounds of the forward on Glorot-uniform weights, outputs O(1) (observed r2: f16 max|d| ~1e-4,
 # bf16 ~1e-3): max |device - fp64 oracle| and the reference's metric (emulator.py:188-191) in percent.
 HALF_BOUNDS = {"f16": dict(max_abs=1e-3, mean_pct=0.05), "bf16": dict(max_abs=1e-2, mean_pct=0.4)}

@@ -93,6 +93,8 @@ def test_route_table():
         (arch, 65536, 256, 0, 0, F | nat.FWD_FORCE_GENERIC, False, "two_launch", 65536),
         (arch, 65536, 256, 0, 0, F | nat.FWD_FORCE_CHAIN, False, "two_launch", 65536),
         (other, 65536, 256, 0, 0, F, False, "two_launch", 65536),    # outside archs.h
+        (ARCHS["S2"], 65536, 256, 0, 0, F, False, "fused", 65536),   # the other stacks of archs.h that a sampler
+        (ARCHS["S3"], 8208, 16, 0, 0, F, True, "fused", 8192),       # takes (S4 has 9 inputs: refused before any route)
         # host chunks: whole ensembles, not above 8,192 rows
         (arch, 8208, 16, 0, 0, F, True, "fused", 8192),
         (arch, 48 * 400, 48, 0, 0, F, True, "fused", 8160),
@@ -128,6 +130,12 @@ def test_route_argument_errors():
         nat.route_ensemble(dims, act, "f32", 64, 16, n_modes=9)
     with pytest.raises(ValueError):
         nat.route_ensemble(dims, act, "f64", 64, 16)
+    # the checks every route query shares refuse a width below 1 for the training query as for the others
+    zero_wide = [dims[0], 0] + list(dims[2:])
+    with pytest.raises(nat.EngineError, match=r"dims\[1\] = 0"):
+        nat.route_ensemble(zero_wide, act, "f32", 64, 16)
+    with pytest.raises(nat.EngineError, match=r"dims\[1\] = 0"):
+        nat.route_train(zero_wide, act, "f16", 256, 256)
     assert nat.route_ensemble(dims, act, "f32", 0, 16) == ("fused", 0)
     assert nat.route_ensemble(dims, act, "f32", 64, 16) == ("fused", 64)  # the library stays usable
 

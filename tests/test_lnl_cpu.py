@@ -30,6 +30,7 @@ def test_route_table():
         (arch, 65536, 0, 0, F | nat.FWD_FORCE_CHAIN, "two_launch"),
         (ARCHS["S4"], 129, 0, 0, nat.FWD_OUT_TRANSFORM, "fused"),
         (ARCHS["S3"], 256, 2, 0, F, "fused"),
+        (ARCHS["S2"], 4099, 0, 0, F, "fused"),
         (other, 65536, 0, 0, F, "two_launch"),      # outside archs.h
         (other, 384, 3, 0, F, "two_launch"),
         (other, 65536, 0, 4, F, "two_launch"),

@@ -179,7 +179,8 @@ def test_route_without_a_gpu():
                                         ((dims, act), 65536, 256, 0, 3, False), ((dims, act), 2 * 256, 256, 2, 0, False),
                                         ((dims, act), 2 * 64, 64, 2, 0, False), (other, 65536, 256, 0, 0, False),
                                         ((dims, act), 64 * 200, 64, 0, 0, True), ((dims, act), 4 * 2560, 64, 4, 0, True),
-                                        ((dims, act), 2 * 65280, 510, 2, 0, True)):
+                                        ((dims, act), 2 * 65280, 510, 2, 0, True), (ARCHS["S2"], 65536, 512, 0, 0, False),
+                                        (ARCHS["S3"], 64 * 200, 64, 0, 0, True)):
         for prec in ("f32", "f16", "bf16"):
             assert nat.route_nested(dm, ac, prec, n, N, nd, K, 0, host) == nat.route_ensemble(dm, ac, prec, n, N, nd, K, 0, host)
     assert nat.route_nested(dims, act, "f16", 65536, 512) == ("fused", 65536)
