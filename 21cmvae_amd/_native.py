@@ -436,15 +436,28 @@ def _data_rows(what, data, n, dout):
     return dp, dp.shape[0]
 
 
-def _count_opts(what, o, more=()):
-    """The counts of a sampler's options o (and the keys `more`): ValueError for what the library would refuse"""
-    for k in tuple(more) + ("n_steps", "n_warmup", "thin", "chain0", "step0", "seed"):
+def _count_opts(what, o, keys, below):
+    """The counts `keys` of a sampler's options o, `below` {key: its limit}: ValueError for what the library would refuse"""
+    for k in keys:
         if int(o[k]) != o[k] or int(o[k]) < 0:
             raise ValueError("%s: %s = %r (a non-negative integer)" % (what, k, o[k]))
-    if int(o["n_steps"]) >= 2 ** 31 or int(o["n_warmup"]) >= 2 ** 31 or int(o["thin"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64:
+    if any(int(o[k]) >= lim for k, lim in below.items()):
         raise ValueError("%s: count out of range" % what)
+
+
+def _step_opts(what, o, more=()):
+    """The counts of the options o of a sampler that runs n_warmup + n_steps steps (and the keys `more`)"""
+    _count_opts(what, o, tuple(more) + ("n_steps", "n_warmup", "thin", "chain0", "step0", "seed"),
+                {"n_steps": 2 ** 31, "n_warmup": 2 ** 31, "thin": 2 ** 31, "seed": 2 ** 64})
     if int(o["step0"]) + int(o["n_warmup"]) + int(o["n_steps"]) >= 2 ** 32:
         raise ValueError("%s: step0 + n_warmup + n_steps must stay below 2^32" % what)
+
+
+def _whole_groups(what, noun, n, n_data, G):
+    """ValueError unless the n rows of a `what` call (None: not known yet), and with n_data the rows of a data row, are
+    whole `noun` of G rows"""
+    if n is not None and (n % G or (n_data and (n // n_data) % G)):
+        raise ValueError("%s: %d rows%s are no whole %s of %d" % (what, n, " over %d data rows" % n_data if n_data else "", noun, G))
 
 
 def _sample_results(x, o, samples, diagnostics, rows=(), diag_rows=()):
@@ -1078,7 +1091,7 @@ class Stack(_Owned):
         o.update({k: v for k, v in (("n_steps", n_steps), ("n_warmup", n_warmup), ("thin", thin), ("eps0", eps0), ("ridge", ridge),
                                     ("target_accept", target_accept), ("seed", seed), ("chain0", chain0), ("step0", step0))
                   if v is not None})
-        _count_opts("sample", o)
+        _step_opts("sample", o)
         for k in ("eps0", "ridge"):
             if not (float(o[k]) > 0 and np.isfinite(float(o[k]))):
                 raise ValueError("sample: %s = %r (positive and finite)" % (k, o[k]))
@@ -1152,8 +1165,7 @@ class Stack(_Owned):
             raise ValueError("sample_tempered: betas = %r (inside [0, 1], strictly decreasing)" % (b.tolist(),))
         if int(swap_every) != swap_every or not 0 <= int(swap_every) < 2 ** 31:
             raise ValueError("sample_tempered: swap_every = %r (a non-negative integer)" % (swap_every,))
-        if n is not None and (n % T or (n_data and (n // n_data) % T)):
-            raise ValueError("sample_tempered: %d rows%s are no whole ladders of %d" % (n, " over %d data rows" % n_data if n_data else "", T))
+        _whole_groups("sample_tempered", "ladders", n, n_data, T)
         return TemperOpts(T, (C.c_double * 32)(*b.tolist()), int(swap_every))
 
     def sample_tempered(self, x0, n_temps=1, betas=None, swap_every=0, precision="f32", flags=0, data=None, eps_start=None, samples=True,
@@ -1197,15 +1209,14 @@ class Stack(_Owned):
         o = dict(ENSEMBLE_DEFAULTS)
         o.update({k: v for k, v in (("n_walkers", n_walkers), ("a", a), ("n_steps", n_steps), ("n_warmup", n_warmup), ("thin", thin),
                                     ("seed", seed), ("chain0", chain0), ("step0", step0)) if v is not None})
-        _count_opts("sample_ensemble", o, more=("n_walkers",))
+        _step_opts("sample_ensemble", o, more=("n_walkers",))
         if not (float(o["a"]) > 1.0 and np.isfinite(float(o["a"]))):
             raise ValueError("sample_ensemble: a = %r (above 1 and finite)" % (o["a"],))
         W = int(o["n_walkers"])
         lo = 2 * (int(in_dim) + 1) if in_dim is not None else 2
         if W % 2 or not lo <= W <= ENSEMBLE_MAX_WALKERS:
             raise ValueError("sample_ensemble: n_walkers = %d (even, %d .. %d)" % (W, lo, ENSEMBLE_MAX_WALKERS))
-        if n is not None and (n % W or (n_data and (n // n_data) % W)):
-            raise ValueError("sample_ensemble: %d rows%s are no whole ensembles of %d" % (n, " over %d data rows" % n_data if n_data else "", W))
+        _whole_groups("sample_ensemble", "ensembles", n, n_data, W)
         return EnsembleOpts(W, float(o["a"]), int(o["n_steps"]), int(o["n_warmup"]), int(o["thin"]), int(o["seed"]), int(o["chain0"]),
                             int(o["step0"]))
 
@@ -1248,11 +1259,8 @@ class Stack(_Owned):
         o = dict(NESTED_DEFAULTS)
         o.update({k: v for k, v in (("n_live", n_live), ("n_repeats", n_repeats), ("n_iter", n_iter), ("gamma", gamma), ("seed", seed),
                                     ("iter0", iter0), ("chain0", chain0)) if v is not None})
-        for k in ("n_live", "n_repeats", "n_iter", "seed", "iter0", "chain0"):
-            if int(o[k]) != o[k] or int(o[k]) < 0:
-                raise ValueError("sample_nested: %s = %r (a non-negative integer)" % (k, o[k]))
-        if int(o["n_repeats"]) >= 2 ** 31 or int(o["n_iter"]) >= 2 ** 31 or int(o["seed"]) >= 2 ** 64 or int(o["iter0"]) >= 2 ** 32:
-            raise ValueError("sample_nested: count out of range")
+        _count_opts("sample_nested", o, ("n_live", "n_repeats", "n_iter", "seed", "iter0", "chain0"),
+                    {"n_repeats": 2 ** 31, "n_iter": 2 ** 31, "seed": 2 ** 64, "iter0": 2 ** 32})
         rep = int(o["n_repeats"]) or 3 * (int(in_dim) if in_dim is not None else 1)
         if (int(o["iter0"]) + int(o["n_iter"])) * rep >= 2 ** 32:
             raise ValueError("sample_nested: (iter0 + n_iter) n_repeats must stay below 2^32")
@@ -1261,8 +1269,7 @@ class Stack(_Owned):
         N = int(o["n_live"])
         if N % 2 or not NESTED_MIN_LIVE <= N <= NESTED_MAX_LIVE:
             raise ValueError("sample_nested: n_live = %d (even, %d .. %d)" % (N, NESTED_MIN_LIVE, NESTED_MAX_LIVE))
-        if n is not None and (n % N or (n_data and (n // n_data) % N)):
-            raise ValueError("sample_nested: %d rows%s are no whole runs of %d" % (n, " over %d data rows" % n_data if n_data else "", N))
+        _whole_groups("sample_nested", "runs", n, n_data, N)
         return NestedOpts(N, int(o["n_repeats"]), int(o["n_iter"]), float(o["gamma"]), int(o["seed"]), int(o["iter0"]), int(o["chain0"]))
 
     def sample_nested(self, u0=None, n=None, n_live=256, precision="f32", flags=0, data=None, dead=True, diagnostics=False, **opts):

@@ -30,32 +30,42 @@ static int ensemble_check(const v21_ensemble_opts& o) {
 static int ensemble_shape(int W, int din, long long n, bool has_data, long long n_data) {
   if (W < 2 || W % 2 != 0 || W < 2 * (din + 1) || W > kEnsMaxWalkers)
     return fail(V21_ERR_ARG, "sample_ensemble: n_walkers = %d (even, %d .. %d for %d parameters)", W, 2 * (din + 1), kEnsMaxWalkers, din);
-  if (n % W != 0) return fail(V21_ERR_ARG, "sample_ensemble: n = %lld rows are no whole ensembles of %d", n, W);
-  if (has_data && n > 0 && (n / n_data) % W != 0)
-    return fail(V21_ERR_ARG, "sample_ensemble: %lld rows per data row are no whole ensembles of %d", n / n_data, W);
-  return V21_OK;
+  return whole_groups("sample_ensemble", "ensembles", n, W, has_data && n > 0, n_data);
 }
 
-extern "C" int v21_route_ensemble(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
-                                  int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows) {
+int ens_route_query(const char* what, int n_layers, const int* dims, const int* act, int precision, long long n, long long n_data, int G,
+                    int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows, const std::function<int()>& shape) {
   CHK(route_query_args(route, n_layers, dims, act, precision));
-  if (n < 0 || n_data < 0 || n_modes < 0 || n_modes > 8) return fail(V21_ERR_ARG, "n = %lld, n_data = %lld, n_modes = %d", (long long)n, (long long)n_data, n_modes);
-  if (dims[0] > kFitMaxIn) return fail(V21_ERR_UNSUPPORTED, "sample_ensemble: %d inputs (at most %d)", dims[0], kFitMaxIn);
-  CHK(call_data_args("sample_ensemble", n, n_data > 0, n_data));
-  CHK(ensemble_shape(n_walkers, dims[0], n, n_data > 0, n_data));
-  const EnsRoute r = decide_ensemble(jac_fused_compiled(n_layers, dims, act), dims[0], n_modes, n_data > 0 ? n / n_data : 0, n, n_walkers,
-                                     flags & 0xFF, host_form != 0, kJacHostChunk);
+  if (n < 0 || n_data < 0 || n_modes < 0 || n_modes > 8) return fail(V21_ERR_ARG, "n = %lld, n_data = %lld, n_modes = %d", n, n_data, n_modes);
+  if (dims[0] > kFitMaxIn) return fail(V21_ERR_UNSUPPORTED, "%s: %d inputs (at most %d)", what, dims[0], kFitMaxIn);
+  CHK(call_data_args(what, n, n_data > 0, n_data));
+  CHK(shape());
+  const EnsRoute r = decide_ensemble(jac_fused_compiled(n_layers, dims, act), dims[0], n_modes, n_data > 0 ? n / n_data : 0, n, G, flags & 0xFF,
+                                     host_form != 0, kJacHostChunk);
   *route = r.route;
   if (chunk_rows) *chunk_rows = r.chunk;
   return V21_OK;
 }
+extern "C" int v21_route_ensemble(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
+                                  int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows) {
+  return ens_route_query("sample_ensemble", n_layers, dims, act, precision, n, n_data, n_walkers, n_modes, flags, host_form, route, chunk_rows,
+                         [&] { return ensemble_shape(n_walkers, dims[0], n, n_data > 0, n_data); });
+}
 
-// the route of one entry-point call, counted once
-static EnsRoute ensemble_route(v21_mlp* m, long long rpd, long long n, int W, int flags, bool host_form) {
-  const EnsRoute r = decide_ensemble(m->fused_id >= 0, m->dims[0], m->nu_k, rpd, n, W, flags, host_form, kJacHostChunk);
+EnsRoute ens_route(v21_mlp* m, long long rpd, long long n, int G, int flags, bool host_form) {
+  const EnsRoute r = decide_ensemble(m->fused_id >= 0, m->dims[0], m->nu_k, rpd, n, G, flags, host_form, kJacHostChunk);
   m->last_lnl_route = r.route;
   m->lnl_route_count[r.route] += 1;
   return r;
+}
+
+int half_eval(v21_mlp* m, int route, long long n, long long n_call, const CallData& data, long long row0, int prec, int flags, HalfEval* ev) {
+  const long long half = n / 2;
+  CHK(m->ens_prop.reserve((size_t)half * m->dims[0]));
+  CHK(m->ens_lnl.reserve((size_t)half));
+  *ev = HalfEval{m->ens_prop.get(), m->ens_lnl.get(), half, n_call / 2, row0 / 2, CallData{data.d, data.ld, data.ld ? data.rpd / 2 : 1},
+                 route, prec, flags & ~V21_FWD_IN_TRANSFORM};
+  return V21_OK;
 }
 
 // the ensembles of n start rows prepped transformed in m->jxt; `out`: device pointers, samples and x_last of x_dtype; the
@@ -64,12 +74,10 @@ static int ensemble_run(v21_mlp* m, int route, long long n, long long n_call, co
                         long long chain0, int prec, int flags, const v21_ensemble_out& out, int x_dtype) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0];
-  const long long half = n / 2;
   CHK(m->ens.reserve((size_t)n));
-  CHK(m->ens_prop.reserve((size_t)half * din));
-  CHK(m->ens_lnl.reserve((size_t)half));
+  HalfEval ev;
+  CHK(half_eval(m, route, n, n_call, data, row0, prec, flags, &ev));
   EnsRow* rows = m->ens.get();
-  float *prop = m->ens_prop.get(), *lnl = m->ens_lnl.get();
   EnsArgs a{};
   a.n = n; a.din = din; a.W = o.n_walkers; a.H = o.n_walkers / 2; a.epw = 256 / a.H;
   a.total = (long long)o.n_warmup + o.n_steps; a.n_warmup = o.n_warmup;
@@ -86,12 +94,10 @@ static int ensemble_run(v21_mlp* m, int route, long long n, long long n_call, co
   const auto step = pri ? (f64 ? ensemble_step_kernel<double, true> : ensemble_step_kernel<float, true>)
                         : (f64 ? ensemble_step_kernel<double, false> : ensemble_step_kernel<float, false>);
   const auto finish = f64 ? ensemble_finish_kernel<double> : ensemble_finish_kernel<float>;
-  // the proposals' data: rows-per-data and the call's first row in the compacted layout
-  const CallData hd{data.d, data.ld, data.ld ? data.rpd / 2 : 1};
   const long long last = 2 * a.total + 2;
   for (long long k = 0; k <= last; ++k) {
-    if (k > 0) CHK(lnl_run(m, route, prop, din, half, n_call / 2, hd, row0 / 2, lnl, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), prop, (const float*)lnl, k, a, m->prior);
+    if (k > 0) CHK(ev.run(m));
+    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), ev.prop, (const float*)ev.lnl, k, a, m->prior);
     HIPCHK(hipGetLastError());
   }
   EnsOutDev od{out.x_last, out.lnl_last, out.accept_rate, out.mean_u, out.cov_u, out.last_log_alpha, out.last_partner};
@@ -112,13 +118,13 @@ extern "C" int v21_mlp_sample_ensemble_dev(v21_mlp* m, const float* d_x0, int64_
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
-  const EnsRoute r = ensemble_route(m, d_data ? data.rpd : 0, n, o.n_walkers, flags, false);
+  const EnsRoute r = ens_route(m, d_data ? data.rpd : 0, n, o.n_walkers, flags, false);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
   return ensemble_run(m, r.route, n, n, data, 0, o, o.chain0, precision, flags, *out, V21_DTYPE_F32);
 }
 
-// the host form: chunks of whole ensembles (routes.h: decide_ensemble), each staged in m->smp_out (ChunkStage), run by
-// ensemble_run and copied back
+// the host form: chunks of whole ensembles (routes.h: decide_ensemble), each staged (ChunkStage), run by ensemble_run and
+// copied back
 extern "C" int v21_mlp_sample_ensemble(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
                                        const v21_ensemble_opts* opts, const v21_ensemble_out* out, int precision, int flags) {
   const v21_ensemble_opts o = opts ? *opts : ensemble_defaults();
@@ -129,16 +135,12 @@ extern "C" int v21_mlp_sample_ensemble(v21_mlp* m, const void* x0, int x_dtype, 
   if (n == 0) return V21_OK;
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
-  const int din = m->dims[0];
-  const EnsRoute r = ensemble_route(m, data ? cd.rpd : 0, n, o.n_walkers, flags, true);
+  const EnsRoute r = ens_route(m, data ? cd.rpd : 0, n, o.n_walkers, flags, true);
   ChunkStage sg;
   v21_ensemble_out d{};
-  stage_sampler_out(sg, *out, d, sample_keep(o.n_steps, o.thin), din, x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float));
+  stage_sampler_out(sg, *out, d, sample_keep(o.n_steps, o.thin), m->dims[0], x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float));
   sg.add(out->last_partner, &d.last_partner, sizeof(int));
-  CHK(m->smp_out.reserve(sg.units(std::min<long long>(n, r.chunk))));
-  return jac_chunks(m, x0, x_dtype, n, 1, 1, [&](long long r0, long long rows, float*) -> int {
-    CHK(sg.place(m, r0, rows));
-    CHK(ensemble_run(m, r.route, rows, n, cd, r0, o, o.chain0 + r0, precision, flags, d, x_dtype));
-    return sg.fetch(m, r0, rows);
+  return jac_chunks(m, x0, x_dtype, n, 1, sg, [&](long long r0, long long rows) {
+    return ensemble_run(m, r.route, rows, n, cd, r0, o, o.chain0 + r0, precision, flags, d, x_dtype);
   }, r.chunk);
 }

@@ -122,14 +122,13 @@ extern "C" int v21_mlp_fisher(v21_mlp* m, const void* x, int x_dtype, int64_t n,
   if (n == 0) return V21_OK;
   const int din = m->dims[0];
   const int route = jac_route(m, flags, m->dims[m->L]);
-  // (the host forms of Fisher and fit stage the same din^2 + din + 3 floats per row: neither regrows what the other left)
-  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, din * din + din + 3, [&](long long r0, long long rows, float* dF) {
-    float* dl = lnl ? dF + rows * din * din : nullptr;
-    float* dg = grad ? dF + rows * (din * din + 1) : nullptr;
-    CHK(reduce_run(m, route, rows, dF, dl, dg, nullptr, m->lk_read(), 0, 1, 0, precision, flags));
-    CHK(to_host(m, fisher + r0 * din * din, dF, (size_t)rows * din * din * sizeof(float)));
-    if (lnl) CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
-    return grad ? to_host(m, grad + r0 * din, dg, (size_t)rows * din * sizeof(float)) : V21_OK;
+  ChunkStage sg;
+  float *dF, *dl, *dg;
+  sg.add(fisher, &dF, (size_t)din * din * sizeof(float));
+  sg.add(lnl, &dl, sizeof(float));
+  sg.add(grad, &dg, din * sizeof(float));
+  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, sg, [&](long long, long long rows) {
+    return reduce_run(m, route, rows, dF, dl, dg, nullptr, m->lk_read(), 0, 1, 0, precision, flags);
   });
 }
 
@@ -184,30 +183,24 @@ static int fit_host(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const fl
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0];
-  const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
   const int route = fit_route(m, flags, fisher != nullptr);
-  // the MAP results of a chunk are staged as the samplers' are (m->smp_out), the fit's own in the chunk's m->hout
   ChunkStage sg;
+  void* dx;
+  float *dF, *dl, *dl0;
+  int32_t* ds;
   v21_map_out d{};
+  sg.add(fisher, &dF, (size_t)din * din * sizeof(float));
+  sg.add(x_hat, &dx, din * (x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float)));
+  sg.add(lnl, &dl, sizeof(float));
+  sg.add(lnl_start, &dl0, sizeof(float));
+  sg.add(status, &ds, sizeof(int32_t));
   if (is_map && mout) {
     sg.add(mout->lnp, &d.lnp, sizeof(double));
     sg.add(mout->laplace, &d.laplace, sizeof(double));
     sg.add(mout->prec_u, &d.prec_u, (size_t)din * din * sizeof(float));
-    CHK(m->smp_out.reserve(sg.units(std::min<long long>(n, kJacHostChunk))));
   }
-  return jac_chunks(m, x0, x_dtype, n, 1, din * din + din + 3, [&](long long r0, long long rows, float* dF) {
-    float* dl = dF + rows * din * din;
-    float* dl0 = dl + rows;
-    int* ds = (int*)(dl0 + rows);
-    CHK(sg.place(m, r0, rows));
-    CHK(fit_run(m, route, rows, cd, r0, o, precision, flags, m->hin.p, x_dtype, dl, dl0, ds, fisher ? dF : nullptr,
-                is_map ? &map : nullptr, &d));
-    CHK(to_host(m, (char*)x_hat + r0 * din * esz, m->hin.p, (size_t)rows * din * esz));
-    CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
-    if (lnl_start) CHK(to_host(m, lnl_start + r0, dl0, (size_t)rows * sizeof(float)));
-    if (status) CHK(to_host(m, status + r0, ds, (size_t)rows * sizeof(int)));
-    if (fisher) CHK(to_host(m, fisher + r0 * din * din, dF, (size_t)rows * din * din * sizeof(float)));
-    return sg.fetch(m, r0, rows);
+  return jac_chunks(m, x0, x_dtype, n, 1, sg, [&](long long r0, long long rows) {
+    return fit_run(m, route, rows, cd, r0, o, precision, flags, dx, x_dtype, dl, dl0, (int*)ds, dF, is_map ? &map : nullptr, &d);
   });
 }
 

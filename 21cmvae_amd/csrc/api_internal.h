@@ -219,13 +219,12 @@ struct v21_mlp {
   Dev<float> lk_data, lk_w;
   Dev<float> lk_ws;      // y and jac of one kLkSlice slice of rows before they are reduced
   Dev<float> jxt, jfac;  // transformed rows and their factors, pitch in_dim (jac_prep)
-  Dev<double> hin;       // the host forms' chunk: its raw rows (float32 or float64; a fit's x_hat) ...
-  Dev<float> hout;       // ... and its results
+  Dev<double> hin;       // the host forms' chunk: its raw rows (float32 or float64) ...
+  Dev<char> stage;       // ... and its results with its further inputs (ChunkStage)
   Dev<FitRow> fit;       // fit state (fit_kernels.h), then F / ln L / gradient of its rows, running rows per iteration, data
   Dev<float> fF, fl, fg, fdata;
   Dev<int> fit_cnt;
   Dev<SampleRow> smp;    // chain state of a sample call (sample_kernels.h; its evaluations land in fF / fl / fg)
-  Dev<double> smp_out;   // the samplers' host forms' chunk: its results, and its per-chain start step sizes (ChunkStage)
   Dev<TemperRow> tmp;    // a tempered sample call's sums of ln L and swap counts per row
   Dev<EnsRow> ens;       // walker state of an ensemble call (ensemble_kernels.h) ...
   Dev<float> ens_prop, ens_lnl;  // ... and the compacted proposals of one half-move (n / 2 rows) with their ln L
@@ -312,11 +311,6 @@ int call_data(v21_mlp* m, long long n, const float* data, bool on_host, long lon
 int nuis_build(const double* basis, const float* w, const float* d, int k, int dout, NuisRecord& rec);
 int nuis_upload(v21_mlp* m, const NuisRecord& rec);
 int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float** out);
-// a host form's rows, chunk by chunk: upload (m->hin) and prep them, run(r0, rows, out) on the chunk (out: m->hout of
-// out_floats per row, and never fewer than a Jacobian row's y and jac, so that no host form regrows what another left),
-// then sync.  chunk_rows: the rows of a chunk (a tempered sample call's is a whole number of ladders)
-int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, long long out_floats,
-               const std::function<int(long long, long long, float*)>& run, long long chunk_rows = kJacHostChunk);
 // api_loglike.hip, shared with api_ensemble.hip and api_nested.hip: lnl of the n device rows d_x (pitch ldx; raw, or transformed already with
 // V21_FWD_IN_TRANSFORM cleared) that start at row0 of a call of n_call rows, on `route` (routes.h: LnlRoute), on the
 // context's stream
@@ -326,47 +320,76 @@ int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n,
 // and the states a row stores
 int sample_counts(const char* what, int n_steps, int n_warmup, int thin, long long chain0, long long step0);
 static inline long long sample_keep(int n_steps, int thin) { return thin > 0 ? n_steps / thin : 0; }
-// device -> host on the context's stream (the host forms' results; jac_chunks syncs)
-static inline int to_host(v21_mlp* m, void* dst, const void* src, size_t bytes) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->ctx->stream));
-  return V21_OK;
-}
-// A sampler's host form stages every chunk in m->smp_out.  The arrays of the call are listed once: add(host, dev, bytes)
-// for an array of `bytes` per row -- host: the caller's (null: not asked for, no slot), dev: where the chunk's device
-// pointer goes (null without a slot), in: an input, copied to the device instead of back.  From that one list come a
-// chunk's size (units), its device pointers with the uploads (place) and the copies back (fetch).
+// api_sample.hip, shared with api_ensemble.hip and api_nested.hip: the n rows of entry `what` are whole `noun` (ladders,
+// ensembles, runs) of G rows and, with per_data, so are the n / n_data rows of a data row (V21_ERR_ARG)
+int whole_groups(const char* what, const char* noun, long long n, int G, bool per_data, long long n_data);
+// api_ensemble.hip, shared with api_nested.hip: the samplers on forward-only ln L in groups of G rows (an ensemble's
+// walkers, a run's live points).  The body of their route queries behind the query's arguments -- shape: the entry's own
+// check of G and n --, the route of one entry-point call, counted once, and the evaluation of a half-move: half_eval
+// reserves the n / 2 pending proposals (m->ens_prop: on u) and their ln L (m->ens_lnl) of the n rows at row0 of a call of
+// n_call rows, with the call's data in the proposals' compacted layout; run() evaluates them once (lnl_run)
+int ens_route_query(const char* what, int n_layers, const int* dims, const int* act, int precision, long long n, long long n_data, int G,
+                    int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows, const std::function<int()>& shape);
+EnsRoute ens_route(v21_mlp* m, long long rpd, long long n, int G, int flags, bool host_form);
+struct HalfEval {
+  float *prop, *lnl; long long half, n_call, row0; CallData hd; int route, prec, flags;
+  int run(v21_mlp* m) const { return lnl_run(m, route, prop, m->dims[0], half, n_call, hd, row0, lnl, prec, flags); }
+};
+int half_eval(v21_mlp* m, int route, long long n, long long n_call, const CallData& data, long long row0, int prec, int flags, HalfEval* ev);
+// A host form stages every chunk of its results in m->stage.  The arrays of the call are listed once: add(host, dev,
+// bytes) for an array of `bytes` per unit -- host: the caller's (null: not asked for, no slot), dev: where the chunk's
+// device pointer goes (null without a slot), in: an input, copied to the device instead of back.  A unit is `unit` rows
+// (1; a nested call's arrays are per run of n_live rows).  A slot of `copies` > 1 is (copies, units, ..) on both sides --
+// the chunk's on the device, the call's on the host, hence a pitched copy back -- and one of 0 copies stages nothing.
+// From that one list come a chunk's size (reserve), its device pointers with the uploads (place) and the copies back
+// (fetch); jac_chunks is the only caller of the three.  A slot starts on 16 bytes: the kernels store dwords, and
+// doubles on 8 bytes, so no result depends on it; 16 is what a 4-dword store would need.
 struct ChunkStage {
-  struct Slot { char* host; void* dev; size_t bytes; bool in; };
+  struct Slot { char* host; void* dev; size_t bytes; long long copies; bool in; };
   std::vector<Slot> slots;
+  long long unit = 1;
+  long long total = 0;  // units of the whole call (reserve): the pitch of the caller's arrays with copies > 1
   template <class T>
-  void add(const T* host, T** dev, size_t bytes, bool in = false) {
+  void add(const T* host, T** dev, size_t bytes, bool in = false, long long copies = 1) {
     *dev = nullptr;
-    if (host) slots.push_back({(char*)host, dev, bytes, in});
+    if (host) slots.push_back({(char*)host, dev, bytes, copies, in});
   }
-  static size_t units_of(const Slot& s, long long rows) { return ((size_t)rows * s.bytes + 7) / 8; }  // (every slot starts on 8 bytes)
-  size_t units(long long rows) const {
-    size_t u = 0;
-    for (const Slot& s : slots) u += units_of(s, rows);
-    return u;
+  static size_t span(const Slot& s, long long units) { return ((size_t)units * s.bytes * (size_t)s.copies + 15) & ~(size_t)15; }
+  // m->stage for chunks of up to chunk_rows of the call's n rows, and never less than a chunk's Jacobian y and jac, so
+  // that no host form regrows what another left
+  int reserve(v21_mlp* m, long long n, long long chunk_rows) {
+    total = n / unit;
+    size_t mine = 0;
+    for (const Slot& s : slots) mine += span(s, chunk_rows / unit);
+    return m->stage.reserve(std::max(mine, (size_t)chunk_rows * m->dims[m->L] * (1 + m->dims[0]) * sizeof(float)));
   }
   int place(v21_mlp* m, long long r0, long long rows) const {
-    double* p = m->smp_out.get();
+    char* p = m->stage.get();
     for (const Slot& s : slots) {
       memcpy(s.dev, &p, sizeof p);
-      if (s.in) HIPCHK(hipMemcpyAsync(p, s.host + r0 * s.bytes, (size_t)rows * s.bytes, hipMemcpyHostToDevice, m->ctx->stream));
-      p += units_of(s, rows);
+      if (s.in) HIPCHK(hipMemcpyAsync(p, s.host + r0 / unit * s.bytes, (size_t)(rows / unit) * s.bytes, hipMemcpyHostToDevice, m->ctx->stream));
+      p += span(s, rows / unit);
     }
     return V21_OK;
   }
   int fetch(v21_mlp* m, long long r0, long long rows) const {
-    const double* p = m->smp_out.get();
+    const char* p = m->stage.get();
     for (const Slot& s : slots) {
-      if (!s.in) CHK(to_host(m, s.host + r0 * s.bytes, p, (size_t)rows * s.bytes));
-      p += units_of(s, rows);
+      const size_t width = (size_t)(rows / unit) * s.bytes;
+      char* dst = s.host + r0 / unit * s.bytes;
+      if (!s.in && s.copies == 1) HIPCHK(hipMemcpyAsync(dst, p, width, hipMemcpyDeviceToHost, m->ctx->stream));
+      if (!s.in && s.copies > 1)
+        HIPCHK(hipMemcpy2DAsync(dst, (size_t)total * s.bytes, p, width, width, (size_t)s.copies, hipMemcpyDeviceToHost, m->ctx->stream));
+      p += span(s, rows / unit);
     }
     return V21_OK;
   }
 };
+// a host form's rows, chunk by chunk: reserve the stage; then per chunk upload (m->hin) and prep its rows (x null: the
+// call has none), place, run(r0, rows) on the device pointers that `add` registered, fetch and sync.  chunk_rows: the
+// rows of a chunk (whole ladders, ensembles, runs or spectra where the call has them)
+int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, ChunkStage& sg,
+               const std::function<int(long long, long long)>& run, long long chunk_rows = kJacHostChunk);
 // the results v21_sample_out and v21_ensemble_out share, `keep` states per row, samples and x_last of esz bytes per element
 template <class Out>
 static void stage_sampler_out(ChunkStage& sg, const Out& host, Out& dev, long long keep, int din, size_t esz) {

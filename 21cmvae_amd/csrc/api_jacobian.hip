@@ -159,19 +159,23 @@ int jac_slices(v21_mlp* m, int route, long long n, bool want_y, int prec, int fl
   return V21_OK;
 }
 
-int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, long long out_floats,
-               const std::function<int(long long, long long, float*)>& run, long long chunk_rows) {
+int jac_chunks(v21_mlp* m, const void* x, int x_dtype, long long n, int tin, ChunkStage& sg,
+               const std::function<int(long long, long long)>& run, long long chunk_rows) {
   hipStream_t st = m->ctx->stream;
-  const int din = m->dims[0], dout = m->dims[m->L];
+  const int din = m->dims[0];
   const long long chunk = std::min(n, chunk_rows);
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
-  CHK(m->hin.reserve((size_t)chunk * din));
-  CHK(m->hout.reserve((size_t)chunk * std::max(out_floats, (long long)dout * (1 + din))));
+  if (x) CHK(m->hin.reserve((size_t)chunk * din));
+  CHK(sg.reserve(m, n, chunk));
   for (long long r0 = 0; r0 < n; r0 += chunk_rows) {
     const long long rows = std::min(chunk_rows, n - r0);
-    HIPCHK(hipMemcpyAsync(m->hin.p, (const char*)x + r0 * din * esz, (size_t)rows * din * esz, hipMemcpyHostToDevice, st));
-    CHK(jac_prep(m, m->hin.p, x_dtype, din, rows, tin));
-    CHK(run(r0, rows, m->hout.get()));
+    if (x) {
+      HIPCHK(hipMemcpyAsync(m->hin.p, (const char*)x + r0 * din * esz, (size_t)rows * din * esz, hipMemcpyHostToDevice, st));
+      CHK(jac_prep(m, m->hin.p, x_dtype, din, rows, tin));
+    }
+    CHK(sg.place(m, r0, rows));
+    CHK(run(r0, rows));
+    CHK(sg.fetch(m, r0, rows));
     HIPCHK(hipStreamSynchronize(st));
   }
   return V21_OK;
@@ -232,22 +236,23 @@ extern "C" int v21_mlp_jacobian(v21_mlp* m, const void* x, int x_dtype, int64_t 
   if (n == 0) return V21_OK;
   const int din = m->dims[0], dout = m->dims[m->L];
   const int route = jac_route(m, flags, dout);
-  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, (long long)dout * (1 + din), [&](long long r0, long long rows, float* out) {
-    float *dy = out, *dj = out + rows * dout;
-    CHK(jac_run(m, route, 0, rows, y ? dy : nullptr, dout, dj, nullptr, nullptr, precision, flags));
-    if (y) CHK(to_host(m, y + r0 * dout, dy, (size_t)rows * dout * sizeof(float)));
-    return to_host(m, jac + r0 * din * dout, dj, (size_t)rows * din * dout * sizeof(float));
+  ChunkStage sg;
+  float *dy, *dj;
+  sg.add(y, &dy, dout * sizeof(float));
+  sg.add(jac, &dj, (size_t)din * dout * sizeof(float));
+  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, sg, [&](long long, long long rows) {
+    return jac_run(m, route, 0, rows, dy, dout, dj, nullptr, nullptr, precision, flags);
   });
 }
 extern "C" int v21_mlp_loglike(v21_mlp* m, const void* x, int x_dtype, int64_t n, float* lnl, float* grad, int precision, int flags) {
   CHK(jac_args(m, x && lnl, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kLoglike));
   if (n == 0) return V21_OK;
-  const int din = m->dims[0];
   const int route = jac_route(m, flags, m->dims[m->L]);
-  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, 1 + din, [&](long long r0, long long rows, float* out) {
-    float *dl = out, *dg = grad ? out + rows : nullptr;
-    CHK(loglike_run(m, route, rows, dl, dg, precision, flags));
-    CHK(to_host(m, lnl + r0, dl, (size_t)rows * sizeof(float)));
-    return grad ? to_host(m, grad + r0 * din, dg, (size_t)rows * din * sizeof(float)) : V21_OK;
+  ChunkStage sg;
+  float *dl, *dg;
+  sg.add(lnl, &dl, sizeof(float));
+  sg.add(grad, &dg, m->dims[0] * sizeof(float));
+  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, sg, [&](long long, long long rows) {
+    return loglike_run(m, route, rows, dl, dg, precision, flags);
   });
 }

@@ -4,7 +4,7 @@
 // (compiled.h: the Lnl family), which reduces chi-square in the output layer's epilogue and writes 4 bytes per row, for the
 // stacks of archs.h whose data are uniform per 128-row workgroup; for everything else the forward on its own route
 // into the likelihood workspace, y only, then lnl_reduce_kernel (reduce_kernels.h).  The host path is the Jacobian
-// side's: jac_args, call_data, jac_chunks, to_host and the lk_ws workspace (api_internal.h).
+// side's: jac_args, call_data, jac_chunks with its ChunkStage and the lk_ws workspace (api_internal.h).
 #include "api_internal.h"
 #include "reduce_kernels.h"
 
@@ -100,8 +100,10 @@ extern "C" int v21_mlp_loglike_fwd(v21_mlp* m, const void* x, int x_dtype, int64
   // jac_chunks leaves a chunk's rows transformed in m->jxt (par_transform.h's own functions, float32 or float64 rows):
   // the kernels read those, without the input transform
   const int din = m->dims[0];
-  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, 1, [&](long long r0, long long rows, float* out) {
-    CHK(lnl_run(m, route, m->jxt.get(), din, rows, n, cd, r0, out, precision, flags & ~V21_FWD_IN_TRANSFORM));
-    return to_host(m, lnl + r0, out, (size_t)rows * sizeof(float));
+  ChunkStage sg;
+  float* dl;
+  sg.add(lnl, &dl, sizeof(float));
+  return jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, sg, [&](long long r0, long long rows) {
+    return lnl_run(m, route, m->jxt.get(), din, rows, n, cd, r0, dl, precision, flags & ~V21_FWD_IN_TRANSFORM);
   }, chunk);
 }

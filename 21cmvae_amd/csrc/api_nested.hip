@@ -32,34 +32,16 @@ static int nested_check(const v21_nested_opts& o, int din, long long n, bool has
                 o.iter0, o.chain0);
   if (o.iter0 >= (1ll << 32) || (o.iter0 + o.n_iter) * (long long)nested_repeats(o, din) >= (1ll << 32))
     return fail(V21_ERR_ARG, "sample_nested: (iter0 + n_iter) n_repeats must stay below 2^32");
-  if (n % N != 0) return fail(V21_ERR_ARG, "sample_nested: n = %lld rows are no whole runs of %d", n, N);
-  if (has_data && n > 0 && (n / n_data) % N != 0)
-    return fail(V21_ERR_ARG, "sample_nested: %lld rows per data row are no whole runs of %d", n / n_data, N);
-  return V21_OK;
+  return whole_groups("sample_nested", "runs", n, N, has_data && n > 0, n_data);
 }
 
 extern "C" int v21_route_nested(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_live,
                                 int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows) {
-  CHK(route_query_args(route, n_layers, dims, act, precision));
-  if (n < 0 || n_data < 0 || n_modes < 0 || n_modes > 8) return fail(V21_ERR_ARG, "n = %lld, n_data = %lld, n_modes = %d", (long long)n, (long long)n_data, n_modes);
-  if (dims[0] > kFitMaxIn) return fail(V21_ERR_UNSUPPORTED, "sample_nested: %d inputs (at most %d)", dims[0], kFitMaxIn);
-  CHK(call_data_args("sample_nested", n, n_data > 0, n_data));
-  v21_nested_opts o = nested_defaults();
-  o.n_live = n_live;
-  CHK(nested_check(o, dims[0], n, n_data > 0, n_data));
-  const EnsRoute r = decide_ensemble(jac_fused_compiled(n_layers, dims, act), dims[0], n_modes, n_data > 0 ? n / n_data : 0, n, n_live,
-                                     flags & 0xFF, host_form != 0, kJacHostChunk);
-  *route = r.route;
-  if (chunk_rows) *chunk_rows = r.chunk;
-  return V21_OK;
-}
-
-// the route of one entry-point call, counted once
-static EnsRoute nested_route(v21_mlp* m, long long rpd, long long n, int N, int flags, bool host_form) {
-  const EnsRoute r = decide_ensemble(m->fused_id >= 0, m->dims[0], m->nu_k, rpd, n, N, flags, host_form, kJacHostChunk);
-  m->last_lnl_route = r.route;
-  m->lnl_route_count[r.route] += 1;
-  return r;
+  return ens_route_query("sample_nested", n_layers, dims, act, precision, n, n_data, n_live, n_modes, flags, host_form, route, chunk_rows, [&] {
+    v21_nested_opts o = nested_defaults();
+    o.n_live = n_live;
+    return nested_check(o, dims[0], n, n_data > 0, n_data);
+  });
 }
 
 // the runs of n rows -- d_start: their start rows (n, din) in u, or nullptr (drawn) -- `out`: device pointers, dead_u and
@@ -69,12 +51,10 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
                       const v21_nested_opts& o, long long chain0, int prec, int flags, const v21_nested_out& out, int x_dtype) {
   hipStream_t st = m->ctx->stream;
   const int din = m->dims[0];
-  const long long half = n / 2;
   CHK(m->nst.reserve((size_t)n));
-  CHK(m->ens_prop.reserve((size_t)half * din));
-  CHK(m->ens_lnl.reserve((size_t)half));
+  HalfEval ev;
+  CHK(half_eval(m, route, n, n_call, data, row0, prec, flags, &ev));
   NestRow* rows = m->nst.get();
-  float *prop = m->ens_prop.get(), *lnl = m->ens_lnl.get();
   NestArgs a{};
   a.runs = n / o.n_live; a.din = din; a.N = o.n_live; a.k = o.n_live / 2; a.rpw = 256 / a.k;
   a.R = nested_repeats(o, din);
@@ -88,8 +68,6 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
   const auto step = pri ? (f64 ? nested_step_kernel<double, true> : nested_step_kernel<float, true>)
                         : (f64 ? nested_step_kernel<double, false> : nested_step_kernel<float, false>);
   const auto finish = f64 ? nested_finish_kernel<double> : nested_finish_kernel<float>;
-  // the proposals' data: rows-per-data and the call's first row in the compacted layout
-  const CallData hd{data.d, data.ld, data.ld ? data.rpd / 2 : 1};
   const long long T = o.n_iter, moves = T * a.R;
   // launch 0 passes start half 0 on, 1 takes it and passes half 1 on, 2 takes that and opens iteration 0; launch 3 + mv
   // decides move mv, opens the next iteration after an iteration's last move, and draws move mv + 1
@@ -107,12 +85,12 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
         if ((mv + 1) % a.R == 0) l.bt = (mv + 1) / a.R;
       }
     }
-    if (q > 0) CHK(lnl_run(m, route, prop, din, half, n_call / 2, hd, row0 / 2, lnl, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, d_start, prop, (const float*)lnl, l, a, m->prior, dec);
+    if (q > 0) CHK(ev.run(m));
+    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, d_start, ev.prop, (const float*)ev.lnl, l, a, m->prior, dec);
     HIPCHK(hipGetLastError());
   }
   NestOutDev od{out.live_u, out.live_lnl, out.accept_rate, out.last_partner, out.last_prop_u};
-  hipLaunchKernelGGL(finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const NestRow*)rows, (const float*)prop, n, din, a.N, moves, od);
+  hipLaunchKernelGGL(finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const NestRow*)rows, (const float*)ev.prop, n, din, a.N, moves, od);
   HIPCHK(hipGetLastError());
   return V21_OK;
 }
@@ -128,14 +106,13 @@ extern "C" int v21_mlp_sample_nested_dev(v21_mlp* m, const float* d_x0, int64_t 
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
-  const EnsRoute r = nested_route(m, d_data ? data.rpd : 0, n, o.n_live, flags, false);
+  const EnsRoute r = ens_route(m, d_data ? data.rpd : 0, n, o.n_live, flags, false);
   if (d_x0) CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 0));  // (the rows at pitch in_dim)
   return nested_run(m, r.route, d_x0 ? m->jxt.get() : nullptr, n, n, data, 0, o, o.chain0, precision, flags, *out, V21_DTYPE_F32);
 }
 
-// the host form: chunks of whole runs (routes.h: decide_ensemble), each staged in m->smp_out, run by nested_run and
-// copied back -- the per-row and per-slot results as they lie, the dead record (T, runs of the chunk, ..) into the
-// caller's (T, runs of the call, ..) with a pitched copy
+// the host form: chunks of whole runs (routes.h: decide_ensemble), each staged (ChunkStage: a unit is a run, the dead
+// record one copy per iteration), run by nested_run on the given starts -- x0 null: drawn -- and copied back
 extern "C" int v21_mlp_sample_nested(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
                                      const v21_nested_opts* opts, const v21_nested_out* out, int precision, int flags) {
   const v21_nested_opts o = opts ? *opts : nested_defaults();
@@ -145,49 +122,22 @@ extern "C" int v21_mlp_sample_nested(v21_mlp* m, const void* x0, int x_dtype, in
   if (n == 0) return V21_OK;
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
-  hipStream_t st = m->ctx->stream;
+  const EnsRoute r = ens_route(m, data ? cd.rpd : 0, n, o.n_live, flags, true);
   const int din = m->dims[0], N = o.n_live, k = N / 2;
-  const long long T = o.n_iter, runs_all = n / N;
+  const long long T = o.n_iter;
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);
-  const EnsRoute r = nested_route(m, data ? cd.rpd : 0, n, N, flags, true);
-  // one list of the call's arrays: host pointer, bytes per run and copies of it (1: as it lies; T: one per iteration)
-  struct Slot { char* host; void** dev; size_t per_run; long long copies; };
+  ChunkStage sg;
+  sg.unit = N;
   v21_nested_out d{};
-  const Slot slots[] = {{(char*)out->dead_u, &d.dead_u, (size_t)k * din * esz, T},
-                        {(char*)out->dead_lnl, (void**)&d.dead_lnl, (size_t)k * sizeof(float), T},
-                        {(char*)out->lstar, (void**)&d.lstar, sizeof(float), T},
-                        {(char*)out->live_u, &d.live_u, (size_t)N * din * esz, 1},
-                        {(char*)out->live_lnl, (void**)&d.live_lnl, (size_t)N * sizeof(float), 1},
-                        {(char*)out->accept_rate, (void**)&d.accept_rate, (size_t)k * sizeof(double), 1},
-                        {(char*)out->last_partner, (void**)&d.last_partner, (size_t)k * 2 * sizeof(int), 1},
-                        {(char*)out->last_prop_u, (void**)&d.last_prop_u, (size_t)k * din * sizeof(float), 1}};
-  const long long chunk = std::min<long long>(n, r.chunk);
-  auto units = [](const Slot& s, long long runs) { return ((size_t)runs * s.per_run * (size_t)s.copies + 7) / 8; };
-  size_t total = 0;
-  for (const Slot& s : slots)
-    if (s.host) total += units(s, chunk / N);
-  CHK(m->smp_out.reserve(total));
-  if (x0) CHK(m->hin.reserve((size_t)chunk * din));
-  for (long long r0 = 0; r0 < n; r0 += chunk) {
-    const long long rows = std::min(chunk, n - r0), runs = rows / N, run0 = r0 / N;
-    double* p = m->smp_out.get();
-    for (const Slot& s : slots) {
-      *s.dev = s.host ? (void*)p : nullptr;
-      if (s.host) p += units(s, runs);
-    }
-    if (x0) {
-      HIPCHK(hipMemcpyAsync(m->hin.p, (const char*)x0 + r0 * din * esz, (size_t)rows * din * esz, hipMemcpyHostToDevice, st));
-      CHK(jac_prep(m, m->hin.p, x_dtype, din, rows, 0));
-    }
-    CHK(nested_run(m, r.route, x0 ? m->jxt.get() : nullptr, rows, n, cd, r0, o, o.chain0 + r0, precision, flags, d, x_dtype));
-    for (const Slot& s : slots) {
-      if (!s.host || s.copies == 0) continue;
-      const size_t width = (size_t)runs * s.per_run;
-      if (s.copies == 1) CHK(to_host(m, s.host + (size_t)run0 * s.per_run, *s.dev, width));
-      else HIPCHK(hipMemcpy2DAsync(s.host + (size_t)run0 * s.per_run, (size_t)runs_all * s.per_run, *s.dev, width, width, (size_t)s.copies,
-                              hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return V21_OK;
+  sg.add(out->dead_u, &d.dead_u, (size_t)k * din * esz, false, T);
+  sg.add(out->dead_lnl, &d.dead_lnl, (size_t)k * sizeof(float), false, T);
+  sg.add(out->lstar, &d.lstar, sizeof(float), false, T);
+  sg.add(out->live_u, &d.live_u, (size_t)N * din * esz);
+  sg.add(out->live_lnl, &d.live_lnl, (size_t)N * sizeof(float));
+  sg.add(out->accept_rate, &d.accept_rate, (size_t)k * sizeof(double));
+  sg.add(out->last_partner, &d.last_partner, (size_t)k * 2 * sizeof(int));
+  sg.add(out->last_prop_u, &d.last_prop_u, (size_t)k * din * sizeof(float));
+  return jac_chunks(m, x0, x_dtype, n, 0, sg, [&](long long r0, long long rows) {
+    return nested_run(m, r.route, x0 ? m->jxt.get() : nullptr, rows, n, cd, r0, o, o.chain0 + r0, precision, flags, d, x_dtype);
+  }, r.chunk);
 }

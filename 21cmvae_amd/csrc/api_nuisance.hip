@@ -138,9 +138,11 @@ extern "C" int v21_mlp_nuisance_coef(v21_mlp* m, const void* x, int x_dtype, int
   const int K = m->nu_k;
   const int route = jac_route(m, flags, m->dims[m->L]);
   std::vector<float> b((size_t)n * K);
-  CHK(jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, K, [&](long long r0, long long rows, float* out) {
-    CHK(reduce_run(m, route, rows, nullptr, nullptr, nullptr, out, m->lk_proj.get(), 0, 1, 0, precision, flags));
-    return to_host(m, b.data() + r0 * K, out, (size_t)rows * K * sizeof(float));
+  ChunkStage sg;
+  float* db;
+  sg.add(b.data(), &db, K * sizeof(float));
+  CHK(jac_chunks(m, x, x_dtype, n, flags & V21_FWD_IN_TRANSFORM, sg, [&](long long, long long rows) {
+    return reduce_run(m, route, rows, nullptr, nullptr, nullptr, db, m->lk_proj.get(), 0, 1, 0, precision, flags);
   }));
   const double* R = m->nu.r.data();
   for (long long i = 0; i < n; ++i)

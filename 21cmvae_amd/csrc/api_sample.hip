@@ -104,62 +104,13 @@ static int sample_check(const v21_sample_opts& o) {
   return V21_OK;
 }
 
-static constexpr JacEntry kSample{"sample", kFitMaxIn, true, true};
-
-extern "C" int v21_mlp_sample_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
-                                  const v21_sample_opts* opts, const double* d_eps_start, const v21_sample_out* out, int precision, int flags) {
-  const v21_sample_opts o = opts ? *opts : sample_defaults();
-  CHK(jac_args(m, d_x0 && out && out->x_last, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kSample));
-  CHK(call_data_args("sample", n, d_data != nullptr, n_data));
-  CHK(sample_check(o));
-  if (n == 0) return V21_OK;
-  CallData data;
-  CHK(call_data(m, n, d_data, false, n_data, &data));
-  const int route = jac_route(m, flags, m->dims[m->L]);
-  CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
-  return sample_run(m, route, n, data, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32);
+int whole_groups(const char* what, const char* noun, long long n, int G, bool per_data, long long n_data) {
+  if (n % G != 0) return fail(V21_ERR_ARG, "%s: n = %lld rows are no whole %s of %d", what, n, noun, G);
+  if (per_data && (n / n_data) % G != 0)
+    return fail(V21_ERR_ARG, "%s: %lld rows per data row are no whole %s of %d", what, n / n_data, noun, G);
+  return V21_OK;
 }
 
-// the host forms: chunks of chunk_rows chains (a whole number of ladders for a tempered call), each staged in
-// m->smp_out (ChunkStage), run by sample_run and copied back
-static int sample_host(v21_mlp* m, const void* x0, int x_dtype, long long n, const float* data, long long n_data, const v21_sample_opts& o,
-                       const double* eps_start, const v21_sample_out* out, int precision, int flags, long long chunk_rows,
-                       const v21_temper_opts* tp, const v21_temper_out* tout) {
-  CallData cd;
-  CHK(call_data(m, n, data, true, n_data, &cd));
-  const int din = m->dims[0], dout = m->dims[m->L];
-  const int route = jac_route(m, flags, dout);
-  ChunkStage sg;
-  double* d_eps = nullptr;
-  v21_sample_out d{};
-  v21_temper_out t{};
-  sg.add(eps_start, &d_eps, sizeof(double), true);
-  stage_sampler_out(sg, *out, d, sample_keep(o.n_steps, o.thin), din, x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float));
-  sg.add(out->eps_last, &d.eps_last, sizeof(double));
-  if (tp && tout) {
-    sg.add(tout->mean_lnl, &t.mean_lnl, sizeof(double));
-    sg.add(tout->var_lnl, &t.var_lnl, sizeof(double));
-    sg.add(tout->swap_accept, &t.swap_accept, sizeof(double));
-  }
-  CHK(m->smp_out.reserve(sg.units(std::min<long long>(n, chunk_rows))));
-  return jac_chunks(m, x0, x_dtype, n, 1, din * din + din + 3, [&](long long r0, long long rows, float*) -> int {
-    CHK(sg.place(m, r0, rows));
-    CHK(sample_run(m, route, rows, cd, r0, o, o.chain0 + r0, d_eps, precision, flags, d, x_dtype, tp, &t));
-    return sg.fetch(m, r0, rows);
-  }, chunk_rows);
-}
-
-extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_sample_opts* opts,
-                              const double* eps_start, const v21_sample_out* out, int precision, int flags) {
-  const v21_sample_opts o = opts ? *opts : sample_defaults();
-  CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kSample));
-  CHK(call_data_args("sample", n, data != nullptr, n_data));
-  CHK(sample_check(o));
-  if (n == 0) return V21_OK;
-  return sample_host(m, x0, x_dtype, n, data, n_data, o, eps_start, out, precision, flags, kJacHostChunk, nullptr, nullptr);
-}
-
-// ---- parallel tempering (include/v21.h: v21_mlp_sample_tempered[_dev])
 static v21_temper_opts temper_defaults() {
   v21_temper_opts t{};
   t.n_temps = 1;
@@ -175,41 +126,88 @@ static int temper_check(const v21_temper_opts& t, long long n, bool has_data, lo
     if (!(t.betas[k] >= 0.0 && t.betas[k] <= 1.0) || (k > 0 && !(t.betas[k] < t.betas[k - 1])))
       return fail(V21_ERR_ARG, "sample_tempered: betas[%d] = %g (inside [0, 1], strictly decreasing)", k, t.betas[k]);
   if (t.swap_every < 0) return fail(V21_ERR_ARG, "sample_tempered: swap_every = %d", t.swap_every);
-  if (n % t.n_temps != 0) return fail(V21_ERR_ARG, "sample_tempered: n = %lld rows are no whole ladders of %d", n, t.n_temps);
-  if (has_data && (n / n_data) % t.n_temps != 0)
-    return fail(V21_ERR_ARG, "sample_tempered: %lld rows per data row are no whole ladders of %d", n / n_data, t.n_temps);
-  return V21_OK;
+  return whole_groups("sample_tempered", "ladders", n, t.n_temps, has_data, n_data);
 }
 
-static constexpr JacEntry kSampleTempered{"sample_tempered", kFitMaxIn, true, true};
+static constexpr JacEntry kSample{"sample", kFitMaxIn, true, true}, kSampleTempered{"sample_tempered", kFitMaxIn, true, true};
 
-extern "C" int v21_mlp_sample_tempered_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
-                                           const v21_sample_opts* opts, const v21_temper_opts* temper, const double* d_eps_start,
-                                           const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags) {
-  const v21_sample_opts o = opts ? *opts : sample_defaults();
-  const v21_temper_opts t = temper ? *temper : temper_defaults();
-  CHK(jac_args(m, d_x0 && out && out->x_last, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kSampleTempered));
-  CHK(call_data_args("sample_tempered", n, d_data != nullptr, n_data));
-  CHK(sample_check(o));
-  CHK(temper_check(t, n, d_data != nullptr, n_data));
+// The four entries (sample and sample_tempered, temper: null for the first; on the device and from the host) share one
+// body each.  What both forms check before any device work (ptrs, ldx: jac_args); o and t: the options in force
+static int sample_args(v21_mlp* m, bool ptrs, long long ldx, int x_dtype, long long n, bool has_data, long long n_data,
+                       const v21_sample_opts* opts, const v21_temper_opts* temper, bool tempered, int precision, int& flags,
+                       v21_sample_opts* o, v21_temper_opts* t) {
+  *o = opts ? *opts : sample_defaults();
+  *t = temper ? *temper : temper_defaults();
+  const JacEntry& entry = tempered ? kSampleTempered : kSample;
+  CHK(jac_args(m, ptrs, n, ldx, kNoPitch, x_dtype, precision, flags, entry));
+  CHK(call_data_args(entry.name, n, has_data, n_data));
+  CHK(sample_check(*o));
+  return tempered ? temper_check(*t, n, has_data, n_data) : V21_OK;
+}
+
+static int sample_dev(v21_mlp* m, const float* d_x0, long long ldx, long long n, const float* d_data, long long n_data,
+                      const v21_sample_opts* opts, const v21_temper_opts* temper, bool tempered, const double* d_eps_start,
+                      const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags) {
+  v21_sample_opts o;
+  v21_temper_opts t;
+  CHK(sample_args(m, d_x0 && out && out->x_last, ldx, V21_DTYPE_F32, n, d_data != nullptr, n_data, opts, temper, tempered, precision, flags, &o, &t));
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
   const int route = jac_route(m, flags, m->dims[m->L]);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
-  return sample_run(m, route, n, data, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32, &t, tout);
+  return sample_run(m, route, n, data, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32, tempered ? &t : nullptr, tout);
+}
+
+// the host forms: chunks of kJacHostChunk chains -- of a tempered call the largest multiple of n_temps that is not above
+// it: no ladder straddles two chunks --, each staged (ChunkStage), run by sample_run and copied back
+static int sample_host(v21_mlp* m, const void* x0, int x_dtype, long long n, const float* data, long long n_data, const v21_sample_opts* opts,
+                       const v21_temper_opts* temper, bool tempered, const double* eps_start, const v21_sample_out* out,
+                       const v21_temper_out* tout, int precision, int flags) {
+  v21_sample_opts o;
+  v21_temper_opts tp;
+  CHK(sample_args(m, x0 && out && out->x_last, kNoPitch, x_dtype, n, data != nullptr, n_data, opts, temper, tempered, precision, flags, &o, &tp));
+  if (n == 0) return V21_OK;
+  CallData cd;
+  CHK(call_data(m, n, data, true, n_data, &cd));
+  const int din = m->dims[0], dout = m->dims[m->L];
+  const int route = jac_route(m, flags, dout);
+  ChunkStage sg;
+  double* d_eps = nullptr;
+  v21_sample_out d{};
+  v21_temper_out t{};
+  sg.add(eps_start, &d_eps, sizeof(double), true);
+  stage_sampler_out(sg, *out, d, sample_keep(o.n_steps, o.thin), din, x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float));
+  sg.add(out->eps_last, &d.eps_last, sizeof(double));
+  if (tempered && tout) {
+    sg.add(tout->mean_lnl, &t.mean_lnl, sizeof(double));
+    sg.add(tout->var_lnl, &t.var_lnl, sizeof(double));
+    sg.add(tout->swap_accept, &t.swap_accept, sizeof(double));
+  }
+  return jac_chunks(m, x0, x_dtype, n, 1, sg, [&](long long r0, long long rows) {
+    return sample_run(m, route, rows, cd, r0, o, o.chain0 + r0, d_eps, precision, flags, d, x_dtype, tempered ? &tp : nullptr, &t);
+  }, tempered ? kJacHostChunk / tp.n_temps * tp.n_temps : kJacHostChunk);
+}
+
+extern "C" int v21_mlp_sample_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                  const v21_sample_opts* opts, const double* d_eps_start, const v21_sample_out* out, int precision, int flags) {
+  return sample_dev(m, d_x0, ldx, n, d_data, n_data, opts, nullptr, false, d_eps_start, out, nullptr, precision, flags);
+}
+
+extern "C" int v21_mlp_sample(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data, const v21_sample_opts* opts,
+                              const double* eps_start, const v21_sample_out* out, int precision, int flags) {
+  return sample_host(m, x0, x_dtype, n, data, n_data, opts, nullptr, false, eps_start, out, nullptr, precision, flags);
+}
+
+// ---- parallel tempering (include/v21.h: v21_mlp_sample_tempered[_dev]; temper NULL: one rung at beta = 1)
+extern "C" int v21_mlp_sample_tempered_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
+                                           const v21_sample_opts* opts, const v21_temper_opts* temper, const double* d_eps_start,
+                                           const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags) {
+  return sample_dev(m, d_x0, ldx, n, d_data, n_data, opts, temper, true, d_eps_start, out, tout, precision, flags);
 }
 
 extern "C" int v21_mlp_sample_tempered(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const float* data, int64_t n_data,
                                        const v21_sample_opts* opts, const v21_temper_opts* temper, const double* eps_start,
                                        const v21_sample_out* out, const v21_temper_out* tout, int precision, int flags) {
-  const v21_sample_opts o = opts ? *opts : sample_defaults();
-  const v21_temper_opts t = temper ? *temper : temper_defaults();
-  CHK(jac_args(m, x0 && out && out->x_last, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kSampleTempered));
-  CHK(call_data_args("sample_tempered", n, data != nullptr, n_data));
-  CHK(sample_check(o));
-  CHK(temper_check(t, n, data != nullptr, n_data));
-  if (n == 0) return V21_OK;
-  // (no ladder straddles two chunks: the largest multiple of n_temps that is not above the host chunk)
-  return sample_host(m, x0, x_dtype, n, data, n_data, o, eps_start, out, precision, flags, kJacHostChunk / t.n_temps * t.n_temps, &t, tout);
+  return sample_host(m, x0, x_dtype, n, data, n_data, opts, temper, true, eps_start, out, tout, precision, flags);
 }

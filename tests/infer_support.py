@@ -127,18 +127,22 @@ def ready(st, prec):
 
 
 # ---- the stacks of tests/shape_cases.py and their records
+def new_stack(ctx, dims, act):
+    """a handle of its own of a stack of the table, with its weights and transforms set (no input transform above 8 inputs)"""
+    rec = sc.make_stack(dims, act)
+    st = pkg("_native").Stack(ctx, dims, act)
+    st.set_weights(rec["flat"])
+    if rec["tin"] is not None:
+        st.set_input_transform(*rec["tin"])
+    st.set_output_transform(rec["tout"][0], rec["tout"][1].astype(np.float32))
+    return st
+
+
 def device_stack(ctx, dims, act):
-    """the handle of a stack of the table with its transforms set (no input transform above 8 inputs), and its host record"""
+    """the one shared handle of a stack of the table (new_stack), and its host record"""
     key = (tuple(dims), tuple(act))
     if key not in _tabled:
-        nat = pkg("_native")
-        rec = sc.make_stack(dims, act)
-        st = nat.Stack(ctx, dims, act)
-        st.set_weights(rec["flat"])
-        if rec["tin"] is not None:
-            st.set_input_transform(*rec["tin"])
-        st.set_output_transform(rec["tout"][0], rec["tout"][1].astype(np.float32))
-        _tabled[key] = st
+        _tabled[key] = new_stack(ctx, dims, act)
     # (no record of an earlier test, should that one have failed half way: clearing the likelihood clears the nuisance too)
     _tabled[key].set_likelihood(None, None)
     _tabled[key].set_prior(None)

@@ -10,7 +10,7 @@ import pytest
 import infer_cases as ic
 import map_ref as mp
 from conftest import pkg
-from infer_support import POISON_BYTE, device_eval, device_stack, fit_setup, flags_of, run_dev, same, shape_setup, u_of
+from infer_support import POISON_BYTE, device_eval, device_stack, fit_setup, flags_of, new_stack, run_dev, same, shape_setup, u_of
 
 pytestmark = pytest.mark.gpu
 fr, pr, jr = mp.fr, mp.pr, mp.fr.jr
@@ -53,6 +53,11 @@ def setup(ctx, which):
     st, rec, prob, _ = shape_setup(ctx, which)
     return (st, rec["tin"], rec["dims"][0], prob["truths_u"][0], None,
             lambda: fr.evaluator(rec["Ws"], rec["bs"], rec["act"], prob["data"][0], prob["w"], rec["tout"]))
+
+
+def tin_of(p):
+    """the input transform of a quadrature problem's stack"""
+    return p["stack"]["tin"]
 
 
 def starts_around(centre, n, seed, scale):
@@ -304,6 +309,44 @@ def test_host_chunks_do_not_move_rows(ctx):
     finally:
         st.set_prior(None)
         st.set_likelihood(None, None)
+
+
+def arrays_of(r):
+    """the arrays of a host form's result (an array, a tuple or a dict of them), in a fixed order"""
+    if isinstance(r, dict):
+        return [r[k] for k in sorted(r)]
+    return list(r) if isinstance(r, tuple) else [r]
+
+
+def test_host_forms_share_one_chunk_buffer(ctx):
+    """One handle of the 2-input problem takes the host forms in turn -- few rows, then two chunks (a regrow of the chunk
+    buffer), few rows again, the nested sampler's per-run slots in between: every result is bit-equal to the same call on a
+    handle of its own that has staged nothing before, and the Jacobian of the first call to that of the last"""
+    nat = pkg("_native")
+    p = ic.problem("i2")
+    flags = flags_of(nat, True)
+    few = untransform(starts_around(p["truth_u"], 5, 4, 0.2), tin_of(p))
+    many = untransform(starts_around(p["truth_u"], 8193, 5, 0.2), tin_of(p))
+    calls = [lambda st: st.jacobian(few, "f32", flags, return_outputs=True),
+             lambda st: st.fit_map(many, "f32", flags, max_iter=4, fisher=True),
+             lambda st: st.loglike(few, "f32", flags),
+             lambda st: st.sample_nested(None, 16, 16, "f32", nat.FWD_OUT_TRANSFORM, diagnostics=True, n_iter=2, seed=9),
+             lambda st: st.fisher(few, "f32", flags, lnl=True, grad=True),
+             lambda st: st.loglike_fwd(many, "f32", flags),
+             lambda st: st.jacobian(few, "f32", flags, return_outputs=True)]
+
+    def handle():
+        st = new_stack(ctx, p["dims"], p["act"])
+        st.set_likelihood(p["data"], p["w"])
+        return st
+
+    one = handle()
+    got = [arrays_of(call(one)) for call in calls]
+    for i, call in enumerate(calls):
+        alone = arrays_of(call(handle()))
+        assert len(alone) == len(got[i]) and all(a.size > 0 and same(a, b) for a, b in zip(got[i], alone)), i
+    assert all(same(a, b) for a, b in zip(got[0], got[-1]))
+    assert all(np.all(np.isfinite(a)) for a in got[0])
 
 
 # ---- 5. edges

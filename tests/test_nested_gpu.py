@@ -1,10 +1,11 @@
 """The nested sampler on the GPU (include/v21.h: v21_mlp_sample_nested[_dev]): iterations rebuilt exactly from the device's
 own evaluations and the same Philox draws (tests/nested_ref.py), independence of chunking / splitting, the evidence against
-quadrature and against the float64 reference, a flat target, edge cases and errors, the emulator classes' surface.
+quadrature and against the float64 reference, given starts and left-out arrays across a host chunk boundary, a flat target,
+edge cases and errors, the emulator classes' surface.
 
 Measured on the MI355X: the rebuild bit-equal in all 18 cases, 0 decisions excused, 42-60 % of the proposals accepted;
 i1 ln Z -39.0255 +- 0.0339 (quadrature -39.0112, z -0.42), i2 -40.9410 +- 0.0350 (quadrature -40.9389, z -0.06), both equal
-to the reference's to the digits shown; the module's 13 tests in 6 s."""
+to the reference's to the digits shown; the module's 13 tests in 6 s, the two chunk-boundary tests added since under 1 s."""
 import ctypes as C
 
 import numpy as np
@@ -139,6 +140,46 @@ def test_continuation_and_splitting(ctx):
             assert same(part[key], four[key][:, rr]), (half, key)
         for key in ("accept_rate", "last_partner", "last_prop_u"):
             assert same(part[key], four[key][rr]), (half, key)
+    st.set_likelihood(None, None)
+
+
+_boundary = {}
+
+
+def boundary_case(ctx):
+    """8,208 given live points (513 runs of 16: host chunks of 8,192 and 16 rows), float64 values that float32 holds
+    exactly, three iterations in f16 -> (stack with its record set, float64 starts, options, the host form's full result,
+    computed once)"""
+    st, dims, act, Ws, bs, tin, tout, truths, data, w = fit_setup(ctx)
+    if not _boundary:
+        n, N = 8208, 16
+        assert st.route_nested("f16", n, N, host_form=True) == ("fused", 8192)
+        u = live_near(truths[0], tin, n, 21).astype(np.float32).astype(np.float64)
+        kw = dict(n_live=N, precision="f16", flags=pkg("_native").FWD_OUT_TRANSFORM, n_iter=3, n_repeats=2, seed=78)
+        _boundary.update(u=u, kw=kw, full=st.sample_nested(u, diagnostics=True, **kw))
+    return st, _boundary["u"], _boundary["kw"], _boundary["full"]
+
+
+def test_given_starts_across_a_chunk_boundary(ctx):
+    """the host form uploads a chunk's given starts as every host form uploads its rows: every output equals the _dev
+    form's on the same float32 rows"""
+    st, u, kw, full = boundary_case(ctx)
+    dev = dev_nested(ctx, st, np.ascontiguousarray(u.astype(np.float32)), u.shape[0], None, kw["n_live"], kw["precision"], kw["flags"],
+                     guard=256, n_iter=kw["n_iter"], n_repeats=kw["n_repeats"], seed=kw["seed"])
+    for key in KEYS:
+        assert full[key].size > 0 and same(full[key].astype(dev[key].dtype), dev[key]), key
+    assert 0.02 < full["accept_rate"].mean() < 0.98
+    st.set_likelihood(None, None)
+
+
+def test_optional_arrays_left_out_across_a_chunk_boundary(ctx):
+    """without the dead record and the diagnostics -- null slots among the slots of one copy per iteration -- the other
+    outputs of the same call do not move"""
+    st, u, kw, full = boundary_case(ctx)
+    lean = st.sample_nested(u, dead=False, diagnostics=False, **kw)
+    assert sorted(lean) == ["accept_rate", "live_lnl", "live_u"]
+    for key in lean:
+        assert same(lean[key], full[key]), key
     st.set_likelihood(None, None)
 
 
