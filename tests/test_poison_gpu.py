@@ -13,30 +13,19 @@ import numpy as np
 import pytest
 
 from conftest import pkg
+from helpers import STACKS
 from oracle import ref_numpy as ora
+from train_support import loss64, new_trainer, signal_rows
 
 pytestmark = pytest.mark.gpu
 
-AE_DIMS, AE_ACT = [451, 352, 9, 32, 352, 451], [1, 0, 1, 1, 0]
-EM_DIMS, EM_ACT = [7, 352, 352, 352, 224, 9], [1, 1, 1, 1, 0]
+(AE_DIMS, AE_ACT), (EM_DIMS, EM_ACT) = STACKS["AE"], STACKS["LE"]
 
 
 def _trainer(ctx, dims, act, prec, batch, seed, lr=1e-3):
-    native = pkg("_native")
     Ws, bs = ora.init_mlp(dims, seed=seed)
-    st = native.Stack(ctx, dims, act)
-    st.set_weights(ora.flatten_params(Ws, bs))
-    tr = native.Trainer(st, prec, batch)
-    tr.set_adam(lr=lr)
+    st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, batch, lr=lr)
     return st, tr, Ws, bs
-
-
-def _oracle_loss(Ws, bs, act, x, y, w):
-    h = x.astype(np.float64)
-    for W_, b_, a_ in zip(Ws, bs, act):
-        h = h @ W_.astype(np.float64) + b_.astype(np.float64)
-        h = np.maximum(h, 0) if a_ else h
-    return float(np.mean(ora.per_sample_loss(h, y.astype(np.float64), w.astype(np.float64))))
 
 
 @pytest.mark.parametrize("prec", ["f16", "bf16"])
@@ -49,16 +38,14 @@ def test_chain_step_does_not_depend_on_what_lds_held(ctx, prec, case):
     rng = np.random.default_rng(3)
     if case == "autoencoder_451":
         dims, act = AE_DIMS, AE_ACT
-        sig = synth.make_signals(n, seed=5)
-        x = ora.preproc(sig, sig); y = None
-        w = ora.relative_mse_row_weight(x, sig).astype(np.float32)
+        (x, w), y = signal_rows(n, seed=5), None
     elif case == "emulator_7_to_9":
         dims, act = EM_DIMS, EM_ACT
         x = rng.uniform(-1, 1, size=(n, 7)).astype(np.float32)
         y = rng.normal(size=(n, 9)).astype(np.float32)
         w = ora.mse_row_weight(y).astype(np.float32)
     else:
-        dims, act = [7, 288, 352, 288, 224, 451], [1, 1, 1, 1, 0]
+        dims, act = STACKS["DE"]
         par = synth.make_params(n, seed=3)
         x = ora.par_transform(par, par).astype(np.float32)
         sig = synth.signals_from_params(par)
@@ -81,20 +68,18 @@ def test_chain_step_does_not_depend_on_what_lds_held(ctx, prec, case):
     for a, b in zip(res[True], res[False]):
         assert np.isfinite(a).all()
         np.testing.assert_array_equal(a, b)
-    lo = _oracle_loss(Ws, bs, act, x, x if y is None else y, w)
+    lo = loss64(Ws, bs, act, x, x if y is None else y, w)
     tol = 3e-3 if prec == "f16" else 3e-2
     assert abs(res[True][0][0] - lo) / lo < tol, (res[True][0][0], lo)
 
 
 def test_variational_chain_step_after_lds_poison(ctx):
     """The variational head keeps (z_mean | z_log_var) and KL_i in LDS as fp32 (train_chain.h: zs, klb)."""
-    native, synth = pkg("_native"), pkg("synth")
+    native = pkg("_native")
     dims, act = [451, 96, 18, 32, 451], [1, native.ACT_GAUSS, 1, 0]
     dims_dense = [451, 96, 9, 32, 451]
     n = 75
-    sig = synth.make_signals(n, seed=8)
-    x = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(x, sig).astype(np.float32)
+    x, w = signal_rows(n, seed=8)
     res = {}
     for poison in (False, True):
         st = native.Stack(ctx, dims_dense, act)
@@ -117,12 +102,10 @@ def test_variational_chain_step_after_lds_poison(ctx):
 def test_joint_and_grouped_chain_after_lds_poison(ctx):
     """train_chain_joint_kernel (two models through one workgroup, latents captured in LDS) and the grouped chain
     of a sweep, ragged batch, full-width autoencoder + latent emulator."""
-    native, synth = pkg("_native"), pkg("synth")
+    native = pkg("_native")
     n = 150
-    sig = synth.make_signals(n, seed=6)
-    y = ora.preproc(sig, sig)
+    y, wa = signal_rows(n, seed=6)
     par = np.random.default_rng(9).uniform(-1, 1, size=(n, 7)).astype(np.float32)
-    wa = ora.relative_mse_row_weight(y, sig).astype(np.float32)
     wz = ora.mse_row_weight(np.zeros((n, 9), np.float32)).astype(np.float32)
     res = {}
     for poison in (False, True):
@@ -138,7 +121,7 @@ def test_joint_and_grouped_chain_after_lds_poison(ctx):
             out.extend(joint.run_epoch(None, n))
         # a sweep of two autoencoders that differ in width (grouped chain + grouped gradient/Adam launch)
         trs = []
-        for k, dims in enumerate(([451, 128, 4, 32, 128, 451], [451, 352, 9, 32, 352, 451])):
+        for k, dims in enumerate(([451, 128, 4, 32, 128, 451], AE_DIMS)):
             _, t, _, _ = _trainer(ctx, dims, AE_ACT, "f16", n, seed=50 + k)
             trs.append(t)
         trs[0].set_data(0, y, None, wa)

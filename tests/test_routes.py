@@ -20,6 +20,7 @@ import pytest
 from conftest import ROOT, pkg
 from helpers import STACKS, assert_step_matches_oracle, stack_data, twin_steps
 from oracle import ref_numpy as ora
+from train_support import forward64
 
 
 def _tables():
@@ -198,10 +199,7 @@ def test_default_forward_routes_match_table_and_oracle(ctx, row, no_switches):
     assert set(counts) == {row["route"]}, counts      # every slice of the host call took the same route
     assert native.route_forward(dims, act, prec, n, rt_ready=row["rt"]) == route
     pick = np.unique(np.concatenate([np.arange(min(n, 40)), np.random.default_rng(3).integers(0, n, 200), [n - 1]]))
-    ref = x[pick].astype(np.float64)
-    for W_, b_, a_ in zip(Ws, bs, act):                  # (a variational head evaluates z = z_mean: its layer is linear here)
-        ref = ref @ W_.astype(np.float64) + b_.astype(np.float64)
-        ref = np.maximum(ref, 0) if a_ == 1 else ref
+    ref = forward64(Ws, bs, [a_ == 1 for a_ in act], x[pick])   # (a variational head evaluates z = z_mean: its layer is linear here)
     err = np.abs(y[pick] - ref)
     if prec == "f32":
         np.testing.assert_allclose(y[pick], ref, atol=2e-5, rtol=1e-5)

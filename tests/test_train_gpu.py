@@ -9,40 +9,35 @@ import os
 
 import numpy as np
 import pytest
+import torch   # before the engine's first call, also when this module runs alone: one HIP runtime per process
 
+import half_ref as hr
 from conftest import pkg
+from helpers import (HALF_STEP_TOL, STACKS, assert_step_matches_oracle, half_step_check, oracle_step, per_layer_gradient_check,
+                     stack_data, twin_steps)
 from oracle import ref_numpy as ora
+from train_support import close as _close, cos as _cos, forward64, loss64, new_trainer, signal_rows, vae_weights
 
 pytestmark = pytest.mark.gpu
 
 
-def _make(ctx, dims, act=None, seed=0, prec="f32", max_batch=256):
-    native = pkg("_native")
+def _make(ctx, dims, act=None, seed=0, prec="f32", max_batch=256, lr=None):
     act = act or [1] * (len(dims) - 2) + [0]
     Ws, bs = ora.init_mlp(dims, seed=seed)
     rng = np.random.default_rng(seed + 1)
     bs = [rng.normal(scale=0.05, size=b.shape).astype(np.float32) for b in bs]
-    st = native.Stack(ctx, dims, act)
-    st.set_weights(ora.flatten_params(Ws, bs))
-    tr = native.Trainer(st, prec, max_batch)
+    st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, max_batch, lr=lr)
     return st, tr, Ws, bs
-
-
-def _close(a, b, rtol, what):
-    scale = np.abs(b).max() + 1e-30
-    err = np.abs(a - b).max() / scale
-    assert err < rtol, "%s: max err / scale = %.3e (limit %.1e)" % (what, err, rtol)
 
 
 def test_single_step_grad_adam_state(ctx):
     dims = [7, 32, 16, 5]
-    st, tr, Ws, bs = _make(ctx, dims, seed=3)
+    st, tr, Ws, bs = _make(ctx, dims, seed=3, lr=1e-2)
     rng = np.random.default_rng(0)
     n = 64
     x = rng.normal(size=(n, 7)).astype(np.float32)
     y = rng.normal(size=(n, 5)).astype(np.float32)
     w = rng.uniform(0.5, 1.5, size=n).astype(np.float32)
-    tr.set_adam(lr=1e-2)
     tr.set_data(0, x, y, w)
     loss = tr.run_epoch(None, n)  # one step, rows in order
     # oracle, float64
@@ -65,12 +60,11 @@ def test_epochs_match_oracle_fit(ctx, n, batch):
     """Keras bookkeeping: shuffled order, partial last batch kept, sample-weighted epoch
     loss, validation pass after the epoch."""
     dims = [7, 24, 12, 9]
-    st, tr, Ws, bs = _make(ctx, dims, seed=5, max_batch=64)
+    st, tr, Ws, bs = _make(ctx, dims, seed=5, max_batch=64, lr=3e-3)
     rng = np.random.default_rng(1)
     x = rng.normal(size=(n, 7)).astype(np.float32); y = rng.normal(size=(n, 9)).astype(np.float32)
     xv = rng.normal(size=(40, 7)).astype(np.float32); yv = rng.normal(size=(40, 9)).astype(np.float32)
     w = ora.mse_row_weight(y).astype(np.float32); wv = ora.mse_row_weight(yv).astype(np.float32)
-    tr.set_adam(lr=3e-3)
     tr.set_data(0, x, y, w); tr.set_data(1, xv, yv, wv)
     sto = ora.AdamState(st.num_params, dtype=np.float64, lr=3e-3)
     W, b = [a.astype(np.float64) for a in Ws], [a.astype(np.float64) for a in bs]
@@ -91,38 +85,22 @@ def test_epochs_match_oracle_fit(ctx, n, batch):
 def test_autoencoder_fit_y_is_x_relative_mse(ctx):
     """AutoEncoderEmulator phase 1 (emulator.py:739-747): x -> x with relative_mse_loss,
     linear latent layer in the middle of the stack."""
-    synth = pkg("synth")
     dims = [451, 48, 9, 16, 451]
     act = [1, 0, 1, 0]
-    st, tr, Ws, bs = _make(ctx, dims, act=act, seed=8, max_batch=128)
-    sig = synth.make_signals(200, seed=3)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
-    tr.set_adam(lr=1e-3)
+    st, tr, Ws, bs = _make(ctx, dims, act=act, seed=8, max_batch=128, lr=1e-3)
+    y, w = signal_rows(200, seed=3)
     tr.set_data(0, y, None, w)
     perm = ora.epoch_permutation(200, 1, 0)
     loss = tr.run_epoch(perm, 128)
     # oracle with the same activations
-    def fwd(Wl, bl, x):
-        acts = [x]
-        for W_, b_, a in zip(Wl, bl, act):
-            z = acts[-1] @ W_ + b_
-            acts.append(np.maximum(z, 0) if a else z)
-        return acts
     W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
     sto = ora.AdamState(st.num_params, dtype=np.float64, lr=1e-3)
     tot = 0.0
     for s in range(0, 200, 128):
         idx = perm[s:s + 128]
-        acts = fwd(W, b, y[idx].astype(np.float64))
-        l, g = ora.batch_loss_and_grad(acts[-1], y[idx].astype(np.float64), w[idx].astype(np.float64))
+        l, g = oracle_step(W, b, act, y[idx], y[idx], w[idx])
         tot += l * len(idx)
-        dz = g; dWs = [None] * 4; dbs = [None] * 4
-        for li in range(3, -1, -1):
-            dWs[li] = acts[li].T @ dz; dbs[li] = dz.sum(0)
-            dh = dz @ W[li].T
-            dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
-        flat = ora.adam_step(ora.flatten_params(W, b), ora.flatten_params(dWs, dbs), sto)
+        flat = ora.adam_step(ora.flatten_params(W, b), g, sto)
         W, b = ora.unflatten_params(flat, dims)
     assert abs(loss - tot / 200) / (tot / 200) < 2e-5
     _close(st.get_weights(), ora.flatten_params(W, b), 2e-4, "AE weights after 1 epoch")
@@ -130,17 +108,13 @@ def test_autoencoder_fit_y_is_x_relative_mse(ctx):
 
 def test_reference_architecture_step_all_precisions(ctx):
     """DirectEmulator default stack (emulator.py:196), batch 256 as emulator.py:372."""
-    synth = pkg("synth")
     dims = [7, 288, 352, 288, 224, 451]
     rng = np.random.default_rng(2)
     x = rng.uniform(-1, 1, size=(256, 7)).astype(np.float32)
-    sig = synth.make_signals(256, seed=4)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(256, seed=4)
     ref = None
     for prec, cos_min in (("f32", 0.999999), ("f16", 0.9995), ("bf16", 0.99)):
-        st, tr, Ws, bs = _make(ctx, dims, seed=6, prec=prec)
-        tr.set_adam(lr=1e-3)
+        st, tr, Ws, bs = _make(ctx, dims, seed=6, prec=prec, lr=1e-3)
         tr.set_data(0, x, y, w)
         loss = tr.run_epoch(None, 256)
         g = tr.get_grad()
@@ -151,14 +125,13 @@ def test_reference_architecture_step_all_precisions(ctx):
                                                w.astype(np.float64), np.float64)
             ref = (loss_o, g_o)
             _close(g, g_o, 5e-4, "f32 gradient of the reference stack")
-        cos = float(g @ ref[1] / (np.linalg.norm(g) * np.linalg.norm(ref[1])))
+        cos = _cos(g, ref[1])
         print("%s: loss rel err %.2e, grad cosine %.7f" % (prec, abs(loss - ref[0]) / ref[0], cos))
         assert cos > cos_min
         assert abs(loss - ref[0]) / ref[0] < (1e-5 if prec == "f32" else 2e-2)
-        from helpers import per_layer_gradient_check   # (r5: layer by layer -- the cosine of the whole arena cannot see a small layer)
+        # (r5: layer by layer -- the cosine of the whole arena cannot see a small layer)
         model = None
         if prec != "f32":   # the 16-bit branch: the rounding reference of the route's model (tests/half_ref.py)
-            import half_ref as hr
             model = hr.route_model(tr.last_route()[0][0])
         ok, note = per_layer_gradient_check(dims, [1, 1, 1, 1, 0], Ws, bs, x, g, ref[1], prec, tgt=y, w=w, loss=loss, model=model)
         assert ok, (prec, note)
@@ -166,12 +139,11 @@ def test_reference_architecture_step_all_precisions(ctx):
 
 def test_loss_decreases_and_state_roundtrip(ctx):
     dims = [7, 64, 64, 20]
-    st, tr, Ws, bs = _make(ctx, dims, seed=9, max_batch=128)
+    st, tr, Ws, bs = _make(ctx, dims, seed=9, max_batch=128, lr=3e-3)
     rng = np.random.default_rng(3)
     x = rng.uniform(-1, 1, size=(1000, 7)).astype(np.float32)
     y = np.tanh(x @ rng.normal(size=(7, 20))).astype(np.float32)
     w = ora.mse_row_weight(y).astype(np.float32)
-    tr.set_adam(lr=3e-3)
     tr.set_data(0, x, y, w)
     losses = [tr.run_epoch(ora.epoch_permutation(1000, 0, ep), 128) for ep in range(8)]
     assert losses[-1] < 0.5 * losses[0], losses
@@ -218,7 +190,6 @@ def test_layers_wider_than_512_train_on_the_per_layer_path(ctx, prec):
     and step through the per-layer NT kernels (csrc/gemm_nt.h); until r4 its launcher REFUSED a contraction over more than
     512 features (V21_ERR_UNSUPPORTED: such a stack could predict but not train) although the kernel walks any range in
     rounds.  First-step loss and full gradient against the float64 oracle, then the loss falls."""
-    native = pkg("_native")
     dims, act = [7, 600, 520, 33], [1, 1, 0]
     n = 300
     rng = np.random.default_rng(3)
@@ -227,27 +198,16 @@ def test_layers_wider_than_512_train_on_the_per_layer_path(ctx, prec):
     x = rng.uniform(-1, 1, size=(n, 7)).astype(np.float32)
     y = rng.normal(size=(n, 33)).astype(np.float32)
     w = ora.mse_row_weight(y).astype(np.float32)
-    st = native.Stack(ctx, dims, act); st.set_weights(ora.flatten_params(Ws, bs))
-    tr = native.Trainer(st, prec, n); tr.set_adam(lr=1e-3)
+    st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, n, lr=1e-3)
     tr.set_data(0, x, y, w)
     l1 = tr.run_epoch(None, n); g = tr.get_grad()
-    acts = [x.astype(np.float64)]
-    for W_, b_, a_ in zip(Ws, bs, act):
-        z = acts[-1] @ W_.astype(np.float64) + b_.astype(np.float64)
-        acts.append(np.maximum(z, 0) if a_ else z)
-    lo, dz = ora.batch_loss_and_grad(acts[-1], y.astype(np.float64), w.astype(np.float64))
-    dWs, dbs = [None] * 3, [None] * 3
-    for li in range(2, -1, -1):
-        dWs[li] = acts[li].T @ dz; dbs[li] = dz.sum(0)
-        dh = dz @ Ws[li].astype(np.float64).T
-        dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
-    go = ora.flatten_params(dWs, dbs)
+    lo, go = oracle_step(Ws, bs, act, x, y, w)
     tol = 2e-5 if prec == "f32" else 3e-3
     assert abs(l1 - lo) <= tol * lo, (l1, lo)
     if prec == "f32":
         _close(g, go, 2e-5, "gradient of a 600-wide stack")
     else:
-        assert float(g @ go / (np.linalg.norm(g) * np.linalg.norm(go))) > 0.9995
+        assert _cos(g, go) > 0.9995
     losses = [tr.run_epoch(None, 100) for _ in range(10)]
     assert losses[-1] < 0.9 * l1, (l1, losses)
 
@@ -275,40 +235,24 @@ def test_rccl_single_rank_communicator_is_identity():
 def test_large_batch_step_uses_big_tiles_and_split_k(ctx):
     """Per-GPU batch 4096 (BASELINE configs[3]): 64x64 workgroup tiles, the batch contraction of
     the weight gradient split into slabs; same gradient as the oracle."""
-    synth = pkg("synth")
-    dims = [451, 352, 9, 32, 352, 451]
-    act = [1, 0, 1, 1, 0]
+    dims, act = STACKS["AE"]
     n = 4096
-    st, tr, Ws, bs = _make(ctx, dims, act=act, seed=12, max_batch=n)
-    sig = synth.make_signals(n, seed=9)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
-    tr.set_adam(lr=1e-3)
+    st, tr, Ws, bs = _make(ctx, dims, act=act, seed=12, max_batch=n, lr=1e-3)
+    y, w = signal_rows(n, seed=9)
     tr.set_data(0, y, None, w)
     loss = tr.run_epoch(None, n)
     g = tr.get_grad()
     # float64 oracle gradient of the same stack
-    W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
-    acts = [y.astype(np.float64)]
-    for W_, b_, a in zip(W, b, act):
-        z = acts[-1] @ W_ + b_
-        acts.append(np.maximum(z, 0) if a else z)
-    l, dz = ora.batch_loss_and_grad(acts[-1], y.astype(np.float64), w.astype(np.float64))
-    dWs, dbs = [None] * 5, [None] * 5
-    for li in range(4, -1, -1):
-        dWs[li] = acts[li].T @ dz; dbs[li] = dz.sum(0)
-        dh = dz @ W[li].T
-        dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
-    ref = ora.flatten_params(dWs, dbs)
+    l, ref = oracle_step(Ws, bs, act, y, y, w)
     assert abs(loss - l) / l < 2e-5
     _close(g, ref, 5e-4, "gradient at batch 4096")
 
 
-FUSED_TRAIN_STACKS = [   # csrc/archs.h: the stacks with a compiled fused training kernel (csrc/fused_train.h)
-    ("T1 autoencoder", [451, 352, 9, 32, 352, 451], [1, 0, 1, 1, 0], True),
-    ("T2 latent emulator", [7, 352, 352, 352, 224, 9], [1, 1, 1, 1, 0], False),
-    ("T3 direct emulator (reference default)", [7, 288, 352, 288, 224, 451], [1, 1, 1, 1, 0], False),
-    ("T4 direct emulator (configs[1])", [7, 352, 352, 352, 224, 451], [1, 1, 1, 1, 0], False),
+FUSED_TRAIN_STACKS = [   # csrc/archs.h: the stacks with a compiled fused training kernel (csrc/fused_train.h); (name, dims, act, y = x)
+    ("T1 autoencoder",) + STACKS["AE"] + (True,),
+    ("T2 latent emulator",) + STACKS["LE"] + (False,),
+    ("T3 direct emulator (reference default)",) + STACKS["DE"] + (False,),
+    ("T4 direct emulator (configs[1])",) + STACKS["D1"] + (False,),
 ]
 
 
@@ -327,7 +271,6 @@ def test_fused_training_kernel_matches_chain_route_and_oracle(ctx, case, prec, r
     every stack it is compiled for: loss and
     FULL gradient against the 32-row chain route (the same 16-bit arithmetic in another order) and the float64 oracle, a
     second step (the packed stream is rebuilt from the arena Adam moved), targets = inputs and separate targets."""
-    native, synth = pkg("_native"), pkg("synth")
     monkeypatch.setenv("V21_FUSED_TRAIN16", "1" if rows_per_wave == 16 else "0")
     name, dims, act, ae = FUSED_TRAIN_STACKS[case]
     n = 777
@@ -336,23 +279,18 @@ def test_fused_training_kernel_matches_chain_route_and_oracle(ctx, case, prec, r
     bs = [rng.normal(scale=0.05, size=b.shape).astype(np.float32) for b in bs]
     flat = ora.flatten_params(Ws, bs)
     if ae:
-        sig = synth.make_signals(n, seed=9)
-        x = ora.preproc(sig, sig); y = None
-        w = ora.relative_mse_row_weight(x, sig).astype(np.float32)
+        (x, w), y = signal_rows(n, seed=9), None
     else:
         x = rng.uniform(-1, 1, size=(n, dims[0])).astype(np.float32)
         if dims[-1] == 451:
-            sig = synth.make_signals(n, seed=10)
-            y = ora.preproc(sig, sig)
-            w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+            y, w = signal_rows(n, seed=10)
         else:
             y = rng.normal(size=(n, dims[-1])).astype(np.float32)
             w = ora.mse_row_weight(y).astype(np.float32)
     res = {}
     for route, rows_env in (("chain", "1000000"), ("fused", "1")):
         monkeypatch.setenv("V21_FUSED_TRAIN_ROWS", rows_env)
-        st = native.Stack(ctx, dims, act); st.set_weights(flat)
-        tr = native.Trainer(st, prec, n); tr.set_adam(lr=1e-3)
+        st, tr = new_trainer(ctx, dims, act, flat, prec, n, lr=1e-3)
         tr.set_data(0, x, y, w)
         l1 = tr.run_epoch(None, n)
         g1 = tr.get_grad()
@@ -365,29 +303,15 @@ def test_fused_training_kernel_matches_chain_route_and_oracle(ctx, case, prec, r
         if route == "fused":       # the first step packs the stream, the second finds it written by the first's Adam pass
             assert rc["stream_packs"] == 1 and rc["stream_adam"] == 2, rc
     # float64 oracle: loss and gradient of the first step
-    W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
-    acts = [x.astype(np.float64)]
-    for W_, b_, a_ in zip(W, b, act):
-        z = acts[-1] @ W_ + b_
-        acts.append(np.maximum(z, 0) if a_ else z)
     tgt = (x if y is None else y).astype(np.float64)
-    lo, dz = ora.batch_loss_and_grad(acts[-1], tgt, w.astype(np.float64))
-    L = len(act)
-    dWs, dbs = [None] * L, [None] * L
-    for li in range(L - 1, -1, -1):
-        dWs[li] = acts[li].T @ dz; dbs[li] = dz.sum(0)
-        dh = dz @ W[li].T
-        dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
-    go = ora.flatten_params(dWs, dbs)
+    lo, go = oracle_step(Ws, bs, act, x, tgt, w)
     tol_l, tol_c = (3e-3, 0.9995) if prec == "f16" else (3e-2, 0.995)
-    import half_ref as hr
-    from helpers import HALF_STEP_TOL, per_layer_gradient_check
     perm2 = ora.epoch_permutation(n, 3, 0)
     for route in ("chain", "fused"):
         l1, g1, l2, _, kind, w_mid = res[route]
         assert kind == ("chain16" if route == "chain" else ("fused64" if rows_per_wave == 16 else "fused128")), (route, kind)
         assert abs(l1 - lo) / lo < tol_l, (name, route, l1, lo)
-        cos = float(g1 @ go / (np.linalg.norm(g1) * np.linalg.norm(go)))
+        cos = _cos(g1, go)
         assert cos > tol_c and abs(np.linalg.norm(g1) / np.linalg.norm(go) - 1) < 10 * tol_l, (name, route, cos)
         # ... and against the rounding reference of the route's model (tests/half_ref.py), every mutation refused
         ok, note = per_layer_gradient_check(dims, act, Ws, bs, x, g1, go, prec, tgt=tgt, w=w, loss=l1, model=hr.route_model(kind))
@@ -402,10 +326,10 @@ def test_fused_training_kernel_matches_chain_route_and_oracle(ctx, case, prec, r
     (lc, gc, lc2, wc, _, _), (lf, gf, lf2, wf, _, _) = res["chain"], res["fused"]
     # the two routes round the same operands to 16 bits and sum in fp32: they agree far better than either meets float64
     assert abs(lf - lc) / lc < 1e-5 and abs(lf2 - lc2) / lc2 < 1e-3, (name, lf, lc, lf2, lc2)
-    cos = float(gc @ gf / (np.linalg.norm(gc) * np.linalg.norm(gf)))
+    cos = _cos(gc, gf)
     assert cos > 0.99999 and np.abs(gc - gf).max() <= 2e-3 * np.abs(gc).max(), (name, cos, np.abs(gc - gf).max(), np.abs(gc).max())
     dc, df = wc - flat, wf - flat
-    assert float(dc @ df / (np.linalg.norm(dc) * np.linalg.norm(df))) > 0.999
+    assert _cos(dc, df) > 0.999
 
 
 @pytest.mark.parametrize("rows_per_wave", [32, 16])
@@ -417,7 +341,6 @@ def test_fused_training_stream_written_by_adam_equals_the_packed_one(ctx, prec, 
     trainer handed the same weights (whose first step packs the stream from the arena) bit for bit, on a
     ragged autoencoder step and on the direct emulator; then set_weights between fused steps invalidates the stream
     (the next step packs again and reproduces the very first loss)."""
-    native, synth = pkg("_native"), pkg("synth")
     monkeypatch.setenv("V21_FUSED_TRAIN_ROWS", "1")
     monkeypatch.setenv("V21_FUSED_TRAIN16", "1" if rows_per_wave == 16 else "0")
     for name, dims, act, ae in (FUSED_TRAIN_STACKS[0], FUSED_TRAIN_STACKS[3]):
@@ -426,12 +349,9 @@ def test_fused_training_stream_written_by_adam_equals_the_packed_one(ctx, prec, 
         Ws, bs = ora.init_mlp(dims, seed=77)
         bs = [rng.normal(scale=0.05, size=b.shape).astype(np.float32) for b in bs]
         flat = ora.flatten_params(Ws, bs)
-        sig = synth.make_signals(n, seed=11)
-        tgt = ora.preproc(sig, sig)
-        w = ora.relative_mse_row_weight(tgt, sig).astype(np.float32)
+        tgt, w = signal_rows(n, seed=11)
         x, y = (tgt, None) if ae else (rng.uniform(-1, 1, size=(n, dims[0])).astype(np.float32), tgt)
-        st = native.Stack(ctx, dims, act); st.set_weights(flat)
-        tr = native.Trainer(st, prec, n); tr.set_adam(lr=1e-3)
+        st, tr = new_trainer(ctx, dims, act, flat, prec, n, lr=1e-3)
         tr.set_data(0, x, y, w)
         l1 = tr.run_epoch(None, n)
         for _ in range(2):
@@ -441,8 +361,7 @@ def test_fused_training_stream_written_by_adam_equals_the_packed_one(ctx, prec, 
         l4 = tr.run_epoch(None, n); g4 = tr.get_grad()
         rc = tr.route_counters()
         assert rc["fused"] == 4 and rc["stream_packs"] == 1 and rc["chain"] == 0, rc
-        st2 = native.Stack(ctx, dims, act); st2.set_weights(w3)
-        tr2 = native.Trainer(st2, prec, n); tr2.set_adam(lr=1e-3)
+        st2, tr2 = new_trainer(ctx, dims, act, w3, prec, n, lr=1e-3)
         tr2.set_data(0, x, y, w)
         l4p = tr2.run_epoch(None, n); g4p = tr2.get_grad()
         assert tr2.route_counters()["stream_packs"] == 1
@@ -455,34 +374,21 @@ def test_fused_training_stream_written_by_adam_equals_the_packed_one(ctx, prec, 
 
 
 # ---- A13: variational latent layer (V21_ACT_GAUSS) -- build-side extension ----------------
-def _make_vae(ctx, dims, gl, seed=0, max_batch=256, prec="f32"):
-    """dims = widths the NEXT layer sees; layer `gl` is the (z_mean | z_log_var) head, so its
-    kernel is (dims[gl], 2*dims[gl+1])."""
-    native = pkg("_native")
-    rng = np.random.default_rng(seed)
-    L = len(dims) - 1
-    act = [2 if l == gl else (1 if l < L - 1 else 0) for l in range(L)]
-    Ws, bs = [], []
-    for l in range(L):
-        nout = dims[l + 1] * (2 if l == gl else 1)
-        Ws.append(ora.glorot_uniform(rng, dims[l], nout))
-        bs.append(rng.normal(scale=0.05, size=nout).astype(np.float32))
-    st = native.Stack(ctx, dims, act)
+def _make_vae(ctx, dims, gl, seed=0, max_batch=256, prec="f32", env=None):
+    """train_support.vae_weights: layer `gl` is the (z_mean | z_log_var) head"""
+    act, Ws, bs = vae_weights(dims, gl, seed)
+    st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, max_batch, env=env)
     assert st.num_params == sum(W.size + b.size for W, b in zip(Ws, bs))
-    st.set_weights(ora.flatten_params(Ws, bs))
-    return st, native.Trainer(st, prec, max_batch), Ws, bs
+    return st, tr, Ws, bs
 
 
 def test_vae_step_matches_oracle(ctx):
     """Sampled step: loss (reconstruction + kl_weight KL) and the full gradient against the
     float64 oracle fed the same counter-based noise; then Adam moved the weights."""
-    synth = pkg("synth")
     dims = [451, 64, 9, 32, 451]
     st, tr, Ws, bs = _make_vae(ctx, dims, gl=1, seed=21, max_batch=160)
     n = 150
-    sig = synth.make_signals(n, seed=4)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(n, seed=4)
     kl_weight, seed = 2e-3, 0xDEADBEEF12345
     tr.set_vae(kl_weight, sample=True, seed=seed)
     tr.set_adam(lr=1e-3)
@@ -540,24 +446,18 @@ def test_chain_job_table_is_validated_against_the_packed_streams(ctx):
 def test_vae_without_noise_and_kl_equals_plain_autoencoder(ctx):
     """kl_weight = 0 and eps = 0 must give the deterministic autoencoder of emulator.py:517:
     same loss and same gradients as the plain stack holding the z_mean columns."""
-    native = pkg("_native")
-    synth = pkg("synth")
     dims = [451, 48, 9, 16, 451]
     st, tr, Ws, bs = _make_vae(ctx, dims, gl=1, seed=5, max_batch=128)
     n = 100
-    sig = synth.make_signals(n, seed=6)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(n, seed=6)
     tr.set_vae(0.0, sample=False, seed=1)
     tr.set_adam(lr=1e-3); tr.set_data(0, y, None, w)
     loss = tr.run_epoch(None, n)
     g = tr.get_grad()
     Wp = [Ws[0], np.ascontiguousarray(Ws[1][:, :9]), Ws[2], Ws[3]]
     bp = [bs[0], bs[1][:9].copy(), bs[2], bs[3]]
-    st2 = native.Stack(ctx, dims, [1, 0, 1, 0])
-    st2.set_weights(ora.flatten_params(Wp, bp))
-    tr2 = native.Trainer(st2, "f32", 128)
-    tr2.set_adam(lr=1e-3); tr2.set_data(0, y, None, w)
+    st2, tr2 = new_trainer(ctx, dims, [1, 0, 1, 0], ora.flatten_params(Wp, bp), "f32", 128, lr=1e-3)
+    tr2.set_data(0, y, None, w)
     loss2 = tr2.run_epoch(None, n)
     g2 = tr2.get_grad()
     assert loss == loss2
@@ -595,38 +495,24 @@ def _half_ref_check(tag, dims, act, Ws, bs, x, tgt, w, loss, g, prec, route, bro
     """the 16-bit branch of the step checks (helpers.half_step_check): loss and FULL gradient against the float64 reference
     that rounds where the kernels round, in the ReLU model of the route taken (tests/half_ref.py); every mutation of the
     catalogue applied to the device's own result refused"""
-    import half_ref as hr
-    from helpers import half_step_check
     dims = [np.shape(Ws[0])[0]] + [np.shape(W)[1] for W in Ws]
     ok, note, _ = half_step_check(dims, act, Ws, bs, x, tgt, w, loss, g, prec, hr.route_model(route), brows=brows)
     assert ok, (tag, route, note)
 
 
+def _chain_env(chain):
+    """the path is chosen when the trainer is created"""
+    return {"V21_TRAIN_CHAIN": "1" if chain else "0"}
+
+
 def _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain, route=None):
-    import os
-    native = pkg("_native")
     Ws, bs = ora.init_mlp(dims, seed=31)
-    old = os.environ.get("V21_TRAIN_CHAIN")
-    os.environ["V21_TRAIN_CHAIN"] = "1" if chain else "0"
-    try:
-        st = native.Stack(ctx, dims, act)
-        st.set_weights(ora.flatten_params(Ws, bs))
-        tr = native.Trainer(st, prec, batch)  # the path is chosen when the trainer is created
-    finally:
-        if old is None:
-            os.environ.pop("V21_TRAIN_CHAIN")
-        else:
-            os.environ["V21_TRAIN_CHAIN"] = old
-    tr.set_adam(lr=1e-3)
+    st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, batch, lr=1e-3, env=_chain_env(chain))
     tr.set_data(0, x, y, w)
     loss = tr.run_epoch(perm, batch)
     if route is not None:   # (a list: the forward route the step took is appended)
         route.append(tr.last_route()[0][0])
     return loss, tr.get_grad().astype(np.float64), st.get_weights(), (Ws, bs)
-
-
-def _cos(a, b):
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
 
 
 @pytest.mark.parametrize("prec", ["f16", "bf16"])
@@ -638,40 +524,28 @@ def test_chain_kernel_matches_per_layer_path_and_oracle(ctx, prec, case):
     separate targets with a 7-wide input; a batch whose weight gradient is split into slabs."""
     synth = pkg("synth")
     if case == "direct_7_to_451":
-        dims, act, n = [7, 288, 352, 288, 224, 451], [1, 1, 1, 1, 0], 300
+        (dims, act), n = STACKS["DE"], 300
         par = synth.make_params(n, seed=3)
         x = ora.par_transform(par, par).astype(np.float32)
         sig = synth.signals_from_params(par)
         y = ora.preproc(sig, sig)
+        w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
         batch = 300
     else:
-        dims, act = [451, 352, 9, 32, 352, 451], [1, 0, 1, 1, 0]
+        dims, act = STACKS["AE"]
         n = 4096 if case == "batch_4096" else 200
-        sig = synth.make_signals(n, seed=13)
-        x = ora.preproc(sig, sig); y = None
+        (x, w), y = signal_rows(n, seed=13), None
         batch = n
-    w = ora.relative_mse_row_weight(x if y is None else y, sig).astype(np.float32)
     perm = np.random.default_rng(2).permutation(n).astype(np.int32)
     routes = []
     lc, gc, wc, (Ws, bs) = _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain=True, route=routes)
     ln, gn, wn, _ = _one_step(ctx, dims, act, prec, x, y, w, perm, batch, chain=False, route=routes)
     assert routes == ["chain16", "per_layer"], routes
+    tgt = x if y is None else y
     for (l_, g_), r_ in zip(((lc, gc), (ln, gn)), routes):   # both routes against the rounding reference
-        _half_ref_check(case, dims, act, Ws, bs, x[perm], (x if y is None else y)[perm], w[perm], l_, g_, prec, r_)
+        _half_ref_check(case, dims, act, Ws, bs, x[perm], tgt[perm], w[perm], l_, g_, prec, r_)
     # float64 oracle of the same step
-    W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
-    xs = x[perm].astype(np.float64); ys = xs if y is None else y[perm].astype(np.float64)
-    acts = [xs]
-    for W_, b_, a_ in zip(W, b, act):
-        z = acts[-1] @ W_ + b_
-        acts.append(np.maximum(z, 0) if a_ else z)
-    lo, dz = ora.batch_loss_and_grad(acts[-1], ys, w[perm].astype(np.float64))
-    dWs, dbs = [None] * len(W), [None] * len(W)
-    for li in range(len(W) - 1, -1, -1):
-        dWs[li] = acts[li].T @ dz; dbs[li] = dz.sum(0)
-        dh = dz @ W[li].T
-        dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
-    go = ora.flatten_params(dWs, dbs)
+    lo, go = oracle_step(Ws, bs, act, x[perm], tgt[perm], w[perm])
     tol = 2e-3 if prec == "f16" else 2e-2
     assert abs(lc - lo) / lo < tol and abs(lc - ln) / ln < tol, (lc, ln, lo)
     assert _cos(gc, go) > (0.9995 if prec == "f16" else 0.995), _cos(gc, go)
@@ -686,26 +560,17 @@ def test_chain_kernel_trains_and_validates(ctx):
     """Several epochs through the chain path: the loss falls, the validation pass (per-layer
     forward on the refreshed weight copies) agrees with the training loss level, and predict()
     sees the trained weights."""
-    synth = pkg("synth")
-    native = pkg("_native")
     dims, act = [451, 64, 9, 32, 451], [1, 0, 1, 0]
     Ws, bs = ora.init_mlp(dims, seed=4)
-    st = native.Stack(ctx, dims, act); st.set_weights(ora.flatten_params(Ws, bs))
-    tr = native.Trainer(st, "f16", 256)
-    sig = synth.make_signals(1000, seed=21)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
-    tr.set_adam(lr=2e-3); tr.set_data(0, y, None, w); tr.set_data(1, y[:300], None, w[:300])
+    st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), "f16", 256, lr=2e-3)
+    y, w = signal_rows(1000, seed=21)
+    tr.set_data(0, y, None, w); tr.set_data(1, y[:300], None, w[:300])
     losses = [tr.run_epoch(ora.epoch_permutation(1000, 3, ep), 256) for ep in range(12)]
     assert losses[-1] < 0.5 * losses[0], losses
     v = tr.evaluate(1, 256)
     assert 0.3 * losses[-1] < v < 3 * losses[-1]
     Wt, bt = ora.unflatten_params(st.get_weights().astype(np.float64), dims)
-    p = y[:50].astype(np.float64)
-    for W_, b_, a_ in zip(Wt, bt, act):
-        p = p @ W_ + b_
-        p = np.maximum(p, 0) if a_ else p
-    np.testing.assert_allclose(st.forward(y[:50], "f32"), p, atol=5e-4, rtol=1e-3)
+    np.testing.assert_allclose(st.forward(y[:50], "f32"), forward64(Wt, bt, act, y[:50]), atol=5e-4, rtol=1e-3)
 
 
 @pytest.mark.parametrize("prec", ["f16", "bf16"])
@@ -713,27 +578,18 @@ def test_validation_pass_is_one_forward_only_chain_launch(ctx, prec):
     """v21_trainer_eval on the chain path: one forward-only launch over ALL rows of the split (more than max_batch,
     not a multiple of 32), against the float64 oracle's loss of the same weights; training state is left alone (the
     next epoch's loss and weights are those of a trainer that never validated)."""
-    native = pkg("_native")
-    synth = pkg("synth")
     dims, act = [451, 64, 9, 32, 451], [1, 0, 1, 0]
     Ws, bs = ora.init_mlp(dims, seed=9)
-    sig = synth.make_signals(1500, seed=5)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(1500, seed=5)
     res = []
     for validate in (True, False):
-        st = native.Stack(ctx, dims, act); st.set_weights(ora.flatten_params(Ws, bs))
-        tr = native.Trainer(st, prec, 128)
-        tr.set_adam(lr=1e-3); tr.set_data(0, y[:500], None, w[:500]); tr.set_data(1, y[500:1477], None, w[500:1477])
+        st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, 128, lr=1e-3)
+        tr.set_data(0, y[:500], None, w[:500]); tr.set_data(1, y[500:1477], None, w[500:1477])
         tr.run_epoch(None, 128)
         if validate:
             v = tr.evaluate(1, 128)
             W, b = ora.unflatten_params(st.get_weights().astype(np.float64), dims)
-            h = y[500:1477].astype(np.float64)
-            for W_, b_, a_ in zip(W, b, act):
-                h = h @ W_ + b_
-                h = np.maximum(h, 0) if a_ else h
-            expect = float(np.mean(ora.per_sample_loss(h, y[500:1477].astype(np.float64), w[500:1477].astype(np.float64))))
+            expect = loss64(W, b, act, y[500:1477], y[500:1477], w[500:1477])
             assert abs(v - expect) / expect < (3e-3 if prec == "f16" else 3e-2), (v, expect)
             assert abs(tr.evaluate(1, 64) - v) == 0.0  # the batch argument no longer cuts the pass: same launch, same sum
         res.append((tr.run_epoch(None, 128), st.get_weights()))
@@ -757,20 +613,9 @@ def test_chain_kernel_odd_shapes(ctx, dims, act, n):
     routes = []
     lc, gc, _, (Ws, bs) = _one_step(ctx, dims, act, "f16", x, y, w, perm, max(n, 2), chain=True, route=routes)
     assert routes == ["chain16"], routes
-    _half_ref_check(dims, dims, act, Ws, bs, x[perm], (x if y is None else y)[perm], w[perm], lc, gc, "f16", routes[0])
-    W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
-    xs = x[perm].astype(np.float64); ys = xs if y is None else y[perm].astype(np.float64)
-    acts = [xs]
-    for W_, b_, a_ in zip(W, b, act):
-        z = acts[-1] @ W_ + b_
-        acts.append(np.maximum(z, 0) if a_ else z)
-    lo, dz = ora.batch_loss_and_grad(acts[-1], ys, w[perm].astype(np.float64))
-    dWs, dbs = [None] * len(W), [None] * len(W)
-    for li in range(len(W) - 1, -1, -1):
-        dWs[li] = acts[li].T @ dz; dbs[li] = dz.sum(0)
-        dh = dz @ W[li].T
-        dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
-    go = ora.flatten_params(dWs, dbs)
+    tgt = x if y is None else y
+    _half_ref_check(dims, dims, act, Ws, bs, x[perm], tgt[perm], w[perm], lc, gc, "f16", routes[0])
+    lo, go = oracle_step(Ws, bs, act, x[perm], tgt[perm], w[perm])
     assert abs(lc - lo) / lo < 3e-3, (lc, lo)
     assert _cos(gc, go) > 0.9995, _cos(gc, go)
     assert abs(np.linalg.norm(gc) / np.linalg.norm(go) - 1) < 5e-3
@@ -788,39 +633,26 @@ def test_one_launch_gradient_adam_kernel_state_and_packed_copies(ctx, prec, dims
     the packed 16-bit weight copies this kernel rebuilt -- is the float64 forward loss of the arena weights.  A stale,
     misplaced or missing fragment of the packed copies shows up as a loss that is off by far more than the
     precision's tolerance."""
-    native = pkg("_native")
     rng = np.random.default_rng(11)
     x = rng.normal(size=(n, dims[0])).astype(np.float32)
     y = None if dims[0] == dims[-1] else rng.normal(size=(n, dims[-1])).astype(np.float32)
     w = rng.uniform(0.5, 1.5, size=n).astype(np.float32) / dims[-1]
+    tgt = x if y is None else y
     Ws, bs = ora.init_mlp(dims, seed=7)
-    st = native.Stack(ctx, dims, act); st.set_weights(ora.flatten_params(Ws, bs))
-    tr = native.Trainer(st, prec, n)
-    tr.set_adam(lr=5e-3); tr.set_data(0, x, y, w)
+    st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, n, lr=5e-3)
+    tr.set_data(0, x, y, w)
     ostate = ora.AdamState(st.num_params, dtype=np.float64, lr=5e-3)
     flat = ora.flatten_params(Ws, bs).astype(np.float64)
     tol = 3e-3 if prec == "f16" else 3e-2
-
-    def oracle_loss(flat64):
-        W, b = ora.unflatten_params(flat64, dims)
-        h = x.astype(np.float64)
-        for W_, b_, a_ in zip(W, b, act):
-            h = h @ W_ + b_
-            h = np.maximum(h, 0) if a_ else h
-        t = x.astype(np.float64) if y is None else y.astype(np.float64)
-        return float(np.mean(ora.per_sample_loss(h, t, w.astype(np.float64))))
-
-    import half_ref as hr
     for step in range(3):
-        before = st.get_weights()
-        expect = oracle_loss(before.astype(np.float64))
+        Wb, bb = ora.unflatten_params(st.get_weights(), dims)   # the arena before the step
+        expect = loss64(Wb, bb, act, x, tgt, w)
         loss = tr.run_epoch(None, n)
         assert abs(loss - expect) / expect < tol, (step, loss, expect)
         g = tr.get_grad().astype(np.float64)
         # ... and against the rounding reference of the arena weights before the step: steps 2 and 3 run on the packed
         # copies this kernel rebuilt, where a stale or misplaced fragment shows at ~1e-6 instead of the float64 bound
-        Wb, bb = ora.unflatten_params(before, dims)
-        _half_ref_check((dims, step), dims, act, Wb, bb, x, x if y is None else y, w, loss, g, prec, tr.last_route()[0][0])
+        _half_ref_check((dims, step), dims, act, Wb, bb, x, tgt, w, loss, g, prec, tr.last_route()[0][0])
         flat = ora.adam_step(flat, g, ostate)
         it, m, v = tr.get_state()
         assert it == step + 1
@@ -840,47 +672,32 @@ def test_f32_chain_kernel_matches_per_layer_path_and_oracle(ctx, case, rows, mon
     (V21_TRAIN_CHAIN=0) and the float64 oracle at the stated f32 tolerance: loss 2e-5, gradient 2e-4 of its scale,
     weights after the step, Adam moments; then two more epochs with a partial last batch and the forward-only
     validation launch."""
-    import os
     monkeypatch.setenv("V21_CHAIN32S", "0" if rows == "rows16" else "1")
     monkeypatch.setenv("V21_C32S_ROWS", "4" if rows == "rows4" else "8")
-    native, synth = pkg("_native"), pkg("synth")
+    synth = pkg("synth")
     if case == "direct_7_to_451":
-        dims, act, n = [7, 288, 352, 288, 224, 451], [1, 1, 1, 1, 0], 300
+        (dims, act), n = STACKS["DE"], 300
         par = synth.make_params(n, seed=3)
         x = ora.par_transform(par, par).astype(np.float32)
         sig = synth.signals_from_params(par)
         y = ora.preproc(sig, sig)
         w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
     elif case == "latent_emulator":
-        dims, act, n = [7, 352, 352, 352, 224, 9], [1, 1, 1, 1, 0], 257
+        (dims, act), n = STACKS["LE"], 257
         rng = np.random.default_rng(3)
         x = rng.uniform(-1, 1, size=(n, 7)).astype(np.float32)
         y = rng.normal(size=(n, 9)).astype(np.float32)
         w = ora.mse_row_weight(y).astype(np.float32)
     else:
-        dims, act = [451, 352, 9, 32, 352, 451], [1, 0, 1, 1, 0]
+        dims, act = STACKS["AE"]
         n = {"autoencoder_ragged": 203, "batch_4096": 4096, "single_row": 1}[case]
-        sig_all = synth.make_signals(max(n, 64), seed=13)   # (statistics over >= 64 signals: one row alone pre-processes to zeros)
-        sig = sig_all[:n]
-        x = ora.preproc(sig, sig_all); y = None
-        w = ora.relative_mse_row_weight(x, sig_all).astype(np.float32)
+        (x, w), y = signal_rows(n, seed=13, stats_from=max(n, 64)), None   # (statistics over >= 64 signals: one row alone pre-processes to zeros)
     perm = np.random.default_rng(2).permutation(n).astype(np.int32)
     batch = max(n, 2)
     res = {}
     for chain in (True, False):
-        old = os.environ.get("V21_TRAIN_CHAIN")
-        os.environ["V21_TRAIN_CHAIN"] = "1" if chain else "0"
-        try:
-            Ws, bs = ora.init_mlp(dims, seed=31)
-            st = native.Stack(ctx, dims, act)
-            st.set_weights(ora.flatten_params(Ws, bs))
-            tr = native.Trainer(st, "f32", batch)
-        finally:
-            if old is None:
-                os.environ.pop("V21_TRAIN_CHAIN")
-            else:
-                os.environ["V21_TRAIN_CHAIN"] = old
-        tr.set_adam(lr=1e-3)
+        Ws, bs = ora.init_mlp(dims, seed=31)
+        st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), "f32", batch, lr=1e-3, env=_chain_env(chain))
         tr.set_data(0, x, y, w)
         tr.set_data(1, x[: max(1, n // 3)], None if y is None else y[: max(1, n // 3)], w[: max(1, n // 3)])
         loss = tr.run_epoch(perm, batch)
@@ -891,21 +708,9 @@ def test_f32_chain_kernel_matches_per_layer_path_and_oracle(ctx, case, rows, mon
         val = tr.evaluate(1, batch)
         res[chain] = (loss, g, w1, m1, v1, np.array(more + [val]), st.get_weights(), tr.get_state()[0])
     # float64 oracle of the first step
-    W = [a.astype(np.float64) for a in Ws]; b = [a.astype(np.float64) for a in bs]
-    xs = x[perm].astype(np.float64); ys = xs if y is None else y[perm].astype(np.float64)
     sto = ora.AdamState(st.num_params, dtype=np.float64, lr=1e-3)
-    acts = [xs]
-    for W_, b_, a_ in zip(W, b, act):
-        z = acts[-1] @ W_ + b_
-        acts.append(np.maximum(z, 0) if a_ else z)
-    lo, dz = ora.batch_loss_and_grad(acts[-1], ys, w[perm].astype(np.float64))
-    dWs, dbs = [None] * len(W), [None] * len(W)
-    for li in range(len(W) - 1, -1, -1):
-        dWs[li] = acts[li].T @ dz; dbs[li] = dz.sum(0)
-        dh = dz @ W[li].T
-        dz = dh * (acts[li] > 0) if li > 0 and act[li - 1] else dh
-    go = ora.flatten_params(dWs, dbs)
-    W2, b2 = ora.unflatten_params(ora.adam_step(ora.flatten_params(W, b), go, sto), dims)
+    lo, go = oracle_step(Ws, bs, act, x[perm], (x if y is None else y)[perm], w[perm])
+    W2, b2 = ora.unflatten_params(ora.adam_step(ora.flatten_params(Ws, bs).astype(np.float64), go, sto), dims)
     lc, gc, wc, mc, vc, morec, wend, itc = res[True]
     ln, gn, wn, mn, vn, moren, wendn, itn = res[False]
     assert abs(lc - lo) / lo < 2e-5 and abs(lc - ln) / ln < 2e-5, (lc, ln, lo)
@@ -964,20 +769,14 @@ def test_data_parallel_arithmetic_without_a_communicator(ctx, prec):
     """What two ranks would feed the all-reduce: each takes its slice of the global batch with
     global_rows = B in the loss scale; the SUM of the two gradient arenas (and of the two loss slots)
     must be the single-process full-batch gradient (per-layer path in f32, chain kernel in f16)."""
-    native = pkg("_native")
-    synth = pkg("synth")
     dims, act = [451, 96, 9, 32, 451], [1, 0, 1, 0]
     n, cut = 200, 77  # uneven split, neither part a multiple of 32
-    sig = synth.make_signals(n, seed=17)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(n, seed=17)
     Ws, bs = ora.init_mlp(dims, seed=2)
     flat = ora.flatten_params(Ws, bs)
 
     def grad_of(rows, global_rows):
-        st = native.Stack(ctx, dims, act); st.set_weights(flat)
-        tr = native.Trainer(st, prec, 256)
-        tr.set_adam(lr=0.0)
+        st, tr = new_trainer(ctx, dims, act, flat, prec, 256, lr=0.0)
         d_x, d_w = ctx.malloc(y[rows].nbytes), ctx.malloc(w[rows].nbytes)
         ctx.h2d(d_x, np.ascontiguousarray(y[rows])); ctx.h2d(d_w, np.ascontiguousarray(w[rows]))
         tr.step_dev(d_x, None, d_w, len(y[rows]), global_rows)
@@ -1005,25 +804,13 @@ def test_variational_stack_on_the_chain_kernel(ctx, prec, monkeypatch):
     if prec.startswith("f32"):
         monkeypatch.setenv("V21_C32S_ROWS", "8" if prec == "f32_rows8" else "4")
         prec = "f32"
-    import os
-    synth = pkg("synth")
     dims = [451, 96, 9, 32, 451]
     n = 150
-    sig = synth.make_signals(n, seed=4)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(n, seed=4)
     kl_weight, seed = 5e-3, 0x1234ABCD
     res = {}
     for chain in (True, False):
-        old = os.environ.get("V21_TRAIN_CHAIN")
-        os.environ["V21_TRAIN_CHAIN"] = "1" if chain else "0"
-        try:
-            st, tr, Ws, bs = _make_vae(ctx, dims, gl=1, seed=21, max_batch=160, prec=prec)
-        finally:
-            if old is None:
-                os.environ.pop("V21_TRAIN_CHAIN")
-            else:
-                os.environ["V21_TRAIN_CHAIN"] = old
+        st, tr, Ws, bs = _make_vae(ctx, dims, gl=1, seed=21, max_batch=160, prec=prec, env=_chain_env(chain))
         tr.set_vae(kl_weight, sample=True, seed=seed)
         tr.set_adam(lr=1e-3)
         tr.set_state(7)
@@ -1054,18 +841,12 @@ def test_replayed_steps_equal_eager_steps_bit_for_bit(ctx, prec):
     come from a device table instead of the kernel arguments): weights, Adam state and epoch losses must be
     IDENTICAL, over epochs with a partial last batch, a learning-rate change between epochs, and on the
     step_dev path."""
-    native = pkg("_native")
     dims, act = [451, 40, 9, 24, 451], [1, 0, 1, 0]
-    synth = pkg("synth")
-    sig = synth.make_signals(300, seed=9)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(300, seed=9)
     res = {}
     for graph in (True, False):
         Ws, bs = ora.init_mlp(dims, seed=21)
-        st = native.Stack(ctx, dims, act)
-        st.set_weights(ora.flatten_params(Ws, bs))
-        tr = native.Trainer(st, prec, 128)
+        st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, 128)
         tr.use_graph(graph)  # (off by default)
         tr.set_adam(lr=2e-3)
         tr.set_data(0, y, None, w)
@@ -1096,9 +877,7 @@ def test_replayed_steps_follow_data_and_state_changes(ctx):
 
     def run(graph):
         Ws, bs = ora.init_mlp(dims, seed=4)
-        st = native.Stack(ctx, dims, act)
-        st.set_weights(ora.flatten_params(Ws, bs))
-        tr = native.Trainer(st, "f32", 64)
+        st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), "f32", 64)
         tr.use_graph(graph)
         out = []
         for k in range(3):
@@ -1126,18 +905,13 @@ def test_replayed_steps_see_weights_set_between_replays(ctx, prec):
     """the lazy refresh of the packed weight copies is not part of a captured step.  An epoch
     with captured steps, then Stack.set_weights(new), then another epoch: the replayed steps must run on the NEW
     weights -- identical, bit for bit, to the same sequence executed eagerly."""
-    native, synth = pkg("_native"), pkg("synth")
     dims, act = [451, 40, 9, 24, 451], [1, 0, 1, 0]
-    sig = synth.make_signals(256, seed=19)
-    y = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, w = signal_rows(256, seed=19)
     W2, b2 = ora.init_mlp(dims, seed=77)
     res = {}
     for graph in (True, False):
         Ws, bs = ora.init_mlp(dims, seed=21)
-        st = native.Stack(ctx, dims, act)
-        st.set_weights(ora.flatten_params(Ws, bs))
-        tr = native.Trainer(st, prec, 128)
+        st, tr = new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, 128)
         tr.use_graph(graph)
         tr.set_adam(lr=2e-3)
         tr.set_data(0, y, None, w)
@@ -1148,11 +922,7 @@ def test_replayed_steps_see_weights_set_between_replays(ctx, prec):
     np.testing.assert_array_equal(res[True][0], res[False][0])
     np.testing.assert_array_equal(res[True][1], res[False][1])
     # and the second epoch really started from the new weights: its first-batch loss level is the new model's
-    h = y[:128].astype(np.float64)
-    for W_, b_, a_ in zip(W2, b2, act):
-        h = h @ W_.astype(np.float64) + b_.astype(np.float64)
-        h = np.maximum(h, 0) if a_ else h
-    l0 = float(np.mean(ora.per_sample_loss(h, y[:128].astype(np.float64), w[:128].astype(np.float64))))
+    l0 = loss64(W2, b2, act, y[:128], y[:128], w[:128])
     assert abs(res[True][0][1] - l0) / l0 < 0.2, (res[True][0][1], l0)   # (epoch mean of two nearby batches vs batch 1)
 
 
@@ -1162,14 +932,13 @@ def test_latent_emulator_full_width_mse_matches_oracle(ctx, prec):
     """The reference's second phase at its real size (emulator.py:657-663, :756-764): 7 -> [352, 352, 352, 224]
     -> 9 trained with mean_squared_error, batch 256 with a partial last batch, against the float64 oracle.
     f32: per-layer path at the stated f32 tolerance; f16: chain kernel, operand-rounding tolerance."""
-    dims = [7, 352, 352, 352, 224, 9]
-    st, tr, Ws, bs = _make(ctx, dims, seed=12, prec=prec, max_batch=256)
+    dims = STACKS["LE"][0]
+    st, tr, Ws, bs = _make(ctx, dims, seed=12, prec=prec, max_batch=256, lr=1e-3)
     rng = np.random.default_rng(3)
     n, batch = 600, 256   # 256 + 256 + 88
     x = rng.uniform(-1, 1, size=(n, 7)).astype(np.float32)
     z = rng.normal(size=(n, 9)).astype(np.float32)
     w = ora.mse_row_weight(z).astype(np.float32)
-    tr.set_adam(lr=1e-3)
     tr.set_data(0, x, z, w)
     sto = ora.AdamState(st.num_params, dtype=np.float64, lr=1e-3)
     W, b = [a.astype(np.float64) for a in Ws], [a.astype(np.float64) for a in bs]
@@ -1185,7 +954,7 @@ def test_latent_emulator_full_width_mse_matches_oracle(ctx, prec):
     if prec == "f32":
         _close(d_dev, d_ora, 5e-3, "weight movement after 2 epochs (f32)")
     else:
-        cos = float(d_dev @ d_ora / (np.linalg.norm(d_dev) * np.linalg.norm(d_ora)))
+        cos = _cos(d_dev, d_ora)
         assert cos > 0.99 and abs(np.linalg.norm(d_dev) / np.linalg.norm(d_ora) - 1) < tol_w, (cos,)
     assert tr.get_state()[0] == 6
 
@@ -1196,30 +965,19 @@ def test_joint_step_is_phase_two_when_the_encoder_is_frozen(ctx, prec, batch):
     (emulator.py:753-764): the emulator trained on encoder(x) of exactly its batch rows.  Checked against (a) the
     float64 oracle's fit on the oracle's latents, (b) a separate device trainer fed those latents; the
     autoencoder must not move and must report the loss it reports alone."""
-    native, synth = pkg("_native"), pkg("synth")
+    native = pkg("_native")
     n = 300   # (batch 300, f32: one step per epoch, more rows than the one-launch gradient kernel of dw_adam32.h takes)
-    sig = synth.make_signals(n, seed=5)
-    y = ora.preproc(sig, sig)
-    par = rng_par = np.random.default_rng(8).uniform(-1, 1, size=(n, 7)).astype(np.float32)
-    wa = ora.relative_mse_row_weight(y, sig).astype(np.float32)
+    y, wa = signal_rows(n, seed=5)
+    par = np.random.default_rng(8).uniform(-1, 1, size=(n, 7)).astype(np.float32)
     ae_dims, ae_act = [451, 48, 9, 24, 451], [1, 0, 1, 0]
     em_dims, em_act = [7, 40, 9], [1, 0]
     Wa, ba = ora.init_mlp(ae_dims, seed=31)
     We, be = ora.init_mlp(em_dims, seed=32)
-    # oracle latents: encoder = the autoencoder's first two layers
-    h = y.astype(np.float64)
-    for W_, b_, a_ in list(zip(Wa, ba, ae_act))[:2]:
-        h = h @ W_.astype(np.float64) + b_.astype(np.float64)
-        h = np.maximum(h, 0) if a_ else h
-    z = h
+    z = forward64(Wa, ba, ae_act, y, layers=2)    # oracle latents: encoder = the autoencoder's first two layers
     wz = ora.mse_row_weight(z.astype(np.float32)).astype(np.float32)
 
     def trainer(dims, act, Ws, bs, lr):
-        st = native.Stack(ctx, dims, act)
-        st.set_weights(ora.flatten_params(Ws, bs))
-        tr = native.Trainer(st, prec, batch)
-        tr.set_adam(lr=lr)
-        return st, tr
+        return new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, batch, lr=lr)
     sta, tra = trainer(ae_dims, ae_act, Wa, ba, 0.0)        # frozen autoencoder
     ste, tre = trainer(em_dims, em_act, We, be, 2e-3)
     tra.set_data(0, y, None, wa)
@@ -1244,7 +1002,7 @@ def test_joint_step_is_phase_two_when_the_encoder_is_frozen(ctx, prec, batch):
     w0 = ora.flatten_params(We, be).astype(np.float64)
     dj, dx, do = (ste.get_weights() - w0), (stx.get_weights() - w0), (ora.flatten_params(W, b) - w0)
     for d, what in ((dx, "separate trainer"), (do, "oracle")):
-        cos = float(dj @ d / (np.linalg.norm(dj) * np.linalg.norm(d)))
+        cos = _cos(dj, d)
         assert cos > (0.995 if prec == "f16" else 0.9999) and abs(np.linalg.norm(dj) / np.linalg.norm(d) - 1) < (2e-2 if prec == "f16" else 2e-3), (what, cos)
     assert tra.get_state()[0] == tre.get_state()[0] == 2 * -(-n // batch)
     # argument checks
@@ -1265,30 +1023,19 @@ def test_joint_step_full_width_against_the_oracle(ctx, prec):
         families of row blocks share nothing), and the emulator's first-step loss is its float64 loss against the
         encoder's latents of that step.
     f32 (the reference's arithmetic; csrc/train_chain32s.h: train_chain32s_joint_kernel): the same at the f32 tolerances."""
-    native, synth = pkg("_native"), pkg("synth")
+    native = pkg("_native")
     n, batch = 600, 256
-    sig = synth.make_signals(n, seed=5)
-    y = ora.preproc(sig, sig)
+    y, wa = signal_rows(n, seed=5)
     par = np.random.default_rng(8).uniform(-1, 1, size=(n, 7)).astype(np.float32)
-    wa = ora.relative_mse_row_weight(y, sig).astype(np.float32)
-    ae_dims, ae_act = [451, 352, 9, 32, 352, 451], [1, 0, 1, 1, 0]
-    em_dims, em_act = [7, 352, 352, 352, 224, 9], [1, 1, 1, 1, 0]
+    (ae_dims, ae_act), (em_dims, em_act) = STACKS["AE"], STACKS["LE"]
     Wa, ba = ora.init_mlp(ae_dims, seed=31)
     We, be = ora.init_mlp(em_dims, seed=32)
-    h = y.astype(np.float64)
-    for W_, b_, a_ in list(zip(Wa, ba, ae_act))[:2]:
-        h = h @ W_.astype(np.float64) + b_.astype(np.float64)
-        h = np.maximum(h, 0) if a_ else h
-    z = h                                                     # the oracle's latents of the initial encoder
+    z = forward64(Wa, ba, ae_act, y, layers=2)                # the oracle's latents of the initial encoder
     wz = ora.mse_row_weight(z.astype(np.float32)).astype(np.float32)
     tol_l, tol_n = {"f16": (5e-3, 3e-2), "bf16": (4e-2, 1e-1), "f32": (5e-5, 2e-3)}[prec]
 
     def trainer(dims, act, Ws, bs, lr):
-        st = native.Stack(ctx, dims, act)
-        st.set_weights(ora.flatten_params(Ws, bs))
-        tr = native.Trainer(st, prec, batch)
-        tr.set_adam(lr=lr)
-        return st, tr
+        return new_trainer(ctx, dims, act, ora.flatten_params(Ws, bs), prec, batch, lr=lr)
     # ---- (a) frozen encoder
     sta, tra = trainer(ae_dims, ae_act, Wa, ba, 0.0)
     ste, tre = trainer(em_dims, em_act, We, be, 1e-3)
@@ -1306,7 +1053,7 @@ def test_joint_step_full_width_against_the_oracle(ctx, prec):
     np.testing.assert_array_equal(sta.get_weights(), ora.flatten_params(Wa, ba))   # lr = 0: untouched
     w0 = ora.flatten_params(We, be).astype(np.float64)
     dj, do = ste.get_weights() - w0, ora.flatten_params(W, b) - w0
-    cos = float(dj @ do / (np.linalg.norm(dj) * np.linalg.norm(do)))
+    cos = _cos(dj, do)
     assert cos > {"f16": 0.99, "bf16": 0.9, "f32": 0.9999}[prec] and abs(np.linalg.norm(dj) / np.linalg.norm(do) - 1) < tol_n, cos
     assert tra.get_state()[0] == tre.get_state()[0] == 6
     # the one-launch validation of both models (v21_joint_eval): the autoencoder's is its own forward-only pass, bit for
@@ -1339,21 +1086,18 @@ def test_joint_step_with_a_variational_autoencoder(ctx, prec):
     encoder of that step (what encoder.predict returns).  With the autoencoder frozen the emulator's epoch equals a
     separate trainer fed the float64 z_mean; with kl_weight = 0 and no sampling the autoencoder's half equals the
     deterministic autoencoder's."""
-    native, synth = pkg("_native"), pkg("synth")
+    native = pkg("_native")
     n, batch = 200, 128
-    sig = synth.make_signals(n, seed=6)
-    y = ora.preproc(sig, sig)
+    y, wa = signal_rows(n, seed=6)
     par = np.random.default_rng(9).uniform(-1, 1, size=(n, 7)).astype(np.float32)
-    wa = ora.relative_mse_row_weight(y, sig).astype(np.float32)
     ae_dims, ae_act = [451, 64, 9, 32, 451], [1, native.ACT_GAUSS, 1, 0]
     em_dims, em_act = [7, 48, 9], [1, 0]
-    sta = native.Stack(ctx, ae_dims, ae_act)
+    sta = native.Stack(ctx, ae_dims, ae_act)   # (the arena's size is the stack's to tell)
     flat = (np.random.default_rng(3).normal(size=sta.num_params) * 0.05).astype(np.float32)
     sta.set_weights(flat)
     tra = native.Trainer(sta, prec, batch); tra.set_adam(lr=0.0); tra.set_vae(1e-3, sample=True, seed=5)
     We, be = ora.init_mlp(em_dims, seed=12)
-    ste = native.Stack(ctx, em_dims, em_act); ste.set_weights(ora.flatten_params(We, be))
-    tre = native.Trainer(ste, prec, batch); tre.set_adam(lr=2e-3)
+    ste, tre = new_trainer(ctx, em_dims, em_act, ora.flatten_params(We, be), prec, batch, lr=2e-3)
     # float64 z_mean of the (frozen) encoder: Dense 451 -> 64 (ReLU), Dense 64 -> 18, first 9 columns
     o = 0
     W0 = flat[o:o + 451 * 64].reshape(451, 64).astype(np.float64); o += 451 * 64
@@ -1365,8 +1109,7 @@ def test_joint_step_with_a_variational_autoencoder(ctx, prec):
     tra.set_data(0, y, None, wa)
     tre.set_data(0, par, np.zeros((n, 9), np.float32), wz)
     joint = native.Joint(tra, tre, latent_layer=1)
-    stx = native.Stack(ctx, em_dims, em_act); stx.set_weights(ora.flatten_params(We, be))
-    trx = native.Trainer(stx, prec, batch); trx.set_adam(lr=2e-3)
+    stx, trx = new_trainer(ctx, em_dims, em_act, ora.flatten_params(We, be), prec, batch, lr=2e-3)
     trx.set_data(0, par, zm.astype(np.float32), wz)
     for ep in range(2):
         perm = ora.epoch_permutation(n, 4, ep)
@@ -1375,7 +1118,7 @@ def test_joint_step_with_a_variational_autoencoder(ctx, prec):
         assert np.isfinite(la) and abs(le - lx) / lx < (3e-3 if prec == "f16" else 2e-5), (ep, le, lx)
     np.testing.assert_array_equal(sta.get_weights(), flat)
     d1, d2 = ste.get_weights() - ora.flatten_params(We, be), stx.get_weights() - ora.flatten_params(We, be)
-    assert float(d1 @ d2 / (np.linalg.norm(d1) * np.linalg.norm(d2))) > (0.995 if prec == "f16" else 0.99999)
+    assert _cos(d1, d2) > (0.995 if prec == "f16" else 0.99999)
 
 
 @pytest.mark.parametrize("prec", ["f16", "f32"])
@@ -1384,26 +1127,23 @@ def test_joint_step_trains_a_sampling_variational_autoencoder_like_the_autoencod
     autoencoder's half must be, bit for bit, the autoencoder trained alone on the same permutations -- which holds only
     if every optimizer step of the joint epoch keys its noise on its own step number (ChainStep::step_off; ADVICE r3:
     the f32 branch of v21_joint_run_epoch drew the same eps in every step of an epoch)."""
-    native, synth = pkg("_native"), pkg("synth")
+    native = pkg("_native")
     n, batch = 300, 128                                   # 3 steps per epoch, the last one partial
-    sig = synth.make_signals(n, seed=16)
-    y = ora.preproc(sig, sig)
+    y, wa = signal_rows(n, seed=16)
     par = np.random.default_rng(19).uniform(-1, 1, size=(n, 7)).astype(np.float32)
-    wa = ora.relative_mse_row_weight(y, sig).astype(np.float32)
     ae_dims, ae_act = [451, 64, 9, 32, 451], [1, native.ACT_GAUSS, 1, 0]
     em_dims, em_act = [7, 48, 9], [1, 0]
     flat = (np.random.default_rng(13).normal(size=native.Stack(ctx, ae_dims, ae_act).num_params) * 0.05).astype(np.float32)
     We, be = ora.init_mlp(em_dims, seed=12)
 
     def ae_trainer():
-        st = native.Stack(ctx, ae_dims, ae_act); st.set_weights(flat)
-        tr = native.Trainer(st, prec, batch); tr.set_adam(lr=1e-3); tr.set_vae(1e-2, sample=True, seed=77)
+        st, tr = new_trainer(ctx, ae_dims, ae_act, flat, prec, batch, lr=1e-3)
+        tr.set_vae(1e-2, sample=True, seed=77)
         tr.set_data(0, y, None, wa)
         return st, tr
     sta, tra = ae_trainer()
     sts, trs = ae_trainer()                               # the autoencoder alone
-    ste = native.Stack(ctx, em_dims, em_act); ste.set_weights(ora.flatten_params(We, be))
-    tre = native.Trainer(ste, prec, batch); tre.set_adam(lr=2e-3)
+    ste, tre = new_trainer(ctx, em_dims, em_act, ora.flatten_params(We, be), prec, batch, lr=2e-3)
     tre.set_data(0, par, np.zeros((n, 9), np.float32), np.full(n, 1 / 9, np.float32))
     joint = native.Joint(tra, tre, latent_layer=1)
     for ep in range(2):
@@ -1491,7 +1231,6 @@ def test_created_and_destroyed_handles_give_their_device_memory_back(ctx):
     step + destroy: the device's free memory may fall by what the allocator keeps, but by less than ONE round holds while
     alive -- a single trainer buffer forgotten per round would show as 200 of them."""
     import gc
-    import torch
     native = pkg("_native")
     n = 256
     x = np.random.default_rng(0).uniform(-1, 1, size=(n, 451)).astype(np.float32)
@@ -1535,20 +1274,16 @@ def test_fused_training_gathers_the_resident_16_bit_copy_with_identical_results(
     the step's largest read).  The same step on a caller's own device copy of the same rows gathers fp32 and rounds in the
     kernel: the operands are the same 16-bit values, so loss, gradient and weights must be identical bit for bit -- whole set,
     and a slice of the resident set stepped through its device pointers (v21_trainer_get_data_dev)."""
-    native, synth = pkg("_native"), pkg("synth")
     monkeypatch.setenv("V21_FUSED_TRAIN_ROWS", "1")
     monkeypatch.setenv("V21_FUSED_TRAIN16", "1" if rows_per_wave == 16 else "0")
     name, dims, act, ae = FUSED_TRAIN_STACKS[0]
     n = 500
-    sig = synth.make_signals(n, seed=12)
-    x = ora.preproc(sig, sig)
-    w = ora.relative_mse_row_weight(x, sig).astype(np.float32)
+    x, w = signal_rows(n, seed=12)
     Ws, bs = ora.init_mlp(dims, seed=5)
     flat = ora.flatten_params(Ws, bs)
     res = []
     for resident in (True, False):
-        st = native.Stack(ctx, dims, act); st.set_weights(flat)
-        tr = native.Trainer(st, "f16", n); tr.set_adam(lr=1e-3)
+        st, tr = new_trainer(ctx, dims, act, flat, "f16", n, lr=1e-3)
         tr.set_data(0, x, None, w)
         if resident:
             d_x, d_y, d_rw, rows = tr.data_dev(0)
@@ -1583,7 +1318,6 @@ def test_layer0_gradient_operand_gathered_from_resident_rows_is_bit_identical(ct
     the step's row table and the compute waves read them through the hardware transpose (train_chain.h: DwXRows).  The operand
     values and the order of every sum are those of the flushed form (V21_DW_XROWS=0): loss, FULL gradient and weights after two
     more epochs must be identical bit for bit -- and match the float64 oracle."""
-    from helpers import STACKS, stack_data, twin_steps, assert_step_matches_oracle
     if dims is None:
         dims, act = STACKS[name]
     n = rows   # the first epoch is ONE step of all rows (through the row table when there is one); the later epochs take steps of

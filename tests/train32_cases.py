@@ -16,6 +16,7 @@ from collections import namedtuple
 
 import numpy as np
 
+import train_support as ts
 from helpers import TOL, init_weights, layer_errors, oracle_step
 from oracle import ref_numpy as ora
 
@@ -173,11 +174,7 @@ def oracle(case, flat, x, tgt, w):
 
 def forward64(case, flat, x):
     Ws, bs = ora.unflatten_params(np.asarray(flat, np.float64), case.dims)
-    h = np.asarray(x, np.float64)
-    for W_, b_, a_ in zip(Ws, bs, case.act):
-        h = h @ W_ + b_
-        h = np.maximum(h, 0) if a_ else h
-    return h
+    return ts.forward64(Ws, bs, case.act, x)
 
 
 def val_loss64(case, flat, d):
@@ -212,13 +209,8 @@ def kink_candidates(case, flat, x, rel_thr=1e-5):
     """float64 pre-activations of ReLU layers with |z| < rel_thr x the layer's largest |z| (the candidates of
     helpers.kink_adjusted_oracle)"""
     Ws, bs = ora.unflatten_params(np.asarray(flat, np.float64), case.dims)
-    h, n = np.asarray(x, np.float64), 0
-    for W_, b_, a_ in zip(Ws, bs, case.act):
-        z = h @ W_ + b_
-        if a_:
-            n += int((np.abs(z) < rel_thr * np.abs(z).max()).sum())
-        h = np.maximum(z, 0) if a_ else z
-    return n
+    return sum(int((np.abs(z) < rel_thr * np.abs(z).max()).sum())
+               for a_, (z, _) in zip(case.act, ts.layers64(Ws, bs, case.act, x)) if a_)
 
 
 # ---- the strict check.  Loss 2e-5 and cosine 0.999999: helpers.TOL["f32"]; every layer's block 2e-6: the f32 bound of
