@@ -19,6 +19,7 @@ PRECISIONS = {"f32": PREC_F32, "fp32": PREC_F32, "float32": PREC_F32,
               "f16": PREC_F16, "fp16": PREC_F16, "float16": PREC_F16,
               "bf16": PREC_BF16, "bfloat16": PREC_BF16}
 ACT_LINEAR, ACT_RELU, ACT_GAUSS = 0, 1, 2
+ACT_TANH, ACT_SIGMOID, ACT_ELU, ACT_SOFTPLUS = 3, 4, 5, 6  # include/v21.h: Keras' definitions, hidden layers
 FWD_IN_TRANSFORM, FWD_OUT_TRANSFORM, FWD_FORCE_GENERIC, FWD_NO_SMALL, FWD_FORCE_CHAIN, FWD_FORCE_JIT = 1, 2, 4, 8, 16, 32
 COMM_ID_BYTES = 128
 

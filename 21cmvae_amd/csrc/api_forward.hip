@@ -27,7 +27,7 @@ int route_query_args(bool ptrs, int n_layers, const int* dims, const int* act, i
 extern "C" int v21_route_forward(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int rt_ready, int* route) {
   CHK(route_query_args(route, n_layers, dims, act, precision));
   for (int l = 0; l < n_layers; ++l)
-    if (act[l] < 0 || act[l] > V21_ACT_GAUSS) return fail(V21_ERR_ARG, "act[%d] = %d unknown", l, act[l]);
+    if (!act_known(act[l])) return fail(V21_ERR_ARG, "act[%d] = %d unknown", l, act[l]);
   const int out = dims[n_layers];
   FwdQuery q{n_layers, dims, act, compiled_index(g_infer, n_layers, dims, act) >= 0, rt_ready ? 2 : 0, precision, (long long)n, flags & 0xFF, (long long)out};
   if (q.jit == 2) {
@@ -64,8 +64,7 @@ extern "C" int v21_mlp_create(v21_ctx* ctx, int n_layers, const int* dims, const
   for (int i = 0; i <= n_layers; ++i)
     if (dims[i] < 1 || dims[i] > 65536) return fail(V21_ERR_ARG, "dims[%d] = %d out of range", i, dims[i]);
   for (int i = 0; i < n_layers; ++i)
-    if (act[i] != V21_ACT_LINEAR && act[i] != V21_ACT_RELU && act[i] != V21_ACT_GAUSS)
-      return fail(V21_ERR_ARG, "act[%d] = %d unknown", i, act[i]);
+    if (!act_known(act[i])) return fail(V21_ERR_ARG, "act[%d] = %d unknown", i, act[i]);
   int n_gauss = 0;
   for (int i = 0; i < n_layers; ++i) n_gauss += act[i] == V21_ACT_GAUSS;
   if (n_gauss > 1) return fail(V21_ERR_UNSUPPORTED, "at most one V21_ACT_GAUSS layer per stack");
@@ -245,6 +244,7 @@ static int dense_forward(v21_mlp* m, int l, const float* in, long long ldin, flo
   g.C = out; g.ldc = ldout;
   g.M = rows; g.N = m->dims[l + 1]; g.K = m->dims[l];
   g.bias = m->d_w + m->b_off[l];
+  if (act_is_smooth(m->act[l])) { g.act = m->act[l]; return launch_gemm_prec<EP_BIAS_ACT>(prec, g, st); }
   return m->act[l] == V21_ACT_RELU ? launch_gemm_prec<EP_BIAS_RELU>(prec, g, st) : launch_gemm_prec<EP_BIAS>(prec, g, st);
 }
 
@@ -582,7 +582,8 @@ static int forward_small(v21_mlp* m, const float* d_x, long long ldx, long long 
     g.M = rows; g.N = m->dims[l + 1]; g.K = m->dims[l];  // V21_ACT_GAUSS: the z_mean rows of W^T only
     g.bias = m->d_w + m->b_off[l];
     g.ep = m->act[l] == V21_ACT_RELU ? NT_FWD_RELU : NT_FWD;
-    if (last && (flags & V21_FWD_OUT_TRANSFORM) && m->has_tout && m->act[l] != V21_ACT_RELU) {
+    if (act_is_smooth(m->act[l])) { g.ep = NT_FWD_ACT; g.act = m->act[l]; }
+    if (last && (flags & V21_FWD_OUT_TRANSFORM) && m->has_tout && g.ep == NT_FWD) {
       g.ep = NT_FWD_UNPRE; g.aff_mean = m->d_mean; g.aff_std = m->out_std;  // unpreproc in the epilogue
       unpre_done = true;
     }

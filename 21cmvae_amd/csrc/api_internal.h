@@ -45,6 +45,12 @@ constexpr int kStampSlots = 64;
 #include "routes.h"
 #include "rowmath.h"
 
+// act.h's codes are include/v21.h's
+static_assert(v21::kActLinear == V21_ACT_LINEAR && v21::kActRelu == V21_ACT_RELU && v21::kActGauss == V21_ACT_GAUSS &&
+              v21::kActTanh == V21_ACT_TANH && v21::kActSigmoid == V21_ACT_SIGMOID && v21::kActElu == V21_ACT_ELU &&
+              v21::kActSoftplus == V21_ACT_SOFTPLUS, "csrc/act.h and include/v21.h agree on the activation codes");
+static inline bool act_known(int code) { return code >= V21_ACT_LINEAR && code <= V21_ACT_SOFTPLUS; }
+
 namespace v21 { struct FitRow; }  // fit_kernels.h (api_fit.hip); both row states are built on rowmath.h
 namespace v21 { struct SampleRow; struct TemperRow; }  // sample_kernels.h (api_sample.hip)
 namespace v21 { struct EnsRow; }  // ensemble_kernels.h (api_ensemble.hip)
@@ -507,8 +513,12 @@ static int launch_nt(int prec, GROUP& grp, hipStream_t st) {
   }
   grp.first[grp.count] = blocks;
   if (blocks <= 0) return V21_OK;
+  bool smooth = false;  // a problem with an epilogue of act.h: the kernel's ACT instantiation (gemm_nt.h)
+  for (int i = 0; i < grp.count; ++i) smooth = smooth || grp.p[i].ep == NT_FWD_ACT || grp.p[i].ep == NT_DX_ACT;
 #define V21_NT(PT) \
-  do { if (T == 2) hipLaunchKernelGGL((gemm_nt_kernel<PT, 2, GROUP>), dim3(blocks), dim3(256), 0, st, grp); \
+  do { if (smooth && T == 2) hipLaunchKernelGGL((gemm_nt_kernel<PT, 2, GROUP, true>), dim3(blocks), dim3(256), 0, st, grp); \
+       else if (smooth) hipLaunchKernelGGL((gemm_nt_kernel<PT, 1, GROUP, true>), dim3(blocks), dim3(256), 0, st, grp); \
+       else if (T == 2) hipLaunchKernelGGL((gemm_nt_kernel<PT, 2, GROUP>), dim3(blocks), dim3(256), 0, st, grp); \
        else hipLaunchKernelGGL((gemm_nt_kernel<PT, 1, GROUP>), dim3(blocks), dim3(256), 0, st, grp); } while (0)
   switch (prec) {
     case V21_PREC_F32: V21_NT(PrecF32); break;

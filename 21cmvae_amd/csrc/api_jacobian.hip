@@ -123,7 +123,8 @@ static int jac_run(v21_mlp* m, int route, long long r0, long long n, float* y, l
   g.tc = tc; g.maxw = maxw;
   static bool attr_done[64] = {};
   if (!attr_done[m->ctx->device & 63]) {
-    HIPCHK(hipFuncSetAttribute((const void*)jac_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    HIPCHK(hipFuncSetAttribute((const void*)jac_generic_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    HIPCHK(hipFuncSetAttribute((const void*)jac_generic_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     attr_done[m->ctx->device & 63] = true;
   }
   g.w = m->d_w; g.ldy = ldy;
@@ -137,7 +138,9 @@ static int jac_run(v21_mlp* m, int route, long long r0, long long n, float* y, l
     g.jac = jac ? jac + q * din * dout : nullptr;
     g.lnl = lnl ? lnl + q : nullptr;
     g.grad = grad ? grad + q * din : nullptr;
-    hipLaunchKernelGGL(jac_generic_kernel, dim3((unsigned)rows, (unsigned)((din + tc - 1) / tc)), dim3(256), lds, st, g);
+    const dim3 grid((unsigned)rows, (unsigned)((din + tc - 1) / tc));
+    if (route_smooth(m->L, m->act.data())) hipLaunchKernelGGL(jac_generic_kernel<true>, grid, dim3(256), lds, st, g);
+    else hipLaunchKernelGGL(jac_generic_kernel<false>, grid, dim3(256), lds, st, g);
     HIPCHK(hipGetLastError());
   }
   return V21_OK;

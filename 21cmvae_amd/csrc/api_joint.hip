@@ -27,6 +27,11 @@ extern "C" int v21_joint_create(v21_trainer* ae, v21_trainer* em, int latent_lay
   if (ae == em || ae->ctx != em->ctx || ae->prec != em->prec || ae->max_batch != em->max_batch)
     return fail(V21_ERR_ARG, "the two trainers must be distinct and share context, precision and max_batch");
   const bool f32 = ae->kind.chain32s && em->kind.chain32s && em->kind.gl < 0;
+  for (const v21_trainer* t : {ae, em})  // (routes.h: route_smooth -- such trainers are per-layer trainers)
+    for (int l = 0; l < t->mlp->L; ++l)
+      if (act_is_smooth(t->mlp->act[l]))
+        return fail(V21_ERR_UNSUPPORTED, "the joint step runs on the chain kernels, which have no %s activation (layer %d of the %s): train the "
+                    "two models with their own trainers", act_name(t->mlp->act[l]), l, t == ae ? "autoencoder" : "emulator");
   if (!f32 && (!ae->kind.chain || !em->kind.chain || em->kind.gl >= 0))
     return fail(V21_ERR_UNSUPPORTED, "the joint step runs on the chain kernels: f16 / bf16 (widths <= %d, no variational layer in the emulator), or "
                 "f32 with max_batch <= %d (variational head: latent <= %d)", kChainMaxDim, kC32sMaxBatch, kChainMaxLatent);

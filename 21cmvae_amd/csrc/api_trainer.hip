@@ -115,6 +115,9 @@ extern "C" int v21_trainer_create(v21_mlp* m, int precision, int max_batch, v21_
   const RouteEnv env = RouteEnv::read();
   t->kind = decide_trainer_kind(L, m->dims.data(), m->act.data(), precision, max_batch, env);
   if (t->kind.gl == L - 1) return fail(V21_ERR_UNSUPPORTED, "a V21_ACT_GAUSS layer cannot be the last layer of a trained stack");
+  if (act_is_smooth(m->act[L - 1]))
+    return fail(V21_ERR_UNSUPPORTED, "layer %d, the output layer of a trained stack, has activation %s: it must be linear (the reference's output "
+                "Dense has no activation, emulator.py:44)", L - 1, act_name(m->act[L - 1]));
   if (m->act[L - 1] != V21_ACT_LINEAR) {  // (the loss gradient is taken w.r.t. the Dense output: no output non-linearity is differentiated)
     return fail(V21_ERR_UNSUPPORTED, "the output layer of a trained stack must be linear (the reference's output Dense has no activation, emulator.py:44)");
   }
@@ -433,6 +436,7 @@ NtArgs nt_forward(const v21_trainer* t, int l, const float* A, int rows, bool wa
   g.M = rows; g.N = m->nw(l); g.K = m->dims[l];
   g.bias = m->d_w + m->b_off[l];
   g.ep = m->act[l] == V21_ACT_RELU ? NT_FWD_RELU : NT_FWD;
+  if (act_is_smooth(m->act[l])) { g.ep = NT_FWD_ACT; g.act = m->act[l]; }
   g.nz = 1;
   return g;
 }
@@ -458,6 +462,7 @@ NtArgs nt_dx(const v21_trainer* t, int l, const float* A, int rows, float gs) {
   d.M = rows; d.N = K; d.K = N;
   d.mask = t->d_h[l]; d.ldmask = p16(K);
   d.ep = m->act[l - 1] == V21_ACT_RELU ? NT_DX_MASK : NT_DX;
+  if (act_is_smooth(m->act[l - 1])) { d.ep = NT_DX_ACT; d.act = m->act[l - 1]; }  // times dh/dz from the stored h[l] (act.h)
   d.nz = 1;
   d.a_scale = gs; d.out_scale = 1.0f / gs;
   return d;

@@ -31,6 +31,7 @@
 
 #include "../../include/v21_types.h"
 #include "par_transform.h"
+#include "act.h"
 
 namespace v21 {
 
@@ -184,7 +185,7 @@ template <class P, class = void> struct spread_of { static constexpr bool value 
 template <class P> struct spread_of<P, std::void_t<decltype(P::SPREAD_DMA)>> { static constexpr bool value = P::SPREAD_DMA; };
 
 // ---- compile-time geometry of (architecture, precision) ---------------------------
-// Arch::L layers, Arch::dims[L+1], Arch::act[L] (1 = ReLU).  The last layer is the
+// Arch::L layers, Arch::dims[L+1], Arch::act[L] (1 = ReLU; 3 .. 6: act.h, hidden layers of run-time instantiations).  The last layer is the
 // "output orientation" layer and must be linear.
 template <class Arch, class P> struct Geo {
   using Prec = P;
@@ -554,7 +555,20 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_fwd(const FusedAr
       if constexpr (item < G::ks_of(l + 1)) {
         auto& out = (l & 1) ? bufA : bufB;
         const float x0 = acc[GT & 1][ct][2 * pr], x1 = acc[GT & 1][ct][2 * pr + 1];
-        if constexpr (EPI == 8) {
+        if constexpr (G::act(l) >= 3) {
+          // an activation of act.h (run-time instantiations only: archs.h has none), in f32 on the accumulator pair BEFORE
+          // packing; its own branch: the ReLU / linear code below is what it was.  Padding: the columns of a partial tile
+          // hold act(0 + 0) afterwards -- 0.5 for sigmoid, ln 2 for softplus, not 0 as after ReLU or linear -- and that is
+          // harmless: they are features >= dim(l + 1) of the next layer's operand, which meet the ZERO weights
+          // pack_stream_kernel writes for f >= K (a finite value times 0), and items past ks_of(l + 1) are never formed.
+          const float y0 = act_apply<G::act(l)>(x0), y1 = act_apply<G::act(l)>(x1);
+          if constexpr (EPI == 8) {
+            out[ct][item][e0 / 2] = P::pack2(y0, y1);
+          } else {
+            out[ct][item][e0] = __builtin_bit_cast(unsigned, y0);
+            out[ct][item][e0 + 1] = __builtin_bit_cast(unsigned, y1);
+          }
+        } else if constexpr (EPI == 8) {
           // pack first, then ReLU on the packed pair as a signed 16-bit max with 0
           // (negative f16/bf16 are negative integers): 2 VALU ops per 2 values
           unsigned w = P::pack2(x0, x1);

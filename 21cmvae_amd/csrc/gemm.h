@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "act.h"
 #include "fused_fwd.h"
 
 namespace v21 {
@@ -27,9 +28,11 @@ struct GemmArgs {
   float* C; long long ldc;                // C(m,n) = C[m*ldc + n]
   int M, N, K;
   const float* bias;                      // N floats
+  int act;                                // EP_BIAS_ACT: the layer's activation code (act.h: 3 .. 6)
 };
 
-enum { EP_BIAS = 1, EP_BIAS_RELU = 2 };
+// EP_BIAS_ACT: bias + activation by code (act.h) -- its own instantiations: the linear and ReLU kernels keep theirs
+enum { EP_BIAS = 1, EP_BIAS_RELU = 2, EP_BIAS_ACT = 3 };
 
 constexpr int kBM = 64, kBN = 64, kBK = 64;
 
@@ -154,7 +157,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(const GemmArgs g) {
   const int n = n0 + wn * 32 + li;
   if (n < g.N) {
     float bias = 0.f;
-    if constexpr (EP == EP_BIAS || EP == EP_BIAS_RELU) bias = g.bias[n];
+    if constexpr (EP == EP_BIAS || EP == EP_BIAS_RELU || EP == EP_BIAS_ACT) bias = g.bias[n];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int m = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh;
@@ -162,6 +165,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(const GemmArgs g) {
         float v = acc[i];
         if constexpr (EP == EP_BIAS) v = v + bias;
         if constexpr (EP == EP_BIAS_RELU) v = fmaxf(v + bias, 0.f);
+        if constexpr (EP == EP_BIAS_ACT) v = act_apply_rt(g.act, v + bias);
         C[(long long)m * g.ldc + n] = v;
       }
     }

@@ -16,11 +16,12 @@
 //     finishes a quarter of the rows;
 //   * contraction ranges longer than kMaxKPerWg (the batch dimension of the weight
 //     gradient) are split over blockIdx.z into slabs that are summed in a fixed order.
-// Epilogues: forward (bias, ReLU; writes H and H^T), backward (ReLU mask; writes dZ and
-// dZ^T), weight gradient (plain store into the [kernel|bias] slab).
+// Epilogues: forward (bias, ReLU or an activation of act.h; writes H and H^T), backward (ReLU mask
+// or act.h's derivative from the stored output; writes dZ and dZ^T), weight gradient (plain store into the [kernel|bias] slab).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "act.h"
 #include "fused_fwd.h"
 #include "train_kernels.h"  // StepCtx
 
@@ -44,6 +45,7 @@ struct NtArgs {
   // scale dZ by a power of two on the way into the MFMA and undo it on the way out (exact).
   float a_scale, b_scale, out_scale;
   const float* aff_mean; float aff_std;  // NT_FWD_UNPRE
+  int act;                         // NT_FWD_ACT / NT_DX_ACT: the activation code (act.h: 3 .. 6) of the layer that made C / mask
 };
 // several independent contractions per launch: the backward of one layer (dW and dX both
 // consume dZ of that layer), and the same layer of every model of a sweep
@@ -59,7 +61,15 @@ struct NtGroupT {  // CAP = 2 for a single model (small kernel-argument block), 
 using NtGroup = NtGroupT<2>;
 using NtGroupBig = NtGroupT<kNtMaxGroup>;
 // NT_FWD_UNPRE: last layer of predict with preprocess.unpreproc fused in: (z + bias) * aff_std + aff_mean[n]
-enum { NT_FWD = 0, NT_FWD_RELU = 1, NT_DX = 2, NT_DX_MASK = 3, NT_DW = 4, NT_FWD_UNPRE = 5 };
+// NT_FWD_ACT: bias + activation by code (act.h); NT_DX_ACT: dX times act_deriv_out of the stored f32 activation (`mask`,
+// the array NT_DX_MASK reads).  Both are further values of the run-time `ep`, served by the kernel's ACT instantiation
+// only (gemm_nt_body): launches without them take the instantiation they always took.
+// Padding: act(0) != 0 for sigmoid and softplus, so an activation array is no longer "zero wherever nothing was written"
+// by construction -- and nothing relies on that: C is written for m < M, n < N only (the p16 padding columns and the rows
+// past the batch keep the zeros they were allocated with), the transposed copy CT gets explicit zeros for the rows
+// mrow .. mrow + 3 past M, and every contraction zeroes its operand elements past the end of its range in registers
+// (below: "padding may hold anything") -- the weight gradient's contraction over the batch included.
+enum { NT_FWD = 0, NT_FWD_RELU = 1, NT_DX = 2, NT_DX_MASK = 3, NT_DW = 4, NT_FWD_UNPRE = 5, NT_FWD_ACT = 6, NT_DX_ACT = 7 };
 
 constexpr int kNtMaxKPerWg = 512;
 
@@ -94,7 +104,11 @@ template <> struct NtTraits<PrecBF16> { static constexpr int KSTEP = 16, MAXSTEP
 #else
 #define NTFINE(i)
 #endif
-template <class P, int T, class GROUP, bool ADAM = false>
+// ACT: the instantiation that also knows NT_FWD_ACT / NT_DX_ACT.  Launches without such a problem keep the instantiation
+// they had (ACT = false: the same code as before act.h existed) -- with the two epilogues as further run-time branches of
+// the one kernel, a ReLU per-layer step of 4,096 rows measured 1.8 % (f32) and 3.5 % (f16) slower than the parent's, outside
+// the parent's own spread of 0.5 %.
+template <class P, int T, class GROUP, bool ADAM = false, bool ACT = false>
 __device__ __forceinline__ void gemm_nt_body(const GROUP& grp, const NtAdamInfo* ad) {
   using TR = NtTraits<P>;
   NTFINE(0);
@@ -328,7 +342,7 @@ __device__ __forceinline__ void gemm_nt_body(const GROUP& grp, const NtAdamInfo*
       const int mrow = m0 + 32 * ti + 8 * wave + 4 * lh;  // rows mrow .. mrow+3
       if (n >= gN) continue;
       float bias = 0.f;
-      if (EP == NT_FWD || EP == NT_FWD_RELU || EP == NT_FWD_UNPRE) bias = g.bias[n];
+      if (EP == NT_FWD || EP == NT_FWD_RELU || EP == NT_FWD_UNPRE || (ACT && EP == NT_FWD_ACT)) bias = g.bias[n];
       const float amean = EP == NT_FWD_UNPRE ? g.aff_mean[n] : 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -338,6 +352,10 @@ __device__ __forceinline__ void gemm_nt_body(const GROUP& grp, const NtAdamInfo*
         if (EP == NT_FWD_RELU) v = fmaxf(v + bias, 0.f);
         if (EP == NT_FWD_UNPRE) v = (v + bias) * g.aff_std + amean;  // rounded as numpy does: (p * std) + mean
         if (EP == NT_DX_MASK) v = (m < gM && g.mask[(long long)m * g.ldmask + n] > 0.f) ? v : 0.f;
+        if constexpr (ACT) {
+          if (EP == NT_FWD_ACT) v = act_apply_rt(g.act, v + bias);
+          if (EP == NT_DX_ACT) v = m < gM ? v * act_deriv_out_rt(g.act, g.mask[(long long)m * g.ldmask + n]) : 0.f;
+        }
         r[e] = v;
         if (m < gM) C[(long long)m * gldc + n] = v;
       }
@@ -356,9 +374,9 @@ __device__ __forceinline__ void gemm_nt_body(const GROUP& grp, const NtAdamInfo*
   NTFINE(5);
 }
 
-template <class P, int T, class GROUP>
+template <class P, int T, class GROUP, bool ACT = false>
 __global__ void __launch_bounds__(256) gemm_nt_kernel(const GROUP grp) {
-  gemm_nt_body<P, T, GROUP, false>(grp, nullptr);
+  gemm_nt_body<P, T, GROUP, false, ACT>(grp, nullptr);
 }
 // every weight gradient of an f32 chain step + Adam + the packed copies in one launch (NtAdamInfo above)
 template <int T>

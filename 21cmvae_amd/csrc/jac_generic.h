@@ -2,13 +2,14 @@
 //   jac_prep_kernel     the input transform of every route (par_transform.h, the forward's own functions: the primal
 //                       sees the bits the forward's prologue computes) and its chain-rule factor per (row, column);
 //   jac_generic_kernel  primal + tangents of ANY stack (any hidden_dims and in_dim, > 512 wide, V21_ACT_GAUSS heads
-//                       evaluated as z = z_mean like the deterministic forward) in f32 arithmetic.  One workgroup per
+//                       evaluated as z = z_mean like the deterministic forward, the activations of act.h) in f32 arithmetic.  One workgroup per
 //                       (row, group of up to 7 tangents); the G columns of a layer's activation live in LDS, every
 //                       output unit is one thread's k-ordered fmaf chain per column.  Correct, not fast: every
 //                       workgroup streams the whole weight set through L2.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "act.h"
 #include "par_transform.h"
 
 namespace v21 {
@@ -63,7 +64,9 @@ struct JacGenArgs {
   const float* mean;            // nullable: no output transform
 };
 
-// grid (n_rows, ceil(in_dim / tc)); block 256; dynamic LDS 2 * (tc + 1) * maxw floats
+// grid (n_rows, ceil(in_dim / tc)); block 256; dynamic LDS 2 * (tc + 1) * maxw floats.  ACT: the instantiation for stacks
+// with an activation of act.h; every other stack keeps the code it had (ACT = false)
+template <bool ACT>
 __global__ void __launch_bounds__(256) jac_generic_kernel(const JacGenArgs a) {
   extern __shared__ float jsh[];
   const long long n = blockIdx.x;
@@ -100,6 +103,14 @@ __global__ void __launch_bounds__(256) jac_generic_kernel(const JacGenArgs a) {
       if (a.act[l] == V21_ACT_RELU && !(s[0] > 0.f)) {
 #pragma unroll
         for (int c = 0; c < kJacGenCols; ++c) s[c] = 0.f;
+      }
+      // an activation of act.h: the primal through act_apply, the tangents times dh/dz taken from z itself (it is in a
+      // register here; 1 - h^2 of a saturated unit has no digits left, 4 e / (1 + e)^2 has)
+      if (ACT && act_is_smooth(a.act[l])) {
+        const float d = act_deriv_in_rt(a.act[l], s[0]);
+        s[0] = act_apply_rt(a.act[l], s[0]);
+#pragma unroll
+        for (int c = 1; c < kJacGenCols; ++c) s[c] *= d;
       }
       if (!last) {
 #pragma unroll

@@ -27,7 +27,7 @@
 namespace v21 {
 namespace {
 
-// include/v21.h + par_transform.h + fused_fwd.h, own #include lines and `#pragma once` removed (Makefile: fused_src.inc)
+// include/v21_types.h + par_transform.h + act.h + fused_fwd.h, own #include lines and `#pragma once` removed (Makefile: fused_src.inc)
 const unsigned char kFusedSrc[] = {
 #include "fused_src.inc"
     0};
@@ -272,7 +272,9 @@ std::string make_spec(int L, const int* dims, const int* act, int prec, bool wid
   if (is_train(prec) && train_depth(L, dims) != V21_TRAIN16_DEPTH) s += "d" + std::to_string(train_depth(L, dims)) + "_";
   for (int l = 0; l <= L; ++l) s += (l ? "x" : "") + std::to_string(dims[l]);
   s += "_a";
-  for (int l = 0; l < L; ++l) s += act[l] ? "1" : "0";
+  // one digit per layer: the code itself for the activations of act.h (3 .. 6), "1" for anything else that is not
+  // linear, as ever (a fused training kernel is never asked for with another code: jit_train_eligible)
+  for (int l = 0; l < L; ++l) s += act_is_smooth(act[l]) ? std::to_string(act[l]) : std::string(act[l] ? "1" : "0");
   s += "_";
   s += prec_type(prec, wide);
   return s;
@@ -283,7 +285,7 @@ std::string make_source(const JitKernel& k) {
          std::to_string(k.L + 1) + "] = {";
   for (int l = 0; l <= k.L; ++l) src += (l ? ", " : "") + std::to_string(k.dims[l]);
   src += "};\n  static constexpr int act[" + std::to_string(k.L) + "] = {";
-  for (int l = 0; l < k.L; ++l) src += (l ? ", " : "") + std::to_string(k.act[l] ? 1 : 0);
+  for (int l = 0; l < k.L; ++l) src += (l ? ", " : "") + std::to_string(act_is_smooth(k.act[l]) ? k.act[l] : (k.act[l] ? 1 : 0));
   src += "};\n};\n}  // namespace v21\n";
   return src;
 }
@@ -379,7 +381,7 @@ bool jit_eligible(int L, const int* dims, const int* act, std::string* why) {
   if (L < 1 || L > 16) return no("layer count not in [1, 16]");
   if (act[L - 1] != 0) return no("the fused kernel's output layer is linear");
   for (int l = 0; l < L; ++l)
-    if (act[l] != 0 && act[l] != 1) return no("the fused kernel has no variational head");
+    if (act[l] != 0 && act[l] != 1 && !act_is_smooth(act[l])) return no("the fused kernel has no variational head");  // (hidden layers: linear, ReLU, act.h)
   for (int l = 0; l <= L; ++l)
     if (dims[l] < 1 || dims[l] > 1024) return no("layer width not in [1, 1024]");
   // fused_fwd.h, Geo::spread_limit: an output layer of several tiles needs more k-steps per tile than the read-ahead depth
@@ -399,6 +401,7 @@ bool jit_train_eligible(int L, const int* dims, const int* act, std::string* why
   if (act[L - 1] != 0) return no("the loss is taken on a linear output layer");
   int pairs = 0;
   for (int l = 0; l < L; ++l) {
+    if (act_is_smooth(act[l])) return no("the fused training kernel has ReLU and linear layers only");
     if (act[l] != 0 && act[l] != 1) return no("the fused training kernel has no variational head");
     if (l + 1 < L && act[l]) pairs += ((dims[l + 1] + 15) / 16 + 1) / 2;
   }

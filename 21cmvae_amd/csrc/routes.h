@@ -15,6 +15,8 @@
 // it down.  Replaces nothing in the reference: Keras has one path (emulator.py:369-378, 402).
 #pragma once
 #include <cstdlib>
+
+#include "act.h"
 // internal forward flag (never part of include/v21.h; v21_mlp_forward masks caller flags to 0xFF): see decide_forward
 #define V21_FWD_RT_LATCH_OFF 0x200
 
@@ -112,6 +114,15 @@ inline NtSlices nt_slices(int rows, bool whole) {
   const int k_chunk = ((rows + nslice - 1) / nslice + 15) / 16 * 16;
   return NtSlices{(rows + k_chunk - 1) / k_chunk, k_chunk};
 }
+// a stack with an activation of act.h (tanh, sigmoid, elu, softplus) on any layer.  The chain kernels, the fused training
+// kernels and the table-driven forward know ReLU and linear only (a `relu` flag, sign bits, bit masks): no route below
+// may hand such a stack to them -- it trains per layer (gemm_nt.h: NT_FWD_ACT / NT_DX_ACT) and runs forward on
+// fused_fwd instantiated at run time, the few-row route or the generic route
+inline bool route_smooth(int L, const int* act) {
+  for (int l = 0; l < L; ++l)
+    if (act_is_smooth(act[l])) return true;
+  return false;
+}
 inline int route_nw(const int* dims, const int* act, int l) { return act[l] == V21_ACT_GAUSS ? 2 * dims[l + 1] : dims[l + 1]; }
 // the tile of a stack's f32 weight gradients in one launch: every layer's [dW; db] problem, one slice each
 inline int dw32_tile(int L, const int* dims, const int* act) {
@@ -208,6 +219,7 @@ inline TrainerKind decide_trainer_kind(int L, const int* dims, const int* act, i
   TrainerKind k;
   for (int l = 0; l < L; ++l)
     if (act[l] == V21_ACT_GAUSS) k.gl = l;
+  if (route_smooth(L, act)) return k;  // per-layer, for every precision and batch: no chain, no fused training kernel
   bool narrow = true;
   for (int l = 0; l <= L; ++l) narrow = narrow && dims[l] <= kChainMaxDim;
   if (precision != V21_PREC_F32) {
@@ -342,6 +354,7 @@ struct FwdQuery {
 };
 inline bool route_chain_fwd_eligible(const FwdQuery& q) {
   if (q.flags & V21_FWD_FORCE_GENERIC) return false;
+  if (route_smooth(q.L, q.act)) return false;  // (the chain kernels' `relu` flag cannot express them: V21_FWD_FORCE_CHAIN gives generic)
   for (int l = 0; l <= q.L; ++l)
     if (q.dims[l] > kChainMaxDim) return false;
   for (int l = 0; l < q.L; ++l)

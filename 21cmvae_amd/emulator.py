@@ -33,7 +33,8 @@ def _with_tqdm(verbose, *callback_lists):
 
 def _gen_model(in_dim, hidden_dims, out_dim, activation_func, name=None, variational=False):
     """Generate a new model: Dense(h, activation) per hidden dim, then a linear
-    Dense(out_dim).  ``in_dim`` None defers weight creation until ``build``/first call
+    Dense(out_dim).  ``activation_func``: "relu", "linear", "tanh", "sigmoid", "elu" or "softplus" (Keras'
+    definitions; a callable is taken by its ``__name__``), as the reference's "str or instance of tf.keras.activations".  ``in_dim`` None defers weight creation until ``build``/first call
     (a decoder that follows another model).  ``variational`` (not in the reference
     snapshot) makes the last layer a ``GaussianLatent`` (z_mean | z_log_var) head."""
     layers = []

@@ -25,6 +25,11 @@ def set_random_seed(seed):
     _rng = np.random.default_rng(seed)
 
 
+# activation name (Keras' spelling) -> the C ABI's code (include/v21.h: the table of definitions)
+_ACT_CODES = {"linear": _native.ACT_LINEAR, "relu": _native.ACT_RELU, "tanh": _native.ACT_TANH, "sigmoid": _native.ACT_SIGMOID,
+              "elu": _native.ACT_ELU, "softplus": _native.ACT_SOFTPLUS}
+
+
 class Dense:
     """One fully connected layer: ``activation(x @ kernel + bias)``; Glorot-uniform
     kernel, zero bias (Keras defaults, confirmed by the shipped files' model_config)."""
@@ -33,9 +38,9 @@ class Dense:
         act = activation if activation is not None else "linear"
         if callable(act):
             act = getattr(act, "__name__", str(act))
-        if act not in ("relu", "linear"):
-            raise NotImplementedError("activation %r: the engine implements 'relu' and linear (the reference "
-                                      "uses ReLU hidden layers and a linear output)" % (activation,))
+        if act not in _ACT_CODES:
+            raise NotImplementedError("activation %r: the engine implements %s (names as Keras spells them, or callables "
+                                      "with those names)" % (activation, ", ".join(repr(a) for a in _ACT_CODES)))
         self.units, self.activation, self.name = int(units), act, name
         self.kernel = None  # (in, out) float32
         self.bias = None
@@ -57,7 +62,7 @@ class Dense:
 
     @property
     def _act_code(self):
-        return _native.ACT_RELU if self.activation == "relu" else _native.ACT_LINEAR
+        return _ACT_CODES[self.activation]
 
     def count_params(self):
         return 0 if self.kernel is None else self.kernel.size + self.bias.size

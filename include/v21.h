@@ -51,7 +51,29 @@ enum { V21_PREC_F32 = 0, V21_PREC_F16 = 1, V21_PREC_BF16 = 2 };
  * layer sees is z = z_mean + exp(z_log_var / 2) * eps (dims[l+1] wide).  forward()
  * is deterministic (z = z_mean); the trainer samples eps and adds
  * kl_weight * KL(N(z_mean, exp z_log_var) || N(0, 1)) to every row's loss. */
-enum { V21_ACT_LINEAR = 0, V21_ACT_RELU = 1, V21_ACT_GAUSS = 2 };
+enum { V21_ACT_LINEAR = 0, V21_ACT_RELU = 1, V21_ACT_GAUSS = 2,
+       V21_ACT_TANH = 3, V21_ACT_SIGMOID = 4, V21_ACT_ELU = 5, V21_ACT_SOFTPLUS = 6 };
+/* V21_ACT_TANH .. V21_ACT_SOFTPLUS: the smooth activations, Keras' definitions (the reference's `activation_func`:
+ * "str or instance of tf.keras.activations"), evaluated in float32 whatever the precision of the contractions
+ * (csrc/act.h: formulas that neither overflow nor give NaN for any finite z; expf / expm1f / log1pf at 1 ulp):
+ *   code                  h = act(z)                  dh/dz, from the stored output h
+ *   V21_ACT_TANH     = 3  tanh z                      1 - h^2
+ *   V21_ACT_SIGMOID  = 4  1 / (1 + exp(-z))           h (1 - h)
+ *   V21_ACT_ELU      = 5  z > 0 ? z : exp(z) - 1      h > 0 ? 1 : h + 1      (alpha = 1)
+ *   V21_ACT_SOFTPLUS = 6  ln(1 + exp(z))              1 - exp(-h)
+ * Who takes them:
+ *   v21_mlp_create          on any layer (as it takes a ReLU output layer);
+ *   v21_mlp_forward[_dev]   fused_fwd instantiated at run time once its code object is ready (hidden layers only; linear
+ *                           output layer), before that and with V21_FWD_FORCE_GENERIC / V21_FWD_FORCE_CHAIN the generic
+ *                           per-layer route, few rows the small route; never the table-driven chain kernels;
+ *   v21_mlp_jacobian / _loglike / _fisher / _fit / _fit_map / the samplers: the generic Jacobian kernel and the two-launch
+ *                           ln L (the fused Jacobian and the fused ln L variant exist for the stacks of csrc/archs.h only);
+ *   v21_trainer_create      the per-layer route for every precision and batch; V21_ERR_UNSUPPORTED (the message names the
+ *                           layer) when the LAST layer has one: the loss is taken on a linear output layer;
+ *   v21_sweep_create        as for any per-layer trainer: works, every member equals its solo trainer;
+ *   v21_joint_create        V21_ERR_UNSUPPORTED (the message names the activation): the joint step runs on the chain kernels;
+ *   v21_mlp_jit             V21_ERR_UNSUPPORTED "no fused kernel for this stack" when the OUTPUT layer has one;
+ *   v21_trainer_jit (fused training kernels): never eligible. */
 enum { V21_DTYPE_F32 = 0, V21_DTYPE_F64 = 1 };
 
 /* Fused prologue = preprocess.par_transform (preprocess.py:49-110) with the training-set statistics cached:
