@@ -199,6 +199,8 @@ SIGNATURES = {
     "v21_mlp_loglike": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, _F, C.c_int, C.c_int]),
     "v21_mlp_loglike_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int]),
     "v21_route_jacobian": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
+    "v21_route_jacobian_rt": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "v21_mlp_jit_jacobian": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "v21_mlp_last_jac_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "v21_mlp_loglike_fwd": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, _F, C.c_int, C.c_int]),
     "v21_mlp_loglike_fwd_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_int]),
@@ -286,13 +288,21 @@ def route_forward(dims, act, precision, n, flags=0, rt_ready=False):
     return FWD_ROUTES[r.value]
 
 
-JAC_ROUTES = {1: "fused", 2: "generic"}
+JAC_ROUTES = {1: "fused", 2: "generic", 3: "fused_rt"}
 
 
 def route_jacobian(dims, act, precision, n, flags=0):
     """The route v21_mlp_jacobian / v21_mlp_loglike take for this stack (pure host logic: no GPU).  -> name of JAC_ROUTES."""
     r = C.c_int(0)
     check(load_library().v21_route_jacobian(*_layers(dims, act), precision_id(precision), int(n), int(flags), C.byref(r)))
+    return JAC_ROUTES[r.value]
+
+
+def route_jacobian_rt(dims, act, precision, flags=0):
+    """The route of a handle that asked for its run-time Jacobian kernel (Stack.jit_jacobian) and has it: "fused_rt" where
+    the stack can have one, else route_jacobian's answer (pure host logic: no GPU).  -> name of JAC_ROUTES."""
+    r = C.c_int(0)
+    check(load_library().v21_route_jacobian_rt(*_layers(dims, act), precision_id(precision), int(flags), C.byref(r)))
     return JAC_ROUTES[r.value]
 
 
@@ -841,6 +851,14 @@ class Stack(_Owned):
         check(self.lib.v21_mlp_jit(self.h, precision_id(precision), int(wait_ms), C.byref(s)))
         return "ready" if s.value == 1 else "compiling"
 
+    def jit_jacobian(self, precision="f32", wait_ms=-1):
+        """Ask for the fused JACOBIAN kernel of THIS stack (include/v21.h: v21_mlp_jit_jacobian) and wait up to `wait_ms`
+        (< 0: until compiled).  -> "ready" / "compiling"; raises EngineError when the stack cannot have one.  Opt-in:
+        once it is ready every Jacobian-side call of this stack in `precision` takes the "fused_rt" route."""
+        s = C.c_int(0)
+        check(self.lib.v21_mlp_jit_jacobian(self.h, precision_id(precision), int(wait_ms), C.byref(s)))
+        return "ready" if s.value == 1 else "compiling"
+
     def forward(self, x, precision="f32", flags=0):
         """host (n, in) float32/float64 -> host (n, out) float32"""
         x, dt = self._rows(x)
@@ -1341,6 +1359,11 @@ def _prebuild(dims, act, kernel, directory):
 def jit_prebuild_train(dims, act, precision, directory=None):
     """jit_prebuild for the fused TRAINING kernel of (dims, act, f16 | bf16) (include/v21.h: v21_trainer_jit)."""
     _prebuild(dims, act, precision_id(precision) | 16, directory)
+
+
+def jit_prebuild_jacobian(dims, act, precision, directory=None):
+    """jit_prebuild for the fused JACOBIAN kernel of (dims, act, precision) (include/v21.h: v21_mlp_jit_jacobian)."""
+    _prebuild(dims, act, precision_id(precision) | 32, directory)
 
 
 def jit_prebuild(dims, act, precision, directory=None):

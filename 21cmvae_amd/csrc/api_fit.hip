@@ -97,9 +97,9 @@ static int fit_check(const v21_fit_opts& o) {
 
 // a fit counts once for its iterations, and once more for the Fisher matrix at x_hat when that is asked for (the same
 // route: decide_jacobian does not read the input transform)
-static int fit_route(v21_mlp* m, int flags, bool fisher) {
-  const int route = jac_route(m, flags, m->dims[m->L]);
-  if (fisher) jac_route(m, flags, m->dims[m->L]);
+static int fit_route(v21_mlp* m, int precision, int flags, bool fisher) {
+  const int route = jac_route(m, precision, flags, m->dims[m->L]);
+  if (fisher) jac_route(m, precision, flags, m->dims[m->L]);
   return route;
 }
 
@@ -112,7 +112,7 @@ extern "C" int v21_mlp_fisher_dev(v21_mlp* m, const float* d_x, int64_t ldx, int
   CHK(jac_args(m, d_x && d_fisher, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kFisher));
   if (n == 0) return V21_OK;
   CHK(jac_prep(m, d_x, V21_DTYPE_F32, ldx, n, flags & V21_FWD_IN_TRANSFORM));
-  return reduce_run(m, jac_route(m, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, nullptr, m->lk_read(), 0, 1, 0, precision,
+  return reduce_run(m, jac_route(m, precision, flags, m->dims[m->L]), n, d_fisher, d_lnl, d_grad, nullptr, m->lk_read(), 0, 1, 0, precision,
                     flags);
 }
 
@@ -121,7 +121,7 @@ extern "C" int v21_mlp_fisher(v21_mlp* m, const void* x, int x_dtype, int64_t n,
   CHK(jac_args(m, x && fisher, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kFisher));
   if (n == 0) return V21_OK;
   const int din = m->dims[0];
-  const int route = jac_route(m, flags, m->dims[m->L]);
+  const int route = jac_route(m, precision, flags, m->dims[m->L]);
   ChunkStage sg;
   float *dF, *dl, *dg;
   sg.add(fisher, &dF, (size_t)din * din * sizeof(float));
@@ -163,7 +163,7 @@ static int fit_dev(v21_mlp* m, const float* d_x0, int64_t ldx, int64_t n, const 
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
-  const int route = fit_route(m, flags, d_fisher != nullptr);
+  const int route = fit_route(m, precision, flags, d_fisher != nullptr);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
   return fit_run(m, route, n, data, 0, o, precision, flags, d_x_hat, V21_DTYPE_F32, d_lnl, d_lnl_start, (int*)d_status, d_fisher,
                  is_map ? &map : nullptr, mout);
@@ -183,7 +183,7 @@ static int fit_host(v21_mlp* m, const void* x0, int x_dtype, int64_t n, const fl
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0];
-  const int route = fit_route(m, flags, fisher != nullptr);
+  const int route = fit_route(m, precision, flags, fisher != nullptr);
   ChunkStage sg;
   void* dx;
   float *dF, *dl, *dl0;

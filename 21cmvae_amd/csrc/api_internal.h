@@ -254,6 +254,10 @@ struct v21_mlp {
   const float* lk_read() const { return nu_k ? lk_proj.get() : lk_data.get(); }
   int last_jac_route = 0;
   long long jac_route_count[4] = {0, 0, 0, 0};
+  // fused_jac<this stack, precision> instantiated at run time (jit.h: kJitJac), only for a handle that ASKED
+  // (v21_mlp_jit_jacobian, or a call with V21_FWD_FORCE_JIT): routes.h JAC_FUSED_RT
+  v21::JitKernel* jac_jit[3] = {nullptr, nullptr, nullptr};
+  bool jac_jit_asked[3] = {false, false, false};
   // forward-only ln L (api_loglike.hip; routes.h: LnlRoute): the route of the last call and the calls per route
   int last_lnl_route = 0;
   long long lnl_route_count[4] = {0, 0, 0, 0};
@@ -290,8 +294,9 @@ bool jac_fused_compiled(int L, const int* dims, const int* act);
 // kNoPitch) and x_dtype, the entry's in_dim limit, then -- from here on only for n > 0, except for a fit -- precision and
 // the state the call needs.  Leaves flags with their defined bits only and, for n > 0, the context's device current.
 int jac_args(v21_mlp* m, bool ptrs, long long n, long long ldx, long long ldy, int x_dtype, int precision, int& flags, const JacEntry& e);
-// the route of one entry-point call (on ldy: a _dev Jacobian's y pitch, else out_dim), counted once
-int jac_route(v21_mlp* m, int flags, long long ldy);
+// the route of one entry-point call (on ldy: a _dev Jacobian's y pitch, else out_dim), counted once -- and decided once:
+// every slice, chunk and iteration of the call takes it (a run-time kernel that arrives mid-call serves the next call)
+int jac_route(v21_mlp* m, int precision, int flags, long long ldy);
 // device rows (float32 / float64, pitch ld) -> m->jxt / jfac, grown to n rows, on the context's stream
 int jac_prep(v21_mlp* m, const void* d_src, int dtype, long long ld, long long n, int tin);
 // Jacobian mode of `route` on the prepped rows into the likelihood workspace, slice by slice, each slice then reduced

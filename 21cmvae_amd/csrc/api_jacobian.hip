@@ -3,7 +3,8 @@
 // The reference's Keras model is differentiated with tf.GradientTape; here one launch pushes the primal and the in_dim
 // tangents through the stack together (forward mode: 7 inputs against 451 outputs).  Routes: csrc/routes.h
 // (decide_jacobian) -- fused_jac<Arch, Prec> (fused_jac.h) for the stacks of archs.h, jac_generic_kernel
-// (jac_generic.h) for every other.  What leaves the device of a Jacobian that stays there -- ln L, its gradient, Fisher
+// (jac_generic.h) for every other -- unless the handle asked for fused_jac instantiated for ITS stack at run time
+// (v21_mlp_jit_jacobian; jit.hip: kJitJac; K18).  What leaves the device of a Jacobian that stays there -- ln L, its gradient, Fisher
 // matrices, marginalised or not -- is reduced by jac_reduce_kernel (reduce_kernels.h; reduce_run).
 #include "api_internal.h"
 #include "fused_jac.h"
@@ -15,7 +16,43 @@ bool jac_fused_compiled(int L, const int* dims, const int* act) { return compile
 extern "C" int v21_route_jacobian(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int* route) {
   CHK(route_query_args(route, n_layers, dims, act, precision));
   (void)n;
-  *route = decide_jacobian(jac_fused_compiled(n_layers, dims, act), dims[0], flags & 0xFF, dims[n_layers]);
+  *route = decide_jacobian(jac_fused_compiled(n_layers, dims, act), dims[0], flags & 0xFF, dims[n_layers], false);
+  return V21_OK;
+}
+// ... and of a handle that asked for its run-time kernel and has it: JAC_FUSED_RT where the stack can have one
+extern "C" int v21_route_jacobian_rt(int n_layers, const int* dims, const int* act, int precision, int flags, int* route) {
+  CHK(route_query_args(route, n_layers, dims, act, precision));
+  *route = decide_jacobian(jac_fused_compiled(n_layers, dims, act), dims[0], flags & 0xFF, dims[n_layers],
+                           v21::jit_jac_eligible(n_layers, dims, act, nullptr));
+  return V21_OK;
+}
+
+// the run-time Jacobian kernel of (stack, precision), requested at most once per handle; nullptr: the stack cannot have
+// one, or V21_JIT=0 and nothing is cached
+static v21::JitKernel* jac_jit_kernel(v21_mlp* m, int precision) {
+  if (!m->jac_jit_asked[precision]) {
+    m->jac_jit[precision] = v21::jit_request(m->L, m->dims.data(), m->act.data(), precision | v21::kJitJac);
+    m->jac_jit_asked[precision] = true;
+  }
+  return m->jac_jit[precision];
+}
+extern "C" int v21_mlp_jit_jacobian(v21_mlp* m, int precision, int wait_ms, int* status) {
+  if (!m || !status) return fail(V21_ERR_ARG, "null argument");
+  if (precision < 0 || precision > 2) return fail(V21_ERR_ARG, "precision %d unknown", precision);
+  *status = -1;
+  if (m->fused_id >= 0) { *status = 1; return V21_OK; }  // compiled into the library (archs.h)
+  std::string why;
+  if (!v21::jit_jac_eligible(m->L, m->dims.data(), m->act.data(), &why))
+    return fail(V21_ERR_UNSUPPORTED, "no fused Jacobian kernel for this stack: %s", why.c_str());
+  v21::JitKernel* k = jac_jit_kernel(m, precision);
+  if (!k) return fail(V21_ERR_UNSUPPORTED, "run-time compilation is switched off (V21_JIT=0) and no cached kernel exists");
+  int s = v21::jit_state(k);
+  if (s == v21::JIT_COMPILING && wait_ms != 0) s = v21::jit_wait(k, wait_ms);
+  *status = s;
+  if (s == v21::JIT_FAILED) {
+    v21::jit_state(k, &why);
+    return fail(V21_ERR_UNSUPPORTED, "fused Jacobian kernel of this stack: %s", why.c_str());
+  }
   return V21_OK;
 }
 extern "C" int v21_mlp_last_jac_route(v21_mlp* m, int* route, long long counts[4]) {
@@ -64,11 +101,40 @@ int jac_args(v21_mlp* m, bool ptrs, long long n, long long ldx, long long ldy, i
   if ((flags & V21_FWD_IN_TRANSFORM) && !m->has_tin) return fail(V21_ERR_STATE, "input transform requested but not set");
   if ((flags & V21_FWD_OUT_TRANSFORM) && !m->has_tout) return fail(V21_ERR_STATE, "output transform requested but not set");
   if (e.like && !m->has_lk) return fail(V21_ERR_STATE, "%s requested but no likelihood set (v21_mlp_set_likelihood)", e.name);
-  return n == 0 ? V21_OK : use(m->ctx);
+  if (n == 0) return V21_OK;
+  if ((flags & V21_FWD_FORCE_JIT) && !(flags & V21_FWD_FORCE_GENERIC)) {
+    // diagnostics, as on the forward: the run-time kernel or an error -- for a stack of archs.h too; waits for the compiler
+    std::string why;
+    if (!v21::jit_jac_eligible(m->L, m->dims.data(), m->act.data(), &why))
+      return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: no run-time Jacobian kernel for this stack: %s", why.c_str());
+    v21::JitKernel* k = jac_jit_kernel(m, precision);
+    if (!k) return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: run-time compilation is switched off (V21_JIT=0) and no cached kernel exists");
+    if (v21::jit_wait(k, -1) != v21::JIT_READY) {
+      v21::jit_state(k, &why);
+      return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: %s", why.c_str());
+    }
+    // route 3 or an error: what decide_jacobian would silently send to the generic kernel is refused here
+    if (ldy != kNoPitch && ldy >= (1ll << 21))
+      return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: the fused Jacobian addresses y with a row pitch below 2^21 (ldy = %lld)", ldy);
+    CHK(use(m->ctx));
+    if (v21::jit_preload(k, m->ctx->device) != hipSuccess) {  // (a kernel that needs scratch memory, or cannot be loaded)
+      (void)hipGetLastError();
+      v21::jit_state(k, &why);
+      return fail(V21_ERR_UNSUPPORTED, "V21_FWD_FORCE_JIT: %s", why.c_str());
+    }
+    return V21_OK;
+  }
+  return use(m->ctx);
 }
 
-int jac_route(v21_mlp* m, int flags, long long ldy) {
-  const int route = decide_jacobian(m->fused_id >= 0, m->dims[0], flags, ldy);
+int jac_route(v21_mlp* m, int precision, int flags, long long ldy) {
+  // opt-in: only a kernel this handle asked for counts, and only once its code object is there (never waited for here)
+  // AND loaded on this device: a code object that cannot be loaded or needs scratch memory is marked failed by the load, so
+  // this call and every later one decide as a handle that never asked -- before anything of the call has run
+  v21::JitKernel* k = m->jac_jit_asked[precision] ? m->jac_jit[precision] : nullptr;
+  bool rt_ready = k && v21::jit_state(k) == v21::JIT_READY;
+  if (rt_ready && v21::jit_preload(k, m->ctx->device) != hipSuccess) { (void)hipGetLastError(); rt_ready = false; }
+  const int route = decide_jacobian(m->fused_id >= 0, m->dims[0], flags, ldy, rt_ready);
   m->last_jac_route = route;
   m->jac_route_count[route] += 1;
   return route;
@@ -99,14 +165,19 @@ static int jac_run(v21_mlp* m, int route, long long r0, long long n, float* y, l
   const bool tout = (flags & V21_FWD_OUT_TRANSFORM) != 0;
   const float* xt = m->jxt.get() + r0 * din;
   const float* fac = m->jfac.get() + r0 * din;
-  if (route == JAC_FUSED) {
+  if (route == JAC_FUSED || route == JAC_FUSED_RT) {
     JacArgs a{};
     a.x = xt; a.ldx = din; a.fac = fac;
     a.y = y; a.ldy = ldy; a.jac = jac; a.n_rows = n;
     CHK(mlp_fused_stream(m, prec, &a.stream));
     a.out_std = tout ? m->out_std : 1.0f;
     a.out_mean_scale = tout ? 1.0f : 0.0f;
-    HIPCHK(g_infer[m->fused_id].jac[prec](a, st));
+    if (route == JAC_FUSED) {
+      HIPCHK(g_infer[m->fused_id].jac[prec](a, st));
+      return V21_OK;
+    }
+    // (jac_route loaded the code object before it answered JAC_FUSED_RT: what is left to fail here is the launch itself)
+    HIPCHK(v21::jit_launch_jac(m->jac_jit[prec], m->ctx->device, a, st));
     return V21_OK;
   }
   // the stack, tangents per workgroup and LDS size (and the kernel's LDS attribute, once per device)
@@ -212,7 +283,7 @@ int reduce_run(v21_mlp* m, int route, long long n, float* d_F, float* d_lnl, flo
 // lnl / grad (nullable) of the n prepped rows: the generic kernel reduces in its own likelihood mode, the fused route's
 // Jacobian -- and, with a nuisance record, either route's -- is reduced slice by slice (reduce_run)
 static int loglike_run(v21_mlp* m, int route, long long n, float* d_lnl, float* d_grad, int prec, int flags) {
-  if (!m->nu_k && route != JAC_FUSED) return jac_run(m, route, 0, n, nullptr, m->dims[m->L], nullptr, d_lnl, d_grad, prec, flags);
+  if (!m->nu_k && route == JAC_GENERIC) return jac_run(m, route, 0, n, nullptr, m->dims[m->L], nullptr, d_lnl, d_grad, prec, flags);
   return reduce_run(m, route, n, nullptr, d_lnl, d_grad, nullptr, m->lk_read(), 0, 1, 0, prec, flags);
 }
 
@@ -224,21 +295,21 @@ extern "C" int v21_mlp_jacobian_dev(v21_mlp* m, const float* d_x, int64_t ldx, i
   if (n == 0) return V21_OK;
   if (!d_y) ldy = m->dims[m->L];
   CHK(jac_prep(m, d_x, V21_DTYPE_F32, ldx, n, flags & V21_FWD_IN_TRANSFORM));
-  return jac_run(m, jac_route(m, flags, ldy), 0, n, d_y, ldy, d_jac, nullptr, nullptr, precision, flags);
+  return jac_run(m, jac_route(m, precision, flags, ldy), 0, n, d_y, ldy, d_jac, nullptr, nullptr, precision, flags);
 }
 extern "C" int v21_mlp_loglike_dev(v21_mlp* m, const float* d_x, int64_t ldx, int64_t n, float* d_lnl, float* d_grad, int precision,
                                    int flags) {
   CHK(jac_args(m, d_x && d_lnl, n, ldx, kNoPitch, V21_DTYPE_F32, precision, flags, kLoglike));
   if (n == 0) return V21_OK;
   CHK(jac_prep(m, d_x, V21_DTYPE_F32, ldx, n, flags & V21_FWD_IN_TRANSFORM));
-  return loglike_run(m, jac_route(m, flags, m->dims[m->L]), n, d_lnl, d_grad, precision, flags);
+  return loglike_run(m, jac_route(m, precision, flags, m->dims[m->L]), n, d_lnl, d_grad, precision, flags);
 }
 
 extern "C" int v21_mlp_jacobian(v21_mlp* m, const void* x, int x_dtype, int64_t n, float* y, float* jac, int precision, int flags) {
   CHK(jac_args(m, x && jac, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kJacobian));
   if (n == 0) return V21_OK;
   const int din = m->dims[0], dout = m->dims[m->L];
-  const int route = jac_route(m, flags, dout);
+  const int route = jac_route(m, precision, flags, dout);
   ChunkStage sg;
   float *dy, *dj;
   sg.add(y, &dy, dout * sizeof(float));
@@ -250,7 +321,7 @@ extern "C" int v21_mlp_jacobian(v21_mlp* m, const void* x, int x_dtype, int64_t 
 extern "C" int v21_mlp_loglike(v21_mlp* m, const void* x, int x_dtype, int64_t n, float* lnl, float* grad, int precision, int flags) {
   CHK(jac_args(m, x && lnl, n, kNoPitch, kNoPitch, x_dtype, precision, flags, kLoglike));
   if (n == 0) return V21_OK;
-  const int route = jac_route(m, flags, m->dims[m->L]);
+  const int route = jac_route(m, precision, flags, m->dims[m->L]);
   ChunkStage sg;
   float *dl, *dg;
   sg.add(lnl, &dl, sizeof(float));

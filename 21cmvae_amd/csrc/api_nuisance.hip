@@ -136,7 +136,7 @@ extern "C" int v21_mlp_nuisance_coef(v21_mlp* m, const void* x, int x_dtype, int
   if (!m->nu_k) return fail(V21_ERR_STATE, "nuisance amplitudes requested but no nuisance modes set (v21_mlp_set_nuisance)");
   if (n == 0) return V21_OK;
   const int K = m->nu_k;
-  const int route = jac_route(m, flags, m->dims[m->L]);
+  const int route = jac_route(m, precision, flags, m->dims[m->L]);
   std::vector<float> b((size_t)n * K);
   ChunkStage sg;
   float* db;

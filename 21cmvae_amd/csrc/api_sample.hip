@@ -154,7 +154,7 @@ static int sample_dev(v21_mlp* m, const float* d_x0, long long ldx, long long n,
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
-  const int route = jac_route(m, flags, m->dims[m->L]);
+  const int route = jac_route(m, precision, flags, m->dims[m->L]);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
   return sample_run(m, route, n, data, 0, o, o.chain0, d_eps_start, precision, flags, *out, V21_DTYPE_F32, tempered ? &t : nullptr, tout);
 }
@@ -171,7 +171,7 @@ static int sample_host(v21_mlp* m, const void* x0, int x_dtype, long long n, con
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
   const int din = m->dims[0], dout = m->dims[m->L];
-  const int route = jac_route(m, flags, dout);
+  const int route = jac_route(m, precision, flags, dout);
   ChunkStage sg;
   double* d_eps = nullptr;
   v21_sample_out d{};

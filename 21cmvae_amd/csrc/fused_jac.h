@@ -33,10 +33,31 @@ struct JacArgs {
   float out_mean_scale;
 };
 
-// virtual rows per signal
+// virtual rows per signal: the one rule, for the kernel (jac_group<IN>) and for the host's launch geometry (jit.hip)
+constexpr int jac_group_of(int in_dim) { return in_dim <= 7 ? 8 : 16; }
 template <int IN> constexpr int jac_group() {
   static_assert(IN >= 1 && IN <= 15, "fused Jacobian: at most 15 inputs");
-  return IN <= 7 ? 8 : 16;
+  return jac_group_of(IN);
+}
+
+// The value of the first lane of each group of GR consecutive lanes (the primal's) in every lane of the group, by DPP:
+// quad_perm [0, 0, 0, 0] fills each quad from its lane 0, then row_shr:4 into bank 1 [and 3] and, for GR = 16, row_shr:8
+// into banks 2 and 3 copy the first quad over the group.  2 (3) VALU moves in the wave's own registers: no LDS-queue
+// slot (ds_bpermute / __shfl take one, and the ring's LDS reads wait on that queue), no memory counter touched -- the
+// ring's counted vmcnt waits stand as they are.  gfx950 has no DPP8 and no row_share; rows are 16 lanes, so a group
+// never crosses one.
+template <int GR>
+__device__ __forceinline__ float jac_group_bcast(float v) {
+  static_assert(GR == 8 || GR == 16, "groups of 8 or 16 lanes");
+  int x = __builtin_bit_cast(int, v);
+  x = __builtin_amdgcn_update_dpp(x, x, 0x000, 0xF, 0xF, false);  // quad_perm [0, 0, 0, 0]
+  if constexpr (GR == 8) {
+    x = __builtin_amdgcn_update_dpp(x, x, 0x114, 0xF, 0xA, false);  // row_shr:4 -> lanes 4-7 and 12-15
+  } else {
+    x = __builtin_amdgcn_update_dpp(x, x, 0x114, 0xF, 0x2, false);  // row_shr:4 -> lanes 4-7
+    x = __builtin_amdgcn_update_dpp(x, x, 0x118, 0xF, 0xC, false);  // row_shr:8 -> lanes 8-15
+  }
+  return __builtin_bit_cast(float, x);
 }
 
 // grid.x = ceil(n_rows * G / (WAVES*CT*32)); block = 64*WAVES threads; dynamic LDS fused_lds<P>().
@@ -141,7 +162,22 @@ __global__ void __launch_bounds__(64 * P::WAVES, P::WPS) fused_jac(const JacArgs
       if constexpr (item < G::ks_of(l + 1)) {
         auto& out = (l & 1) ? bufA : bufB;
         float x0 = acc[GT & 1][ct][2 * pr], x1 = acc[GT & 1][ct][2 * pr + 1];
-        if constexpr (G::act(l) != 0) {
+        if constexpr (G::act(l) >= 3) {
+          // an activation of act.h (run-time instantiations only: archs.h has none); its own branch: the ReLU / linear
+          // code below is what it was.  Primal lanes take act_apply on the f32 accumulator before the pack -- fused_fwd's
+          // smooth branch, bit for bit; tangent lanes take t * act'(z) with act' from the PRIMAL's z (act.h: a saturated
+          // unit has no digits left in 1 - h^2), brought from the group's first lane by jac_group_bcast.  |act'| <= 1.
+          // Padding: the features >= dim(l + 1) of a partial tile hold act(0) on primal lanes afterwards (0.5 for sigmoid,
+          // ln 2 for softplus) and meet only the ZERO weights pack_stream_kernel writes for them, as in fused_fwd; padding
+          // virtual rows (g_lane > in_dim) carry zero tangents and 0 * act' stays 0; rows past n_rows are dropped by the
+          // stores' range check.  (Both functions are also evaluated on tangent lanes, whose "z" is a tangent: whatever they
+          // give there -- an inf included -- is dropped by the prim_lane selects and overwritten by the broadcast.)
+          const float d0 = jac_group_bcast<GR>(act_deriv_in<G::act(l)>(x0));
+          const float d1 = jac_group_bcast<GR>(act_deriv_in<G::act(l)>(x1));
+          const float h0 = act_apply<G::act(l)>(x0), h1 = act_apply<G::act(l)>(x1);
+          x0 = prim_lane ? h0 : x0 * d0;
+          x1 = prim_lane ? h1 : x1 * d1;
+        } else if constexpr (G::act(l) != 0) {
           const unsigned long long m0 = (__ballot(x0 > 0.f) & PAT) * SPR;
           const unsigned long long m1 = (__ballot(x1 > 0.f) & PAT) * SPR;
           x0 = __builtin_amdgcn_inverse_ballot_w64(m0) ? x0 : 0.f;

@@ -19,12 +19,26 @@
 
 namespace v21 {
 struct JitKernel;  // one (stack, precision); lives until the library is unloaded
+struct JacArgs;    // fused_jac.h
 enum { JIT_COMPILING = 0, JIT_READY = 1, JIT_FAILED = -1 };
 // r5: `prec | kJitTrain16` asks for the fused TRAINING kernel of the stack (fused_train16<Arch, Prec>, f16 / bf16) instead
 // of the forward kernel: same registry, same caches, same compiler process
 constexpr int kJitTrain16 = 16;
 bool jit_train_eligible(int L, const int* dims, const int* act, std::string* why);
 hipError_t jit_launch_train(JitKernel* k, int device, const ChainArgs& a, hipStream_t st);
+// K18: `prec | kJitJac` (f32 / f16 / bf16) asks for the fused JACOBIAN kernel of the stack (fused_jac<Arch, Prec>, fused_jac.h),
+// on the forward's packed weight stream: a third kind in the same registry, caches and compiler process, with a source
+// blob of its own (the forward objects' cache keys do not move)
+constexpr int kJitJac = 32;
+// jit_eligible plus what fused_jac's own static_asserts require (1 <= dims[0] <= 15; the linear output layer and its aux
+// double buffer are jit_eligible's already).  Widths: the template compiles up to jit_eligible's 1,024; what does not
+// fit a wave's registers spills and is refused when it is loaded.
+bool jit_jac_eligible(int L, const int* dims, const int* act, std::string* why);
+// as jit_launch: hipErrorNotReady while compiling; a code object that needs scratch memory is marked failed at load time
+hipError_t jit_launch_jac(JitKernel* k, int device, const JacArgs& a, hipStream_t st);
+// load a ready kernel's code object on `device` now (what the first launch would do): a route is decided on a kernel that
+// can be launched, not on one that turns out to need scratch memory half way through a call
+hipError_t jit_preload(JitKernel* k, int device);
 
 // false (with a reason) for stacks fused_fwd cannot express: a non-linear output layer, a variational head, > 16 layers
 bool jit_eligible(int L, const int* dims, const int* act, std::string* why);

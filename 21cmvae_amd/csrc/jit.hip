@@ -1,7 +1,8 @@
 // jit.hip -- run-time instantiation of fused_fwd<Arch, Prec> -- and, r5, of the fused training kernel
-// fused_train16<Arch, Prec> -- through hiprtc (see jit.h).  A kernel's KIND rides in bit 4 of the precision argument of
-// the internal interface (kJitTrain16 | V21_PREC_F16 ...), so that the registry, the cache and the compiler process
-// (v21_jitc -> v21_jit_prebuild) serve both with the same code.
+// fused_train16<Arch, Prec>, and, K18, of the fused Jacobian kernel fused_jac<Arch, Prec> -- through hiprtc (see jit.h).
+// A kernel's KIND rides in bits 4 and 5 of the precision argument of the internal interface (kJitTrain16 | V21_PREC_F16,
+// kJitJac | V21_PREC_F32 ...), so that the registry, the cache and the compiler process (v21_jitc -> v21_jit_prebuild)
+// serve all three with the same code.
 #include "jit.h"
 #include "fused_families.h"
 
@@ -35,8 +36,21 @@ const unsigned char kFusedSrc[] = {
 const unsigned char kTrainSrc[] = {
 #include "fused_train_src.inc"
     0};
+// ... + fused_jac.h (Makefile: fused_jac_src.inc): a blob of its own, so that kFusedSrc -- and with it the file names of the
+// forward kernels' cached code objects -- stays what it was
+const unsigned char kJacSrc[] = {
+#include "fused_jac_src.inc"
+    0};
 inline bool is_train(int prec) { return (prec & kJitTrain16) != 0; }
+inline bool is_jac(int prec) { return (prec & kJitJac) != 0; }
 inline int base_prec(int prec) { return prec & 15; }
+// the embedded sources of a kernel's kind
+struct Blob { const unsigned char* p; size_t n; };
+inline Blob kind_src(int prec) {
+  if (is_train(prec)) return Blob{kTrainSrc, sizeof(kTrainSrc)};
+  if (is_jac(prec)) return Blob{kJacSrc, sizeof(kJacSrc)};
+  return Blob{kFusedSrc, sizeof(kFusedSrc)};
+}
 
 // ---- hiprtc, loaded at run time (a user who never predicts on a custom stack needs no libhiprtc)
 typedef void* rtc_prog;
@@ -106,6 +120,8 @@ bool jit_wide() { return false; }
 #endif
 const char* prec_type(int prec, bool wide) {
   if (is_train(prec)) return base_prec(prec) == 1 ? "PrecF16t16" : "PrecBF16t16";
+  // (the Jacobian kernels exist in the forms the compiled S1-S4 launchers use only: never `wide`)
+  if (is_jac(prec)) return base_prec(prec) == 0 ? "PrecF32" : (base_prec(prec) == 1 ? "PrecF16x2sp" : "PrecBF16x2sp");
   return prec == 0 ? "PrecF32" : (prec == 1 ? (wide ? "PrecF16" : "PrecF16x2sp") : (wide ? "PrecBF16" : "PrecBF16x2sp"));
 }
 // LDS read-ahead (fragments) of a run-time training kernel: the template's default (V21_TRAIN16_DEPTH = 4) unless the loss
@@ -120,7 +136,10 @@ int train_depth(int L, const int* dims) {
 // the launch geometry of a run-time kernel: that of its family (fused_families.h), as the compiled kernels take it
 struct Launch { int threads, lds; long long (*workgroups)(long long rows); };
 template <class F, class P> constexpr Launch launch_of() { return Launch{F::template threads<P>(), F::template lds<P>(), &F::template workgroups<P>}; }
+// (a Jacobian launch covers rows x jac_group virtual rows: jit_launch_jac multiplies, from the stack's in_dim)
 Launch launch_geometry(int prec, bool wide) {
+  if (is_jac(prec))
+    return base_prec(prec) == 0 ? launch_of<FamilyJac, PrecF32>() : (base_prec(prec) == 1 ? launch_of<FamilyJac, PrecF16x2sp>() : launch_of<FamilyJac, PrecBF16x2sp>());
   if (is_train(prec)) return base_prec(prec) == 1 ? launch_of<FamilyTrain16, PrecF16t16>() : launch_of<FamilyTrain16, PrecBF16t16>();
   if (prec == 0) return launch_of<FamilyFwd, PrecF32>();
   if (prec == 1) return wide ? launch_of<FamilyFwd, PrecF16>() : launch_of<FamilyFwd, PrecF16x2sp>();
@@ -268,7 +287,7 @@ struct Registry {
 Registry g_reg;
 
 std::string make_spec(int L, const int* dims, const int* act, int prec, bool wide) {
-  std::string s = is_train(prec) ? "train16_" : "";
+  std::string s = is_train(prec) ? "train16_" : (is_jac(prec) ? "jac_" : "");
   if (is_train(prec) && train_depth(L, dims) != V21_TRAIN16_DEPTH) s += "d" + std::to_string(train_depth(L, dims)) + "_";
   for (int l = 0; l <= L; ++l) s += (l ? "x" : "") + std::to_string(dims[l]);
   s += "_a";
@@ -280,7 +299,7 @@ std::string make_spec(int L, const int* dims, const int* act, int prec, bool wid
   return s;
 }
 std::string make_source(const JitKernel& k) {
-  std::string src((const char*)(is_train(k.prec) ? kTrainSrc : kFusedSrc));
+  std::string src((const char*)kind_src(k.prec).p);
   src += "\nnamespace v21 {\nstruct ArchRT {\n  static constexpr int L = " + std::to_string(k.L) + ";\n  static constexpr int dims[" +
          std::to_string(k.L + 1) + "] = {";
   for (int l = 0; l <= k.L; ++l) src += (l ? ", " : "") + std::to_string(k.dims[l]);
@@ -308,7 +327,7 @@ int toolchain_version() {
   return cached;
 }
 std::string file_name(const JitKernel& k) {
-  unsigned long long h = is_train(k.prec) ? fnv1a(kTrainSrc, sizeof(kTrainSrc)) : fnv1a(kFusedSrc, sizeof(kFusedSrc));
+  unsigned long long h = fnv1a(kind_src(k.prec).p, kind_src(k.prec).n);
   for (int i = 0; i < kNumOptions; ++i) h = fnv1a(kOptions[i], strlen(kOptions[i]), h);
   h = fnv1a(k.spec.data(), k.spec.size(), h);
   const int meta[3] = {kCacheFormat, toolchain_version(), HIP_VERSION};
@@ -321,7 +340,8 @@ std::string file_name(const JitKernel& k) {
 int compile(const JitKernel& k, std::string& sym, std::vector<char>& code, std::string& why) {
   if (!load_rtc(&why)) return -1;
   const std::string src = make_source(k);
-  const std::string expr = std::string(is_train(k.prec) ? "v21::fused_train16<v21::ArchRT, v21::" : "v21::fused_fwd<v21::ArchRT, v21::") +
+  const std::string expr = std::string(is_train(k.prec) ? "v21::fused_train16<v21::ArchRT, v21::"
+                                                        : (is_jac(k.prec) ? "v21::fused_jac<v21::ArchRT, v21::" : "v21::fused_fwd<v21::ArchRT, v21::")) +
                            prec_type(k.prec, k.wide) + ">";
   rtc_prog prog = nullptr;
   int r = g_rtc.CreateProgram(&prog, src.c_str(), "v21_fused_rt.hip", 0, nullptr, nullptr);
@@ -368,7 +388,7 @@ void finish(JitKernel* k, int state, const std::string& why) {
   k->cv.notify_all();
 }
 void fill(JitKernel* k, int L, const int* dims, const int* act, int prec) {
-  k->L = L; k->prec = prec; k->wide = jit_wide();
+  k->L = L; k->prec = prec; k->wide = jit_wide() && !is_jac(prec);
   for (int l = 0; l <= L; ++l) k->dims[l] = dims[l];
   for (int l = 0; l < L; ++l) k->act[l] = act[l];
   k->spec = make_spec(L, dims, act, prec, k->wide);
@@ -387,6 +407,18 @@ bool jit_eligible(int L, const int* dims, const int* act, std::string* why) {
   // fused_fwd.h, Geo::spread_limit: an output layer of several tiles needs more k-steps per tile than the read-ahead depth
   // (f32: 8 features per k-step, depth 2)
   if (dims[L] > 32 && dims[L - 1] <= 32) return no("the output layer's input is too narrow for the fused kernel's aux double buffer");
+  return true;
+}
+
+// fused_jac<ArchRT, Prec> (fused_jac.h) for this stack: what jit_eligible asks of fused_fwd -- the linear output layer and
+// its aux double buffer are the same two static_asserts in both templates -- and jac_group's own: 1 .. 15 inputs.  Every
+// static_assert a stack could trip is refused HERE by name, so that no hiprtc log reaches a user.  Widths: the template
+// compiles up to jit_eligible's 1,024 (7 -> 1024 -> 1024 -> 451 compiles in f16 and f32, with 2 - 4 KB of scratch: the two
+// operand buffers alone are 2 x 4 x width / 16 registers in 16 bits, 2 x 4 x width / 8 in f32); what spills is refused
+// when it is loaded, and the handle stays on the generic route.
+bool jit_jac_eligible(int L, const int* dims, const int* act, std::string* why) {
+  if (!jit_eligible(L, dims, act, why)) return false;
+  if (dims[0] > 15) { if (why) *why = "the fused Jacobian takes at most 15 inputs"; return false; }
   return true;
 }
 
@@ -412,11 +444,17 @@ bool jit_train_eligible(int L, const int* dims, const int* act, std::string* why
   return true;
 }
 
+// a kernel argument of the internal interface: one kind bit at most over a base precision that kind has, and a stack it takes
+static bool kind_ok(int L, const int* dims, const int* act, int prec, std::string* why) {
+  if (prec < 0 || (prec & ~(15 | kJitTrain16 | kJitJac)) || (is_train(prec) && is_jac(prec))) return false;
+  if (is_train(prec)) return (base_prec(prec) == 1 || base_prec(prec) == 2) && jit_train_eligible(L, dims, act, why);
+  if (base_prec(prec) > 2) return false;
+  return is_jac(prec) ? jit_jac_eligible(L, dims, act, why) : jit_eligible(L, dims, act, why);
+}
+
 JitKernel* jit_request(int L, const int* dims, const int* act, int prec) {
-  if (is_train(prec)) {
-    if ((base_prec(prec) != 1 && base_prec(prec) != 2) || !jit_train_eligible(L, dims, act, nullptr)) return nullptr;
-  } else if (prec < 0 || prec > 2 || !jit_eligible(L, dims, act, nullptr)) return nullptr;
-  const std::string spec = make_spec(L, dims, act, prec, jit_wide());
+  if (!kind_ok(L, dims, act, prec, nullptr)) return nullptr;
+  const std::string spec = make_spec(L, dims, act, prec, jit_wide() && !is_jac(prec));
   std::lock_guard<std::mutex> lk(g_reg.mu);
   auto it = g_reg.all.find(spec);
   if (it != g_reg.all.end()) return it->second;
@@ -518,6 +556,12 @@ int jit_wait(JitKernel* k, int timeout_ms) {
 }
 
 static hipError_t jit_launch_any(JitKernel* k, int device, void* arg_block, long long rows, hipStream_t st);
+hipError_t jit_launch_jac(JitKernel* k, int device, const JacArgs& a, hipStream_t st) {
+  if (!k || !is_jac(k->prec)) return hipErrorInvalidValue;
+  JacArgs copy = a;
+  // FamilyJac::rows: jac_group_of(in_dim) virtual rows per row of the call (fused_jac.h)
+  return jit_launch_any(k, device, &copy, a.n_rows * jac_group_of(k->dims[0]), st);
+}
 hipError_t jit_launch(JitKernel* k, int device, const FusedArgs& a, hipStream_t st) {
   FusedArgs copy = a;
   return jit_launch_any(k, device, &copy, a.n_rows, st);
@@ -526,12 +570,13 @@ hipError_t jit_launch_train(JitKernel* k, int device, const ChainArgs& a, hipStr
   ChainArgs copy = a;
   return jit_launch_any(k, device, &copy, a.rows, st);
 }
-static hipError_t jit_launch_any(JitKernel* k, int device, void* arg_block, long long rows, hipStream_t st) {
+// the code object of a ready kernel on `device`, loaded on first use; a kernel that needs scratch memory or cannot be
+// loaded is marked failed
+static hipError_t jit_load(JitKernel* k, int device, const Launch& g, JitKernel::Loaded* out) {
   if (!k) return hipErrorInvalidValue;
   const int s = k->state.load(std::memory_order_acquire);
   if (s == JIT_COMPILING) return hipErrorNotReady;
   if (s != JIT_READY) return hipErrorInvalidValue;
-  const Launch g = launch_geometry(k->prec, k->wide);
   JitKernel::Loaded ld;
   {
     std::lock_guard<std::mutex> lk(k->mu);
@@ -563,6 +608,20 @@ static hipError_t jit_launch_any(JitKernel* k, int device, void* arg_block, long
     }
     ld = it->second;
   }
+  *out = ld;
+  return hipSuccess;
+}
+hipError_t jit_preload(JitKernel* k, int device) {
+  if (!k) return hipErrorInvalidValue;
+  JitKernel::Loaded ld;
+  return jit_load(k, device, launch_geometry(k->prec, k->wide), &ld);
+}
+static hipError_t jit_launch_any(JitKernel* k, int device, void* arg_block, long long rows, hipStream_t st) {
+  if (!k) return hipErrorInvalidValue;
+  const Launch g = launch_geometry(k->prec, k->wide);
+  JitKernel::Loaded ld;
+  const hipError_t le = jit_load(k, device, g, &ld);
+  if (le != hipSuccess) return le;
   const long long nwg = g.workgroups(rows);
   if (nwg <= 0) return hipSuccess;
   void* args[] = {arg_block};
@@ -571,8 +630,7 @@ static hipError_t jit_launch_any(JitKernel* k, int device, void* arg_block, long
 
 int jit_prebuild(int L, const int* dims, const int* act, int prec, const char* dir, std::string* why) {
   std::string w;
-  const bool ok = is_train(prec) ? ((base_prec(prec) == 1 || base_prec(prec) == 2) && jit_train_eligible(L, dims, act, &w))
-                                 : (prec >= 0 && prec <= 2 && jit_eligible(L, dims, act, &w));
+  const bool ok = kind_ok(L, dims, act, prec, &w);
   if (!ok) { if (why) *why = w.empty() ? "bad precision" : w; return -1; }
   JitKernel k;
   fill(&k, L, dims, act, prec);

@@ -388,11 +388,16 @@ enum JacRoute {
   JAC_NONE = 0,
   JAC_FUSED = 1,    // fused_jac<Arch, Prec> compiled into the library (archs.h S1-S4; fused_jac.h)
   JAC_GENERIC = 2,  // any other stack, any in_dim, variational stacks: jac_generic_kernel (jac_generic.h), f32 arithmetic
+  JAC_FUSED_RT = 3, // fused_jac<this stack, Prec> instantiated at run time (jit.hip: kJitJac), for a handle that asked (K18)
 };
 constexpr int kJacMaxIn = 15;  // the fused Jacobian's in_dim limit, and that of the reduction of its rows (reduce_kernels.h)
-inline int decide_jacobian(bool fused_compiled, int in_dim, int flags, long long ldy) {
-  const bool fused = fused_compiled && in_dim <= kJacMaxIn && !(flags & V21_FWD_FORCE_GENERIC) && ldy < (1ll << 21);
-  return fused ? JAC_FUSED : JAC_GENERIC;
+// rt_ready: the handle asked for its run-time kernel (v21_mlp_jit_jacobian, or V21_FWD_FORCE_JIT on this call) and the
+// code object is there.  The route is opt-in: a handle that never asked -- and every query without a handle -- passes
+// false and gets what it always got.  A stack of archs.h keeps its compiled kernel unless the call forces the run-time one.
+inline int decide_jacobian(bool fused_compiled, int in_dim, int flags, long long ldy, bool rt_ready) {
+  const bool ok = in_dim <= kJacMaxIn && !(flags & V21_FWD_FORCE_GENERIC) && ldy < (1ll << 21);
+  if (ok && rt_ready && (!fused_compiled || (flags & V21_FWD_FORCE_JIT))) return JAC_FUSED_RT;
+  return ok && fused_compiled ? JAC_FUSED : JAC_GENERIC;
 }
 
 // ---- forward-only Gaussian log-likelihood (v21_mlp_loglike_fwd[_dev]): ln L without its gradient, the call an outside

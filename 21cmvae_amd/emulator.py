@@ -416,7 +416,39 @@ class _EmulatorBase:
         """(model, stack, flags, rows) of the model ``predict`` evaluates, with both transforms set, for the derivatives
         below (the library differentiates par_transform for the rows' dtype)."""
         model = self._predict_chain() if hasattr(self, "_predict_chain") else self.emulator
-        return (model,) + self._stack_rows(model, params, host_fallback=False)
+        out = (model,) + self._stack_rows(model, params, host_fallback=False)
+        # compile_derivatives: a stack REBUILT since then (new weights of another shape, another precision) asks again,
+        # without waiting; the stack that was asked is not asked twice
+        if getattr(self, "_derivatives_rt", None) not in (None, (out[1], model.precision)):
+            self._ask_derivatives(out[1], model.precision, 0)
+            self._derivatives_rt = (out[1], model.precision)
+        return out
+
+    @staticmethod
+    def _ask_derivatives(st, precision, wait_ms):
+        """Stack.jit_jacobian; "unsupported" for a stack the kernel cannot express (the library's "no fused Jacobian kernel
+        for this stack").  Every other failure -- run-time compilation switched off with nothing cached, a compiler
+        error, a kernel too wide for the registers -- is raised as it is: it is not the stack's shape that is in the way."""
+        try:
+            return st.jit_jacobian(precision, wait_ms)
+        except nat.EngineError as e:
+            if "no fused Jacobian kernel for this stack" in str(e):
+                return "unsupported"
+            raise
+
+    def compile_derivatives(self, wait=True):
+        """Opt in to the fused Jacobian kernel instantiated for THIS emulator's stack at run time (include/v21.h:
+        v21_mlp_jit_jacobian): afterwards ``jacobian``, ``log_likelihood(grad=True)``, ``fisher``, ``fit_parameters``,
+        ``sample_posterior`` and ``sample_tempered`` take the "fused_rt" route in the model's precision instead of the
+        generic kernel -- for any ``hidden_dims``, with ReLU or a smooth ``activation_func``.  wait=True waits for the
+        compilation (seconds, once per stack: the code object is cached on disk).  -> "ready", "compiling", or
+        "unsupported" for a stack the kernel cannot express (a variational head, a non-linear output layer, more than 15
+        parameters): such an emulator computes as before.  Never raises for an ineligible stack; an eligible stack whose
+        kernel cannot be had (V21_JIT=0 with nothing cached, a compiler failure) raises EngineError with the reason."""
+        model, st, _, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
+        state = self._ask_derivatives(st, model.precision, -1 if wait else 0)
+        self._derivatives_rt = None if state == "unsupported" else (st, model.precision)
+        return state
 
     def jacobian(self, params, return_signal=False):
         """d signal / d params in mK per raw parameter unit (not in the reference: there, tf.GradientTape around

@@ -204,10 +204,26 @@ int v21_jit_prebuild(int n_layers, const int* dims, const int* act, int precisio
  *     NULL clears).  Bins with w == 0 do not influence any result.
  *   v21_mlp_loglike[_dev]   lnl[n] = -1/2 sum_k w_k (d_k - y_k)^2 and grad[n, j] = d lnl / d x[n, j] (nullable), reduced
  *     on the device (4 (1 + in_dim) bytes per row leave it instead of the whole Jacobian).
- * Routes (v21_route_jacobian; csrc/routes.h: 1 = fused, 2 = generic): the stacks of archs.h (S1-S4, up to 15 inputs)
- * take fused_jac<Arch, Prec>, whose primal is bit-identical to the forward's fused route in the same precision; every
- * other stack (any hidden_dims, any in_dim, wider than 512, V21_ACT_GAUSS evaluated as z = z_mean) takes a generic
- * kernel in f32 arithmetic whatever the precision.  n = 0 is a no-op.  The _dev forms are asynchronous on the
+ * Routes (v21_route_jacobian; csrc/routes.h: 1 = fused, 2 = generic, 3 = fused_rt): the stacks of archs.h (S1-S4, up to
+ * 15 inputs) take fused_jac<Arch, Prec>, whose primal is bit-identical to the forward's fused route in the same
+ * precision; every other stack (any hidden_dims, any in_dim, wider than 512, V21_ACT_GAUSS evaluated as z = z_mean)
+ * takes a generic kernel in f32 arithmetic whatever the precision -- unless the handle ASKED for route 3:
+ *   v21_mlp_jit_jacobian  fused_jac instantiated for THIS stack at run time (csrc/jit.h; ReLU, linear and the smooth
+ *     activations 3 .. 6 on hidden layers; 1 .. 15 inputs, a linear output layer, widths up to 1,024 where the registers
+ *     hold them), semantics as v21_mlp_jit: *status 1 ready (also for a compiled-in stack), 0 compiling,
+ *     V21_ERR_UNSUPPORTED (status -1) with the reason in v21_last_error.  It marks the handle as asked for that
+ *     precision: from the first call that starts with the code object in place, every Jacobian-side call of the handle
+ *     (Jacobian, ln L + gradient, Fisher, fits, MAP, both samplers) takes route 3.  A call decides its route once, for all
+ *     its slices, chunks and iterations; a kernel that arrives mid-call serves the next call; one that cannot be loaded
+ *     or needs scratch memory (found when the first call after its arrival decides its route) leaves the handle on
+ *     route 2, without an error.  Its primal is bit-identical to the
+ *     forward's run-time route (v21_mlp_jit) in the same precision.  Without the call nothing changes.
+ *   v21_route_jacobian_rt  the route of a handle that asked and has its kernel: 3 where the stack can have one and the
+ *     flags allow it, else v21_route_jacobian's answer (which never says 3: it knows no handle).  Pure host logic.
+ *   V21_FWD_FORCE_JIT on any Jacobian-side call (diagnostics): route 3 or V21_ERR_UNSUPPORTED (an ineligible stack, a
+ *     kernel that needs scratch memory, a y pitch of 2^21 floats or more) -- asks, waits for the compilation, and works
+ *     on S1-S4 too.  A forced call ASKS: it opts the handle in for that precision like v21_mlp_jit_jacobian, for good.  v21_jit_prebuild(..., precision | 32, dir) compiles the kernel ahead of time.
+ * n = 0 is a no-op.  The _dev forms are asynchronous on the
  * context's stream; the host forms return when the results are in place.  v21_mlp_last_jac_route: the route of the
  * last call and the calls per route (counts[4], indexed by route). */
 int v21_mlp_jacobian(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, float* y, float* jac, int precision, int flags);
@@ -218,6 +234,8 @@ int v21_mlp_loglike(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, float* 
 int v21_mlp_loglike_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, float* d_lnl, float* d_grad, int precision,
                         int flags);
 int v21_route_jacobian(int n_layers, const int* dims, const int* act, int precision, int64_t n, int flags, int* route);
+int v21_route_jacobian_rt(int n_layers, const int* dims, const int* act, int precision, int flags, int* route);
+int v21_mlp_jit_jacobian(v21_mlp* mlp, int precision, int wait_ms, int* status);
 int v21_mlp_last_jac_route(v21_mlp* mlp, int* route, long long counts[4]);
 
 /* ---- forward-only log-likelihood: lnl[n] = -1/2 sum_k w_k (d_k - y_k)^2 WITHOUT its gradient -- the call nested
