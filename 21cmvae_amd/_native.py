@@ -206,6 +206,9 @@ SIGNATURES = {
     "v21_mlp_loglike_fwd_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_int]),
     "v21_route_loglike_fwd": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                         C.POINTER(C.c_int)]),
+    "v21_route_loglike_fwd_rt": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                           C.POINTER(C.c_int)]),
+    "v21_mlp_jit_loglike": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "v21_mlp_last_lnl_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "v21_mlp_fisher": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, _F, _F, C.c_int, C.c_int]),
     "v21_mlp_fisher_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int]),
@@ -230,6 +233,8 @@ SIGNATURES = {
                                               C.c_int, C.c_int]),
     "v21_route_ensemble": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "v21_route_ensemble_rt": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "v21_mlp_sample_nested": (C.c_int, [_P, _P, C.c_int, C.c_int64, _F, C.c_int64, C.POINTER(NestedOpts), C.POINTER(NestedOut), C.c_int,
                                         C.c_int]),
     "v21_mlp_sample_nested_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(NestedOpts), C.POINTER(NestedOut),
@@ -306,7 +311,10 @@ def route_jacobian_rt(dims, act, precision, flags=0):
     return JAC_ROUTES[r.value]
 
 
-LNL_ROUTES = {1: "fused", 2: "two_launch"}
+LNL_ROUTES = {1: "fused", 2: "two_launch"}   # what a route query without a handle can answer
+# ... and what a handle can record (last_lnl_route) and the _rt queries answer: route 3 is the fused kernel instantiated for
+# the handle's own stack at run time, only for a handle that asked (Stack.jit_loglike)
+LNL_ROUTES_RT = {1: "fused", 2: "two_launch", 3: "fused_rt"}
 
 
 def route_loglike_fwd(dims, act, precision, n, n_data=0, n_modes=0, flags=0):
@@ -316,6 +324,25 @@ def route_loglike_fwd(dims, act, precision, n, n_data=0, n_modes=0, flags=0):
     check(load_library().v21_route_loglike_fwd(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_modes),
                                                int(flags), C.byref(r)))
     return LNL_ROUTES[r.value]
+
+
+def route_loglike_fwd_rt(dims, act, precision, n, n_data=0, n_modes=0, flags=0):
+    """route_loglike_fwd for a handle that asked for its run-time ln L kernel (Stack.jit_loglike) and has it: "fused_rt"
+    where a compiled stack would say "fused" and this stack can have the kernel, else route_loglike_fwd's answer (pure
+    host logic: no GPU).  -> name of LNL_ROUTES."""
+    r = C.c_int(0)
+    check(load_library().v21_route_loglike_fwd_rt(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_modes),
+                                                  int(flags), C.byref(r)))
+    return LNL_ROUTES_RT[r.value]
+
+
+def route_ensemble_rt(dims, act, precision, n, n_walkers, n_data=0, n_modes=0, flags=0, host_form=False):
+    """route_ensemble -- and, with n_live for n_walkers, route_nested -- for a handle that asked for its run-time ln L kernel
+    and has it (pure host logic: no GPU).  -> (name of LNL_ROUTES, chunk rows)."""
+    r, c = C.c_int(0), C.c_int64(0)
+    check(load_library().v21_route_ensemble_rt(*_layers(dims, act), precision_id(precision), int(n), int(n_data), int(n_walkers),
+                                               int(n_modes), int(flags), 1 if host_form else 0, C.byref(r), C.byref(c)))
+    return LNL_ROUTES_RT[r.value], int(c.value)
 
 
 def route_ensemble(dims, act, precision, n, n_walkers, n_data=0, n_modes=0, flags=0, host_form=False):
@@ -859,6 +886,15 @@ class Stack(_Owned):
         check(self.lib.v21_mlp_jit_jacobian(self.h, precision_id(precision), int(wait_ms), C.byref(s)))
         return "ready" if s.value == 1 else "compiling"
 
+    def jit_loglike(self, precision="f32", wait_ms=-1):
+        """Ask for the fused forward-only ln L kernel of THIS stack (include/v21.h: v21_mlp_jit_loglike) and wait up to
+        `wait_ms` (< 0: until compiled).  -> "ready" / "compiling"; raises EngineError when the stack cannot have one.
+        Opt-in: once it is ready every loglike_fwd, sample_ensemble and sample_nested call of this stack in `precision`
+        whose data layout the fused route serves takes the "fused_rt" route."""
+        s = C.c_int(0)
+        check(self.lib.v21_mlp_jit_loglike(self.h, precision_id(precision), int(wait_ms), C.byref(s)))
+        return "ready" if s.value == 1 else "compiling"
+
     def forward(self, x, precision="f32", flags=0):
         """host (n, in) float32/float64 -> host (n, out) float32"""
         x, dt = self._rows(x)
@@ -979,7 +1015,7 @@ class Stack(_Owned):
 
     def last_lnl_route(self):
         """(route name of the last loglike_fwd / loglike_fwd_dev call, {route name: calls since creation})."""
-        (last,), (counts,) = _last_route(self.lib.v21_mlp_last_lnl_route, self.h, [LNL_ROUTES], slots=4)
+        (last,), (counts,) = _last_route(self.lib.v21_mlp_last_lnl_route, self.h, [LNL_ROUTES_RT], slots=4)
         return last, counts
 
     def route_loglike_fwd(self, precision, n, n_data=0, flags=0):
@@ -1364,6 +1400,11 @@ def jit_prebuild_train(dims, act, precision, directory=None):
 def jit_prebuild_jacobian(dims, act, precision, directory=None):
     """jit_prebuild for the fused JACOBIAN kernel of (dims, act, precision) (include/v21.h: v21_mlp_jit_jacobian)."""
     _prebuild(dims, act, precision_id(precision) | 32, directory)
+
+
+def jit_prebuild_loglike(dims, act, precision, directory=None):
+    """jit_prebuild for the fused forward-only ln L kernel of (dims, act, precision) (include/v21.h: v21_mlp_jit_loglike)."""
+    _prebuild(dims, act, precision_id(precision) | 64, directory)
 
 
 def jit_prebuild(dims, act, precision, directory=None):

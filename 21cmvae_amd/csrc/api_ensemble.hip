@@ -34,14 +34,14 @@ static int ensemble_shape(int W, int din, long long n, bool has_data, long long 
 }
 
 int ens_route_query(const char* what, int n_layers, const int* dims, const int* act, int precision, long long n, long long n_data, int G,
-                    int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows, const std::function<int()>& shape) {
+                    int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows, const std::function<int()>& shape, bool rt) {
   CHK(route_query_args(route, n_layers, dims, act, precision));
   if (n < 0 || n_data < 0 || n_modes < 0 || n_modes > 8) return fail(V21_ERR_ARG, "n = %lld, n_data = %lld, n_modes = %d", n, n_data, n_modes);
   if (dims[0] > kFitMaxIn) return fail(V21_ERR_UNSUPPORTED, "%s: %d inputs (at most %d)", what, dims[0], kFitMaxIn);
   CHK(call_data_args(what, n, n_data > 0, n_data));
   CHK(shape());
   const EnsRoute r = decide_ensemble(jac_fused_compiled(n_layers, dims, act), dims[0], n_modes, n_data > 0 ? n / n_data : 0, n, G, flags & 0xFF,
-                                     host_form != 0, kJacHostChunk);
+                                     host_form != 0, kJacHostChunk, rt && v21::jit_lnl_eligible(n_layers, dims, act, nullptr));
   *route = r.route;
   if (chunk_rows) *chunk_rows = r.chunk;
   return V21_OK;
@@ -52,8 +52,18 @@ extern "C" int v21_route_ensemble(int n_layers, const int* dims, const int* act,
                          [&] { return ensemble_shape(n_walkers, dims[0], n, n_data > 0, n_data); });
 }
 
-EnsRoute ens_route(v21_mlp* m, long long rpd, long long n, int G, int flags, bool host_form) {
-  const EnsRoute r = decide_ensemble(m->fused_id >= 0, m->dims[0], m->nu_k, rpd, n, G, flags, host_form, kJacHostChunk);
+// ... and of a handle that asked for its run-time ln L kernel and has it (v21_mlp_jit_loglike): route 3 where the stack can
+// have one.  The nested sampler's query is this one with n_live in the place of n_walkers (decide_ensemble reads no more
+// of G than the chunk arithmetic).
+extern "C" int v21_route_ensemble_rt(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
+                                     int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows) {
+  return ens_route_query("sample_ensemble", n_layers, dims, act, precision, n, n_data, n_walkers, n_modes, flags, host_form, route, chunk_rows,
+                         [&] { return ensemble_shape(n_walkers, dims[0], n, n_data > 0, n_data); }, true);
+}
+
+EnsRoute ens_route(v21_mlp* m, int precision, long long rpd, long long n, int G, int flags, bool host_form) {
+  const EnsRoute r = decide_ensemble(m->fused_id >= 0, m->dims[0], m->nu_k, rpd, n, G, flags, host_form, kJacHostChunk,
+                                     lnl_rt_ready(m, precision));
   m->last_lnl_route = r.route;
   m->lnl_route_count[r.route] += 1;
   return r;
@@ -118,7 +128,7 @@ extern "C" int v21_mlp_sample_ensemble_dev(v21_mlp* m, const float* d_x0, int64_
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
-  const EnsRoute r = ens_route(m, d_data ? data.rpd : 0, n, o.n_walkers, flags, false);
+  const EnsRoute r = ens_route(m, precision, d_data ? data.rpd : 0, n, o.n_walkers, flags, false);
   CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 1));
   return ensemble_run(m, r.route, n, n, data, 0, o, o.chain0, precision, flags, *out, V21_DTYPE_F32);
 }
@@ -135,7 +145,7 @@ extern "C" int v21_mlp_sample_ensemble(v21_mlp* m, const void* x0, int x_dtype, 
   if (n == 0) return V21_OK;
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
-  const EnsRoute r = ens_route(m, data ? cd.rpd : 0, n, o.n_walkers, flags, true);
+  const EnsRoute r = ens_route(m, precision, data ? cd.rpd : 0, n, o.n_walkers, flags, true);
   ChunkStage sg;
   v21_ensemble_out d{};
   stage_sampler_out(sg, *out, d, sample_keep(o.n_steps, o.thin), m->dims[0], x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float));

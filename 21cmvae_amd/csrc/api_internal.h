@@ -261,6 +261,10 @@ struct v21_mlp {
   // forward-only ln L (api_loglike.hip; routes.h: LnlRoute): the route of the last call and the calls per route
   int last_lnl_route = 0;
   long long lnl_route_count[4] = {0, 0, 0, 0};
+  // fused_fwd<this stack, precision's ln L traits> instantiated at run time (jit.h: kJitLnl), only for a handle that
+  // ASKED (v21_mlp_jit_loglike): routes.h LNL_FUSED_RT
+  v21::JitKernel* lnl_jit[3] = {nullptr, nullptr, nullptr};
+  bool lnl_jit_asked[3] = {false, false, false};
 };
 // the layout of this stack's chain streams in `fmt`
 static inline ChainLayout chain_layout(const v21_mlp* m, ChainFmt fmt) {
@@ -327,6 +331,11 @@ int nuis_project(v21_mlp* m, const float* d_data, long long n_data, const float*
 // context's stream
 int lnl_run(v21_mlp* m, int route, const float* d_x, long long ldx, long long n, long long n_call, const CallData& cd, long long row0,
             float* d_lnl, int prec, int flags);
+// whether a call of this handle in `precision` may take LNL_FUSED_RT: the handle asked (v21_mlp_jit_loglike), the code
+// object is there (never waited for here) AND loaded on the context's device -- one that cannot be loaded or needs scratch
+// memory is marked failed by the load, so this call and every later one decide as a handle that never asked, before
+// anything of the call has run.  Asked once per entry-point call, with the context's device current.
+bool lnl_rt_ready(v21_mlp* m, int precision);
 // api_sample.hip, shared with api_ensemble.hip: the ranges of the counts in the options of entry `what` (V21_ERR_ARG),
 // and the states a row stores
 int sample_counts(const char* what, int n_steps, int n_warmup, int thin, long long chain0, long long step0);
@@ -340,8 +349,8 @@ int whole_groups(const char* what, const char* noun, long long n, int G, bool pe
 // reserves the n / 2 pending proposals (m->ens_prop: on u) and their ln L (m->ens_lnl) of the n rows at row0 of a call of
 // n_call rows, with the call's data in the proposals' compacted layout; run() evaluates them once (lnl_run)
 int ens_route_query(const char* what, int n_layers, const int* dims, const int* act, int precision, long long n, long long n_data, int G,
-                    int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows, const std::function<int()>& shape);
-EnsRoute ens_route(v21_mlp* m, long long rpd, long long n, int G, int flags, bool host_form);
+                    int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows, const std::function<int()>& shape, bool rt = false);
+EnsRoute ens_route(v21_mlp* m, int precision, long long rpd, long long n, int G, int flags, bool host_form);
 struct HalfEval {
   float *prop, *lnl; long long half, n_call, row0; CallData hd; int route, prec, flags;
   int run(v21_mlp* m) const { return lnl_run(m, route, prop, m->dims[0], half, n_call, hd, row0, lnl, prec, flags); }

@@ -106,7 +106,7 @@ extern "C" int v21_mlp_sample_nested_dev(v21_mlp* m, const float* d_x0, int64_t 
   if (n == 0) return V21_OK;
   CallData data;
   CHK(call_data(m, n, d_data, false, n_data, &data));
-  const EnsRoute r = ens_route(m, d_data ? data.rpd : 0, n, o.n_live, flags, false);
+  const EnsRoute r = ens_route(m, precision, d_data ? data.rpd : 0, n, o.n_live, flags, false);
   if (d_x0) CHK(jac_prep(m, d_x0, V21_DTYPE_F32, ldx, n, 0));  // (the rows at pitch in_dim)
   return nested_run(m, r.route, d_x0 ? m->jxt.get() : nullptr, n, n, data, 0, o, o.chain0, precision, flags, *out, V21_DTYPE_F32);
 }
@@ -122,7 +122,7 @@ extern "C" int v21_mlp_sample_nested(v21_mlp* m, const void* x0, int x_dtype, in
   if (n == 0) return V21_OK;
   CallData cd;
   CHK(call_data(m, n, data, true, n_data, &cd));
-  const EnsRoute r = ens_route(m, data ? cd.rpd : 0, n, o.n_live, flags, true);
+  const EnsRoute r = ens_route(m, precision, data ? cd.rpd : 0, n, o.n_live, flags, true);
   const int din = m->dims[0], N = o.n_live, k = N / 2;
   const long long T = o.n_iter;
   const size_t esz = x_dtype == V21_DTYPE_F64 ? sizeof(double) : sizeof(float);

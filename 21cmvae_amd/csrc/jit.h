@@ -39,6 +39,18 @@ hipError_t jit_launch_jac(JitKernel* k, int device, const JacArgs& a, hipStream_
 // load a ready kernel's code object on `device` now (what the first launch would do): a route is decided on a kernel that
 // can be launched, not on one that turns out to need scratch memory half way through a call
 hipError_t jit_preload(JitKernel* k, int device);
+// K19: `prec | kJitLnl` (f32 / f16 / bf16) asks for the ln L variant of the fused FORWARD kernel of the stack
+// (fused_fwd<Arch, PrecF32Lnl | PrecF16x2spLnl | PrecBF16x2spLnl>: chi-square reduced in the output layer's epilogue, 4 bytes
+// per row): a fourth kind in the same registry, caches and compiler process, on the forward's own source blob (the
+// spec, "lnl_...", and the traits' name tell the objects apart; the forward objects' cache keys do not move).  Launch
+// geometry: FamilyLnl's; never `wide`.
+constexpr int kJitLnl = 64;
+// every static_assert of fused_fwd.h a stack could trip in the ln L variant, by name: today jit_eligible's list (the
+// variant's own two -- one column tile per wave, at most 32 output tiles -- hold for the three forms above and every
+// output layer up to jit_eligible's 1,024), so that no hiprtc log reaches a user
+bool jit_lnl_eligible(int L, const int* dims, const int* act, std::string* why);
+// as jit_launch, for a kernel of the ln L kind only (hipErrorInvalidValue for any other kind; jit_launch refuses this one)
+hipError_t jit_launch_lnl(JitKernel* k, int device, const FusedArgs& a, hipStream_t st);
 
 // false (with a reason) for stacks fused_fwd cannot express: a non-linear output layer, a variational head, > 16 layers
 bool jit_eligible(int L, const int* dims, const int* act, std::string* why);

@@ -1,8 +1,8 @@
 // jit.hip -- run-time instantiation of fused_fwd<Arch, Prec> -- and, r5, of the fused training kernel
-// fused_train16<Arch, Prec>, and, K18, of the fused Jacobian kernel fused_jac<Arch, Prec> -- through hiprtc (see jit.h).
-// A kernel's KIND rides in bits 4 and 5 of the precision argument of the internal interface (kJitTrain16 | V21_PREC_F16,
-// kJitJac | V21_PREC_F32 ...), so that the registry, the cache and the compiler process (v21_jitc -> v21_jit_prebuild)
-// serve all three with the same code.
+// fused_train16<Arch, Prec>, K18, of the fused Jacobian kernel fused_jac<Arch, Prec>, and, K19, of fused_fwd's ln L
+// variant -- through hiprtc (see jit.h).  A kernel's KIND rides in bits 4 to 6 of the precision argument of the internal
+// interface (kJitTrain16 | V21_PREC_F16, kJitJac | V21_PREC_F32, kJitLnl | V21_PREC_F16 ...), so that the registry, the
+// cache and the compiler process (v21_jitc -> v21_jit_prebuild) serve all four with the same code.
 #include "jit.h"
 #include "fused_families.h"
 
@@ -43,8 +43,10 @@ const unsigned char kJacSrc[] = {
     0};
 inline bool is_train(int prec) { return (prec & kJitTrain16) != 0; }
 inline bool is_jac(int prec) { return (prec & kJitJac) != 0; }
+inline bool is_lnl(int prec) { return (prec & kJitLnl) != 0; }
+constexpr int kKindBits = kJitTrain16 | kJitJac | kJitLnl;
 inline int base_prec(int prec) { return prec & 15; }
-// the embedded sources of a kernel's kind
+// the embedded sources of a kernel's kind (the ln L variant is fused_fwd.h's own: the forward's blob)
 struct Blob { const unsigned char* p; size_t n; };
 inline Blob kind_src(int prec) {
   if (is_train(prec)) return Blob{kTrainSrc, sizeof(kTrainSrc)};
@@ -122,6 +124,8 @@ const char* prec_type(int prec, bool wide) {
   if (is_train(prec)) return base_prec(prec) == 1 ? "PrecF16t16" : "PrecBF16t16";
   // (the Jacobian kernels exist in the forms the compiled S1-S4 launchers use only: never `wide`)
   if (is_jac(prec)) return base_prec(prec) == 0 ? "PrecF32" : (base_prec(prec) == 1 ? "PrecF16x2sp" : "PrecBF16x2sp");
+  // (... and the ln L variants: one column tile per wave)
+  if (is_lnl(prec)) return base_prec(prec) == 0 ? "PrecF32Lnl" : (base_prec(prec) == 1 ? "PrecF16x2spLnl" : "PrecBF16x2spLnl");
   return prec == 0 ? "PrecF32" : (prec == 1 ? (wide ? "PrecF16" : "PrecF16x2sp") : (wide ? "PrecBF16" : "PrecBF16x2sp"));
 }
 // LDS read-ahead (fragments) of a run-time training kernel: the template's default (V21_TRAIN16_DEPTH = 4) unless the loss
@@ -140,6 +144,8 @@ template <class F, class P> constexpr Launch launch_of() { return Launch{F::temp
 Launch launch_geometry(int prec, bool wide) {
   if (is_jac(prec))
     return base_prec(prec) == 0 ? launch_of<FamilyJac, PrecF32>() : (base_prec(prec) == 1 ? launch_of<FamilyJac, PrecF16x2sp>() : launch_of<FamilyJac, PrecBF16x2sp>());
+  if (is_lnl(prec))
+    return base_prec(prec) == 0 ? launch_of<FamilyLnl, PrecF32Lnl>() : (base_prec(prec) == 1 ? launch_of<FamilyLnl, PrecF16x2spLnl>() : launch_of<FamilyLnl, PrecBF16x2spLnl>());
   if (is_train(prec)) return base_prec(prec) == 1 ? launch_of<FamilyTrain16, PrecF16t16>() : launch_of<FamilyTrain16, PrecBF16t16>();
   if (prec == 0) return launch_of<FamilyFwd, PrecF32>();
   if (prec == 1) return wide ? launch_of<FamilyFwd, PrecF16>() : launch_of<FamilyFwd, PrecF16x2sp>();
@@ -287,7 +293,7 @@ struct Registry {
 Registry g_reg;
 
 std::string make_spec(int L, const int* dims, const int* act, int prec, bool wide) {
-  std::string s = is_train(prec) ? "train16_" : (is_jac(prec) ? "jac_" : "");
+  std::string s = is_train(prec) ? "train16_" : (is_jac(prec) ? "jac_" : (is_lnl(prec) ? "lnl_" : ""));
   if (is_train(prec) && train_depth(L, dims) != V21_TRAIN16_DEPTH) s += "d" + std::to_string(train_depth(L, dims)) + "_";
   for (int l = 0; l <= L; ++l) s += (l ? "x" : "") + std::to_string(dims[l]);
   s += "_a";
@@ -388,7 +394,7 @@ void finish(JitKernel* k, int state, const std::string& why) {
   k->cv.notify_all();
 }
 void fill(JitKernel* k, int L, const int* dims, const int* act, int prec) {
-  k->L = L; k->prec = prec; k->wide = jit_wide() && !is_jac(prec);
+  k->L = L; k->prec = prec; k->wide = jit_wide() && !is_jac(prec) && !is_lnl(prec);
   for (int l = 0; l <= L; ++l) k->dims[l] = dims[l];
   for (int l = 0; l < L; ++l) k->act[l] = act[l];
   k->spec = make_spec(L, dims, act, prec, k->wide);
@@ -422,6 +428,17 @@ bool jit_jac_eligible(int L, const int* dims, const int* act, std::string* why) 
   return true;
 }
 
+// fused_fwd<ArchRT, Prec...Lnl> for this stack.  The variant adds two static_asserts to the forward's (fused_fwd.h: CT == 1,
+// which the three ln L forms satisfy by construction, and at most 32 output tiles, which jit_eligible's 1,024-wide limit
+// implies); the smooth hidden-layer epilogue and the ln L output epilogue are separate branches of the template.  So the
+// list is jit_eligible's -- kept as a function of its own so that a rule the variant gains later is named HERE and no
+// hiprtc log reaches a user.  What does not fit a wave's registers spills and is refused when it is loaded.
+bool jit_lnl_eligible(int L, const int* dims, const int* act, std::string* why) {
+  if (!jit_eligible(L, dims, act, why)) return false;
+  if ((dims[L] + 31) / 32 > 32) { if (why) *why = "the fused ln L epilogue takes at most 32 output tiles"; return false; }
+  return true;
+}
+
 // The fused training kernel on 16 rows per wave (fused_train16.h) for a stack outside archs.h.  What the template's own
 // static_asserts and its register budget allow: a linear output layer, ReLU / linear hidden layers, no variational head,
 // 2 .. 8 layers up to 512 wide (the chain kernel's limit: the trainer falls back to it), at most 44 ReLU mask tile pairs,
@@ -446,15 +463,17 @@ bool jit_train_eligible(int L, const int* dims, const int* act, std::string* why
 
 // a kernel argument of the internal interface: one kind bit at most over a base precision that kind has, and a stack it takes
 static bool kind_ok(int L, const int* dims, const int* act, int prec, std::string* why) {
-  if (prec < 0 || (prec & ~(15 | kJitTrain16 | kJitJac)) || (is_train(prec) && is_jac(prec))) return false;
+  const int kind = prec & kKindBits;
+  if (prec < 0 || (prec & ~(15 | kKindBits)) || (kind & (kind - 1))) return false;
   if (is_train(prec)) return (base_prec(prec) == 1 || base_prec(prec) == 2) && jit_train_eligible(L, dims, act, why);
   if (base_prec(prec) > 2) return false;
+  if (is_lnl(prec)) return jit_lnl_eligible(L, dims, act, why);
   return is_jac(prec) ? jit_jac_eligible(L, dims, act, why) : jit_eligible(L, dims, act, why);
 }
 
 JitKernel* jit_request(int L, const int* dims, const int* act, int prec) {
   if (!kind_ok(L, dims, act, prec, nullptr)) return nullptr;
-  const std::string spec = make_spec(L, dims, act, prec, jit_wide() && !is_jac(prec));
+  const std::string spec = make_spec(L, dims, act, prec, jit_wide() && !is_jac(prec) && !is_lnl(prec));
   std::lock_guard<std::mutex> lk(g_reg.mu);
   auto it = g_reg.all.find(spec);
   if (it != g_reg.all.end()) return it->second;
@@ -562,7 +581,13 @@ hipError_t jit_launch_jac(JitKernel* k, int device, const JacArgs& a, hipStream_
   // FamilyJac::rows: jac_group_of(in_dim) virtual rows per row of the call (fused_jac.h)
   return jit_launch_any(k, device, &copy, a.n_rows * jac_group_of(k->dims[0]), st);
 }
+hipError_t jit_launch_lnl(JitKernel* k, int device, const FusedArgs& a, hipStream_t st) {
+  if (!k || !is_lnl(k->prec)) return hipErrorInvalidValue;
+  FusedArgs copy = a;
+  return jit_launch_any(k, device, &copy, a.n_rows, st);
+}
 hipError_t jit_launch(JitKernel* k, int device, const FusedArgs& a, hipStream_t st) {
+  if (k && (k->prec & kKindBits)) return hipErrorInvalidValue;  // (a forward launch of another kind's kernel)
   FusedArgs copy = a;
   return jit_launch_any(k, device, &copy, a.n_rows, st);
 }

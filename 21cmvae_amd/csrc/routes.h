@@ -406,6 +406,7 @@ enum LnlRoute {
   LNL_NONE = 0,
   LNL_FUSED = 1,  // the ln L variant of fused_fwd<Arch, Prec> (fused_fwd.h: traits with LNL): chi-square reduced in the epilogue
   LNL_TWO = 2,    // the forward on its own route into the likelihood workspace, then lnl_reduce_kernel (reduce_kernels.h)
+  LNL_FUSED_RT = 3,  // route 1's kernel instantiated for this stack at run time (jit.hip: kJitLnl), for a handle that asked (K19)
 };
 constexpr int kLnlWgRows = 128;  // rows per workgroup of the ln L variants: one data row per workgroup
 // fused_compiled: archs.h holds the stack (no ReLU end, no Gauss layer); n_modes: the handle's nuisance modes; rpd: rows
@@ -415,12 +416,17 @@ constexpr int kLnlWgRows = 128;  // rows per workgroup of the ln L variants: one
 inline long long lnl_host_chunk(long long chunk_rows, long long rpd) {
   return rpd > 0 && rpd <= chunk_rows ? chunk_rows / rpd * rpd : chunk_rows;
 }
-inline int decide_loglike_fwd(bool fused_compiled, int in_dim, int n_modes, long long rpd, long long n, int flags) {
+// rt_ready: the handle asked for its run-time ln L kernel (v21_mlp_jit_loglike) and the code object is loaded.  Opt-in, as
+// decide_jacobian's: a handle that never asked -- and every query without a handle -- passes false and gets what it always
+// got.  Route 3 stands exactly where route 1 would for a compiled stack; a stack of archs.h keeps its compiled kernel, and
+// V21_FWD_FORCE_JIT here keeps its meaning: two-launch with the run-time FORWARD inside.
+inline int decide_loglike_fwd(bool fused_compiled, int in_dim, int n_modes, long long rpd, long long n, int flags, bool rt_ready) {
   const bool forced = (flags & (V21_FWD_FORCE_GENERIC | V21_FWD_FORCE_CHAIN | V21_FWD_FORCE_JIT)) != 0;
   const bool tin_ok = !(flags & V21_FWD_IN_TRANSFORM) || in_dim <= 8;
   const bool uniform = rpd == 0 || rpd % kLnlWgRows == 0;  // one data row per workgroup
   const bool range = n / kLnlWgRows < (1ll << 31);         // (32-bit workgroup numbers)
-  return fused_compiled && !forced && tin_ok && n_modes == 0 && uniform && range ? LNL_FUSED : LNL_TWO;
+  if (forced || !tin_ok || n_modes != 0 || !uniform || !range) return LNL_TWO;
+  return fused_compiled ? LNL_FUSED : (rt_ready ? LNL_FUSED_RT : LNL_TWO);
 }
 
 // ---- the ensemble sampler (v21_mlp_sample_ensemble[_dev]): every evaluation of a call scores the n / 2 proposals of one
@@ -433,13 +439,13 @@ inline int decide_loglike_fwd(bool fused_compiled, int in_dim, int n_modes, long
 constexpr int kEnsMaxWalkers = 512;  // an ensemble's two sets are decided and read inside one 256-thread workgroup
 struct EnsRoute { int route; long long chunk; };
 inline EnsRoute decide_ensemble(bool fused_compiled, int in_dim, int n_modes, long long rpd, long long n, int W, int flags, bool host_form,
-                                long long chunk_rows) {
+                                long long chunk_rows, bool rt_ready) {
   EnsRoute r;
-  r.route = decide_loglike_fwd(fused_compiled, in_dim, n_modes, rpd / 2, n / 2, flags & ~V21_FWD_IN_TRANSFORM);
+  r.route = decide_loglike_fwd(fused_compiled, in_dim, n_modes, rpd / 2, n / 2, flags & ~V21_FWD_IN_TRANSFORM, rt_ready);
   r.chunk = n;
   if (!host_form) return r;
   long long unit = W;
-  if (r.route == LNL_FUSED && rpd > 0) {
+  if ((r.route == LNL_FUSED || r.route == LNL_FUSED_RT) && rpd > 0) {  // (the same kernel, the same workgroup boundaries)
     long long a = W, b = 2 * kLnlWgRows;
     while (b) { const long long t = a % b; a = b; b = t; }
     unit = (long long)W / a * (2 * kLnlWgRows);

@@ -422,6 +422,10 @@ class _EmulatorBase:
         if getattr(self, "_derivatives_rt", None) not in (None, (out[1], model.precision)):
             self._ask_derivatives(out[1], model.precision, 0)
             self._derivatives_rt = (out[1], model.precision)
+        # compile_likelihood: the same rule for the forward-only ln L kernel
+        if getattr(self, "_likelihood_rt", None) not in (None, (out[1], model.precision)):
+            self._ask_likelihood(out[1], model.precision, 0)
+            self._likelihood_rt = (out[1], model.precision)
         return out
 
     @staticmethod
@@ -448,6 +452,33 @@ class _EmulatorBase:
         model, st, _, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
         state = self._ask_derivatives(st, model.precision, -1 if wait else 0)
         self._derivatives_rt = None if state == "unsupported" else (st, model.precision)
+        return state
+
+    @staticmethod
+    def _ask_likelihood(st, precision, wait_ms):
+        """Stack.jit_loglike; "unsupported" for a stack the kernel cannot express (the library's "no fused ln L kernel for
+        this stack"); every other failure is raised as it is (_ask_derivatives says why)."""
+        try:
+            return st.jit_loglike(precision, wait_ms)
+        except nat.EngineError as e:
+            if "no fused ln L kernel for this stack" in str(e):
+                return "unsupported"
+            raise
+
+    def compile_likelihood(self, wait=True):
+        """Opt in to the fused forward-only ln L kernel instantiated for THIS emulator's stack at run time (include/v21.h:
+        v21_mlp_jit_loglike): afterwards ``log_likelihood(forward_only=True)``, ``log_posterior``, ``sample_ensemble``
+        and ``nested_sample`` take the "fused_rt" route in the model's precision -- chi-square reduced inside the forward
+        kernel, 4 bytes per row -- instead of the two-launch route, for any ``hidden_dims``, with ReLU or a smooth
+        ``activation_func``, wherever the compiled stacks take "fused" (no ``foreground``; data uniform per 128 rows).
+        wait=True waits for the compilation (seconds, once per stack: the code object is cached on disk).  -> "ready",
+        "compiling", or "unsupported" for a stack the kernel cannot express (a variational head, a non-linear output
+        layer): such an emulator computes as before.  Never raises for an ineligible stack; an eligible stack whose kernel
+        cannot be had (V21_JIT=0 with nothing cached, a compiler failure) raises EngineError with the reason.  A stack
+        rebuilt later (new weights of another shape, another precision) asks again by itself, without waiting."""
+        model, st, _, _ = self._diff_stack(np.zeros((1, len(self.par_labels))))
+        state = self._ask_likelihood(st, model.precision, -1 if wait else 0)
+        self._likelihood_rt = None if state == "unsupported" else (st, model.precision)
         return state
 
     def jacobian(self, params, return_signal=False):

@@ -258,7 +258,30 @@ int v21_mlp_last_jac_route(v21_mlp* mlp, int* route, long long counts[4]);
  *   rounded down to whole spectra when data is given, and returns when the results are in place.
  *   v21_route_loglike_fwd: the route of a call of n rows against n_data data rows (0: the record) for a handle with
  *   n_modes nuisance modes -- pure host logic.  v21_mlp_last_lnl_route: the route of the last of these calls and the
- *   calls per route (counts[4], indexed by route); v21_mlp_last_jac_route is not touched by them. */
+ *   calls per route (counts[4], indexed by route); v21_mlp_last_jac_route is not touched by them.
+ * Route 3 = fused_rt (K19), for a handle that ASKED:
+ *   v21_mlp_jit_loglike  the fused route's kernel instantiated for THIS stack at run time (csrc/jit.h: kJitLnl; ReLU,
+ *     linear and the smooth activations 3 .. 6 on hidden layers, a linear output layer, widths up to 1,024 where the
+ *     registers hold them), semantics as v21_mlp_jit_jacobian: *status 1 ready (also for a compiled-in stack, which
+ *     keeps route 1), 0 compiling, V21_ERR_UNSUPPORTED (status -1) with the reason in v21_last_error -- a stack the
+ *     kernel cannot express, V21_JIT=0 with nothing cached, a compiler failure.  Requested at most once per (handle,
+ *     precision).  It marks the handle as asked for that precision: from the first call that starts with the code
+ *     object in place, every call of v21_mlp_loglike_fwd[_dev], v21_mlp_sample_ensemble[_dev] and
+ *     v21_mlp_sample_nested[_dev] of the handle that would take route 1 on a stack of archs.h -- the same conditions:
+ *     uniform data, no nuisance record, no forward route flag, in_dim <= 8 with the input transform -- takes route 3.  A
+ *     call decides its route once, for all its slices, chunks and evaluations; a kernel that arrives mid-call serves the
+ *     next call; one that cannot be loaded or needs scratch memory (found when the first call after its arrival
+ *     decides its route) leaves the handle on route 2, without an error.  y is the forward's run-time route's
+ *     (v21_mlp_jit) bit for bit.  Without the call nothing changes; V21_FWD_FORCE_JIT here still means route 2 with the
+ *     run-time forward inside.  v21_jit_prebuild(..., precision | 64, dir) compiles the kernel ahead of time.
+ *   v21_route_loglike_fwd_rt / v21_route_ensemble_rt (the nested sampler's: n_live in the place of n_walkers)  the route
+ *     of a handle that asked and has its kernel: 3 where v21_route_loglike_fwd / v21_route_ensemble would say 1 for a
+ *     compiled stack and this stack can have the kernel, else their answer (which never is 3: they know no handle). */
+int v21_mlp_jit_loglike(v21_mlp* mlp, int precision, int wait_ms, int* status);
+int v21_route_loglike_fwd_rt(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_modes,
+                             int flags, int* route);
+int v21_route_ensemble_rt(int n_layers, const int* dims, const int* act, int precision, int64_t n, int64_t n_data, int n_walkers,
+                          int n_modes, int flags, int host_form, int* route, int64_t* chunk_rows);
 int v21_mlp_loglike_fwd(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, const float* data, int64_t n_data, float* lnl,
                         int precision, int flags);
 int v21_mlp_loglike_fwd_dev(v21_mlp* mlp, const float* d_x, int64_t ldx, int64_t n, const float* d_data, int64_t n_data,
