@@ -244,6 +244,7 @@ SIGNATURES = {
     "v21_nuisance_whiten": (C.c_int, [C.POINTER(C.c_double), _F, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "v21_mlp_set_nuisance": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, C.c_int32]),
     "v21_mlp_set_prior": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
+    "v21_mlp_set_hold": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32]),
     "v21_mlp_nuisance_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "v21_mlp_nuisance_coef": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int]),
     "v21_trainer_last_route": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -777,7 +778,7 @@ class Stack(_Owned):
         check(self.lib.v21_mlp_num_params(h, C.byref(n)))
         self.num_params = n.value
         # what the device holds, as use_output_stats / use_input_stats / use_likelihood left it (None: nothing, or set directly)
-        self.out_stats = self.in_stats = self.lk_record = self.nu_record = self.prior_record = None
+        self.out_stats = self.in_stats = self.lk_record = self.nu_record = self.prior_record = self.hold_record = None
 
     def set_weights(self, flat):
         flat = np.ascontiguousarray(flat, dtype=np.float32).ravel()
@@ -859,6 +860,20 @@ class Stack(_Owned):
         if rec is None or not all(np.array_equal(a, b) for a, b in zip(rec, new)):
             self.set_prior(*new)
             self.prior_record = new
+
+    def use_hold(self, hold):
+        """set_hold(hold, u) from a (hold, u) pair (None: nothing held), set only when it changed; kept on the host by
+        value as `hold_record`"""
+        rec = self.hold_record
+        if hold is None:
+            if rec is not None:
+                self.set_hold(None)
+                self.hold_record = None
+            return
+        new = (np.array(hold[0], np.int32), np.array(hold[1], np.float64))
+        if rec is None or not all(np.array_equal(a, b) for a, b in zip(rec, new)):
+            self.set_hold(*new)
+            self.hold_record = new
 
     def has_fused(self, precision="f32"):
         y = C.c_int(0)
@@ -968,6 +983,23 @@ class Stack(_Owned):
                 raise ValueError("set_prior: kind, mu and sd must have one entry per input column")
         dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
         check(self.lib.v21_mlp_set_prior(self.h, kind.ctypes.data_as(C.POINTER(C.c_int32)), dp(mu), dp(sd), kind.size))
+
+    def set_hold(self, hold, u=None):
+        """The samplers' held columns in the transformed coordinates u (include/v21.h: v21_mlp_set_hold): per input column
+        hold 0 (sampled) or 1 (held at u, rounded to float32 once in the library); copied.  None, or nothing held, clears.
+        The four samplers read the record; the fits, fisher and loglike do not."""
+        self.hold_record = None
+        if hold is None:
+            check(self.lib.v21_mlp_set_hold(self.h, None, None, 0))
+            return
+        hold = np.ascontiguousarray(hold, dtype=np.int32).ravel()
+        u = None if u is None else np.ascontiguousarray(u, dtype=np.float64).ravel()
+        if u is not None and u.size != hold.size:
+            raise ValueError("set_hold: hold and u must have one entry per input column")
+        if u is None and hold.any():
+            raise ValueError("set_hold: a held column needs its u")
+        check(self.lib.v21_mlp_set_hold(self.h, hold.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        None if u is None else u.ctypes.data_as(C.POINTER(C.c_double)), hold.size))
 
     def nuisance_modes(self):
         """the number of nuisance modes the library holds for this stack (0: none)"""

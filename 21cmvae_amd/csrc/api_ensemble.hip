@@ -100,18 +100,30 @@ static int ensemble_run(v21_mlp* m, int route, long long n, long long n_call, co
   const dim3 grid((unsigned)((ensembles + a.epw - 1) / a.epw));
   // (samples and x_last are of x_dtype, the prior record (api_prior.hip) is there or not: one set of instantiations,
   // picked once)
-  const bool f64 = x_dtype == V21_DTYPE_F64, pri = m->has_prior;
-  const auto step = pri ? (f64 ? ensemble_step_kernel<double, true> : ensemble_step_kernel<float, true>)
-                        : (f64 ? ensemble_step_kernel<double, false> : ensemble_step_kernel<float, false>);
-  const auto finish = f64 ? ensemble_finish_kernel<double> : ensemble_finish_kernel<float>;
+  // ... and so is the hold record (api_hold.hip), which the HOLD instantiations take as their last argument
+  const SamplerRecords rec = sampler_records(m);
+  const bool f64 = x_dtype == V21_DTYPE_F64, pri = rec.pri;
+  const auto step = pri ? (f64 ? ensemble_step_kernel<double, true, false> : ensemble_step_kernel<float, true, false>)
+                        : (f64 ? ensemble_step_kernel<double, false, false> : ensemble_step_kernel<float, false, false>);
+  const auto finish = f64 ? ensemble_finish_kernel<double, false> : ensemble_finish_kernel<float, false>;
+  const auto step_h = pri ? (f64 ? ensemble_step_kernel<double, true, true, HoldArgs> : ensemble_step_kernel<float, true, true, HoldArgs>)
+                          : (f64 ? ensemble_step_kernel<double, false, true, HoldArgs> : ensemble_step_kernel<float, false, true, HoldArgs>);
+  const auto finish_h = f64 ? ensemble_finish_kernel<double, true, HoldArgs> : ensemble_finish_kernel<float, true, HoldArgs>;
   const long long last = 2 * a.total + 2;
   for (long long k = 0; k <= last; ++k) {
     if (k > 0) CHK(ev.run(m));
-    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), ev.prop, (const float*)ev.lnl, k, a, m->prior);
+    if (rec.hold)
+      hipLaunchKernelGGL(step_h, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), ev.prop, (const float*)ev.lnl, k, a, rec.pr, rec.ho);
+    else
+      hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, (const float*)m->jxt.get(), ev.prop, (const float*)ev.lnl, k, a, rec.pr);
     HIPCHK(hipGetLastError());
   }
   EnsOutDev od{out.x_last, out.lnl_last, out.accept_rate, out.mean_u, out.cov_u, out.last_log_alpha, out.last_partner};
-  hipLaunchKernelGGL(finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const EnsRow*)rows, n, din, (long long)o.n_steps, m->tin, od);
+  if (rec.hold)
+    hipLaunchKernelGGL(finish_h, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const EnsRow*)rows, n, din, (long long)o.n_steps, m->tin,
+                       od, rec.ho);
+  else
+    hipLaunchKernelGGL(finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const EnsRow*)rows, n, din, (long long)o.n_steps, m->tin, od);
   HIPCHK(hipGetLastError());
   return V21_OK;
 }

@@ -240,6 +240,11 @@ struct v21_mlp {
   // (has_prior false: never set, cleared, or every column uniform) they run their PRIOR = false instantiations
   bool has_prior = false;
   PriorArgs prior{};
+  // the samplers' hold record (api_hold.hip: v21_mlp_set_hold), as their init, step and finish kernels take it by value;
+  // without one (has_hold false: never set, cleared, or nothing held) they run their HOLD = false instantiations, which
+  // take no such argument.  Read by the four samplers' launch sites alone (through SamplerRecords)
+  bool has_hold = false;
+  HoldArgs hold{};
   // linear nuisance modes marginalised in those reductions (api_nuisance.hip): nu_k modes (0: none), the float64 basis
   // as it was handed in, the record built from it, and the host copy of the likelihood record both are re-whitened from.
   // On the device: Q in float32 (the reductions) and float64 (nuis_project_kernel), the record's projected data BESIDE
@@ -266,6 +271,27 @@ struct v21_mlp {
   v21::JitKernel* lnl_jit[3] = {nullptr, nullptr, nullptr};
   bool lnl_jit_asked[3] = {false, false, false};
 };
+// what a sampler's launch site hands its kernels: the hold record (hold: there is one) and the prior record with the
+// held normal columns made uniform -- a held column is no parameter, its prior is never read: FitMapArgs::free_prior's
+// rule (fit_kernels.h) applied on the host -- (pri: a free normal column is left)
+struct SamplerRecords {
+  bool pri, hold;
+  PriorArgs pr;
+  HoldArgs ho;
+};
+static inline SamplerRecords sampler_records(const v21_mlp* m) {
+  SamplerRecords r{m->has_prior, m->has_hold, m->prior, m->hold};
+  if (!r.hold || !r.pri) return r;
+  r.pri = false;
+  for (int i = 0; i < kFitMaxIn; ++i) {
+    if ((r.ho.mask >> i) & 1u) {
+      r.pr.kind[i] = 0;
+      r.pr.mu[i] = r.pr.w[i] = r.pr.wmu[i] = 0.0;
+    }
+    if (r.pr.kind[i]) r.pri = true;
+  }
+  return r;
+}
 // the layout of this stack's chain streams in `fmt`
 static inline ChainLayout chain_layout(const v21_mlp* m, ChainFmt fmt) {
   ChainLayout y;

@@ -64,9 +64,13 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
   const dim3 grid((unsigned)((a.runs + a.rpw - 1) / a.rpw));
   // (dead_u and live_u are of x_dtype, the prior record (api_prior.hip) is there or not: one set of instantiations,
   // picked once)
-  const bool f64 = x_dtype == V21_DTYPE_F64, pri = m->has_prior;
-  const auto step = pri ? (f64 ? nested_step_kernel<double, true> : nested_step_kernel<float, true>)
-                        : (f64 ? nested_step_kernel<double, false> : nested_step_kernel<float, false>);
+  // ... and so is the hold record (api_hold.hip), which the HOLD instantiations take as their last argument
+  const SamplerRecords rec = sampler_records(m);
+  const bool f64 = x_dtype == V21_DTYPE_F64, pri = rec.pri;
+  const auto step = pri ? (f64 ? nested_step_kernel<double, true, false> : nested_step_kernel<float, true, false>)
+                        : (f64 ? nested_step_kernel<double, false, false> : nested_step_kernel<float, false, false>);
+  const auto step_h = pri ? (f64 ? nested_step_kernel<double, true, true, HoldArgs> : nested_step_kernel<float, true, true, HoldArgs>)
+                          : (f64 ? nested_step_kernel<double, false, true, HoldArgs> : nested_step_kernel<float, false, true, HoldArgs>);
   const auto finish = f64 ? nested_finish_kernel<double> : nested_finish_kernel<float>;
   const long long T = o.n_iter, moves = T * a.R;
   // launch 0 passes start half 0 on, 1 takes it and passes half 1 on, 2 takes that and opens iteration 0; launch 3 + mv
@@ -86,7 +90,10 @@ static int nested_run(v21_mlp* m, int route, const float* d_start, long long n, 
       }
     }
     if (q > 0) CHK(ev.run(m));
-    hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, d_start, ev.prop, (const float*)ev.lnl, l, a, m->prior, dec);
+    if (rec.hold)
+      hipLaunchKernelGGL(step_h, grid, dim3(256), 0, st, rows, d_start, ev.prop, (const float*)ev.lnl, l, a, rec.pr, dec, rec.ho);
+    else
+      hipLaunchKernelGGL(step, grid, dim3(256), 0, st, rows, d_start, ev.prop, (const float*)ev.lnl, l, a, rec.pr, dec);
     HIPCHK(hipGetLastError());
   }
   NestOutDev od{out.live_u, out.live_lnl, out.accept_rate, out.last_partner, out.last_prop_u};

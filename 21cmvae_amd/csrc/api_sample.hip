@@ -5,7 +5,8 @@
 // and the host only launches.  The tempered entries (v21_mlp_sample_tempered[_dev]) run the same loop with
 // sample_step_tempered_kernel in the step kernel's place: T consecutive rows form a ladder of inverse temperatures whose
 // rungs exchange their points inside that kernel.  A handle with a prior record (api_prior.hip) launches the PRIOR
-// instantiations of both step kernels.
+// instantiations of both step kernels, one with a hold record (api_hold.hip) the HOLD instantiations of the init, step
+// and finish kernels, which take the record as one further argument.
 #include "api_internal.h"
 #include "sample_kernels.h"
 
@@ -47,15 +48,27 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   a.seed = o.seed; a.chain0 = (uint64_t)chain0; a.step0 = (uint64_t)o.step0;
   a.samples = out.samples; a.samples_lnl = out.samples_lnl;
   a.t = m->tin;
-  hipLaunchKernelGGL(sample_init_kernel, grid, dim3(256), 0, st, cs, m->jxt.get(), m->jfac.get(), n, din, o.eps0, d_eps_start);
+  // (samples and x_last are of x_dtype, the prior record is there or not, the hold record is there or not: one set of
+  // instantiations, picked once; the HOLD ones take the record as their last argument)
+  const SamplerRecords rec = sampler_records(m);
+  const bool f64 = x_dtype == V21_DTYPE_F64, pri = rec.pri;
+  if (rec.hold)
+    hipLaunchKernelGGL((sample_init_kernel<true, HoldArgs>), grid, dim3(256), 0, st, cs, m->jxt.get(), m->jfac.get(), n, din, o.eps0, d_eps_start,
+                       rec.ho);
+  else
+    hipLaunchKernelGGL(sample_init_kernel<false>, grid, dim3(256), 0, st, cs, m->jxt.get(), m->jfac.get(), n, din, o.eps0, d_eps_start);
   HIPCHK(hipGetLastError());
-  // (samples and x_last are of x_dtype, the prior record is there or not: one set of instantiations, picked once)
-  const bool f64 = x_dtype == V21_DTYPE_F64, pri = m->has_prior;
-  const auto step = pri ? (f64 ? sample_step_kernel<double, true> : sample_step_kernel<float, true>)
-                        : (f64 ? sample_step_kernel<double, false> : sample_step_kernel<float, false>);
-  const auto tstep = pri ? (f64 ? sample_step_tempered_kernel<double, true> : sample_step_tempered_kernel<float, true>)
-                         : (f64 ? sample_step_tempered_kernel<double, false> : sample_step_tempered_kernel<float, false>);
-  const auto finish = f64 ? sample_finish_kernel<double> : sample_finish_kernel<float>;
+  const auto step = pri ? (f64 ? sample_step_kernel<double, true, false> : sample_step_kernel<float, true, false>)
+                        : (f64 ? sample_step_kernel<double, false, false> : sample_step_kernel<float, false, false>);
+  const auto tstep = pri ? (f64 ? sample_step_tempered_kernel<double, true, false> : sample_step_tempered_kernel<float, true, false>)
+                         : (f64 ? sample_step_tempered_kernel<double, false, false> : sample_step_tempered_kernel<float, false, false>);
+  const auto finish = f64 ? sample_finish_kernel<double, false> : sample_finish_kernel<float, false>;
+  const auto step_h = pri ? (f64 ? sample_step_kernel<double, true, true, HoldArgs> : sample_step_kernel<float, true, true, HoldArgs>)
+                          : (f64 ? sample_step_kernel<double, false, true, HoldArgs> : sample_step_kernel<float, false, true, HoldArgs>);
+  const auto tstep_h = pri ? (f64 ? sample_step_tempered_kernel<double, true, true, HoldArgs> : sample_step_tempered_kernel<float, true, true, HoldArgs>)
+                           : (f64 ? sample_step_tempered_kernel<double, false, true, HoldArgs>
+                                  : sample_step_tempered_kernel<float, false, true, HoldArgs>);
+  const auto finish_h = f64 ? sample_finish_kernel<double, true, HoldArgs> : sample_finish_kernel<float, true, HoldArgs>;
   TemperArgs ta{};
   TemperRow* tr = nullptr;
   dim3 tgrid(1);
@@ -70,16 +83,26 @@ static int sample_run(v21_mlp* m, int route, long long n, const CallData& data, 
   }
   for (long long it = 0; it <= a.total; ++it) {
     CHK(reduce_run(m, route, n, F, l, g, nullptr, data.d, data.ld, data.rpd, row0, prec, flags & ~V21_FWD_IN_TRANSFORM));
-    if (tp)
+    if (tp && rec.hold)
+      hipLaunchKernelGGL(tstep_h, tgrid, dim3(256), 0, st, cs, tr, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, ta,
+                         rec.pr, rec.ho);
+    else if (tp)
       hipLaunchKernelGGL(tstep, tgrid, dim3(256), 0, st, cs, tr, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, ta,
-                         m->prior);
+                         rec.pr);
+    else if (rec.hold)
+      hipLaunchKernelGGL(step_h, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, rec.pr,
+                         rec.ho);
     else
-      hipLaunchKernelGGL(step, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, m->prior);
+      hipLaunchKernelGGL(step, grid, dim3(256), 0, st, cs, m->jxt.get(), (const float*)l, (const float*)g, (const float*)F, it, a, rec.pr);
     HIPCHK(hipGetLastError());
   }
   SampleOutDev od{out.x_last, out.lnl_last, out.eps_last, out.accept_rate, out.mean_u, out.cov_u, out.last_prop_u, out.last_log_alpha};
-  hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din, (long long)o.n_steps, m->tin,
-                     od);
+  if (rec.hold)
+    hipLaunchKernelGGL(finish_h, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din, (long long)o.n_steps,
+                       m->tin, od, rec.ho);
+  else
+    hipLaunchKernelGGL(finish, grid, dim3(256), 0, st, (const SampleRow*)cs, (const float*)m->jxt.get(), n, din, (long long)o.n_steps, m->tin,
+                       od);
   HIPCHK(hipGetLastError());
   if (tp && to && (to->mean_lnl || to->var_lnl || to->swap_accept)) {
     hipLaunchKernelGGL(sample_finish_tempered_kernel, grid, dim3(256), 0, st, (const SampleRow*)cs, (const TemperRow*)tr, n,

@@ -22,6 +22,12 @@
 //   log alpha = (din - 1) ln z + ln L(y) - ln L(x)   [PRIOR: + ln p(y) - ln p(x)]
 // No LDS, no atomics; float64 in registers.  Random numbers: Philox4x32-10 of sample_kernels.h, block 0 at step = the
 // sweep: w0 the stretch, w1 the partner, w2 the acceptance uniform.  The prior draws nothing.
+// With a hold record (HOLD; rowmath.h: HoldArgs) the start launches (k < 2) write the held float32 over the start's and
+// the stretch's Jacobian counts the free columns, lz = (d_free - 1) ln z.  The stretch itself needs no change: every
+// walker of an ensemble carries the same float32 x in a held column, xi - xp is exactly 0 there, and x + z 0 rounds
+// to x, so a proposal, and with it every state and stored sample, returns the held value bit for bit.  The launch site
+// hands over the prior record with the held normal columns made uniform; the finish kernel writes the held column's
+// mean_u as the value and its cov_u row and column as exact zeros (hold_finish).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,11 +68,14 @@ struct EnsArgs {
 
 // one thread per (ensemble, j): launch k of the call (above).  start: the transformed start rows (n, din), read by
 // k = 0, 1; prop: the compacted proposals (n / 2, din); lnl_new: their evaluation (n / 2).  XT: the samples' type;
-// PRIOR: the handle holds a prior record, pr (else not read).
-template <class XT, bool PRIOR>
+// PRIOR: the handle holds a prior record, pr (else not read).  HOLD: it holds a hold record; Hold: HoldArgs for HOLD =
+// true, no argument for HOLD = false.
+template <class XT, bool PRIOR, bool HOLD, class... Hold>
 __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const float* __restrict__ start, float* __restrict__ prop,
                                                             const float* __restrict__ lnl_new, long long k, const EnsArgs a,
-                                                            const PriorArgs pr) {
+                                                            const PriorArgs pr, const Hold... hold) {
+  static_assert(sizeof...(Hold) == (HOLD ? 1 : 0), "HOLD takes one HoldArgs, its absence nothing");
+  [[maybe_unused]] const auto& ho = hold_of(hold...);
   constexpr int NI = kFitMaxIn;
   const int din = a.din, H = a.H, W = a.W;
   const int slot = (int)threadIdx.x / H, j = (int)threadIdx.x % H;
@@ -124,6 +133,7 @@ __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const fl
       // the start into the box, the state reset
       const float* x0 = start + row * din;
       for (int i = 0; i < din; ++i) y[i] = box_clamp1(x0[i]);
+      hold_row<HOLD>(ho, din, y);
       s.lnl = 0.f;
       s.reject = 0;
       s.partner = -1;
@@ -150,7 +160,7 @@ __global__ void __launch_bounds__(256) ensemble_step_kernel(EnsRow* st, const fl
       }
       s.reject = inside ? 0 : 1;
       s.partner = prow;
-      s.lz = (double)(din - 1) * log(z);
+      s.lz = (double)(hold_free<HOLD>(ho, din) - 1) * log(z);
 #pragma unroll
       for (int i = 0; i < NI; ++i)
         if (i < din) y[i] = finite ? yf[i] : s.u[i];
@@ -166,15 +176,18 @@ struct EnsOutDev {
   double *accept_rate, *mean_u, *cov_u, *last_log_alpha;
   int* last_partner;
 };
-template <class XT>
+template <class XT, bool HOLD, class... Hold>
 __global__ void __launch_bounds__(256) ensemble_finish_kernel(const EnsRow* __restrict__ st, long long n, int din, long long kept,
-                                                              const v21_affine_in t, const EnsOutDev o) {
+                                                              const v21_affine_in t, const EnsOutDev o, const Hold... hold) {
+  static_assert(sizeof...(Hold) == (HOLD ? 1 : 0), "HOLD takes one HoldArgs, its absence nothing");
+  [[maybe_unused]] const auto& ho = hold_of(hold...);
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   const EnsRow& s = st[row];
   raw_row<XT>(o.x_last, row, din, s.u, t);
   if (o.lnl_last) o.lnl_last[row] = s.lnl;
   s.m.finish(row, din, kept, s.u, o.mean_u, o.cov_u, o.accept_rate);
+  hold_finish<HOLD>(ho, row, din, o.mean_u, o.cov_u);
   if (o.last_log_alpha) o.last_log_alpha[row] = s.log_alpha;
   if (o.last_partner) o.last_partner[row] = s.partner;
 }

@@ -29,6 +29,11 @@
 //                                                 column of a prior record: float(mu + sd z), z the truncated standard
 //                                                 normal's inverse CDF at U(w) (nest_tnorm_z);
 //   block 4, step = that of block 0 (PRIOR only): the prior's acceptance uniform U(w0).
+// With a hold record (HOLD; rowmath.h: HoldArgs) the start section writes the held float32 into given and drawn starts
+// alike; a held column consumes no draw of its own (its word is left unused, the free columns keep theirs).  The
+// difference move needs no change: every live point of a run carries the same float32 x in a held column, x_a - x_b is
+// exactly 0 there and x + gamma 0 is x, bit for bit.  Ranking, shrinkage and the finish kernel are untouched: the prior
+// mass is that of the free columns, whose record the launch site hands over with the held normal columns made uniform.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -85,11 +90,14 @@ __device__ inline double nest_tnorm_z(double a, double b, double U) {
 
 // one thread per (run, j).  start: the start rows (n, din) in u, or nullptr (drawn); prop: the compacted proposals
 // (n / 2, din); lnl_new: their evaluation.  XT: the dead record's type; PRIOR: the handle holds a prior record, pr, and
-// `dec` is the local move a deciding launch decides (neither is read without it).
-template <class XT, bool PRIOR>
+// `dec` is the local move a deciding launch decides (neither is read without it).  HOLD: it holds a hold record; Hold:
+// HoldArgs for HOLD = true, no argument for HOLD = false.
+template <class XT, bool PRIOR, bool HOLD, class... Hold>
 __global__ void __launch_bounds__(256) nested_step_kernel(NestRow* st, const float* __restrict__ start, float* __restrict__ prop,
                                                           const float* __restrict__ lnl_new, const NestLaunch l, const NestArgs a,
-                                                          const PriorArgs pr, const long long dec) {
+                                                          const PriorArgs pr, const long long dec, const Hold... hold) {
+  static_assert(sizeof...(Hold) == (HOLD ? 1 : 0), "HOLD takes one HoldArgs, its absence nothing");
+  [[maybe_unused]] const auto& ho = hold_of(hold...);
   constexpr int NI = kFitMaxIn;
   __shared__ float key[512];
   __shared__ float ls[256 / (kNestMinLive / 2)];
@@ -236,6 +244,7 @@ __global__ void __launch_bounds__(256) nested_step_kernel(NestRow* st, const flo
         }
       }
     }
+    hold_row<HOLD>(ho, din, prop + p * din);
   }
 }
 

@@ -12,6 +12,8 @@
 //   box_to_raw / raw_row    a coordinate, and a row of a result, back to raw units;
 //   PriorArgs               the prior record as the step kernels take it;
 //   prior_logp / prior_eval its ln p, and its gradient and precision added to an evaluation;
+//   HoldArgs / NoHold       the hold record as the samplers' kernels take it (HOLD), and its absence;
+//   hold_eval / hold_row / hold_free / hold_finish  a held column in an evaluation, a row, the count, the results;
 //   Moments                 the bookkeeping of a sampler's kept transitions, the tail of its row state: the sums of u and
 //                           u u^T and the accepted count, the thinned store of a state, the per-row results.
 #pragma once
@@ -55,6 +57,62 @@ __device__ __forceinline__ void prior_eval(const PriorArgs& pr, const double* u,
       if (i < din && pr.kind[i]) {
         g[i] += pr.wmu[i] - pr.w[i] * u[i];
         F[i * kFitMaxIn - i * (i - 1) / 2] += pr.w[i];
+      }
+  }
+}
+
+// ---- the handle's hold record (include/v21.h: v21_mlp_set_hold; api_hold.hip) as the init, step and finish kernels of
+// the four samplers receive it, by value: bit i of mask set = input column i is held at u[i], the float32 every state,
+// proposal and stored sample of that column carries.  A kernel's HOLD = false form takes no such argument (a parameter
+// pack, as fit_lm_kernel's Map): its argument list and its code are what they were.
+struct HoldArgs {
+  unsigned mask;
+  float u[kFitMaxIn];
+  __device__ __forceinline__ bool held(int i) const { return (mask >> i) & 1u; }
+};
+struct NoHold {};
+__device__ __forceinline__ NoHold hold_of() { return {}; }
+__device__ __forceinline__ const HoldArgs& hold_of(const HoldArgs& h) { return h; }
+// a held column i of an evaluation (g, packed F), after the prior's additions: g_i = 0, F_ij = F_ji = 0 (j != i),
+// F_ii = 1 -- the arithmetic of FitMapArgs::system (fit_kernels.h)
+template <bool HOLD, class H>
+__device__ __forceinline__ void hold_eval(const H& ho, int din, double* g, double* F) {
+  if constexpr (HOLD) {
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < kFitMaxIn; ++i) {
+      if (i < din && ho.held(i)) g[i] = 0.0;
+#pragma unroll
+      for (int j = i; j < kFitMaxIn; ++j, ++p)
+        if (j < din && (ho.held(i) || ho.held(j))) F[p] = i == j ? 1.0 : 0.0;
+    }
+  }
+}
+// the held coordinates written over those of a row of din floats
+template <bool HOLD, class H>
+__device__ __forceinline__ void hold_row(const H& ho, int din, float* u) {
+  if constexpr (HOLD) {
+#pragma unroll
+    for (int i = 0; i < kFitMaxIn; ++i)
+      if (i < din && ho.held(i)) u[i] = ho.u[i];
+  }
+}
+// d_free: the columns that are sampled (HOLD = false: din itself)
+template <bool HOLD, class H>
+__device__ __forceinline__ int hold_free(const H& ho, int din) {
+  if constexpr (HOLD) return din - __popc(ho.mask);
+  else return din;
+}
+// a sampler's per-row results after Moments::finish: mean_u of a held column is the held value, its row and column of
+// cov_u exact zeros (both nullable)
+template <bool HOLD, class H>
+__device__ __forceinline__ void hold_finish(const H& ho, long long row, int din, double* mean_u, double* cov_u) {
+  if constexpr (HOLD) {
+    for (int i = 0; i < din; ++i)
+      if (ho.held(i)) {
+        if (mean_u) mean_u[row * din + i] = (double)ho.u[i];
+        if (cov_u)
+          for (int j = 0; j < din; ++j) cov_u[(row * din + i) * din + j] = cov_u[(row * din + j) * din + i] = 0.0;
       }
   }
 }

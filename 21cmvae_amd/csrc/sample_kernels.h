@@ -25,6 +25,13 @@
 //   blocks 0 and 1, step = the transition: the proposal's normals;  block 2, same step: the acceptance uniform (w0);
 //   block 3, step = the transition a swap event follows: the swap's uniform (w0), drawn for the pair's lower row.
 // The prior draws nothing.
+// With a hold record (HOLD; include/v21.h: v21_mlp_set_hold; rowmath.h: HoldArgs) a held column i is no parameter: the
+// init kernel writes its float32 over the start's, at every point g_i = 0, F_ij = F_ji = 0, F_ii = 1 after the prior's
+// additions (hold_eval), the ridge goes to the FREE pivots only -- so a held pivot is exactly 1, its row and column of L
+// exactly 0, its log 0 and its drift component 0 --, its normal is 0 (drawn from the same Philox words and dropped: a
+// free column's draw does not depend on what is held), u'_i is the stored float32 bit for bit, and log q is normalised
+// over the d_free free columns: the transition is that of the d_free-dimensional sampler on the free block.  The launch
+// site hands over the prior record with the held normal columns made uniform.  The swap, TemperArgs and Moments are untouched.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -84,8 +91,13 @@ struct SampleArgs {
 };
 
 // Cholesky factor of G = F + ridge I (rowmath.h); false: a pivot is not positive and finite
-__device__ inline bool sample_chol(const double* F, double ridge, int din, double* Lm) {
-  return chol_factor(F, din, Lm, [&](int) { return ridge; }, [](double pivot) { return pivot > 0.0 && pivot < 1.79e308; });
+// HOLD: a held pivot gets no ridge
+template <bool HOLD = false, class H = NoHold>
+__device__ inline bool sample_chol(const double* F, double ridge, int din, double* Lm, const H& ho = {}) {
+  if constexpr (HOLD)
+    return chol_factor(F, din, Lm, [&](int i) { return ho.held(i) ? 0.0 : ridge; }, [](double pivot) { return pivot > 0.0 && pivot < 1.79e308; });
+  else
+    return chol_factor(F, din, Lm, [&](int) { return ridge; }, [](double pivot) { return pivot > 0.0 && pivot < 1.79e308; });
 }
 // mu = u + e^2 / 2 G^-1 g (two triangular solves) and sum_i log L_ii
 __device__ inline double sample_drift(const double* Lm, const double* u, const double* g, double eps, int din, double* mu) {
@@ -100,8 +112,9 @@ __device__ inline double sample_drift(const double* Lm, const double* u, const d
   }
   return ld;
 }
-// log q(b | a) from a's factor, drift and log-determinant term
-__device__ inline double sample_logq(const double* Lm, const double* mu, double ld, const double* b, double eps, int din) {
+// log q(b | a) from a's factor, drift and log-determinant term; dn: the dimension of its normalisation (din; d_free
+// with a hold record, whose held columns add exact zeros everywhere else)
+__device__ inline double sample_logq(const double* Lm, const double* mu, double ld, const double* b, double eps, int din, int dn) {
   constexpr int NI = kFitMaxIn;
   double q = 0.0;
 #pragma unroll
@@ -111,16 +124,22 @@ __device__ inline double sample_logq(const double* Lm, const double* mu, double 
     for (int k = i; k < NI; ++k) v += Lm[k * (k + 1) / 2 + i] * (b[k] - mu[k]);
     if (i < din) q += v * v;
   }
-  return -q / (2.0 * eps * eps) + ld - 0.5 * din * log(kSampleTwoPi * eps * eps);
+  return -q / (2.0 * eps * eps) + ld - 0.5 * dn * log(kSampleTwoPi * eps * eps);
 }
 
 // one thread per chain: u_prop (pitch din, the rows the next evaluation reads) into the box (box_clamp), the state reset;
-// the step size from eps_start (nullable: eps0)
-static __global__ void __launch_bounds__(256) sample_init_kernel(SampleRow* __restrict__ st, float* __restrict__ up, float* __restrict__ fac,
-                                                                 long long n, int din, double eps0, const double* __restrict__ eps_start) {
+// the step size from eps_start (nullable: eps0).  HOLD: the held coordinates over the start's; Hold: HoldArgs for HOLD =
+// true, no argument for HOLD = false
+template <bool HOLD, class... Hold>
+__global__ void __launch_bounds__(256) sample_init_kernel(SampleRow* __restrict__ st, float* __restrict__ up, float* __restrict__ fac,
+                                                          long long n, int din, double eps0, const double* __restrict__ eps_start,
+                                                          const Hold... hold) {
+  static_assert(sizeof...(Hold) == (HOLD ? 1 : 0), "HOLD takes one HoldArgs, its absence nothing");
+  [[maybe_unused]] const auto& ho = hold_of(hold...);
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   box_clamp(up + row * din, fac + row * din, din);
+  hold_row<HOLD>(ho, din, up + row * din);
   SampleRow& s = st[row];
   double e = eps_start ? eps_start[row] : eps0;
   s.eps = e > 0.0 && e < 1.79e308 ? e : eps0;
@@ -150,10 +169,10 @@ __device__ __forceinline__ void temper_eval(double beta, double* g, double* F) {
 // it == 0 is the start's, accepted whatever its value; it >= 1 is the proposal's of transition it - 1.  Adapts the
 // step size in warm-up and takes an accepted proposal as the current point.  -> accepted; have_factor: Lm, mu and ld
 // belong to the current point at the current step size
-template <bool TEMPER, bool PRIOR>
+template <bool TEMPER, bool PRIOR, bool HOLD, class H>
 __device__ __forceinline__ bool sample_decide(SampleRow& s, const float* upr, const float* lnl_new, const float* gn, const float* Fn,
                                               long long it, long long row, const SampleArgs& a, double beta, const PriorArgs& pr,
-                                              double& eps, double* Lm, double* mu, double& ld, bool& have_factor) {
+                                              const H& ho, double& eps, double* Lm, double* mu, double& ld, bool& have_factor) {
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const int din = a.din;
   double F[NP], g[NI], u[NI];
@@ -167,10 +186,11 @@ __device__ __forceinline__ bool sample_decide(SampleRow& s, const float* upr, co
       widen_eval(gn, Fn, din, g, F);
       temper_eval<TEMPER>(beta, g, F);
       prior_eval<PRIOR>(pr, up64, din, g, F);
+      hold_eval<HOLD>(ho, din, g, F);
       s.p.widen_u(din, u);
-      if (sample_chol(F, a.ridge, din, Lm)) {
+      if (sample_chol<HOLD>(F, a.ridge, din, Lm, ho)) {
         ld = sample_drift(Lm, up64, g, eps, din, mu);
-        const double lq_rev = sample_logq(Lm, mu, ld, u, eps, din);
+        const double lq_rev = sample_logq(Lm, mu, ld, u, eps, din, hold_free<HOLD>(ho, din));
         if constexpr (TEMPER)
           log_alpha = temper_mul(beta, (double)*lnl_new - (double)s.p.lnl) + lq_rev - s.lq_fwd;
         else
@@ -207,9 +227,9 @@ __device__ __forceinline__ void sample_keep(SampleRow& s, const double* u, bool 
 }
 
 // the proposal of transition `it` from the current point u, written to upr
-template <bool TEMPER, bool PRIOR>
+template <bool TEMPER, bool PRIOR, bool HOLD, class H>
 __device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const double* u, long long it, long long row, const SampleArgs& a,
-                                            double beta, const PriorArgs& pr, double eps, double* Lm, double* mu, double ld,
+                                            double beta, const PriorArgs& pr, const H& ho, double eps, double* Lm, double* mu, double ld,
                                             bool have_factor) {
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const int din = a.din;
@@ -218,7 +238,8 @@ __device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const doub
     s.p.widen(din, g, F);
     temper_eval<TEMPER>(beta, g, F);
     prior_eval<PRIOR>(pr, u, din, g, F);
-    if (!sample_chol(F, a.ridge, din, Lm)) {
+    hold_eval<HOLD>(ho, din, g, F);
+    if (!sample_chol<HOLD>(F, a.ridge, din, Lm, ho)) {
       // (only a start whose evaluation is not finite: the chain stays where it is)
       s.reject = 1;
       s.lq_fwd = 0.0;
@@ -248,13 +269,21 @@ __device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const doub
 #pragma unroll
   for (int i = 0; i < NI; ++i)
     if (i >= din) xi[i] = 0.0;  // (the rest of the last block's draws)
+  if constexpr (HOLD) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+      if (ho.held(i)) xi[i] = 0.0;  // (a held column's normal: drawn and dropped)
+  }
   // u' = mu + eps L^-T xi, rounded to the float32 that is evaluated
   double v[NI], ub[NI];
   bool inside = true;
   solve_upper(Lm, xi, v);
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    const float f = (float)(mu[i] + eps * v[i]);
+    float f = (float)(mu[i] + eps * v[i]);
+    // (a held mu_i is u_i and its v_i exactly 0, so f is the stored float32 already unless a free column's NaN reached it)
+    if constexpr (HOLD)
+      if (i < din && ho.held(i)) f = ho.u[i];
     ub[i] = i < din ? (double)f : 0.0;
     if (i < din && !(f >= -1.f && f <= 1.f)) inside = false;
   }
@@ -263,7 +292,7 @@ __device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const doub
   for (int i = 0; i < NI; ++i)
     if (i < din && !(fabs(ub[i]) < 3.0e38)) finite = false;
   s.reject = inside ? 0 : 1;
-  s.lq_fwd = inside ? sample_logq(Lm, mu, ld, ub, eps, din) : 0.0;
+  s.lq_fwd = inside ? sample_logq(Lm, mu, ld, ub, eps, din, hold_free<HOLD>(ho, din)) : 0.0;
 #pragma unroll
   for (int i = 0; i < NI; ++i)
     if (i < din) upr[i] = finite ? (float)ub[i] : s.p.u[i];
@@ -272,11 +301,14 @@ __device__ __forceinline__ void sample_draw(SampleRow& s, float* upr, const doub
 // one thread per chain, after evaluation number `it` of the call (lnl_new, g_new, F_new at u_prop, u coordinates):
 // the pending proposal is decided (sample_decide), a kept transition accumulated and stored (sample_keep) and, unless
 // it == a.total, the proposal of transition `it` drawn and written to u_prop (sample_draw).  T: the samples' type;
-// PRIOR: the handle holds a prior record, pr (else not read).
-template <class T, bool PRIOR>
+// PRIOR: the handle holds a prior record, pr (else not read).  HOLD: it holds a hold record; Hold: HoldArgs for HOLD =
+// true, no argument for HOLD = false.
+template <class T, bool PRIOR, bool HOLD, class... Hold>
 __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict__ st, float* __restrict__ up, const float* __restrict__ lnl_new,
                                                           const float* __restrict__ g_new, const float* __restrict__ F_new, long long it,
-                                                          const SampleArgs a, const PriorArgs pr) {
+                                                          const SampleArgs a, const PriorArgs pr, const Hold... hold) {
+  static_assert(sizeof...(Hold) == (HOLD ? 1 : 0), "HOLD takes one HoldArgs, its absence nothing");
+  [[maybe_unused]] const auto& ho = hold_of(hold...);
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= a.n) return;
@@ -288,13 +320,13 @@ __global__ void __launch_bounds__(256) sample_step_kernel(SampleRow* __restrict_
   bool have_factor = false;  // Lm, mu and ld below belong to the current point
   double ld = 0.0;
   const bool accept =
-      sample_decide<false, PRIOR>(s, upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, 1.0, pr, eps, Lm, mu, ld,
-                                  have_factor);
+      sample_decide<false, PRIOR, HOLD>(s, upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, 1.0, pr, ho, eps, Lm,
+                                        mu, ld, have_factor);
   // the current point
   s.p.widen_u(din, u);
   sample_keep<T>(s, u, accept, it, row, a);
   if (it == a.total) return;
-  sample_draw<false, PRIOR>(s, upr, u, it, row, a, 1.0, pr, eps, Lm, mu, ld, have_factor);
+  sample_draw<false, PRIOR, HOLD>(s, upr, u, it, row, a, 1.0, pr, ho, eps, Lm, mu, ld, have_factor);
 }
 
 // ---- parallel tempering (include/v21.h: v21_mlp_sample_tempered): T consecutive rows are the rungs of one ladder, row r
@@ -314,11 +346,13 @@ struct TemperRow {
   long long proposed, swapped;
 };
 
-template <class T, bool PRIOR>
+template <class T, bool PRIOR, bool HOLD, class... Hold>
 __global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st, TemperRow* __restrict__ tr, float* __restrict__ up,
                                                                    const float* __restrict__ lnl_new, const float* __restrict__ g_new,
                                                                    const float* __restrict__ F_new, long long it, const SampleArgs a,
-                                                                   const TemperArgs ta, const PriorArgs pr) {
+                                                                   const TemperArgs ta, const PriorArgs pr, const Hold... hold) {
+  static_assert(sizeof...(Hold) == (HOLD ? 1 : 0), "HOLD takes one HoldArgs, its absence nothing");
+  [[maybe_unused]] const auto& ho = hold_of(hold...);
   constexpr int NI = kFitMaxIn, NP = kFitPacked;
   const long long row = (long long)blockIdx.x * ta.rows_per_wg + threadIdx.x;
   // (no thread returns before the last barrier: one that is not `active` skips the work between them)
@@ -332,8 +366,8 @@ __global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st
   bool have_factor = false, accept = false;
   if (active) {
     eps = st[row].eps;
-    accept = sample_decide<true, PRIOR>(st[row], upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, beta, pr, eps,
-                                        Lm, mu, ld, have_factor);
+    accept = sample_decide<true, PRIOR, HOLD>(st[row], upr, lnl_new + row, g_new + row * din, F_new + row * din * din, it, row, a, beta, pr,
+                                              ho, eps, Lm, mu, ld, have_factor);
   }
   // the swap event that follows transition S = step0 + it - 1: the same branch for every thread of the launch
   const uint64_t s1 = a.step0 + (uint64_t)it;  // S + 1
@@ -378,7 +412,7 @@ __global__ void __launch_bounds__(256) sample_step_tempered_kernel(SampleRow* st
   }
   sample_keep<T>(s, u, accept, it, row, a);
   if (it == a.total) return;
-  sample_draw<true, PRIOR>(s, upr, u, it, row, a, beta, pr, eps, Lm, mu, ld, have_factor);
+  sample_draw<true, PRIOR, HOLD>(s, upr, u, it, row, a, beta, pr, ho, eps, Lm, mu, ld, have_factor);
 }
 
 // one thread per chain: the last state in raw units (raw_row) and the per-chain results (nullable; the moments'
@@ -390,9 +424,11 @@ struct SampleOutDev {
   float* last_prop_u;
   double* last_log_alpha;
 };
-template <class T>
+template <class T, bool HOLD, class... Hold>
 __global__ void __launch_bounds__(256) sample_finish_kernel(const SampleRow* __restrict__ st, const float* __restrict__ up, long long n, int din,
-                                                            long long kept, const v21_affine_in t, const SampleOutDev o) {
+                                                            long long kept, const v21_affine_in t, const SampleOutDev o, const Hold... hold) {
+  static_assert(sizeof...(Hold) == (HOLD ? 1 : 0), "HOLD takes one HoldArgs, its absence nothing");
+  [[maybe_unused]] const auto& ho = hold_of(hold...);
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   const SampleRow& s = st[row];
@@ -400,6 +436,7 @@ __global__ void __launch_bounds__(256) sample_finish_kernel(const SampleRow* __r
   if (o.lnl_last) o.lnl_last[row] = s.p.lnl;
   if (o.eps_last) o.eps_last[row] = s.eps;
   s.m.finish(row, din, kept, s.p.u, o.mean_u, o.cov_u, o.accept_rate);
+  hold_finish<HOLD>(ho, row, din, o.mean_u, o.cov_u);
   if (o.last_prop_u)
     for (int j = 0; j < din; ++j) o.last_prop_u[row * din + j] = up[row * din + j];
   if (o.last_log_alpha) o.last_log_alpha[row] = s.log_alpha;

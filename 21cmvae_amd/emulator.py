@@ -311,13 +311,22 @@ class LogPosterior:
     outside the box (or not finite), and such rows are never sent to the device.
     ``lp.prior_transform(cube)``: (7,) or (n, 7) points of the unit cube -> raw parameters, uniform in u
     (``preprocess.par_untransform``) -- the form nested samplers ask for.
+    With ``fixed`` (``{label: raw value}``, as ``fit_parameters`` takes it) those columns are no parameters: ``ndim`` is
+    the number of free columns d_free, theta and cube are (d_free,) or (n, d_free) -- the free columns in label order --,
+    the held columns take their values, and their prior is not read.
     The data / sigma record is uploaded when the object is made and again only if another call replaced it."""
 
-    def __init__(self, em, data, sigma, flow=None, fhigh=None, foreground=None, prior=None):
+    def __init__(self, em, data, sigma, flow=None, fhigh=None, foreground=None, prior=None, fixed=None):
         self.em = em
         self.prior = Prior.of(prior, em.par_train)
-        self.ndim = len(em.par_labels)
-        model, st, flags, _ = em._diff_stack(np.zeros((1, self.ndim)))
+        self.hold, self.held = em._fixed_columns(fixed)
+        if self.hold.all():
+            raise ValueError("fixed: every parameter is fixed (nothing to sample)")
+        if self.prior is not None and self.hold.any():
+            labels = list(em.par_labels)
+            self.prior = Prior({k: v for k, v in self.prior.spec.items() if not self.hold[labels.index(k)]}, em.par_train, self.prior.labels)
+        self.ndim = int(np.count_nonzero(~self.hold))
+        model, st, flags, _ = em._diff_stack(np.zeros((1, len(em.par_labels))))
         nb = st.dims[-1]
         self._d = np.ascontiguousarray(np.broadcast_to(np.asarray(data, np.float32), (nb,)))
         self._w = em._band_weights(nb, sigma, flow, fhigh)
@@ -327,9 +336,19 @@ class LogPosterior:
     def _record(self, st):
         self.em._use_record(st, self._d, self._w, self._fg, *self._band)
 
+    def _full(self, free):
+        """(n, ndim) rows of the free columns -> (n, din) with the held columns at their values (a copy)"""
+        f = np.array(free, np.float64, ndmin=2)
+        if not self.hold.any():
+            return f
+        x = np.empty((f.shape[0], self.hold.size))
+        x[:, ~self.hold] = f
+        x[:, self.hold] = self.held[self.hold]
+        return x
+
     def inside(self, theta):
         """(n,) bool: the rows of raw parameters inside the training box"""
-        x = np.array(theta, np.float64, ndmin=2)
+        x = self._full(theta)
         with np.errstate(invalid="ignore", divide="ignore"):
             u = pp.par_transform(x, self.em.par_train)
         return np.all(np.isfinite(u) & (np.abs(u) <= 1.0), axis=1)
@@ -339,6 +358,7 @@ class LogPosterior:
         if x.ndim != 2 or x.shape[1] != self.ndim:
             raise ValueError("expected parameters of shape (%d,) or (n, %d), got %r" % (self.ndim, self.ndim, np.shape(theta)))
         ok = self.inside(x)
+        x = self._full(x)
         out = np.full(x.shape[0], -np.inf, np.float64)
         if ok.any():
             model, st, flags, rows = self.em._diff_stack(x[ok])
@@ -350,8 +370,14 @@ class LogPosterior:
 
     def prior_transform(self, cube):
         c = np.array(cube, np.float64, ndmin=2)
+        if self.hold.any():
+            if c.ndim != 2 or c.shape[1] != self.ndim:
+                raise ValueError("expected a cube of shape (%d,) or (n, %d), got %r" % (self.ndim, self.ndim, np.shape(cube)))
+            full = np.full((c.shape[0], self.hold.size), 0.5)
+            full[:, ~self.hold] = c
+            c = full
         u = 2.0 * c - 1.0 if self.prior is None else self.prior.ppf_u(c, self.em.par_train)
-        x = pp.par_untransform(u, self.em.par_train)
+        x = pp.par_untransform(u, self.em.par_train)[:, ~self.hold]
         return x[0] if np.ndim(cube) == 1 else x
 
 
@@ -556,14 +582,15 @@ class _EmulatorBase:
         self._use_record(st, dat[0], self._band_weights(nb, sigma, flow, fhigh), foreground, flow, fhigh)
         return st.loglike_fwd(x, model.precision, flags, data=dat).reshape(M, R)
 
-    def log_posterior(self, data, sigma, flow=None, fhigh=None, foreground=None, prior=None):
+    def log_posterior(self, data, sigma, flow=None, fhigh=None, foreground=None, prior=None, fixed=None):
         """The log-posterior of the parameters given one observed signal, as an object to hand to an outside sampler
         (nested, ensemble, importance; not in the reference): a ``LogPosterior``.  ``lp(theta)``: float64 ln L of
         ``log_likelihood(forward_only=True)`` under the uniform prior on the training box in par_transform's coordinates,
         -inf outside the box; ``lp.prior_transform(cube)``: the unit cube -> raw parameters, uniform in those coordinates.
         ``prior``: as in ``sample_posterior``; ``lp(theta)`` then adds ``Prior.log_density_u`` and ``prior_transform``
-        draws from the prior."""
-        return LogPosterior(self, data, sigma, flow, fhigh, foreground, prior)
+        draws from the prior.  ``fixed``: ``{label: raw value}`` as in ``sample_posterior``; ``lp.ndim`` is then the number
+        of free columns, and theta / cube are those columns in label order."""
+        return LogPosterior(self, data, sigma, flow, fhigh, foreground, prior, fixed)
 
     def _use_prior(self, st, prior):
         """the samplers' prior record on the stack -- ``prior``: None (the record is cleared: a prior of another call
@@ -571,6 +598,29 @@ class _EmulatorBase:
         pr = Prior.of(prior, self.par_train)
         st.use_prior(None if pr is None else pr.to_u(self.par_train))
         return pr
+
+    def _hold_u(self, fixed):
+        """the samplers' ``fixed`` ({label: raw value}, None: nothing; ``_fixed_columns``' errors) -> (hold mask (din,) bool,
+        raw values (din,), u (din,) float64: par_transform of the values, 0 where free)"""
+        hold, val = self._fixed_columns(fixed)
+        if hold.all():
+            raise ValueError("fixed: every parameter is fixed (nothing to sample)")
+        row = pp.par_untransform(np.zeros((1, hold.size)), self.par_train)
+        row[0, hold] = val[hold]
+        u = np.where(hold, np.clip(pp.par_transform(row, self.par_train)[0], -1.0, 1.0), 0.0)
+        return hold, val, u
+
+    @staticmethod
+    def _held_results(hold, u, mean, cov, r_hat=None):
+        """a sampler's pooled moments (..., din) / (..., din, din) with the held columns as the device reports them per
+        row: the mean the float32 the column carries, its row and column of cov exact zeros; r_hat NaN there"""
+        if hold.any():
+            mean[..., hold] = u.astype(np.float32)[hold]
+            cov[..., hold, :] = 0.0
+            cov[..., :, hold] = 0.0
+            if r_hat is not None:
+                r_hat[..., hold] = np.nan
+        return mean, cov, r_hat
 
     def _use_record(self, st, d, w, foreground, flow, fhigh):
         """the likelihood record (d, w) and the nuisance basis of ``foreground`` (None: none) on the stack"""
@@ -635,15 +685,16 @@ class _EmulatorBase:
             raise ValueError("data must be (%d,) or (M, %d), got %r" % (nb, nb, np.shape(data)))
         return model, st, flags, dat, one
 
-    def _sampler_starts(self, st, dat, per, p0, sigma, flow, fhigh, seed, foreground, prior=None):
+    def _sampler_starts(self, st, dat, per, p0, sigma, flow, fhigh, seed, foreground, prior=None, fixed=None):
         """The samplers' raw start rows (M prod(per), din), ``per`` the shape of one spectrum's starts: ``p0`` ((din,) or
         (per[-1], din), the same for every spectrum) or the best ``fit_parameters`` start per spectrum -- under the call's
-        ``prior`` its MAP fit --, every row jittered (seeded, 0.02 in u, clipped into the box); then the call's likelihood
-        record is set on the stack"""
+        ``prior`` its MAP fit, with ``fixed`` that fit with those columns held --, every row jittered (seeded, 0.02 in u,
+        clipped into the box), the ``fixed`` columns then set to their values; then the call's likelihood record is set on
+        the stack"""
         din, shape = st.dims[0], (dat.shape[0],) + tuple(per) + (st.dims[0],)
         if p0 is None:
-            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground, prior=prior).params,
-                              np.float64, ndmin=2)
+            centre = np.array(self.fit_parameters(dat, sigma, flow=flow, fhigh=fhigh, seed=seed, foreground=foreground, prior=prior,
+                                                  fixed=fixed).params, np.float64, ndmin=2)
             u0 = np.repeat(pp.par_transform(centre, self.par_train)[:, None, :], int(np.prod(per)), axis=1).reshape(shape)
         else:
             starts = np.array(p0, np.float64, ndmin=2)
@@ -653,13 +704,17 @@ class _EmulatorBase:
         rng = np.random.default_rng(seed)
         u0 = np.clip(np.clip(u0, -1.0, 1.0) + 0.02 * rng.normal(size=shape), -1.0, 1.0)
         x0 = pp.par_untransform(u0.reshape(-1, din), self.par_train)
+        if fixed is not None:
+            hold, val = self._fixed_columns(fixed)
+            x0[:, hold] = val[hold]
         self._use_record(st, dat[0], self._band_weights(st.dims[-1], sigma, flow, fhigh), foreground, flow, fhigh)
         return x0
 
     @staticmethod
-    def _posterior_samples(r, view, n_kept, return_lnl, one):
+    def _posterior_samples(r, view, n_kept, return_lnl, one, held=None):
         """``PosteriorSamples`` from a sampler's result arrays r; view: a per-row array (n, ...) -> (M, chains, ...), or
-        (M, ensembles, walkers, ...) whose walkers are pooled before the ensembles are compared; n_kept: kept transitions"""
+        (M, ensembles, walkers, ...) whose walkers are pooled before the ensembles are compared; n_kept: kept transitions;
+        held: (hold mask, u) of a call with ``fixed`` (``_held_results``)"""
         K = r["samples"].shape[1] if "samples" in r else 0
         params = view(r["samples"]) if K else None
         lnl = view(r["samples_lnl"]) if K and return_lnl else None
@@ -669,7 +724,10 @@ class _EmulatorBase:
             n_kept *= mean_c.shape[2]
             mean_c, cov_c = pooled_moments(mean_c, cov_c)
         rh = r_hat_from_moments(mean_c, cov_c, n_kept)
-        out = (params, lnl, acc, step, rh) + pooled_moments(mean_c, cov_c)
+        mean_p, cov_p = pooled_moments(mean_c, cov_c)
+        if held is not None:
+            mean_p, cov_p, rh = _EmulatorBase._held_results(held[0], held[1], np.array(mean_p), np.array(cov_p), np.array(rh))
+        out = (params, lnl, acc, step, rh, mean_p, cov_p)
         return PosteriorSamples(*[a[0] if one and a is not None else a for a in out])
 
     def _fixed_columns(self, fixed):
@@ -776,7 +834,7 @@ class _EmulatorBase:
         return FitResult(xh, lnl, status, F, *extra)
 
     def sample_posterior(self, data, sigma, n_chains=64, n_steps=1000, n_warmup=200, thin=1, p0=None, flow=None, fhigh=None, seed=0,
-                         eps=None, return_lnl=False, foreground=None, prior=None):
+                         eps=None, return_lnl=False, foreground=None, prior=None, fixed=None):
         """Posterior samples of the parameters given observed signal(s) (not in the reference): ``n_chains`` independent
         Markov chains per spectrum, run entirely on the device -- a Metropolis-adjusted Langevin sampler preconditioned
         with the Fisher matrix at the current point (include/v21.h: v21_mlp_sample) -- of the Gaussian ln L of
@@ -787,6 +845,14 @@ class _EmulatorBase:
         ``("normal", mean, sd)`` in raw units on a linear column, ``("lognormal", mean_log10, sd_dex)`` on a log10 column;
         the others stay uniform.  The sampler then targets L times that prior on the device (include/v21.h:
         v21_mlp_set_prior); every returned ``lnl`` stays ln L.  The default starts are then MAP fits (``fit_parameters(prior=...)``).
+        ``fixed`` (here and in ``sample_ensemble``, ``sample_tempered``, ``nested_sample``, ``log_posterior``): None, or
+        ``{label: raw value}`` as ``fit_parameters`` takes it (ValueError naming the column: an unknown label, a value
+        outside the training box; every column fixed).  Those columns are no parameters of the call: the sampler runs on
+        the device over the d_free others with the fixed ones held at their values (include/v21.h: v21_mlp_set_hold), their
+        prior is not read, the default starts are ``fit_parameters(..., prior=prior, fixed=fixed)`` and the fixed columns
+        of ``p0`` are overwritten.  In the results a fixed column of ``params`` is the value to float32 rounding in u in
+        every sample, ``mean_u`` is that float32, its row and column of ``cov_u`` are zeros and its ``r_hat`` is NaN (a
+        constant has none): take ``np.nanmax(r_hat)`` for a convergence check.
         ``data``: (451,) or (M, 451) mK.  Starts: ``p0`` ((7,) or (n_chains, 7) raw parameters, the same for every
         spectrum), or by default the best ``fit_parameters`` start per spectrum; either way every chain is jittered
         (seeded, 0.02 in u, clipped into the box).  Each chain runs ``n_warmup`` transitions adapting its step size
@@ -797,6 +863,7 @@ class _EmulatorBase:
         potential scale reduction in u -- and the pooled mean_u (M, 7) / cov_u (M, 7, 7), all three from the per-chain
         moments the device accumulates in float64; the M axis is dropped for one spectrum.  Bounds: a log column's lower
         bound comes back as 10^lo (the fx zero floor 1e-6, not 0)."""
+        held = None if fixed is None else self._hold_u(fixed)  # (argument errors before any device work)
         model, st, flags, dat, one = self._spectra(data)
         prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         M, C = dat.shape[0], int(n_chains)
@@ -804,13 +871,21 @@ class _EmulatorBase:
             raise ValueError("n_chains must be >= 1")
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
-        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground, prior))
+        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground, prior, fixed))
         self._use_prior(st, prior)
-        r = st.sample(x0, model.precision, flags, data=dat, **opts)
-        return self._posterior_samples(r, lambda a: a.reshape((M, C) + a.shape[1:]), int(n_steps), return_lnl, one)
+        if held is None:
+            r = st.sample(x0, model.precision, flags, data=dat, **opts)
+        else:
+            try:
+                st.use_hold((held[0], held[2]))
+                r = st.sample(x0, model.precision, flags, data=dat, **opts)
+            finally:
+                st.use_hold(None)  # (never leaks into the next call)
+        return self._posterior_samples(r, lambda a: a.reshape((M, C) + a.shape[1:]), int(n_steps), return_lnl, one,
+                                       held and (held[0], held[2]))
 
     def sample_ensemble(self, data, sigma, n_walkers=64, n_ensembles=4, n_steps=1000, n_warmup=500, thin=1, a=2.0, p0=None, flow=None,
-                        fhigh=None, seed=0, return_lnl=False, foreground=None, prior=None):
+                        fhigh=None, seed=0, return_lnl=False, foreground=None, prior=None, fixed=None):
         """Posterior samples from the affine-invariant ensemble sampler (not in the reference): ``n_ensembles`` independent
         ensembles of ``n_walkers`` walkers per spectrum, moved by Goodman & Weare's stretch move with scale ``a`` entirely
         on the device (include/v21.h: v21_mlp_sample_ensemble), on the forward-only ln L of ``log_likelihood`` under
@@ -824,7 +899,9 @@ class _EmulatorBase:
         last axis; None unless ``return_lnl``), accept_rate (M, n_ensembles, n_walkers), step_size None (the move has none),
         r_hat (M, 7) taken BETWEEN ENSEMBLES -- the walkers of one ensemble are not independent chains, so each ensemble's
         walkers are pooled (``pooled_moments``) and the ensembles compared (``r_hat_from_moments``; NaN for one ensemble) --
-        and the pooled mean_u (M, 7) / cov_u (M, 7, 7); the M axis is dropped for one spectrum."""
+        and the pooled mean_u (M, 7) / cov_u (M, 7, 7); the M axis is dropped for one spectrum.
+        ``fixed``: as in ``sample_posterior``.  The walker rule stays on the 7 columns."""
+        held = None if fixed is None else self._hold_u(fixed)  # (argument errors before any device work)
         model, st, flags, dat, one = self._spectra(data)
         prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         din = st.dims[0]
@@ -833,13 +910,21 @@ class _EmulatorBase:
             raise ValueError("n_ensembles must be >= 1")
         opts = dict(a=a, n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed)
         nat.Stack.ensemble_opts(W, in_dim=din, **opts)  # (argument errors before any device work)
-        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (E, W), p0, sigma, flow, fhigh, seed, foreground, prior))
+        x0 = np.ascontiguousarray(self._sampler_starts(st, dat, (E, W), p0, sigma, flow, fhigh, seed, foreground, prior, fixed))
         self._use_prior(st, prior)
-        r = st.sample_ensemble(x0, W, model.precision, flags, data=dat, **opts)
-        return self._posterior_samples(r, lambda a: a.reshape((M, E, W) + a.shape[1:]), int(n_steps), return_lnl, one)
+        if held is None:
+            r = st.sample_ensemble(x0, W, model.precision, flags, data=dat, **opts)
+        else:
+            try:
+                st.use_hold((held[0], held[2]))
+                r = st.sample_ensemble(x0, W, model.precision, flags, data=dat, **opts)
+            finally:
+                st.use_hold(None)  # (never leaks into the next call)
+        return self._posterior_samples(r, lambda a: a.reshape((M, E, W) + a.shape[1:]), int(n_steps), return_lnl, one,
+                                       held and (held[0], held[2]))
 
     def sample_tempered(self, data, sigma, n_ladders=16, n_temps=8, betas=None, swap_every=5, n_steps=1000, n_warmup=200, thin=1,
-                        p0=None, flow=None, fhigh=None, seed=0, eps=None, return_lnl=False, foreground=None, prior=None):
+                        p0=None, flow=None, fhigh=None, seed=0, eps=None, return_lnl=False, foreground=None, prior=None, fixed=None):
         """Parallel-tempered posterior samples and the Bayesian evidence (not in the reference): ``n_ladders`` ladders per
         spectrum, each of ``n_temps`` chains of ``sample_posterior``'s sampler at the inverse temperatures ``betas``
         (default ``default_betas(n_temps)``, from 1 down to 0), run entirely on the device (include/v21.h:
@@ -862,7 +947,12 @@ class _EmulatorBase:
         foreground modes: their flat prior is improper.  nan with ``n_temps = 1``.
         With ``prior`` a chain at beta samples L^beta times the prior, the beta = 0 rung the prior itself, mean_lnl stays the
         mean of ln L alone, and log_evidence is ln of the mean of L under the STATED, normalised prior.  It is comparable
-        across priors only as a Bayes factor between models, not as a goodness of fit."""
+        across priors only as a Bayes factor between models, not as a goodness of fit.
+        ``fixed``: as in ``sample_posterior``.  log_evidence is then the CONDITIONAL evidence of the nested model: ln of the
+        mean of L, at the fixed values, under the normalised prior on the FREE columns -- the definition
+        ``FitResult.log_evidence`` uses with ``fixed``.  Its difference to the evidence of the call without ``fixed`` is
+        not yet the Bayes factor "is this parameter needed?": that also takes the prior density of the fixed value."""
+        held = None if fixed is None else self._hold_u(fixed)  # (argument errors before any device work)
         model, st, flags, dat, one = self._spectra(data)
         prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         M, C, T = dat.shape[0], int(n_ladders), int(n_temps)
@@ -872,12 +962,20 @@ class _EmulatorBase:
         opts = dict(n_steps=n_steps, n_warmup=n_warmup, thin=thin, seed=seed, eps0=eps)
         nat.Stack.sample_opts(**opts)  # (argument errors before any device work)
         nat.Stack.temper_opts(T, b, swap_every)
-        x0 = self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground, prior)
+        x0 = self._sampler_starts(st, dat, (C,), p0, sigma, flow, fhigh, seed, foreground, prior, fixed)
         x0 = np.ascontiguousarray(np.repeat(x0, T, axis=0))  # (every rung of a ladder from its ladder's start)
         self._use_prior(st, prior)
-        r = st.sample_tempered(x0, T, b, swap_every, model.precision, flags, data=dat, **opts)
+        if held is None:
+            r = st.sample_tempered(x0, T, b, swap_every, model.precision, flags, data=dat, **opts)
+        else:
+            try:
+                st.use_hold((held[0], held[2]))
+                r = st.sample_tempered(x0, T, b, swap_every, model.precision, flags, data=dat, **opts)
+            finally:
+                st.use_hold(None)  # (never leaks into the next call)
         # (the beta = 1 rows)
-        ps = self._posterior_samples(r, lambda a: a.reshape((M, C, T) + a.shape[1:])[:, :, 0], int(n_steps), return_lnl, one)
+        ps = self._posterior_samples(r, lambda a: a.reshape((M, C, T) + a.shape[1:])[:, :, 0], int(n_steps), return_lnl, one,
+                                     held and (held[0], held[2]))
         E = r["mean_lnl"].reshape(M, C, T)
         with np.errstate(invalid="ignore", divide="ignore"):
             # (pooled over ladders: every ladder proposes a pair equally often, so the mean of the ratios is the ratio)
@@ -890,7 +988,7 @@ class _EmulatorBase:
         return TemperedSamples(*ps, b, E, swap, lz, lz_err)
 
     def nested_sample(self, data, sigma, n_live=256, n_runs=1, n_repeats=None, dlogz=0.01, max_iter=2000, flow=None, fhigh=None,
-                      foreground=None, seed=0, return_lnl=True, prior=None):
+                      foreground=None, seed=0, return_lnl=True, prior=None, fixed=None):
         """Nested sampling of the posterior given observed signal(s) (not in the reference): the Bayesian evidence with its
         error and weighted posterior samples in one run, without a gradient, entirely on the device (include/v21.h:
         v21_mlp_sample_nested) on the forward-only ln L of ``log_likelihood`` under ``sample_posterior``'s prior -- uniform
@@ -920,7 +1018,12 @@ class _EmulatorBase:
         improper.
         With ``prior`` the live points are drawn from it, a move is a Metropolis move on the prior inside the deleted
         points' highest ln L, ``lnl`` stays ln L, and log_evidence is ln of the mean of L under the STATED, normalised
-        prior.  It is comparable across priors only as a Bayes factor between models, not as a goodness of fit."""
+        prior.  It is comparable across priors only as a Bayes factor between models, not as a goodness of fit.
+        ``fixed``: as in ``sample_posterior``; every live and dead point carries the fixed columns' values.  The default
+        ``n_repeats`` is then 3 x d_free (the ``n_live`` rule stays on the 7 columns), and log_evidence is the CONDITIONAL
+        evidence of the nested model: ln of the mean of L, at the fixed values, under the normalised prior on the FREE
+        columns -- the definition ``FitResult.log_evidence`` uses with ``fixed``, and ``sample_tempered``'s."""
+        held = None if fixed is None else self._hold_u(fixed)  # (argument errors before any device work)
         model, st, flags, dat, one = self._spectra(data)
         prior = Prior.of(prior, self.par_train)  # (argument errors before any device work)
         din = st.dims[0]
@@ -931,12 +1034,25 @@ class _EmulatorBase:
             raise ValueError("n_live = %d: an evidence needs at least %d live points for %d parameters" % (N, 8 * din, din))
         if int(max_iter) < 1 or not float(dlogz) > 0.0:
             raise ValueError("max_iter must be >= 1 and dlogz positive")
-        n, k, block = M * R * N, N // 2, 16
+        if held is not None and not n_repeats:
+            n_repeats = 3 * int(np.count_nonzero(~held[0]))
         opts = dict(n_repeats=n_repeats, seed=seed)
         nat.Stack.nested_opts(N, n_iter=int(max_iter), in_dim=din, **opts)  # (argument errors before any device work)
         rep = int(n_repeats) if n_repeats else 3 * din
         self._use_record(st, dat[0], self._band_weights(st.dims[-1], sigma, flow, fhigh), foreground, flow, fhigh)
         self._use_prior(st, prior)
+        if held is not None:
+            st.use_hold((held[0], held[2]))
+        try:
+            return self._nested_blocks(model, st, flags, dat, one, M, R, N, int(max_iter), float(dlogz), opts, rep, return_lnl, held)
+        finally:
+            if held is not None:
+                st.use_hold(None)  # (never leaks into the next call)
+
+    def _nested_blocks(self, model, st, flags, dat, one, M, R, N, max_iter, dlogz, opts, rep, return_lnl, held):
+        """``nested_sample``'s loop over blocks of iterations and its result, the records set on the stack"""
+        din = st.dims[0]
+        n, k, block = M * R * N, N // 2, 16
         s_k = np.sum(1.0 / (N - np.arange(k)))
         u, T, dead_u, dead_l, acc, stopped = None, 0, [], [], 0.0, "max_iter"
         while T < int(max_iter):
@@ -962,6 +1078,8 @@ class _EmulatorBase:
         mean = np.einsum("mp,mpi->mi", w, flat)
         cen = flat - mean[:, None, :]
         cov = np.einsum("mp,mpi,mpj->mij", w, cen, cen)
+        if held is not None:
+            self._held_results(held[0], held[2], mean, cov)
         params = pp.par_untransform(pts.reshape(-1, din), self.par_train).reshape(pts.shape)
         lz_err = lz.std(axis=1, ddof=1) / np.sqrt(R) if R > 1 else err[:, 0]
         out = [params, lnl if return_lnl else None, lw, lz.mean(axis=1), lz_err, H.mean(axis=1), T, R * (N + k * T * rep),

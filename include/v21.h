@@ -577,6 +577,31 @@ int v21_mlp_nuisance_coef(v21_mlp* mlp, const void* x, int x_dtype, int64_t n, d
  *     host bookkeeping: no GPU work. */
 int v21_mlp_set_prior(v21_mlp* mlp, const int32_t* kind, const double* mu, const double* sd, int32_t in_dim);
 
+/* ---- the samplers' held parameters.  A hold record takes input columns out of the four samplers (the entries listed
+ * above): a held column i is no parameter of the call but the constant u_i = float32(u[i]) -- rounded ONCE, here, and that
+ * float32 is what every state, proposal, stored sample, x_last, dead_u and live_u carries in the column, bit for bit.
+ * Its prior is never read (a normal column of the prior record that is held counts as uniform); d_free = the columns
+ * left.  No sampler entry changes its signature; with a record
+ *   v21_mlp_sample[_tempered]  the start's held coordinates are overwritten; at every point, after the prior's additions,
+ *                             g_i = 0, F_ij = F_ji = 0 (j != i), F_ii = 1 (v21_mlp_fit_map's arithmetic), the ridge is
+ *                             added to the free pivots only, the held normal is 0 (the free columns draw from the words
+ *                             they always drew from), and log q is normalised with d_free: the transition is that of
+ *                             the d_free-dimensional sampler on the free block of F + P + ridge I;
+ *   v21_mlp_sample_ensemble    the starts' held coordinates are overwritten; log alpha takes (d_free - 1) ln z.  The
+ *                             stretch returns a held coordinate exactly: x + z (x - x) = x in float arithmetic;
+ *   v21_mlp_sample_nested      given and drawn starts get the held coordinates (a held column consumes no draw; the free
+ *                             columns keep their words); the difference move returns them exactly.  The shrinkage and
+ *                             v21_nested_evidence are untouched: the evidence is the mean of L under the normalised prior
+ *                             of the free columns, at the held values;
+ *   results                   mean_u of a held column is u_i, its row and column of cov_u are exact zeros.
+ * (n_walkers and n_live keep their rules on in_dim, n_repeats = 0 stays 3 in_dim.)  v21_mlp_fit, v21_mlp_fit_map (which
+ * keeps the hold mask of its own options), v21_mlp_fisher, v21_mlp_loglike and v21_mlp_loglike_fwd do not read the record.
+ *   v21_mlp_set_hold  hold, u: in_dim entries each (copied); hold[i] in {0, 1}, u[i] read only where hold[i] is 1.
+ *     hold = NULL, in_dim = 0 or an all-zero mask clears the record: the samplers then launch what they launched before.
+ *     V21_ERR_ARG, the handle keeping what it had: in_dim is not the stack's (or above 8); a mask entry outside {0, 1};
+ *     a held u NULL, not finite or outside [-1, 1]; every column held (nothing to sample).  Pure host bookkeeping. */
+int v21_mlp_set_hold(v21_mlp* mlp, const int32_t* hold, const double* u, int32_t in_dim);
+
 /* ---- trainer: replaces Model.compile + Model.fit (emulator.py:369-378, :739-747,
  * :756-764; optimizer/loss from notebooks/Training.ipynb cells 4 and 10). ------- */
 typedef struct {
